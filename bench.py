@@ -14,9 +14,11 @@ scaling) and, per submit, on a stream of its own behind d2fe_pipe_device_view (d
 {desc, kps, scores, netvlad, n}, ships them with ONE RCCL all-gather, evaluates the reference's NetVLAD gate for every (local frame, remote frame) pair on the
 device, matches its frames against every other rank's frame of the same time index and delivers those match lists to host memory too.
 
-Prints ONE JSON line on rank 0 with `roofline` (the dominant kernel: conv1b, HIP events on the launch stream, one submit in flight), `step_roofline` (the whole
-step against the matrix pipe), `roofline_netvlad` and `cpu_baseline` (torch/oneDNN network + the C oracle's post-processing and matcher on the host cores,
-bounded sample).
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps of `value` and prints ONE JSON line on rank 0: the contract keys,
+`step_roofline` (the whole step against the matrix pipe) and `roofline` / `roofline_netvlad` from HIP events inside the timed region.  `--dump-outputs DIR` also writes
+what the last timed step delivered to its caller as DIR/<name>.npy.  `--full` adds every secondary leg: `roofline` of the dominant kernel (conv1b) with one submit in
+flight, `cpu_baseline` (torch/oneDNN network + the C oracle's post-processing and matcher on the host cores, bounded sample), the other precisions and configurations,
+the batch curve, single-call latencies, quadcam, the NetVLAD width legs, the in-run parity checks and the live PMC traffic passes.
 """
 import argparse
 import json
@@ -46,6 +48,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=32, help="stereo frames per step and per GPU (32: 64 images per launch)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (solo roofline, cpu_baseline, in-run parity checks, the other precisions and configurations, "
+                                                        "batch curve, latency, quadcam, NetVLAD widths, one-GPU RCCL exchange, live PMC traffic); without it a run times `value` only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step delivered to its caller (keypoints, scores, descriptors, counts, NetVLAD vectors, match lists) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--precision", choices=["f32", "f16x2", "wino"], default=os.environ.get("D2FE_BENCH_PRECISION", "wino"),
                     help="wino: fp32, 3x3 layers as Winograd F(2x2,3x3) on the fp32 MFMA pipe (headline); f32: direct convolutions, "
                          "bitwise equal to the oracle's fmaf chains; f16x2: fp16 hi/lo split operands")
@@ -95,6 +102,8 @@ def main():
     for k in REFUSED_ENV:
         if os.environ.get(k):
             raise SystemExit("%s is set: that switch changes what the kernels compute; bench.py refuses to time it" % k)
+    if args.dump_outputs and args.workload != "d435":
+        raise SystemExit("--dump-outputs writes the results of the d435 pipe step; --workload %s has no dump" % args.workload)
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         # a bare `python bench.py --gpus N`: re-launch this command line as N ranks (one process per GPU) under torch.distributed.run;
@@ -325,13 +334,15 @@ def main():
     lanes = args.lanes or (LANES_FOR.get(args.frames, 2) if not dist_path else LANES_WITH_EXCHANGE.get(args.frames, LANES_FOR.get(args.frames, 2)))
     xmode = args.exchange if dist_path else None
     pk = dict(world=world, dist=dist, exchange=xmode, loopback=loopback, exchange_impl=args.exchange_impl, exchange_own_stream=not args.exchange_lane_streams)
-    full_run = world == 1 and not dist_path and not args.single_mode          # the default `python bench.py`: every secondary leg
-    primary = run_pipe(torch, api, weights, nv_weights, args.precision, args.frames, lanes, args.steps, args.warmup, local_rank, rank, netvlad=use_nv, **pk)
+    full_run = args.full and world == 1 and not dist_path and not args.single_mode          # `python bench.py --full`: every secondary leg
+    primary = run_pipe(torch, api, weights, nv_weights, args.precision, args.frames, lanes, args.steps, args.warmup, local_rank, rank, netvlad=use_nv,
+                       keep_last=bool(args.dump_outputs), **pk)
+    dumped = dump_outputs(args.dump_outputs, primary["last"]) if (rank == 0 and args.dump_outputs) else None
     if rank == 0 and not (primary.get("stream_placement") or {}).get("classes_told_apart"):
         # a pipe whose stream placement could not be MEASURED (device not quiet when it was created: two ranks on one GPU, another handle at work) used creation
         # order, which may put both of a lane's streams on one hardware pipe -- say so next to the number (`config.stream_placement.classes_told_apart` = 0 in the line)
         print("bench.py: WARNING: the timed pipe's stream placement was not measured (classes_told_apart = 0): streams in creation order", file=sys.stderr, flush=True)
-    if world == 1 and not dist_path and lanes > 1 and not args.no_solo:
+    if args.full and world == 1 and not dist_path and lanes > 1 and not args.no_solo:
         # the step with ONE submit in flight: every kernel has the device to itself -- the dominant kernel's own roofline measurement (also the batch curve's F x 1 point)
         solo = run_pipe(torch, api, weights, nv_weights, args.precision, args.frames, 1, max(5, args.steps // 2) if args.single_mode else max(12, min(400, int(700 / args.frames))), 4,
                         local_rank, rank, netvlad=use_nv)
@@ -394,13 +405,13 @@ def main():
                                         "note": "dynamic batching: up to 4 consecutive submits per pass, launched early whenever fewer than 2 passes are in flight"})
     # cpu_baseline (SURVEY.md section 8d protocol: warm-up 5, >= 50 timed iterations, median + p95; one thread and all cores): two child processes started HERE, after the
     # headline, solo, latency and batch-curve legs, so that their 1-2 minutes pass beside the secondary GPU legs below (a few host threads on a 256-core box) instead of adding to the run
-    cpu_children = start_cpu_baseline(args, use_nv) if (rank == 0 and world == 1 and not dist_path and not args.no_cpu_baseline) else None
+    cpu_children = start_cpu_baseline(args, use_nv) if (args.full and rank == 0 and world == 1 and not dist_path and not args.no_cpu_baseline) else None
     legs, legs_solo = {}, {}
     short = max(5, args.steps // 2)
-    if dist_path:
+    if args.full and dist_path:
         # the same ranks, the same step, WITHOUT the exchange: what the exchange costs the step (its kernels share the device with the lanes' launches)
         noexch = run_pipe(torch, api, weights, nv_weights, args.precision, args.frames, lanes, short, 2, local_rank, rank, netvlad=use_nv, light=True, world=world, dist=dist)
-    if not args.single_mode:
+    if args.full and not args.single_mode:
         legs["configs1"] = run_pipe(torch, api, weights, nv_weights, args.precision, args.frames, lanes, short, 2, local_rank, rank, netvlad=False, **pk)
         for om in ("f32", "f16x2", "wino"):
             if om != args.precision:
@@ -462,7 +473,7 @@ def main():
 
     cpu_baseline = None
     parity = None
-    if rank == 0 and world == 1 and not dist_path and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not dist_path and not args.no_cpu_baseline:
         cpu_baseline = join_cpu_baseline(cpu_children, weights)
         parity = run_parity_check(primary, weights, nv_weights if use_nv else None, args.precision)
 
@@ -524,6 +535,8 @@ def main():
                                    "%d x 1, %.1f stereo fps): the launch has the device to itself" % (solo["steps"], solo["F"], solo["value"]),
                                    in_timed_region_of_value={"avg_launch_ms": shared["avg_launch_ms"], "launches": shared["launches"], "frac_executed": shared["frac_executed"],
                                                              "note": "with %d submits in flight the launch overlaps the other lanes' NetVLAD / post-processing / copy work" % primary["lanes"]})
+        elif not args.full and out["roofline"] and primary.get("lanes", 1) > 1:
+            out["roofline"]["measured"] = "HIP events in the timed region of `value`, %d submits in flight (one in flight: --full)" % primary["lanes"]
         if full_run and not args.no_live_traffic and args.precision == "wino" and args.frames == 32 and out["roofline"].get("kernel", "").startswith("conv_wino"):
             live = live_traffic("conv_wino_kernel<64, true, true, 0, 1, true")
             if live:
@@ -573,9 +586,11 @@ def main():
             out["f16x2_vs_exact_on_bench_frames"] = disagreement_fast
         if parity_in_run:
             out["index_parity_in_run"] = parity_in_run
-        ev = index_parity_evidence()
+        ev = index_parity_evidence() if args.full else None
         if ev:
             out["index_parity_evidence"] = ev
+        if dumped:
+            out["outputs_dumped"] = dumped
         if width_sens:
             out["netvlad_width_sensitivity"] = width_sens
         if exch_1gpu:
@@ -610,6 +625,40 @@ def main():
                                      note="two distance strips per pair (one per direction): 2 x 2 x na x nb x 256 FLOP on v_mfma_f32_16x16x4_f32"),
             }
     finish(out)
+
+
+DUMP_BUDGET = 64 << 20          # bytes, all arrays of --dump-outputs together
+# per-keypoint / per-match arrays and the count that says how many of their rows the caller reads
+_DUMP_ROWS = {"kps_xy": "n_kp", "scores": "n_kp", "desc": "n_kp", "lr_q": "lr_n", "lr_t": "lr_n", "lr_dist": "lr_n", "prev_q": "prev_n", "prev_t": "prev_n", "prev_dist": "prev_n"}
+
+
+def dump_outputs(d, res, budget=DUMP_BUDGET):
+    """--dump-outputs: `res` (StereoPipe.wait of the last timed submit, copied) as d/<name>.npy.  Float arrays as float32, counts and indices as float64 (exact).
+    Entries past an image's or pair's count are zeroed: the caller reads the first n, the rest of the pinned block holds whatever an earlier pass left there.
+    Above `budget` bytes in all, every array larger than 1 MiB is replaced by the same seeded sample of its flattened elements (a fixed fraction, sorted indices)."""
+    arrs = {}
+    for k, v in res.items():
+        if v is None:
+            continue
+        a = np.array(v, dtype=np.float32 if v.dtype.kind == "f" else np.float64)
+        if k in _DUMP_ROWS:
+            n = np.minimum(np.asarray(res[_DUMP_ROWS[k]]).astype(np.int64), a.shape[1])
+            a[np.arange(a.shape[1])[None, :] >= n[:, None]] = 0
+        arrs[k] = a
+    small = sum(a.nbytes for a in arrs.values() if a.nbytes <= 1 << 20)
+    large = sum(a.nbytes for a in arrs.values() if a.nbytes > 1 << 20)
+    sampled = {}
+    if small + large > budget:
+        frac = (budget - small) / float(large)
+        for k, a in arrs.items():
+            if a.nbytes > 1 << 20:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+                arrs[k] = a.reshape(-1)[idx]
+                sampled[k] = "%d of %d elements (flattened, seed 0)" % (idx.size, a.size)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return {"dir": os.path.abspath(d), "arrays": sorted(arrs), "bytes": int(sum(a.nbytes for a in arrs.values())), "sampled": sampled or None}
 
 
 # ---- cpu_baseline (kind "port") and the in-run parity check: the ONLY places of the benchmark that touch oracle/ (the checker and the reported baseline, never the

@@ -66,13 +66,15 @@ def stream_classes(r):
 
 
 def run_pipe(torch, api, weights, nv_weights, precision, F, lanes, steps, warmup, local_rank, rank, netvlad=True, light=False, coalesce=1, depth=0, inflight=0,
-             world=1, dist=None, exchange=None, nv_flop_per_img=NV_FLOP_PER_IMG, nv_group=1, loopback=False, exchange_impl="capi", exchange_own_stream=True):
+             world=1, dist=None, exchange=None, nv_flop_per_img=NV_FLOP_PER_IMG, nv_group=1, loopback=False, exchange_impl="capi", exchange_own_stream=True,
+             keep_last=False):
     """`steps` submits of F stereo frames through the frames-in-flight pipe with `lanes` submits in flight: the timed region holds, per submit, the H2D of
     the 2F frames from pinned memory, SuperPoint on them, NetVLAD of the F left images, ONE matcher launch (L<->R, L<->previous L) and the D2H of every
     result into pinned memory.  EVERY --gpus N runs this function (N = 1: no process group, no barrier).  N > 1 with `exchange`: one cross-agent exchange
     (d2slam_amd.swarm.PipeExchange: pack -> ONE all-gather -> gate -> remote matches -> D2H) per submit on a stream of its own, enqueued one submit behind the
     pipe and collected with the ticket -- inside the timed region, beside the lanes' work.  Timing: barrier + device synchronisation on both sides (N > 1),
-    perf_counter around exactly `steps` submits + the waits for all of them; the caller takes the MAX over ranks."""
+    perf_counter around exactly `steps` submits + the waits for all of them; the caller takes the MAX over ranks.  keep_last: `last` = a copy of what the
+    caller of the last timed submit received (StereoPipe.wait), taken after the timed region."""
     from d2slam_amd import swarm
     prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}[precision]
     fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=CAP, input_width=W, input_height=H, max_batch=1, precision=prec, device_id=local_rank))
@@ -154,6 +156,8 @@ def run_pipe(torch, api, weights, nv_weights, precision, F, lanes, steps, warmup
     tk, th = drive(steps, 0)
     barrier()
     elapsed = time.perf_counter() - t0
+    # a ticket may be waited for again until 2 x lanes later passes reuse its result block; nothing has been submitted since the timed region
+    delivered = {k: v.copy() for k, v in pipe.wait(tk[-1]).items() if v is not None} if keep_last else None
     prof = pipe.profile_read() if not light else None
     if not light:
         pipe.profile_enable(0)
@@ -164,7 +168,7 @@ def run_pipe(torch, api, weights, nv_weights, precision, F, lanes, steps, warmup
     fb = fe.match_fallback_rows(reset=True, full=True)
     NI, NP = 2 * F, 2 * F + (xch.NR if xch else 0)
     res = dict(steps=steps, value=F * world * steps / elapsed, ms_per_step=elapsed / steps * 1e3, host_submit_ms=th / steps * 1e3, lanes=lanes, F=F, NI=NI, NP=NP, gated=None, exch=None,
-               breakdown=None, fallback_rows=(fb[0] / float(steps + warmup), fb[1] / float(steps + warmup)), roofline=None, roofline_nv=None)
+               breakdown=None, fallback_rows=(fb[0] / float(steps + warmup), fb[1] / float(steps + warmup)), roofline=None, roofline_nv=None, last=delivered)
     if xch:
         S = last["x"]
         res["exch"] = {"impl": ximpl, "wire_precision": exchange, "block_bytes": xch.block_bytes, "all_gather_bytes_received_per_step_per_gpu": xch.block_bytes * F * (world - 1 + (1 if loopback else 0)),

@@ -164,3 +164,31 @@ def test_headline_fits_the_tail_and_names_the_extras_file(tmp_path, monkeypatch)
     # a run without a CPU baseline / roofline still carries the keys (null)
     line2, _ = bench.headline({"metric": "m", "value": 1.0})
     assert line2["cpu_baseline"] is None and line2["roofline"] is None and line2["vs_baseline"] is None
+
+
+def test_dump_outputs_zeroes_rows_past_the_counts_and_fits_the_budget(tmp_path):
+    """--dump-outputs: one .npy per delivered array, float32 for floats and float64 for counts / indices (exact), rows past an image's or pair's count zeroed;
+    above the budget the large arrays become the same seeded sample on every call."""
+    rng = np.random.RandomState(1)
+    I, F, C, D, G = 4, 2, 5, 8, 6
+    res = {"kps_xy": rng.rand(I, C, 2).astype(np.float32), "scores": rng.rand(I, C).astype(np.float32), "desc": rng.rand(I, C, D).astype(np.float32),
+           "n_kp": np.array([5, 0, 3, 9], np.int32), "netvlad": rng.rand(F, G).astype(np.float32), "lr_q": rng.randint(0, C, (F, C)).astype(np.int32),
+           "lr_t": rng.randint(0, C, (F, C)).astype(np.int32), "lr_dist": rng.rand(F, C).astype(np.float32), "lr_n": np.array([2, 5], np.int32),
+           "prev_q": rng.randint(0, C, (F, C)).astype(np.int32), "prev_t": rng.randint(0, C, (F, C)).astype(np.int32), "prev_dist": rng.rand(F, C).astype(np.float32),
+           "prev_n": np.array([0, 1], np.int32), "unused": None}
+    rec = bench.dump_outputs(str(tmp_path / "a"), res)
+    got = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in os.listdir(str(tmp_path / "a"))}
+    assert sorted(got) == rec["arrays"] == sorted(k for k in res if k != "unused") and rec["sampled"] is None
+    assert got["desc"].dtype == np.float32 and got["n_kp"].dtype == np.float64 and got["lr_q"].dtype == np.float64
+    assert np.array_equal(got["n_kp"], [5, 0, 3, 9]) and np.array_equal(got["netvlad"], res["netvlad"])
+    assert np.array_equal(got["desc"][0], res["desc"][0]) and np.array_equal(got["desc"][3], res["desc"][3]) and not got["desc"][1].any()
+    assert np.array_equal(got["desc"][2, :3], res["desc"][2, :3]) and not got["desc"][2, 3:].any() and not got["kps_xy"][2, 3:].any() and not got["scores"][1].any()
+    assert np.array_equal(got["lr_q"][0, :2], res["lr_q"][0, :2]) and not got["lr_q"][0, 2:].any() and np.array_equal(got["lr_t"][1], res["lr_t"][1])
+    assert not got["prev_dist"][0].any() and np.array_equal(got["prev_dist"][1, :1], res["prev_dist"][1, :1])
+    big = dict(res, desc=rng.rand(I, C, 20000).astype(np.float32))          # 1.6 MB: over a 1 MiB + small budget
+    budget = (1 << 20) + 4096
+    r1 = bench.dump_outputs(str(tmp_path / "b"), big, budget=budget)
+    r2 = bench.dump_outputs(str(tmp_path / "c"), big, budget=budget)
+    assert r1["bytes"] <= budget and list(r1["sampled"]) == ["desc"]
+    s1, s2 = np.load(str(tmp_path / "b" / "desc.npy")), np.load(str(tmp_path / "c" / "desc.npy"))
+    assert s1.ndim == 1 and np.array_equal(s1, s2) and s1.nbytes < big["desc"].nbytes

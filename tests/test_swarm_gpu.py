@@ -164,12 +164,12 @@ def _bare_env(**extra):
 
 
 def test_bench_default_line_contract_and_one_gpu_rccl_loopback_leg(tmp_path):
-    """`python bench.py` as the driver runs it (fewer steps / CPU iterations, the long legs off), stderr MERGED into stdout: the JSON line is the last line although the run
+    """`python bench.py --full` (fewer steps / CPU iterations, the long legs off), stderr MERGED into stdout: the JSON line is the last line although the run
     creates and destroys a one-rank RCCL communicator (whose banner C stdio flushes at exit -- round 5's line was lost to it), it is < 6 KB and carries `roofline` and
     `cpu_baseline` by the SURVEY 8(d) protocol; the other legs are in the extras file it names.  `exchange_on_one_gpu_rccl` there: the N > 1 exchange sequence behind the
     value step over the one-rank communicator (loopback), with vs without; it must run (no "error") and cost a few per cent at most."""
     ex = str(tmp_path / "extras.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--frames", "8", "--cpu-iterations", "3", "--no-latency", "--no-batch-curve",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--frames", "8", "--cpu-iterations", "3", "--no-latency", "--no-batch-curve",
                         "--no-live-traffic", "--no-width-sensitivity", "--no-parity-study"], cwd=ROOT, env=_bare_env(D2FE_BENCH_EXTRAS=ex),
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:]
@@ -189,11 +189,38 @@ def test_bench_default_line_contract_and_one_gpu_rccl_loopback_leg(tmp_path):
     assert e["exchange_cost_frac_of_step"] < 0.25, e      # ~2 % at 32 frames per submit; small steps on a shared box are noisier
 
 
+def test_bench_plain_run_times_value_only_and_dumps_identical_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: the headline step only (no CPU baseline, no secondary leg), and --dump-outputs writes what the
+    last timed step delivered -- the same arrays, bit for bit, from two runs with the same arguments."""
+    runs = []
+    for i in range(2):
+        d = str(tmp_path / ("out%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--frames", "4", "--dump-outputs", d], cwd=ROOT,
+                           env=_bare_env(D2FE_BENCH_EXTRAS=str(tmp_path / ("extras%d.json" % i))), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:]
+        j = _last_line(r)
+        assert j["steps"] == 4 and j["ms_per_step"] > 0 and j["higher_is_better"] is True and j["dtype"] == "f32" and j["unit"] == "stereo_frames/s"
+        assert abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) / j["value"] < 0.01
+        assert j["cpu_baseline"] is None and "parity" not in j
+        full = _full(j)
+        for k in ("configs1", "exact_mode", "fast_mode", "batch_curve", "latency", "quadcam", "device_resident", "index_parity_in_run", "exchange_on_one_gpu_rccl"):
+            assert k not in full, k
+        runs.append({n[:-4]: np.load(os.path.join(d, n)) for n in os.listdir(d)})
+    a, b = runs
+    assert sorted(a) == sorted(["kps_xy", "scores", "desc", "n_kp", "netvlad", "lr_q", "lr_t", "lr_dist", "lr_n", "prev_q", "prev_t", "prev_dist", "prev_n"])
+    assert a["desc"].shape == (8, 200, 256) and a["netvlad"].shape[0] == 4 and a["lr_n"].shape == (4,)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    n = a["n_kp"].astype(np.int64)
+    assert (n > 0).all() and all(not a["desc"][i, n[i]:].any() for i in range(8))
+    assert np.allclose(np.linalg.norm(a["desc"][0, :n[0]], axis=1), 1.0, atol=1e-4)
+
+
 def test_bench_force_dist_sends_one_rank_through_the_n_gpu_path(tmp_path):
     """--force-dist: --gpus 1 through self_launch -> torch.distributed.run -> init_process_group("nccl", device_id) -> collective_evidence -> PipeExchange
     (loopback) -> destroy_process_group with the N > 1 lane count; the line is still the last line of the merged stream and says what it ran."""
     ex = str(tmp_path / "extras.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "6", "--warmup", "2", "--frames", "8", "--single-mode"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--full", "--steps", "6", "--warmup", "2", "--frames", "8", "--single-mode"], cwd=ROOT,
                        env=_bare_env(D2FE_BENCH_EXTRAS=ex), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
     j = _last_line(r)
@@ -266,7 +293,7 @@ def test_bench_gpus2_one_frame_per_step_timeline():
     """The real swarm cadence (VERDICT r03 #6b): ONE stereo frame per agent and step.  Two ranks share the GPU under gloo (the all-gather is staged
     through the host there, so ITS time says nothing about xGMI); what is held to a budget is everything this library adds on the device beside
     it: packing the blocks and decode / count fix-up / NetVLAD gate, from HIP events on the exchange's stream."""
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--frames", "1", "--single-mode", "--no-cpu-baseline"],
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "6", "--warmup", "2", "--frames", "1", "--single-mode", "--no-cpu-baseline"],
                   {"D2FE_BENCH_BACKEND": "gloo"}, merged=True)
     assert r.returncode == 0, r.stdout[-3000:]
     j = _full(_last_line(r))

@@ -52,11 +52,30 @@ def test_load_superpoint_pth_missing_layer_fails_loudly(tmp_path):
         W.load_superpoint_pth(p)
 
 
-@pytest.mark.skipif(not os.path.exists(NB), reason="needs the reference tree (the notebook's module is executed, not copied)")
+SP_KEYS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "superpoint_state_dict_keys.json")
+
+
 def test_load_superpoint_pth_from_the_notebook_module(tmp_path):
     """torch.save of the state_dict of the reference's OWN module (SuperPointNet, superpoint.ipynb cell 1, executed from the notebook as
     tests/golden/make_golden_ref.py does): its key set is exactly the loader's, and what the loader returns loads back into the module
-    (load_state_dict is strict) and reproduces its parameters."""
+    (load_state_dict is strict) and reproduces its parameters.  Without the reference tree the module's key names and shapes recorded from it
+    (tests/golden/superpoint_state_dict_keys.json, make_golden_sp_keys.py) stand in for it: a state_dict of exactly those keys and shapes."""
+    rec = json.load(open(SP_KEYS))
+    assert rec["keys"] == [n + s for n in W.SP_LAYERS for s in (".weight", ".bias")]
+    for n in W.SP_LAYERS:
+        co, ci, k = W.SP_SHAPES[n]
+        assert rec["shapes"][n + ".weight"] == [co, ci, k, k] and rec["shapes"][n + ".bias"] == [co]
+    if not os.path.exists(NB):
+        torch.manual_seed(5)
+        sd = {k: torch.randn(rec["shapes"][k]) for k in rec["keys"]}
+        p = str(tmp_path / "superpoint_v1.pth")
+        torch.save(sd, p)
+        got = W.load_superpoint_pth(p)
+        for n in W.SP_LAYERS:
+            assert np.array_equal(got[n][0], sd[n + ".weight"].numpy()) and np.array_equal(got[n][1], sd[n + ".bias"].numpy())
+        back = _state_dict(got)
+        assert sorted(back) == sorted(rec["keys"]) and all(list(back[k].shape) == rec["shapes"][k] for k in rec["keys"])
+        return
     cells = ["".join(c["source"]) for c in json.load(open(NB))["cells"]]
     ns = {"torch": torch}
     exec(compile(cells[1], NB + ":cell1", "exec"), ns)
@@ -65,6 +84,7 @@ def test_load_superpoint_pth_from_the_notebook_module(tmp_path):
     p = str(tmp_path / "superpoint_v1.pth")
     torch.save(net.state_dict(), p)
     assert sorted(net.state_dict()) == sorted(n + s for n in W.SP_LAYERS for s in (".weight", ".bias"))
+    assert list(net.state_dict()) == rec["keys"] and all(list(v.shape) == rec["shapes"][k] for k, v in net.state_dict().items())
     got = W.load_superpoint_pth(p)
     for n in W.SP_LAYERS:
         assert np.array_equal(got[n][0], getattr(net, n).weight.detach().numpy()) and np.array_equal(got[n][1], getattr(net, n).bias.detach().numpy())

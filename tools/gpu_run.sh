@@ -5,11 +5,11 @@
 #
 #   suite [pytest args...]       pytest -m gpu (extra args are passed on, e.g.  suite -k "pipe or match")            -> gpurun_out/run/pytest_gpu.txt
 #   smoke                        __graft_entry__.smoke()
-#   bench [bench.py args...]     bench.py with its JSON line saved and the key numbers printed                        -> gpurun_out/run/bench*.json
+#   bench [bench.py args...]     bench.py --full with its JSON line saved and the key numbers printed                 -> run/bench*.json of the output folder
 #   profile <tag> [precision]    tools/profile.sh: rocprofv3 kernel-trace stats + four PMC passes of bench.py        -> gpurun_out/prof_<tag>_<prec>/summary.txt
 #   stats <tag> [bench args...]  tools/prof_stats.sh: kernel-trace stats of any bench configuration
 #   ab <tag> [bench args...]     same-box A/B: d2slam_amd/lib/libd2fe_hip_A.so (a copy of the previous build) against the current library,
-#                                three alternating runs of bench.py --single-mode (value, ms/step, conv1b ms, NetVLAD ms, per-stage times)
+#                                three alternating runs of bench.py --full --single-mode (value, ms/step, conv1b ms, NetVLAD ms, per-stage times)
 #   envab <tag> VAR a b [args]   the same for an environment switch of the development library
 #   latency                      bench.py --latency-only (single-call latencies through the C ABI, p50)
 #   pipe <sweep> [args...]       tools/pipe_probe.py --sweep <lanes x frames,...>  (e.g.  pipe 1x1,4x1,8x1 --coalesce 4)
@@ -59,20 +59,20 @@ run_task() {
              ( time timeout 2400 python -m pytest $where -x -q -m gpu "$@" 2>&1 | tail -25 ) > $O/pytest_gpu.txt 2>&1; tail -8 $O/pytest_gpu.txt ;;
     smoke)   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -3 $O/smoke.txt ;;
     bench)   BENCH_N=$((BENCH_N+1)); local f=$O/bench$BENCH_N
-             ( time timeout 1200 python bench.py "$@" > $f.json 2> $f.err ) 2> $f.time; tail -3 $f.time | head -1; grep -v amdgpu.ids $f.err | tail -4; bench_summary $f.json ;;
+             ( time timeout 1200 python bench.py --full "$@" > $f.json 2> $f.err ) 2> $f.time; tail -3 $f.time | head -1; grep -v amdgpu.ids $f.err | tail -4; bench_summary $f.json ;;
     profile) bash tools/profile.sh "$@" > $O/profile.log 2>&1; tail -2 $O/profile.log ;;
     stats)   bash tools/prof_stats.sh "$@" ;;
     ab)      local tag=$1; shift; local d=gpurun_out/ab_$tag; mkdir -p $d; : > $d/ab.txt
              for r in 1 2 3; do for lib in A cur; do
                if [ $lib = A ]; then export D2FE_LIB=$PWD/d2slam_amd/lib/libd2fe_hip_A.so; else unset D2FE_LIB; fi
                echo -n "$lib: " >> $d/ab.txt
-               timeout 300 python bench.py --single-mode --no-cpu-baseline --no-latency --breakdown "$@" 2>$d/err_$lib.txt | python -c "$ab_line" >> $d/ab.txt 2>&1
+               timeout 300 python bench.py --full --single-mode --no-cpu-baseline --no-latency --breakdown "$@" 2>$d/err_$lib.txt | python -c "$ab_line" >> $d/ab.txt 2>&1
              done; done; unset D2FE_LIB
              for lib in A cur; do grep "per-stage" $d/err_$lib.txt | tail -1 >> $d/ab.txt; done; cat $d/ab.txt ;;
     envab)   local tag=$1 var=$2 a=$3 b=$4; shift 4; local d=gpurun_out/envab_$tag; mkdir -p $d; : > $d/ab.txt
              for r in 1 2 3; do for v in "$a" "$b"; do
                echo -n "$var=$v: " >> $d/ab.txt
-               env $var=$v timeout 300 python bench.py --single-mode --no-cpu-baseline --no-latency --breakdown "$@" 2>$d/err_$v.txt | python -c "$ab_line" >> $d/ab.txt 2>&1
+               env $var=$v timeout 300 python bench.py --full --single-mode --no-cpu-baseline --no-latency --breakdown "$@" 2>$d/err_$v.txt | python -c "$ab_line" >> $d/ab.txt 2>&1
              done; done
              for v in "$a" "$b"; do grep "per-stage" $d/err_$v.txt | tail -1 >> $d/ab.txt; done; cat $d/ab.txt ;;
     latency) timeout 300 python bench.py --latency-only "$@" 2>/dev/null | python -c 'import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1])["latency"]; print({k:v["p50_ms"] for k,v in j.items() if isinstance(v,dict)})' ;;
