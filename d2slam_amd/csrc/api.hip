@@ -23,18 +23,15 @@
 using namespace d2fe;
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
+// accessors for the translation units that keep their own extern "C" entry points (lk.hip, netvlad_host.hip)
+namespace d2fe {
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-}  // namespace
-
-// accessors for the translation units that keep their own extern "C" entry points (lk.hip)
-namespace d2fe {
 int ctx_fail(int code, const std::string& msg) { return fail(code, msg); }
 int ctx_device(d2fe_handle h) { return h->cfg.device_id; }
 hipStream_t ctx_stream(d2fe_handle h) { return h->stream; }
@@ -50,6 +47,11 @@ int ctx_scratch(d2fe_handle h, size_t bytes, void** out) {
   *out = h->lk_scratch;
   return D2FE_OK;
 }
+int upload(const void* src, size_t bytes, void** dst) {
+  HIP_TRY(hipMalloc(dst, bytes));
+  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return D2FE_OK;
+}
 }  // namespace d2fe
 
 namespace {
@@ -57,12 +59,6 @@ namespace {
 int alloc_f(Tensor& t, size_t per_img, int batch) {
   t.per_img = per_img;
   HIP_TRY(hipMalloc(&t.p, per_img * batch * sizeof(float)));
-  return D2FE_OK;
-}
-
-int upload(const void* src, size_t bytes, void** dst) {
-  HIP_TRY(hipMalloc(dst, bytes));
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
   return D2FE_OK;
 }
 
@@ -108,25 +104,9 @@ int check_layer(const d2fe_conv_params& p, int cout, int cin, int ks, const char
   return D2FE_OK;
 }
 
-struct ProfScope {
-  d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
-  ProfScope(d2fe_context* h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {
-    on = h->prof_mode == 2 || (h->prof_mode == 1 && (stage == D2FE_PROF_CONV1B || stage == D2FE_PROF_NETVLAD));
-    if (!on) return;
-    if (h->prof_used + 2 > h->prof_pool.size()) {
-      for (int i = 0; i < 64; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { on = false; return; } h->prof_pool.push_back(e); }
-    }
-    a = h->prof_pool[h->prof_used++]; b = h->prof_pool[h->prof_used++];
-    (void)hipEventRecord(a, s);
-  }
-  ~ProfScope() {
-    if (!on) return;
-    (void)hipEventRecord(b, s);
-    h->prof_recs.push_back({stage, a, b});
-  }
-};
+}  // namespace
 
-// weights / PCA matrices were (re)loaded: the captured launch sequences hold the old device pointers
+namespace d2fe {
 void graphs_clear(d2fe_context* h) {
   if (h->graphs.empty()) return;
   (void)hipStreamSynchronize(h->stream);
@@ -134,57 +114,20 @@ void graphs_clear(d2fe_context* h) {
   h->graphs.clear();
 }
 
-// Runs `fn(s)` -- a launch sequence on `s` whose arguments are a pure function of `key` (handle-owned buffers only) -- directly the
-// first time a key is seen (module loads, function attributes, lazy allocations happen there), captures it into a hipGraph the second
-// time and replays the instantiated graph from then on.  Anything that cannot be captured marks the key bad and runs directly.
 void host_state_save(const d2fe_context* h, d2fe_context::HostState& st) {
   st.last_w = h->last_w; st.last_h = h->last_h; st.last_n = h->last_n; st.last_set = h->last_set;
   st.last_gray = h->last_gray; st.last_stride = h->last_stride; st.last_istride = h->last_istride;
-  st.nv_slabs.clear();
-  for (const auto& l : h->nv) st.nv_slabs.emplace_back(l.slabs, l.slab_stride);
-  st.nv_feat_slabs = h->nv_feat_slabs; st.nv_feat_slab_stride = h->nv_feat_slab_stride; st.nv_stamp_wgs = h->nv_stamp_wgs;
+  st.nv = h->nv_run.last;
 }
 void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool netvlad) {
   if (netvlad) {
-    for (size_t i = 0; i < h->nv.size() && i < st.nv_slabs.size(); ++i) { h->nv[i].slabs = st.nv_slabs[i].first; h->nv[i].slab_stride = st.nv_slabs[i].second; }
-    h->nv_feat_slabs = st.nv_feat_slabs; h->nv_feat_slab_stride = st.nv_feat_slab_stride; h->nv_stamp_wgs = st.nv_stamp_wgs;
+    h->nv_run.last = st.nv;
   } else {
     h->last_w = st.last_w; h->last_h = st.last_h; h->last_n = st.last_n; h->last_set = st.last_set;
     h->last_gray = st.last_gray; h->last_stride = st.last_stride; h->last_istride = st.last_istride;
   }
 }
 
-template <class F>
-int run_cached(d2fe_context* h, const std::array<long, 6>& key, hipStream_t s, F&& fn) {
-  if (!h->use_graphs || h->prof_mode != 0) return fn(s);
-  auto& e = h->graphs[key];
-  if (e.bad) return fn(s);
-  const bool netvlad = key[0] != 1;       // key[0]: 1 = the SuperPoint sequence, 2 / 3 = NetVLAD (own frames / the frames SuperPoint reads)
-  if (e.exec) { HIP_TRY(hipGraphLaunch(e.exec, s)); host_state_restore(h, e.st, netvlad); return D2FE_OK; }
-  if (e.seen++ < 1) return fn(s);
-  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); e.bad = true; return fn(s); }
-  const int rc = fn(s);
-  hipGraph_t g = nullptr;
-  const hipError_t er = hipStreamEndCapture(s, &g);
-  if (rc != D2FE_OK || er != hipSuccess || !g) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    e.bad = true;
-    return rc != D2FE_OK ? rc : fn(s);
-  }
-  hipGraphExec_t ex = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ei != hipSuccess || !ex) { (void)hipGetLastError(); e.bad = true; return fn(s); }
-  e.exec = ex;
-  host_state_save(h, e.st);               // fn(s) ran its host code during the capture: this is the state a direct run leaves
-  HIP_TRY(hipGraphLaunch(e.exec, s));
-  return D2FE_OK;
-}
-
-}  // namespace
-
-namespace d2fe {
 // the launch sequence == one TensorRT executeV2 + processOutput of the reference
 int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride,
                    float* d_kps, float* d_scores, float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s,
@@ -474,10 +417,6 @@ static int create_context(const d2fe_config* cfg, d2fe_handle* out, bool lane, h
 extern "C" {
 int d2fe_create(const d2fe_config* cfg, d2fe_handle* out) { return d2fe::create_context(cfg, out, false); }
 
-}  // extern "C"
-namespace { void nv_free(d2fe_context* h); }
-extern "C" {
-
 void d2fe_destroy(d2fe_handle h) {
   if (!h) return;
   // pipes created from this handle run on ITS packed weights: destroying it under them would leave every lane with dangling pointers.  The destruction is
@@ -492,11 +431,10 @@ void d2fe_destroy(d2fe_handle h) {
     if (t->p) hipFree(t->p);
   if (!h->borrowed) {
     for (auto& L : h->L) { if (L.wpack) hipFree(L.wpack); if (L.bias) hipFree(L.bias); }
-    for (void* p : {(void*)h->w1a, (void*)h->b1a, (void*)h->pca_comp_t, (void*)h->pca_mean, (void*)h->nv_pca_comp, (void*)h->nv_pca_mean}) if (p) hipFree(p);
+    for (void* p : {(void*)h->w1a, (void*)h->b1a, (void*)h->pca_comp_t, (void*)h->pca_mean}) if (p) hipFree(p);
   }
   for (void* p : {(void*)h->cand, (void*)h->s_img, (void*)h->aconf, (void*)h->clist, (void*)h->a_ncand, (void*)h->a_samp, (void*)h->a_cn, h->lk_scratch, (void*)h->zeros, (void*)h->work_ctrs, (void*)h->match_stats, (void*)h->match_stamps, (void*)h->sp_flags, (void*)h->sp_slotmap, (void*)h->sp_cells, (void*)h->sp_count, (void*)h->sp_desc, (void*)h->sp_mid})
     if (p) hipFree(p);
-  nv_free(h);
   for (void* p : {(void*)h->nv_s_img, (void*)h->nv_s_out}) if (p) hipFree(p);
   for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
   if (h->nv_stream) { hipStreamSynchronize(h->nv_stream); (void)hipStreamDestroy(h->nv_stream); }
@@ -622,10 +560,9 @@ int d2fe_superpoint_wait_tail(d2fe_handle h, void* stream) {
   return D2FE_OK;
 }
 
-// host image(s) -> the handle's device staging, tight rows: through the pinned staging buffer (CPU row copy + ONE DMA) or, when that
-// is off, with pageable 2D copies
-static int upload_frames(d2fe_context* h, uint8_t* d_dst, const uint8_t* gray, int n, int width, int height, int stride, size_t image_stride,
-                         hipStream_t s) {
+}  // extern "C"
+int d2fe::upload_frames(d2fe_context* h, uint8_t* d_dst, const uint8_t* gray, int n, int width, int height, int stride, size_t image_stride,
+                        hipStream_t s) {
   const size_t bytes = (size_t)width * height * n;
   if (h->use_pinned && bytes <= h->pin_in_bytes) {
     HIP_TRY(hipStreamSynchronize(s));            // the previous call's DMA out of pin_in has completed (calls are synchronous: a no-op)
@@ -647,7 +584,7 @@ static int upload_frames(d2fe_context* h, uint8_t* d_dst, const uint8_t* gray, i
   }
   return D2FE_OK;
 }
-
+extern "C" {
 
 // host-pointer extract of n images; n_netvlad > 0: the NetVLAD descriptors of the first n_netvlad of them as well, from the SAME uploaded frames,
 // on a second stream beside SuperPoint (d2fe_extract_all*)
@@ -703,7 +640,7 @@ static int extract_host(d2fe_handle h, const uint8_t* gray, int n, int width, in
     HIP_TRY(hipEventRecord(h->ev_up, s));
     HIP_TRY(hipStreamWaitEvent(h->nv_stream, h->ev_up, 0));
     nv_guard.armed = true;
-    rc = run_cached(h, {3, n_netvlad, width, height, (long)h->nv_pca_m, 0}, h->nv_stream, [&](hipStream_t st) {
+    rc = run_cached(h, {3, n_netvlad, width, height, (long)h->nv_net->pca_m, 0}, h->nv_stream, [&](hipStream_t st) {
       return run_netvlad(h, h->s_img, n_netvlad, width, height, width, (size_t)width * height, h->nv_s_out, st);
     });
     if (rc) return rc;
@@ -788,500 +725,6 @@ int d2fe_superpoint_extract(d2fe_handle h, const uint8_t* gray, int width, int h
 }
 
 }  // extern "C"
-// ---- NetVLAD -----------------------------------------------------------------------------------------------------------
-namespace {
-void nv_free(d2fe_context* h) {
-  const bool own = !h->borrowed;      // a pipeline lane owns its activations only
-  for (auto& l : h->nv) { if (own && l.w) hipFree(l.w); if (own && l.b) hipFree(l.b); if (l.out) hipFree(l.out); }
-  h->nv.clear();
-  if (own) for (auto& st : h->nv_plan) { if (st.we) hipFree(st.we); if (st.wp) hipFree(st.wp); if (st.bp) hipFree(st.bp); if (st.w0) hipFree(st.w0); if (st.wp2) hipFree(st.wp2); if (st.bp2) hipFree(st.bp2); }
-  h->nv_plan.clear();
-  for (float** p : {&h->nv_pre_w, &h->nv_pre_b, &h->nv_aw, &h->nv_aw_pack, &h->nv_ab, &h->nv_cen})
-    if (*p) { if (own) hipFree(*p); *p = nullptr; }
-  for (float** p : {&h->nv_feat_buf, &h->nv_raw, &h->nv_pca_out, &h->nv_part})
-    if (*p) { hipFree(*p); *p = nullptr; }
-  if (h->nv_stamps) { hipFree(h->nv_stamps); h->nv_stamps = nullptr; }
-  h->nv_loaded = false;
-}
-inline int same_out(int in, int stride) { return (in + stride - 1) / stride; }
-inline int same_pad_begin(int in, int stride, int out) { const int t = (out - 1) * stride + 3 - in; return t > 0 ? t / 2 : 0; }   // TF "SAME", 3x3
-
-// hidden-channel groups for a fused step: enough workgroups to fill the chip (2 per CU), at least 3 chunks of 16 per group (every
-// group stages the whole input patch again, and its consumer reads one more partial slab).  Three or more groups (two, when the consumer reads a
-// single slab: `sum_at_2`) cost a slab-sum launch of ~6 us behind the block; a chunk costs ~2.3 us of a workgroup's latency (tools/nv_stamps.py):
-// the split goes past two groups only when the chunks it takes off every workgroup are worth more than that launch (30 x 40 layers: 9-12 chunks,
-// two groups; 15 x 20 layers: 60 chunks, seven)
-inline void nv_groups(long base_blocks, int nchunk, int gmax, int* groups, int* cpg, int target, long cap = 0, bool sum_at_2 = false, bool rule = true) {
-  int g = (int)((target + base_blocks - 1) / base_blocks);
-  if (cap > 0 && g > 1 && g * base_blocks > cap) --g;      // a second round of workgroups costs more than one more chunk per group
-  if (g > gmax) g = gmax;
-  if (g > nchunk / 3) g = nchunk / 3;
-  if (g < 1) g = 1;
-  auto per = [&](int gg) { return (nchunk + gg - 1) / gg; };
-  const double chunk_us = 2.3, launch_us = 6.0;
-  if (rule && g >= 3 && (per(2) - per(g)) * chunk_us < launch_us) g = 2;
-  if (rule && g == 2 && sum_at_2 && (per(1) - per(2)) * chunk_us < launch_us) g = 1;
-  // round 6 (MobileNetV2-0.75: 9 chunks at 120 x 160 and 60 x 80): with 32 or more tiles per image a second group halves a workgroup's chunks (~10 us of ONE image's
-  // latency) but makes every batch stage each input patch twice, write and re-read a second slab and, where the consumer wants one slab, launch the slab sum:
-  // measured at 32 images 194 + 26 us with two groups against 160 us with one (profiles/r06_netvlad_timeline.txt).  The split stays per IMAGE (batch invariance)
-  if (rule && g == 2 && base_blocks >= 32 && nchunk <= 12) g = 1;
-  *cpg = per(g);
-  *groups = (nchunk + *cpg - 1) / *cpg;
-}
-
-}  // namespace
-namespace d2fe {
-int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_out,
-                hipStream_t s) {
-  ProfScope ps(h, D2FE_PROF_NETVLAD, s);
-  int ch = H, cw = W;
-  bool feat_done = false;
-  for (size_t si = 0; si < h->nv_plan.size(); ++si) {
-    const auto& st = h->nv_plan[si];
-    const bool next_fused = si + 1 < h->nv_plan.size() && h->nv_plan[si + 1].fused;
-    // nv_xblock_kernel (stride-2 blocks) and nv_tail_kernel read ONE input slab: their producer's partial slabs are summed first
-    const bool next_single = next_fused && ((h->nv_plan[si + 1].xblock && !h->nv_plan[si + 1].pblock) || h->nv_plan[si + 1].tail ||
-                                            (h->nv_plan[si + 1].pblock && !h->nv_plan[si + 1].front && nv_pblock_single_input(h->nv[h->nv_plan[si + 1].l0].cin)));
-    if (!st.fused) {
-      auto& l = h->nv[st.l0];
-      const float* in = st.l0 ? h->nv[st.l0 - 1].out : nullptr;
-      const int ho = same_out(ch, l.stride), wo = same_out(cw, l.stride);
-      if (l.kind == D2FE_NV_CONV) {
-        HIP_TRY(launch_nv_conv0(d_gray, stride, (long)image_stride, ch, cw, ho, wo, l.stride, l.cout, l.act, l.w, l.b, l.out, n, s));
-      } else if (l.kind == D2FE_NV_DW) {
-        HIP_TRY(launch_nv_dw(in, ch, cw, l.cin, ho, wo, l.stride, l.act, l.w, l.b, l.out, n, s));
-      } else {
-        HIP_TRY(launch_nv_pw(in, (long)n * ch * cw, l.cin, l.cout, l.cout_pad, l.act, l.w, l.b, l.res >= 0 ? h->nv[l.res].out : nullptr,
-                             l.out, s));
-      }
-      l.slabs = 1; l.slab_stride = 0;
-      ch = ho; cw = wo;
-      continue;
-    }
-    NvBlockArgs a{};
-    int li = st.l0;
-    if (st.front) {
-      const auto& c0 = h->nv[li++];
-      a.img = d_gray; a.img_stride = stride; a.img_istride = (long)image_stride; a.H0 = ch; a.W0 = cw;
-      const int ho = same_out(ch, c0.stride), wo = same_out(cw, c0.stride);
-      a.c0_stride = c0.stride; a.c0_pt = same_pad_begin(ch, c0.stride, ho); a.c0_pl = same_pad_begin(cw, c0.stride, wo);
-      a.act0 = c0.act; a.w0 = st.w0;
-      ch = ho; cw = wo;
-    } else {
-      const auto& pin = h->nv[st.l0 - 1];
-      a.in = pin.out; a.in_slabs = pin.slabs; a.in_slab_stride = pin.slab_stride;
-    }
-    int groups = 1, cpg = 0;
-    if (st.tail) {
-      // the trunk's last 1x1 (expand: feat_dim hidden channels) chained with the NetVLAD pre-projection, over the flat pixel list
-      const auto& e = h->nv[li];
-      a.we = st.we; a.act_e = e.act;
-      a.H = ch; a.W = cw; a.Ho = ch; a.Wo = cw; a.Cin = e.cin; a.Chid = e.cout; a.Cout = h->nv_proj; a.stride = 1;
-      a.P = (long)n * ch * cw;
-      a.wp = st.wp; a.bp = st.bp; a.act_p = 0;
-      // three workgroups per CU fit (registers), and the MFMA pipe is the limit: ~768 workgroups of equal length load every SIMD alike
-      // (the hidden-channel split is decided on ONE image's pixel count whatever the batch: see the block steps below)
-      nv_groups(((long)ch * cw + 127) / 128, a.Chid / 16, h->nv_feat_gmax, &groups, &cpg, h->nv_tail_blocks);
-      a.cpg = cpg; a.out = h->nv_feat_buf; a.out_slab_stride = a.P * a.Cout;
-      h->nv_feat_slabs = groups; h->nv_feat_slab_stride = a.out_slab_stride;
-      if (nv_tail_supported(a.Cin, a.Cout)) HIP_TRY(launch_nv_tail(a, groups, s));     // st.we was packed in that kernel's K order
-      else HIP_TRY(launch_nv_block(a, true, 2, n, groups, s));
-      // no slab sum here: the VLAD stage reads every feature exactly once and adds the slabs, in slab order, while it stages them
-      feat_done = true;
-      continue;
-    }
-    if (st.expand) { const auto& e = h->nv[li++]; a.we = st.we; a.act_e = e.act; }
-    const auto& d = h->nv[li++];
-    auto& pj = h->nv[li];
-    a.H = ch; a.W = cw; a.Cin = st.expand ? h->nv[st.l0].cin : d.cin; a.Chid = d.cin; a.Cout = pj.cout; a.stride = d.stride;
-    a.Ho = same_out(ch, d.stride); a.Wo = same_out(cw, d.stride);
-    a.pt = same_pad_begin(ch, d.stride, a.Ho); a.pl = same_pad_begin(cw, d.stride, a.Wo);
-    a.act_d = d.act;
-    a.wp = st.wp; a.bp = st.bp; a.act_p = pj.act;
-    if (pj.res >= 0) { const auto& r = h->nv[pj.res]; a.res = r.out; a.res_slabs = r.slabs; a.res_slab_stride = r.slab_stride; }
-    a.th = 8; a.tw = 16;
-    if (st.pblock) nv_pblock_tile(a.Ho, a.Wo, &a.th, &a.tw, st.front ? a.c0_stride : 0);
-    else if (st.xblock) nv_xblock_tile(a.Ho, a.Wo, a.stride, &a.th, &a.tw);
-    const long tiles1 = (long)((a.Wo + a.tw - 1) / a.tw) * ((a.Ho + a.th - 1) / a.th);
-    const long tiles = tiles1 * n;
-    // partial slabs are summed by the consumer's staging: only when that consumer is a fused step
-    // pixel-pair kernel: no more workgroups than 85 % of what the device holds at once (registers / LDS of that block shape).
-    // The split of the hidden channels over workgroup groups fixes the fp32 summation order of the block's output, so it is decided on ONE
-    // image's tile count and the DEVICE's compute units (not the batch, not a pipeline lane's share): an image's descriptor is the same bits
-    // in a 1-image call, a 32-image batch and any pass of the frames-in-flight pipe.  A batch then runs with more groups than it needs to fill
-    // the device (15 x 20 layers at 32 images: 7 slabs instead of 4) -- a few MB of partial-slab traffic
-    // a consumer that is NOT a fused step (a generic per-layer launch: the stride-2 block 72 -> 432 -> 120 of the 0.75-wide trunk) reads one plain tensor: the split is
-    // still worth it (27 chunks in ONE workgroup per tile ran 115 us at 32 images and 70 us for one image; nine groups + the slab sum: 55 + 17 us), the slabs are summed below
-    const bool sum_for_plain_consumer = !next_fused;
-    nv_groups(tiles1, a.Chid / 16, pj.gmax, &groups, &cpg, h->nv_blocks_target,
-              st.pblock ? nv_pblock_slots(a.Cin, a.Cout, h->ncu_dev, 1) * 85 / 100 : 0, next_single || sum_for_plain_consumer, h->nv_group_rule);
-    a.cpg = cpg; a.out = pj.out; a.out_slab_stride = (long)n * a.Ho * a.Wo * a.Cout;
-    // Six or more groups per image (30 x 40 and 15 x 20 layers: what ONE image needs to reach 60-135 workgroups) are 2-3 rounds of short workgroups for a batch, each
-    // staging its input patch again and writing its own slab.  The summation order of such a layer is a two-level tree -- runs of `tree` groups, then the runs in order --
-    // and a batch lets one workgroup walk a whole run (NvBlockArgs::gmerge): same bits as one image's unmerged launch + tree-ordered slab sum, a third of the
-    // workgroups, patch loads and slabs.  `tree` depends on the layer alone, merging on the batch
-    int tree = 1, wgroups = groups;
-    const int half0 = nv_pblock_half_cout(a.Cout, 0);
-    if (st.pblock && !st.front && groups >= 6 && nv_pblock_can_merge(a.Cin, half0) &&
-        (!st.wp2 || nv_pblock_can_merge(a.Cin, a.Cout - half0))) {
-      tree = 3;
-      const long slots = nv_pblock_slots(a.Cin, a.Cout, h->ncu_dev, 1);
-      if (h->nv_merge && tiles * groups > slots && tiles * ((groups + tree - 1) / tree) * 2 >= (h->ncu_dev > 0 ? h->ncu_dev : 256)) { a.gmerge = tree; wgroups = (groups + tree - 1) / tree; }
-    }
-    pj.slabs = wgroups; pj.slab_stride = a.out_slab_stride;
-    a.ncu = h->ncu; a.tpw = h->nv_front_tpw; a.nbuf = h->nv_nbuf;
-    if ((int)si == h->nv_stamp_step && h->nv_stamps && (tiles * wgroups <= 32768)) {
-      HIP_TRY(hipMemsetAsync(h->nv_stamps, 0, sizeof(unsigned long long) * 32 * 32768, s));
-      a.stamps = h->nv_stamps; h->nv_stamp_wgs = (int)(tiles * wgroups);
-    }
-    if (st.pblock && st.front) HIP_TRY(launch_nv_fpair(a, n, s));
-    else if (st.pblock && st.wp2) {
-      // more than 128 output channels: two launches over channel halves, each with its own project record (the expand + depthwise stages run in both)
-      NvBlockArgs h0 = a, h1 = a;
-      h0.co0 = 0; h0.Cv = nv_pblock_half_cout(a.Cout, 0);
-      h1.co0 = h0.Cv; h1.Cv = a.Cout - h0.Cv; h1.wp = st.wp2; h1.bp = st.bp2; h1.stamps = nullptr;
-      HIP_TRY(launch_nv_pblock(h0, n, groups, s));
-      HIP_TRY(launch_nv_pblock(h1, n, groups, s));
-    }
-    else if (st.pblock) HIP_TRY(launch_nv_pblock(a, n, groups, s));
-    else if (st.xblock) HIP_TRY(launch_nv_xblock(a, n, groups, s));
-    else HIP_TRY(launch_nv_block(a, st.expand, st.front ? 1 : 0, n, groups, s));
-    // three or more partial slabs: sum them once instead of in every consumer workgroup (and in every residual read)
-    // (decided on `groups`, the layer's own count: a consumer sees one slab or several whatever the batch merged)
-    // (a tree-ordered layer is always summed here: a consumer adding the slabs itself would do so in slab order, i.e. differently for merged and unmerged launches)
-    if (tree > 1 || (h->nv_slabsum > 0 && groups >= h->nv_slabsum) || ((next_single || sum_for_plain_consumer) && groups > 1)) {
-      HIP_TRY(launch_nv_slab_sum(pj.out, wgroups, pj.slab_stride, pj.slab_stride, s, a.gmerge > 1 ? 1 : tree));
-      pj.slabs = 1;
-    }
-    ch = a.Ho; cw = a.Wo;
-  }
-  const int np = ch * cw;
-  if (!feat_done) {
-    const int pp = (h->nv_proj + 31) / 32 * 32;
-    HIP_TRY(launch_nv_pw(h->nv.back().out, (long)n * np, h->nv_feat, h->nv_proj, pp, 0, h->nv_pre_w, h->nv_pre_b, nullptr, h->nv_feat_buf, s));
-    h->nv_feat_slabs = 1; h->nv_feat_slab_stride = 0;
-  }
-  float* raw = h->nv_pca_m ? h->nv_raw : d_out;
-  HIP_TRY(launch_nv_vlad(h->nv_feat_buf, h->nv_feat_slabs, h->nv_feat_slab_stride, np, h->nv_proj, h->nv_k, h->nv_aw, h->nv_aw_pack, h->nv_ab, h->nv_cen,
-                         h->nv_part, raw, n, s));
-  if (h->nv_pca_m) HIP_TRY(launch_nv_pca(raw, h->nv_k * h->nv_proj, h->nv_pca_comp, h->nv_pca_mean, h->nv_pca_m, d_out, n, s));
-  return D2FE_OK;
-}
-}  // namespace d2fe
-extern "C" {
-
-int d2fe_load_netvlad(d2fe_handle h, const d2fe_netvlad_weights* w) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
-  if (h) graphs_clear(h);
-  if (!h || !w || !w->layers || w->n_layers < 1) return fail(D2FE_ERR_INVALID, "null argument");
-  if (!w->pre_w || !w->pre_b || !w->assign_w || !w->assign_b || !w->centroids) return fail(D2FE_ERR_INVALID, "null head weights");
-  if (w->n_clusters < 1 || w->n_clusters > 64 || w->proj_dim < 4 || w->proj_dim > 256 || (w->proj_dim & 3) ||
-      w->n_clusters * w->proj_dim > 8192 || (w->feat_dim & 3))
-    return fail(D2FE_ERR_INVALID, "unsupported NetVLAD head shape");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  nv_free(h);
-  const int B = h->cfg.max_batch;
-  int ch = h->cfg.max_height, cw = h->cfg.max_width, cprev = 1;
-  // any failure below leaves the handle without a NetVLAD network and frees what was uploaded so far
-  struct Guard { d2fe_context* h; bool ok = false; ~Guard() { if (!ok) nv_free(h); } } guard{h};
-  for (int i = 0; i < w->n_layers; ++i) {
-    const d2fe_nv_layer& L = w->layers[i];
-    d2fe_context::NvLayer l;
-    l.kind = L.kind; l.cin = L.cin; l.cout = L.cout; l.stride = L.stride; l.act = L.act; l.res = L.res;
-    if (!L.weight || !L.bias || L.stride < 1 || L.stride > 2 || L.cin != cprev || L.res >= i || L.act < 0 || L.act > 2)
-      return fail(D2FE_ERR_INVALID, "netvlad layer " + std::to_string(i) + ": bad descriptor");
-    std::vector<float> wt, bt;
-    if (L.kind == D2FE_NV_CONV) {
-      if (i != 0 || L.cin != 1 || L.cout > 32) return fail(D2FE_ERR_INVALID, "conv layer must be first, 1 -> <=32 channels");
-      wt.assign(9 * 32, 0.f); bt.assign(32, 0.f);
-      for (int co = 0; co < L.cout; ++co) { bt[co] = L.bias[co]; for (int t = 0; t < 9; ++t) wt[t * 32 + co] = L.weight[co * 9 + t]; }
-      l.cout_pad = 32;
-    } else if (L.kind == D2FE_NV_DW) {
-      if (L.cin != L.cout || (L.cin & 3)) return fail(D2FE_ERR_INVALID, "depthwise layer: channels must match and be a multiple of 4");
-      wt.resize(9 * (size_t)L.cin); bt.assign(L.bias, L.bias + L.cin);
-      for (int c = 0; c < L.cin; ++c) for (int t = 0; t < 9; ++t) wt[(size_t)t * L.cin + c] = L.weight[c * 9 + t];
-      l.cout_pad = L.cout;
-    } else if (L.kind == D2FE_NV_PW) {
-      if ((L.cin & 3) || L.stride != 1) return fail(D2FE_ERR_INVALID, "pointwise layer: cin must be a multiple of 4, stride 1");
-      if (L.cin & 7) return fail(D2FE_ERR_INVALID, "pointwise layer: cin must be a multiple of 8");
-      l.cout_pad = (L.cout + 31) / 32 * 32;
-      wt.resize(packed_weight_floats_f32(l.cout_pad, L.cin, 1)); bt.assign(l.cout_pad, 0.f);
-      pack_weights_f32(L.weight, L.cout, L.cin, 1, l.cout_pad, wt.data());
-      for (int co = 0; co < L.cout; ++co) bt[co] = L.bias[co];
-    } else {
-      return fail(D2FE_ERR_INVALID, "unknown layer kind");
-    }
-    ch = same_out(ch, L.stride); cw = same_out(cw, L.stride);
-    l.oh = ch; l.ow = cw;
-    if (L.res >= 0) {
-      // a skip connection adds two tensors of the SAME shape: channels and spatial size (a stride-2 layer in between would make
-      // the 1x1 kernel read past the smaller buffer)
-      const auto& r = h->nv[L.res];
-      if (L.kind != D2FE_NV_PW || r.cout != L.cout || r.oh != ch || r.ow != cw)
-        return fail(D2FE_ERR_INVALID, "netvlad layer " + std::to_string(i) + ": residual source has a different shape");
-    }
-    h->nv.push_back(l);                 // pushed before the uploads: nv_free() releases whatever made it to the device
-    auto& dl = h->nv.back();
-    int rc = upload(wt.data(), wt.size() * sizeof(float), reinterpret_cast<void**>(&dl.w));
-    rc = rc ? rc : upload(bt.data(), bt.size() * sizeof(float), reinterpret_cast<void**>(&dl.b));
-    if (rc) return rc;
-    cprev = L.cout;
-  }
-  // ---- plan: fuse [conv0 ->] [pw expand ->] dw -> pw project where the kernels support the shape (D2FE_NV_LEGACY=1: one launch per layer)
-  {
-    // schedule switches of the development library (A/B measurements; the product library always takes the defaults: the measured best)
-    const bool legacy = d2fe_dev_env("D2FE_NV_LEGACY", 0) != 0;
-    { const int v = d2fe_dev_env("D2FE_NV_BLOCKS", 0); if (v > 0) h->nv_blocks_target = v; }
-    { const int v = d2fe_dev_env("D2FE_NV_TAIL_BLOCKS", 0); if (v > 0) h->nv_tail_blocks = v; }
-    h->nv_slabsum = d2fe_dev_env("D2FE_NV_SLABSUM", h->nv_slabsum);
-    h->nv_group_rule = d2fe_dev_env("D2FE_NV_GROUP_RULE", 1) != 0;
-    h->nv_merge = d2fe_dev_env("D2FE_NV_MERGE", 1) != 0;
-    h->nv_front_tpw = d2fe_dev_env("D2FE_NV_FRONT_TPW", 0); h->nv_nbuf = d2fe_dev_env("D2FE_NV_NBUF", 0);
-    h->nv_stamp_step = d2fe_dev_env("D2FE_NV_STAMP_STEP", -1);
-    if (h->nv_stamp_step >= 0 && !h->nv_stamps) HIP_TRY(hipMalloc(&h->nv_stamps, sizeof(unsigned long long) * 32 * 32768));
-    const int nl = w->n_layers;
-    auto K = [&](int i) { return i < nl ? h->nv[i].kind : -1; };
-    std::vector<char> materialised(nl, 0);
-    int i = 0;
-    while (i < nl) {
-      d2fe_context::NvStep st;
-      st.l0 = st.l1 = i;
-      if (!legacy) {
-        const bool pair_on = d2fe_dev_env("D2FE_NV_PAIR", 1) != 0;
-        // pixel-pair forms (netvlad_pair.hip): the first block with a first conv of 16 / 24 / 32 channels, stride-1 expand blocks of the widths in NVP_SHAPES
-        const bool fp_ok = pair_on && K(i) == D2FE_NV_CONV && K(i + 1) == D2FE_NV_DW && K(i + 2) == D2FE_NV_PW &&
-                           nv_fpair_supported(h->nv[i].cout, h->nv[i].stride, h->nv[i + 1].stride, h->nv[i + 2].cout);
-        const bool pb_ok = pair_on && i > 0 && K(i) == D2FE_NV_PW && K(i + 1) == D2FE_NV_DW && K(i + 2) == D2FE_NV_PW &&
-                           nv_pblock_supported(h->nv[i].cin, h->nv[i].cout, h->nv[i + 2].cout, h->nv[i + 1].stride);
-        if (K(i) == D2FE_NV_CONV && K(i + 1) == D2FE_NV_DW && K(i + 2) == D2FE_NV_PW && h->nv[i + 1].res < 0 && h->nv[i + 2].res < 0 &&
-            (fp_ok || nv_block_supported(h->nv[i + 1].cin, h->nv[i + 1].cin, h->nv[i + 2].cout, h->nv[i + 1].stride, false, 1))) {
-          st.fused = true; st.front = true; st.l1 = i + 2;
-          st.pblock = fp_ok;
-        } else if (i > 0 && K(i) == D2FE_NV_PW && K(i + 1) == D2FE_NV_DW && K(i + 2) == D2FE_NV_PW && h->nv[i].res < 0 &&
-                   (pb_ok || nv_block_supported(h->nv[i].cin, h->nv[i].cout, h->nv[i + 2].cout, h->nv[i + 1].stride, true, 0))) {
-          st.fused = true; st.expand = true; st.l1 = i + 2;
-          {       // input-in-registers form of the block where the shape allows it (otherwise the LDS-resident form)
-            st.xblock = d2fe_dev_env("D2FE_NV_XBLOCK", 1) != 0 && nv_xblock_supported(h->nv[i].cin, h->nv[i].cout, h->nv[i + 2].cout, h->nv[i + 1].stride);
-            // stride 1: the pixel-pair form of the same block (netvlad_pair.hip; D2FE_NV_PAIR=0: nv_xblock_kernel / nv_block_kernel)
-            st.pblock = pb_ok; }
-        } else if (i > 0 && K(i) == D2FE_NV_DW && K(i + 1) == D2FE_NV_PW &&
-                   nv_block_supported(h->nv[i].cin, h->nv[i].cin, h->nv[i + 1].cout, h->nv[i].stride, false, 0)) {
-          st.fused = true; st.l1 = i + 1;
-        } else if (i > 0 && i == nl - 1 && K(i) == D2FE_NV_PW && h->nv[i].res < 0 &&
-                   (nv_tail_supported(h->nv[i].cin, w->proj_dim) || nv_block_supported(h->nv[i].cin, h->nv[i].cout, w->proj_dim, 1, true, 2))) {
-          st.fused = true; st.tail = true; st.expand = true;        // last 1x1 of the trunk + the NetVLAD pre-projection in one launch
-        }
-        // a residual must read a tensor that exists in HBM: the output of an earlier step
-        if (st.fused && !st.tail && h->nv[st.l1].res >= 0 && !materialised[h->nv[st.l1].res]) { st = d2fe_context::NvStep(); st.l0 = st.l1 = i; }
-      }
-      if (!st.fused && h->nv[i].res >= 0 && !materialised[h->nv[i].res])
-        return fail(D2FE_ERR_UNSUPPORTED, "netvlad layer " + std::to_string(i) + ": residual source is internal to a fused block");
-      if (st.fused) {
-        int li = st.l0 + (st.front ? 1 : 0);
-        if (st.front) {
-          std::vector<float> pk(384);
-          pack_nv_conv0(w->layers[st.l0].weight, w->layers[st.l0].bias, w->layers[st.l0].cout, pk.data());
-          const int rc = upload(pk.data(), pk.size() * sizeof(float), reinterpret_cast<void**>(&st.w0));
-          if (rc) { h->nv_plan.push_back(st); return rc; }
-        }
-        if (st.expand) {
-          const d2fe_nv_layer& E = w->layers[li++];
-          std::vector<float> pk(pack_nv_expand_floats(E.cout, E.cin));
-          if (st.tail && nv_tail_supported(E.cin, w->proj_dim)) pack_nv_expand_tail(E.weight, E.bias, E.cout, E.cin, pk.data());
-          else if (st.pblock) { pk.assign(pack_nv_expand_pair_floats(E.cout, E.cin), 0.f); pack_nv_expand_pair(E.weight, E.bias, E.cout, E.cin, pk.data()); }
-          else if (st.xblock) { pk.assign(pack_nv_expand_perm_floats(E.cout, E.cin), 0.f); pack_nv_expand_perm(E.weight, E.bias, E.cout, E.cin, pk.data()); }
-          else pack_nv_expand(E.weight, E.bias, E.cout, E.cin, pk.data());
-          const int rc = upload(pk.data(), pk.size() * sizeof(float), reinterpret_cast<void**>(&st.we));
-          if (rc) { h->nv_plan.push_back(st); return rc; }
-        }
-        // depthwise + project record: the block's dw 3x3 and last 1x1, or (tail) no dw and the NetVLAD pre-projection [proj_dim][feat_dim]
-        const float* pwt = st.tail ? w->pre_w : w->layers[li + 1].weight;
-        const float* pbs = st.tail ? w->pre_b : w->layers[li + 1].bias;
-        const int pco = st.tail ? w->proj_dim : w->layers[li + 1].cout, pci = st.tail ? w->feat_dim : w->layers[li + 1].cin;
-        // pixel-pair kernels: any n-tile count up to 8 per launch, wider outputs as two channel halves (each with its own project record and bias)
-        const int halves = st.pblock ? nv_pblock_halves(pco) : 1, pco0 = st.pblock ? nv_pblock_half_cout(pco, 0) : pco;
-        const int nt = st.pblock ? nv_pblock_ntiles(pco0) : nv_block_ntiles(pco);
-        std::vector<float> pk(st.pblock ? pack_nv_dwproj_pair_floats(pci, nt) : pack_nv_dwproj_floats(pci, nt)), pb(nt * 16, 0.f);
-        if (st.pblock) pack_nv_dwproj_pair(w->layers[li].weight, w->layers[li].bias, pwt, pco0, pci, nt, pk.data(), 0);
-        else if (st.tail && nv_tail_supported(w->layers[st.l0].cin, w->proj_dim)) pack_nv_proj_t(pwt, pco, pci, nt, pk.data());
-        else if (st.xblock && !st.tail) pack_nv_dwproj_x(w->layers[li].weight, w->layers[li].bias, pwt, pco, pci, nt, pk.data());
-        else pack_nv_dwproj(st.tail ? nullptr : w->layers[li].weight, st.tail ? nullptr : w->layers[li].bias, pwt, pco, pci, nt, pk.data());
-        for (int co = 0; co < pco0; ++co) pb[co] = pbs[co];
-        h->nv_plan.push_back(st);
-        auto& ds = h->nv_plan.back();
-        int rc = upload(pk.data(), pk.size() * sizeof(float), reinterpret_cast<void**>(&ds.wp));
-        rc = rc ? rc : upload(pb.data(), pb.size() * sizeof(float), reinterpret_cast<void**>(&ds.bp));
-        if (rc) return rc;
-        if (halves == 2) {
-          const int pco1 = pco - pco0, nt1 = nv_pblock_ntiles(pco1);
-          std::vector<float> pk1(pack_nv_dwproj_pair_floats(pci, nt1)), pb1(nt1 * 16, 0.f);
-          pack_nv_dwproj_pair(w->layers[li].weight, w->layers[li].bias, pwt, pco1, pci, nt1, pk1.data(), pco0);
-          for (int co = 0; co < pco1; ++co) pb1[co] = pbs[pco0 + co];
-          rc = upload(pk1.data(), pk1.size() * sizeof(float), reinterpret_cast<void**>(&ds.wp2));
-          rc = rc ? rc : upload(pb1.data(), pb1.size() * sizeof(float), reinterpret_cast<void**>(&ds.bp2));
-          if (rc) return rc;
-        }
-        if (st.tail) {
-          h->nv_feat_gmax = std::max(1, std::min(16, w->feat_dim / 32));
-        } else if (h->nv[st.l1].act == 0) {
-          // a linear bottleneck output may be written as partial slabs (hidden channels split over workgroup groups)
-          const int nchunk = h->nv[st.l1].cin / 16;
-          h->nv[st.l1].gmax = std::max(1, std::min(16, nchunk / 2));
-        }
-      } else {
-        h->nv_plan.push_back(st);
-      }
-      if (!st.tail) materialised[st.l1] = 1;
-      i = st.l1 + 1;
-    }
-    for (int li = 0; li < nl; ++li)
-      if (materialised[li]) HIP_TRY(hipMalloc(&h->nv[li].out, sizeof(float) * (size_t)h->nv[li].gmax * B * h->nv[li].oh * h->nv[li].ow * h->nv[li].cout));
-  }
-  if (cprev != w->feat_dim) return fail(D2FE_ERR_INVALID, "feat_dim does not match the last layer");
-  h->nv_feat = w->feat_dim; h->nv_proj = w->proj_dim; h->nv_k = w->n_clusters;
-  const int pp = (w->proj_dim + 31) / 32 * 32;
-  if (w->feat_dim & 7) return fail(D2FE_ERR_INVALID, "feat_dim must be a multiple of 8");
-  std::vector<float> pw(packed_weight_floats_f32(pp, w->feat_dim, 1)), pb(pp, 0.f);
-  pack_weights_f32(w->pre_w, w->proj_dim, w->feat_dim, 1, pp, pw.data());
-  for (int co = 0; co < w->proj_dim; ++co) pb[co] = w->pre_b[co];
-  int rc = upload(pw.data(), pw.size() * sizeof(float), reinterpret_cast<void**>(&h->nv_pre_w));
-  rc = rc ? rc : upload(pb.data(), pb.size() * sizeof(float), reinterpret_cast<void**>(&h->nv_pre_b));
-  rc = rc ? rc : upload(w->assign_w, sizeof(float) * w->n_clusters * w->proj_dim, reinterpret_cast<void**>(&h->nv_aw));
-  if (w->n_clusters % 16 == 0 && w->proj_dim % 4 == 0) {
-    std::vector<float> ap((size_t)w->n_clusters * w->proj_dim);
-    pack_nv_assign(w->assign_w, w->n_clusters, w->proj_dim, ap.data());
-    rc = rc ? rc : upload(ap.data(), ap.size() * sizeof(float), reinterpret_cast<void**>(&h->nv_aw_pack));
-  }
-  rc = rc ? rc : upload(w->assign_b, sizeof(float) * w->n_clusters, reinterpret_cast<void**>(&h->nv_ab));
-  rc = rc ? rc : upload(w->centroids, sizeof(float) * w->n_clusters * w->proj_dim, reinterpret_cast<void**>(&h->nv_cen));
-  if (rc) return rc;
-  HIP_TRY(hipMalloc(&h->nv_feat_buf, sizeof(float) * (size_t)h->nv_feat_gmax * B * ch * cw * w->proj_dim));
-  HIP_TRY(hipMalloc(&h->nv_raw, sizeof(float) * (size_t)B * w->n_clusters * w->proj_dim));
-  HIP_TRY(hipMalloc(&h->nv_part, sizeof(float) * (size_t)B * nv_vlad_part_floats(ch * cw, w->proj_dim, w->n_clusters)));
-  if (!h->nv_s_img) HIP_TRY(hipMalloc(&h->nv_s_img, (size_t)h->cfg.max_width * h->cfg.max_height * B));
-  if (!h->nv_s_out) HIP_TRY(hipMalloc(&h->nv_s_out, sizeof(float) * 8192 * B));
-  h->nv_loaded = true;
-  guard.ok = true;
-  return D2FE_OK;
-}
-
-#ifdef D2FE_DEVTOOLS      /* development library only: include/d2fe_debug.h */
-/* diagnostics: with D2FE_NV_STAMP_STEP=<plan step> set at d2fe_load_netvlad() time, the wall_clock64() phase stamps [workgroup][32] that step's
- * nv_xblock_kernel wrote during the last d2fe_netvlad* call; returns the number of workgroups (tools/nv_stamps.py). */
-long d2fe_debug_netvlad_stamps(d2fe_handle h, unsigned long long* dst, long max_wgs) {
-  if (!h || !dst || !h->nv_stamps) return fail(D2FE_ERR_NOT_READY, "D2FE_NV_STAMP_STEP was not set when the network was loaded");
-  hipSetDevice(h->cfg.device_id);
-  const long nw = std::min<long>(max_wgs, h->nv_stamp_wgs);
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dst, h->nv_stamps, sizeof(unsigned long long) * 32 * nw, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(D2FE_ERR_HIP, "D2H");
-  return nw;
-}
-
-/* test hook: the output of layer `layer` of the loaded network for the last d2fe_netvlad* call (NHWC fp32), if the execution plan
- * materialises it (the last layer of every fused block and every unfused layer); D2FE_ERR_NOT_READY otherwise. */
-long d2fe_debug_netvlad_layer(d2fe_handle h, int layer, int n_images, void* dst, size_t max_bytes) {
-  if (!h || !dst || !h->nv_loaded || layer < 0 || layer >= (int)h->nv.size() || n_images < 1 || n_images > h->cfg.max_batch)
-    return fail(D2FE_ERR_INVALID, "bad argument");
-  const auto& l = h->nv[layer];
-  if (!l.out) return fail(D2FE_ERR_NOT_READY, "layer output lives inside a fused block");
-  // spatial size of the LAST call: the plan works for any size up to the maximum; the caller passes images of the handle's maximum size here
-  const size_t bytes = sizeof(float) * (size_t)n_images * l.oh * l.ow * l.cout;
-  if (bytes > max_bytes) return fail(D2FE_ERR_TRUNCATED, "destination too small");
-  hipSetDevice(h->cfg.device_id);
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dst, l.out, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
-  if (l.slabs > 1) {      // hidden-channel groups wrote partial slabs: the tensor is their sum (what the consumer's staging forms)
-    if ((size_t)l.slab_stride * sizeof(float) != bytes) return fail(D2FE_ERR_INVALID, "n_images differs from the last call");
-    std::vector<float> tmp(bytes / sizeof(float));
-    float* o = static_cast<float*>(dst);
-    for (int sl = 1; sl < l.slabs; ++sl) {
-      if (hipMemcpy(tmp.data(), l.out + (size_t)sl * l.slab_stride, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
-      for (size_t i = 0; i < tmp.size(); ++i) o[i] += tmp[i];
-    }
-  }
-  return (long)bytes;
-}
-
-#endif  // D2FE_DEVTOOLS
-
-int d2fe_set_netvlad_pca(d2fe_handle h, const float* comp, const float* mean, int m) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
-  if (h) graphs_clear(h);
-  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  if (!h->nv_loaded) return fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
-  const int G = h->nv_k * h->nv_proj;
-  if (m < 0 || m > 8192 || (m > 0 && (!comp || !mean)) || (G & 3)) return fail(D2FE_ERR_INVALID, "bad PCA arguments");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->nv_pca_comp) { hipFree(h->nv_pca_comp); h->nv_pca_comp = nullptr; }
-  if (h->nv_pca_mean) { hipFree(h->nv_pca_mean); h->nv_pca_mean = nullptr; }
-  h->nv_pca_m = 0;
-  if (m == 0) return D2FE_OK;
-  int rc = upload(comp, sizeof(float) * (size_t)m * G, reinterpret_cast<void**>(&h->nv_pca_comp));
-  rc = rc ? rc : upload(mean, sizeof(float) * G, reinterpret_cast<void**>(&h->nv_pca_mean));
-  if (rc) return rc;
-  h->nv_pca_m = m;
-  return D2FE_OK;
-}
-
-int d2fe_netvlad_dim(d2fe_handle h) {
-  if (!h || !h->nv_loaded) return fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
-  return h->nv_pca_m ? h->nv_pca_m : h->nv_k * h->nv_proj;
-}
-
-}  // extern "C"
-namespace d2fe {
-int nv_check(d2fe_context* h, int n, int W, int H, int stride) {
-  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  if (!h->nv_loaded) return fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
-  if (n < 1 || n > h->cfg.max_batch) return fail(D2FE_ERR_INVALID, "batch size out of range");
-  if (W < 32 || H < 32 || W > h->cfg.max_width || H > h->cfg.max_height) return fail(D2FE_ERR_INVALID, "image size out of range");
-  if (stride < W) return fail(D2FE_ERR_INVALID, "stride < width");
-  return D2FE_OK;
-}
-}  // namespace d2fe
-extern "C" {
-
-int d2fe_netvlad_device(d2fe_handle h, const uint8_t* d_gray, int n, int width, int height, int stride, size_t image_stride,
-                        float* d_out, void* stream) {
-  int rc = nv_check(h, n, width, height, stride);
-  if (rc) return rc;
-  if (!d_gray || !d_out) return fail(D2FE_ERR_INVALID, "null device pointer");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  return run_netvlad(h, d_gray, n, width, height, stride, image_stride, d_out, stream ? (hipStream_t)stream : h->stream);
-}
-
-int d2fe_netvlad_batch(d2fe_handle h, const uint8_t* gray, int n, int width, int height, int stride, size_t image_stride,
-                       float* out) {
-  int rc = nv_check(h, n, width, height, stride);
-  if (rc) return rc;
-  if (!gray || !out) return fail(D2FE_ERR_INVALID, "null pointer");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  hipStream_t s = h->stream;
-  rc = upload_frames(h, h->nv_s_img, gray, n, width, height, stride, image_stride, s);
-  if (rc) return rc;
-  rc = run_cached(h, {2, n, width, height, (long)h->nv_pca_m, 0}, s, [&](hipStream_t st) {
-    return run_netvlad(h, h->nv_s_img, n, width, height, width, (size_t)width * height, h->nv_s_out, st);
-  });
-  if (rc) return rc;
-  const int G = d2fe_netvlad_dim(h);
-  const size_t bytes = sizeof(float) * (size_t)G * n;
-  if (h->use_pinned && h->pin_out && bytes <= h->pin_out_bytes) {
-    HIP_TRY(hipMemcpyAsync(h->pin_out, h->nv_s_out, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out, h->pin_out, bytes);
-  } else {
-    HIP_TRY(hipMemcpyAsync(out, h->nv_s_out, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return D2FE_OK;
-}
-
-int d2fe_netvlad(d2fe_handle h, const uint8_t* gray, int width, int height, int stride, float* out) {
-  return d2fe_netvlad_batch(h, gray, 1, width, height, stride, (size_t)stride * height, out);
-}
-
-}  // extern "C"
 namespace d2fe {
 int clone_lane(d2fe_context* p, int max_batch, d2fe_context** out, hipStream_t stream, int ncu, bool with_netvlad) {
   *out = nullptr;
@@ -1298,28 +741,11 @@ int clone_lane(d2fe_context* p, int max_batch, d2fe_context** out, hipStream_t s
   c->sp_loaded = p->sp_loaded;
   c->pca_comp_t = p->pca_comp_t; c->pca_mean = p->pca_mean; c->pca_dims = p->pca_dims;
   c->fuse1a = p->fuse1a; c->wino_dynamic = p->wino_dynamic; c->sp_min_batch = p->sp_min_batch;
-  if (p->nv_loaded && with_netvlad) {
-    const int B = max_batch;
-    c->nv = p->nv;
-    for (auto& l : c->nv) { l.out = nullptr; l.slabs = 1; l.slab_stride = 0; }
-    c->nv_plan = p->nv_plan;
-    c->nv_feat_gmax = p->nv_feat_gmax; c->nv_blocks_target = p->nv_blocks_target; c->nv_tail_blocks = p->nv_tail_blocks; c->nv_slabsum = p->nv_slabsum; c->nv_group_rule = p->nv_group_rule; c->nv_merge = p->nv_merge;
-    c->nv_front_tpw = p->nv_front_tpw; c->nv_nbuf = p->nv_nbuf;
-    c->nv_feat = p->nv_feat; c->nv_proj = p->nv_proj; c->nv_k = p->nv_k;
-    c->nv_pre_w = p->nv_pre_w; c->nv_pre_b = p->nv_pre_b; c->nv_aw = p->nv_aw; c->nv_aw_pack = p->nv_aw_pack; c->nv_ab = p->nv_ab; c->nv_cen = p->nv_cen;
-    c->nv_pca_comp = p->nv_pca_comp; c->nv_pca_mean = p->nv_pca_mean; c->nv_pca_m = p->nv_pca_m;
-    auto alloc = [&]() -> int {
-      for (size_t li = 0; li < c->nv.size(); ++li)
-        if (p->nv[li].out) HIP_TRY(hipMalloc(&c->nv[li].out, sizeof(float) * (size_t)c->nv[li].gmax * B * c->nv[li].oh * c->nv[li].ow * c->nv[li].cout));
-      const int ch = c->nv.back().oh, cw = c->nv.back().ow;
-      HIP_TRY(hipMalloc(&c->nv_feat_buf, sizeof(float) * (size_t)c->nv_feat_gmax * B * ch * cw * c->nv_proj));
-      HIP_TRY(hipMalloc(&c->nv_raw, sizeof(float) * (size_t)B * c->nv_k * c->nv_proj));
-      HIP_TRY(hipMalloc(&c->nv_part, sizeof(float) * (size_t)B * nv_vlad_part_floats(ch * cw, c->nv_proj, c->nv_k)));
-      return D2FE_OK;       // no nv_s_img / nv_s_out: the host-pointer NetVLAD calls never run on a lane
-    };
-    rc = alloc();
+  if (p->nv_net && with_netvlad) {
+    // the network is shared; the activations are the lane's own (no nv_s_img / nv_s_out: the host-pointer NetVLAD calls never run on a lane)
+    c->nv_net = p->nv_net;
+    rc = c->nv_run.alloc(*c->nv_net, max_batch);
     if (rc) { if (stream) c->stream = nullptr; d2fe_destroy(c); return rc; }       // the stream stays the caller's
-    c->nv_loaded = true;
   }
   *out = c;
   return D2FE_OK;

@@ -8,6 +8,7 @@
 #include <array>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -40,6 +41,71 @@ enum { L_1B = 0, L_2A, L_2B, L_3A, L_3B, L_4A, L_4B, L_PADA, L_PB, L_DB, L_PA, L
 struct Tensor {
   float* p = nullptr;
   size_t per_img = 0;  // floats per image at max size
+};
+
+// ---- NetVLAD (netvlad_host.hip) ----
+// One launch form of the execution plan over the flat layer list: fused MobileNetV2 blocks (netvlad_fused.hip, netvlad_pair.hip) where the pattern
+// matches, single layers otherwise.  Only the LAST layer of a step is materialised in HBM (NvRun::out); everything inside a fused block lives in LDS
+enum class NvKind : int {
+  Conv0, Dw, Pw,              // one layer through the generic launchers (launch_nv_conv0 / launch_nv_dw / launch_nv_pw)
+  Front, Expand, Block,       // nv_block_kernel: conv0 -> dw -> pw (mode 1), pw -> dw -> pw (mode 0 with its expand stage), dw -> pw (mode 0)
+  XBlock, PBlock, FPair,      // pw -> dw -> pw: nv_xblock_kernel (input in registers), nv_pblock_kernel (pixel pairs; one launch per output-channel half);
+                              // conv0 -> dw -> pw: nv_fpair_kernel (pixel pairs)
+  Tail, TailBlock,            // the trunk's last pw + the NetVLAD pre-projection: nv_tail_kernel, nv_block_kernel mode 2
+};
+inline bool nv_fused(NvKind k) { return k != NvKind::Conv0 && k != NvKind::Dw && k != NvKind::Pw; }
+inline bool nv_is_tail(NvKind k) { return k == NvKind::Tail || k == NvKind::TailBlock; }
+
+struct NvLayer {
+  int kind, cin, cout, cout_pad, stride, act, res; int oh = 0, ow = 0;   // oh, ow: at the handle's maximum image size
+  int gmax = 1;                      // slabs the output has room for (a fused block may split its hidden channels over workgroup groups)
+  bool materialised = false;         // the last layer of a step: its output exists in HBM
+  float* w = nullptr; float* b = nullptr;      // packed weights of a layer that runs as a single step
+};
+struct NvStep {
+  NvKind kind = NvKind::Pw; int l0 = 0, l1 = 0;
+  int halves = 1;                    // PBlock: launches over output-channel halves (more than 128 output channels: 2)
+  bool one_slab_out = false;         // the consumer reads ONE plain tensor (a single step, or a kernel that reads one input slab): partial slabs are summed here
+  float* w0 = nullptr; float* we = nullptr; float* wp = nullptr; float* bp = nullptr;   // packed first-conv / expand / depthwise + project records and bias
+  float* wp2 = nullptr; float* bp2 = nullptr;                                            // PBlock in two halves: the second half's project record and bias
+};
+// schedule knobs, read when constructed: the D2FE_NV_* switches of the development library (A/B measurements, tools/README.md); the product library's
+// d2fe_dev_env returns the defaults, the measured best
+struct NvKnobs {
+  static int positive(int v, int dflt) { return v > 0 ? v : dflt; }
+  bool legacy = d2fe_dev_env("D2FE_NV_LEGACY", 0) != 0;     // one launch per layer
+  bool pair = d2fe_dev_env("D2FE_NV_PAIR", 1) != 0, xblock = d2fe_dev_env("D2FE_NV_XBLOCK", 1) != 0;     // the pixel-pair kernels, nv_xblock_kernel
+  int blocks_target = positive(d2fe_dev_env("D2FE_NV_BLOCKS", 0), 512);     // workgroups per IMAGE the hidden-channel split of a block aims at
+  int tail_blocks = positive(d2fe_dev_env("D2FE_NV_TAIL_BLOCKS", 0), 30);   // the same for the tail (3 pixel tiles x 10 groups at 15 x 20)
+  int slabsum = d2fe_dev_env("D2FE_NV_SLABSUM", 3);        // partial slabs from which they are summed once instead of by every consumer (0 = never)
+  bool group_rule = d2fe_dev_env("D2FE_NV_GROUP_RULE", 1) != 0;   // nv_groups() stops splitting where the slab-sum launch costs more than the chunks it saves
+  bool merge = d2fe_dev_env("D2FE_NV_MERGE", 1) != 0;     // a batch lets one workgroup walk a run of hidden-channel groups (NvBlockArgs::gmerge): same bits
+  int front_tpw = d2fe_dev_env("D2FE_NV_FRONT_TPW", 0), nbuf = d2fe_dev_env("D2FE_NV_NBUF", 0);      // 0: the launchers decide
+  int stamp_step = d2fe_dev_env("D2FE_NV_STAMP_STEP", -1);     // the plan step whose kernel writes phase stamps (diagnostics)
+};
+// what d2fe_load_netvlad builds: read-only while pipeline lanes share it (d2fe_load_netvlad / d2fe_set_netvlad_pca refuse while pipes are alive); owns its device memory
+struct NvNet {
+  std::vector<NvLayer> layers;
+  std::vector<NvStep> plan;
+  int feat = 0, proj = 0, k = 0, feat_gmax = 1;       // feat_gmax: slabs of the pre-projected features (input of the VLAD stage)
+  float *pre_w = nullptr, *pre_b = nullptr, *aw = nullptr, *aw_pack = nullptr, *ab = nullptr, *cen = nullptr;
+  float *pca_comp = nullptr, *pca_mean = nullptr; int pca_m = 0;
+  NvKnobs knobs;
+  NvNet() = default; NvNet(const NvNet&) = delete; NvNet& operator=(const NvNet&) = delete; ~NvNet();
+};
+// a tensor of the last call = the sum of `n` partial slabs `stride` floats apart
+struct NvSlabs { int n = 1; long stride = 0; };
+// the host-side bookkeeping a NetVLAD call leaves behind (what the next step of the call and the debug reads consult)
+struct NvLast { std::vector<NvSlabs> layer; NvSlabs feat; int stamp_wgs = 0; };
+// what one context owns to run the network: its activations and the bookkeeping of its last call
+struct NvRun {
+  std::vector<float*> out;           // [layer]: output of a materialised layer (nullptr: the layer lives inside a fused block)
+  float *feat_buf = nullptr, *raw = nullptr, *part = nullptr;
+  unsigned long long* stamps = nullptr;     // D2FE_NV_STAMP_STEP: [32768][32] phase stamps (the loading handle only)
+  NvLast last;
+  int alloc(const NvNet& net, int max_batch);
+  void release();
+  NvRun() = default; NvRun(const NvRun&) = delete; NvRun& operator=(const NvRun&) = delete; ~NvRun() { release(); }
 };
 
 }  // namespace d2fe
@@ -87,7 +153,7 @@ struct d2fe_context {
   // host-side bookkeeping a launch sequence leaves behind (what the debug reads and the next NetVLAD step consult): saved when a sequence is
   // captured, restored on every replay, so that a replay leaves the handle exactly as a direct run of the same geometry would
   struct HostState { int last_w = 0, last_h = 0, last_n = 0, last_set = 0; const uint8_t* last_gray = nullptr; int last_stride = 0; size_t last_istride = 0;
-                     std::vector<std::pair<int, long>> nv_slabs; int nv_feat_slabs = 1; long nv_feat_slab_stride = 0; int nv_stamp_wgs = 0; };
+                     d2fe::NvLast nv; };
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; bool bad = false; HostState st; };
   std::map<std::array<long, 6>, GraphEntry> graphs;
   int ncu = 256;               // compute units this context sizes its persistent grids for: the device's (d2fe_create) or a pipeline lane's share
@@ -103,31 +169,9 @@ struct d2fe_context {
   void* lk_scratch = nullptr; size_t lk_scratch_bytes = 0;   // grow-only scratch of the LK / detector entry points (lk.hip)
   float* a_samp = nullptr; float* a_cn = nullptr; int a_scap = 0;   // variant A sampling: [batch][a_scap][256] samples, [batch][256] channel norms
   float* pca_comp_t = nullptr; float* pca_mean = nullptr; int pca_dims = 0;
-  // NetVLAD
-  struct NvLayer { int kind, cin, cout, cout_pad, stride, act, res; float* w = nullptr; float* b = nullptr; float* out = nullptr; int oh = 0, ow = 0;
-                   int gmax = 1;                 // slabs `out` has room for (a fused block may split its hidden channels over workgroup groups)
-                   int slabs = 1; long slab_stride = 0; };   // of the last call: out = sum of `slabs` partial tensors `slab_stride` floats apart
-  std::vector<NvLayer> nv;
-  // execution plan over the flat layer list: fused MobileNetV2 blocks (netvlad_fused.hip) where the pattern matches, single layers otherwise;
-  // only the LAST layer of a step is materialised in HBM (NvLayer::out), everything inside a fused block lives in LDS
-  struct NvStep { int l0 = 0, l1 = 0; bool fused = false, expand = false, front = false, tail = false, xblock = false, pblock = false; float* we = nullptr; float* wp = nullptr; float* bp = nullptr; float* w0 = nullptr;
-                  float* wp2 = nullptr; float* bp2 = nullptr; };      // pblock with more than 128 output channels: the second channel half's project record / bias (netvlad_pair.hip)
-  int nv_feat_gmax = 1, nv_feat_slabs = 1; long nv_feat_slab_stride = 0;
-  // scheduling knobs of the fused plan, read from the environment by d2fe_load_netvlad (A/B measurements; defaults measured best):
-  // workgroups per launch the hidden-channel split aims at (D2FE_NV_BLOCKS), the same for the tail kernel (D2FE_NV_TAIL_BLOCKS),
-  // and the number of partial slabs from which they are summed once instead of by every consumer (D2FE_NV_SLABSUM, 0 = never)
-  int nv_front_tpw = 0, nv_nbuf = 0;       // D2FE_NV_FRONT_TPW, D2FE_NV_NBUF (0: the launchers decide)
-  int nv_stamp_step = -1; unsigned long long* nv_stamps = nullptr; int nv_stamp_wgs = 0;     // D2FE_NV_STAMP_STEP (diagnostics)
-  int nv_blocks_target = 512, nv_tail_blocks = 30, nv_slabsum = 3;      // workgroups per IMAGE the hidden-channel split aims at (blocks; tail: 3 pixel tiles x 10 groups at 15 x 20)
-       // the pre-projected features (input of the VLAD stage), same slab scheme
-  std::vector<NvStep> nv_plan;
-  bool nv_loaded = false;
-  int nv_feat = 0, nv_proj = 0, nv_k = 0;
-  float *nv_pre_w = nullptr, *nv_pre_b = nullptr, *nv_aw = nullptr, *nv_aw_pack = nullptr, *nv_ab = nullptr, *nv_cen = nullptr;
-  float *nv_feat_buf = nullptr, *nv_raw = nullptr, *nv_pca_out = nullptr, *nv_part = nullptr;
-  bool nv_group_rule = true;       // nv_groups(): no split past two groups when the slab-sum launch costs more than the chunks it saves (D2FE_NV_GROUP_RULE=0, development library: off)
-  bool nv_merge = true;            // a batch lets one workgroup walk a run of hidden-channel groups (NvBlockArgs::gmerge; D2FE_NV_MERGE=0, development library: never) -- same bits either way
-  float *nv_pca_comp = nullptr, *nv_pca_mean = nullptr; int nv_pca_m = 0;
+  // NetVLAD: the network (shared with the pipeline lanes), this context's buffers and the host-pointer staging of d2fe_netvlad(_batch)
+  std::shared_ptr<d2fe::NvNet> nv_net;
+  d2fe::NvRun nv_run;
   uint8_t* nv_s_img = nullptr; float* nv_s_out = nullptr;
   bool fuse1a = true;      // conv1a fused into conv1b's staging (D2FE_FUSE1A=0 keeps the stand-alone conv1a kernel)
   // host-pointer matcher: pool of (stream, scratch) slots so that concurrent callers (the reference calls matchKNN from three
@@ -148,7 +192,7 @@ struct d2fe_context {
 
 
 namespace d2fe {
-// launch sequences (api.hip).  run_superpoint == one TensorRT executeV2 + processOutput of the reference; run_netvlad == one
+// launch sequences (api.hip, netvlad_host.hip).  run_superpoint == one TensorRT executeV2 + processOutput of the reference; run_netvlad == one
 // MobileNetVLADONNX::inference.  Both only enqueue work on the given stream(s)
 int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_kps, float* d_scores,
                    float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s, hipStream_t s_tail = nullptr, int bs = 0);
@@ -165,4 +209,63 @@ int clone_lane(d2fe_context* parent, int max_batch, d2fe_context** out, hipStrea
 // a new non-blocking stream that does NOT take turns with `beside` on the device (pipe.hip: the same measurement as d2fe_pipe_create's stream placement, on up to four
 // candidates; the first candidate if none can be told apart).  hipSuccess or the failing call's error
 hipError_t create_stream_beside(int device_id, hipStream_t beside, hipStream_t* out);
+// helpers of the entry points (api.hip) that netvlad_host.hip shares
+int fail(int code, const std::string& msg);      // records d2fe_last_error(), returns `code`
+int upload(const void* src, size_t bytes, void** dst);
+// host image(s) -> the handle's device staging, tight rows: through the pinned staging buffer (CPU row copy + ONE DMA) or, when that
+// is off, with pageable 2D copies
+int upload_frames(d2fe_context* h, uint8_t* d_dst, const uint8_t* gray, int n, int width, int height, int stride, size_t image_stride, hipStream_t s);
+// weights / PCA matrices were (re)loaded: the captured launch sequences hold the old device pointers
+void graphs_clear(d2fe_context* h);
+void host_state_save(const d2fe_context* h, d2fe_context::HostState& st);
+void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool netvlad);
+
+struct ProfScope {
+  d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
+  ProfScope(d2fe_context* h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {
+    on = h->prof_mode == 2 || (h->prof_mode == 1 && (stage == D2FE_PROF_CONV1B || stage == D2FE_PROF_NETVLAD));
+    if (!on) return;
+    if (h->prof_used + 2 > h->prof_pool.size()) {
+      for (int i = 0; i < 64; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { on = false; return; } h->prof_pool.push_back(e); }
+    }
+    a = h->prof_pool[h->prof_used++]; b = h->prof_pool[h->prof_used++];
+    (void)hipEventRecord(a, s);
+  }
+  ~ProfScope() {
+    if (!on) return;
+    (void)hipEventRecord(b, s);
+    h->prof_recs.push_back({stage, a, b});
+  }
+};
+
+// Runs `fn(s)` -- a launch sequence on `s` whose arguments are a pure function of `key` (handle-owned buffers only) -- directly the
+// first time a key is seen (module loads, function attributes, lazy allocations happen there), captures it into a hipGraph the second
+// time and replays the instantiated graph from then on.  Anything that cannot be captured marks the key bad and runs directly.
+template <class F>
+int run_cached(d2fe_context* h, const std::array<long, 6>& key, hipStream_t s, F&& fn) {
+  if (!h->use_graphs || h->prof_mode != 0) return fn(s);
+  auto& e = h->graphs[key];
+  if (e.bad) return fn(s);
+  const bool netvlad = key[0] != 1;       // key[0]: 1 = the SuperPoint sequence, 2 / 3 = NetVLAD (own frames / the frames SuperPoint reads)
+  if (e.exec) { HIP_TRY(hipGraphLaunch(e.exec, s)); host_state_restore(h, e.st, netvlad); return D2FE_OK; }
+  if (e.seen++ < 1) return fn(s);
+  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); e.bad = true; return fn(s); }
+  const int rc = fn(s);
+  hipGraph_t g = nullptr;
+  const hipError_t er = hipStreamEndCapture(s, &g);
+  if (rc != D2FE_OK || er != hipSuccess || !g) {
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipGetLastError();
+    e.bad = true;
+    return rc != D2FE_OK ? rc : fn(s);
+  }
+  hipGraphExec_t ex = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ei != hipSuccess || !ex) { (void)hipGetLastError(); e.bad = true; return fn(s); }
+  e.exec = ex;
+  host_state_save(h, e.st);               // fn(s) ran its host code during the capture: this is the state a direct run leaves
+  HIP_TRY(hipGraphLaunch(e.exec, s));
+  return D2FE_OK;
+}
 }  // namespace d2fe

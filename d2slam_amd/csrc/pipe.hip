@@ -379,7 +379,7 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(d2fe_pipe_config)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_config size mismatch");
   if (!h->sp_loaded) return pipe_fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
-  if (cfg->netvlad && !h->nv_loaded) return pipe_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
+  if (cfg->netvlad && !h->nv_net) return pipe_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
   if (cfg->lanes < 1 || cfg->lanes > 16 || cfg->frames < 1 || cfg->frames > 4096) return pipe_fail(D2FE_ERR_INVALID, "lanes must be 1..16, frames >= 1");
   const int C = cfg->coalesce > 0 ? cfg->coalesce : 1;
   if (C > 16 || (C > 1 && cfg->frames != 1)) return pipe_fail(D2FE_ERR_INVALID, "coalesce must be 1..16 and needs frames == 1");

@@ -24,6 +24,12 @@ D2FE_API long d2fe_debug_netvlad_layer(d2fe_handle h, int layer, int n_images, v
  * wall_clock64() phase stamps [workgroup][32] (100 MHz ticks) that step's block kernel wrote during the last d2fe_netvlad* call.  Returns the number
  * of workgroups copied (<= max_wgs) or <0. */
 D2FE_API long d2fe_debug_netvlad_stamps(d2fe_handle h, unsigned long long* dst, long max_wgs);
+/* The execution plan d2fe_load_netvlad builds for this layer list and proj_dim under the D2FE_NV_* switches of the environment (needs no GPU; weights may
+ * be NULL).  Writes (kind, first layer, last layer, halves) for each step, at most max_steps, and returns the number of steps or <0.  Kinds: 0 / 1 / 2 one
+ * conv / dw / pw layer through the generic launchers, 3 conv -> dw -> pw (nv_block_kernel), 4 pw -> dw -> pw (nv_block_kernel), 5 dw -> pw (nv_block_kernel),
+ * 6 nv_xblock_kernel, 7 nv_pblock_kernel (`halves` launches), 8 nv_fpair_kernel, 9 the last pw + the pre-projection (nv_tail_kernel), 10 the same
+ * through nv_block_kernel. */
+D2FE_API int d2fe_debug_netvlad_plan(const d2fe_nv_layer* layers, int n_layers, int proj_dim, int* out, int max_steps);
 /* One 3x3 / pad 1 layer (cin 64 or 128, ReLU, optional 2x2 max-pool) through the Winograd kernels of D2FE_PREC_F32_WINO, host
  * NHWC buffers in and out; iters > 0 also times `iters` back-to-back launches (HIP events on the handle's stream).  For the
  * layer-level parity tests (tests/test_wino.py) and tools/; the product path is d2fe_superpoint_extract*. */

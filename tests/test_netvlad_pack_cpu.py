@@ -193,3 +193,52 @@ def test_tile_shapes_respect_the_kernels_limits(lib):
             assert th.value * tw.value <= 128
             assert ((th.value - 1) * s_ + 3) * ((tw.value - 1) * s_ + 3) <= (192 if s_ == 1 else 576)
     assert lib.d2fe_debug_netvlad_tile(7, 10, 10, 1, C.byref(th), C.byref(tw)) < 0
+
+
+# plan step kinds of d2fe_debug_netvlad_plan (include/d2fe_debug.h)
+CONV0, DW, PW, FRONT, EXPAND, BLOCK, XBLOCK, PBLOCK, FPAIR, TAIL, TAIL_BLOCK = range(11)
+
+
+def _plan(lib, depth_multiplier):
+    from d2slam_amd import netvlad
+    from d2slam_amd.api import _NvLayer
+    arch = netvlad.mobilenetvlad_arch(depth_multiplier)
+    kinds = {"conv": 0, "pw": 1, "dw": 2}
+    layers = (_NvLayer * len(arch))(*[_NvLayer(kinds[l["kind"]], l["cin"], l["cout"], l["stride"], l["act"], l["res"], None, None) for l in arch])
+    out = (C.c_int * (4 * 64))()
+    n = lib.d2fe_debug_netvlad_plan(layers, len(arch), netvlad.NETVLAD_D, out, 64)
+    assert 0 < n <= 64, n
+    steps = [tuple(out[4 * i:4 * i + 4]) for i in range(n)]
+    # the steps cover the layer list in order, each layer exactly once
+    assert [s[1] for s in steps] == [0] + [s[2] + 1 for s in steps[:-1]] and steps[-1][2] == len(arch) - 1
+    return [(s[0], s[3]) for s in steps], arch
+
+
+def test_netvlad_execution_plan(lib, monkeypatch):
+    """The execution plan of the stand-in trunk (d2fe_load_netvlad; DESIGN.md, NetVLAD row): at 0.75 the first block as nv_fpair_kernel, the stride-1 blocks as
+    nv_pblock_kernel (13 launches: 120 -> 720 -> 240 in two channel halves), three nv_xblock_kernel stride-2 blocks, the stride-2 block 72 -> 432 -> 120 as
+    three single layers and the tail kernel.  The development library's D2FE_NV_LEGACY / D2FE_NV_PAIR / D2FE_NV_XBLOCK switches change the plan."""
+    for k in ("D2FE_NV_LEGACY", "D2FE_NV_PAIR", "D2FE_NV_XBLOCK"):
+        monkeypatch.delenv(k, raising=False)
+    X, P = (XBLOCK, 1), (PBLOCK, 1)
+    plan, _ = _plan(lib, 0.75)
+    assert plan == [(FPAIR, 1), X, P, X, P, P, X, P, P, P, P, P, P, (PW, 1), (DW, 1), (PW, 1), P, P, (PBLOCK, 2), (TAIL, 1)]
+    assert sum(h for k, h in plan if k == PBLOCK) == 13
+    plan, _ = _plan(lib, 0.35)
+    assert plan == [(FPAIR, 1), X, P, X, P, P, X, P, P, P, P, P, P, X, P, P, P, (TAIL, 1)]
+    monkeypatch.setenv("D2FE_NV_LEGACY", "1")          # one launch per layer
+    for dm in (0.75, 0.35):
+        plan, arch = _plan(lib, dm)
+        assert plan == [({"conv": CONV0, "dw": DW, "pw": PW}[l["kind"]], 1) for l in arch]
+    monkeypatch.delenv("D2FE_NV_LEGACY")
+    monkeypatch.setenv("D2FE_NV_PAIR", "0")            # no pixel-pair kernels: nv_xblock_kernel where it applies, nv_block_kernel elsewhere
+    plan, _ = _plan(lib, 0.35)
+    assert plan == [(FRONT, 1)] + [(XBLOCK, 1)] * 16 + [(TAIL, 1)]
+    plan, _ = _plan(lib, 0.75)
+    assert not any(k in (PBLOCK, FPAIR) for k, _ in plan) and (XBLOCK, 1) in plan and (TAIL, 1) == plan[-1]
+    monkeypatch.setenv("D2FE_NV_XBLOCK", "0")
+    plan, _ = _plan(lib, 0.35)
+    assert plan == [(FRONT, 1)] + [(EXPAND, 1)] * 16 + [(TAIL, 1)]
+    monkeypatch.delenv("D2FE_NV_PAIR")
+    plan, _ = _plan(lib, 0.75)                         # pixel-pair kernels on, nv_xblock_kernel off: the stride-2 blocks on nv_block_kernel
+    assert plan == [(FPAIR, 1), (EXPAND, 1), P, (EXPAND, 1), P, P, (EXPAND, 1), P, P, P, P, P, P, (PW, 1), (DW, 1), (PW, 1), P, P, (PBLOCK, 2), (TAIL, 1)]
