@@ -106,6 +106,33 @@ class _PipeDeviceResult(C.Structure):
                 ("d_kps_xy", C.c_void_p), ("d_scores", C.c_void_p), ("d_desc", C.c_void_p), ("d_n_kp", C.c_void_p), ("d_netvlad", C.c_void_p)]
 
 
+class _QuadPipeConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("lanes", C.c_int32), ("quads", C.c_int32), ("raw_width", C.c_int32), ("raw_height", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("cap", C.c_int32), ("netvlad", C.c_int32), ("match_neighbour", C.c_int32),
+                ("match_prev", C.c_int32), ("pinned_input", C.c_int32), ("ratio", C.c_double), ("radius_neighbour", C.c_double),
+                ("radius_prev", C.c_double), ("undistort_fov", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class _QuadMaps(C.Structure):
+    _fields_ = [("mapx", C.c_void_p * 4), ("mapy", C.c_void_p * 4), ("gain", C.c_void_p * 4), ("device", C.c_int32)]
+
+
+class _QuadPipeResult(C.Structure):
+    _fields_ = [("quads", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
+                ("kps_xy", C.c_void_p), ("scores", C.c_void_p), ("desc", C.c_void_p), ("n_kp", C.c_void_p), ("netvlad", C.c_void_p),
+                ("nb_q", C.c_void_p), ("nb_t", C.c_void_p), ("nb_dist", C.c_void_p), ("nb_n", C.c_void_p),
+                ("prev_q", C.c_void_p), ("prev_t", C.c_void_p), ("prev_dist", C.c_void_p), ("prev_n", C.c_void_p)]
+
+
+def _quad_maps(maps, device):
+    """d2fe_quad_maps from four (mapx, mapy, gain or None) raw addresses"""
+    m = _QuadMaps()
+    for c, (mx, my, g) in enumerate(maps):
+        m.mapx[c], m.mapy[c], m.gain[c] = mx, my, g
+    m.device = int(bool(device))
+    return m
+
+
 _lib = None
 _dev_lib = None
 
@@ -124,6 +151,8 @@ EXPORTS = [
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
+    "d2fe_quad_pipe_default_config", "d2fe_quad_pipe_create", "d2fe_quad_pipe_destroy", "d2fe_quad_pipe_submit", "d2fe_quad_pipe_wait",
+    "d2fe_quad_pipe_lanes", "d2fe_quad_pipe_geometry", "d2fe_quad_undistort_device",
     "d2fe_exchange_default_config", "d2fe_exchange_create", "d2fe_exchange_destroy", "d2fe_exchange_enqueue", "d2fe_exchange_collect", "d2fe_exchange_pairs",
     "d2fe_exchange_block_bytes", "d2fe_exchange_stream", "d2fe_rccl_load", "d2fe_rccl_path", "d2fe_rccl_unique_id", "d2fe_rccl_comm_init_rank", "d2fe_rccl_comm_destroy"]
 # the development library (lib/libd2fe_hip_dev.so, include/d2fe_debug.h) exports these on top: test hooks and kernel diagnostics
@@ -274,6 +303,15 @@ def _open_library(path, dev):
         lib.d2fe_pipe_lane_stream.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_handle.argtypes = [C.c_void_p]; lib.d2fe_pipe_handle.restype = C.c_void_p
+        lib.d2fe_quad_pipe_default_config.argtypes = [C.c_void_p]; lib.d2fe_quad_pipe_default_config.restype = None
+        lib.d2fe_quad_pipe_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_pipe_destroy.argtypes = [C.c_void_p]; lib.d2fe_quad_pipe_destroy.restype = None
+        lib.d2fe_quad_pipe_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.d2fe_quad_pipe_wait.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_quad_pipe_lanes.argtypes = [C.c_void_p]
+        lib.d2fe_quad_pipe_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_undistort_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.d2fe_exchange_default_config.argtypes = [C.c_void_p]; lib.d2fe_exchange_default_config.restype = None
         lib.d2fe_exchange_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_exchange_destroy.argtypes = [C.c_void_p]; lib.d2fe_exchange_destroy.restype = None
@@ -597,6 +635,16 @@ class FrontEnd:
         _check(self._lib.d2fe_undistort_device(self._h, d_src, n, sw, sh, sstride or sw, src_image_stride if src_image_stride is not None else sw * sh,
                                                d_mapx, d_mapy, d_gain, dw, dh, d_dst, stream))
 
+    def quad_undistort_device(self, d_raw, quads, sw, sh, maps, dw, dh, d_dst, stream=None, sstride=None, camera_stride=None, quad_stride=None):
+        """The quad pipe's undistort step on its own (d2fe_quad_undistort_device): 4 cameras x quads raw frames in ONE launch.  maps: per camera
+        (d_mapx, d_mapy, d_gain or None), raw device addresses, 16-byte aligned; view (q, c) is written to d_dst + (q * 4 + c) * dw * dh."""
+        st = int(sstride or sw)
+        cs = int(camera_stride if camera_stride is not None else st * sh)
+        qs = int(quad_stride if quad_stride is not None else 4 * cs)
+        m = _quad_maps(maps, True)
+        _check(self._lib.d2fe_quad_undistort_device(self._h, C.c_void_p(d_raw), int(quads), int(sw), int(sh), st, cs, qs, C.byref(m), int(dw), int(dh),
+                                                    C.c_void_p(d_dst), C.c_void_p(stream or 0)))
+
     def prepare_gray(self, img, width, height):
         """cv::cvtColor(BGR2GRAY) if 3 channels + cv::resize to (width, height) if the size differs (superpoint_onnx.cpp:76-83)."""
         img = np.ascontiguousarray(img, np.uint8)
@@ -860,6 +908,105 @@ class StereoPipe:
         for k in ("lr", "prev"):
             out[k + "_q"] = view(getattr(r, k + "_q"), (F, cap), np.int32); out[k + "_t"] = view(getattr(r, k + "_t"), (F, cap), np.int32)
             out[k + "_dist"] = view(getattr(r, k + "_dist"), (F, cap), np.float32); out[k + "_n"] = view(getattr(r, k + "_n"), (F,), np.int32)
+        return out
+
+
+def _pinned_view(ptr, shape, dt):
+    if not ptr:
+        return None
+    n = int(np.prod(shape))
+    buf = (C.c_float * n).from_address(ptr) if dt == np.float32 else (C.c_int32 * n).from_address(ptr)
+    return np.frombuffer(buf, dtype=dt).reshape(shape)
+
+
+class QuadPipe:
+    """Quadcam frames in flight (include/d2fe.h, d2fe_quad_pipe_*): per submit `quads` quad frames of four raw fisheye frames -> ONE undistort launch ->
+    SuperPoint and NetVLAD of every view -> the four neighbour pairs (0,1) (1,2) (2,3) (0,3) and the temporal pairs, with up to `lanes` submits in flight.
+    maps: per camera (mapx, mapy, gain or None) as [height][width] float32 numpy arrays or device tensors (anything with .data_ptr()); the pipe copies them.
+    submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits).
+    Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit)."""
+
+    def __init__(self, fe: FrontEnd, maps, lanes=4, quads=1, raw_width=1280, raw_height=800, width=800, height=400, cap=None, netvlad=True,
+                 match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False):
+        self._lib = fe._lib
+        self._fe = fe           # the pipe borrows the handle's weights
+        c = _QuadPipeConfig()
+        self._lib.d2fe_quad_pipe_default_config(C.byref(c))
+        c.lanes, c.quads, c.raw_width, c.raw_height, c.width, c.height = int(lanes), int(quads), int(raw_width), int(raw_height), int(width), int(height)
+        c.cap = int(cap or fe.cfg.max_keypoints)
+        c.netvlad, c.match_neighbour, c.match_prev, c.pinned_input = int(bool(netvlad)), int(bool(match_neighbour)), int(bool(match_prev)), int(bool(pinned_input))
+        c.ratio = float(ratio)
+        c.radius_neighbour = float(0.2 * width if radius_neighbour is None else radius_neighbour)      # search_local_max_dist_lr * width
+        c.radius_prev, c.undistort_fov = float(radius_prev), float(undistort_fov)
+        device = all(hasattr(m, "data_ptr") for mm in maps for m in mm if m is not None)
+        keep = []
+
+        def addr(a):
+            if a is None:
+                return None
+            if device:
+                return int(a.data_ptr())
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != width * height:
+                raise ValueError("QuadPipe: every map must hold width * height floats")
+            keep.append(a)
+            return a.ctypes.data
+        m = _quad_maps([tuple(addr(a) for a in mm) for mm in maps], device)
+        self._p = C.c_void_p()
+        _check(self._lib.d2fe_quad_pipe_create(fe.handle, C.byref(c), C.byref(m), C.byref(self._p)))
+        if not hasattr(fe, "_pipes"):
+            import weakref
+            fe._pipes = weakref.WeakSet()
+        fe._pipes.add(self)
+        self.lanes, self.quads, self.raw_width, self.raw_height = int(lanes), int(quads), int(raw_width), int(raw_height)
+        self._pinned_input = bool(pinned_input)
+        self._res = _QuadPipeResult()
+
+    def close(self):
+        if getattr(self, "_p", None) and self._p.value:
+            self._lib.d2fe_quad_pipe_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def submit_ptr(self, raw_ptr, stride=None, camera_stride=None, quad_stride=None):
+        """raw host address (e.g. of a pinned torch tensor); image (q, c) at raw_ptr + q * quad_stride + c * camera_stride"""
+        t = C.c_int64()
+        st = int(stride or self.raw_width)
+        cs = int(camera_stride if camera_stride is not None else st * self.raw_height)
+        qs = int(quad_stride if quad_stride is not None else 4 * cs)
+        _check(self._lib.d2fe_quad_pipe_submit(self._p, C.c_void_p(raw_ptr), st, cs, qs, C.byref(t)))
+        return int(t.value)
+
+    def submit(self, raw):
+        """raw: u8 [quads][4][raw_height][raw_width].  The library copies the frames into its pinned staging before this returns (pinned_input = 0);
+        a pipe with pinned_input=True takes page-locked memory that outlives the ticket: use submit_ptr."""
+        if self._pinned_input:
+            raise ValueError("QuadPipe(pinned_input=True): submit() takes numpy arrays, which are neither page-locked nor kept alive until wait(); use submit_ptr()")
+        raw = np.ascontiguousarray(raw, np.uint8)
+        if raw.shape != (self.quads, 4, self.raw_height, self.raw_width):
+            raise ValueError("QuadPipe.submit: expected [%d][4][%d][%d] u8, got %s" % (self.quads, self.raw_height, self.raw_width, raw.shape))
+        return self.submit_ptr(raw.ctypes.data)
+
+    def wait_raw(self, ticket):
+        _check(self._lib.d2fe_quad_pipe_wait(self._p, C.c_int64(ticket), C.byref(self._res)))
+        return self._res
+
+    def wait(self, ticket):
+        """dict of numpy VIEWS into the pinned result block, quad-major: [quads][4 views]..."""
+        r = self.wait_raw(ticket)
+        Q, cap, D, G = r.quads, r.cap, r.desc_dim, r.netvlad_dim
+        f, i = np.float32, np.int32
+        out = {"kps_xy": _pinned_view(r.kps_xy, (Q, 4, cap, 2), f), "scores": _pinned_view(r.scores, (Q, 4, cap), f),
+               "desc": _pinned_view(r.desc, (Q, 4, cap, D), f), "n_kp": _pinned_view(r.n_kp, (Q, 4), i),
+               "netvlad": _pinned_view(r.netvlad, (Q, 4, G), f) if G else None}
+        for k in ("nb", "prev"):
+            out[k + "_q"] = _pinned_view(getattr(r, k + "_q"), (Q, 4, cap), i); out[k + "_t"] = _pinned_view(getattr(r, k + "_t"), (Q, 4, cap), i)
+            out[k + "_dist"] = _pinned_view(getattr(r, k + "_dist"), (Q, 4, cap), f); out[k + "_n"] = _pinned_view(getattr(r, k + "_n"), (Q, 4), i)
         return out
 
 

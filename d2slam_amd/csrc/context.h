@@ -209,6 +209,10 @@ int clone_lane(d2fe_context* parent, int max_batch, d2fe_context** out, hipStrea
 // a new non-blocking stream that does NOT take turns with `beside` on the device (pipe.hip: the same measurement as d2fe_pipe_create's stream placement, on up to four
 // candidates; the first candidate if none can be told apart).  hipSuccess or the failing call's error
 hipError_t create_stream_beside(int device_id, hipStream_t beside, hipStream_t* out);
+// n_first + n_second non-blocking streams placed by measurement (pipe.hip): a lane's own and second stream on different hardware pipes, consecutive lanes' streams
+// on different ones too -- the lanes of d2fe_pipe_create and d2fe_quad_pipe_create.  first_class / second_class / n_classes: what was measured (-1 / 0: nothing)
+int place_streams(int device_id, int n_first, int n_second, std::vector<hipStream_t>& first, std::vector<hipStream_t>& second, std::vector<int>& first_class,
+                  std::vector<int>& second_class, int* n_classes, long long* probe_ticks, double* probe_turns_us);
 // helpers of the entry points (api.hip) that netvlad_host.hip shares
 int fail(int code, const std::string& msg);      // records d2fe_last_error(), returns `code`
 int upload(const void* src, size_t bytes, void** dst);

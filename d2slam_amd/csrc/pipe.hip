@@ -117,6 +117,9 @@ double probe_pair_us(hipStream_t a, hipStream_t b, long long ticks) {       // <
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
 }
 
+}  // namespace
+
+namespace d2fe {
 // n_first + n_second streams out of measured classes; on any doubt (HIP error, a device that is not quiet, nothing told apart) the classes a fresh process would have
 // (hardware queues in creation order, queue i on hardware pipe i mod 4) are assumed instead and *n_classes = 0 says so
 int place_streams(int device_id, int n_first, int n_second, std::vector<hipStream_t>& first, std::vector<hipStream_t>& second, std::vector<int>& first_class,
@@ -210,6 +213,9 @@ int place_streams(int device_id, int n_first, int n_second, std::vector<hipStrea
   for (size_t c = 0; c < cand.size(); ++c) if (!keep[c]) (void)hipStreamDestroy(cand[c]);
   return D2FE_OK;
 }
+}  // namespace d2fe
+
+namespace {
 
 int lane_sync(d2fe_pipe_s::Lane& L) {       // called with the pipe's mutex held for the whole wait
   if (L.synced < L.rec) {

@@ -1,0 +1,511 @@
+// quad_pipe.hip -- quadcam frames in flight: d2fe_quad_pipe_* of include/d2fe.h (BASELINE configs[2], FOURCORNER_FISHEYE).
+//
+// The quadcam per-frame work that d2slam_amd/quadcam.py's QuadcamChain sequences from Python (four undistort launches, torch.index_select of the pair
+// counts, a torch copy of the previous views, two matcher launches, one stream, one step at a time) as the stereo pipe's lanes (pipe.hip).  A submit =
+// Q quad frames = one pass on lane P % K, on the lane's own streams:
+//     ONE H2D of the 4 Q raw frames -> quad_undistort_kernel (4 cameras x Q frames in ONE launch, quad-major views) -> [NetVLAD of the 4 Q views on the
+//     lane's second stream] -> SuperPoint of the 4 Q views -> half_compact_kernel over the 8 Q neighbour jobs -> ONE matcher launch over the 4 Q neighbour
+//     pairs and the 4 Q temporal pairs (pair tables per lane and result block: the temporal pairs of quad frame 0 read the previous pass's block in place)
+//     -> remap_matches_kernel of the neighbour pairs -> ONE D2H of the result block into pinned memory.
+// Only the undistort launch is new device code; extraction, NetVLAD, compaction, matcher and remap are the kernels the single calls launch.  Result blocks,
+// tickets and their lifetime are the stereo pipe's with one submit per pass: two blocks per lane, a ticket's block is written again 2 K passes later.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "context.h"
+
+using namespace d2fe;
+
+namespace {
+
+// ---- the undistort step: 4 cameras x Q raw frames in ONE launch ---------------------------------------------------------------------------------------
+// undistort_kernel (next.hip) is one pixel per thread and one launch per camera, and every image of a launch re-reads the 12 B/pixel of map and gain.  Here
+// a workgroup owns a tile of QU_TILE pixels of ONE camera's maps, loads mapx / mapy / gain once (16 B per lane and array) and writes that tile of every quad
+// frame of the pass, 4 output bytes per lane and frame.  The arithmetic is undistort_kernel's operation for operation (the same bilinear weights in the
+// same order, zero outside the frame, both saturate_cast roundings; the library is built with -ffp-contract=off): the same bytes, which
+// tests/test_quad_pipe.py checks against d2fe_undistort_device.  HBM bytes of a launch: the maps once (4 cameras x 8 or 12 B per pixel), the raw taps
+// (neighbouring lanes' taps share cache lines: at most the raw frames once) and 1 B per pixel and view out -- tools/bench_quad_pipe.py counts them.
+constexpr int QU_THREADS = 256, QU_PX = 4, QU_TILE = QU_THREADS * QU_PX;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct QuadUndistortArgs {
+  const uint8_t* raw; long cam_stride, quad_stride; int sh, sw, sstride;
+  const float* mapx[4]; const float* mapy[4]; const float* gain[4];      // gain[c] may be null
+  int npix, quads, vec_out;                                               // vec_out: every view starts 4-byte aligned (npix % 4 == 0, aligned dst)
+  uint8_t* dst;                                                           // view (q, c) at dst + (q * 4 + c) * npix
+};
+
+__device__ __forceinline__ unsigned qu_sat_u8(float v) {   // saturate_cast<uchar>(float): round-to-nearest-even, clamp (next.hip: sat_u8)
+  if (!(v > 0.f)) return 0u;
+  if (v >= 255.f) return 255u;
+  return (unsigned)__builtin_rintf(v);
+}
+
+// cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) of one pixel + the first rounding: undistort_kernel's expression
+__device__ __forceinline__ unsigned qu_remap(const uint8_t* __restrict__ s, int sh, int sw, int sstride, float x, float y) {
+  const int x1 = (int)__builtin_floorf(x), y1 = (int)__builtin_floorf(y), x2 = x1 + 1, y2 = y1 + 1;
+  auto S = [&](int yy, int xx) -> float {
+    return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (float)s[(size_t)yy * sstride + xx] : 0.f;
+  };
+  float out = 0.f;
+  out = out + S(y1, x1) * (((float)x2 - x) * ((float)y2 - y));
+  out = out + S(y1, x2) * ((x - (float)x1) * ((float)y2 - y));
+  out = out + S(y2, x1) * (((float)x2 - x) * (y - (float)y1));
+  out = out + S(y2, x2) * ((x - (float)x1) * (y - (float)y1));
+  return qu_sat_u8(out);
+}
+
+__global__ __launch_bounds__(QU_THREADS) void quad_undistort_kernel(QuadUndistortArgs a) {
+  const int c = blockIdx.y;
+  const int i0 = (blockIdx.x * QU_THREADS + threadIdx.x) * QU_PX;
+  if (i0 >= a.npix) return;
+  const float* __restrict__ mx = a.mapx[c];
+  const float* __restrict__ my = a.mapy[c];
+  const float* __restrict__ mg = a.gain[c];
+  const int m = min(QU_PX, a.npix - i0);
+  float x[QU_PX], y[QU_PX], g[QU_PX];
+  if (m == QU_PX) {      // the maps are 16-byte aligned (d2fe_quad_undistort_device checks; the pipe's own maps come from hipMalloc)
+    const f32x4 vx = *reinterpret_cast<const f32x4*>(mx + i0), vy = *reinterpret_cast<const f32x4*>(my + i0);
+    const f32x4 vg = mg ? *reinterpret_cast<const f32x4*>(mg + i0) : f32x4{1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+    for (int k = 0; k < QU_PX; ++k) { x[k] = vx[k]; y[k] = vy[k]; g[k] = vg[k]; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < QU_PX; ++k) {
+      x[k] = k < m ? mx[i0 + k] : 0.f; y[k] = k < m ? my[i0 + k] : 0.f; g[k] = mg && k < m ? mg[i0 + k] : 1.f;
+    }
+  }
+  for (int q = 0; q < a.quads; ++q) {
+    const uint8_t* s = a.raw + q * a.quad_stride + c * a.cam_stride;
+    uint8_t* d = a.dst + ((size_t)q * 4 + c) * a.npix + i0;
+    unsigned u[QU_PX];
+#pragma unroll
+    for (int k = 0; k < QU_PX; ++k) {
+      u[k] = qu_remap(s, a.sh, a.sw, a.sstride, x[k], y[k]);
+      if (mg) u[k] = qu_sat_u8((float)u[k] * g[k]);
+    }
+    if (m == QU_PX && a.vec_out) *reinterpret_cast<uint32_t*>(d) = u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24);
+    else for (int k = 0; k < m; ++k) d[k] = (uint8_t)u[k];
+  }
+}
+
+hipError_t launch_quad_undistort(const QuadUndistortArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(quad_undistort_kernel, dim3((a.npix + QU_TILE - 1) / QU_TILE, 4), dim3(QU_THREADS), 0, s, a);
+  return hipGetLastError();
+}
+
+constexpr int NB[4][3] = {{0, 1, 1}, {1, 2, 1}, {2, 3, 1}, {0, 3, 2}};     // quadcam.NEIGHBOURS: (view a, view b, type) 1 LEFT_RIGHT, 2 RIGHT_LEFT
+
+size_t up64(size_t w) { return (w + 63) / 64 * 64; }
+
+}  // namespace
+
+struct d2fe_quad_pipe_s {
+  d2fe_context* parent = nullptr;
+  d2fe_quad_pipe_config cfg{};
+  int K = 0, Q = 0, NI = 0, RW = 0, RH = 0, W = 0, H = 0, cap = 0, D = 256, G = 0;
+  int n_nb = 0, n_pr = 0, NP = 0;      // neighbour pairs, temporal pairs, all pairs of a pass (neighbour pairs first)
+  float move_cols = 0.f;
+  // result block (float words from its base; every array starts on a 64-word boundary); the words below d2h_words go to the host
+  size_t o_desc = 0, o_kps = 0, o_scores = 0, o_nv = 0, o_cnt = 0, o_mn = 0, o_mq = 0, o_mt = 0, o_md = 0, o_idx = 0, blk_words = 0, d2h_words = 0;
+  // lane scratch (float words): the undistorted views and the half-image jobs' pools, read only by the lane's own pass
+  size_t x_und = 0, x_jdesc = 0, x_jpts = 0, x_jmap = 0, x_jn = 0, scr_words = 0;
+  float* d_all = nullptr;              // [64 zero words | K lanes x 2 sets x block]
+  float* d_scr = nullptr;              // [K][scr_words]
+  uint8_t* d_raw_all = nullptr;        // [K][4 Q raw frames], quad-major, tight rows
+  float* d_maps = nullptr;             // [4 cameras][mapx | mapy | gain], W * H floats each
+  int32_t* d_jobs = nullptr;           // job_row [8 Q] | job_left [8 Q] | job_shift (float) [8 Q] | map_a_job [4 Q] | map_b_job [4 Q]
+  MatchPairDesc* d_pairs = nullptr;    // [K][2][NP]
+  int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;
+  QuadUndistortArgs ua{};              // everything but the lane's raw frames and views
+  struct Lane {
+    d2fe_context* ctx = nullptr;
+    hipStream_t s = nullptr, nv = nullptr;
+    hipEvent_t ev_up = nullptr, ev_nv = nullptr, ev_ext[2] = {nullptr, nullptr}, ev_done = nullptr;
+    uint8_t* d_raw = nullptr;
+    uint8_t* pin_in = nullptr;
+    float* pin_out[2] = {nullptr, nullptr};
+    long long rec = -1, synced = -1;   // the pass whose completion ev_done last recorded / the newest pass known to be complete
+  };
+  std::vector<Lane> lanes;
+  std::vector<int> first_class, second_class;
+  int n_classes = 0; long long probe_ticks = 0; double probe_turns_us = 0.0;
+  std::mutex mu;                       // submit() and wait() may come from different threads; wait() drops it while it blocks
+  long long next_ticket = 0;           // one submit = one pass: ticket == pass
+  int failed = D2FE_OK;                // sticky: the first error of an enqueue leaves a pass half-queued
+  std::string failed_msg;
+  float* block(int lane, int set) const { return d_all + 64 + ((size_t)lane * 2 + set) * blk_words; }
+  float* scratch(int lane) const { return d_scr + (size_t)lane * scr_words; }
+};
+
+namespace {
+
+int lane_sync(d2fe_quad_pipe_s::Lane& L) {       // called with the pipe's mutex held
+  if (L.synced < L.rec) {
+    HIP_TRY(hipEventSynchronize(L.ev_done));
+    L.synced = L.rec;
+  }
+  return D2FE_OK;
+}
+
+// one submit: H2D, undistort, NetVLAD beside SuperPoint, compaction, ONE matcher launch, remap, ONE D2H -- all on the lane's streams
+int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_stride, size_t quad_stride, int64_t* ticket) {
+  const long long P = p->next_ticket;
+  const int k = (int)(P % p->K), set = (int)((P / p->K) & 1);
+  auto& L = p->lanes[k];
+  // the lane's previous pass (P - K) must be complete before its input, staging and scratch are reused.  The result block this pass writes was last read
+  // by pass P - 2 K + 1 (its temporal pairs), which is complete too: the submit of pass P - K + 1 synchronised with it
+  int rc = lane_sync(L);
+  if (rc) return rc;
+  const size_t rimg = (size_t)p->RW * p->RH, img = (size_t)p->W * p->H;
+  const int Q = p->Q, NI = p->NI, W = p->W, H = p->H, RW = p->RW, RH = p->RH;
+  hipStream_t s = L.s;
+  // 1. the raw frames -> the lane's input buffer, quad-major and tight: ONE DMA unless pinned input comes in scattered images
+  const bool tight = stride == RW && cam_stride == rimg && quad_stride == 4 * rimg;
+  if (p->cfg.pinned_input) {
+    if (tight) HIP_TRY(hipMemcpyAsync(L.d_raw, raw, rimg * NI, hipMemcpyHostToDevice, s));
+    else if (cam_stride == (size_t)stride * RH && quad_stride == 4 * cam_stride)
+      HIP_TRY(hipMemcpy2DAsync(L.d_raw, RW, raw, stride, RW, (size_t)RH * NI, hipMemcpyHostToDevice, s));
+    else
+      for (int q = 0; q < Q; ++q)
+        for (int c = 0; c < 4; ++c)
+          HIP_TRY(hipMemcpy2DAsync(L.d_raw + (size_t)(q * 4 + c) * rimg, RW, raw + q * quad_stride + c * cam_stride, stride, RW, RH, hipMemcpyHostToDevice, s));
+  } else {
+    if (tight) memcpy(L.pin_in, raw, rimg * NI);
+    else
+      for (int q = 0; q < Q; ++q)
+        for (int c = 0; c < 4; ++c) {
+          const uint8_t* src = raw + q * quad_stride + c * cam_stride;
+          uint8_t* dst = L.pin_in + (size_t)(q * 4 + c) * rimg;
+          if (stride == RW) memcpy(dst, src, rimg);
+          else for (int y = 0; y < RH; ++y) memcpy(dst + (size_t)y * RW, src + (size_t)y * stride, RW);
+        }
+    HIP_TRY(hipMemcpyAsync(L.d_raw, L.pin_in, rimg * NI, hipMemcpyHostToDevice, s));
+  }
+  float* B = p->block(k, set);
+  float* X = p->scratch(k);
+  uint8_t* und = reinterpret_cast<uint8_t*>(X + p->x_und);
+  int32_t* cnt = reinterpret_cast<int32_t*>(B + p->o_cnt);
+  // 2. the 4 Q views in ONE launch
+  QuadUndistortArgs ua = p->ua;
+  ua.raw = L.d_raw; ua.dst = und;
+  HIP_TRY(launch_quad_undistort(ua, s));
+  // 3-4. SuperPoint on the lane's stream, NetVLAD beside it on the lane's second stream (the stereo pipe's netvlad_inline = 0); SuperPoint is issued first:
+  // it is the long pole of a pass
+  const bool nv = p->G > 0;
+  if (nv) HIP_TRY(hipEventRecord(L.ev_up, s));
+  rc = run_superpoint(L.ctx, und, NI, W, H, W, img, B + p->o_kps, B + p->o_scores, B + p->o_desc, reinterpret_cast<int32_t*>(B + p->o_idx), p->cap, cnt, s);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(L.ev_ext[set], s));
+  if (nv) {
+    HIP_TRY(hipStreamWaitEvent(L.nv, L.ev_up, 0));
+    rc = run_netvlad(L.ctx, und, NI, W, H, W, img, B + p->o_nv, L.nv);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(L.ev_nv, L.nv));
+  }
+  // 5. getFeatureHalfImg of both views of every neighbour pair + the a-side shift
+  const int32_t* job_row = p->d_jobs;
+  const int32_t* job_left = job_row + 8 * Q;
+  const float* job_shift = reinterpret_cast<const float*>(job_left + 8 * Q);
+  const int32_t* map_a = job_left + 16 * Q;
+  const int32_t* map_b = map_a + 4 * Q;
+  int32_t* jmap = reinterpret_cast<int32_t*>(X + p->x_jmap);
+  if (p->n_nb)
+    HIP_TRY(launch_half_compact(B + p->o_desc, B + p->o_kps, cnt, job_row, job_left, job_shift, 8 * Q, p->cap, p->D, (float)W, p->move_cols, X + p->x_jdesc,
+                                X + p->x_jpts, jmap, reinterpret_cast<int32_t*>(X + p->x_jn), s));
+  // 6. ONE matcher launch over the neighbour and the temporal pairs (the counts are read where compaction and extraction wrote them)
+  if (p->NP) {
+    if (p->n_pr && P > 0 && p->K > 1) {      // the temporal pairs of quad frame 0 read the previous pass's block: wait for ITS extraction only
+      const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+      HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_ext[pset], 0));
+    }
+    MatchArgs m{};
+    m.pairs = p->d_pairs + ((size_t)k * 2 + set) * p->NP;
+    m.npairs = p->NP; m.dim = p->D; m.max_n = p->cap; m.mode = 0; m.ratio = p->cfg.ratio; m.radius = -1.0;
+    m.q_idx = reinterpret_cast<int32_t*>(B + p->o_mq); m.t_idx = reinterpret_cast<int32_t*>(B + p->o_mt); m.dist = B + p->o_md;
+    m.n_out = reinterpret_cast<int32_t*>(B + p->o_mn);
+    match_scratch_carve(reinterpret_cast<char*>(p->d_match_scratch) + p->match_scratch_lane * k, p->NP, &m);
+    m.stats = p->parent->match_stats; m.ncu = L.ctx->ncu;
+    HIP_TRY(launch_match(m, s));
+  }
+  // 7. neighbour indices back into the full view lists, then ONE D2H
+  if (p->n_nb)
+    HIP_TRY(launch_remap_matches(reinterpret_cast<int32_t*>(B + p->o_mq), reinterpret_cast<int32_t*>(B + p->o_mt), reinterpret_cast<int32_t*>(B + p->o_mn), map_a,
+                                 map_b, jmap, p->n_nb, p->cap, p->cap, s));
+  if (nv) HIP_TRY(hipStreamWaitEvent(s, L.ev_nv, 0));
+  HIP_TRY(hipMemcpyAsync(L.pin_out[set], B, sizeof(float) * p->d2h_words, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipEventRecord(L.ev_done, s));
+  L.rec = P;
+  p->next_ticket = P + 1;
+  *ticket = P;
+  return D2FE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void d2fe_quad_pipe_default_config(d2fe_quad_pipe_config* c) {
+  memset(c, 0, sizeof(*c));
+  c->struct_size = (int32_t)sizeof(d2fe_quad_pipe_config);
+  c->lanes = 4; c->quads = 1; c->raw_width = 1280; c->raw_height = 800; c->width = 800; c->height = 400; c->cap = 100;
+  c->netvlad = 1; c->match_neighbour = 1; c->match_prev = 1; c->pinned_input = 0;
+  c->ratio = 0.8; c->radius_neighbour = 0.2 * 800; c->radius_prev = -1.0; c->undistort_fov = 200.0;
+}
+
+int d2fe_quad_undistort_device(d2fe_handle h, const uint8_t* d_raw, int quads, int sw, int sh, int sstride, size_t camera_stride, size_t quad_stride,
+                               const d2fe_quad_maps* maps, int dw, int dh, uint8_t* d_dst, void* stream) {
+  if (!h || !d_raw || !maps || !d_dst) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (!maps->device) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_undistort_device takes device maps (maps->device = 1)");
+  if (quads < 1 || sw < 1 || sh < 1 || sstride < sw || dw < 1 || dh < 1 || (long)dw * dh > (1L << 30)) return ctx_fail(D2FE_ERR_INVALID, "bad geometry");
+  QuadUndistortArgs a{};
+  for (int c = 0; c < 4; ++c) {
+    if (!maps->mapx[c] || !maps->mapy[c]) return ctx_fail(D2FE_ERR_INVALID, "maps: mapx / mapy of every camera");
+    if (((uintptr_t)maps->mapx[c] | (uintptr_t)maps->mapy[c] | (uintptr_t)maps->gain[c]) & 15) return ctx_fail(D2FE_ERR_INVALID, "maps must be 16-byte aligned");
+    a.mapx[c] = maps->mapx[c]; a.mapy[c] = maps->mapy[c]; a.gain[c] = maps->gain[c];
+  }
+  a.raw = d_raw; a.cam_stride = (long)camera_stride; a.quad_stride = (long)quad_stride; a.sh = sh; a.sw = sw; a.sstride = sstride;
+  a.npix = dw * dh; a.quads = quads; a.vec_out = (a.npix % 4 == 0 && ((uintptr_t)d_dst & 3) == 0) ? 1 : 0; a.dst = d_dst;
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  HIP_TRY(launch_quad_undistort(a, stream ? (hipStream_t)stream : h->stream));
+  return D2FE_OK;
+}
+
+int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const d2fe_quad_maps* maps, d2fe_quad_pipe* out) {
+  if (!h || !cfg || !maps || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->struct_size != (int32_t)sizeof(d2fe_quad_pipe_config)) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_pipe_config size mismatch");
+  if (!h->sp_loaded) return ctx_fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
+  if (cfg->netvlad && !h->nv_net) return ctx_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
+  if (cfg->lanes < 1 || cfg->lanes > 16 || cfg->quads < 1) return ctx_fail(D2FE_ERR_INVALID, "lanes must be 1..16, quads >= 1");
+  if (4L * cfg->quads > h->cfg.max_batch) return ctx_fail(D2FE_ERR_INVALID, "4 * quads views exceed the handle's max_batch");
+  if (h->cfg.max_keypoints < 0) return ctx_fail(D2FE_ERR_UNSUPPORTED, "keep-all handles (max_keypoints = -1) are served by the single-call entry points");
+  if (cfg->cap < 1 || cfg->cap > h->cfg.max_keypoints) return ctx_fail(D2FE_ERR_INVALID, "cap must be 1..the handle's max_keypoints");
+  if (cfg->match_neighbour && cfg->cap > 1024) return ctx_fail(D2FE_ERR_INVALID, "neighbour matching takes cap <= 1024 (the half-image compaction)");
+  if (cfg->raw_width < 1 || cfg->raw_height < 1) return ctx_fail(D2FE_ERR_INVALID, "raw frame size");
+  if (cfg->width > h->cfg.max_width || cfg->height > h->cfg.max_height) return ctx_fail(D2FE_ERR_INVALID, "view size exceeds the handle's maximum");
+  if (((long)cfg->width * cfg->height) % 4) return ctx_fail(D2FE_ERR_INVALID, "width * height must be a multiple of 4 (the maps' 16-byte loads)");
+  if (cfg->match_neighbour && !(cfg->undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "undistort_fov must be > 0");
+  for (int c = 0; c < 4; ++c)
+    if (!maps->mapx[c] || !maps->mapy[c]) return ctx_fail(D2FE_ERR_INVALID, "maps: mapx / mapy of every camera");
+  const int NI = 4 * cfg->quads;
+  int rc = check_geometry(h, NI, cfg->width, cfg->height, cfg->width, cfg->cap);
+  if (rc) return rc;
+  if (cfg->netvlad && (rc = nv_check(h, NI, cfg->width, cfg->height, cfg->width)) != D2FE_OK) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  d2fe_quad_pipe_s* p = new d2fe_quad_pipe_s();
+  p->parent = h; p->cfg = *cfg;
+  h->live_pipes.fetch_add(1);        // the stereo pipes' accounting: d2fe_quad_pipe_destroy (every failure path below goes through it) gives it back
+  p->K = cfg->lanes; p->Q = cfg->quads; p->NI = NI; p->RW = cfg->raw_width; p->RH = cfg->raw_height; p->W = cfg->width; p->H = cfg->height;
+  p->cap = cfg->cap; p->D = d2fe_desc_dim(h); p->G = cfg->netvlad ? d2fe_netvlad_dim(h) : 0;
+  p->n_nb = cfg->match_neighbour ? 4 * p->Q : 0; p->n_pr = cfg->match_prev ? 4 * p->Q : 0; p->NP = p->n_nb + p->n_pr;
+  p->move_cols = d2fe_half_move_cols(p->W, cfg->undistort_fov);
+  const size_t cap = p->cap, D = p->D, img = (size_t)p->W * p->H, NJ = 8 * (size_t)p->Q, NP = p->NP;
+  size_t o = 0;
+  p->o_desc = o; o += up64(NI * cap * D);
+  p->o_kps = o; o += up64(NI * cap * 2);
+  p->o_scores = o; o += up64(NI * cap);
+  p->o_nv = o; o += up64(NI * (size_t)p->G);
+  p->o_cnt = o; o += up64(NI);
+  p->o_mn = o; o += up64(NP);
+  p->o_mq = o; o += up64(NP * cap);
+  p->o_mt = o; o += up64(NP * cap);
+  p->o_md = o; o += up64(NP * cap);
+  p->d2h_words = o;
+  p->o_idx = o; o += up64(NI * cap);
+  p->blk_words = o;
+  o = 0;
+  p->x_und = o; o += up64((NI * img + 3) / 4);
+  p->x_jdesc = o; o += up64(p->n_nb ? NJ * cap * D : 0);
+  p->x_jpts = o; o += up64(p->n_nb ? NJ * cap * 2 : 0);
+  p->x_jmap = o; o += up64(p->n_nb ? NJ * cap : 0);
+  p->x_jn = o; o += up64(p->n_nb ? NJ : 0);
+  p->scr_words = o;
+  rc = [&]() -> int {
+    const size_t all_words = 64 + (size_t)p->K * 2 * p->blk_words;
+    HIP_TRY(hipMalloc(&p->d_all, sizeof(float) * all_words));
+    HIP_TRY(hipMemset(p->d_all, 0, sizeof(float) * all_words));      // the blocks the first passes' temporal pairs read: no keypoints
+    HIP_TRY(hipMalloc(&p->d_scr, sizeof(float) * p->scr_words * p->K));
+    const size_t rimg = (size_t)p->RW * p->RH;
+    HIP_TRY(hipMalloc(&p->d_raw_all, rimg * NI * p->K));
+    // the maps, copied into memory the pipe owns
+    HIP_TRY(hipMalloc(&p->d_maps, sizeof(float) * 12 * img));
+    const hipMemcpyKind kind = maps->device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int c = 0; c < 4; ++c) {
+      float* mc = p->d_maps + (size_t)c * 3 * img;
+      HIP_TRY(hipMemcpy(mc, maps->mapx[c], sizeof(float) * img, kind));
+      HIP_TRY(hipMemcpy(mc + img, maps->mapy[c], sizeof(float) * img, kind));
+      if (maps->gain[c]) HIP_TRY(hipMemcpy(mc + 2 * img, maps->gain[c], sizeof(float) * img, kind));
+      p->ua.mapx[c] = mc; p->ua.mapy[c] = mc + img; p->ua.gain[c] = maps->gain[c] ? mc + 2 * img : nullptr;
+    }
+    p->ua.cam_stride = (long)rimg; p->ua.quad_stride = (long)(4 * rimg); p->ua.sh = p->RH; p->ua.sw = p->RW; p->ua.sstride = p->RW;
+    p->ua.npix = (int)img; p->ua.quads = p->Q; p->ua.vec_out = 1;      // img % 4 == 0 and the views start at 256-byte boundaries of the lane scratch
+    // the half-image jobs of quad frame q: 2 (q * 4 + n) reads view a of neighbour pair n, 2 (q * 4 + n) + 1 view b
+    const int Q = p->Q;
+    std::vector<int32_t> jobs((size_t)32 * Q, 0);
+    int32_t* jrow = jobs.data(); int32_t* jleft = jrow + 8 * Q; float* jshift = reinterpret_cast<float*>(jleft + 8 * Q);
+    int32_t* ma = jleft + 16 * Q; int32_t* mb = ma + 4 * Q;
+    for (int q = 0; q < Q; ++q)
+      for (int n = 0; n < 4; ++n) {
+        const int ja = 2 * (q * 4 + n), jb = ja + 1;
+        const bool lr = NB[n][2] == 1;
+        jrow[ja] = q * 4 + NB[n][0]; jleft[ja] = lr ? 1 : 0; jshift[ja] = lr ? p->move_cols : -p->move_cols;
+        jrow[jb] = q * 4 + NB[n][1]; jleft[jb] = lr ? 0 : 1; jshift[jb] = 0.f;
+        ma[q * 4 + n] = ja; mb[q * 4 + n] = jb;
+      }
+    HIP_TRY(hipMalloc(&p->d_jobs, sizeof(int32_t) * jobs.size()));
+    HIP_TRY(hipMemcpy(p->d_jobs, jobs.data(), sizeof(int32_t) * jobs.size(), hipMemcpyHostToDevice));
+    p->lanes.resize(p->K);
+    // the stereo pipe's measured stream placement: a lane's two streams on different hardware pipes, consecutive lanes' streams on different ones too
+    struct Spare { std::vector<hipStream_t> first, second; ~Spare() { for (auto& v : {&first, &second}) for (hipStream_t q : *v) if (q) (void)hipStreamDestroy(q); } } spare;
+    const int rcs = place_streams(h->cfg.device_id, p->K, p->G ? p->K : 0, spare.first, spare.second, p->first_class, p->second_class, &p->n_classes, &p->probe_ticks,
+                                  &p->probe_turns_us);
+    if (rcs) return rcs;
+    for (int k = 0; k < p->K; ++k) {
+      auto& L = p->lanes[k];
+      hipStream_t ms = spare.first[k]; spare.first[k] = nullptr;
+      if (p->G) { L.nv = spare.second[k]; spare.second[k] = nullptr; }
+      const int rc2 = clone_lane(h, NI, &L.ctx, ms, 0, p->G > 0);
+      if (rc2) { (void)hipStreamDestroy(ms); return rc2; }
+      L.s = L.ctx->stream;
+      for (hipEvent_t* e : {&L.ev_up, &L.ev_nv, &L.ev_ext[0], &L.ev_ext[1], &L.ev_done}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      L.d_raw = p->d_raw_all + (size_t)k * NI * rimg;
+      if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, rimg * NI, hipHostMallocDefault));
+      for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
+    }
+    if (p->NP) {
+      // pair tables [lane][set][NP]: the 4 Q neighbour pairs on the lane's compacted pools, then the 4 Q temporal pairs (view c of quad frame q against view c
+      // of quad frame q - 1; q = 0: the last quad frame of the previous pass P - 1 = lane k - 1 of the same set, or lane K - 1 of the other set when k = 0)
+      std::vector<MatchPairDesc> tab((size_t)p->K * 2 * NP);
+      for (int k = 0; k < p->K; ++k)
+        for (int set = 0; set < 2; ++set) {
+          float* B = p->block(k, set);
+          float* PB = p->block(k > 0 ? k - 1 : p->K - 1, k > 0 ? set : set ^ 1);
+          float* X = p->scratch(k);
+          MatchPairDesc* row = tab.data() + ((size_t)k * 2 + set) * NP;
+          int pi = 0;
+          for (int j = 0; p->n_nb && j < 4 * Q; ++j) {
+            MatchPairDesc& d = row[pi++];
+            const size_t ja = 2 * (size_t)j, jb = ja + 1;
+            d.a = X + p->x_jdesc + ja * cap * D; d.b = X + p->x_jdesc + jb * cap * D;
+            d.pts_a = X + p->x_jpts + ja * cap * 2; d.pts_b = X + p->x_jpts + jb * cap * 2;
+            d.na = reinterpret_cast<int32_t*>(X + p->x_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + p->x_jn) + jb;
+            d.radius = cfg->radius_neighbour;
+          }
+          for (int v = 0; p->n_pr && v < 4 * Q; ++v) {
+            MatchPairDesc& d = row[pi++];
+            float* BB = v >= 4 ? B : PB;
+            const size_t ra = v, rb = v >= 4 ? v - 4 : (size_t)(4 * (Q - 1) + v);
+            d.a = B + p->o_desc + ra * cap * D; d.b = BB + p->o_desc + rb * cap * D;
+            d.pts_a = B + p->o_kps + ra * cap * 2; d.pts_b = BB + p->o_kps + rb * cap * 2;
+            d.na = reinterpret_cast<int32_t*>(B + p->o_cnt) + ra; d.nb = reinterpret_cast<int32_t*>(BB + p->o_cnt) + rb;
+            d.radius = cfg->radius_prev;
+          }
+        }
+      HIP_TRY(hipMalloc(&p->d_pairs, sizeof(MatchPairDesc) * tab.size()));
+      HIP_TRY(hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice));
+      p->match_scratch_lane = match_scratch_bytes((int)NP, p->cap);
+      HIP_TRY(hipMalloc(&p->d_match_scratch, p->match_scratch_lane * p->K));
+      HIP_TRY(hipMemset(p->d_match_scratch, 0, p->match_scratch_lane * p->K));
+    }
+    return D2FE_OK;
+  }();
+  if (rc != D2FE_OK) { d2fe_quad_pipe_destroy(p); return rc; }
+  // the copies and memsets above ran on the null stream; the lanes' non-blocking streams do not wait for it
+  if (hipDeviceSynchronize() != hipSuccess) { d2fe_quad_pipe_destroy(p); return ctx_fail(D2FE_ERR_HIP, "hipDeviceSynchronize"); }
+  *out = p;
+  return D2FE_OK;
+}
+
+void d2fe_quad_pipe_destroy(d2fe_quad_pipe p) {
+  if (!p) return;
+  (void)hipSetDevice(p->parent->cfg.device_id);
+  for (auto& L : p->lanes) {
+    if (L.s) (void)hipStreamSynchronize(L.s);
+    if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
+    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done}) if (e) (void)hipEventDestroy(e);
+    if (L.pin_in) (void)hipHostFree(L.pin_in);
+    for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
+    if (L.ctx) d2fe_destroy(L.ctx);
+  }
+  for (void* q : {(void*)p->d_all, (void*)p->d_scr, (void*)p->d_raw_all, (void*)p->d_maps, (void*)p->d_jobs, (void*)p->d_pairs, (void*)p->d_match_scratch})
+    if (q) (void)hipFree(q);
+  d2fe_context* parent = p->parent;
+  delete p;
+  // a handle destroyed while this pipe was alive was only MARKED (d2fe_destroy): the last pipe to go releases it
+  if (parent->live_pipes.fetch_sub(1) == 1 && parent->doomed.load()) d2fe_destroy(parent);
+}
+
+int d2fe_quad_pipe_submit(d2fe_quad_pipe p, const uint8_t* raw, int stride, size_t camera_stride, size_t quad_stride, int64_t* ticket) {
+  if (!p || !raw || !ticket) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (stride < p->RW) return ctx_fail(D2FE_ERR_INVALID, "stride < raw_width");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call and accepts no more work (destroy it): " + p->failed_msg);
+  // an error below leaves the pass half-enqueued: no later pass can build on it, so the first error is final for the pipe
+  const int rc = quad_pass(p, raw, stride, camera_stride, quad_stride, ticket);
+  if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
+  return rc;
+}
+
+int d2fe_quad_pipe_wait(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_pipe_result* out) {
+  if (!p || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  std::unique_lock<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "unknown ticket");
+  // the ticket's result block is written again by the pass 2 K submits later
+  if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: wait for a ticket within 2 * lanes submits");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  const int k = (int)(ticket % p->K), set = (int)((ticket / p->K) & 1);
+  auto& L = p->lanes[k];
+  if (L.synced < ticket) {
+    // block WITHOUT the mutex, so that the other thread can go on submitting; a later pass of the lane may re-record the event meanwhile: the wait then
+    // covers that pass too, and everything the lane recorded up to `rec` is complete either way (one stream, in order)
+    const long long rec = L.rec;
+    hipEvent_t ev = L.ev_done;
+    lk.unlock();
+    const hipError_t e = hipEventSynchronize(ev);
+    lk.lock();
+    if (e != hipSuccess) {
+      p->failed = D2FE_ERR_HIP; p->failed_msg = std::string("hipEventSynchronize: ") + hipGetErrorString(e);
+      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+    }
+    if (L.synced < rec) L.synced = rec;
+    if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block was reused while this call waited for it");
+  }
+  const float* B = L.pin_out[set];
+  const size_t cap = p->cap;
+  out->quads = p->Q; out->cap = p->cap; out->desc_dim = p->D; out->netvlad_dim = p->G;
+  out->kps_xy = B + p->o_kps; out->scores = B + p->o_scores; out->desc = B + p->o_desc;
+  out->n_kp = reinterpret_cast<const int32_t*>(B + p->o_cnt);
+  out->netvlad = p->G ? B + p->o_nv : nullptr;
+  const int32_t* mq = reinterpret_cast<const int32_t*>(B + p->o_mq);
+  const int32_t* mt = reinterpret_cast<const int32_t*>(B + p->o_mt);
+  const int32_t* mn = reinterpret_cast<const int32_t*>(B + p->o_mn);
+  const float* md = B + p->o_md;
+  if (p->n_nb) { out->nb_q = mq; out->nb_t = mt; out->nb_dist = md; out->nb_n = mn; }
+  if (p->n_pr) {
+    const size_t pi = p->n_nb;
+    out->prev_q = mq + pi * cap; out->prev_t = mt + pi * cap; out->prev_dist = md + pi * cap; out->prev_n = mn + pi;
+  }
+  return D2FE_OK;
+}
+
+int d2fe_quad_pipe_lanes(d2fe_quad_pipe p) { return p ? p->K : ctx_fail(D2FE_ERR_INVALID, "null pipe"); }
+
+int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* cap, int32_t* desc_dim, int32_t* netvlad_dim) {
+  if (!p) return ctx_fail(D2FE_ERR_INVALID, "null pipe");
+  if (quads) *quads = p->Q;
+  if (cap) *cap = p->cap;
+  if (desc_dim) *desc_dim = p->D;
+  if (netvlad_dim) *netvlad_dim = p->G;
+  return D2FE_OK;
+}
+
+}  // extern "C"

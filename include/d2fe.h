@@ -577,6 +577,80 @@ D2FE_API int d2fe_remap_matches_device(d2fe_handle h, int32_t* d_q_idx, int32_t*
                                        const int32_t* d_map_a_job, const int32_t* d_map_b_job, const int32_t* d_maps, int npairs,
                                        int cap_match, int cap_map, void* stream);
 
+/* ---- Quadcam frames in flight (BASELINE configs[2], FOURCORNER_FISHEYE) ----------------------------------------------------------------------------
+ * The per-frame work of a quadcam agent -- FisheyeUndist of the four raw fisheye frames (fisheye_undistort.h:152-176), SuperPoint and NetVLAD of every
+ * undistorted view (loop_cam.cpp:589-648), the four neighbour matches (0,1) (1,2) (2,3) LEFT_RIGHT and (0,3) RIGHT_LEFT of matchLocalFeatures
+ * (d2featuretracker.cpp:121-133,1144-1182: half images, a-side shift by +-move_cols, radius gate, indices mapped back) and the temporal matchKNN of every
+ * view against the same view of the previous quad frame (:403-456) -- as ONE submit and ONE wait per `quads` quad frames, with up to `lanes` submits in
+ * flight.  Per submit, on the lane's own streams: one H2D of the raw frames -> ONE undistort launch for 4 cameras x quads frames -> [NetVLAD of the
+ * 4 quads views on the lane's second stream] -> SuperPoint of the 4 quads views -> half-image compaction of the 8 quads neighbour jobs -> ONE matcher
+ * launch over every neighbour and temporal pair -> index remap -> ONE D2H.  The results equal those of the building blocks (d2fe_undistort_device,
+ * d2fe_netvlad_device, d2fe_superpoint_extract_device, d2fe_half_image_compact_device, d2fe_match_batch_device, d2fe_remap_matches_device) composed by
+ * hand at the same image count.
+ * Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit; the very first quad
+ * frame of the pipe has prev_n = 0).  With quads > 1 this DIFFERS from d2slam_amd/quadcam.py's QuadcamChain, which pairs frame q of a step with frame q
+ * of the previous step.
+ * Lifetime and errors are the stereo pipe's (d2fe_pipe_*, above): while a quad pipe exists d2fe_destroy of its handle is DEFERRED and d2fe_load_* /
+ * d2fe_set_*_pca return D2FE_ERR_INVALID; the first error of a submit or wait is final for the pipe; one submitting thread, d2fe_quad_pipe_wait may be
+ * called from a second one; results stay valid for 2 * lanes further submits. */
+typedef struct d2fe_quad_pipe_s* d2fe_quad_pipe;
+typedef struct {
+  int32_t struct_size;          /* sizeof(d2fe_quad_pipe_config) */
+  int32_t lanes;                /* submits in flight, 1..16 */
+  int32_t quads;                /* quad frames per submit (>= 1), consecutive in time; 4 * quads <= the handle's max_batch */
+  int32_t raw_width, raw_height;      /* raw fisheye frame size (1280 x 800 in the reference) */
+  int32_t width, height;        /* undistorted view size (800 x 400 in the reference), within the handle's maximum */
+  int32_t cap;                  /* keypoint capacity per view: <= the handle's max_keypoints (and <= 1024 with match_neighbour) */
+  int32_t netvlad;              /* 1: NetVLAD of every view */
+  int32_t match_neighbour;      /* 1: the four neighbour pairs of every quad frame */
+  int32_t match_prev;           /* 1: every view against the same view of the previous quad frame */
+  int32_t pinned_input;         /* 1: the raw pointer handed to submit is page-locked and stays valid until the ticket was waited for (DMA straight from it);
+                                   0: submit copies the frames into the lane's pinned staging first */
+  double ratio;                 /* knn_match_ratio */
+  double radius_neighbour;      /* search_local_max_dist_lr * width (<= 0: off), d2featuretracker.cpp:669 */
+  double radius_prev;           /* pixel gate of the temporal pairs (<= 0: off -- the whole image, as QuadcamChain) */
+  double undistort_fov;         /* move_cols = width * 90 / undistort_fov (d2fe_half_move_cols) */
+  int32_t reserved[8];          /* zero; kept for the stereo pipe's tuning knobs */
+} d2fe_quad_pipe_config;
+/* The four cameras' undistortion maps (d2fe_gen_cylinder_map(_device) or the caller's own), width * height floats each.  gain[c] may be NULL
+ * (calib_photometric off for that camera).  device = 1: device pointers, 0: host pointers.  d2fe_quad_pipe_create copies them into memory the pipe owns. */
+typedef struct {
+  const float* mapx[4];
+  const float* mapy[4];
+  const float* gain[4];
+  int32_t device;
+} d2fe_quad_maps;
+typedef struct {            /* HOST pointers into the lane's pinned block, quad-major (image row q * 4 + c); valid until 2 * lanes further submits */
+  int32_t quads, cap, desc_dim, netvlad_dim;
+  const float* kps_xy;      /* [quads][4][cap][2] */
+  const float* scores;      /* [quads][4][cap] */
+  const float* desc;        /* [quads][4][cap][desc_dim] */
+  const int32_t* n_kp;      /* [quads][4] */
+  const float* netvlad;     /* [quads][4][netvlad_dim] or NULL */
+  /* neighbour pair n = 0..3 of quad frame q in the order (0,1) (1,2) (2,3) LEFT_RIGHT, (0,3) RIGHT_LEFT: [quads][4][cap] x3, [quads][4]; NULL when off.
+     nb_q / nb_t index the full keypoint lists of views a / b (after the remap) */
+  const int32_t* nb_q; const int32_t* nb_t; const float* nb_dist; const int32_t* nb_n;
+  /* temporal pairs, view c of quad frame q against view c of quad frame q - 1: [quads][4][cap] x3, [quads][4]; NULL when off */
+  const int32_t* prev_q; const int32_t* prev_t; const float* prev_dist; const int32_t* prev_n;
+} d2fe_quad_pipe_result;
+/* defaults: lanes 4, quads 1, raw 1280 x 800, views 800 x 400, cap 100, netvlad / match_neighbour / match_prev 1, pinned_input 0, ratio 0.8,
+ * radius_neighbour 160 (0.2 * 800), radius_prev -1, undistort_fov 200 */
+D2FE_API void d2fe_quad_pipe_default_config(d2fe_quad_pipe_config* cfg);
+D2FE_API int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const d2fe_quad_maps* maps, d2fe_quad_pipe* out);
+D2FE_API void d2fe_quad_pipe_destroy(d2fe_quad_pipe p);
+/* raw: u8 fisheye frames, image (quad frame q, camera c) at raw + q * quad_stride + c * camera_stride, rows `stride` bytes apart.  Returns at once with
+ * a ticket (0, 1, 2, ...); blocks only while the ticket's lane still runs the submit of `lanes` submits ago. */
+D2FE_API int d2fe_quad_pipe_submit(d2fe_quad_pipe p, const uint8_t* raw, int stride, size_t camera_stride, size_t quad_stride, int64_t* ticket);
+/* Blocks until the ticket's results are in host memory.  Tickets may be waited for in any order, each within 2 * lanes submits. */
+D2FE_API int d2fe_quad_pipe_wait(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_pipe_result* out);
+D2FE_API int d2fe_quad_pipe_lanes(d2fe_quad_pipe p);
+D2FE_API int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* cap, int32_t* desc_dim, int32_t* netvlad_dim);
+/* The pipe's undistort step on its own: ONE launch for 4 cameras x quads raw frames (image (q, c) at d_raw + q * quad_stride + c * camera_stride), maps
+ * as above with device = 1 and every map pointer 16-byte aligned; view (q, c) is written to d_dst + (q * 4 + c) * dw * dh.  Same bytes as
+ * d2fe_undistort_device camera by camera. */
+D2FE_API int d2fe_quad_undistort_device(d2fe_handle h, const uint8_t* d_raw, int quads, int sw, int sh, int sstride, size_t camera_stride,
+                                        size_t quad_stride, const d2fe_quad_maps* maps, int dw, int dh, uint8_t* d_dst, void* stream);
+
 /* Test hooks and kernel diagnostics (d2fe_debug_*) are NOT part of this library: they live in the development library
  * (lib/libd2fe_hip_dev.so, built with -DD2FE_DEVTOOLS) and are declared in include/d2fe_debug.h. */
 

@@ -246,6 +246,22 @@ class StereoPipe {
   d2fe_pipe p_ = nullptr;
 };
 
+// d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
+class QuadPipe {
+ public:
+  QuadPipe(d2fe_handle h, const d2fe_quad_pipe_config& cfg, const d2fe_quad_maps& maps) {
+    if (d2fe_quad_pipe_create(h, &cfg, &maps, &p_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_pipe_create: %s\n", d2fe_last_error()); p_ = nullptr; }
+  }
+  ~QuadPipe() { if (p_) d2fe_quad_pipe_destroy(p_); }
+  QuadPipe(const QuadPipe&) = delete;
+  QuadPipe& operator=(const QuadPipe&) = delete;
+  bool ok() const { return p_ != nullptr; }
+  d2fe_quad_pipe get() const { return p_; }
+
+ private:
+  d2fe_quad_pipe p_ = nullptr;
+};
+
 // feature_matcher.h:6-11.  `h` replaces the implicit global state of cv::BFMatcher; everything else as in the reference.
 inline std::vector<DMatch> matchKNN(d2fe_handle h, const DescView& desc_a, const DescView& desc_b, double knn_match_ratio = 0.8,
                                     const std::vector<Point2f>& pts_a = std::vector<Point2f>(),
