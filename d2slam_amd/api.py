@@ -29,7 +29,7 @@ PREC_F32, PREC_F16X2, PREC_F32_WINO = 0, 1, 2
 ERR_TRUNCATED = -4            # d2fe_status: output capacity too small, n_out holds what was written
 KEEP_ALL_CAP = 1024           # host-pointer staging capacity of a keep-all handle (max_keypoints = -1)
 PROF_STAGES = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPaDa",
-               "convPb", "convDb", "softmax_cand", "select", "sample", "match", "netvlad"]
+               "convPb", "convDb", "softmax_cand", "select", "sample", "match", "netvlad", "lk"]
 
 
 class D2FEError(RuntimeError):
@@ -91,7 +91,7 @@ class _ExchangeResult(C.Structure):
 class _PipeConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("lanes", C.c_int32), ("frames", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("cap", C.c_int32), ("netvlad", C.c_int32), ("match_lr", C.c_int32), ("match_prev", C.c_int32), ("pinned_input", C.c_int32),
-                ("ratio", C.c_double), ("radius_lr", C.c_double), ("radius_prev", C.c_double), ("cu_partition", C.c_int32), ("netvlad_inline", C.c_int32), ("coalesce", C.c_int32), ("lane_cus", C.c_int32), ("netvlad_group", C.c_int32), ("coalesce_depth", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("ratio", C.c_double), ("radius_lr", C.c_double), ("radius_prev", C.c_double), ("cu_partition", C.c_int32), ("netvlad_inline", C.c_int32), ("coalesce", C.c_int32), ("lane_cus", C.c_int32), ("netvlad_group", C.c_int32), ("coalesce_depth", C.c_int32), ("lr_lk", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class _PipeResult(C.Structure):
@@ -99,6 +99,10 @@ class _PipeResult(C.Structure):
                 ("kps_xy", C.c_void_p), ("scores", C.c_void_p), ("desc", C.c_void_p), ("n_kp", C.c_void_p), ("netvlad", C.c_void_p),
                 ("lr_q", C.c_void_p), ("lr_t", C.c_void_p), ("lr_dist", C.c_void_p), ("lr_n", C.c_void_p),
                 ("prev_q", C.c_void_p), ("prev_t", C.c_void_p), ("prev_dist", C.c_void_p), ("prev_n", C.c_void_p)]
+
+
+class _PipeLKResult(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("pts_xy", C.c_void_p), ("status", C.c_void_p)]
 
 
 class _PipeDeviceResult(C.Structure):
@@ -148,6 +152,7 @@ EXPORTS = [
     "d2fe_dequantize_int8", "d2fe_sync", "d2fe_profile_enable", "d2fe_profile_read", "d2fe_prepare_gray", "d2fe_prepare_gray_device",
     "d2fe_gen_cylinder_map", "d2fe_gen_cylinder_map_device", "d2fe_gen_pinhole_map", "d2fe_gen_pinhole_map_device", "d2fe_lk_frame_create",
     "d2fe_lk_frame_create_device", "d2fe_lk_frame_destroy", "d2fe_lk_frame_read_level", "d2fe_lk_track", "d2fe_lk_track_batch",
+    "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -282,6 +287,11 @@ def _open_library(path, dev):
                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.d2fe_lk_track_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p]
+        lib.d2fe_lk_stereo_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.d2fe_lk_stereo_workspace_bytes.restype = C.c_size_t
+        lib.d2fe_lk_track_stereo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_lk_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_detect_fast_by_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_void_p]
         lib.d2fe_good_features_to_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
@@ -784,10 +794,13 @@ class DevFrontEnd(FrontEnd):
 class StereoPipe:
     """Frames in flight (include/d2fe.h, d2fe_pipe_*): the per-frame work of D2Frontend::processStereoframe (SuperPoint on both images, NetVLAD on
     the left one, matchKNN L<->R and L<->previous L) for `frames` stereo frames per submit with up to `lanes` submits in flight.
+    lr_lk=True (needs match_lr=False): the reference's default stereo path (lr_match_use_lk) -- SuperPoint on the left images only, every left keypoint
+    tracked into the right image with pyramidal LK inside the pass; wait() then also returns "lk_pts" [F, cap, 2] and "lk_status" [F, cap].
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits)."""
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
-                 ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0):
+                 ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
+                 lr_lk=False):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _PipeConfig()
@@ -798,6 +811,9 @@ class StereoPipe:
         c.ratio, c.radius_lr, c.radius_prev = float(ratio), float(radius_lr), float(radius_prev)
         c.cu_partition = int(bool(cu_partition)); c.coalesce = int(coalesce); c.lane_cus = int(lane_cus); c.netvlad_group = int(netvlad_group); c.coalesce_depth = int(coalesce_depth)
         c.netvlad_inline = 2 if netvlad_inline is None else int(bool(netvlad_inline))      # None: auto (inline when lanes > 2)
+        c.lr_lk = int(bool(lr_lk))
+        self._lr_lk = bool(lr_lk)
+        self._lk_res = _PipeLKResult()
         self._p = C.c_void_p()
         _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
         if not hasattr(fe, "_pipes"):
@@ -908,7 +924,16 @@ class StereoPipe:
         for k in ("lr", "prev"):
             out[k + "_q"] = view(getattr(r, k + "_q"), (F, cap), np.int32); out[k + "_t"] = view(getattr(r, k + "_t"), (F, cap), np.int32)
             out[k + "_dist"] = view(getattr(r, k + "_dist"), (F, cap), np.float32); out[k + "_n"] = view(getattr(r, k + "_n"), (F,), np.int32)
+        if self._lr_lk:
+            lk = self.lk_result_raw(ticket)
+            out["lk_pts"] = view(lk.pts_xy, (F, cap, 2), np.float32)
+            out["lk_status"] = np.frombuffer((C.c_uint8 * (F * cap)).from_address(lk.status), dtype=np.uint8).reshape(F, cap)
         return out
+
+    def lk_result_raw(self, ticket):
+        """d2fe_pipe_lk_result_get: the left -> right LK tracks of a ticket that wait() has returned (lr_lk pipes)"""
+        _check(self._lib.d2fe_pipe_lk_result_get(self._p, C.c_int64(ticket), C.byref(self._lk_res)))
+        return self._lk_res
 
 
 def _pinned_view(ptr, shape, dt):
@@ -1133,6 +1158,20 @@ def lk_track(fe: FrontEnd, prev: LKFrame, cur: LKFrame, prev_pts, cur_init, trac
     _check(fe._lib.d2fe_lk_track(fe.handle, prev._f, cur._f, _ptr(pp), _ptr(ci), n, int(track_type), float(move_cols), int(win),
                                  int(iters), _ptr(out), _ptr(st)))
     return out[:n], st[:n]
+
+
+def lk_stereo_workspace_bytes(n_frames, width, height, levels=PYR_LEVEL):
+    """d2fe_lk_stereo_workspace_bytes (host arithmetic): the pyramids of n_frames left and n_frames right frames"""
+    return int(load_library().d2fe_lk_stereo_workspace_bytes(int(n_frames), int(width), int(height), int(levels)))
+
+
+def lk_track_stereo_device(fe: FrontEnd, d_left, d_right, n_frames, width, height, d_kps_xy, d_n_kp, cap, d_workspace, d_pts_xy, d_status,
+                           stream=None, stride=None, image_stride=None, levels=PYR_LEVEL, win=WIN_SIZE, iters=LK_ITERS):
+    """Device-resident stereo tracks (d2fe_lk_track_stereo_device); arguments are raw device addresses (ints), as for FrontEnd.extract_device: the keypoints
+    [n_frames, cap, 2] and counts [n_frames] are the ones extract_device left; only enqueues on `stream`."""
+    _check(fe._lib.d2fe_lk_track_stereo_device(fe.handle, d_left, d_right, int(n_frames), int(width), int(height), int(stride or width),
+                                               int(image_stride or (stride or width) * height), d_kps_xy, d_n_kp, int(cap), int(levels), int(win), int(iters),
+                                               d_workspace, d_pts_xy, d_status, stream))
 
 
 class _LKPair(C.Structure):

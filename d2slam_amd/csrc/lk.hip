@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/d2fe.h"
+#include "context.h"
 #include "kernels.h"
 
 namespace d2fe {
@@ -30,10 +31,7 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 }
 
 // ---- pyrDown: 5x5 [1 4 6 4 1]^2 / 256, reflect-101 border, round half to even --------------------------------------------
-__global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ dst,
-                                                       int dw, int dh) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= dw || y >= dh) return;
+__device__ __forceinline__ uint8_t pyr_down_px(const uint8_t* __restrict__ src, size_t stride, int w, int h, int x, int y) {
   const int k[5] = {1, 4, 6, 4, 1};
   int xs[5];
 #pragma unroll
@@ -41,7 +39,7 @@ __global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* __restrict
   int s = 0;
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    const uint8_t* row = src + (size_t)reflect101(2 * y + i - 2, h) * w;
+    const uint8_t* row = src + (size_t)reflect101(2 * y + i - 2, h) * stride;
     int r = 0;
 #pragma unroll
     for (int j = 0; j < 5; ++j) r += k[j] * row[xs[j]];
@@ -50,7 +48,47 @@ __global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* __restrict
   int q = s >> 8;
   const int rem = s & 255;
   if (rem > 128 || (rem == 128 && (q & 1))) ++q;
-  dst[(size_t)y * dw + x] = (uint8_t)(q > 255 ? 255 : q);
+  return (uint8_t)(q > 255 ? 255 : q);
+}
+
+__global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ dst,
+                                                       int dw, int dh) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= dw || y >= dh) return;
+  dst[(size_t)y * dw + x] = pyr_down_px(src, (size_t)w, w, h, x, y);
+}
+
+// Batched form for the stereo tracker: pyramids of 2 n frames (n left, n right images that are already in HBM) side by side in one workspace,
+// image i at i * total, each in the layout of d2fe_lk_frame_s.  ONE launch per level over all images (blockIdx.z = image).  The launch of level 1
+// reads the caller's frames (any row stride) and also writes level 0, the tight copy: thread (x, y) of level 1 owns the 2 x 2 pixels under it.
+// levels == 0: the same launch with dst_off < 0 only copies
+struct PyrBatchArgs {
+  const uint8_t* left; const uint8_t* right;      // level 1: the frames; deeper levels: unused
+  size_t src_stride, src_image_stride;
+  uint8_t* ws; size_t total;
+  int n, first;                                   // images per side; first != 0: this launch reads the caller's frames and writes level 0
+  int src_off, sw, sh, dst_off, dw, dh;           // source / destination level inside a pyramid
+};
+
+__global__ __launch_bounds__(256) void pyr_down_batch_kernel(PyrBatchArgs a) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int i = blockIdx.z;
+  uint8_t* pyr = a.ws + (size_t)i * a.total;
+  const uint8_t* src = pyr + a.src_off;
+  size_t stride = (size_t)a.sw;
+  if (a.first) {
+    src = (i < a.n ? a.left + (size_t)i * a.src_image_stride : a.right + (size_t)(i - a.n) * a.src_image_stride);
+    stride = a.src_stride;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const int px = 2 * x + dx, py = 2 * y + dy;
+        if (px < a.sw && py < a.sh) pyr[(size_t)py * a.sw + px] = src[(size_t)py * stride + px];
+      }
+  }
+  if (a.dst_off < 0 || x >= a.dw || y >= a.dh) return;
+  pyr[(size_t)a.dst_off + (size_t)y * a.dw + x] = pyr_down_px(src, stride, a.sw, a.sh, x, y);
 }
 
 // ---- sparse pyramidal LK ---------------------------------------------------------------------------------------------------------
@@ -205,6 +243,51 @@ __global__ __launch_bounds__(256) void lk_track_kernel(LkArgs a) {
   if (lane == 0) {
     a.cur_pts[2 * i] = cx; a.cur_pts[2 * i + 1] = cy;
     a.status[i] = (uint8_t)ok;
+  }
+}
+
+// The stereo form (trackLK left -> right, d2featuretracker.cpp:697-752): points and their number come from DEVICE memory -- the keypoints SuperPoint left
+// for image f (d2fe_superpoint_extract_device / the pipe) -- so nothing of it needs the host.  One wave per (frame, keypoint slot); (prev, cur) = (left,
+// right) pyramid of the frame in the workspace of pyr_down_batch_kernel; cur_init = prev_pts (opticaltrack_utils.cpp:195-196); WHOLE_IMG_MATCH.
+// Slots >= n_kp[f] are written too (status 0, point (0, 0)): the result block never carries stale data and needs no memset
+struct LkStereoArgs {
+  const uint8_t* ws; size_t total;
+  LkPairDev P;                      // geometry only (prev / cur are per frame)
+  int n_frames, cap, win, iters;
+  const float* kps; const int* n_kp;
+  float* cur_pts; uint8_t* status;
+};
+
+__global__ __launch_bounds__(256) void lk_track_stereo_kernel(LkStereoArgs s) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), f = blockIdx.y;
+  if (slot >= s.cap) return;
+  const size_t i = (size_t)f * s.cap + slot;
+  if (slot >= s.n_kp[f]) {          // wave-uniform: dead slots leave before touching an image
+    if (lane == 0) { s.cur_pts[2 * i] = 0.f; s.cur_pts[2 * i + 1] = 0.f; s.status[i] = 0; }
+    return;
+  }
+  LkArgs a{};
+  a.win = s.win; a.iters = s.iters;
+  const LkPairDev& P = s.P;
+  const uint8_t* L = s.ws + (size_t)f * s.total;
+  const uint8_t* R = s.ws + (size_t)(s.n_frames + f) * s.total;
+  const float ppx = s.kps[2 * i], ppy = s.kps[2 * i + 1];
+  float cx = ppx, cy = ppy;
+  int st = 1, rst = 1;
+  lk_calc(a, P, L, R, ppx, ppy, cx, cy, st, lane);
+  float rx = cx, ry = cy;
+  lk_calc(a, P, R, L, cx, cy, rx, ry, rst, lane);
+  const float dx = ppx - rx, dy = ppy - ry;
+  const double nrm = __builtin_sqrt((double)dx * dx + (double)dy * dy);
+  int ok = (st && rst && nrm <= 0.5) ? 1 : 0;
+  if (ok) {
+    const int ix = (int)__builtin_rint((double)cx), iy = (int)__builtin_rint((double)cy);
+    if (!(1 <= ix && ix < P.w - 1 && 1 <= iy && iy < P.h - 1)) ok = 0;
+  }
+  if (lane == 0) {
+    s.cur_pts[2 * i] = cx; s.cur_pts[2 * i + 1] = cy;
+    s.status[i] = (uint8_t)ok;
   }
 }
 
@@ -509,6 +592,49 @@ int d2fe_lk_track_batch(d2fe_handle h, const d2fe_lk_pair* pairs, int npairs, co
     memcpy(status, back.data() + (o_st - o_cur), n);
   }
   return rc;
+}
+
+size_t d2fe_lk_stereo_workspace_bytes(int n_frames, int width, int height, int levels) {
+  if (n_frames < 1 || width < 16 || height < 16 || levels < 0 || levels > 7) return 0;
+  size_t total = 0;
+  for (int l = 0, w = width, hh = height; l <= levels; ++l) { total += (size_t)w * hh; w = (w + 1) / 2; hh = (hh + 1) / 2; }
+  return 2 * (size_t)n_frames * total;
+}
+
+int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint8_t* d_right, int n_frames, int width, int height, int stride,
+                                size_t image_stride, const float* d_kps_xy, const int32_t* d_n_kp, int cap, int levels, int win, int iters,
+                                void* d_workspace, float* d_pts_xy, uint8_t* d_status, void* stream) {
+  if (!h || !d_left || !d_right || !d_kps_xy || !d_n_kp || !d_workspace || !d_pts_xy || !d_status) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (width < 16 || height < 16 || levels < 0 || levels > 7 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
+  if (stride < width || (n_frames > 1 && image_stride < (size_t)stride * (height - 1) + width)) return ctx_fail(D2FE_ERR_INVALID, "bad stride / image stride");
+  if (n_frames < 1 || n_frames > 32767 || cap < 1 || cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "n_frames must be 1..32767, cap 1..16384");
+  if (win < 3 || win > 24 || !(win & 1) || iters < 1) return ctx_fail(D2FE_ERR_INVALID, "bad LK parameters (win odd, 3..23)");
+  LK_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  LkStereoArgs t{};
+  LkPairDev& P = t.P;
+  int o = 0;
+  for (int l = 0, w = width, hh = height; l <= levels; ++l) { P.off[l] = o; P.ws[l] = w; P.hs[l] = hh; o += w * hh; w = (w + 1) / 2; hh = (hh + 1) / 2; }
+  P.levels = levels; P.w = width; P.h = height; P.type = 0; P.move_cols = 0.f;
+  PyrBatchArgs a{};
+  a.left = d_left; a.right = d_right; a.src_stride = (size_t)stride; a.src_image_stride = image_stride;
+  a.ws = static_cast<uint8_t*>(d_workspace); a.total = (size_t)o; a.n = n_frames;
+  // level 0 (the tight copy) and level 1 in one launch, one launch per deeper level: `levels` launches (levels == 0: the copy alone)
+  for (int l = 1; l <= (levels > 0 ? levels : 1); ++l) {
+    a.first = l == 1;
+    a.src_off = P.off[l - 1]; a.sw = P.ws[l - 1]; a.sh = P.hs[l - 1];
+    a.dw = (a.sw + 1) / 2; a.dh = (a.sh + 1) / 2; a.dst_off = l <= levels ? P.off[l] : -1;
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(pyr_down_batch_kernel, dim3((a.dw + 63) / 64, (a.dh + 3) / 4, 2 * n_frames), dim3(256), 0, s, a);
+  }
+  t.ws = a.ws; t.total = a.total; t.n_frames = n_frames; t.cap = cap; t.win = win; t.iters = iters;
+  t.kps = d_kps_xy; t.n_kp = d_n_kp; t.cur_pts = d_pts_xy; t.status = d_status;
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_track_stereo_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, s, t);
+  }
+  LK_TRY(hipGetLastError());
+  return D2FE_OK;
 }
 
 int d2fe_lk_track(d2fe_handle h, d2fe_lk_frame prev, d2fe_lk_frame cur, const float* prev_pts, const float* cur_init, int n,

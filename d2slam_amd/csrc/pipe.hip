@@ -14,6 +14,11 @@
 //     -> ONE matcher launch over {L_f <-> R_f, L_f <-> L_(f-1)} (the pair table addresses the previous frame's block directly; the
 //        launch waits for the previous submit's extraction event, nothing else of it) -> ONE D2H of the block into pinned memory.
 // Outputs are bit-identical to the single-call entry points (same kernels, same launch shapes for the same image count).
+//
+// cfg.lr_lk (the reference's default stereo path, lr_match_use_lk): SuperPoint and NetVLAD see the LEFT images only (they take an image stride, which is what
+// the interleaved L, R, L, R rows of coalesce > 1 need); behind SuperPoint the lane builds the pyramids of both images in its own workspace and tracks every left
+// keypoint left -> right (d2fe_lk_track_stereo_device, lk.hip: levels + 1 launches, points and counts read on the device).  The tracks live in the result block
+// in front of d2h_words, so they travel with the pass's one D2H.  Rows of right images are never written: they keep the zeros of creation (n_kp = 0).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +43,11 @@ struct d2fe_pipe_s {
   int K = 0, F = 0, C = 1, NI = 0, W = 0, H = 0, cap = 0, D = 256, G = 0, npp = 0;      // NI: images per full pass; npp: matcher pairs per submit
   // block layout (float words from the block base; every array starts on a 64-word boundary)
   size_t o_desc = 0, o_kps = 0, o_scores = 0, o_nv = 0, o_cnt = 0, o_mn = 0, o_mq = 0, o_mt = 0, o_md = 0, o_idx = 0, blk_words = 0, d2h_words = 0;
+  // lr_lk: the tracks [F * C][cap][2] floats and [F * C][cap] bytes (inside d2h_words); coalesce > 1: SuperPoint writes the g left images of a pass to the compact
+  // staging rows o_s* (device only) and pipe_rows_kernel moves row j to the result row 2 j, so that a ticket's result keeps the [L, R] row pair of frames = 1
+  bool lk = false;
+  size_t o_lkp = 0, o_lks = 0, o_sdesc = 0, o_skps = 0, o_sscores = 0, o_scnt = 0, o_sidx = 0;
+  uint8_t* d_lk_ws = nullptr; size_t lk_ws_lane = 0;     // per lane: the pyramids of the NI images of a pass
   float* d_all = nullptr;            // [64 zero words | K lanes x 2 sets x block]
   MatchPairDesc* d_pairs = nullptr;  // [K][2][C variants: submits of the PREVIOUS pass][C * npp]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;   // per lane: tickets + records
@@ -53,6 +63,7 @@ struct d2fe_pipe_s {
     uint8_t* d_img = nullptr;
     uint8_t* pin_in = nullptr;
     float* pin_out[2] = {nullptr, nullptr};
+    uint8_t* d_lk = nullptr;           // lr_lk: this lane's pyramid workspace
     long long rec = -1, synced = -1;   // the pass whose completion ev_done last recorded / the newest pass known to be complete (idle: synced >= rec)
   };
   std::vector<Lane> lanes;
@@ -91,6 +102,9 @@ namespace {
 
 size_t up64(size_t w) { return (w + 63) / 64 * 64; }
 
+// lr_lk: the reference's tracker constants (PYR_LEVEL opticaltrack_utils.h:10, WIN_SIZE opticaltrack_utils.cpp:25, 30 iterations :239)
+constexpr int LK_LEVELS = 2, LK_WIN = 21, LK_ITERS = 30;
+
 int pipe_fail(int code, const std::string& msg) { return ctx_fail(code, msg); }
 
 // ---- stream placement by measurement ---------------------------------------------------------------------------------------------------------
@@ -102,6 +116,18 @@ int pipe_fail(int code, const std::string& msg) { return ctx_fail(code, msg); }
 __global__ void pipe_spin_kernel(long long ticks) {
   const long long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(4);
+}
+
+// lr_lk with coalesce > 1: compact SuperPoint rows 0 .. g - 1 (staging) -> result rows 0, 2, .. 2 (g - 1); blockIdx.y = row, the x dimension strides over its words
+__global__ __launch_bounds__(256) void pipe_rows_kernel(const float* __restrict__ s_desc, const float* __restrict__ s_kps, const float* __restrict__ s_scores,
+                                                        const int32_t* __restrict__ s_cnt, float* __restrict__ desc, float* __restrict__ kps,
+                                                        float* __restrict__ scores, int32_t* __restrict__ cnt, int cap, int D) {
+  const size_t j = blockIdx.y, nd = (size_t)cap * D, nk = (size_t)cap * 2, nsc = (size_t)cap;
+  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = t0; i < nd; i += step) desc[2 * j * nd + i] = s_desc[j * nd + i];
+  for (size_t i = t0; i < nk; i += step) kps[2 * j * nk + i] = s_kps[j * nk + i];
+  for (size_t i = t0; i < nsc; i += step) scores[2 * j * nsc + i] = s_scores[j * nsc + i];
+  if (t0 == 0) cnt[2 * j] = s_cnt[j];
 }
 
 constexpr int PROBE_CHAIN = 6;         // dependent launches per stream and probe
@@ -249,7 +275,8 @@ int pipe_flush(d2fe_pipe_s* p) {
   const int F = p->F, W = p->W, H = p->H;
   hipStream_t s = L.s;
   float* B = p->block(k, set);
-  const int n_left = p->C > 1 ? g : F, n_img = p->C > 1 ? 2 * g : 2 * F;
+  const int n_left = p->C > 1 ? g : F, n_img = p->lk ? n_left : 2 * n_left;      // images SuperPoint sees
+  const bool staged = p->lk && p->C > 1;
   const size_t left_stride = p->C > 1 ? 2 * img : img;
   int rc;
   // Where this pass's NetVLAD runs.  The device runs FOUR busy streams of a process side by side and makes a fifth take turns (d2fe_pipe_create), so in auto mode a pass
@@ -278,10 +305,26 @@ int pipe_flush(d2fe_pipe_s* p) {
     rc = netvlad(s);
     if (rc) return rc;
   }
-  rc = run_superpoint(L.ctx, L.d_img, n_img, W, H, W, img, B + p->o_kps, B + p->o_scores, B + p->o_desc, reinterpret_cast<int32_t*>(B + p->o_idx), p->cap,
-                      reinterpret_cast<int32_t*>(B + p->o_cnt), s);
-  if (rc) return rc;
+  if (!staged) {
+    rc = run_superpoint(L.ctx, L.d_img, n_img, W, H, W, img, B + p->o_kps, B + p->o_scores, B + p->o_desc, reinterpret_cast<int32_t*>(B + p->o_idx), p->cap,
+                        reinterpret_cast<int32_t*>(B + p->o_cnt), s);
+    if (rc) return rc;
+  } else {
+    rc = run_superpoint(L.ctx, L.d_img, n_img, W, H, W, left_stride, B + p->o_skps, B + p->o_sscores, B + p->o_sdesc, reinterpret_cast<int32_t*>(B + p->o_sidx), p->cap,
+                        reinterpret_cast<int32_t*>(B + p->o_scnt), s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(pipe_rows_kernel, dim3(16, g), dim3(256), 0, s, B + p->o_sdesc, B + p->o_skps, B + p->o_sscores, reinterpret_cast<const int32_t*>(B + p->o_scnt),
+                       B + p->o_desc, B + p->o_kps, B + p->o_scores, reinterpret_cast<int32_t*>(B + p->o_cnt), p->cap, p->D);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipEventRecord(L.ev_ext[set], s));
+  if (p->lk) {
+    // left -> right tracks of the pass's n_left frames: C == 1: left rows [0, F), right images F further on; C > 1: L, R interleaved, keypoints from the staging rows
+    rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride,
+                                     staged ? B + p->o_skps : B + p->o_kps, reinterpret_cast<const int32_t*>(staged ? B + p->o_scnt : B + p->o_cnt), p->cap,
+                                     LK_LEVELS, LK_WIN, LK_ITERS, L.d_lk, B + p->o_lkp, reinterpret_cast<uint8_t*>(B + p->o_lks), s);
+    if (rc) return rc;
+  }
   if (nv_side) {
     HIP_TRY(hipStreamWaitEvent(L.nv, L.ev_up, 0));
     rc = netvlad(L.nv);
@@ -394,6 +437,9 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   const int M = cfg->netvlad && cfg->netvlad_group > 1 ? cfg->netvlad_group : 1;
   if (M > 1 && (cfg->frames != 1 || C != 1 || cfg->lanes % M != 0)) return pipe_fail(D2FE_ERR_INVALID, "netvlad_group needs frames == 1, coalesce == 1 and lanes % netvlad_group == 0");
   if (cfg->cap < 1 || cfg->cap > 16384) return pipe_fail(D2FE_ERR_INVALID, "cap out of range");
+  if (cfg->lr_lk != 0 && cfg->lr_lk != 1) return pipe_fail(D2FE_ERR_INVALID, "lr_lk must be 0 or 1");
+  if (cfg->lr_lk && cfg->match_lr) return pipe_fail(D2FE_ERR_INVALID, "lr_lk = 1 needs match_lr = 0: SuperPoint does not run on the right image, so it has no descriptors to match");
+  if (cfg->lr_lk && (cfg->width < 16 || cfg->height < 16)) return pipe_fail(D2FE_ERR_INVALID, "lr_lk needs frames of at least 16 x 16");
   if (h->cfg.max_keypoints < 0) return pipe_fail(D2FE_ERR_UNSUPPORTED, "keep-all handles (max_keypoints = -1) are served by the single-call entry points");
   if (cfg->width > h->cfg.max_width || cfg->height > h->cfg.max_height) return pipe_fail(D2FE_ERR_INVALID, "frame size exceeds the handle's maximum");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
@@ -401,6 +447,7 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   p->parent = h; p->cfg = *cfg;
   h->live_pipes.fetch_add(1);        // from here on d2fe_pipe_destroy (every failure path below goes through it or through `delete p` + the decrement) gives it back
   p->M = M;
+  p->lk = cfg->lr_lk != 0;
   p->nv_inline = cfg->netvlad_inline == 1;
   p->nv_auto = cfg->netvlad_inline == 2 && cfg->lanes > 2;      // one or two lanes: never more than four busy streams, the second stream always
   p->K = cfg->lanes; p->F = cfg->frames; p->C = C; p->NI = 2 * cfg->frames * C; p->W = cfg->width; p->H = cfg->height;
@@ -425,14 +472,29 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   p->o_mq = o; o += up64(MP * cap);
   p->o_mt = o; o += up64(MP * cap);
   p->o_md = o; o += up64(MP * cap);
+  if (p->lk) {
+    p->o_lkp = o; o += up64(NL * cap * 2);
+    p->o_lks = o; o += up64((NL * cap + 3) / 4);
+  }
   p->d2h_words = o;
   p->o_idx = o; o += up64(NI * cap);
+  if (p->lk && C > 1) {
+    p->o_sdesc = o; o += up64(NL * cap * p->D);
+    p->o_skps = o; o += up64(NL * cap * 2);
+    p->o_sscores = o; o += up64(NL * cap);
+    p->o_scnt = o; o += up64(NL);
+    p->o_sidx = o; o += up64(NL * cap);
+  }
   p->blk_words = o;
   const int rc = [&]() -> int {
     const size_t all_words = 64 + (size_t)p->K * 2 * p->blk_words;
     HIP_TRY(hipMalloc(&p->d_all, sizeof(float) * all_words));
     HIP_TRY(hipMemset(p->d_all, 0, sizeof(float) * all_words));
     HIP_TRY(hipMalloc(&p->d_img_all, (size_t)p->W * p->H * p->NI * p->K));
+    if (p->lk) {
+      p->lk_ws_lane = (d2fe_lk_stereo_workspace_bytes((int)NL, p->W, p->H, LK_LEVELS) + 255) / 256 * 256;
+      HIP_TRY(hipMalloc(&p->d_lk_ws, p->lk_ws_lane * p->K));
+    }
     if (p->M > 1) {
       const int rcg = clone_lane(h, p->M, &p->gctx, nullptr, 0, true);
       if (rcg) return rcg;
@@ -483,7 +545,7 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       // for a share of the device leave workgroup slots on every CU to the other lanes
       if (!lane_cus && cfg->lane_cus > 0 && cfg->lane_cus < h->ncu) lane_cus = cfg->lane_cus;
       if (!masked) { ms = spare.first[k]; spare.first[k] = nullptr; if (nv_streams) { L.nv = spare.second[k]; spare.second[k] = nullptr; } }
-      int rc2 = clone_lane(h, p->NI, &L.ctx, ms, lane_cus, cfg->netvlad && p->M == 1);
+      int rc2 = clone_lane(h, p->lk ? (int)NL : p->NI, &L.ctx, ms, lane_cus, cfg->netvlad && p->M == 1);      // lr_lk: the networks see the left images only
       if (rc2) { if (ms) (void)hipStreamDestroy(ms); return rc2; }
       L.s = L.ctx->stream;
       HIP_TRY(hipEventCreateWithFlags(&L.ev_up, hipEventDisableTiming));
@@ -494,6 +556,7 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[0], hipEventDisableTiming));
       HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[1], hipEventDisableTiming));
       L.d_img = p->d_img_all + (size_t)k * p->NI * p->W * p->H;
+      if (p->lk) L.d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
       if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, (size_t)p->W * p->H * p->NI, hipHostMallocDefault));
       for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
     }
@@ -562,6 +625,7 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   if (p->d_gnv) (void)hipFree(p->d_gnv);
   if (p->pin_gnv) (void)hipHostFree(p->pin_gnv);
   if (p->d_img_all) (void)hipFree(p->d_img_all);
+  if (p->d_lk_ws) (void)hipFree(p->d_lk_ws);
   if (p->d_pairs) (void)hipFree(p->d_pairs);
   if (p->d_match_scratch) (void)hipFree(p->d_match_scratch);
   if (p->d_all) (void)hipFree(p->d_all);
@@ -722,6 +786,26 @@ int d2fe_pipe_wait(d2fe_pipe p, int64_t ticket, d2fe_pipe_result* out) {
     out->prev_q = reinterpret_cast<const int32_t*>(B + p->o_mq) + pi * cap; out->prev_t = reinterpret_cast<const int32_t*>(B + p->o_mt) + pi * cap;
     out->prev_dist = B + p->o_md + pi * cap; out->prev_n = reinterpret_cast<const int32_t*>(B + p->o_mn) + pi;
   }
+  return D2FE_OK;
+}
+
+int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_result* out) {
+  if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (!p->lk) return pipe_fail(D2FE_ERR_UNSUPPORTED, "this pipe was created without lr_lk: it has no left -> right LK tracks");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
+  const auto ti = p->tinfo[(size_t)(ticket % (long long)p->tinfo.size())];
+  if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass < 0 || ti.pass + 2 * p->K < p->next_pass)
+    return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the tracks within 2 * lanes passes");
+  if (!ti.waited) return pipe_fail(D2FE_ERR_NOT_READY, "d2fe_pipe_wait has not returned this ticket yet");
+  const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
+  const float* B = p->lanes[k].pin_out[set];
+  const size_t cap = p->cap, r0 = p->C > 1 ? (size_t)ti.j : 0;
+  out->frames = p->F; out->cap = p->cap;
+  out->pts_xy = B + p->o_lkp + r0 * cap * 2;
+  out->status = reinterpret_cast<const uint8_t*>(B + p->o_lks) + r0 * cap;
   return D2FE_OK;
 }
 

@@ -244,7 +244,8 @@ D2FE_API int d2fe_match_batch_device(d2fe_handle h, const d2fe_match_batch* mb, 
 typedef struct d2fe_pipe_s* d2fe_pipe;
 typedef struct {
   int32_t struct_size;      /* sizeof(d2fe_pipe_config) */
-  int32_t lanes;            /* submits in flight, 1..16 (each lane owns its activations: ~58 MB per 640x480 image) */
+  int32_t lanes;            /* submits in flight, 1..16 (each lane owns its activations: ~58 MB per 640x480 image; lr_lk: activations for the left images
+                               only, plus the lane's image pyramids, 1.3125 bytes per pixel of both images = 0.8 MB per 640x480 stereo frame) */
   int32_t frames;           /* stereo frames per submit (>= 1); consecutive in time */
   int32_t width, height;    /* frame size, within the handle's maximum */
   int32_t cap;              /* keypoint capacity per image (rows of the result arrays) */
@@ -285,7 +286,18 @@ typedef struct {
                                gets every frame launched at once (the latency of coalesce = 1), a caller that keeps many frames in flight gets passes
                                that grow up to `coalesce` frames while the device is busy with N others (the throughput of large passes).  2 is the
                                measured choice: one pass running, one queued behind it */
-  int32_t reserved[2];
+  int32_t lr_lk;            /* 1: the reference's DEFAULT stereo path (lr_match_use_lk = true, d2featuretracker.h:61; trackLocalFrames, d2featuretracker.cpp:110-116):
+                               SuperPoint (and NetVLAD) on the LEFT images only; the image pyramids of both images are built on the device and every left
+                               keypoint is tracked left -> right with pyramidal LK (trackLK -> opticalflowTrackPyr, d2featuretracker.cpp:697-752,
+                               opticaltrack_utils.cpp:173-279: forward, reverse, 0.5 px round trip, inBorder; window 21, PYR_LEVEL 2, 30 iterations), stream-ordered
+                               inside the pass (levels + 1 launches whatever `frames` is, no host synchronisation); the results travel with the pass's one D2H
+                               and are read with d2fe_pipe_lk_result_get.  submit() takes the same arguments (the right images are uploaded; only their
+                               pyramids are built).  d2fe_pipe_result keeps its layout: rows of right images have n_kp = 0, the left rows, NetVLAD and the
+                               prev_* lists are bit-identical to the same pipe with lr_lk = 0, match_lr = 0; lr_* are NULL.  Needs match_lr = 0 (the right
+                               image has no descriptors: D2FE_ERR_INVALID otherwise).  Works with any lanes / frames, netvlad, match_prev, pinned_input,
+                               coalesce, coalesce_depth, netvlad_inline, netvlad_group, lane_cus and cu_partition (the LK launches run on the lane's own
+                               stream, CU-masked or not).  0 (d2fe_pipe_default_config): SuperPoint on both images, as before */
+  int32_t reserved[1];
 } d2fe_pipe_config;
 typedef struct {            /* HOST pointers into the lane's pinned block; valid until 2 * lanes further submits */
   int32_t frames, cap, desc_dim, netvlad_dim;
@@ -297,6 +309,15 @@ typedef struct {            /* HOST pointers into the lane's pinned block; valid
   const int32_t* lr_q; const int32_t* lr_t; const float* lr_dist; const int32_t* lr_n;            /* [frames][cap] x3, [frames]; NULL when off */
   const int32_t* prev_q; const int32_t* prev_t; const float* prev_dist; const int32_t* prev_n;    /* prev_t indexes the previous left frame's keypoints */
 } d2fe_pipe_result;
+/* lr_lk = 1: the left -> right LK tracks of a ticket that d2fe_pipe_wait has returned (D2FE_ERR_NOT_READY before that, D2FE_ERR_UNSUPPORTED on a pipe without
+ * lr_lk).  Every left keypoint is tracked: keypoint i of left frame f (d2fe_pipe_result::kps_xy row f, i < n_kp[f]) is at pts_xy[f][i] in the right image when
+ * status[f][i] == 1; slots i >= n_kp[f] hold status 0 and (0, 0).  The reduceVector compaction and the landmark_id >= 0 filter of trackLK
+ * (d2featuretracker.cpp:707-719) stay with the caller, as for d2fe_lk_track. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
+  int32_t frames, cap;
+  const float* pts_xy;      /* [frames][cap][2]  right-image position of left keypoint i of frame f */
+  const uint8_t* status;    /* [frames][cap]     1: forward && reverse && |prev - reverse| <= 0.5 && inBorder (opticaltrack_utils.cpp:260-272) */
+} d2fe_pipe_lk_result;
 D2FE_API void d2fe_pipe_default_config(d2fe_pipe_config* cfg);
 D2FE_API int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out);
 D2FE_API void d2fe_pipe_destroy(d2fe_pipe p);
@@ -314,6 +335,7 @@ D2FE_API int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* r
 /* Blocks until the ticket's frame is complete on the host (launching its pass first if coalescing still holds it back).  Tickets may be waited
  * for in any order, each within 2 * lanes passes (a pass = `coalesce` submits). */
 D2FE_API int d2fe_pipe_wait(d2fe_pipe p, int64_t ticket, d2fe_pipe_result* out);
+D2FE_API int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_result* out);
 
 /* Device-side consumers of a ticket's results: the cross-agent exchange (pack -> all-gather -> gate -> remote matching; the reference broadcasts
  * the frame it has just extracted, loop_net.cpp:24-87, d2featuretracker.cpp:237-310) runs on a stream of its OWN, behind the extraction of the ticket and beside the
@@ -498,6 +520,18 @@ typedef struct {
 } d2fe_lk_pair;
 D2FE_API int d2fe_lk_track_batch(d2fe_handle h, const d2fe_lk_pair* pairs, int npairs, const float* prev_pts,
                                  const float* cur_init, int n_total, int win, int iters, float* cur_pts, uint8_t* status);
+/* The stereo tracks of trackLK (d2featuretracker.cpp:697-752) for callers of d2fe_superpoint_extract_device, and what a pipe with lr_lk = 1 runs: the pyramids of
+ * n_frames left and n_frames right gray frames that are already in HBM (frame f at d_left / d_right + f * image_stride, rows `stride` bytes apart) are built in
+ * d_workspace (d2fe_lk_stereo_workspace_bytes: 2 * n_frames pyramids in the layout of a d2fe_lk_frame, no padding) and keypoint i < d_n_kp[f] of left frame f,
+ * d_kps_xy[f][i], is tracked into right frame f exactly as d2fe_lk_track(left, right, pts, pts, n, WHOLE_IMG_MATCH, 0, win, iters) does (same bits).
+ * d_pts_xy [n_frames][cap][2] and d_status [n_frames][cap] are written for EVERY slot (i >= d_n_kp[f]: status 0, point (0, 0)).  Points and counts are read on
+ * the device: the call only enqueues on `stream` (NULL: the handle's stream) -- max(levels, 1) + 1 launches whatever n_frames is, no allocation, no
+ * synchronisation.  Parameter ranges as d2fe_lk_track_batch (win odd 3..23, levels 0..7, iters >= 1).  d2fe_lk_stereo_workspace_bytes is host arithmetic
+ * (no GPU needed; 0 for a geometry the call would refuse). */
+D2FE_API size_t d2fe_lk_stereo_workspace_bytes(int n_frames, int width, int height, int levels);
+D2FE_API int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint8_t* d_right, int n_frames, int width, int height, int stride,
+                                         size_t image_stride, const float* d_kps_xy /*[n_frames][cap][2]*/, const int32_t* d_n_kp /*[n_frames]*/, int cap,
+                                         int levels, int win, int iters, void* d_workspace, float* d_pts_xy, uint8_t* d_status, void* stream);
 /* detectFastByRegion (opticaltrack_utils.cpp:444-493): cv::cuda::FastFeatureDetector(threshold, nonmax, TYPE_9_16,
  * max_npoints = features) on each of the cols x rows regions of level 0, sorted by response, top `features`.
  * response (optional) receives the FAST scores. */
@@ -661,7 +695,7 @@ D2FE_API int d2fe_quad_undistort_device(d2fe_handle h, const uint8_t* d_raw, int
 enum {
   D2FE_PROF_CONV1A = 0, D2FE_PROF_CONV1B, D2FE_PROF_CONV2A, D2FE_PROF_CONV2B, D2FE_PROF_CONV3A, D2FE_PROF_CONV3B,
   D2FE_PROF_CONV4A, D2FE_PROF_CONV4B, D2FE_PROF_CONVPADA, D2FE_PROF_CONVPB, D2FE_PROF_CONVDB, D2FE_PROF_SOFTMAX,
-  D2FE_PROF_SELECT, D2FE_PROF_SAMPLE, D2FE_PROF_MATCH, D2FE_PROF_NETVLAD, D2FE_PROF_COUNT
+  D2FE_PROF_SELECT, D2FE_PROF_SAMPLE, D2FE_PROF_MATCH, D2FE_PROF_NETVLAD, D2FE_PROF_LK, D2FE_PROF_COUNT
 };
 D2FE_API int d2fe_profile_enable(d2fe_handle h, int mode);
 D2FE_API int d2fe_profile_read(d2fe_handle h, float* ms /*[D2FE_PROF_COUNT]*/, int32_t* launches /*[D2FE_PROF_COUNT]*/);

@@ -190,12 +190,18 @@ struct StereoFrameResult {
   std::vector<float> netvlad;                        // empty when the pipe runs without NetVLAD
   std::vector<DMatch> left_right;                    // queryIdx: left keypoint, trainIdx: right keypoint
   std::vector<DMatch> left_prev;                     // queryIdx: left keypoint, trainIdx: keypoint of the PREVIOUS left frame
+  // cfg.lr_lk = 1 (lr_match_use_lk, the reference's default): the left -> right LK track of EVERY left keypoint, uncompacted -- lk_right[i] is where kps_left[i]
+  // sits in the right image when lk_status[i] != 0 (what trackLK, d2featuretracker.cpp:697-752, hands to reduceVector); kps_right / left_right stay empty
+  std::vector<Point2f> lk_right;
+  std::vector<uint8_t> lk_status;
 };
 class StereoPipe {
  public:
-  // cfg: d2fe_pipe_default_config() + the fields the caller sets (lanes, width, height, cap, netvlad, coalesce, coalesce_depth, ...); frames is forced to 1
+  // cfg: d2fe_pipe_default_config() + the fields the caller sets (lanes, width, height, cap, netvlad, coalesce, coalesce_depth, lr_lk (with match_lr = 0), ...);
+  // frames is forced to 1
   StereoPipe(d2fe_handle h, d2fe_pipe_config cfg) {
     cfg.frames = 1;
+    lr_lk_ = cfg.lr_lk != 0;
     if (d2fe_pipe_create(h, &cfg, &p_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_create: %s\n", d2fe_last_error()); p_ = nullptr; }
   }
   ~StereoPipe() { if (p_) d2fe_pipe_destroy(p_); }
@@ -228,6 +234,14 @@ class StereoPipe {
     };
     matches(r.lr_q, r.lr_t, r.lr_dist, r.lr_n, out.left_right);
     matches(r.prev_q, r.prev_t, r.prev_dist, r.prev_n, out.left_prev);
+    out.lk_right.clear(); out.lk_status.clear();
+    if (lr_lk_) {
+      d2fe_pipe_lk_result lk;
+      if (d2fe_pipe_lk_result_get(p_, ticket, &lk) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_lk_result_get: %s\n", d2fe_last_error()); return false; }
+      const int n = r.n_kp[0];
+      for (int j = 0; j < n; ++j) out.lk_right.emplace_back(lk.pts_xy[2 * j], lk.pts_xy[2 * j + 1]);
+      out.lk_status.assign(lk.status, lk.status + n);
+    }
     return true;
   }
   // d2fe_pipe_stream_placement: the hardware-pipe class measured for every lane's (own, second) stream; the return value = classes told apart (0: not measured)
@@ -244,6 +258,7 @@ class StereoPipe {
 
  private:
   d2fe_pipe p_ = nullptr;
+  bool lr_lk_ = false;
 };
 
 // d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
