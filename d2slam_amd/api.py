@@ -164,7 +164,11 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
-    "d2fe_debug_netvlad_plan"]
+    "d2fe_debug_netvlad_plan", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset"]
+# enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
+# most recent Winograd launch, not counts)
+REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
+           "match_nw4", "match_nw2", "nv_gmerge", "nv_front_tpw", "wino_last_grid", "wino_last_total"]
 
 
 def _preload_hip_runtime():
@@ -215,6 +219,8 @@ def _open_library(path, dev):
             lib.d2fe_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
             for nm in ("d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino", "d2fe_debug_pack_netvlad", "d2fe_debug_match_stamps"):
                 getattr(lib, nm).restype = C.c_long
+            lib.d2fe_debug_regime_counts.argtypes = [C.c_void_p, C.c_int]
+            lib.d2fe_debug_regime_reset.argtypes = []; lib.d2fe_debug_regime_reset.restype = None
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
         lib.d2fe_half_move_cols.argtypes = [C.c_int, C.c_double]
@@ -789,6 +795,24 @@ class DevFrontEnd(FrontEnd):
 
     def __init__(self, cfg: SuperPointConfig):
         super().__init__(cfg, dev=True)
+
+    @staticmethod
+    def regime_counts(reset=False):
+        """{regime name: launches since the last reset} of the development library's process-wide launch-regime record (REGIMES; include/d2fe_debug.h):
+        which size-dependent code path the Winograd, matcher and NetVLAD launchers took.  Needs no handle (pipes and handles of this process share it)."""
+        lib = load_library(dev=True)
+        n = int(lib.d2fe_debug_regime_counts(None, 0))
+        if n != len(REGIMES):
+            raise D2FEError(-1, "api.REGIMES (%d names) out of sync with enum d2fe_regime (%d entries)" % (len(REGIMES), n))
+        out = (C.c_longlong * n)()
+        lib.d2fe_debug_regime_counts(out, n)
+        if reset:
+            lib.d2fe_debug_regime_reset()
+        return {k: int(out[i]) for i, k in enumerate(REGIMES)}
+
+    @staticmethod
+    def regime_reset():
+        load_library(dev=True).d2fe_debug_regime_reset()
 
 
 class StereoPipe:

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <array>
+#include <atomic>
 #include <deque>
 #include <map>
 #include <mutex>
@@ -53,6 +54,17 @@ int upload(const void* src, size_t bytes, void** dst) {
   return D2FE_OK;
 }
 }  // namespace d2fe
+
+#ifdef D2FE_DEVTOOLS
+// launch-regime record (kernels.h: D2FE_REGIME): process-wide, written by the launchers from any thread (pipe lanes)
+namespace {
+std::atomic<long long> g_regime[D2FE_REGIME_COUNT];
+}
+namespace d2fe {
+void regime_note(int regime) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].fetch_add(1, std::memory_order_relaxed); }
+void regime_set(int regime, long long value) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].store(value, std::memory_order_relaxed); }
+}  // namespace d2fe
+#endif
 
 namespace {
 
@@ -1277,6 +1289,14 @@ int d2fe_half_image_filter(const float* pts_xy, int n, int require_left, int wid
 }
 
 #ifdef D2FE_DEVTOOLS      /* development library only: include/d2fe_debug.h */
+int d2fe_debug_regime_counts(long long* out, int max) {
+  for (int i = 0; out && i < max && i < D2FE_REGIME_COUNT; ++i) out[i] = g_regime[i].load(std::memory_order_relaxed);
+  return D2FE_REGIME_COUNT;
+}
+void d2fe_debug_regime_reset(void) {
+  for (auto& c : g_regime) c.store(0, std::memory_order_relaxed);
+}
+
 long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_bytes) {
   if (!h || !name || !dst) return fail(D2FE_ERR_INVALID, "null argument");
   if (h->last_n == 0) return fail(D2FE_ERR_NOT_READY, "no extract call yet");
@@ -1377,7 +1397,12 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
   std::vector<float> pk(packed_weight_floats_wino(cout_pad, cin)), bp(cout_pad, 0.f);
   pack_weights_wino(weight, cout, cin, cout_pad, pk.data());
   memcpy(bp.data(), bias, sizeof(float) * cout);
-  auto launch = [&](const ConvArgs& ca) { return launch_conv_wino(cin, pool != 0, relu != 0, cout_pad, ca, h->stream); };
+  // as a pass of run_superpoint: the work counter is zero when the launch starts (the last of the handle's 64, which no layer of the network uses)
+  int* const wctr = h->wino_dynamic ? h->work_ctrs + 63 : nullptr;
+  auto launch = [&](const ConvArgs& ca) {
+    if (wctr) { const hipError_t e = hipMemsetAsync(wctr, 0, sizeof(int), h->stream); if (e != hipSuccess) return e; }
+    return launch_conv_wino(cin, pool != 0, relu != 0, cout_pad, ca, h->stream);
+  };
   float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = [&]() -> int {
@@ -1395,6 +1420,7 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
     a.cout_real = cout; a.wpack = d_w; a.bias = d_b; a.H = H; a.W = W; a.n_img = n;
     a.in_img_stride = (long)H * W * cin; a.out_img_stride = (long)Ho * Wo * cout; a.zeros = h->zeros; a.ncu = h->ncu;
     a.ablate = d2fe_dev_env("D2FE_ABLATE", 0);
+    a.work_ctr = wctr;
     HIP_TRY(launch(a));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(out, d_out, out_fl * 4, hipMemcpyDeviceToHost));

@@ -128,7 +128,7 @@ __device__ __forceinline__ void wino_body(const ConvArgs& a, int nbx, int nby, i
   // of the matrix pipe (issue arbitration is by age; measured with D2FE_ABLATE=256), so with an equal split it is done early and its
   // partner runs the tail alone, every MFMA-free phase exposed.
   const int tstride = gridDim.x;
-  const bool dyn = a.work_ctr != nullptr && total >= 48 * tstride;      // short walks (10-40 items per workgroup) gain nothing from claiming (measured)
+  const bool dyn = wino_claims_items(a.work_ctr, total, tstride);      // short walks (10-40 items per workgroup) gain nothing from claiming (measured)
   int icur = blockIdx.x, inxt = icur + tstride;                  // indices >= total: no such item
   int* claim_slot = reinterpret_cast<int*>(FUSE ? wlds + 8 * (2 * 4 * (FUSE ? 272 : 256)) + 64 : wlds + WR * WCHUNK + WXCHN);
 
@@ -608,6 +608,18 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(ConvArg
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// development library: the walk a launch of `grid` workgroups over `total` items takes, for d2fe_debug_regime_counts (the claim rule is the kernel's own)
+static inline void wino_note_regime(int nt, bool fused, const ConvArgs& a, int total, int grid) {
+#ifdef D2FE_DEVTOOLS
+  const bool claimed = wino_claims_items(a.work_ctr, total, grid);
+  if (nt == 1) D2FE_REGIME(grid == total ? D2FE_REGIME_WINO_NT1_ONE : claimed ? D2FE_REGIME_WINO_NT1_CLAIMED : D2FE_REGIME_WINO_NT1_STATIC);
+  else D2FE_REGIME(grid == total ? D2FE_REGIME_WINO_NT2_ONE : !claimed ? D2FE_REGIME_WINO_NT2_STATIC
+                   : fused ? D2FE_REGIME_WINO_NT2_CLAIMED_FUSED1B : D2FE_REGIME_WINO_NT2_CLAIMED_RING);
+  D2FE_REGIME_SET(D2FE_REGIME_WINO_LAST_GRID, grid);
+  D2FE_REGIME_SET(D2FE_REGIME_WINO_LAST_TOTAL, total);
+#endif
+}
+
 hipError_t launch_conv_wino(int cin, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
   if (cout_pad % 64 || (a.in_cstride & 3) || (a.in_coff & 3)) return hipErrorInvalidValue;
   // buffer addressing: 32-bit byte offsets inside one image's tensor, 0x80000000 must stay out of range
@@ -636,6 +648,7 @@ hipError_t launch_conv_wino(int cin, bool pool, bool relu, int cout_pad, const C
   const int wg_per_cu = NTsel == 1 ? 3 : 2;
   const int grid = total < wg_per_cu * ncu ? total : wg_per_cu * ncu;
   const size_t lds = (size_t)(WR * WCHUNK + (NTsel == 1 ? WXCH / 2 : WXCH)) * sizeof(float) + 16;      // ring + exchange area + the claim slot
+  wino_note_regime(NTsel, false, a, total, grid);
 #define D2FE_WINO_K(K)                                                                                       \
   do {                                                                                                      \
     auto k = K;                                                                                             \
@@ -720,6 +733,7 @@ hipError_t launch_conv_wino_fused1b(int cout_pad, const ConvArgs& a, hipStream_t
   const int grid = total < 2 * ncu ? total : 2 * ncu;
   constexpr size_t lds = (size_t)8 * 2 * 4 * 272 * sizeof(float) + 256 + 16;      // the 64-channel patch (the exchange area, 48 KiB, reuses it) + the 12 x 20 frame bytes
   static_assert(lds >= (size_t)WXCH * sizeof(float), "exchange area must fit into the patch buffer");
+  wino_note_regime(2, true, a, total, grid);
   auto k = conv_wino_kernel<64, true, true, 0, 1, true>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;

@@ -17,7 +17,24 @@ static inline int d2fe_dev_env(const char*, int dflt) { return dflt; }
 #define D2FE_STAMP(buf, wg, i) do {} while (0)
 #endif
 
+// Launch-regime record (development library only; include/d2fe_debug.h, d2fe_debug_regime_counts): the launchers note which of their
+// size-dependent code paths a launch took, so that a test can prove the path it claims to cover ran.  The product library compiles the
+// note to nothing: no symbol, no counter, no branch.
+#ifdef D2FE_DEVTOOLS
+#include "../../include/d2fe_debug.h"
+namespace d2fe { void regime_note(int regime); void regime_set(int regime, long long value); }      // api.hip
+#define D2FE_REGIME(r) ::d2fe::regime_note(r)
+#define D2FE_REGIME_SET(r, v) ::d2fe::regime_set(r, v)
+#else
+#define D2FE_REGIME(r) do {} while (0)
+#define D2FE_REGIME_SET(r, v) do {} while (0)
+#endif
+
 namespace d2fe {
+
+// The persistent Winograd kernels (conv_wino.hip) CLAIM their work items from a device counter instead of striding through them when the launch has a
+// counter and every workgroup walks at least 48 items.  One definition for the kernel (grid = gridDim.x) and for the launcher's regime record.
+__host__ __device__ inline bool wino_claims_items(const int* work_ctr, int total, int grid) { return work_ctr != nullptr && total >= 48 * grid; }
 
 // ---- conv stack -----------------------------------------------------------------------------------
 // Activations: NHWC fp32 in HBM, addressed as base + ((img*H + y)*W + x)*cstride + coff + c.

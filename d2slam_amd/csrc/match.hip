@@ -586,7 +586,9 @@ hipError_t launch_match(const MatchArgs& m, hipStream_t s) {
   // four waves per workgroup split a tile's train rows four ways (half the latency of a workgroup) but only two such workgroups fit a
   // CU (256 registers per lane): used while the whole launch is resident at once
   const int ncu = m.ncu > 0 ? m.ncu : 256;
-  return nwg <= 2L * ncu ? launch_match_nw<4>(m, tiles, nwg, s) : launch_match_nw<2>(m, tiles, nwg, s);
+  if (nwg <= 2L * ncu) { D2FE_REGIME(D2FE_REGIME_MATCH_NW4); return launch_match_nw<4>(m, tiles, nwg, s); }
+  D2FE_REGIME(D2FE_REGIME_MATCH_NW2);
+  return launch_match_nw<2>(m, tiles, nwg, s);
 }
 
 }  // namespace d2fe

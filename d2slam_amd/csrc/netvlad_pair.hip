@@ -744,6 +744,7 @@ static hipError_t launch_fpair_t(const NvBlockArgs& a, int n, hipStream_t s) {
   if (e != hipSuccess) return e;
   const long tiles = (long)((a.Wo + a.tw - 1) / a.tw) * ((a.Ho + a.th - 1) / a.th);
   const int tpw = a.tpw > 0 ? a.tpw : 1;
+  if (tpw > 1) D2FE_REGIME(D2FE_REGIME_NV_FRONT_TPW);
   hipLaunchKernelGGL(k, dim3((unsigned)((tiles + tpw - 1) / tpw), n, 1), dim3(256), lds, s, a);
   return hipGetLastError();
 }
@@ -783,6 +784,7 @@ hipError_t launch_nv_pblock(const NvBlockArgs& a_in, int n, int groups, hipStrea
   if (a.in_slabs > 1 && !nvp_multi_in(nk)) return hipErrorInvalidValue;
   if (a.gmerge > 1) {                    // `groups` stays the number of groups of the summation order; the launch has ceil(groups / gmerge) workgroup groups
     const int wg = (groups + a.gmerge - 1) / a.gmerge;
+    D2FE_REGIME(D2FE_REGIME_NV_GMERGE);
 #define X(K, T, M) if (nk == K && nt == T) return launch_pblock_t<T, K, M>(a, n, wg, s);
     NVP_MERGE_SHAPES(X)
 #undef X

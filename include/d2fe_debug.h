@@ -32,7 +32,9 @@ D2FE_API long d2fe_debug_netvlad_stamps(d2fe_handle h, unsigned long long* dst, 
 D2FE_API int d2fe_debug_netvlad_plan(const d2fe_nv_layer* layers, int n_layers, int proj_dim, int* out, int max_steps);
 /* One 3x3 / pad 1 layer (cin 64 or 128, ReLU, optional 2x2 max-pool) through the Winograd kernels of D2FE_PREC_F32_WINO, host
  * NHWC buffers in and out; iters > 0 also times `iters` back-to-back launches (HIP events on the handle's stream).  For the
- * layer-level parity tests (tests/test_wino.py) and tools/; the product path is d2fe_superpoint_extract*. */
+ * layer-level parity tests (tests/test_wino.py, tests/test_launch_regimes.py) and tools/; the product path is d2fe_superpoint_extract*.  Like a pass
+ * of the extractor, every launch gets a zeroed work counter unless D2FE_WINO_DYNAMIC=0 was set when the handle was created, so a large enough layer
+ * takes the claimed walk. */
 /* The host-side weight transform of that mode (U = G g G^T, packed [32-channel group][k-step][row i][lane][4]); needs no GPU.
  * Returns the number of floats written (16 * cin * cout rounded up to 64 channels). */
 /* Tile shape the NetVLAD block launchers pick for an Ho x Wo output map (needs no GPU): kind 0 stride-1 blocks, 1 the first block (stride = the first
@@ -50,6 +52,30 @@ D2FE_API int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int 
  * environment turns that off).  Returns how many graphs the handle holds; *rejected (may be NULL) = geometries whose capture failed and which
  * therefore keep launching kernel by kernel (diagnostic). */
 D2FE_API int d2fe_debug_graph_count(d2fe_handle h, int* rejected);
+
+/* Launch-regime record.  Several launchers switch to another code path once a launch is large; the development library counts, process-wide,
+ * how many launches each of these paths has taken, so that a test can prove that the path it means to cover ran (the count comes from the
+ * launcher, the Winograd claim rule from the one function the kernel itself evaluates).  A launch is counted when the launcher is called: a
+ * cached hipGraph that replays a launch sequence counts it once, at capture. */
+enum d2fe_regime {
+  D2FE_REGIME_WINO_NT1_ONE = 0,          /* Winograd, 32-channel items (NT = 1), one item per workgroup (grid == total) */
+  D2FE_REGIME_WINO_NT1_STATIC,           /*   ... persistent workgroups striding through the items */
+  D2FE_REGIME_WINO_NT1_CLAIMED,          /*   ... persistent workgroups claiming items from the device counter (only with D2FE_WINO_NT=1 forced on a large launch) */
+  D2FE_REGIME_WINO_NT2_ONE,              /* Winograd, 64-channel items (NT = 2), one item per workgroup; ring kernels and the fused conv1a + conv1b kernel */
+  D2FE_REGIME_WINO_NT2_STATIC,           /*   ... static walk; ring kernels and the fused kernel */
+  D2FE_REGIME_WINO_NT2_CLAIMED_RING,     /*   ... claimed walk of a ring kernel (launch_conv_wino) */
+  D2FE_REGIME_WINO_NT2_CLAIMED_FUSED1B,  /*   ... claimed walk of the fused conv1a + conv1b kernel (launch_conv_wino_fused1b) */
+  D2FE_REGIME_MATCH_NW4,                 /* matcher, four waves per workgroup (the whole launch resident at once) */
+  D2FE_REGIME_MATCH_NW2,                 /* matcher, two waves per workgroup */
+  D2FE_REGIME_NV_GMERGE,                 /* NetVLAD nv_pblock_kernel launches in which a workgroup walks several channel groups (gmerge > 1) */
+  D2FE_REGIME_NV_FRONT_TPW,              /* NetVLAD nv_fpair_kernel launches with several tiles per workgroup (front_tpw > 1) */
+  D2FE_REGIME_WINO_LAST_GRID,            /* not a count: workgroups of the most recent Winograd launch ... */
+  D2FE_REGIME_WINO_LAST_TOTAL,           /* ... and its work items */
+  D2FE_REGIME_COUNT
+};
+/* Copies min(max, D2FE_REGIME_COUNT) entries of the record to out (may be NULL with max 0) and returns D2FE_REGIME_COUNT. */
+D2FE_API int d2fe_debug_regime_counts(long long* out, int max);
+D2FE_API void d2fe_debug_regime_reset(void);
 
 /* The wall_clock64() phase stamps [workgroup][16] of the last d2fe_match_batch_device launch made with D2FE_MATCH_STAMPS=1 in the environment
  * (tools/match_stamps.py).  Returns the number of workgroups copied or <0. */

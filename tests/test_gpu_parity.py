@@ -255,13 +255,8 @@ SATURATED = ["eight_identical_train_rows", "twenty_identical_train_rows", "all_e
              "both_sets_all_equal"]
 
 
-@pytest.mark.parametrize("case", SATURATED)
-def test_match_saturated_candidate_lists_are_exact(api, orc, case):
-    """Many train rows within fp32 round-off of the nearest distance (repeated texture, a frame against a near-copy): every row the
-    Gram-trick distance cannot separate from the second neighbour must be re-ranked exactly, and beyond the kernel's 16 candidate slots
-    per query the exact scan of every row must run (match.hip header).
-    Indices AND distances bitwise against the oracle and, when present, the reference's own matchKNN (oracle/_ref)."""
-    from oracle import ref
+def saturated_pair(case):
+    """the descriptor sets of one SATURATED case (tests/test_launch_regimes.py runs them again as a batch of 64 pairs)"""
     rng = np.random.RandomState(11)
     a = _unit(rng.randn(150, 256)); b = _unit(rng.randn(180, 256))
     if case == "eight_identical_train_rows":
@@ -279,6 +274,17 @@ def test_match_saturated_candidate_lists_are_exact(api, orc, case):
         a = _unit(base[rng.randint(0, 30, 150)] + 0.05 * rng.randn(150, 256))
     elif case == "both_sets_all_equal":
         a[:] = a[0]; b[:] = a[0]
+    return a, b
+
+
+@pytest.mark.parametrize("case", SATURATED)
+def test_match_saturated_candidate_lists_are_exact(api, orc, case):
+    """Many train rows within fp32 round-off of the nearest distance (repeated texture, a frame against a near-copy): every row the
+    Gram-trick distance cannot separate from the second neighbour must be re-ranked exactly, and beyond the kernel's 16 candidate slots
+    per query the exact scan of every row must run (match.hip header).
+    Indices AND distances bitwise against the oracle and, when present, the reference's own matchKNN (oracle/_ref)."""
+    from oracle import ref
+    a, b = saturated_pair(case)
     fe = _fe(api, 64, 64, 1, api.PREC_F32)
     fe.match_fallback_rows(reset=True)
     for ratio in (0.8, 1.5):          # 1.5: ties pass the ratio test, so a wrong index among equals would surface as a wrong match
@@ -603,7 +609,10 @@ def test_netvlad_pair_kernel_variants(api, orc, monkeypatch, env):
         monkeypatch.setenv(k, v)
     fe = api.DevFrontEnd(api.SuperPointConfig(input_width=W, input_height=H, max_batch=2))
     fe.load_netvlad(nv)
+    api.DevFrontEnd.regime_reset()
     got = fe.netvlad(imgs)
+    if "D2FE_NV_FRONT_TPW" in env:      # the launch-regime record (include/d2fe_debug.h): the forced variant is the one that ran
+        assert api.DevFrontEnd.regime_counts()["nv_front_tpw"] >= 1
     assert np.array_equal(got, base), np.abs(got - base).max()
     refs = [orc.netvlad_forward(imgs[i], nv, return_layers=True) for i in range(2)]
     for li in range(len(nv["layers"])):
