@@ -128,6 +128,24 @@ class _QuadPipeResult(C.Structure):
                 ("prev_q", C.c_void_p), ("prev_t", C.c_void_p), ("prev_dist", C.c_void_p), ("prev_n", C.c_void_p)]
 
 
+class _QuadDeviceResult(C.Structure):
+    _fields_ = [("quads", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
+                ("d_kps_xy", C.c_void_p), ("d_scores", C.c_void_p), ("d_desc", C.c_void_p), ("d_n_kp", C.c_void_p), ("d_netvlad", C.c_void_p)]
+
+
+class _QuadExchangeConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("world", C.c_int32), ("rank", C.c_int32), ("wire", C.c_int32), ("loopback", C.c_int32), ("slots", C.c_int32),
+                ("own_stream", C.c_int32), ("timing", C.c_int32), ("mode", C.c_int32), ("reserved0", C.c_int32), ("gate_thres", C.c_double), ("ratio", C.c_double),
+                ("all_gather", ALL_GATHER_FN), ("all_gather_user", C.c_void_p), ("reserved", C.c_int32 * 6)]
+
+
+class _QuadExchangeResult(C.Structure):
+    _fields_ = [("ticket", C.c_int64), ("njobs", C.c_int32), ("npairs", C.c_int32), ("pairs_per_job", C.c_int32), ("cap", C.c_int32),
+                ("job_rank", C.c_void_p), ("job_quad", C.c_void_p), ("q_idx", C.c_void_p), ("t_idx", C.c_void_p), ("dist", C.c_void_p), ("n_match", C.c_void_p),
+                ("local_view", C.c_void_p), ("remote_view", C.c_void_p), ("dir_prev", C.c_void_p), ("gate_sims", C.c_void_p), ("gate_n", C.c_int32),
+                ("phase_ms", C.c_float * 5)]
+
+
 def _quad_maps(maps, device):
     """d2fe_quad_maps from four (mapx, mapy, gain or None) raw addresses"""
     m = _QuadMaps()
@@ -158,6 +176,9 @@ EXPORTS = [
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
     "d2fe_quad_pipe_default_config", "d2fe_quad_pipe_create", "d2fe_quad_pipe_destroy", "d2fe_quad_pipe_submit", "d2fe_quad_pipe_wait",
     "d2fe_quad_pipe_lanes", "d2fe_quad_pipe_geometry", "d2fe_quad_undistort_device",
+    "d2fe_quad_device_view", "d2fe_quad_device_release", "d2fe_quad_lane_stream", "d2fe_quad_handle",
+    "d2fe_quad_exchange_default_config", "d2fe_quad_exchange_create", "d2fe_quad_exchange_destroy", "d2fe_quad_exchange_enqueue", "d2fe_quad_exchange_collect",
+    "d2fe_quad_exchange_jobs", "d2fe_quad_exchange_pairs", "d2fe_quad_exchange_block_bytes", "d2fe_quad_exchange_stream", "d2fe_quad_exchange_gathered", "d2fe_quad_exchange_job_layout",
     "d2fe_exchange_default_config", "d2fe_exchange_create", "d2fe_exchange_destroy", "d2fe_exchange_enqueue", "d2fe_exchange_collect", "d2fe_exchange_pairs",
     "d2fe_exchange_block_bytes", "d2fe_exchange_stream", "d2fe_rccl_load", "d2fe_rccl_path", "d2fe_rccl_unique_id", "d2fe_rccl_comm_init_rank", "d2fe_rccl_comm_destroy"]
 # the development library (lib/libd2fe_hip_dev.so, include/d2fe_debug.h) exports these on top: test hooks and kernel diagnostics
@@ -328,6 +349,20 @@ def _open_library(path, dev):
         lib.d2fe_quad_pipe_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_quad_undistort_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p,
                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_device_view.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_device_release.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_quad_lane_stream.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_quad_handle.argtypes = [C.c_void_p]; lib.d2fe_quad_handle.restype = C.c_void_p
+        lib.d2fe_quad_exchange_default_config.argtypes = [C.c_void_p]; lib.d2fe_quad_exchange_default_config.restype = None
+        lib.d2fe_quad_exchange_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_exchange_destroy.argtypes = [C.c_void_p]; lib.d2fe_quad_exchange_destroy.restype = None
+        lib.d2fe_quad_exchange_enqueue.argtypes = [C.c_void_p, C.c_int64, C.c_int]
+        lib.d2fe_quad_exchange_collect.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for nm in ("d2fe_quad_exchange_jobs", "d2fe_quad_exchange_pairs", "d2fe_quad_exchange_block_bytes"):
+            getattr(lib, nm).argtypes = [C.c_void_p]
+        lib.d2fe_quad_exchange_stream.argtypes = [C.c_void_p]; lib.d2fe_quad_exchange_stream.restype = C.c_void_p
+        lib.d2fe_quad_exchange_gathered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_exchange_job_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         lib.d2fe_exchange_default_config.argtypes = [C.c_void_p]; lib.d2fe_exchange_default_config.restype = None
         lib.d2fe_exchange_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_exchange_destroy.argtypes = [C.c_void_p]; lib.d2fe_exchange_destroy.restype = None
@@ -1041,6 +1076,22 @@ class QuadPipe:
             raise ValueError("QuadPipe.submit: expected [%d][4][%d][%d] u8, got %s" % (self.quads, self.raw_height, self.raw_width, raw.shape))
         return self.submit_ptr(raw.ctypes.data)
 
+    def device_view(self, ticket, stream):
+        """DEVICE pointers into the ticket's result block (quad-major rows q * 4 + c) for a consumer on `stream` (a raw hipStream_t, not 0): the stream is made to
+        wait for the ticket's SuperPoint and NetVLAD results; release with device_release(ticket, stream) once the consumer's work is queued (d2fe_quad_device_view)."""
+        r = _QuadDeviceResult()
+        _check(self._lib.d2fe_quad_device_view(self._p, C.c_int64(ticket), C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def device_release(self, ticket, stream):
+        _check(self._lib.d2fe_quad_device_release(self._p, C.c_int64(ticket), C.c_void_p(stream)))
+
+    def lane_stream(self, ticket):
+        """the hipStream_t (int) of the lane that ran the ticket's submit"""
+        st = C.c_void_p()
+        _check(self._lib.d2fe_quad_lane_stream(self._p, C.c_int64(ticket), C.byref(st)))
+        return st.value
+
     def wait_raw(self, ticket):
         _check(self._lib.d2fe_quad_pipe_wait(self._p, C.c_int64(ticket), C.byref(self._res)))
         return self._res
@@ -1433,6 +1484,83 @@ class Exchange:
     def close(self):
         if getattr(self, "_x", None) and self._x.value:
             self._lib.d2fe_exchange_destroy(self._x)
+            self._x = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+QUAD_MODE = {"all2all": 0, "gated": 1}
+QUAD_EXCHANGE_PHASES = ("pack_blocks", "all_gather", "decode_prepare", "match_remote", "release_and_d2h")
+
+
+def quad_exchange_job_layout(world, rank, quads, loopback=False):
+    """d2fe_quad_exchange_job_layout: ([remote rank], [quad frame]) of every job of one rank; needs no device"""
+    lib = load_library()
+    n = int(lib.d2fe_quad_exchange_job_layout(int(world), int(rank), int(quads), int(bool(loopback)), None, None, 0))
+    _check(n if n < 0 else 0)
+    jr, jq = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    lib.d2fe_quad_exchange_job_layout(int(world), int(rank), int(quads), int(bool(loopback)), jr, jq, n)
+    return list(jr[:n]), list(jq[:n])
+
+
+class QuadExchange:
+    """d2fe_quad_exchange_*: device view -> pack one block per view -> ONE all-gather -> [int8: decode] -> ONE prepare launch (gate, matcher table, counter) ->
+    ONE matcher launch -> release -> ONE D2H per ticket of a QuadPipe, on one stream of its own (own_stream=True) or on the producing lane's stream.  comm: an
+    ncclComm_t address (rccl_comm_init_rank, or D2SLAM's own) or None with `all_gather` = a Python callable (user, d_send, d_recv, bytes_per_rank, stream) -> 0.
+    Job j = (remote rank, quad frame), rank-major; all2all: problem j * 16 + lv * 4 + rv, gated: problem j * 4 + k (include/d2fe.h has the layout)."""
+
+    def __init__(self, quad_pipe, comm=None, world=1, rank=0, wire="fp32", mode="all2all", loopback=False, slots=4, own_stream=True, timing=False, gate_thres=0.8,
+                 ratio=0.8, all_gather=None):
+        self._lib = quad_pipe._lib
+        self._pipe = quad_pipe
+        c = _QuadExchangeConfig()
+        self._lib.d2fe_quad_exchange_default_config(C.byref(c))
+        c.world, c.rank, c.wire, c.mode, c.loopback, c.slots = int(world), int(rank), WIRE[wire], QUAD_MODE[mode], int(bool(loopback)), int(slots)
+        c.own_stream, c.timing, c.gate_thres, c.ratio = int(bool(own_stream)), int(bool(timing)), float(gate_thres), float(ratio)
+        self._cb = ALL_GATHER_FN(all_gather) if all_gather is not None else ALL_GATHER_FN()
+        c.all_gather = self._cb
+        self._x = C.c_void_p()
+        _check(self._lib.d2fe_quad_exchange_create(quad_pipe._p, C.c_void_p(comm) if comm else None, C.byref(c), C.byref(self._x)))
+        self.njobs = int(self._lib.d2fe_quad_exchange_jobs(self._x))
+        self.npairs = int(self._lib.d2fe_quad_exchange_pairs(self._x))
+        self.block_bytes = int(self._lib.d2fe_quad_exchange_block_bytes(self._x))
+        self.slots, self.timing, self.mode = int(slots), bool(timing), mode
+        self._res = _QuadExchangeResult()
+
+    @property
+    def stream(self):
+        """own_stream=True: that hipStream_t (int), else None"""
+        return self._lib.d2fe_quad_exchange_stream(self._x)
+
+    def gathered(self, slot):
+        """(fp32 blocks, wire blocks): device addresses of the slot's gathered blocks [world][4 quads] (d2fe_quad_exchange_gathered)"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self._lib.d2fe_quad_exchange_gathered(self._x, int(slot), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def enqueue(self, ticket, slot):
+        _check(self._lib.d2fe_quad_exchange_enqueue(self._x, int(ticket), int(slot)))
+
+    def collect(self, slot):
+        """blocks until the slot's results are in host memory; numpy VIEWS into the pinned slot (valid until the slot is enqueued again)"""
+        r = self._res
+        _check(self._lib.d2fe_quad_exchange_collect(self._x, int(slot), C.byref(r)))
+        nj, n, cap = int(r.njobs), int(r.npairs), int(r.cap)
+        f, i = np.float32, np.int32
+        return {"ticket": int(r.ticket), "njobs": nj, "npairs": n, "pairs_per_job": int(r.pairs_per_job), "cap": cap,
+                "job_rank": _pinned_view(r.job_rank, (nj,), i), "job_quad": _pinned_view(r.job_quad, (nj,), i),
+                "mq": _pinned_view(r.q_idx, (n, cap), i), "mt": _pinned_view(r.t_idx, (n, cap), i), "md": _pinned_view(r.dist, (n, cap), f),
+                "mn": _pinned_view(r.n_match, (n,), i), "local_view": _pinned_view(r.local_view, (n,), i), "remote_view": _pinned_view(r.remote_view, (n,), i),
+                "dir_prev": _pinned_view(r.dir_prev, (nj,), i), "sims": _pinned_view(r.gate_sims, (nj, 4), f), "gate_n": int(r.gate_n),
+                "phase_ms": [float(v) for v in r.phase_ms] if self.timing else None}
+
+    def close(self):
+        if getattr(self, "_x", None) and self._x.value:
+            self._lib.d2fe_quad_exchange_destroy(self._x)
             self._x = C.c_void_p()
 
     def __del__(self):

@@ -19,23 +19,14 @@
 #include <vector>
 
 #include "context.h"
+#include "rccl_table.h"
 
 using namespace d2fe;
 
-namespace {
-// the five RCCL entry points the exchange needs; ncclComm_t and ncclUniqueId stay opaque (a pointer; 128 bytes)
-struct Rccl {
-  struct Uid { char b[128]; };       // ncclUniqueId: 128 bytes, passed BY VALUE to ncclCommInitRank
-  void* lib = nullptr;
-  int (*GetUniqueId)(void*) = nullptr;
-  int (*CommInitRank)(void**, int, Uid, int) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-  std::string path;
-};
+namespace d2fe {
+// the dlopen table of librccl (rccl_table.h: shared with quad_exchange.hip, loaded once)
 Rccl g_rccl;
-std::mutex g_rccl_mu;
+namespace { std::mutex g_rccl_mu; }
 
 int rccl_load(const char* path) {
   std::lock_guard<std::mutex> lk(g_rccl_mu);
@@ -62,6 +53,9 @@ int rccl_load(const char* path) {
 int rccl_fail(const char* what, int rc) {
   return ctx_fail(D2FE_ERR_HIP, std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error ") + " (" + std::to_string(rc) + ")");
 }
+}  // namespace d2fe
+
+namespace {
 
 // a_cnt[p] = n of the local frame of pair p (read from this rank's own packed blocks), b_cnt[p] = n of the remote block of pair p (read from the gathered fp32 blocks)
 __global__ void exchange_counts_kernel(const int32_t* __restrict__ own_n, int own_stride_words, const int32_t* __restrict__ gath, int blk_words, int n_off,

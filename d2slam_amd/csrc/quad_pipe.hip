@@ -131,6 +131,10 @@ struct d2fe_quad_pipe_s {
     uint8_t* pin_in = nullptr;
     float* pin_out[2] = {nullptr, nullptr};
     long long rec = -1, synced = -1;   // the pass whose completion ev_done last recorded / the newest pass known to be complete
+    // device views of the two result blocks (d2fe_quad_device_view / _release): views handed out and not released yet; ev_rel = the consumers' last release
+    hipEvent_t ev_rel[2] = {nullptr, nullptr};
+    int views[2] = {0, 0};
+    bool rel_pending[2] = {false, false};
   };
   std::vector<Lane> lanes;
   std::vector<int> first_class, second_class;
@@ -162,6 +166,10 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
   // by pass P - 2 K + 1 (its temporal pairs), which is complete too: the submit of pass P - K + 1 synchronised with it
   int rc = lane_sync(L);
   if (rc) return rc;
+  // device views of this block (handed out 2 K passes ago): the consumer's stream must be through with it before this pass writes it.  The NetVLAD stream
+  // is ordered behind this wait through ev_up
+  if (L.views[set] > 0) return ctx_fail(D2FE_ERR_INVALID, "a device view of this lane's result block was not released (d2fe_quad_device_release) within 2 * lanes submits");
+  if (L.rel_pending[set]) { HIP_TRY(hipStreamWaitEvent(L.s, L.ev_rel[set], 0)); L.rel_pending[set] = false; }
   const size_t rimg = (size_t)p->RW * p->RH, img = (size_t)p->W * p->H;
   const int Q = p->Q, NI = p->NI, W = p->W, H = p->H, RW = p->RW, RH = p->RH;
   hipStream_t s = L.s;
@@ -373,7 +381,7 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
       const int rc2 = clone_lane(h, NI, &L.ctx, ms, 0, p->G > 0);
       if (rc2) { (void)hipStreamDestroy(ms); return rc2; }
       L.s = L.ctx->stream;
-      for (hipEvent_t* e : {&L.ev_up, &L.ev_nv, &L.ev_ext[0], &L.ev_ext[1], &L.ev_done}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      for (hipEvent_t* e : {&L.ev_up, &L.ev_nv, &L.ev_ext[0], &L.ev_ext[1], &L.ev_done, &L.ev_rel[0], &L.ev_rel[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
       L.d_raw = p->d_raw_all + (size_t)k * NI * rimg;
       if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, rimg * NI, hipHostMallocDefault));
       for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
@@ -428,7 +436,7 @@ void d2fe_quad_pipe_destroy(d2fe_quad_pipe p) {
   for (auto& L : p->lanes) {
     if (L.s) (void)hipStreamSynchronize(L.s);
     if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
-    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1]}) if (e) (void)hipEventDestroy(e);
     if (L.pin_in) (void)hipHostFree(L.pin_in);
     for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
     if (L.ctx) d2fe_destroy(L.ctx);
@@ -507,5 +515,67 @@ int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* cap, int3
   if (netvlad_dim) *netvlad_dim = p->G;
   return D2FE_OK;
 }
+
+// ---- device-side consumers of a ticket (the cross-agent exchange, quad_exchange.hip) ------------------------------------------------------------------
+namespace {
+// the ticket's (lane, set) while its result block is still the one the ticket wrote (called with the pipe's mutex held)
+int quad_view_locate(d2fe_quad_pipe_s* p, int64_t ticket, int* k, int* set) {
+  if (ticket < 0 || ticket >= p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "unknown ticket");
+  if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: take the view within 2 * lanes submits");
+  *k = (int)(ticket % p->K); *set = (int)((ticket / p->K) & 1);
+  return D2FE_OK;
+}
+}  // namespace
+
+int d2fe_quad_device_view(d2fe_quad_pipe p, int64_t ticket, void* stream, d2fe_quad_device_result* out) {
+  if (!p || !out || !stream) return ctx_fail(D2FE_ERR_INVALID, "null argument (the consumer's stream must be a real hipStream_t)");
+  memset(out, 0, sizeof(*out));
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  int k, set;
+  const int rc = quad_view_locate(p, ticket, &k, &set);
+  if (rc) return rc;
+  auto& L = p->lanes[k];
+  hipStream_t cs = static_cast<hipStream_t>(stream);
+  // SuperPoint of the pass: ev_ext[set] (re-recorded only by the pass that rewrites this block, which quad_view_locate has excluded).  NetVLAD on the lane's
+  // second stream: ev_nv -- a later pass of the lane may have re-recorded it; waiting for that later record is merely later, never earlier
+  HIP_TRY(hipStreamWaitEvent(cs, L.ev_ext[set], 0));
+  if (p->G) HIP_TRY(hipStreamWaitEvent(cs, L.ev_nv, 0));
+  const float* B = p->block(k, set);
+  out->quads = p->Q; out->cap = p->cap; out->desc_dim = p->D; out->netvlad_dim = p->G;
+  out->d_kps_xy = B + p->o_kps; out->d_scores = B + p->o_scores; out->d_desc = B + p->o_desc;
+  out->d_n_kp = reinterpret_cast<const int32_t*>(B + p->o_cnt);
+  out->d_netvlad = p->G ? B + p->o_nv : nullptr;
+  ++L.views[set];
+  return D2FE_OK;
+}
+
+int d2fe_quad_device_release(d2fe_quad_pipe p, int64_t ticket, void* stream) {
+  if (!p || !stream) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(p->mu);
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  int k, set;
+  const int rc = quad_view_locate(p, ticket, &k, &set);
+  if (rc) return rc;
+  auto& L = p->lanes[k];
+  if (L.views[set] <= 0) return ctx_fail(D2FE_ERR_INVALID, "no device view of this ticket's block is outstanding");
+  HIP_TRY(hipEventRecord(L.ev_rel[set], static_cast<hipStream_t>(stream)));
+  L.rel_pending[set] = true;
+  --L.views[set];
+  return D2FE_OK;
+}
+
+int d2fe_quad_lane_stream(d2fe_quad_pipe p, int64_t ticket, void** stream) {
+  if (!p || !stream) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(p->mu);
+  int k, set;
+  const int rc = quad_view_locate(p, ticket, &k, &set);
+  if (rc) return rc;
+  *stream = p->lanes[k].s;
+  return D2FE_OK;
+}
+
+d2fe_handle d2fe_quad_handle(d2fe_quad_pipe p) { return p ? p->parent : nullptr; }
 
 }  // extern "C"

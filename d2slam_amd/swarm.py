@@ -324,6 +324,88 @@ class PipeExchange:
         return out
 
 
+def quad_remote_job_layout(world: int, rank: int, Q: int, loopback: bool = False):
+    """The cross-agent jobs of one submit of a quadcam rank behind the quad pipe (pure host logic; the Python statement of d2fe_quad_exchange_job_layout and of the
+    problem indexing documented in include/d2fe.h).  One block per view, block q * 4 + v within a rank (the pipe's row order; QuadSwarm above uses v * Q + q).  Job j =
+    (remote rank r, quad frame q), rank-major over the OTHER ranks (all ranks with loopback), then q.  Returns a dict:
+        job_rank, job_quad         [njobs]
+        local_row0, remote_block0  [njobs]  row of local view 0 of quad frame q in the result block; block of view 0 of the remote quad frame in [world][4 Q] blocks
+        all2all                    [njobs * 16] (local view, remote view) of problem j * 16 + lv * 4 + rv
+        gated(dir_b)               the four (local view, remote view) of a job whose gate chose dir_b, problems j * 4 + k in trackRemoteFrames' order
+                                   (d2featuretracker.cpp:282-297): remote view a = (2 + k) % 4, local view (dir_b - 2 + a) mod 4; dir_b < 0: four (-1, -1)."""
+    assert world >= 1 and 0 <= rank < world and Q >= 1
+    job_rank, job_quad = [], []
+    for r in range(world):
+        if r == rank and not loopback:
+            continue
+        for q in range(Q):
+            job_rank.append(r); job_quad.append(q)
+
+    def gated(dir_b):
+        if dir_b < 0:
+            return [(-1, -1)] * 4
+        return [((dir_b - 2 + (2 + k) % 4) % 4, (2 + k) % 4) for k in range(4)]
+    return {"job_rank": job_rank, "job_quad": job_quad, "local_row0": [4 * q for q in job_quad],
+            "remote_block0": [r * 4 * Q + 4 * q for r, q in zip(job_rank, job_quad)],
+            "all2all": [(lv, rv) for _ in job_rank for lv in range(4) for rv in range(4)], "gated": gated}
+
+
+class QuadPipeExchange(PipeExchange):
+    """swarm.PipeExchange for a quadcam rank: a thin caller of d2fe_quad_exchange_* (include/d2fe.h, csrc/quad_exchange.hip) behind an api.QuadPipe.  Backend "nccl":
+    ncclAllGather on an RCCL communicator of the library's own; any other backend (gloo in the tests, two ranks on one GPU): the library calls back into
+    PipeExchange._all_gather_host, which stages the blocks through the host, from a worker thread.  collect() returns the numpy views of api.QuadExchange.collect."""
+
+    def __init__(self, torch, pipe, dev, world, rank, exchange="fp32", mode="all2all", gate_thres=0.8, ratio=0.8, slots=4, group=None, loopback=False, own_stream=True,
+                 timing=True):
+        from . import api
+        assert exchange in ("fp32", "int8", "int8-renorm256") and mode in ("all2all", "gated") and (world > 1 or loopback)
+        self.torch, self.pipe, self.world, self.rank, self.group, self.dev = torch, pipe, world, rank, group, dev
+        self.exchange, self.mode = exchange, mode
+        self.comm = None
+        self.worker = None
+        self.err = None
+        self.timeline = []
+        self.backend = dist.get_backend(group)
+        cb = None
+        if self.backend == "nccl":
+            uid = [api.rccl_unique_id() if dist.get_rank(group) == 0 else None]
+            dist.broadcast_object_list(uid, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+            self.comm = api.rccl_comm_init_rank(uid[0], world, rank, dev.index if dev.index is not None else 0)
+        else:
+            cb = self._all_gather_host
+        self.x = api.QuadExchange(pipe, comm=self.comm, world=world, rank=rank, wire=exchange, mode=mode, loopback=loopback, slots=slots, own_stream=own_stream,
+                                  timing=timing, gate_thres=gate_thres, ratio=ratio, all_gather=cb)
+        self.njobs, self.npairs, self.block_bytes = self.x.njobs, self.x.npairs, self.x.block_bytes
+        self.stream = None
+        if self.backend != "nccl":
+            import queue, threading
+            self.q = queue.Queue()
+            self.posted = [threading.Event() for _ in range(slots)]
+            self.worker = threading.Thread(target=self._work, daemon=True)
+            self.worker.start()
+
+    def collect(self, slot):
+        """blocks until the slot's results are in host memory; numpy views of the pinned slot (valid until the slot is enqueued again)"""
+        if self.worker:
+            self.posted[slot].wait()
+        if self.err:
+            raise self.err
+        r = self.x.collect(slot)
+        if r["phase_ms"] is not None and len(self.timeline) < 4096:
+            self.timeline.append(r["phase_ms"])
+        return r
+
+    def timeline_ms(self):
+        import numpy as np
+        from . import api
+        if not self.timeline:
+            return None
+        tl = np.array(self.timeline)
+        out = {n: round(float(np.median(tl[:, i])), 4) for i, n in enumerate(api.QUAD_EXCHANGE_PHASES)}
+        out["exchange_stream_busy_ms_per_submit"] = round(float(np.median(tl.sum(1))), 4)
+        return out
+
+
 _HIP = None
 
 

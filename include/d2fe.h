@@ -685,6 +685,97 @@ D2FE_API int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* 
 D2FE_API int d2fe_quad_undistort_device(d2fe_handle h, const uint8_t* d_raw, int quads, int sw, int sh, int sstride, size_t camera_stride,
                                         size_t quad_stride, const d2fe_quad_maps* maps, int dw, int dh, uint8_t* d_dst, void* stream);
 
+/* Device-side consumers of a quad ticket: the contract of d2fe_pipe_device_view / _device_release / _lane_stream / _handle above, for the quad pipe.
+ *   d2fe_quad_device_view     launches nothing; makes `stream` (a hipStream_t, not NULL) wait for the ticket's SuperPoint and NetVLAD results (not for its matcher
+ *                             or its D2H) and returns DEVICE pointers into the lane's result block, in the block's own quad-major row order (row q * 4 + c).
+ *                             Read-only.  Valid until the matching release, at most 2 * lanes submits.
+ *   d2fe_quad_device_release  everything queued on `stream` so far is what read the view: the lane's next write of that block (pass + 2 * lanes) waits for it on
+ *                             the device (an event, no host wait).
+ * A block whose view is still outstanding when its lane comes round again fails that submit with D2FE_ERR_INVALID (and, like every failed submit, ends the
+ * pipe).  ONE consumer stream per pipe.  Both calls may come from a thread other than the submitting one.  A pipe nobody takes a view of runs as before. */
+typedef struct {
+  int32_t quads, cap, desc_dim, netvlad_dim;
+  const float* d_kps_xy;    /* [quads][4][cap][2] */
+  const float* d_scores;    /* [quads][4][cap] */
+  const float* d_desc;      /* [quads][4][cap][desc_dim] */
+  const int32_t* d_n_kp;    /* [quads][4] */
+  const float* d_netvlad;   /* [quads][4][netvlad_dim] or NULL */
+} d2fe_quad_device_result;
+D2FE_API int d2fe_quad_device_view(d2fe_quad_pipe p, int64_t ticket, void* stream, d2fe_quad_device_result* out);
+D2FE_API int d2fe_quad_device_release(d2fe_quad_pipe p, int64_t ticket, void* stream);
+/* the stream of the lane that ran the ticket's submit (a hipStream_t): work queued on it runs behind that submit's D2H and in front of the lane's next submit */
+D2FE_API int d2fe_quad_lane_stream(d2fe_quad_pipe p, int64_t ticket, void** stream);
+D2FE_API d2fe_handle d2fe_quad_handle(d2fe_quad_pipe p);
+
+/* ---- Cross-agent exchange behind a quad pipe (BASELINE configs[4]: a swarm of quadcam agents) ---------------------------------------------------------
+ * d2fe_exchange_* above for a FOURCORNER_FISHEYE agent.  Replaces, per remote quad frame: LoopNet::broadcastVisualImageDescArray
+ * (d2frontend/src/loop_net.cpp:24-87) in the int8 wire form of d2common/include/d2common/d2frontend_types.h:228-268,319-338, the FOURCORNER_FISHEYE branch of
+ * D2FeatureTracker::getMatchedPrevKeyframe (d2frontend/src/d2featuretracker.cpp:212-233) and the four view pairs of trackRemoteFrames (:282-297).  One
+ * sequence per ticket, asynchronous, on ONE stream of the exchange's own (own_stream = 1) or on the producing lane's stream (own_stream = 0):
+ *   d2fe_quad_device_view -> pack 4 * quads blocks straight from the result block (fp32 or int8) -> ONE all-gather -> [int8: decode] -> ONE launch of
+ *   quad_exchange_prepare_kernel (the gate of every job, the matcher's problem table, the counter) -> ONE d2fe_match_batch_device launch (local descriptors in
+ *   place in the lane's block, remote ones in place in the gathered blocks) -> d2fe_quad_device_release -> ONE D2H into pinned slot `slot`.
+ * No host synchronisation in d2fe_quad_exchange_enqueue (the matcher's scratch is allocated by the first launch on a stream, as everywhere); whatever fails
+ * after the view was taken, the view is released.
+ * Layout.  One block per VIEW; block index within a rank = q * 4 + v, the pipe's row order (d2slam_amd/swarm.py's QuadSwarm uses v * Q + q); the gathered
+ * buffer is [world][4 * quads][block].  Job j = (remote rank r, quad frame q), rank-major over the OTHER ranks (all ranks with loopback), then q: local quad
+ * frame q against quad frame q of rank r (d2fe_quad_exchange_job_layout, which needs no device).
+ *   mode 0, all2all: 16 problems per job, index j * 16 + lv * 4 + rv (local view lv against remote view rv); the gate is evaluated and counted, nothing is zeroed.
+ *   mode 1, gated  : 4 problems per job, index j * 4 + k, in trackRemoteFrames' order: remote view a = (2 + k) % 4, local view (dir_b - 2 + a) mod 4.  A job that
+ *                    fails the gate has n_match = 0 for its four problems and local_view = remote_view = -1.  Needs NetVLAD (else D2FE_ERR_INVALID).
+ * gate_sims / dir_prev are bit-equal to d2fe_quad_gate_device on the same vectors (local: the view's d_netvlad, remote: the netvlad field of the gathered fp32
+ * blocks).  A pipe with descriptor PCA (desc_dim != 256) is D2FE_ERR_UNSUPPORTED. */
+typedef enum { D2FE_QUAD_ALL2ALL = 0, D2FE_QUAD_GATED = 1 } d2fe_quad_exchange_mode;
+typedef struct {
+  int32_t struct_size;
+  int32_t world, rank;          /* of the communicator */
+  int32_t wire;                 /* d2fe_wire */
+  int32_t loopback;             /* the rank's OWN gathered blocks count as a remote agent too */
+  int32_t slots;                /* ring of pinned result slots */
+  int32_t own_stream;           /* 1 (default): one stream of the exchange's own; 0: each ticket's sequence on its lane's stream */
+  int32_t timing;               /* 1: HIP events around the five phases (d2fe_quad_exchange_result.phase_ms) */
+  int32_t mode;                 /* d2fe_quad_exchange_mode */
+  int32_t reserved0;
+  double gate_thres;            /* track_remote_netvlad_thres */
+  double ratio;                 /* knn_match_ratio */
+  d2fe_all_gather_fn all_gather; void* all_gather_user;      /* used when the communicator is NULL */
+  int32_t reserved[6];
+} d2fe_quad_exchange_config;
+typedef struct {            /* HOST pointers into the pinned slot, valid until the slot is enqueued again */
+  int64_t ticket;
+  int32_t njobs, npairs, pairs_per_job /* 16 or 4 */, cap;
+  const int32_t* job_rank;      /* [njobs] remote rank */
+  const int32_t* job_quad;      /* [njobs] quad frame */
+  const int32_t* q_idx;         /* [npairs][cap] local keypoint index */
+  const int32_t* t_idx;         /* [npairs][cap] remote keypoint index */
+  const float* dist;            /* [npairs][cap] */
+  const int32_t* n_match;       /* [npairs] */
+  const int32_t* local_view;    /* [npairs] 0..3, or -1 (gated: the job failed the gate) */
+  const int32_t* remote_view;   /* [npairs] */
+  const int32_t* dir_prev;      /* [njobs] dir_b or -1 (NULL without NetVLAD) */
+  const float* gate_sims;       /* [njobs][4] for dirs {2, 3, 0, 1} (NULL without NetVLAD) */
+  int32_t gate_n;               /* jobs passing the gate */
+  float phase_ms[5];            /* timing = 1: pack, all-gather, decode + prepare, remote matchKNN, release + D2H */
+} d2fe_quad_exchange_result;
+typedef struct d2fe_quad_exchange_s* d2fe_quad_exchange;
+/* defaults: world 1, rank 0, fp32, no loopback, 4 slots, own_stream 1, timing 0, all2all, gate_thres 0.8, ratio 0.8 */
+D2FE_API void d2fe_quad_exchange_default_config(d2fe_quad_exchange_config* c);
+D2FE_API int d2fe_quad_exchange_create(d2fe_quad_pipe p, void* nccl_comm, const d2fe_quad_exchange_config* cfg, d2fe_quad_exchange* out);
+D2FE_API void d2fe_quad_exchange_destroy(d2fe_quad_exchange x);      /* before the pipe */
+D2FE_API int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot);      /* asynchronous; within 2 * lanes submits of the ticket's */
+D2FE_API int d2fe_quad_exchange_collect(d2fe_quad_exchange x, int slot, d2fe_quad_exchange_result* out);      /* blocks until the slot's results are in host memory */
+D2FE_API int d2fe_quad_exchange_jobs(d2fe_quad_exchange x);
+D2FE_API int d2fe_quad_exchange_pairs(d2fe_quad_exchange x);         /* matcher problems per enqueue: 16 or 4 per job */
+D2FE_API int d2fe_quad_exchange_block_bytes(d2fe_quad_exchange x);   /* bytes one VIEW contributes to the all-gather */
+D2FE_API void* d2fe_quad_exchange_stream(d2fe_quad_exchange x);      /* own_stream = 1: that stream (hipStream_t), else NULL */
+/* DEVICE pointers of the slot's gathered blocks [world][4 * quads] (either may be NULL): *d_blocks = the fp32 blocks gate and matcher read (for an int8 wire: the
+ * decode), *d_wire_blocks = the blocks as they crossed the wire (fp32: the same pointer).  The remote keypoints a t_idx refers to are in there
+ * (d2fe_block_field_offset).  Complete once the slot was collected; valid until the slot is enqueued again. */
+D2FE_API int d2fe_quad_exchange_gathered(d2fe_quad_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks);
+/* The job list of one rank without a device: job_rank[j] / job_quad[j] for j < min(njobs, cap_jobs) (either array may be NULL); returns njobs =
+ * (world - 1, or world with loopback) * quads, or D2FE_ERR_INVALID.  d2fe_quad_exchange_create builds its table with this function. */
+D2FE_API int d2fe_quad_exchange_job_layout(int world, int rank, int quads, int loopback, int32_t* job_rank, int32_t* job_quad, int cap_jobs);
+
 /* Test hooks and kernel diagnostics (d2fe_debug_*) are NOT part of this library: they live in the development library
  * (lib/libd2fe_hip_dev.so, built with -DD2FE_DEVTOOLS) and are declared in include/d2fe_debug.h. */
 

@@ -277,6 +277,45 @@ class QuadPipe {
   d2fe_quad_pipe p_ = nullptr;
 };
 
+// d2fe_quad_exchange_* (the cross-agent exchange behind a quad pipe, include/d2fe.h) with the lifetime of a C++ object.  Destroy it BEFORE its QuadPipe
+// (declare it after the pipe).  comm: an ncclComm_t of the caller's, or nullptr with cfg.all_gather set.
+class QuadExchange {
+ public:
+  QuadExchange(const QuadPipe& pipe, void* comm, const d2fe_quad_exchange_config& cfg) {
+    if (d2fe_quad_exchange_create(pipe.get(), comm, &cfg, &x_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_exchange_create: %s\n", d2fe_last_error()); x_ = nullptr; }
+  }
+  ~QuadExchange() { if (x_) d2fe_quad_exchange_destroy(x_); }
+  QuadExchange(const QuadExchange&) = delete;
+  QuadExchange& operator=(const QuadExchange&) = delete;
+  bool ok() const { return x_ != nullptr; }
+  d2fe_quad_exchange get() const { return x_; }
+  int jobs() const { return x_ ? d2fe_quad_exchange_jobs(x_) : 0; }
+  int pairs() const { return x_ ? d2fe_quad_exchange_pairs(x_) : 0; }
+  // asynchronous: the whole sequence of one ticket is queued; the results arrive in pinned slot `slot`
+  bool enqueue(int64_t ticket, int slot) {
+    if (x_ && d2fe_quad_exchange_enqueue(x_, ticket, slot) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_quad_exchange_enqueue: %s\n", d2fe_last_error());
+    return false;
+  }
+  // blocks until the slot's results are in host memory; `out` points into the pinned slot (valid until the slot is enqueued again)
+  bool collect(int slot, d2fe_quad_exchange_result& out) {
+    if (x_ && d2fe_quad_exchange_collect(x_, slot, &out) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_quad_exchange_collect: %s\n", d2fe_last_error());
+    return false;
+  }
+  // the matches of problem p of a collected result (all2all: p = job * 16 + local view * 4 + remote view; gated: p = job * 4 + k)
+  static std::vector<DMatch> matches(const d2fe_quad_exchange_result& r, int p) {
+    std::vector<DMatch> m;
+    if (p < 0 || p >= r.npairs) return m;
+    const size_t o = (size_t)p * r.cap;
+    for (int j = 0; j < r.n_match[p]; ++j) m.emplace_back(r.q_idx[o + j], r.t_idx[o + j], r.dist[o + j]);
+    return m;
+  }
+
+ private:
+  d2fe_quad_exchange x_ = nullptr;
+};
+
 // feature_matcher.h:6-11.  `h` replaces the implicit global state of cv::BFMatcher; everything else as in the reference.
 inline std::vector<DMatch> matchKNN(d2fe_handle h, const DescView& desc_a, const DescView& desc_b, double knn_match_ratio = 0.8,
                                     const std::vector<Point2f>& pts_a = std::vector<Point2f>(),
