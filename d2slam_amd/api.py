@@ -91,7 +91,7 @@ class _ExchangeResult(C.Structure):
 class _PipeConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("lanes", C.c_int32), ("frames", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("cap", C.c_int32), ("netvlad", C.c_int32), ("match_lr", C.c_int32), ("match_prev", C.c_int32), ("pinned_input", C.c_int32),
-                ("ratio", C.c_double), ("radius_lr", C.c_double), ("radius_prev", C.c_double), ("cu_partition", C.c_int32), ("netvlad_inline", C.c_int32), ("coalesce", C.c_int32), ("lane_cus", C.c_int32), ("netvlad_group", C.c_int32), ("coalesce_depth", C.c_int32), ("lr_lk", C.c_int32), ("reserved", C.c_int32 * 1)]
+                ("ratio", C.c_double), ("radius_lr", C.c_double), ("radius_prev", C.c_double), ("cu_partition", C.c_int32), ("netvlad_inline", C.c_int32), ("coalesce", C.c_int32), ("lane_cus", C.c_int32), ("netvlad_group", C.c_int32), ("coalesce_depth", C.c_int32), ("lr_lk", C.c_int32), ("sp_lk", C.c_int32)]
 
 
 class _PipeResult(C.Structure):
@@ -103,6 +103,19 @@ class _PipeResult(C.Structure):
 
 class _PipeLKResult(C.Structure):
     _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("pts_xy", C.c_void_p), ("status", C.c_void_p)]
+
+
+class _TrackParams(C.Structure):
+    """d2fe_track_params: the tracker parameters of the LK-carried landmark list (sp_track_use_lk)"""
+    _fields_ = [("total_feature_num", C.c_int32), ("levels", C.c_int32), ("win", C.c_int32), ("iters", C.c_int32), ("near_lk_thread_rate", C.c_float),
+                ("reserved", C.c_int32), ("feature_min_dist", C.c_double)]
+
+
+class _PipeTrackResult(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("cap_tracks", C.c_int32), ("desc_dim", C.c_int32), ("list_words", C.c_int32),
+                ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p),
+                ("pts_xy", C.c_void_p), ("id", C.c_void_p), ("src", C.c_void_p), ("kp", C.c_void_p), ("desc", C.c_void_p), ("scores", C.c_void_p),
+                ("right_xy", C.c_void_p), ("right_status", C.c_void_p)]
 
 
 class _PipeDeviceResult(C.Structure):
@@ -171,6 +184,8 @@ EXPORTS = [
     "d2fe_gen_cylinder_map", "d2fe_gen_cylinder_map_device", "d2fe_gen_pinhole_map", "d2fe_gen_pinhole_map_device", "d2fe_lk_frame_create",
     "d2fe_lk_frame_create_device", "d2fe_lk_frame_destroy", "d2fe_lk_frame_read_level", "d2fe_lk_track", "d2fe_lk_track_batch",
     "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
+    "d2fe_track_default_params", "d2fe_lk_carry_list_bytes", "d2fe_lk_carry_list_offset", "d2fe_lk_carry_step_device", "d2fe_pipe_track_result_get",
+    "d2fe_pipe_set_track_params",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -319,6 +334,16 @@ def _open_library(path, dev):
         lib.d2fe_lk_track_stereo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_lk_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_track_default_params.argtypes = [C.c_void_p]
+        lib.d2fe_track_default_params.restype = None
+        lib.d2fe_lk_carry_list_bytes.argtypes = [C.c_int, C.c_int]
+        lib.d2fe_lk_carry_list_bytes.restype = C.c_size_t
+        lib.d2fe_lk_carry_list_offset.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.d2fe_lk_carry_list_offset.restype = C.c_long
+        lib.d2fe_lk_carry_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_track_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_pipe_set_track_params.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_detect_fast_by_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_void_p]
         lib.d2fe_good_features_to_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
@@ -855,11 +880,16 @@ class StereoPipe:
     the left one, matchKNN L<->R and L<->previous L) for `frames` stereo frames per submit with up to `lanes` submits in flight.
     lr_lk=True (needs match_lr=False): the reference's default stereo path (lr_match_use_lk) -- SuperPoint on the left images only, every left keypoint
     tracked into the right image with pyramidal LK inside the pass; wait() then also returns "lk_pts" [F, cap, 2] and "lk_status" [F, cap].
+    sp_lk=True (needs lr_lk=True; together the reference's defaults, sp_track_use_lk): the LK-carried landmark list of D2FeatureTracker::trackLK is kept on the
+    device and carried across frames, passes and lanes; track_params (a dict of d2fe_track_params fields, or track_params()) replaces the reference's defaults.
+    wait() then returns, instead of lk_*, per frame f: "track_n" [F], "track_pts" [F, cap_tracks, 2], "track_id" / "track_src" / "track_kp" [F, cap_tracks],
+    "track_desc" [F, cap_tracks, D], "track_scores", "track_right_pts" [F, cap_tracks, 2], "track_right_status" [F, cap_tracks] and the counts
+    "track_n_tracked_in", "track_n_lost", "track_n_removed_near", "track_n_new" [F] (include/d2fe.h, d2fe_pipe_track_result).
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits)."""
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
                  ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
-                 lr_lk=False):
+                 lr_lk=False, sp_lk=False, track_params=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _PipeConfig()
@@ -871,10 +901,19 @@ class StereoPipe:
         c.cu_partition = int(bool(cu_partition)); c.coalesce = int(coalesce); c.lane_cus = int(lane_cus); c.netvlad_group = int(netvlad_group); c.coalesce_depth = int(coalesce_depth)
         c.netvlad_inline = 2 if netvlad_inline is None else int(bool(netvlad_inline))      # None: auto (inline when lanes > 2)
         c.lr_lk = int(bool(lr_lk))
+        c.sp_lk = int(bool(sp_lk))
         self._lr_lk = bool(lr_lk)
+        self._sp_lk = bool(sp_lk)
         self._lk_res = _PipeLKResult()
+        self._track_res = _PipeTrackResult()
         self._p = C.c_void_p()
         _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
+        if track_params is not None:
+            try:
+                self.set_track_params(track_params)
+            except Exception:
+                self.close()
+                raise
         if not hasattr(fe, "_pipes"):
             import weakref
             fe._pipes = weakref.WeakSet()
@@ -983,7 +1022,23 @@ class StereoPipe:
         for k in ("lr", "prev"):
             out[k + "_q"] = view(getattr(r, k + "_q"), (F, cap), np.int32); out[k + "_t"] = view(getattr(r, k + "_t"), (F, cap), np.int32)
             out[k + "_dist"] = view(getattr(r, k + "_dist"), (F, cap), np.float32); out[k + "_n"] = view(getattr(r, k + "_n"), (F,), np.int32)
-        if self._lr_lk:
+        if self._sp_lk:
+            t = self.track_result_raw(ticket)
+            T, lw, base = t.cap_tracks, t.list_words, t.n          # the header of frame 0's list is the lowest address of the lists
+            words = np.frombuffer((C.c_int32 * (F * lw)).from_address(base), dtype=np.int32).reshape(F, lw)
+
+            def per_list(ptr, shape, dt):
+                o = (ptr - base) // 4
+                return words[:, o:o + int(np.prod(shape))].view(dt).reshape((F,) + tuple(shape))
+            for k in ("n", "n_tracked_in", "n_lost", "n_removed_near", "n_new"):
+                out["track_" + k] = per_list(getattr(t, k), (1,), np.int32)[:, 0]
+            out["track_pts"] = per_list(t.pts_xy, (T, 2), np.float32); out["track_desc"] = per_list(t.desc, (T, D), np.float32)
+            out["track_scores"] = per_list(t.scores, (T,), np.float32)
+            for k in ("id", "src", "kp"):
+                out["track_" + k] = per_list(getattr(t, k), (T,), np.int32)
+            out["track_right_pts"] = view(t.right_xy, (F, T, 2), np.float32)
+            out["track_right_status"] = np.frombuffer((C.c_uint8 * (F * T)).from_address(t.right_status), dtype=np.uint8).reshape(F, T)
+        elif self._lr_lk:
             lk = self.lk_result_raw(ticket)
             out["lk_pts"] = view(lk.pts_xy, (F, cap, 2), np.float32)
             out["lk_status"] = np.frombuffer((C.c_uint8 * (F * cap)).from_address(lk.status), dtype=np.uint8).reshape(F, cap)
@@ -993,6 +1048,16 @@ class StereoPipe:
         """d2fe_pipe_lk_result_get: the left -> right LK tracks of a ticket that wait() has returned (lr_lk pipes)"""
         _check(self._lib.d2fe_pipe_lk_result_get(self._p, C.c_int64(ticket), C.byref(self._lk_res)))
         return self._lk_res
+
+
+    def track_result_raw(self, ticket):
+        """d2fe_pipe_track_result_get: the landmark lists of a ticket that wait() has returned (sp_lk pipes)"""
+        _check(self._lib.d2fe_pipe_track_result_get(self._p, C.c_int64(ticket), C.byref(self._track_res)))
+        return self._track_res
+
+    def set_track_params(self, tp):
+        """d2fe_pipe_set_track_params: only before the first submit"""
+        _check(self._lib.d2fe_pipe_set_track_params(self._p, C.byref(track_params(**tp) if isinstance(tp, dict) else tp)))
 
 
 def _pinned_view(ptr, shape, dt):
@@ -1247,6 +1312,56 @@ def lk_track_stereo_device(fe: FrontEnd, d_left, d_right, n_frames, width, heigh
     _check(fe._lib.d2fe_lk_track_stereo_device(fe.handle, d_left, d_right, int(n_frames), int(width), int(height), int(stride or width),
                                                int(image_stride or (stride or width) * height), d_kps_xy, d_n_kp, int(cap), int(levels), int(win), int(iters),
                                                d_workspace, d_pts_xy, d_status, stream))
+
+
+LKC_FIELDS = ["hdr", "pts", "id", "src", "kp", "scores", "desc", "trk_xy", "trk_status"]      # enum D2FE_LKC_* of include/d2fe.h, in order
+
+
+def track_params(**kw):
+    """d2fe_track_params with the reference's defaults (d2fe_track_default_params), fields replaced by keyword"""
+    tp = _TrackParams()
+    load_library().d2fe_track_default_params(C.byref(tp))
+    for k, v in kw.items():
+        if k not in dict(_TrackParams._fields_) or k == "reserved":
+            raise TypeError("d2fe_track_params has no field %r" % k)
+        setattr(tp, k, v)
+    return tp
+
+
+def lk_carry_list_bytes(cap_tracks, desc_dim=256):
+    """d2fe_lk_carry_list_bytes (host arithmetic): one landmark-list block"""
+    return int(load_library().d2fe_lk_carry_list_bytes(int(cap_tracks), int(desc_dim)))
+
+
+def lk_carry_list_offset(cap_tracks, desc_dim, field):
+    """d2fe_lk_carry_list_offset: 32-bit words from the block base to `field` (a name of LKC_FIELDS or its index)"""
+    return int(load_library().d2fe_lk_carry_list_offset(int(cap_tracks), int(desc_dim), LKC_FIELDS.index(field) if isinstance(field, str) else int(field)))
+
+
+def lk_carry_list_views(block, cap_tracks, desc_dim=256):
+    """dict of numpy views into a HOST copy of one list block (a 4-byte-aligned uint8 / int32 / float32 array of lk_carry_list_bytes bytes)"""
+    w = np.ascontiguousarray(block).view(np.int32).reshape(-1)
+    T, D = int(cap_tracks), int(desc_dim)
+    shapes = {"hdr": ((64,), np.int32), "pts": ((T, 2), np.float32), "id": ((T,), np.int32), "src": ((T,), np.int32), "kp": ((T,), np.int32),
+              "scores": ((T,), np.float32), "desc": ((T, D), np.float32), "trk_xy": ((T, 2), np.float32)}
+    out = {}
+    for k, (shape, dt) in shapes.items():
+        o = lk_carry_list_offset(T, D, k)
+        out[k] = w[o:o + int(np.prod(shape))].view(dt).reshape(shape)
+    o = lk_carry_list_offset(T, D, "trk_status")
+    out["trk_status"] = w[o:o + (T + 3) // 4].view(np.uint8)[:T]
+    out.update(n=int(out["hdr"][0]), n_tracked_in=int(out["hdr"][1]), n_lost=int(out["hdr"][2]), n_removed_near=int(out["hdr"][3]), n_new=int(out["hdr"][4]))
+    return out
+
+
+def lk_carry_step(fe: FrontEnd, d_prev_pyr, d_cur_pyr, width, height, d_prev_list, d_cur_list, d_kps_xy, d_kp_scores, d_kp_desc, d_n_kp, kp_cap, d_next_id,
+                  tp=None, desc_dim=256, stream=None):
+    """One frame of the LK-carried landmark list on the device (d2fe_lk_carry_step_device); arguments are raw device addresses (ints), as for
+    lk_track_stereo_device: the pyramids (one image of the stereo workspace, or an LKFrame's), the previous and the current list block (zeroed once), the outputs
+    extract_device left for the current frame, one int32 next_id.  Only enqueues on `stream`."""
+    tp = tp if tp is not None else track_params()
+    _check(fe._lib.d2fe_lk_carry_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(width), int(height), d_prev_list, d_cur_list, int(desc_dim), d_kps_xy or None,
+                                             d_kp_scores or None, d_kp_desc or None, d_n_kp or None, int(kp_cap), C.byref(tp), d_next_id, stream))
 
 
 class _LKPair(C.Structure):

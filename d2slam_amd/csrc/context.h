@@ -224,6 +224,12 @@ void graphs_clear(d2fe_context* h);
 void host_state_save(const d2fe_context* h, d2fe_context::HostState& st);
 void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool netvlad);
 
+// lk_carry.hip, for the pipe's sp_lk mode: what d2fe_lk_carry_step_device would refuse (nullptr: nothing), and trackLK(left, right) over the lists of a pass --
+// n_frames list blocks, consecutive in d_lists, against the pass's stereo workspace (d2fe_lk_track_stereo_device), ONE launch
+const char* lk_carry_check_params(const d2fe_track_params* tp);
+int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int width, int height, const d2fe_track_params& tp, const float* d_lists, int desc_dim,
+                          float* d_right_xy, uint8_t* d_right_status, hipStream_t s);
+
 struct ProfScope {
   d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
   ProfScope(d2fe_context* h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {

@@ -19,6 +19,7 @@
 #include "../../include/d2fe.h"
 #include "context.h"
 #include "kernels.h"
+#include "lk_device.h"
 
 namespace d2fe {
 
@@ -91,135 +92,7 @@ __global__ __launch_bounds__(256) void pyr_down_batch_kernel(PyrBatchArgs a) {
   pyr[(size_t)a.dst_off + (size_t)y * a.dw + x] = pyr_down_px(src, stride, a.sw, a.sh, x, y);
 }
 
-// ---- sparse pyramidal LK ---------------------------------------------------------------------------------------------------------
-// one (previous frame, current frame) pair of a batched call; a point carries the index of its pair
-struct LkPairDev {
-  const uint8_t* prev; const uint8_t* cur;
-  int off[8], ws[8], hs[8];
-  int levels, w, h, type;
-  float move_cols;
-  int pad_[3];
-};
-struct LkArgs {
-  const LkPairDev* pairs; const int* pair_of;
-  int n, win, iters;
-  const float* prev_pts; const float* cur_init;
-  float* cur_pts; uint8_t* status;
-};
-
-__device__ __forceinline__ float tex(const uint8_t* __restrict__ im, int w, int h, float x, float y) {
-  const float xs = x - 0.5f, ys = y - 0.5f;
-  const float xf = __builtin_floorf(xs), yf = __builtin_floorf(ys);
-  const float fx = xs - xf, fy = ys - yf;
-  int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
-  x0 = min(max(x0, 0), w - 1); x1 = min(max(x1, 0), w - 1);
-  y0 = min(max(y0, 0), h - 1); y1 = min(max(y1, 0), h - 1);
-  const float s = 1.0f / 255.0f;
-  const float p00 = (float)im[(size_t)y0 * w + x0] * s, p10 = (float)im[(size_t)y0 * w + x1] * s;
-  const float p01 = (float)im[(size_t)y1 * w + x0] * s, p11 = (float)im[(size_t)y1 * w + x1] * s;
-  const float gx = 1.0f - fx, gy = 1.0f - fy;
-  float v = (gx * gy) * p00;
-  v = v + (fx * gy) * p10;
-  v = v + (gx * fy) * p01;
-  v = v + (fx * fy) * p11;
-  return v;
-}
-
-// the shared-memory tree of OpenCV's block reduce, v[t] += v[t+s] for s = 32..1, result broadcast from lane 0
-__device__ __forceinline__ float tree64(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v = v + __shfl_down(v, s, 64);
-  return __shfl(v, 0, 64);
-}
-
-// one pyramid level for one point, executed by a whole wave with uniform control flow
-__device__ void lk_level(const uint8_t* __restrict__ I, const uint8_t* __restrict__ J, int cols, int rows, int level, int win,
-                         int iters, float ppx, float ppy, float& npx, float& npy, int& status, int lane) {
-  const float half = (float)((win - 1) / 2);
-  float px = ppx * (1.0f / (float)(1 << level)), py = ppy * (1.0f / (float)(1 << level));
-  if (px < 0 || px >= (float)cols || py < 0 || py >= (float)rows) {
-    if (level == 0) status = 0;
-    return;
-  }
-  px -= half; py -= half;
-  const int tx = lane & 7, ty = lane >> 3;
-  float Ip[3][3], Dx[3][3], Dy[3][3];
-  float s11 = 0.f, s12 = 0.f, s22 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int xb = tx + 8 * j, yb = ty + 8 * i;
-      Ip[i][j] = 0.f; Dx[i][j] = 0.f; Dy[i][j] = 0.f;
-      if (xb < win && yb < win) {
-        const float x = px + (float)xb + 0.5f, y = py + (float)yb + 0.5f;
-        Ip[i][j] = tex(I, cols, rows, x, y);
-        const float tmm = tex(I, cols, rows, x - 1, y - 1), tpm = tex(I, cols, rows, x + 1, y - 1);
-        const float tmp = tex(I, cols, rows, x - 1, y + 1), tpp = tex(I, cols, rows, x + 1, y + 1);
-        float dx = 3.0f * tpm;
-        dx = dx + 10.0f * tex(I, cols, rows, x + 1, y);
-        dx = dx + 3.0f * tpp;
-        float mx = 3.0f * tmm;
-        mx = mx + 10.0f * tex(I, cols, rows, x - 1, y);
-        mx = mx + 3.0f * tmp;
-        dx = dx - mx;
-        float dy = 3.0f * tmp;
-        dy = dy + 10.0f * tex(I, cols, rows, x, y + 1);
-        dy = dy + 3.0f * tpp;
-        float my = 3.0f * tmm;
-        my = my + 10.0f * tex(I, cols, rows, x, y - 1);
-        my = my + 3.0f * tpm;
-        dy = dy - my;
-        Dx[i][j] = dx; Dy[i][j] = dy;
-        s11 = s11 + dx * dx; s12 = s12 + dx * dy; s22 = s22 + dy * dy;
-      }
-    }
-  float A11 = tree64(s11), A12 = tree64(s12), A22 = tree64(s22);
-  float D = A11 * A22 - A12 * A12;
-  if (D < 1.1920928955078125e-07f) {
-    if (level == 0) status = 0;
-    return;
-  }
-  D = 1.0f / D;
-  A11 = A11 * D; A12 = A12 * D; A22 = A22 * D;
-  float nx = npx * 2.0f, ny = npy * 2.0f;
-  nx -= half; ny -= half;
-  for (int k = 0; k < iters; ++k) {
-    if (nx < -half || nx >= (float)cols || ny < -half || ny >= (float)rows) {
-      if (level == 0) status = 0;
-      return;
-    }
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int xb = tx + 8 * j, yb = ty + 8 * i;
-        if (xb < win && yb < win) {
-          const float Jv = tex(J, cols, rows, nx + (float)xb + 0.5f, ny + (float)yb + 0.5f);
-          const float diff = (Jv - Ip[i][j]) * 32.0f;
-          s1 = s1 + diff * Dx[i][j];
-          s2 = s2 + diff * Dy[i][j];
-        }
-      }
-    const float B1 = tree64(s1), B2 = tree64(s2);
-    const float ddx = A12 * B2 - A22 * B1;
-    const float ddy = A12 * B1 - A11 * B2;
-    nx = nx + ddx; ny = ny + ddy;
-    if (__builtin_fabsf(ddx) < 0.01f && __builtin_fabsf(ddy) < 0.01f) break;
-  }
-  npx = nx + half; npy = ny + half;
-}
-
-__device__ __forceinline__ void lk_calc(const LkArgs& a, const LkPairDev& P, const uint8_t* Ip, const uint8_t* Jp, float ppx,
-                                        float ppy, float& npx, float& npy, int& status, int lane) {
-  const float sc = (float)(1.0 / (double)(1 << P.levels) / 2.0);
-  npx = npx * sc; npy = npy * sc;
-  status = 1;
-  for (int l = P.levels; l >= 0; --l)
-    lk_level(Ip + P.off[l], Jp + P.off[l], P.ws[l], P.hs[l], l, a.win, a.iters, ppx, ppy, npx, npy, status, lane);
-}
-
+// ---- sparse pyramidal LK: the device functions (tex, lk_level, lk_calc) and LkPairDev / LkArgs live in lk_device.h ------------------------------------------
 __global__ __launch_bounds__(256) void lk_track_kernel(LkArgs a) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -604,10 +477,12 @@ size_t d2fe_lk_stereo_workspace_bytes(int n_frames, int width, int height, int l
 int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint8_t* d_right, int n_frames, int width, int height, int stride,
                                 size_t image_stride, const float* d_kps_xy, const int32_t* d_n_kp, int cap, int levels, int win, int iters,
                                 void* d_workspace, float* d_pts_xy, uint8_t* d_status, void* stream) {
-  if (!h || !d_left || !d_right || !d_kps_xy || !d_n_kp || !d_workspace || !d_pts_xy || !d_status) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  // d_kps_xy, d_n_kp, d_pts_xy and d_status all NULL: the pyramids alone (the workspace a caller of d2fe_lk_carry_step_device needs)
+  const bool tracks = d_kps_xy || d_n_kp || d_pts_xy || d_status;
+  if (!h || !d_left || !d_right || !d_workspace || (tracks && (!d_kps_xy || !d_n_kp || !d_pts_xy || !d_status))) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   if (width < 16 || height < 16 || levels < 0 || levels > 7 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
   if (stride < width || (n_frames > 1 && image_stride < (size_t)stride * (height - 1) + width)) return ctx_fail(D2FE_ERR_INVALID, "bad stride / image stride");
-  if (n_frames < 1 || n_frames > 32767 || cap < 1 || cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "n_frames must be 1..32767, cap 1..16384");
+  if (n_frames < 1 || n_frames > 32767 || (tracks && (cap < 1 || cap > 16384))) return ctx_fail(D2FE_ERR_INVALID, "n_frames must be 1..32767, cap 1..16384");
   if (win < 3 || win > 24 || !(win & 1) || iters < 1) return ctx_fail(D2FE_ERR_INVALID, "bad LK parameters (win odd, 3..23)");
   LK_TRY(hipSetDevice(ctx_device(h)));
   hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
@@ -629,7 +504,7 @@ int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint
   }
   t.ws = a.ws; t.total = a.total; t.n_frames = n_frames; t.cap = cap; t.win = win; t.iters = iters;
   t.kps = d_kps_xy; t.n_kp = d_n_kp; t.cur_pts = d_pts_xy; t.status = d_status;
-  {
+  if (tracks) {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_track_stereo_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, s, t);
   }

@@ -19,6 +19,13 @@
 // the interleaved L, R, L, R rows of coalesce > 1 need); behind SuperPoint the lane builds the pyramids of both images in its own workspace and tracks every left
 // keypoint left -> right (d2fe_lk_track_stereo_device, lk.hip: levels + 1 launches, points and counts read on the device).  The tracks live in the result block
 // in front of d2h_words, so they travel with the pass's one D2H.  Rows of right images are never written: they keep the zeros of creation (n_kp = 0).
+//
+// cfg.sp_lk (with lr_lk: the reference's defaults, sp_track_use_lk): behind the pass's pyramids the LK-carried landmark list (lk_carry.hip) is stepped once per left
+// frame, in time order -- frame f's list block in the result block is the previous list of frame f + 1.  The chain of a pass starts from the previous pass's last list
+// (read where that pass left it: its block is not rewritten for 2 K passes) and its last left pyramid.  That pyramid lives in another lane's workspace, or, with one
+// lane, in the very workspace this pass has just overwritten, so every pass ends its chain with a device copy of its last left pyramid into ONE pipe-owned buffer; the
+// lane's ev_chain, recorded behind the copy, is what the next pass's first step waits for (a strict chain: the buffer's reader and its next writer are the same
+// stream).  ONE launch then tracks the list entries of all frames left -> right; the per-keypoint launch of lr_lk is not issued.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +55,13 @@ struct d2fe_pipe_s {
   bool lk = false;
   size_t o_lkp = 0, o_lks = 0, o_sdesc = 0, o_skps = 0, o_sscores = 0, o_scnt = 0, o_sidx = 0;
   uint8_t* d_lk_ws = nullptr; size_t lk_ws_lane = 0;     // per lane: the pyramids of the NI images of a pass
+  // sp_lk: per left frame of a pass one list block (d2fe_lk_carry_list_bytes) at o_list, the right tracks [F * C][capT][2] floats and [F * C][capT] bytes (inside d2h_words)
+  bool sp_lk = false;
+  d2fe_track_params tp{};
+  int capT = 0;
+  size_t list_words = 0, o_list = 0, o_rxy = 0, o_rst = 0, pyr_total = 0;
+  uint8_t* d_carry_pyr = nullptr;    // the last left pyramid of the last launched pass
+  int32_t* d_next_id = nullptr;
   float* d_all = nullptr;            // [64 zero words | K lanes x 2 sets x block]
   MatchPairDesc* d_pairs = nullptr;  // [K][2][C variants: submits of the PREVIOUS pass][C * npp]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;   // per lane: tickets + records
@@ -57,6 +71,7 @@ struct d2fe_pipe_s {
     hipEvent_t ev_up = nullptr, ev_nv = nullptr, ev_ext[2] = {nullptr, nullptr}, ev_done = nullptr;
     // device views of the two result blocks (d2fe_pipe_device_view / _release): views handed out and not released yet; ev_rel = the consumers' last release
     hipEvent_t ev_rel[2] = {nullptr, nullptr};
+    hipEvent_t ev_chain = nullptr;     // sp_lk: the landmark-list chain of the lane's last pass and the carry copy behind it are complete
     int views[2] = {0, 0};
     bool rel_pending[2] = {false, false};
     bool nv_on_side[2] = {false, false};      // the pass that wrote this block ran NetVLAD on the lane's second stream (auto mode decides per pass)
@@ -318,11 +333,36 @@ int pipe_flush(d2fe_pipe_s* p) {
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(L.ev_ext[set], s));
-  if (p->lk) {
+  if (p->lk && !p->sp_lk) {
     // left -> right tracks of the pass's n_left frames: C == 1: left rows [0, F), right images F further on; C > 1: L, R interleaved, keypoints from the staging rows
     rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride,
                                      staged ? B + p->o_skps : B + p->o_kps, reinterpret_cast<const int32_t*>(staged ? B + p->o_scnt : B + p->o_cnt), p->cap,
                                      LK_LEVELS, LK_WIN, LK_ITERS, L.d_lk, B + p->o_lkp, reinterpret_cast<uint8_t*>(B + p->o_lks), s);
+    if (rc) return rc;
+  }
+  if (p->sp_lk) {
+    // the pyramids of the pass (the same two launches), then the landmark list: one step per left frame in time order, the carry copy, ONE left -> right launch
+    rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride, nullptr, nullptr, 0, p->tp.levels,
+                                     p->tp.win, p->tp.iters, L.d_lk, nullptr, nullptr, s);
+    if (rc) return rc;
+    const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+    if (P > 0 && p->K > 1) HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_chain, 0));
+    const int32_t* cnt = reinterpret_cast<const int32_t*>(B + p->o_cnt);
+    for (int f = 0; f < n_left; ++f) {
+      // previous list / pyramid: the frame before in this pass; f = 0: the previous pass's last list (its last submit is prev_g - 1) and the carried pyramid;
+      // the very first frame reads the 64 zero words in front of the blocks (the empty list) and tracks nothing
+      const float* prev_list = f > 0 ? B + p->o_list + (size_t)(f - 1) * p->list_words
+                                     : P > 0 ? p->block(pk, pset) + p->o_list + (size_t)((p->C > 1 ? p->prev_g : F) - 1) * p->list_words : p->d_all;
+      const uint8_t* prev_pyr = f > 0 ? L.d_lk + (size_t)(f - 1) * p->pyr_total : p->d_carry_pyr;
+      const size_t r = (size_t)p->left_row(f, f);        // C > 1: frame f is submit f (row 2 f); C == 1: row f
+      rc = d2fe_lk_carry_step_device(L.ctx, prev_pyr, L.d_lk + (size_t)f * p->pyr_total, W, H, prev_list, B + p->o_list + (size_t)f * p->list_words, p->D,
+                                     B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap, B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp,
+                                     p->d_next_id, s);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(p->d_carry_pyr, L.d_lk + (size_t)(n_left - 1) * p->pyr_total, p->pyr_total, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipEventRecord(L.ev_chain, s));
+    rc = lk_carry_right_launch(L.ctx, L.d_lk, n_left, W, H, p->tp, B + p->o_list, p->D, B + p->o_rxy, reinterpret_cast<uint8_t*>(B + p->o_rst), s);
     if (rc) return rc;
   }
   if (nv_side) {
@@ -352,6 +392,102 @@ int pipe_flush(d2fe_pipe_s* p) {
   L.rec = P;
   p->prev_g = g;
   p->pend = 0;
+  return D2FE_OK;
+}
+
+// The result blocks in three steps, which d2fe_pipe_create takes in the order it always allocated in (the blocks first, a lane's pinned copies with the lane, the pair
+// tables behind the lanes) and d2fe_pipe_set_track_params takes again before the first submit, when cap_tracks -- and with it the size of a list block -- changes.
+// (1) the block layout and d_all (zeroed)
+int pipe_alloc_blocks(d2fe_pipe_s* p) {
+  const int C = p->C;
+  const size_t NI = p->NI, cap = p->cap, F = p->F, NL = (size_t)F * C, MP = (size_t)p->npp * C;
+  size_t o = 0;
+  p->o_desc = o; o += up64(NI * cap * p->D);
+  p->o_kps = o; o += up64(NI * cap * 2);
+  p->o_scores = o; o += up64(NI * cap);
+  p->o_nv = o; o += up64(NL * (size_t)p->G);
+  p->o_cnt = o; o += up64(NI);
+  p->o_mn = o; o += up64(MP);
+  p->o_mq = o; o += up64(MP * cap);
+  p->o_mt = o; o += up64(MP * cap);
+  p->o_md = o; o += up64(MP * cap);
+  if (p->lk && !p->sp_lk) {
+    p->o_lkp = o; o += up64(NL * cap * 2);
+    p->o_lks = o; o += up64((NL * cap + 3) / 4);
+  }
+  if (p->sp_lk) {
+    p->capT = p->tp.total_feature_num + 1;
+    p->list_words = d2fe_lk_carry_list_bytes(p->capT, p->D) / sizeof(float);
+    p->o_list = o; o += NL * p->list_words;
+    p->o_rxy = o; o += up64(NL * p->capT * 2);
+    p->o_rst = o; o += up64((NL * p->capT + 3) / 4);
+  }
+  p->d2h_words = o;
+  p->o_idx = o; o += up64(NI * cap);
+  if (p->lk && C > 1) {
+    p->o_sdesc = o; o += up64(NL * cap * p->D);
+    p->o_skps = o; o += up64(NL * cap * 2);
+    p->o_sscores = o; o += up64(NL * cap);
+    p->o_scnt = o; o += up64(NL);
+    p->o_sidx = o; o += up64(NL * cap);
+  }
+  p->blk_words = o;
+  if (p->d_all) { (void)hipFree(p->d_all); p->d_all = nullptr; }
+  const size_t all_words = 64 + (size_t)p->K * 2 * p->blk_words;
+  HIP_TRY(hipMalloc(&p->d_all, sizeof(float) * all_words));
+  HIP_TRY(hipMemset(p->d_all, 0, sizeof(float) * all_words));
+  return D2FE_OK;
+}
+
+// (2) a lane's pinned copies of its two blocks
+int pipe_alloc_pinned(d2fe_pipe_s* p, d2fe_pipe_s::Lane& L) {
+  for (int set = 0; set < 2; ++set) {
+    if (L.pin_out[set]) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = nullptr; }
+    HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
+  }
+  return D2FE_OK;
+}
+
+// (3) the matcher's pair tables, which address the blocks
+int pipe_alloc_pairs(d2fe_pipe_s* p) {
+  const d2fe_pipe_config* cfg = &p->cfg;
+  const int C = p->C;
+  const size_t cap = p->cap, F = p->F, MP = (size_t)p->npp * C;
+  if (p->d_pairs) { (void)hipFree(p->d_pairs); p->d_pairs = nullptr; }
+  if (p->npp > 0) {
+    // pair tables [lane][set][variant v = submits of the previous pass - 1][C * npp].  Submit j of a pass contributes npp consecutive pairs:
+    // L_f <-> R_f for its F frames (when match_lr), then L_f <-> L_(f-1); the first left frame of a pass pairs with the LAST left frame
+    // of the previous pass, whose row in the previous pass's block depends on how many submits that pass carried (the variant)
+    const size_t maxp = MP;
+    std::vector<MatchPairDesc> tab((size_t)p->K * 2 * C * maxp);
+    for (int k = 0; k < p->K; ++k)
+      for (int set = 0; set < 2; ++set)
+        for (int v = 0; v < C; ++v) {
+          float* B = p->block(k, set);
+          // the previous pass: P - 1.  With P = i K + k the set is i & 1; P - 1 = i K + k - 1 (k > 0: same i) or (i - 1) K + K - 1
+          const int pk = k > 0 ? k - 1 : p->K - 1;
+          const int pset = k > 0 ? set : set ^ 1;
+          float* PB = p->block(pk, pset);
+          MatchPairDesc* row = tab.data() + (((size_t)k * 2 + set) * C + v) * maxp;
+          int pi = 0;
+          auto fill = [&](MatchPairDesc& d, float* BA, int ra, float* BB, int rb, double radius) {
+            d.a = BA + p->o_desc + (size_t)ra * cap * p->D; d.b = BB + p->o_desc + (size_t)rb * cap * p->D;
+            d.pts_a = BA + p->o_kps + (size_t)ra * cap * 2; d.pts_b = BB + p->o_kps + (size_t)rb * cap * 2;
+            d.na = reinterpret_cast<int32_t*>(BA + p->o_cnt) + ra; d.nb = reinterpret_cast<int32_t*>(BB + p->o_cnt) + rb;
+            d.radius = radius;
+          };
+          for (int j = 0; j < C; ++j) {
+            for (int f = 0; cfg->match_lr && f < (int)F; ++f) fill(row[pi++], B, p->left_row(j, f), B, p->right_row(j, f), cfg->radius_lr);
+            for (int f = 0; cfg->match_prev && f < (int)F; ++f) {
+              if (f > 0) fill(row[pi++], B, p->left_row(j, f), B, p->left_row(j, f - 1), cfg->radius_prev);
+              else if (j > 0) fill(row[pi++], B, p->left_row(j, 0), B, p->left_row(j - 1, (int)F - 1), cfg->radius_prev);
+              else fill(row[pi++], B, p->left_row(0, 0), PB, p->left_row(v, (int)F - 1), cfg->radius_prev);        // previous pass: its last submit is v
+            }
+          }
+        }
+    HIP_TRY(hipMalloc(&p->d_pairs, sizeof(MatchPairDesc) * tab.size()));
+    HIP_TRY(hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice));
+  }
   return D2FE_OK;
 }
 
@@ -440,6 +576,8 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   if (cfg->lr_lk != 0 && cfg->lr_lk != 1) return pipe_fail(D2FE_ERR_INVALID, "lr_lk must be 0 or 1");
   if (cfg->lr_lk && cfg->match_lr) return pipe_fail(D2FE_ERR_INVALID, "lr_lk = 1 needs match_lr = 0: SuperPoint does not run on the right image, so it has no descriptors to match");
   if (cfg->lr_lk && (cfg->width < 16 || cfg->height < 16)) return pipe_fail(D2FE_ERR_INVALID, "lr_lk needs frames of at least 16 x 16");
+  if (cfg->sp_lk != 0 && cfg->sp_lk != 1) return pipe_fail(D2FE_ERR_INVALID, "sp_lk must be 0 or 1");
+  if (cfg->sp_lk && !cfg->lr_lk) return pipe_fail(D2FE_ERR_INVALID, "sp_lk = 1 needs lr_lk = 1: the landmark list is tracked on the pyramids the lr_lk stage builds");
   if (h->cfg.max_keypoints < 0) return pipe_fail(D2FE_ERR_UNSUPPORTED, "keep-all handles (max_keypoints = -1) are served by the single-call entry points");
   if (cfg->width > h->cfg.max_width || cfg->height > h->cfg.max_height) return pipe_fail(D2FE_ERR_INVALID, "frame size exceeds the handle's maximum");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
@@ -448,6 +586,9 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   h->live_pipes.fetch_add(1);        // from here on d2fe_pipe_destroy (every failure path below goes through it or through `delete p` + the decrement) gives it back
   p->M = M;
   p->lk = cfg->lr_lk != 0;
+  p->sp_lk = cfg->sp_lk != 0;
+  d2fe_track_default_params(&p->tp);
+  if (p->sp_lk) p->pyr_total = d2fe_lk_stereo_workspace_bytes(1, cfg->width, cfg->height, LK_LEVELS) / 2;
   p->nv_inline = cfg->netvlad_inline == 1;
   p->nv_auto = cfg->netvlad_inline == 2 && cfg->lanes > 2;      // one or two lanes: never more than four busy streams, the second stream always
   p->K = cfg->lanes; p->F = cfg->frames; p->C = C; p->NI = 2 * cfg->frames * C; p->W = cfg->width; p->H = cfg->height;
@@ -461,35 +602,12 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
     if (rc) { h->live_pipes.fetch_sub(1); delete p; return rc; }
     if (cfg->netvlad) { rc = nv_check(h, 1, p->W, p->H, p->W); if (rc) { h->live_pipes.fetch_sub(1); delete p; return rc; } }
   }
-  const size_t NI = p->NI, cap = p->cap, F = p->F, NL = (size_t)F * C, MP = (size_t)p->npp * C;
-  size_t o = 0;
-  p->o_desc = o; o += up64(NI * cap * p->D);
-  p->o_kps = o; o += up64(NI * cap * 2);
-  p->o_scores = o; o += up64(NI * cap);
-  p->o_nv = o; o += up64(NL * (size_t)p->G);
-  p->o_cnt = o; o += up64(NI);
-  p->o_mn = o; o += up64(MP);
-  p->o_mq = o; o += up64(MP * cap);
-  p->o_mt = o; o += up64(MP * cap);
-  p->o_md = o; o += up64(MP * cap);
-  if (p->lk) {
-    p->o_lkp = o; o += up64(NL * cap * 2);
-    p->o_lks = o; o += up64((NL * cap + 3) / 4);
-  }
-  p->d2h_words = o;
-  p->o_idx = o; o += up64(NI * cap);
-  if (p->lk && C > 1) {
-    p->o_sdesc = o; o += up64(NL * cap * p->D);
-    p->o_skps = o; o += up64(NL * cap * 2);
-    p->o_sscores = o; o += up64(NL * cap);
-    p->o_scnt = o; o += up64(NL);
-    p->o_sidx = o; o += up64(NL * cap);
-  }
-  p->blk_words = o;
+  const size_t NL = (size_t)p->F * C;
   const int rc = [&]() -> int {
-    const size_t all_words = 64 + (size_t)p->K * 2 * p->blk_words;
-    HIP_TRY(hipMalloc(&p->d_all, sizeof(float) * all_words));
-    HIP_TRY(hipMemset(p->d_all, 0, sizeof(float) * all_words));
+    {
+      const int rcb = pipe_alloc_blocks(p);
+      if (rcb) return rcb;
+    }
     HIP_TRY(hipMalloc(&p->d_img_all, (size_t)p->W * p->H * p->NI * p->K));
     if (p->lk) {
       p->lk_ws_lane = (d2fe_lk_stereo_workspace_bytes((int)NL, p->W, p->H, LK_LEVELS) + 255) / 256 * 256;
@@ -555,46 +673,27 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       HIP_TRY(hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming));
       HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[0], hipEventDisableTiming));
       HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[1], hipEventDisableTiming));
+      if (p->sp_lk) HIP_TRY(hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming));
       L.d_img = p->d_img_all + (size_t)k * p->NI * p->W * p->H;
       if (p->lk) L.d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
       if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, (size_t)p->W * p->H * p->NI, hipHostMallocDefault));
-      for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
+      rc2 = pipe_alloc_pinned(p, L);
+      if (rc2) return rc2;
     }
     if (nv_streams)      // CU-masked lanes whose second stream could not be created with the mask above
       for (auto& L : p->lanes) if (!L.nv) HIP_TRY(hipStreamCreateWithFlags(&L.nv, hipStreamNonBlocking));
+    if (p->sp_lk) {
+      HIP_TRY(hipMalloc(&p->d_carry_pyr, p->pyr_total));
+      HIP_TRY(hipMemset(p->d_carry_pyr, 0, p->pyr_total));
+      HIP_TRY(hipMalloc(&p->d_next_id, 64));
+      HIP_TRY(hipMemset(p->d_next_id, 0, 64));
+    }
+    {
+      const int rcr = pipe_alloc_pairs(p);
+      if (rcr) return rcr;
+    }
     if (p->npp > 0) {
-      // pair tables [lane][set][variant v = submits of the previous pass - 1][C * npp].  Submit j of a pass contributes npp consecutive pairs:
-      // L_f <-> R_f for its F frames (when match_lr), then L_f <-> L_(f-1); the first left frame of a pass pairs with the LAST left frame
-      // of the previous pass, whose row in the previous pass's block depends on how many submits that pass carried (the variant)
-      const size_t maxp = MP;
-      std::vector<MatchPairDesc> tab((size_t)p->K * 2 * C * maxp);
-      for (int k = 0; k < p->K; ++k)
-        for (int set = 0; set < 2; ++set)
-          for (int v = 0; v < C; ++v) {
-            float* B = p->block(k, set);
-            // the previous pass: P - 1.  With P = i K + k the set is i & 1; P - 1 = i K + k - 1 (k > 0: same i) or (i - 1) K + K - 1
-            const int pk = k > 0 ? k - 1 : p->K - 1;
-            const int pset = k > 0 ? set : set ^ 1;
-            float* PB = p->block(pk, pset);
-            MatchPairDesc* row = tab.data() + (((size_t)k * 2 + set) * C + v) * maxp;
-            int pi = 0;
-            auto fill = [&](MatchPairDesc& d, float* BA, int ra, float* BB, int rb, double radius) {
-              d.a = BA + p->o_desc + (size_t)ra * cap * p->D; d.b = BB + p->o_desc + (size_t)rb * cap * p->D;
-              d.pts_a = BA + p->o_kps + (size_t)ra * cap * 2; d.pts_b = BB + p->o_kps + (size_t)rb * cap * 2;
-              d.na = reinterpret_cast<int32_t*>(BA + p->o_cnt) + ra; d.nb = reinterpret_cast<int32_t*>(BB + p->o_cnt) + rb;
-              d.radius = radius;
-            };
-            for (int j = 0; j < C; ++j) {
-              for (int f = 0; cfg->match_lr && f < (int)F; ++f) fill(row[pi++], B, p->left_row(j, f), B, p->right_row(j, f), cfg->radius_lr);
-              for (int f = 0; cfg->match_prev && f < (int)F; ++f) {
-                if (f > 0) fill(row[pi++], B, p->left_row(j, f), B, p->left_row(j, f - 1), cfg->radius_prev);
-                else if (j > 0) fill(row[pi++], B, p->left_row(j, 0), B, p->left_row(j - 1, (int)F - 1), cfg->radius_prev);
-                else fill(row[pi++], B, p->left_row(0, 0), PB, p->left_row(v, (int)F - 1), cfg->radius_prev);        // previous pass: its last submit is v
-              }
-            }
-          }
-      HIP_TRY(hipMalloc(&p->d_pairs, sizeof(MatchPairDesc) * tab.size()));
-      HIP_TRY(hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice));
+      const size_t maxp = (size_t)p->npp * C;
       p->match_scratch_lane = match_scratch_bytes((int)maxp, p->cap);
       HIP_TRY(hipMalloc(&p->d_match_scratch, p->match_scratch_lane * p->K));
       HIP_TRY(hipMemset(p->d_match_scratch, 0, p->match_scratch_lane * p->K));
@@ -614,7 +713,7 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   for (auto& L : p->lanes) {
     if (L.s) (void)hipStreamSynchronize(L.s);
     if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
-    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1], L.ev_chain}) if (e) (void)hipEventDestroy(e);
     if (L.pin_in) (void)hipHostFree(L.pin_in);
     for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
     if (L.ctx) d2fe_destroy(L.ctx);
@@ -626,6 +725,8 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   if (p->pin_gnv) (void)hipHostFree(p->pin_gnv);
   if (p->d_img_all) (void)hipFree(p->d_img_all);
   if (p->d_lk_ws) (void)hipFree(p->d_lk_ws);
+  if (p->d_carry_pyr) (void)hipFree(p->d_carry_pyr);
+  if (p->d_next_id) (void)hipFree(p->d_next_id);
   if (p->d_pairs) (void)hipFree(p->d_pairs);
   if (p->d_match_scratch) (void)hipFree(p->d_match_scratch);
   if (p->d_all) (void)hipFree(p->d_all);
@@ -793,6 +894,7 @@ int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_result* ou
   if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
   memset(out, 0, sizeof(*out));
   if (!p->lk) return pipe_fail(D2FE_ERR_UNSUPPORTED, "this pipe was created without lr_lk: it has no left -> right LK tracks");
+  if (p->sp_lk) return pipe_fail(D2FE_ERR_UNSUPPORTED, "this pipe runs sp_lk: the per-keypoint left -> right launch is not issued; the tracks of the list entries are in d2fe_pipe_track_result_get");
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
   if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
@@ -807,6 +909,55 @@ int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_result* ou
   out->pts_xy = B + p->o_lkp + r0 * cap * 2;
   out->status = reinterpret_cast<const uint8_t*>(B + p->o_lks) + r0 * cap;
   return D2FE_OK;
+}
+
+int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_track_result* out) {
+  if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (!p->sp_lk) return pipe_fail(D2FE_ERR_UNSUPPORTED, "this pipe was created without sp_lk: it carries no landmark list");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
+  const auto ti = p->tinfo[(size_t)(ticket % (long long)p->tinfo.size())];
+  if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass < 0 || ti.pass + 2 * p->K < p->next_pass)
+    return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the lists within 2 * lanes passes");
+  if (!ti.waited) return pipe_fail(D2FE_ERR_NOT_READY, "d2fe_pipe_wait has not returned this ticket yet");
+  const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
+  const float* B = p->lanes[k].pin_out[set];
+  const size_t r0 = p->C > 1 ? (size_t)ti.j : 0, capT = (size_t)p->capT;
+  const float* list = B + p->o_list + r0 * p->list_words;
+  auto at = [&](int field) { return list + d2fe_lk_carry_list_offset(p->capT, p->D, field); };
+  const int32_t* hdr = reinterpret_cast<const int32_t*>(at(D2FE_LKC_HDR));
+  out->frames = p->F; out->cap_tracks = p->capT; out->desc_dim = p->D; out->list_words = (int32_t)p->list_words;
+  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
+  out->pts_xy = at(D2FE_LKC_PTS);
+  out->id = reinterpret_cast<const int32_t*>(at(D2FE_LKC_ID)); out->src = reinterpret_cast<const int32_t*>(at(D2FE_LKC_SRC));
+  out->kp = reinterpret_cast<const int32_t*>(at(D2FE_LKC_KP));
+  out->desc = at(D2FE_LKC_DESC); out->scores = at(D2FE_LKC_SCORES);
+  out->right_xy = B + p->o_rxy + r0 * capT * 2;
+  out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_rst) + r0 * capT;
+  return D2FE_OK;
+}
+
+int d2fe_pipe_set_track_params(d2fe_pipe p, const d2fe_track_params* tp) {
+  if (!p || !tp) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  if (!p->sp_lk) return pipe_fail(D2FE_ERR_INVALID, "this pipe was created without sp_lk: it has no tracker parameters");
+  if (const char* why = lk_carry_check_params(tp)) return pipe_fail(D2FE_ERR_INVALID, why);
+  if (tp->levels != LK_LEVELS) return pipe_fail(D2FE_ERR_INVALID, "levels must be 2 (PYR_LEVEL): the lanes' pyramid workspaces are that deep");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->next_ticket > 0) return pipe_fail(D2FE_ERR_INVALID, "the tracker parameters are fixed by the first submit");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  const d2fe_track_params old = p->tp;
+  p->tp = *tp; p->tp.reserved = 0;
+  if (p->tp.total_feature_num == old.total_feature_num) return D2FE_OK;       // same cap_tracks: same blocks
+  // a failure below leaves the pipe without result blocks: final, like a failed submit
+  int rc = pipe_alloc_blocks(p);
+  for (auto& L : p->lanes) if (rc == D2FE_OK) rc = pipe_alloc_pinned(p, L);
+  if (rc == D2FE_OK) rc = pipe_alloc_pairs(p);
+  if (rc == D2FE_OK && hipDeviceSynchronize() != hipSuccess) rc = pipe_fail(D2FE_ERR_HIP, "hipDeviceSynchronize");      // the blocks are zeroed on the null stream
+  if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
+  return rc;
 }
 
 // ---- device-side consumers of a ticket (the cross-agent exchange on a stream of its own) ----------------------------------------------------------------

@@ -297,7 +297,17 @@ typedef struct {
                                image has no descriptors: D2FE_ERR_INVALID otherwise).  Works with any lanes / frames, netvlad, match_prev, pinned_input,
                                coalesce, coalesce_depth, netvlad_inline, netvlad_group, lane_cus and cu_partition (the LK launches run on the lane's own
                                stream, CU-masked or not).  0 (d2fe_pipe_default_config): SuperPoint on both images, as before */
-  int32_t reserved[1];
+  int32_t sp_lk;            /* 1 (needs lr_lk = 1, D2FE_ERR_INVALID otherwise; the two together are the reference's defaults): the OTHER half of the reference's stereo
+                               tracker, sp_track_use_lk = true (d2featuretracker.h:63): the temporal association is the LK-carried landmark list of
+                               D2FeatureTracker::trackLK(frame) (d2featuretracker.cpp:472-621), kept on the DEVICE and carried across frames, passes and lanes: per left
+                               frame one d2fe_lk_carry_step_device (track the previous list, reduceVector, removeNearPoints, replenish from the frame's SuperPoint
+                               keypoints, carry descriptors), in time order behind the pass's pyramids, then ONE left -> right launch over the list entries of all
+                               frames.  A pass's chain starts from the last list and the last left pyramid of the previous pass (an event orders it behind that pass's
+                               chain; the pyramid is copied to a pipe-owned buffer, the list is read where the previous pass left it); next_id is the pipe's.  The
+                               lists travel with the pass's one D2H and are read with d2fe_pipe_track_result_get; d2fe_pipe_lk_result_get is D2FE_ERR_UNSUPPORTED (the
+                               per-keypoint left -> right launch is not issued).  d2fe_pipe_result is bit-identical to the same pipe with sp_lk = 0 (match_prev stays
+                               available).  Parameters: d2fe_pipe_set_track_params before the first submit (the reference's defaults otherwise).  Works with any
+                               lanes / frames and every other option; frames are chained in submit order.  0 (d2fe_pipe_default_config): off */
 } d2fe_pipe_config;
 typedef struct {            /* HOST pointers into the lane's pinned block; valid until 2 * lanes further submits */
   int32_t frames, cap, desc_dim, netvlad_dim;
@@ -336,6 +346,34 @@ D2FE_API int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* r
  * for in any order, each within 2 * lanes passes (a pass = `coalesce` submits). */
 D2FE_API int d2fe_pipe_wait(d2fe_pipe p, int64_t ticket, d2fe_pipe_result* out);
 D2FE_API int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_result* out);
+/* sp_lk = 1: the landmark lists of a ticket that d2fe_pipe_wait has returned (D2FE_ERR_NOT_READY before that, D2FE_ERR_UNSUPPORTED on a pipe without sp_lk).
+ * Frame f's list is a d2fe_lk_carry_step_device list block; the per-list pointers below address frame 0's block and frame f's is `list_words` 32-bit words
+ * further on for EVERY one of them (n[f * list_words], pts_xy + f * list_words, ...).  Entry i < n of frame f: position pts_xy[i] in the left image, id[i]
+ * (pipe-wide, counted from 0 in order of discovery: the caller maps it to its lmanager id), src[i] = its index in the PREVIOUS frame's list (-1: discovered in
+ * this frame, from SuperPoint keypoint kp[i] of d2fe_pipe_result's left row; kp = -1 for tracked entries), desc / scores = the SuperPoint row of its discovery
+ * frame (d2featuretracker.cpp:509-521), right_xy[f][i] / right_status[f][i] = its left -> right track (trackLK(left, right), :697-752; semantics of
+ * d2fe_pipe_lk_result).  Slots >= n hold zeros.  What stays with the caller: id -> lmanager ids, createLKLandmark / liftProjective (an entry it rejects keeps
+ * its slot here), velocities and the lk_lk_use_pred gate. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
+  int32_t frames, cap_tracks, desc_dim, list_words;
+  const int32_t* n;                  /* per list: entries -- frame f's count is n[f * list_words], NOT n[f]; the same stride for every "per list" pointer below */
+  const int32_t* n_tracked_in;       /* per list (n_tracked_in[f * list_words]): entries of the previous list that were tracked (its n) */
+  const int32_t* n_lost;             /* per list (n_lost[f * list_words]): dropped by the tracker's status (reduceVector) */
+  const int32_t* n_removed_near;     /* per list (n_removed_near[f * list_words]): dropped by removeNearPoints */
+  const int32_t* n_new;              /* per list (n_new[f * list_words]): appended from this frame's SuperPoint keypoints */
+  const float* pts_xy;               /* per list: [cap_tracks][2] at pts_xy + f * list_words */
+  const int32_t* id; const int32_t* src; const int32_t* kp;      /* per list: [cap_tracks] at + f * list_words */
+  const float* desc;                 /* per list: [cap_tracks][desc_dim] at desc + f * list_words */
+  const float* scores;               /* per list: [cap_tracks] at scores + f * list_words */
+  const float* right_xy;             /* [frames][cap_tracks][2], contiguous (NOT strided by list_words) */
+  const uint8_t* right_status;       /* [frames][cap_tracks], contiguous */
+} d2fe_pipe_track_result;
+D2FE_API int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_track_result* out);
+/* sp_lk = 1: replaces the reference's default tracker parameters (d2fe_track_default_params).  Accepted only before the first submit (D2FE_ERR_INVALID afterwards,
+ * on a pipe without sp_lk, for levels != 2 -- the lane's pyramid workspace is PYR_LEVEL deep -- and for parameters d2fe_lk_carry_step_device refuses, e.g.
+ * total_feature_num + 1 > 1024); a refusal leaves the pipe as it was. */
+struct d2fe_track_params_s;
+D2FE_API int d2fe_pipe_set_track_params(d2fe_pipe p, const struct d2fe_track_params_s* tp);
 
 /* Device-side consumers of a ticket's results: the cross-agent exchange (pack -> all-gather -> gate -> remote matching; the reference broadcasts
  * the frame it has just extracted, loop_net.cpp:24-87, d2featuretracker.cpp:237-310) runs on a stream of its OWN, behind the extraction of the ticket and beside the
@@ -532,6 +570,47 @@ D2FE_API size_t d2fe_lk_stereo_workspace_bytes(int n_frames, int width, int heig
 D2FE_API int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint8_t* d_right, int n_frames, int width, int height, int stride,
                                          size_t image_stride, const float* d_kps_xy /*[n_frames][cap][2]*/, const int32_t* d_n_kp /*[n_frames]*/, int cap,
                                          int levels, int win, int iters, void* d_workspace, float* d_pts_xy, uint8_t* d_status, void* stream);
+/* d_kps_xy, d_n_kp, d_pts_xy and d_status all NULL (cap ignored): the pyramids alone, max(levels, 1) launches -- the workspace of d2fe_lk_carry_step_device. */
+
+/* The LK-carried landmark list of sp_track_use_lk (D2FeatureTracker::trackLK(frame), d2featuretracker.cpp:472-621) for ONE camera and ONE frame, on the device:
+ *   a. every entry i < n of the previous list is tracked from the previous pyramid to the current one: opticalflowTrackPyr(..., WHOLE_IMG_MATCH)
+ *      (opticaltrack_utils.cpp:173-279; cur_init = prev_pts, forward, reverse, 0.5 px round trip, inBorder) -- the bits of d2fe_lk_track(prev, cur, pts, pts, n, 0, 0, win, iters);
+ *   b. order-preserving compaction by status (reduceVector, :273-276);
+ *   c. removeNearPoints(info, near_lk_thread_rate) (opticaltrack_utils.h:61-89): greedy, in order, an entry is dropped when an earlier KEPT entry is nearer than the
+ *      threshold; distance as cv::norm(Point2f): float difference, squares and sqrt in double, `<` against the float threshold widened to double;
+ *   d. replenish (d2featuretracker.cpp:556-589) over the frame's SuperPoint keypoints i = 0 .. n_kp - 1 in list order: stop when n > total_feature_num (strict: the list
+ *      can reach total_feature_num + 1 = cap_tracks), skip keypoint i if ANY current entry (those appended in this loop included) is nearer than feature_min_dist (a
+ *      double), otherwise append it with id = next_id++, src = -1, kp = i and its SuperPoint descriptor row and score;
+ *   e. a tracked entry keeps its id, src = its index in the previous list, kp = -1, descriptor and score carried from the previous list (:509-521).
+ * A previous list with n = 0 (the first frame) skips a-c.  ONE launch: one wave per entry tracks, the last workgroup to finish does b-e.
+ * A LIST is one block of d2fe_lk_carry_list_bytes(cap_tracks, desc_dim) bytes (host arithmetic; 0 for cap_tracks outside 1..1024 or desc_dim < 1), 32-bit words, every
+ * array on a 64-word boundary, d2fe_lk_carry_list_offset(cap_tracks, desc_dim, field) words from its base (-1: bad field):
+ *   D2FE_LKC_HDR     int32[64]: [0] n, [1] n_tracked_in (the previous list's n), [2] n_lost, [3] n_removed_near, [4] n_new, [5] the launch's arrival counter (0 between
+ *                    launches), [6] next_id after this frame, rest 0
+ *   D2FE_LKC_PTS     float[cap_tracks][2]      D2FE_LKC_ID / _SRC / _KP   int32[cap_tracks]      D2FE_LKC_SCORES  float[cap_tracks]
+ *   D2FE_LKC_DESC    float[cap_tracks][desc_dim]
+ *   D2FE_LKC_TRK_XY  float[cap_tracks][2], D2FE_LKC_TRK_STATUS uint8[cap_tracks]: step a's raw result for the PREVIOUS list's entries (before b)
+ * Slots >= n of every array are written as zeros.  A block must be ZERO once before its first use as d_cur_list (the arrival counter; the launch leaves it zero), and
+ * an all-zero block is the empty list.  d_prev_list != d_cur_list; the previous list's cap_tracks / desc_dim are this call's.  The pyramids are in the layout of a
+ * d2fe_lk_frame / one image of the d2fe_lk_track_stereo_device workspace (tp->levels + 1 levels, no padding).  d_kps_xy [kp_cap][2], d_kp_scores [kp_cap],
+ * d_kp_desc [kp_cap][desc_dim], d_n_kp [1]: the outputs of d2fe_superpoint_extract_device for the current frame (n_kp is clamped to kp_cap; kp_cap = 0: none).
+ * d_next_id: one int32 in device memory, read and advanced by the launch.  Everything is read on the device: the call only enqueues on `stream` (NULL: the handle's
+ * stream) -- no allocation, no synchronisation, no memset.  D2FE_ERR_INVALID: total_feature_num outside 0..1023, thresholds < 0 or NaN, LK parameters outside the
+ * ranges of d2fe_lk_track_batch, bad geometry. */
+typedef struct d2fe_track_params_s {
+  int32_t total_feature_num;      /* 150   max_cnt (d2frontend_params.cpp:62) */
+  int32_t levels, win, iters;     /* 2, 21, 30   PYR_LEVEL, WIN_SIZE, opticaltrack_utils.cpp:239 */
+  float near_lk_thread_rate;      /* 5.0   d2featuretracker.h:69 */
+  int32_t reserved;               /* zero */
+  double feature_min_dist;        /* 20    d2frontend_params.h:65 */
+} d2fe_track_params;
+enum { D2FE_LKC_HDR = 0, D2FE_LKC_PTS, D2FE_LKC_ID, D2FE_LKC_SRC, D2FE_LKC_KP, D2FE_LKC_SCORES, D2FE_LKC_DESC, D2FE_LKC_TRK_XY, D2FE_LKC_TRK_STATUS, D2FE_LKC_FIELDS };
+D2FE_API void d2fe_track_default_params(d2fe_track_params* tp);
+D2FE_API size_t d2fe_lk_carry_list_bytes(int cap_tracks, int desc_dim);
+D2FE_API long d2fe_lk_carry_list_offset(int cap_tracks, int desc_dim, int field);
+D2FE_API int d2fe_lk_carry_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list,
+                                       void* d_cur_list, int desc_dim, const float* d_kps_xy, const float* d_kp_scores, const float* d_kp_desc,
+                                       const int32_t* d_n_kp, int kp_cap, const d2fe_track_params* tp, int32_t* d_next_id, void* stream);
 /* detectFastByRegion (opticaltrack_utils.cpp:444-493): cv::cuda::FastFeatureDetector(threshold, nonmax, TYPE_9_16,
  * max_npoints = features) on each of the cols x rows regions of level 0, sorted by response, top `features`.
  * response (optional) receives the FAST scores. */

@@ -183,6 +183,16 @@ class MobileNetVLAD {
 // D2FeatureTracker::trackLocalFrames, d2featuretracker.cpp:403-456,658-695) with several frames in flight: d2fe_pipe_* of include/d2fe.h behind the
 // containers the reference's call sites use.  submit() from the image callback, wait() from the tracker thread; results bit-identical to
 // SuperPoint::infer + MobileNetVLAD::inference + matchKNN on the same frames.
+// cfg.sp_lk = 1 (sp_track_use_lk, with lr_lk the reference's defaults): the frame's LK-carried landmark list, what D2FeatureTracker::trackLK(frame) leaves in
+// LKImageInfo (d2featuretracker.cpp:472-621) -- entry i at pts[i] with the pipe-wide id[i]; src[i] = its index in the previous frame's list (-1: discovered in this
+// frame from SuperPoint keypoint kp[i] of kps_left); desc / scores are the SuperPoint row of its discovery frame; right[i] / right_status[i] its left -> right track
+struct StereoTrackList {
+  std::vector<Point2f> pts, right;
+  std::vector<int32_t> id, src, kp;
+  std::vector<float> scores, desc;                   // desc: [n][desc_dim]
+  std::vector<uint8_t> right_status;
+  int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0;
+};
 struct StereoFrameResult {
   std::vector<Point2f> kps_left, kps_right;
   std::vector<float> scores_left, scores_right;
@@ -194,15 +204,21 @@ struct StereoFrameResult {
   // sits in the right image when lk_status[i] != 0 (what trackLK, d2featuretracker.cpp:697-752, hands to reduceVector); kps_right / left_right stay empty
   std::vector<Point2f> lk_right;
   std::vector<uint8_t> lk_status;
+  StereoTrackList tracks;                            // cfg.sp_lk = 1 (lk_right / lk_status then stay empty: the list entries are what is tracked into the right image)
 };
 class StereoPipe {
  public:
   // cfg: d2fe_pipe_default_config() + the fields the caller sets (lanes, width, height, cap, netvlad, coalesce, coalesce_depth, lr_lk (with match_lr = 0), ...);
-  // frames is forced to 1
-  StereoPipe(d2fe_handle h, d2fe_pipe_config cfg) {
+  // frames is forced to 1.  cfg.sp_lk = 1 (with lr_lk = 1): tp replaces the reference's tracker parameters (d2fe_track_default_params)
+  StereoPipe(d2fe_handle h, d2fe_pipe_config cfg, const d2fe_track_params* tp = nullptr) {
     cfg.frames = 1;
-    lr_lk_ = cfg.lr_lk != 0;
+    sp_lk_ = cfg.sp_lk != 0;
+    lr_lk_ = cfg.lr_lk != 0 && !sp_lk_;
     if (d2fe_pipe_create(h, &cfg, &p_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_create: %s\n", d2fe_last_error()); p_ = nullptr; }
+    if (p_ && tp && d2fe_pipe_set_track_params(p_, tp) != D2FE_OK) {
+      std::fprintf(stderr, "[d2fe] d2fe_pipe_set_track_params: %s\n", d2fe_last_error());
+      d2fe_pipe_destroy(p_); p_ = nullptr;
+    }
   }
   ~StereoPipe() { if (p_) d2fe_pipe_destroy(p_); }
   StereoPipe(const StereoPipe&) = delete;
@@ -242,6 +258,18 @@ class StereoPipe {
       for (int j = 0; j < n; ++j) out.lk_right.emplace_back(lk.pts_xy[2 * j], lk.pts_xy[2 * j + 1]);
       out.lk_status.assign(lk.status, lk.status + n);
     }
+    out.tracks = StereoTrackList();
+    if (sp_lk_) {
+      d2fe_pipe_track_result tr;
+      if (d2fe_pipe_track_result_get(p_, ticket, &tr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_track_result_get: %s\n", d2fe_last_error()); return false; }
+      StereoTrackList& t = out.tracks;
+      const int n = tr.n[0];
+      for (int j = 0; j < n; ++j) { t.pts.emplace_back(tr.pts_xy[2 * j], tr.pts_xy[2 * j + 1]); t.right.emplace_back(tr.right_xy[2 * j], tr.right_xy[2 * j + 1]); }
+      t.id.assign(tr.id, tr.id + n); t.src.assign(tr.src, tr.src + n); t.kp.assign(tr.kp, tr.kp + n);
+      t.scores.assign(tr.scores, tr.scores + n); t.desc.assign(tr.desc, tr.desc + (size_t)n * tr.desc_dim);
+      t.right_status.assign(tr.right_status, tr.right_status + n);
+      t.n_tracked_in = tr.n_tracked_in[0]; t.n_lost = tr.n_lost[0]; t.n_removed_near = tr.n_removed_near[0]; t.n_new = tr.n_new[0];
+    }
     return true;
   }
   // d2fe_pipe_stream_placement: the hardware-pipe class measured for every lane's (own, second) stream; the return value = classes told apart (0: not measured)
@@ -258,7 +286,7 @@ class StereoPipe {
 
  private:
   d2fe_pipe p_ = nullptr;
-  bool lr_lk_ = false;
+  bool lr_lk_ = false, sp_lk_ = false;
 };
 
 // d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
