@@ -141,6 +141,15 @@ class _QuadPipeResult(C.Structure):
                 ("prev_q", C.c_void_p), ("prev_t", C.c_void_p), ("prev_dist", C.c_void_p), ("prev_n", C.c_void_p)]
 
 
+class _QuadTrackResult(C.Structure):
+    """d2fe_quad_track_result: the landmark lists, neighbour tracks and list matches of a quad ticket (d2fe_quad_track_enable)"""
+    _fields_ = [("quads", C.c_int32), ("cap_tracks", C.c_int32), ("desc_dim", C.c_int32), ("list_words", C.c_int32),
+                ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p),
+                ("pts_xy", C.c_void_p), ("id", C.c_void_p), ("src", C.c_void_p), ("kp", C.c_void_p), ("desc", C.c_void_p), ("scores", C.c_void_p),
+                ("nb_lk_xy", C.c_void_p), ("nb_lk_status", C.c_void_p),
+                ("lnb_q", C.c_void_p), ("lnb_t", C.c_void_p), ("lnb_dist", C.c_void_p), ("lnb_n", C.c_void_p)]
+
+
 class _QuadDeviceResult(C.Structure):
     _fields_ = [("quads", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
                 ("d_kps_xy", C.c_void_p), ("d_scores", C.c_void_p), ("d_desc", C.c_void_p), ("d_n_kp", C.c_void_p), ("d_netvlad", C.c_void_p)]
@@ -185,7 +194,7 @@ EXPORTS = [
     "d2fe_lk_frame_create_device", "d2fe_lk_frame_destroy", "d2fe_lk_frame_read_level", "d2fe_lk_track", "d2fe_lk_track_batch",
     "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
     "d2fe_track_default_params", "d2fe_lk_carry_list_bytes", "d2fe_lk_carry_list_offset", "d2fe_lk_carry_step_device", "d2fe_pipe_track_result_get",
-    "d2fe_pipe_set_track_params",
+    "d2fe_pipe_set_track_params", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -343,6 +352,12 @@ def _open_library(path, dev):
         lib.d2fe_lk_carry_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_track_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_lk_carry_quad_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_lk_carry_neighbour_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_track_enable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_track_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_set_track_params.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_detect_fast_by_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_void_p]
@@ -1073,10 +1088,13 @@ class QuadPipe:
     SuperPoint and NetVLAD of every view -> the four neighbour pairs (0,1) (1,2) (2,3) (0,3) and the temporal pairs, with up to `lanes` submits in flight.
     maps: per camera (mapx, mapy, gain or None) as [height][width] float32 numpy arrays or device tensors (anything with .data_ptr()); the pipe copies them.
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits).
-    Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit)."""
+    Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit).
+    sp_lk=True (d2fe_quad_track_enable; track_params: a dict of d2fe_track_params fields, a _TrackParams or None for the reference's defaults): the LK-carried
+    landmark lists of the four cameras, the neighbour LK tracks and the neighbour matches of the lists; wait() then carries the track_* keys."""
 
     def __init__(self, fe: FrontEnd, maps, lanes=4, quads=1, raw_width=1280, raw_height=800, width=800, height=400, cap=None, netvlad=True,
-                 match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False):
+                 match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False,
+                 sp_lk=False, track_params=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _QuadPipeConfig()
@@ -1110,6 +1128,25 @@ class QuadPipe:
         self.lanes, self.quads, self.raw_width, self.raw_height = int(lanes), int(quads), int(raw_width), int(raw_height)
         self._pinned_input = bool(pinned_input)
         self._res = _QuadPipeResult()
+        self._track_res = _QuadTrackResult()
+        self._sp_lk = False
+        if sp_lk:
+            try:
+                self.track_enable(track_params)
+            except Exception:
+                self.close()
+                raise
+
+    def track_enable(self, tp=None):
+        """d2fe_quad_track_enable: once, before the first submit (tp: dict of d2fe_track_params fields, a _TrackParams, or None for the defaults)"""
+        tp = track_params(**tp) if isinstance(tp, dict) else tp
+        _check(self._lib.d2fe_quad_track_enable(self._p, C.byref(tp) if tp is not None else None))
+        self._sp_lk = True
+
+    def track_result_raw(self, ticket):
+        """d2fe_quad_track_result_get: the lists of a ticket that wait() has returned"""
+        _check(self._lib.d2fe_quad_track_result_get(self._p, C.c_int64(ticket), C.byref(self._track_res)))
+        return self._track_res
 
     def close(self):
         if getattr(self, "_p", None) and self._p.value:
@@ -1172,6 +1209,23 @@ class QuadPipe:
         for k in ("nb", "prev"):
             out[k + "_q"] = _pinned_view(getattr(r, k + "_q"), (Q, 4, cap), i); out[k + "_t"] = _pinned_view(getattr(r, k + "_t"), (Q, 4, cap), i)
             out[k + "_dist"] = _pinned_view(getattr(r, k + "_dist"), (Q, 4, cap), f); out[k + "_n"] = _pinned_view(getattr(r, k + "_n"), (Q, 4), i)
+        if self._sp_lk:
+            t = self.track_result_raw(ticket)
+            T, lw = t.cap_tracks, t.list_words
+
+            def per_list(ptr, shape, dt):      # [quads][4] + shape views of a per-list array: list (q, c) is (q * 4 + c) * list_words words further on
+                base = _pinned_view(ptr, ((Q * 4 - 1) * lw + int(np.prod(shape or (1,))),), dt)
+                return np.lib.stride_tricks.as_strided(base, (Q, 4) + tuple(shape), (16 * lw, 4 * lw) + tuple(np.zeros(shape, dt).strides), writeable=False)
+            for k in ("n", "n_tracked_in", "n_lost", "n_removed_near", "n_new"):
+                out["track_" + k] = per_list(getattr(t, k), (), i)
+            out["track_pts"] = per_list(t.pts_xy, (T, 2), f); out["track_scores"] = per_list(t.scores, (T,), f); out["track_desc"] = per_list(t.desc, (T, D), f)
+            for k in ("id", "src", "kp"):
+                out["track_" + k] = per_list(getattr(t, k), (T,), i)
+            out["track_nb_lk_xy"] = _pinned_view(t.nb_lk_xy, (Q, 4, T, 2), f)
+            out["track_nb_lk_status"] = np.frombuffer((C.c_uint8 * (Q * 4 * T)).from_address(t.nb_lk_status), dtype=np.uint8).reshape(Q, 4, T)
+            for k in ("q", "t"):
+                out["track_lnb_" + k] = _pinned_view(getattr(t, "lnb_" + k), (Q, 4, T), i)
+            out["track_lnb_dist"] = _pinned_view(t.lnb_dist, (Q, 4, T), f); out["track_lnb_n"] = _pinned_view(t.lnb_n, (Q, 4), i)
         return out
 
 
@@ -1362,6 +1416,25 @@ def lk_carry_step(fe: FrontEnd, d_prev_pyr, d_cur_pyr, width, height, d_prev_lis
     tp = tp if tp is not None else track_params()
     _check(fe._lib.d2fe_lk_carry_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(width), int(height), d_prev_list, d_cur_list, int(desc_dim), d_kps_xy or None,
                                              d_kp_scores or None, d_kp_desc or None, d_n_kp or None, int(kp_cap), C.byref(tp), d_next_id, stream))
+
+
+def lk_carry_quad_step(fe: FrontEnd, d_prev_pyr, d_cur_pyr, pyr_stride, width, height, d_prev_lists, d_cur_lists, list_stride, d_kps_xy, d_kp_scores, d_kp_desc,
+                       d_n_kp, kp_cap, d_next_id, tp=None, desc_dim=256, stream=None):
+    """The four cameras' lists of one quad frame in ONE launch (d2fe_lk_carry_quad_step_device): camera c's lists / pyramids are c * list_stride words /
+    c * pyr_stride bytes behind the bases, its keypoints row c of the dense [4][kp_cap] extract outputs.  The bits of four lk_carry_step calls in camera order."""
+    tp = tp if tp is not None else track_params()
+    _check(fe._lib.d2fe_lk_carry_quad_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(pyr_stride), int(width), int(height), d_prev_lists, d_cur_lists, int(list_stride),
+                                                  int(desc_dim), d_kps_xy or None, d_kp_scores or None, d_kp_desc or None, d_n_kp or None, int(kp_cap), C.byref(tp),
+                                                  d_next_id, stream))
+
+
+def lk_carry_neighbour(fe: FrontEnd, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, d_nb_xy, d_nb_status, tp=None, desc_dim=256,
+                       stream=None):
+    """trackLK(left, right, type) of the four neighbour pairs of `quads` quad frames over device-resident lists, ONE launch (d2fe_lk_carry_neighbour_device):
+    d_nb_xy [quads][4][cap_tracks][2] float32, d_nb_status [quads][4][cap_tracks] uint8, written for every slot."""
+    tp = tp if tp is not None else track_params()
+    _check(fe._lib.d2fe_lk_carry_neighbour_device(fe.handle, d_pyr, int(pyr_stride), int(quads), int(width), int(height), float(undistort_fov), d_lists,
+                                                  int(list_stride), int(desc_dim), C.byref(tp), d_nb_xy, d_nb_status, stream))
 
 
 class _LKPair(C.Structure):

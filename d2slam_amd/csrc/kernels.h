@@ -226,6 +226,9 @@ hipError_t launch_quad_gate(const float* loc, long loc_stride, const float* rem,
 hipError_t launch_half_compact(const float* desc, const float* pts, const int32_t* n_kp, const int32_t* job_row, const int32_t* job_left,
                                const float* job_shift, int njobs, int cap, int dim, float width_undistort, float move_cols,
                                float* out_desc, float* out_pts, int32_t* out_map, int32_t* out_n, hipStream_t s);
+hipError_t launch_half_compact_strided(const float* desc, const float* pts, const int32_t* n_kp, size_t desc_stride, size_t pts_stride, size_t n_stride,
+                                       const int32_t* job_row, const int32_t* job_left, const float* job_shift, int njobs, int cap, int dim, float width_undistort,
+                                       float move_cols, float* out_desc, float* out_pts, int32_t* out_map, int32_t* out_n, hipStream_t s);
 hipError_t launch_remap_matches(int32_t* q_idx, int32_t* t_idx, const int32_t* n_match, const int32_t* map_a_job, const int32_t* map_b_job,
                                 const int32_t* maps, int npairs, int cap_match, int cap_map, hipStream_t s);
 

@@ -157,5 +157,27 @@ __device__ __forceinline__ int lk_bidir(const LkArgs& a, const LkPairDev& P, con
   return ok;
 }
 
+// The half-image form (LEFT_RIGHT_IMG_MATCH type 1 / RIGHT_LEFT_IMG_MATCH type 2, opticaltrack_utils.cpp:197-253) for one point that has passed the gate: the
+// initial guess is the point shifted by +move_cols (type 1) or -move_cols (type 2), the reverse track starts from the forward result shifted back when the
+// forward status is 1.  The arithmetic of lk_track_kernel (lk.hip) with P.type 1 / 2 and cur_init = (ppx +- move_cols, ppy)
+__device__ __forceinline__ int lk_bidir_half(const LkArgs& a, const LkPairDev& P, const uint8_t* Ip, const uint8_t* Jp, float ppx, float ppy, int type, float move_cols,
+                                             float& cx, float& cy, int lane) {
+  cx = type == 1 ? ppx + move_cols : ppx - move_cols; cy = ppy;
+  int st = 1, rst = 1;
+  lk_calc(a, P, Ip, Jp, ppx, ppy, cx, cy, st, lane);
+  float rx = cx, ry = cy;
+  if (type == 1 && st == 1) rx -= move_cols;
+  if (type == 2 && st == 1) rx += move_cols;
+  lk_calc(a, P, Jp, Ip, cx, cy, rx, ry, rst, lane);
+  const float dx = ppx - rx, dy = ppy - ry;
+  const double nrm = __builtin_sqrt((double)dx * dx + (double)dy * dy);
+  int ok = (st && rst && nrm <= 0.5) ? 1 : 0;
+  if (ok) {
+    const int ix = (int)__builtin_rint((double)cx), iy = (int)__builtin_rint((double)cy);
+    if (!(1 <= ix && ix < P.w - 1 && 1 <= iy && iy < P.h - 1)) ok = 0;
+  }
+  return ok;
+}
+
 }  // namespace
 }  // namespace d2fe

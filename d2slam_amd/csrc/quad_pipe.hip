@@ -9,6 +9,15 @@
 //     -> remap_matches_kernel of the neighbour pairs -> ONE D2H of the result block into pinned memory.
 // Only the undistort launch is new device code; extraction, NetVLAD, compaction, matcher and remap are the kernels the single calls launch.  Result blocks,
 // tickets and their lifetime are the stereo pipe's with one submit per pass: two blocks per lane, a ticket's block is written again 2 K passes later.
+//
+// d2fe_quad_track_enable (sp_lk: enable_lk_optical_flow + sp_track_use_lk of the reference's quadcam tracker, trackLocalFrames d2featuretracker.cpp:121-133): behind the
+// pass's SuperPoint the lane builds the pyramids of its 4 Q views, then the landmark lists (lk_carry.hip) are stepped once per quad frame -- ONE launch for the four
+// cameras, d2fe_lk_carry_quad_step_device.  The lists are a chain across quad frames, passes and lanes: quad frame 0 of a pass reads the last four lists of the
+// previous pass in that pass's result block and its four pyramids from d_carry_pyr, which the previous pass copied there on its own stream; the lane's ev_chain,
+// recorded behind the copy, is what the next pass's first step waits for (pipe.hip's scheme).  ONE launch then tracks the list entries of every neighbour pair
+// (d2fe_lk_carry_neighbour_device), and the lists go through the half-image compaction (reading the list blocks in place), ONE matcher launch and the remap, like the
+// keypoints.  The mode's arrays are appended to the result block in front of d2h_words, so they travel in the pass's one D2H; a pipe that never enables the mode
+// keeps the layout and the allocations it had.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -123,10 +132,24 @@ struct d2fe_quad_pipe_s {
   MatchPairDesc* d_pairs = nullptr;    // [K][2][NP]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;
   QuadUndistortArgs ua{};              // everything but the lane's raw frames and views
+  // d2fe_quad_track_enable: per pass 4 Q list blocks at o_list (list (q, c) at (q * 4 + c) * list_words), the neighbour tracks [4 Q][capT][2] floats and [4 Q][capT]
+  // bytes, the list matches (o_lm*), all inside d2h_words.  Lane scratch of the mode (float words from tscratch(k)): the half-image pools of the lists
+  bool trk = false;
+  bool trk_split = false;              // D2FE_QUAD_TRACK_SPLIT of the development library: four single-camera steps per quad frame (a measurement, not an option)
+  d2fe_track_params tp{};
+  int capT = 0;
+  size_t list_words = 0, pyr_total = 0;
+  size_t o_list = 0, o_nbxy = 0, o_nbst = 0, o_lmn = 0, o_lmq = 0, o_lmt = 0, o_lmd = 0;
+  size_t t_jdesc = 0, t_jpts = 0, t_jmap = 0, t_jn = 0, tscr_words = 0;
+  float* d_trk = nullptr;              // [4 empty lists | 64 words: next_id | K lanes x tscr_words]
+  uint8_t* d_trk_pyr = nullptr;        // [4 carried pyramids | K lanes x 4 Q pyramids], pyr_total bytes each
+  MatchPairDesc* d_lpairs = nullptr;   // [K][4 Q]: the neighbour pairs of the lists, on the lane's pools
+  int32_t* d_lmatch_scratch = nullptr; size_t lmatch_scratch_lane = 0;
   struct Lane {
     d2fe_context* ctx = nullptr;
     hipStream_t s = nullptr, nv = nullptr;
     hipEvent_t ev_up = nullptr, ev_nv = nullptr, ev_ext[2] = {nullptr, nullptr}, ev_done = nullptr;
+    hipEvent_t ev_chain = nullptr;     // track mode: the landmark-list chain of the lane's last pass and the carry copy behind it are complete
     uint8_t* d_raw = nullptr;
     uint8_t* pin_in = nullptr;
     float* pin_out[2] = {nullptr, nullptr};
@@ -145,6 +168,10 @@ struct d2fe_quad_pipe_s {
   std::string failed_msg;
   float* block(int lane, int set) const { return d_all + 64 + ((size_t)lane * 2 + set) * blk_words; }
   float* scratch(int lane) const { return d_scr + (size_t)lane * scr_words; }
+  float* tscratch(int lane) const { return d_trk + 4 * list_words + 64 + (size_t)lane * tscr_words; }
+  int32_t* next_id() const { return reinterpret_cast<int32_t*>(d_trk + 4 * list_words); }
+  uint8_t* carry_pyr() const { return d_trk_pyr; }
+  uint8_t* lane_pyr(int lane) const { return d_trk_pyr + (4 + (size_t)lane * NI) * pyr_total; }
 };
 
 namespace {
@@ -155,6 +182,41 @@ int lane_sync(d2fe_quad_pipe_s::Lane& L) {       // called with the pipe's mutex
     L.synced = L.rec;
   }
   return D2FE_OK;
+}
+
+// the matcher's pair tables of the keypoints; they hold addresses inside the result blocks (d2fe_quad_track_enable moves those and fills the table again)
+void quad_fill_pairs(const d2fe_quad_pipe_s* p, std::vector<MatchPairDesc>& tab) {
+  const size_t cap = p->cap, D = p->D, NP = p->NP;
+  const int Q = p->Q;
+  const d2fe_quad_pipe_config* cfg = &p->cfg;
+  // pair tables [lane][set][NP]: the 4 Q neighbour pairs on the lane's compacted pools, then the 4 Q temporal pairs (view c of quad frame q against view c
+  // of quad frame q - 1; q = 0: the last quad frame of the previous pass P - 1 = lane k - 1 of the same set, or lane K - 1 of the other set when k = 0)
+  tab.assign((size_t)p->K * 2 * NP, MatchPairDesc{});
+  for (int k = 0; k < p->K; ++k)
+    for (int set = 0; set < 2; ++set) {
+      float* B = p->block(k, set);
+      float* PB = p->block(k > 0 ? k - 1 : p->K - 1, k > 0 ? set : set ^ 1);
+      float* X = p->scratch(k);
+      MatchPairDesc* row = tab.data() + ((size_t)k * 2 + set) * NP;
+      int pi = 0;
+      for (int j = 0; p->n_nb && j < 4 * Q; ++j) {
+        MatchPairDesc& d = row[pi++];
+        const size_t ja = 2 * (size_t)j, jb = ja + 1;
+        d.a = X + p->x_jdesc + ja * cap * D; d.b = X + p->x_jdesc + jb * cap * D;
+        d.pts_a = X + p->x_jpts + ja * cap * 2; d.pts_b = X + p->x_jpts + jb * cap * 2;
+        d.na = reinterpret_cast<int32_t*>(X + p->x_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + p->x_jn) + jb;
+        d.radius = cfg->radius_neighbour;
+      }
+      for (int v = 0; p->n_pr && v < 4 * Q; ++v) {
+        MatchPairDesc& d = row[pi++];
+        float* BB = v >= 4 ? B : PB;
+        const size_t ra = v, rb = v >= 4 ? v - 4 : (size_t)(4 * (Q - 1) + v);
+        d.a = B + p->o_desc + ra * cap * D; d.b = BB + p->o_desc + rb * cap * D;
+        d.pts_a = B + p->o_kps + ra * cap * 2; d.pts_b = BB + p->o_kps + rb * cap * 2;
+        d.na = reinterpret_cast<int32_t*>(B + p->o_cnt) + ra; d.nb = reinterpret_cast<int32_t*>(BB + p->o_cnt) + rb;
+        d.radius = cfg->radius_prev;
+      }
+    }
 }
 
 // one submit: H2D, undistort, NetVLAD beside SuperPoint, compaction, ONE matcher launch, remap, ONE D2H -- all on the lane's streams
@@ -216,13 +278,64 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
     if (rc) return rc;
     HIP_TRY(hipEventRecord(L.ev_nv, L.nv));
   }
-  // 5. getFeatureHalfImg of both views of every neighbour pair + the a-side shift
   const int32_t* job_row = p->d_jobs;
   const int32_t* job_left = job_row + 8 * Q;
   const float* job_shift = reinterpret_cast<const float*>(job_left + 8 * Q);
   const int32_t* map_a = job_left + 16 * Q;
   const int32_t* map_b = map_a + 4 * Q;
   int32_t* jmap = reinterpret_cast<int32_t*>(X + p->x_jmap);
+  if (p->trk) {
+    // the pyramids of the pass's 4 Q views (view i of the lane's scratch = image i of the workspace), then the landmark lists: ONE step per quad frame in time order,
+    // the carry copy, ONE launch for the neighbour tracks of every list
+    uint8_t* pyr = p->lane_pyr(k);
+    rc = d2fe_lk_track_stereo_device(L.ctx, und, und + (size_t)2 * Q * img, 2 * Q, W, H, W, img, nullptr, nullptr, 0, p->tp.levels, p->tp.win, p->tp.iters, pyr, nullptr,
+                                     nullptr, s);
+    if (rc) return rc;
+    const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+    if (P > 0 && p->K > 1) HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_chain, 0));
+    float* lists = B + p->o_list;
+    for (int q = 0; q < Q; ++q) {
+      // the predecessor: the quad frame before in this pass; q = 0: the last quad frame of the previous pass (its block, the carried pyramids); the very first quad
+      // frame reads four empty lists and tracks nothing
+      const float* prev_lists = q > 0 ? lists + (size_t)(q - 1) * 4 * p->list_words : P > 0 ? p->block(pk, pset) + p->o_list + (size_t)(Q - 1) * 4 * p->list_words : p->d_trk;
+      const uint8_t* prev_pyr = q > 0 ? pyr + (size_t)(q - 1) * 4 * p->pyr_total : p->carry_pyr();
+      const size_t r = (size_t)q * 4;
+      if (p->trk_split) {        // development library only (tools/bench_quad_pipe_sp_lk.py): the chain composed from four single-camera launches, the same bits
+        for (int c = 0; c < 4 && !rc; ++c)
+          rc = d2fe_lk_carry_step_device(L.ctx, prev_pyr + c * p->pyr_total, pyr + (r + c) * p->pyr_total, W, H, prev_lists + c * p->list_words,
+                                         lists + (r + c) * p->list_words, p->D, B + p->o_kps + (r + c) * p->cap * 2, B + p->o_scores + (r + c) * p->cap,
+                                         B + p->o_desc + (r + c) * p->cap * p->D, cnt + r + c, p->cap, &p->tp, p->next_id(), s);
+        if (rc) return rc;
+        continue;
+      }
+      rc = d2fe_lk_carry_quad_step_device(L.ctx, prev_pyr, pyr + r * p->pyr_total, p->pyr_total, W, H, prev_lists, lists + r * p->list_words, p->list_words, p->D,
+                                          B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap, B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp,
+                                          p->next_id(), s);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(p->carry_pyr(), pyr + (size_t)(Q - 1) * 4 * p->pyr_total, 4 * p->pyr_total, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipEventRecord(L.ev_chain, s));
+    rc = d2fe_lk_carry_neighbour_device(L.ctx, pyr, p->pyr_total, Q, W, H, p->cfg.undistort_fov, lists, p->list_words, p->D, &p->tp, B + p->o_nbxy,
+                                        reinterpret_cast<uint8_t*>(B + p->o_nbst), s);
+    if (rc) return rc;
+    // matchLocalFeatures on the lists: the compaction reads the list blocks in place (descriptors, points and count of list r are r * list_words further on), the
+    // same jobs and shifts as the keypoints'; ONE matcher launch over the 4 Q pairs, then the remap
+    float* T = p->tscratch(k);
+    int32_t* tmap = reinterpret_cast<int32_t*>(T + p->t_jmap);
+    HIP_TRY(launch_half_compact_strided(lists + d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_DESC), lists + d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_PTS),
+                                        reinterpret_cast<const int32_t*>(lists), p->list_words, p->list_words, p->list_words, job_row, job_left, job_shift, 8 * Q, p->capT,
+                                        p->D, (float)W, p->move_cols, T + p->t_jdesc, T + p->t_jpts, tmap, reinterpret_cast<int32_t*>(T + p->t_jn), s));
+    MatchArgs m{};
+    m.pairs = p->d_lpairs + (size_t)k * 4 * Q;
+    m.npairs = 4 * Q; m.dim = p->D; m.max_n = p->capT; m.mode = 0; m.ratio = p->cfg.ratio; m.radius = -1.0;
+    m.q_idx = reinterpret_cast<int32_t*>(B + p->o_lmq); m.t_idx = reinterpret_cast<int32_t*>(B + p->o_lmt); m.dist = B + p->o_lmd;
+    m.n_out = reinterpret_cast<int32_t*>(B + p->o_lmn);
+    match_scratch_carve(reinterpret_cast<char*>(p->d_lmatch_scratch) + p->lmatch_scratch_lane * k, 4 * Q, &m);
+    m.stats = p->parent->match_stats; m.ncu = L.ctx->ncu;
+    HIP_TRY(launch_match(m, s));
+    HIP_TRY(launch_remap_matches(m.q_idx, m.t_idx, m.n_out, map_a, map_b, tmap, 4 * Q, p->capT, p->capT, s));
+  }
+  // 5. getFeatureHalfImg of both views of every neighbour pair + the a-side shift
   if (p->n_nb)
     HIP_TRY(launch_half_compact(B + p->o_desc, B + p->o_kps, cnt, job_row, job_left, job_shift, 8 * Q, p->cap, p->D, (float)W, p->move_cols, X + p->x_jdesc,
                                 X + p->x_jpts, jmap, reinterpret_cast<int32_t*>(X + p->x_jn), s));
@@ -387,34 +500,8 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
       for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
     }
     if (p->NP) {
-      // pair tables [lane][set][NP]: the 4 Q neighbour pairs on the lane's compacted pools, then the 4 Q temporal pairs (view c of quad frame q against view c
-      // of quad frame q - 1; q = 0: the last quad frame of the previous pass P - 1 = lane k - 1 of the same set, or lane K - 1 of the other set when k = 0)
-      std::vector<MatchPairDesc> tab((size_t)p->K * 2 * NP);
-      for (int k = 0; k < p->K; ++k)
-        for (int set = 0; set < 2; ++set) {
-          float* B = p->block(k, set);
-          float* PB = p->block(k > 0 ? k - 1 : p->K - 1, k > 0 ? set : set ^ 1);
-          float* X = p->scratch(k);
-          MatchPairDesc* row = tab.data() + ((size_t)k * 2 + set) * NP;
-          int pi = 0;
-          for (int j = 0; p->n_nb && j < 4 * Q; ++j) {
-            MatchPairDesc& d = row[pi++];
-            const size_t ja = 2 * (size_t)j, jb = ja + 1;
-            d.a = X + p->x_jdesc + ja * cap * D; d.b = X + p->x_jdesc + jb * cap * D;
-            d.pts_a = X + p->x_jpts + ja * cap * 2; d.pts_b = X + p->x_jpts + jb * cap * 2;
-            d.na = reinterpret_cast<int32_t*>(X + p->x_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + p->x_jn) + jb;
-            d.radius = cfg->radius_neighbour;
-          }
-          for (int v = 0; p->n_pr && v < 4 * Q; ++v) {
-            MatchPairDesc& d = row[pi++];
-            float* BB = v >= 4 ? B : PB;
-            const size_t ra = v, rb = v >= 4 ? v - 4 : (size_t)(4 * (Q - 1) + v);
-            d.a = B + p->o_desc + ra * cap * D; d.b = BB + p->o_desc + rb * cap * D;
-            d.pts_a = B + p->o_kps + ra * cap * 2; d.pts_b = BB + p->o_kps + rb * cap * 2;
-            d.na = reinterpret_cast<int32_t*>(B + p->o_cnt) + ra; d.nb = reinterpret_cast<int32_t*>(BB + p->o_cnt) + rb;
-            d.radius = cfg->radius_prev;
-          }
-        }
+      std::vector<MatchPairDesc> tab;
+      quad_fill_pairs(p, tab);
       HIP_TRY(hipMalloc(&p->d_pairs, sizeof(MatchPairDesc) * tab.size()));
       HIP_TRY(hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice));
       p->match_scratch_lane = match_scratch_bytes((int)NP, p->cap);
@@ -436,12 +523,13 @@ void d2fe_quad_pipe_destroy(d2fe_quad_pipe p) {
   for (auto& L : p->lanes) {
     if (L.s) (void)hipStreamSynchronize(L.s);
     if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
-    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1], L.ev_chain}) if (e) (void)hipEventDestroy(e);
     if (L.pin_in) (void)hipHostFree(L.pin_in);
     for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
     if (L.ctx) d2fe_destroy(L.ctx);
   }
-  for (void* q : {(void*)p->d_all, (void*)p->d_scr, (void*)p->d_raw_all, (void*)p->d_maps, (void*)p->d_jobs, (void*)p->d_pairs, (void*)p->d_match_scratch})
+  for (void* q : {(void*)p->d_all, (void*)p->d_scr, (void*)p->d_raw_all, (void*)p->d_maps, (void*)p->d_jobs, (void*)p->d_pairs, (void*)p->d_match_scratch,
+                  (void*)p->d_trk, (void*)p->d_trk_pyr, (void*)p->d_lpairs, (void*)p->d_lmatch_scratch})
     if (q) (void)hipFree(q);
   d2fe_context* parent = p->parent;
   delete p;
@@ -502,6 +590,135 @@ int d2fe_quad_pipe_wait(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_pipe_result*
     const size_t pi = p->n_nb;
     out->prev_q = mq + pi * cap; out->prev_t = mt + pi * cap; out->prev_dist = md + pi * cap; out->prev_n = mn + pi;
   }
+  return D2FE_OK;
+}
+
+int d2fe_quad_track_enable(d2fe_quad_pipe p, const d2fe_track_params* tp_in) {
+  if (!p) return ctx_fail(D2FE_ERR_INVALID, "null pipe");
+  d2fe_track_params tp;
+  if (tp_in) tp = *tp_in; else d2fe_track_default_params(&tp);
+  tp.reserved = 0;
+  if (const char* why = lk_carry_check_params(&tp)) return ctx_fail(D2FE_ERR_INVALID, why);
+  if (tp.levels != 2) return ctx_fail(D2FE_ERR_INVALID, "levels must be 2 (PYR_LEVEL): the lanes' pyramids are that deep");
+  if (!(p->cfg.undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "undistort_fov must be > 0 (move_cols of the neighbour tracks)");
+  if (p->W < 16 || p->H < 16) return ctx_fail(D2FE_ERR_INVALID, "views smaller than 16 x 16 have no pyramid");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->trk) return ctx_fail(D2FE_ERR_INVALID, "the mode is already on");
+  if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_track_enable comes before the first submit");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  const int Q = p->Q, K = p->K, capT = tp.total_feature_num + 1;
+  const size_t T = (size_t)capT, D = (size_t)p->D, NI = (size_t)p->NI, NJ = 8 * (size_t)Q;
+  const size_t lw = d2fe_lk_carry_list_bytes(capT, p->D) / sizeof(float);
+  const size_t pyr_total = d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, tp.levels) / 2;
+  if (!lw || !pyr_total) return ctx_fail(D2FE_ERR_INVALID, "bad list or pyramid geometry");
+  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
+  size_t o = p->d2h_words;
+  const size_t o_list = o; o += NI * lw;
+  const size_t o_nbxy = o; o += up64(NI * T * 2);
+  const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
+  const size_t o_lmn = o; o += up64(NI);
+  const size_t o_lmq = o; o += up64(NI * T);
+  const size_t o_lmt = o; o += up64(NI * T);
+  const size_t o_lmd = o; o += up64(NI * T);
+  const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap);
+  size_t t = 0;
+  const size_t t_jdesc = t; t += up64(NJ * T * D);
+  const size_t t_jpts = t; t += up64(NJ * T * 2);
+  const size_t t_jmap = t; t += up64(NJ * T);
+  const size_t t_jn = t; t += up64(NJ);
+  const size_t tscr_words = t;
+  // everything new first; the pipe changes only when all of it is there
+  struct Fresh {
+    float* d_all = nullptr; float* d_trk = nullptr; uint8_t* d_pyr = nullptr; MatchPairDesc* d_lpairs = nullptr; int32_t* d_lms = nullptr;
+    std::vector<float*> pin; std::vector<hipEvent_t> ev; bool keep = false;
+    ~Fresh() {
+      if (keep) return;
+      for (void* q : {(void*)d_all, (void*)d_trk, (void*)d_pyr, (void*)d_lpairs, (void*)d_lms}) if (q) (void)hipFree(q);
+      for (float* q : pin) if (q) (void)hipHostFree(q);
+      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+  } f;
+  const size_t all_words = 64 + (size_t)K * 2 * blk_words, trk_words = 4 * lw + 64 + (size_t)K * tscr_words;
+  const size_t pyr_bytes = (4 + (size_t)K * NI) * pyr_total, lms_lane = match_scratch_bytes(4 * Q, capT);
+  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
+  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // no keypoints, empty lists, every arrival counter zero
+  HIP_TRY(hipMalloc(&f.d_trk, sizeof(float) * trk_words));
+  HIP_TRY(hipMemset(f.d_trk, 0, sizeof(float) * trk_words));        // the four empty lists in front of the first quad frame, next_id = 0
+  HIP_TRY(hipMalloc(&f.d_pyr, pyr_bytes));
+  HIP_TRY(hipMemset(f.d_pyr, 0, pyr_bytes));
+  HIP_TRY(hipMalloc(&f.d_lpairs, sizeof(MatchPairDesc) * (size_t)K * 4 * Q));
+  HIP_TRY(hipMalloc(&f.d_lms, lms_lane * K));
+  HIP_TRY(hipMemset(f.d_lms, 0, lms_lane * K));
+  f.pin.assign((size_t)2 * K, nullptr); f.ev.assign((size_t)K, nullptr);
+  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
+  for (int k = 0; k < K; ++k) HIP_TRY(hipEventCreateWithFlags(&f.ev[k], hipEventDisableTiming));
+  {
+    std::vector<MatchPairDesc> lt((size_t)K * 4 * Q);
+    for (int k = 0; k < K; ++k) {
+      float* X = f.d_trk + 4 * lw + 64 + (size_t)k * tscr_words;
+      for (int j = 0; j < 4 * Q; ++j) {
+        MatchPairDesc& d = lt[(size_t)k * 4 * Q + j];
+        const size_t ja = 2 * (size_t)j, jb = ja + 1;
+        d.a = X + t_jdesc + ja * T * D; d.b = X + t_jdesc + jb * T * D;
+        d.pts_a = X + t_jpts + ja * T * 2; d.pts_b = X + t_jpts + jb * T * 2;
+        d.na = reinterpret_cast<int32_t*>(X + t_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + t_jn) + jb;
+        d.radius = p->cfg.radius_neighbour;
+      }
+    }
+    HIP_TRY(hipMemcpy(f.d_lpairs, lt.data(), sizeof(MatchPairDesc) * lt.size(), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipDeviceSynchronize());        // the memsets ran on the null stream, which the lanes' streams do not wait for
+  // ---- commit: nothing has been submitted, so no stream holds an address of the old blocks
+  f.keep = true;
+  (void)hipFree(p->d_all);
+  p->d_all = f.d_all; p->d_trk = f.d_trk; p->d_trk_pyr = f.d_pyr; p->d_lpairs = f.d_lpairs; p->d_lmatch_scratch = f.d_lms; p->lmatch_scratch_lane = lms_lane;
+  for (int k = 0; k < K; ++k) {
+    auto& L = p->lanes[k];
+    for (int set = 0; set < 2; ++set) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = f.pin[(size_t)2 * k + set]; }
+    L.ev_chain = f.ev[k];
+  }
+  p->tp = tp; p->capT = capT; p->list_words = lw; p->pyr_total = pyr_total;
+  p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst; p->o_lmn = o_lmn; p->o_lmq = o_lmq; p->o_lmt = o_lmt; p->o_lmd = o_lmd;
+  p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
+  p->t_jdesc = t_jdesc; p->t_jpts = t_jpts; p->t_jmap = t_jmap; p->t_jn = t_jn; p->tscr_words = tscr_words;
+  p->trk = true;
+  p->trk_split = d2fe_dev_env("D2FE_QUAD_TRACK_SPLIT", 0) != 0;
+  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
+    std::vector<MatchPairDesc> tab;
+    quad_fill_pairs(p, tab);
+    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
+      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+    }
+  }
+  return D2FE_OK;
+}
+
+int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track_result* out) {
+  if (!p || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->trk) return ctx_fail(D2FE_ERR_UNSUPPORTED, "d2fe_quad_track_enable was not called on this pipe: it carries no landmark lists");
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "unknown ticket");
+  if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the lists within 2 * lanes submits");
+  const int k = (int)(ticket % p->K), set = (int)((ticket / p->K) & 1);
+  const auto& L = p->lanes[k];
+  if (L.synced < ticket) return ctx_fail(D2FE_ERR_NOT_READY, "d2fe_quad_pipe_wait has not returned this ticket yet");
+  const float* B = L.pin_out[set];
+  const float* list = B + p->o_list;
+  auto at = [&](int field) { return list + d2fe_lk_carry_list_offset(p->capT, p->D, field); };
+  const int32_t* hdr = reinterpret_cast<const int32_t*>(at(D2FE_LKC_HDR));
+  out->quads = p->Q; out->cap_tracks = p->capT; out->desc_dim = p->D; out->list_words = (int32_t)p->list_words;
+  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
+  out->pts_xy = at(D2FE_LKC_PTS);
+  out->id = reinterpret_cast<const int32_t*>(at(D2FE_LKC_ID)); out->src = reinterpret_cast<const int32_t*>(at(D2FE_LKC_SRC));
+  out->kp = reinterpret_cast<const int32_t*>(at(D2FE_LKC_KP));
+  out->desc = at(D2FE_LKC_DESC); out->scores = at(D2FE_LKC_SCORES);
+  out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
+  out->lnb_q = reinterpret_cast<const int32_t*>(B + p->o_lmq); out->lnb_t = reinterpret_cast<const int32_t*>(B + p->o_lmt);
+  out->lnb_dist = B + p->o_lmd; out->lnb_n = reinterpret_cast<const int32_t*>(B + p->o_lmn);
   return D2FE_OK;
 }
 

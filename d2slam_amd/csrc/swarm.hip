@@ -270,15 +270,16 @@ __global__ __launch_bounds__(256) void half_compact_kernel(const float* __restri
                                                            const int32_t* __restrict__ job_left, const float* __restrict__ job_shift,
                                                            int cap, int dim, float width_undistort, float move_cols,
                                                            float* __restrict__ out_desc, float* __restrict__ out_pts,
-                                                           int32_t* __restrict__ out_map, int32_t* __restrict__ out_n) {
+                                                           int32_t* __restrict__ out_map, int32_t* __restrict__ out_n,
+                                                           size_t desc_stride, size_t pts_stride, size_t n_stride) {
   __shared__ int s_wcnt[4], s_base;
   __shared__ int s_src[1024];
   const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int row = job_row[j];
   const bool left = job_left[j] != 0;
   const float shift = job_shift[j];
-  const int n = max(0, min(n_kp[row], cap));
-  const float* p = pts + (size_t)row * cap * 2;
+  const int n = max(0, min(n_kp[row * n_stride], cap));
+  const float* p = pts + row * pts_stride;
   if (tid == 0) s_base = 0;
   __syncthreads();
   for (int i0 = 0; i0 < n; i0 += 256) {
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(256) void half_compact_kernel(const float* __restri
   const int c_n = s_base;
   if (tid == 0) out_n[j] = c_n;
   const int d4 = dim >> 2;
-  const f32x4* src = reinterpret_cast<const f32x4*>(desc + (size_t)row * cap * dim);
+  const f32x4* src = reinterpret_cast<const f32x4*>(desc + row * desc_stride);
   f32x4* dst = reinterpret_cast<f32x4*>(out_desc + (size_t)j * cap * dim);
   for (int i = tid; i < c_n * d4; i += 256) { const int c = i / d4, q = i - c * d4; dst[i] = src[(size_t)s_src[c] * d4 + q]; }
 }
@@ -327,7 +328,16 @@ hipError_t launch_half_compact(const float* desc, const float* pts, const int32_
                                const float* job_shift, int njobs, int cap, int dim, float width_undistort, float move_cols,
                                float* out_desc, float* out_pts, int32_t* out_map, int32_t* out_n, hipStream_t s) {
   hipLaunchKernelGGL(half_compact_kernel, dim3(njobs), dim3(256), 0, s, desc, pts, n_kp, job_row, job_left, job_shift, cap, dim, width_undistort,
-                     move_cols, out_desc, out_pts, out_map, out_n);
+                     move_cols, out_desc, out_pts, out_map, out_n, (size_t)cap * dim, (size_t)cap * 2, (size_t)1);
+  return hipGetLastError();
+}
+// the same compaction over rows that are not dense: row r's descriptors, points and count are r * desc_stride / pts_stride / n_stride words behind the bases (the
+// landmark-list blocks of lk_carry.hip: all three strides are the block size)
+hipError_t launch_half_compact_strided(const float* desc, const float* pts, const int32_t* n_kp, size_t desc_stride, size_t pts_stride, size_t n_stride,
+                                       const int32_t* job_row, const int32_t* job_left, const float* job_shift, int njobs, int cap, int dim, float width_undistort,
+                                       float move_cols, float* out_desc, float* out_pts, int32_t* out_map, int32_t* out_n, hipStream_t s) {
+  hipLaunchKernelGGL(half_compact_kernel, dim3(njobs), dim3(256), 0, s, desc, pts, n_kp, job_row, job_left, job_shift, cap, dim, width_undistort,
+                     move_cols, out_desc, out_pts, out_map, out_n, desc_stride, pts_stride, n_stride);
   return hipGetLastError();
 }
 hipError_t launch_remap_matches(int32_t* q_idx, int32_t* t_idx, const int32_t* n_match, const int32_t* map_a_job, const int32_t* map_b_job,

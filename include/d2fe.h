@@ -611,6 +611,27 @@ D2FE_API long d2fe_lk_carry_list_offset(int cap_tracks, int desc_dim, int field)
 D2FE_API int d2fe_lk_carry_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list,
                                        void* d_cur_list, int desc_dim, const float* d_kps_xy, const float* d_kp_scores, const float* d_kp_desc,
                                        const int32_t* d_n_kp, int kp_cap, const d2fe_track_params* tp, int32_t* d_next_id, void* stream);
+/* The quadcam forms (trackLocalFrames with sp_track_use_lk, d2featuretracker.cpp:121-133).
+ * d2fe_lk_carry_quad_step_device: the lists of the FOUR cameras of one quad frame in ONE launch of (cap_tracks / 4, 4) workgroups.  Camera c's previous / current list
+ * is c * list_stride 32-bit words behind d_prev_lists / d_cur_lists (list_stride >= one list block), its previous / current pyramid c * pyr_stride bytes behind
+ * d_prev_pyr / d_cur_pyr, its keypoints row c of the dense d_kps_xy [4][kp_cap][2], d_kp_scores [4][kp_cap], d_kp_desc [4][kp_cap][desc_dim], d_n_kp [4] (the rows of
+ * one quad frame of d2fe_quad_device_result).  Every bit of the four lists and of *d_next_id equals four d2fe_lk_carry_step_device calls for cameras 0, 1, 2, 3 in
+ * that order with the same d_next_id: a new entry's id is next_id + the new entries of the lower cameras + its rank among its own camera's new entries, whichever
+ * camera's workgroups finish last.  The block-zero rule holds per list: besides word 5 of every header the launch uses header word 7 of CAMERA 0's current list
+ * as its quad-level arrival counter, and leaves it zero.  No current list may overlap a previous one.  Only enqueues.
+ * d2fe_lk_carry_neighbour_device: trackLK(left, right, type) (:697-752) of the four neighbour pairs (0,1) (1,2) (2,3) LEFT_RIGHT_IMG_MATCH, (0,3) RIGHT_LEFT_IMG_MATCH
+ * of `quads` quad frames in ONE launch, over lists that are on the device: list and pyramid of view (q, v) are (q * 4 + v) * list_stride words / pyr_stride bytes
+ * behind d_lists / d_pyr.  One wave per (q, pair, slot i of list a): the gate and shift of opticaltrack_utils.cpp:195-223 with move_cols =
+ * d2fe_half_move_cols(width, undistort_fov), then forward a -> b, reverse from the result shifted back, the 0.5 px test and inBorder.  d_nb_xy [quads][4][cap_tracks][2]
+ * and d_nb_status [quads][4][cap_tracks] are written for EVERY slot: i >= n or an entry the gate rejects -> (0, 0), status 0; an eligible entry -> exactly what
+ * d2fe_lk_track(a, b, pt, pt +- move_cols, 1, type, move_cols, win, iters) returns for it.  Only enqueues. */
+D2FE_API int d2fe_lk_carry_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, size_t pyr_stride, int width, int height,
+                                            const void* d_prev_lists, void* d_cur_lists, size_t list_stride, int desc_dim, const float* d_kps_xy,
+                                            const float* d_kp_scores, const float* d_kp_desc, const int32_t* d_n_kp, int kp_cap, const d2fe_track_params* tp,
+                                            int32_t* d_next_id, void* stream);
+D2FE_API int d2fe_lk_carry_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov,
+                                            const void* d_lists, size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy,
+                                            uint8_t* d_nb_status, void* stream);
 /* detectFastByRegion (opticaltrack_utils.cpp:444-493): cv::cuda::FastFeatureDetector(threshold, nonmax, TYPE_9_16,
  * max_npoints = features) on each of the cols x rows regions of level 0, sorted by response, top `features`.
  * response (optional) receives the FAST scores. */
@@ -758,6 +779,37 @@ D2FE_API int d2fe_quad_pipe_submit(d2fe_quad_pipe p, const uint8_t* raw, int str
 D2FE_API int d2fe_quad_pipe_wait(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_pipe_result* out);
 D2FE_API int d2fe_quad_pipe_lanes(d2fe_quad_pipe p);
 D2FE_API int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* cap, int32_t* desc_dim, int32_t* netvlad_dim);
+/* sp_lk for the quad pipe: the reference's quadcam tracker with enable_lk_optical_flow = 1 and sp_track_use_lk = 1 (config/quadcam_drone_nxt_tmp/quadcam_single.yaml).
+ * d2fe_quad_track_enable(p, tp) (tp = NULL: d2fe_track_default_params) switches the mode on and allocates what it needs.  It is accepted once, before the first
+ * submit; D2FE_ERR_INVALID after the first submit, a second time, for tp->levels != 2 (the lane's pyramids are PYR_LEVEL deep) and for parameters
+ * d2fe_lk_carry_step_device refuses (total_feature_num + 1 > 1024, ...); a refusal leaves the pipe as it was, and a pipe it was never called on behaves, allocates
+ * and measures as before.  Per submit, behind the SuperPoint results of the pass and on the lane's own streams, with no host synchronisation:
+ *   the pyramids of the 4 * quads undistorted views -> for q = 0 .. quads - 1 ONE d2fe_lk_carry_quad_step_device (track(images[c]), c = 0..3: four lists, ONE id
+ *   counter in camera order; the predecessor of q = 0 is the last quad frame of the previous SUBMIT, whichever lane ran it: its lists are read in place, its four
+ *   pyramids from a pipe-owned copy, behind an event the previous pass recorded) -> ONE d2fe_lk_carry_neighbour_device over the pass's lists -> the neighbour
+ *   matchKNN of the LISTS (matchLocalFeatures :1144-1182 on the frames' landmarks, which in this mode are the list entries with their carried descriptors): exactly
+ *   d2fe_half_image_compact_device + d2fe_match_batch_device + d2fe_remap_matches_device over dense copies of the lists' points, descriptors and counts, with the
+ *   pipe's ratio, radius_neighbour, undistort_fov and a-side shift, cap = cap_tracks -> everything in the pass's ONE D2H.
+ * d2fe_quad_track_result_get after d2fe_quad_pipe_wait (D2FE_ERR_NOT_READY before it, D2FE_ERR_UNSUPPORTED on a pipe without the mode): list (q, c) is the list
+ * block (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the conventions of d2fe_pipe_track_result: n[(q * 4 + c) * list_words], ...); the list
+ * of camera a that a neighbour pair tracks and matches is the list AFTER this frame's step.  d2fe_quad_pipe_result and its nb_* / prev_* stay keypoint-based,
+ * governed by match_neighbour / match_prev (the reference's configuration of this mode has both off).  Results are bit-identical for every (lanes, quads).
+ * With the caller, as for the stereo mode: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
+  int32_t quads, cap_tracks, desc_dim, list_words;
+  const int32_t* n;                  /* per list: list (q, c)'s count is n[(q * 4 + c) * list_words]; the same stride for every "per list" pointer below */
+  const int32_t* n_tracked_in; const int32_t* n_lost; const int32_t* n_removed_near; const int32_t* n_new;      /* per list */
+  const float* pts_xy;               /* per list: [cap_tracks][2] */
+  const int32_t* id; const int32_t* src; const int32_t* kp;      /* per list: [cap_tracks] */
+  const float* desc;                 /* per list: [cap_tracks][desc_dim] */
+  const float* scores;               /* per list: [cap_tracks] */
+  const float* nb_lk_xy;             /* [quads][4][cap_tracks][2], contiguous: neighbour pair n, slot i of list a */
+  const uint8_t* nb_lk_status;       /* [quads][4][cap_tracks] */
+  /* the neighbour matchKNN of the lists: [quads][4][cap_tracks] x3, [quads][4]; lnb_q / lnb_t index the entries of the lists of views a / b */
+  const int32_t* lnb_q; const int32_t* lnb_t; const float* lnb_dist; const int32_t* lnb_n;
+} d2fe_quad_track_result;
+D2FE_API int d2fe_quad_track_enable(d2fe_quad_pipe p, const d2fe_track_params* tp);
+D2FE_API int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track_result* out);
 /* The pipe's undistort step on its own: ONE launch for 4 cameras x quads raw frames (image (q, c) at d_raw + q * quad_stride + c * camera_stride), maps
  * as above with device = 1 and every map pointer 16-byte aligned; view (q, c) is written to d_dst + (q * 4 + c) * dw * dh.  Same bytes as
  * d2fe_undistort_device camera by camera. */

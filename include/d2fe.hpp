@@ -289,6 +289,22 @@ class StereoPipe {
   bool lr_lk_ = false, sp_lk_ = false;
 };
 
+// trackEnable(): the LK-carried landmark list of one view of a quad frame (what D2FeatureTracker::trackLK(frame) leaves in keyframe_lk_infos[frame_id][c] with
+// sp_track_use_lk; the fields of StereoTrackList without the right track), and one neighbour pair (a, b) of a quad frame: lk[i] is where entry i of list a sits in
+// view b when lk_status[i] != 0 (trackLK(left, right, type), d2featuretracker.cpp:697-752; entries the half-image gate rejects have status 0), matches are the
+// matchLocalFeatures pairs of the two lists (queryIdx: entry of list a, trainIdx: entry of list b)
+struct QuadTrackList {
+  std::vector<Point2f> pts;
+  std::vector<int32_t> id, src, kp;
+  std::vector<float> scores, desc;                   // desc: [n][desc_dim]
+  int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0;
+};
+struct QuadNeighbourTracks {
+  std::vector<Point2f> lk;
+  std::vector<uint8_t> lk_status;
+  std::vector<DMatch> matches;
+};
+
 // d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
 class QuadPipe {
  public:
@@ -300,6 +316,36 @@ class QuadPipe {
   QuadPipe& operator=(const QuadPipe&) = delete;
   bool ok() const { return p_ != nullptr; }
   d2fe_quad_pipe get() const { return p_; }
+  // d2fe_quad_track_enable (enable_lk_optical_flow + sp_track_use_lk): once, before the first submit; tp = nullptr: the reference's tracker parameters
+  bool trackEnable(const d2fe_track_params* tp = nullptr) {
+    if (!p_ || d2fe_quad_track_enable(p_, tp) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_track_enable: %s\n", d2fe_last_error()); return false; }
+    return true;
+  }
+  // the lists of a ticket that d2fe_quad_pipe_wait has returned: lists[q * 4 + c] = view c of quad frame q, nb[q * 4 + n] = neighbour pair n = (0,1) (1,2) (2,3) (0,3)
+  bool tracks(int64_t ticket, std::vector<QuadTrackList>& lists, std::vector<QuadNeighbourTracks>& nb) const {
+    d2fe_quad_track_result tr;
+    if (!p_ || d2fe_quad_track_result_get(p_, ticket, &tr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_track_result_get: %s\n", d2fe_last_error()); return false; }
+    static const int view_a[4] = {0, 1, 2, 0};
+    const size_t T = (size_t)tr.cap_tracks, lw = (size_t)tr.list_words;
+    lists.assign((size_t)4 * tr.quads, QuadTrackList()); nb.assign((size_t)4 * tr.quads, QuadNeighbourTracks());
+    for (size_t i = 0; i < lists.size(); ++i) {
+      QuadTrackList& t = lists[i];
+      const size_t o = i * lw;
+      const int n = tr.n[o];
+      for (int j = 0; j < n; ++j) t.pts.emplace_back(tr.pts_xy[o + 2 * j], tr.pts_xy[o + 2 * j + 1]);
+      t.id.assign(tr.id + o, tr.id + o + n); t.src.assign(tr.src + o, tr.src + o + n); t.kp.assign(tr.kp + o, tr.kp + o + n);
+      t.scores.assign(tr.scores + o, tr.scores + o + n); t.desc.assign(tr.desc + o, tr.desc + o + (size_t)n * tr.desc_dim);
+      t.n_tracked_in = tr.n_tracked_in[o]; t.n_lost = tr.n_lost[o]; t.n_removed_near = tr.n_removed_near[o]; t.n_new = tr.n_new[o];
+    }
+    for (size_t i = 0; i < nb.size(); ++i) {
+      QuadNeighbourTracks& t = nb[i];
+      const int n = tr.n[(i / 4 * 4 + view_a[i % 4]) * lw];
+      for (int j = 0; j < n; ++j) t.lk.emplace_back(tr.nb_lk_xy[(i * T + j) * 2], tr.nb_lk_xy[(i * T + j) * 2 + 1]);
+      t.lk_status.assign(tr.nb_lk_status + i * T, tr.nb_lk_status + i * T + n);
+      for (int j = 0; j < tr.lnb_n[i]; ++j) t.matches.emplace_back(tr.lnb_q[i * T + j], tr.lnb_t[i * T + j], tr.lnb_dist[i * T + j]);
+    }
+    return true;
+  }
 
  private:
   d2fe_quad_pipe p_ = nullptr;
