@@ -168,6 +168,20 @@ class _QuadExchangeResult(C.Structure):
                 ("phase_ms", C.c_float * 5)]
 
 
+class _LoopConfig(C.Structure):
+    """d2fe_loop_config"""
+    _fields_ = [("struct_size", C.c_int32), ("capacity_keyframes", C.c_int32), ("max_index", C.c_int32), ("mode", C.c_int32), ("slots", C.c_int32),
+                ("timing", C.c_int32), ("max_queries", C.c_int32), ("reserved0", C.c_int32), ("thres", C.c_double), ("ratio", C.c_double), ("reserved", C.c_int32 * 6)]
+
+
+class _LoopResult(C.Structure):
+    """d2fe_loop_result"""
+    _fields_ = [("ticket", C.c_int64), ("frames", C.c_int32), ("views", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32),
+                ("queried", C.c_void_p), ("label", C.c_void_p), ("sim", C.c_void_p), ("keyframe", C.c_void_p), ("dir_old", C.c_void_p), ("ntotal_at_query", C.c_void_p),
+                ("added_label", C.c_void_p), ("dir_a", C.c_void_p), ("dir_b", C.c_void_p), ("n_match", C.c_void_p), ("q_idx", C.c_void_p), ("t_idx", C.c_void_p),
+                ("dist", C.c_void_p), ("phase_ms", C.c_float * 4)]
+
+
 def _quad_maps(maps, device):
     """d2fe_quad_maps from four (mapx, mapy, gain or None) raw addresses"""
     m = _QuadMaps()
@@ -204,7 +218,9 @@ EXPORTS = [
     "d2fe_quad_exchange_default_config", "d2fe_quad_exchange_create", "d2fe_quad_exchange_destroy", "d2fe_quad_exchange_enqueue", "d2fe_quad_exchange_collect",
     "d2fe_quad_exchange_jobs", "d2fe_quad_exchange_pairs", "d2fe_quad_exchange_block_bytes", "d2fe_quad_exchange_stream", "d2fe_quad_exchange_gathered", "d2fe_quad_exchange_job_layout",
     "d2fe_exchange_default_config", "d2fe_exchange_create", "d2fe_exchange_destroy", "d2fe_exchange_enqueue", "d2fe_exchange_collect", "d2fe_exchange_pairs",
-    "d2fe_exchange_block_bytes", "d2fe_exchange_stream", "d2fe_rccl_load", "d2fe_rccl_path", "d2fe_rccl_unique_id", "d2fe_rccl_comm_init_rank", "d2fe_rccl_comm_destroy"]
+    "d2fe_exchange_block_bytes", "d2fe_exchange_stream",
+    "d2fe_loop_default_config", "d2fe_loop_create", "d2fe_loop_create_quad", "d2fe_loop_destroy", "d2fe_loop_enqueue", "d2fe_loop_collect", "d2fe_loop_ntotal",
+    "d2fe_loop_keyframes", "d2fe_loop_stream", "d2fe_loop_query_device", "d2fe_loop_add_host", "d2fe_rccl_load", "d2fe_rccl_path", "d2fe_rccl_unique_id", "d2fe_rccl_comm_init_rank", "d2fe_rccl_comm_destroy"]
 # the development library (lib/libd2fe_hip_dev.so, include/d2fe_debug.h) exports these on top: test hooks and kernel diagnostics
 DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
@@ -411,6 +427,17 @@ def _open_library(path, dev):
         lib.d2fe_exchange_pairs.argtypes = [C.c_void_p]
         lib.d2fe_exchange_block_bytes.argtypes = [C.c_void_p]
         lib.d2fe_exchange_stream.argtypes = [C.c_void_p]; lib.d2fe_exchange_stream.restype = C.c_void_p
+        lib.d2fe_loop_default_config.argtypes = [C.c_void_p]; lib.d2fe_loop_default_config.restype = None
+        lib.d2fe_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_loop_create_quad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_loop_destroy.argtypes = [C.c_void_p]; lib.d2fe_loop_destroy.restype = None
+        lib.d2fe_loop_enqueue.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int]
+        lib.d2fe_loop_collect.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.d2fe_loop_ntotal.argtypes = [C.c_void_p]
+        lib.d2fe_loop_keyframes.argtypes = [C.c_void_p]
+        lib.d2fe_loop_stream.argtypes = [C.c_void_p]; lib.d2fe_loop_stream.restype = C.c_void_p
+        lib.d2fe_loop_add_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        lib.d2fe_loop_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.d2fe_rccl_load.argtypes = [C.c_char_p]
         lib.d2fe_rccl_path.restype = C.c_char_p
         lib.d2fe_rccl_unique_id.argtypes = [C.c_void_p]
@@ -1749,6 +1776,109 @@ class QuadExchange:
     def close(self):
         if getattr(self, "_x", None) and self._x.value:
             self._lib.d2fe_quad_exchange_destroy(self._x)
+            self._x = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- loop query behind a pipe (include/d2fe.h, d2fe_loop_*; csrc/loop.hip) -----------------------------------------------------------------------------------
+LOOP_QUERY, LOOP_ADD = 1, 2      # enum D2FE_LOOP_*
+LOOP_PHASES = ("search_gate_prepare", "match", "append", "release_and_d2h")
+
+
+def loop_select(sims, ntotal, max_index, thres):
+    """The selection of the search kernel in numpy: the best row by (similarity descending, label ascending) among the rows with label <= ntotal - max_index,
+    accepted when its similarity exceeds thres -> (label or -1, similarity).  sims: the similarities of rows 0 .. ntotal - 1."""
+    s = np.asarray(sims, np.float32)[:ntotal]
+    lab = np.arange(len(s))
+    ok = lab <= ntotal - max_index
+    if not ok.any():
+        return -1, 0.0
+    best = int(lab[ok][np.argmax(s[ok])])      # argmax returns the first (lowest label) of equal similarities
+    return (best, float(s[best])) if float(s[best]) > thres else (-1, 0.0)
+
+
+def loop_dirs(views, main_dir, dir_old):
+    """[(dir_a, dir_b)] of the `views` matcher problems of a hit (loop_detector.cpp:461-476 with main_dir_a = main_dir, main_dir_b = dir_old)"""
+    return [((main_dir + i) % views, ((dir_old - main_dir + views) % views + main_dir + i) % views) for i in range(views)]
+
+
+class LoopQuery:
+    """d2fe_loop_*: the device keyframe store behind a StereoPipe or a QuadPipe and, per ticket, search + gate -> matchKNN against the stored keyframe -> add, on
+    one stream of its own (LoopDetector::processImageArray, loop_detector.cpp:23-215).  Destroy it before the pipe."""
+
+    def __init__(self, pipe, capacity_keyframes=4096, max_index=10, thres=0.6, ratio=0.8, mode=0, slots=4, timing=False, max_queries=64):
+        self._lib = pipe._lib
+        self._pipe = pipe
+        c = _LoopConfig()
+        self._lib.d2fe_loop_default_config(C.byref(c))
+        c.capacity_keyframes, c.max_index, c.mode, c.slots, c.timing, c.max_queries = int(capacity_keyframes), int(max_index), int(mode), int(slots), int(bool(timing)), int(max_queries)
+        c.thres, c.ratio = float(thres), float(ratio)
+        self._x = C.c_void_p()
+        quad = isinstance(pipe, QuadPipe)
+        _check((self._lib.d2fe_loop_create_quad if quad else self._lib.d2fe_loop_create)(pipe._p, C.byref(c), C.byref(self._x)))
+        self.views, self.main_dir = (4, 2) if quad else (1, 0)
+        self.slots, self.timing = int(slots), bool(timing)
+        self._res = _LoopResult()
+
+    @property
+    def stream(self):
+        return self._lib.d2fe_loop_stream(self._x)
+
+    @property
+    def ntotal(self):
+        r = int(self._lib.d2fe_loop_ntotal(self._x))
+        if r < 0:
+            _check(r)
+        return r
+
+    @property
+    def keyframes(self):
+        r = int(self._lib.d2fe_loop_keyframes(self._x))
+        if r < 0:
+            _check(r)
+        return r
+
+    def enqueue(self, ticket, slot, is_keyframe=None, flags=LOOP_QUERY | LOOP_ADD):
+        m = None if is_keyframe is None else np.ascontiguousarray(is_keyframe, np.uint8)
+        _check(self._lib.d2fe_loop_enqueue(self._x, int(ticket), int(slot), _ptr(m) if m is not None else None, int(flags)))
+
+    def add_host(self, netvlad, desc, n_kp):
+        """keyframes from host arrays [n][views][netvlad_dim], [n][views][cap][desc_dim] (or None when every count is 0), [n][views] -> ordinal of the first"""
+        n_kp = np.ascontiguousarray(n_kp, np.int32).reshape(-1, self.views)
+        nv = np.ascontiguousarray(netvlad, np.float32); d = None if desc is None else np.ascontiguousarray(desc, np.float32)
+        r = int(self._lib.d2fe_loop_add_host(self._x, _ptr(nv), _ptr(d), _ptr(n_kp), n_kp.shape[0]))
+        if r < 0:
+            _check(r)
+        return r
+
+    def query_device(self, d_netvlad, d_desc, d_n_kp, nq, max_index, slot, stream=None):
+        """query only, raw device addresses (ints) in the pipe's row order: [nq][views][netvlad_dim], [nq][views][cap][desc_dim], [nq][views]"""
+        _check(self._lib.d2fe_loop_query_device(self._x, C.c_void_p(d_netvlad), C.c_void_p(d_desc), C.c_void_p(d_n_kp), int(nq), int(max_index), int(slot),
+                                                C.c_void_p(stream or 0)))
+
+    def collect(self, slot):
+        """blocks until the slot's results are in host memory; numpy VIEWS into the pinned slot (valid until the slot is enqueued again)"""
+        r = self._res
+        _check(self._lib.d2fe_loop_collect(self._x, int(slot), C.byref(r)))
+        F, V, cap = int(r.frames), int(r.views), int(r.cap)
+        f, i = np.float32, np.int32
+        out = {"ticket": int(r.ticket), "frames": F, "views": V, "cap": cap, "sim": _pinned_view(r.sim, (F,), f)}
+        for k in ("queried", "label", "keyframe", "dir_old", "ntotal_at_query"):
+            out[k] = _pinned_view(getattr(r, k), (F,), i)
+        for k in ("added_label", "dir_a", "dir_b", "n_match"):
+            out[k] = _pinned_view(getattr(r, k), (F, V), i)
+        out["q_idx"] = _pinned_view(r.q_idx, (F, V, cap), i); out["t_idx"] = _pinned_view(r.t_idx, (F, V, cap), i); out["dist"] = _pinned_view(r.dist, (F, V, cap), f)
+        out["phase_ms"] = [float(v) for v in r.phase_ms] if self.timing else None
+        return out
+
+    def close(self):
+        if getattr(self, "_x", None) and self._x.value:
+            self._lib.d2fe_loop_destroy(self._x)
             self._x = C.c_void_p()
 
     def __del__(self):

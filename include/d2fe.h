@@ -907,6 +907,86 @@ D2FE_API int d2fe_quad_exchange_gathered(d2fe_quad_exchange x, int slot, const f
  * (world - 1, or world with loopback) * quads, or D2FE_ERR_INVALID.  d2fe_quad_exchange_create builds its table with this function. */
 D2FE_API int d2fe_quad_exchange_job_layout(int world, int rank, int quads, int loopback, int32_t* job_rank, int32_t* job_quad, int cap_jobs);
 
+/* ---- Loop query behind a pipe: device keyframe store, search and match --------------------------------------------------------------------------------
+ * What LoopDetector::processImageArray (d2frontend/src/loop_detector.cpp:23-215) does with a keyframe once the tracker is done with it, per ticket of a stereo
+ * pipe or a quad pipe, asynchronous, on ONE stream of the object's own and without a host synchronisation:
+ *   device view of the ticket -> ONE search-gate-prepare launch (queryImageArrayFromDatabase -> queryIndexFromDatabase, :300-406, for every frame of the ticket)
+ *   -> ONE matcher launch (computeCorrespondFeaturesOnImageArray -> computeCorrespondFeatures -> matchKNN, :443-578: the frame's descriptors read in place in the
+ *   lane's result block, the stored keyframe's in place in the store) -> ONE append launch (addImageArrayToDatabase, :228-263, device to device) -> release of the
+ *   view -> ONE D2H into pinned slot `slot`.
+ * The store is on the device: the index [capacity_keyframes * V][netvlad_dim] with the keyframe ordinal and the view of every row (index_to_frame_id, imgid2dir),
+ * the descriptors [capacity_keyframes][V][cap][desc_dim] with their counts, and ntotal.  V = 1 behind a stereo pipe (only the left image carries an image_desc,
+ * loop_cam.cpp:446-451), V = 4 behind a quad pipe; the queried view is main_dir = 0 / 2 (:358-371).  A view gets an index row when its n_kp > 0 (:233): the DEVICE
+ * decides, the host knows an upper bound.  There is ONE index: the reference's remote_index is never filled (add_to_faiss is false for remote frames, :200-206) and
+ * its merge (:284, :288) returns a similarity as an index.
+ * Order.  Frame f of a ticket sees the index rows [0, ntotal_f): those before the ticket and those the ticket's earlier frames add -- query, then add, frame by frame
+ * (:157-207).  A frame is queried when it is flagged, its main view has keypoints (:378) and ntotal_f > max_index (:157).
+ * Selection.  The best row by (similarity descending, label ascending) among the rows with label <= ntotal_f - max_index, accepted when its similarity > thres: what
+ * the reference's scan of the top min(5 + max_index, ntotal) returns (:314-345), as it excludes at most max_index - 1 labels.  Similarities are bit-equal to
+ * d2fe_db_search's.
+ * Pairs.  A hit on (keyframe k, view dir_old) gives V matcher problems, i = 0 .. V - 1: dir_a = (main_dir + i) % V of the frame against
+ * dir_b = ((dir_old - main_dir + V) % V + main_dir + i) % V of keyframe k (:461-476); an empty side gives 0 matches (:470-471).  Without a hit: n_match = 0,
+ * dir_a = dir_b = -1.  Match lists are bit-equal to d2fe_match_knn (mode 0: ratio, no radius, :572-574) / d2fe_match_crosscheck (mode 1, :576-577).
+ * With the caller: frame_id <-> keyframe ordinal (the k-th frame ever added has ordinal k), the landmark_db flag filter (:582-...), MIN_MATCH_PRE_DIR,
+ * MIN_DIRECTION_LOOP, loop_inlier_feature_num, PnP, lazy and pre-matched frames, SuperGlue.
+ * Errors are the exchanges': a refused d2fe_loop_enqueue (busy slot, ticket not after the last one, full store, a ticket older than 2 * lanes passes) queues nothing
+ * and leaves the store as it was; whatever fails after the view was taken, the view is released. */
+enum { D2FE_LOOP_QUERY = 1, D2FE_LOOP_ADD = 2 };
+typedef struct {
+  int32_t struct_size;          /* sizeof(d2fe_loop_config) */
+  int32_t capacity_keyframes;   /* keyframes the store holds (V index rows each); nothing is evicted or overwritten */
+  int32_t max_index;            /* match_index_dist (loop_detector.cpp:157, :339) */
+  int32_t mode;                 /* 0: matchKNN with `ratio` (enable_knn_match, :572-574); 1: cross-check (:576-577) */
+  int32_t slots;                /* ring of pinned result slots */
+  int32_t timing;               /* 1: HIP events around the phases (d2fe_loop_result.phase_ms) */
+  int32_t max_queries;          /* frames one d2fe_loop_query_device call may carry (1..256) */
+  int32_t reserved0;
+  double thres;                 /* loop_detection_netvlad_thres (:267, :339) */
+  double ratio;                 /* knn_match_ratio */
+  int32_t reserved[6];
+} d2fe_loop_config;
+typedef struct {            /* HOST pointers into the pinned slot, valid until the slot is enqueued again */
+  int64_t ticket;               /* -1: d2fe_loop_query_device */
+  int32_t frames, views, cap, reserved;
+  const int32_t* queried;       /* [frames] 1: the frame was searched */
+  const int32_t* label;         /* [frames] index row, or -1 */
+  const float* sim;             /* [frames] its similarity (0 without a hit) */
+  const int32_t* keyframe;      /* [frames] ordinal of the keyframe the row belongs to, or -1 */
+  const int32_t* dir_old;       /* [frames] the view the row came from (camera_index_old), or -1 */
+  const int32_t* ntotal_at_query;   /* [frames] */
+  const int32_t* added_label;   /* [frames][views] the index row view v of the frame received, or -1 */
+  const int32_t* dir_a;         /* [frames][views] view of the frame, or -1 */
+  const int32_t* dir_b;         /* [frames][views] view of the keyframe, or -1 */
+  const int32_t* n_match;       /* [frames][views] */
+  const int32_t* q_idx;         /* [frames][views][cap] keypoint of the frame's view dir_a */
+  const int32_t* t_idx;         /* [frames][views][cap] keypoint of the keyframe's view dir_b */
+  const float* dist;            /* [frames][views][cap] */
+  float phase_ms[4];            /* timing = 1: search-gate-prepare, match, append, release + D2H */
+} d2fe_loop_result;
+typedef struct d2fe_loop_s* d2fe_loop;
+/* defaults: capacity_keyframes 4096, max_index 10, mode 0, 4 slots, timing 0, max_queries 64, thres 0.6, ratio 0.8 */
+D2FE_API void d2fe_loop_default_config(d2fe_loop_config* c);
+/* the pipe must have NetVLAD on (D2FE_ERR_INVALID otherwise) */
+D2FE_API int d2fe_loop_create(d2fe_pipe p, const d2fe_loop_config* cfg, d2fe_loop* out);
+D2FE_API int d2fe_loop_create_quad(d2fe_quad_pipe p, const d2fe_loop_config* cfg, d2fe_loop* out);
+D2FE_API void d2fe_loop_destroy(d2fe_loop x);      /* before the pipe */
+/* asynchronous.  is_keyframe: [frames] (quad pipe: [quads]) or NULL = every frame; flags: D2FE_LOOP_QUERY | D2FE_LOOP_ADD for the flagged frames.  Tickets in
+ * submit order, each within 2 * lanes passes of its submit. */
+D2FE_API int d2fe_loop_enqueue(d2fe_loop x, int64_t ticket, int slot, const uint8_t* is_keyframe, int flags);
+D2FE_API int d2fe_loop_collect(d2fe_loop x, int slot, d2fe_loop_result* out);      /* blocks until the slot's results are in host memory */
+D2FE_API int d2fe_loop_ntotal(d2fe_loop x);         /* index rows; synchronises the loop's stream */
+D2FE_API int d2fe_loop_keyframes(d2fe_loop x);      /* keyframes in the store; synchronises the loop's stream */
+D2FE_API void* d2fe_loop_stream(d2fe_loop x);       /* the loop's stream (hipStream_t) */
+/* n keyframes from HOST memory in the layout of the device arrays below (netvlad [n][V][netvlad_dim], desc [n][V][cap][desc_dim], n_kp [n][V]): the append step as
+ * blocking copies, for a store that does not start empty (and for tests and benchmarks).  Synchronises the loop's stream.  Returns the ordinal of the first
+ * keyframe added, or D2FE_ERR_TRUNCATED (nothing added) when they do not all fit. */
+D2FE_API int d2fe_loop_add_host(d2fe_loop x, const float* netvlad, const float* desc, const int32_t* n_kp, int n);
+/* Query only, for frames that did not come from this pipe: a remote agent's frames query the local index with match_index_dist_remote and are never added
+ * (:200-206, :294-295).  DEVICE arrays in the pipe's own row order and geometry: d_netvlad [nq][V][netvlad_dim] (16-byte aligned), d_desc [nq][V][cap][desc_dim],
+ * d_n_kp [nq][V]; they are read in place and stay valid until the slot was collected.  stream: the hipStream_t that produced them (the loop's stream waits for what is
+ * queued on it now), or NULL when they are complete.  Same sequence without the append; results with d2fe_loop_collect (ticket = -1). */
+D2FE_API int d2fe_loop_query_device(d2fe_loop x, const float* d_netvlad, const float* d_desc, const int32_t* d_n_kp, int nq, int max_index, int slot, void* stream);
+
 /* Test hooks and kernel diagnostics (d2fe_debug_*) are NOT part of this library: they live in the development library
  * (lib/libd2fe_hip_dev.so, built with -DD2FE_DEVTOOLS) and are declared in include/d2fe_debug.h. */
 

@@ -224,6 +224,7 @@ class StereoPipe {
   StereoPipe(const StereoPipe&) = delete;
   StereoPipe& operator=(const StereoPipe&) = delete;
   bool ok() const { return p_ != nullptr; }
+  d2fe_pipe get() const { return p_; }
   // returns the ticket (>= 0) or -1
   int64_t submit(const ImageView& left, const ImageView& right) {
     int64_t t = -1;
@@ -388,6 +389,64 @@ class QuadExchange {
 
  private:
   d2fe_quad_exchange x_ = nullptr;
+};
+
+// d2fe_loop_* (the loop query behind a pipe: device keyframe store, search, match and add; include/d2fe.h) with the lifetime of a C++ object: what
+// LoopDetector::processImageArray (loop_detector.cpp:23-215) does with a keyframe, per ticket, without a host round trip.  Destroy it BEFORE its pipe (declare it
+// after the pipe).
+struct LoopHit {                       // one frame of a collected result
+  bool queried = false;
+  int label = -1, keyframe = -1, dir_old = -1, ntotal_at_query = 0;      // index row, ordinal of the stored keyframe, camera_index_old
+  float similarity = 0.f;
+  std::vector<int> added_label;                                            // per view: the index row it received, or -1
+  std::vector<int> dir_a, dir_b;                                           // per pair: view of the frame, view of the keyframe (-1 without a hit)
+  std::vector<std::vector<DMatch>> matches;                                // per pair; queryIdx: keypoint of the frame, trainIdx: keypoint of the keyframe
+};
+class LoopQuery {
+ public:
+  LoopQuery(const StereoPipe& pipe, const d2fe_loop_config& cfg) {
+    if (d2fe_loop_create(pipe.get(), &cfg, &x_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_loop_create: %s\n", d2fe_last_error()); x_ = nullptr; }
+  }
+  LoopQuery(const QuadPipe& pipe, const d2fe_loop_config& cfg) {
+    if (d2fe_loop_create_quad(pipe.get(), &cfg, &x_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_loop_create_quad: %s\n", d2fe_last_error()); x_ = nullptr; }
+  }
+  ~LoopQuery() { if (x_) d2fe_loop_destroy(x_); }
+  LoopQuery(const LoopQuery&) = delete;
+  LoopQuery& operator=(const LoopQuery&) = delete;
+  bool ok() const { return x_ != nullptr; }
+  d2fe_loop get() const { return x_; }
+  int ntotal() const { return x_ ? d2fe_loop_ntotal(x_) : 0; }
+  int keyframes() const { return x_ ? d2fe_loop_keyframes(x_) : 0; }
+  // asynchronous: query and / or add the flagged frames of one ticket (is_keyframe = nullptr: all of them); tickets in submit order
+  bool enqueue(int64_t ticket, int slot, const uint8_t* is_keyframe = nullptr, int flags = D2FE_LOOP_QUERY | D2FE_LOOP_ADD) {
+    if (x_ && d2fe_loop_enqueue(x_, ticket, slot, is_keyframe, flags) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_loop_enqueue: %s\n", d2fe_last_error());
+    return false;
+  }
+  // blocks until the slot's results are in host memory; `out` points into the pinned slot (valid until the slot is enqueued again)
+  bool collect(int slot, d2fe_loop_result& out) {
+    if (x_ && d2fe_loop_collect(x_, slot, &out) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_loop_collect: %s\n", d2fe_last_error());
+    return false;
+  }
+  // frame f of a collected result
+  static LoopHit hit(const d2fe_loop_result& r, int f) {
+    LoopHit h;
+    if (f < 0 || f >= r.frames) return h;
+    h.queried = r.queried[f] != 0; h.label = r.label[f]; h.keyframe = r.keyframe[f]; h.dir_old = r.dir_old[f]; h.ntotal_at_query = r.ntotal_at_query[f];
+    h.similarity = r.sim[f];
+    for (int i = 0; i < r.views; ++i) {
+      const size_t p = (size_t)f * r.views + i, o = p * r.cap;
+      h.added_label.push_back(r.added_label[p]); h.dir_a.push_back(r.dir_a[p]); h.dir_b.push_back(r.dir_b[p]);
+      std::vector<DMatch> m;
+      for (int j = 0; j < r.n_match[p]; ++j) m.emplace_back(r.q_idx[o + j], r.t_idx[o + j], r.dist[o + j]);
+      h.matches.push_back(std::move(m));
+    }
+    return h;
+  }
+
+ private:
+  d2fe_loop x_ = nullptr;
 };
 
 // feature_matcher.h:6-11.  `h` replaces the implicit global state of cv::BFMatcher; everything else as in the reference.
