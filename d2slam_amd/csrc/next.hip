@@ -233,6 +233,7 @@ hipError_t launch_db_search(const float* db, int ntotal, int dim, const float* q
 
 // ---- (f)-3: int8 codec ----------------------------------------------------------------------------------------------------------------
 // quantise: q = (int8)(x / max|x| * 127) (C cast = truncation); max over the whole tensor (one block per tensor).
+// max|x| == 0 encodes to zeros (the reference evaluates 0/0 there, d2frontend_types.h:228-237).
 __global__ __launch_bounds__(1024) void quant_int8_kernel(const float* __restrict__ x, int n, int double_max,
                                                           int8_t* __restrict__ out) {
   __shared__ float red[16];
@@ -244,7 +245,9 @@ __global__ __launch_bounds__(1024) void quant_int8_kernel(const float* __restric
   __syncthreads();
   m = 0.f;
   for (int w = 0; w < 16; ++w) m = fmaxf(m, red[w]);
-  if (double_max) {
+  if (!(m > 0.f)) {      // an all-zero tensor: 0/0 in the reference; zeros here, as pack_blocks_int8_kernel defines it
+    for (int i = tid; i < n; i += 1024) out[i] = 0;
+  } else if (double_max) {
     const double md = (double)m;
     for (int i = tid; i < n; i += 1024) out[i] = (int8_t)(int)((double)x[i] / md * 127.0);
   } else {

@@ -525,7 +525,8 @@ D2FE_API int d2fe_db_query_gated(d2fe_db_handle db, const float* q, int max_inde
 /* (f)-3 int8 wire codec.  Replaces the quantisation in VisualImageDesc::toLCM (d2common/include/d2common/d2frontend_types.h:
  * 228-237 landmark descriptors, float max; 260-268 NetVLAD, double max: pass double_max = 1) and the decode of the LCM
  * constructor (:313-351): x = q/127.0; landmark_num >= 0: the first landmark_num 32-float segments are re-normalised
- * (the reference's hard-coded 32); landmark_num < 0: whole-vector L2 (global descriptor). */
+ * (the reference's hard-coded 32); landmark_num < 0: whole-vector L2 (global descriptor).  An all-zero tensor encodes to
+ * zeros (the reference divides 0 by 0 there); an all-zero segment or vector decodes to zeros (Eigen's normalize()). */
 D2FE_API int d2fe_quantize_int8(d2fe_handle h, const float* x, int n, int double_max, int8_t* out);
 D2FE_API int d2fe_dequantize_int8(d2fe_handle h, const int8_t* q, int n, int landmark_num, float* out);
 

@@ -771,7 +771,9 @@ ORC_API int orc_db_query(const float* db, int ntotal, int dim, const float* q, i
 ORC_API void orc_quant_int8(const float* x, int n, int double_max, int8_t* out) {
   float m = 0.f;
   for (int i = 0; i < n; ++i) { const float a = fabsf(x[i]); if (a > m) m = a; }
-  if (double_max) {
+  if (!(m > 0.f)) {                      /* an all-zero tensor: the reference divides 0 by 0 and casts the NaN (undefined); defined as zeros here */
+    for (int i = 0; i < n; ++i) out[i] = 0;
+  } else if (double_max) {
     const double md = (double)m;
     for (int i = 0; i < n; ++i) out[i] = (int8_t)((double)x[i] / md * 127);
   } else {

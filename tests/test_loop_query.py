@@ -249,6 +249,46 @@ def test_stereo_pipe_loop_query_equals_the_host_composition(lanes, F):
     loop.close(); pipe.close(); fe.close()
 
 
+# a stationary camera: the same image array twice inside one ticket and again in later tickets.  Bit-identical NetVLAD rows tie exactly -- stored row against stored
+# row, and stored row against a row the same ticket adds -- and every repeat reports the FIRST occurrence (similarity descending, then label ascending)
+STATIONARY_SCENES = [0, 0, 1, 2, 0, 0, 1, 3]
+
+
+@pytest.mark.gpu
+def test_stereo_pipe_loop_query_stationary_camera_reports_the_first_occurrence():
+    lanes, F, MI, thres = 2, 2, 0, 0.999
+    api, fe = _stereo_fe(2 * F)
+    G = fe.netvlad_dim
+    base = {s: synth_stereo(H, W, seed=900 + s) for s in set(STATIONARY_SCENES)}
+    fr = [base[s] for s in STATIONARY_SCENES]
+    N = len(fr)
+    submits = [(np.stack([fr[i * F + k][0] for k in range(F)]), np.stack([fr[i * F + k][1] for k in range(F)])) for i in range(N // F)]
+    masks = [np.ones(F, np.uint8) for _ in submits]                      # every frame is a keyframe
+    flags = [api.LOOP_QUERY | api.LOOP_ADD] * len(submits)
+    pipe = api.StereoPipe(fe, lanes=lanes, frames=F, width=W, height=H, cap=CAP, netvlad=True)
+    alone, _ = _drive(api, pipe, submits)
+    pipe.close()
+    per_frame = [(o["netvlad"][k][None], o["desc"][k][None], o["n_kp"][k:k + 1]) for o in alone for k in range(F)]
+    first = [STATIONARY_SCENES.index(s) for s in STATIONARY_SCENES]
+    for t in range(N):                                                   # the premise: a repeated frame's row is its first occurrence's, bit for bit
+        assert int(per_frame[t][2][0]) > 10 and np.array_equal(_bits(per_frame[t][0]), _bits(per_frame[first[t]][0])), t
+    comp = _compose(api, fe, per_frame, [flags[0]] * N, 1, 0, MI, 0, G)
+    pipe = api.StereoPipe(fe, lanes=lanes, frames=F, width=W, height=H, cap=CAP, netvlad=True)
+    loop = api.LoopQuery(pipe, capacity_keyframes=N, max_index=MI, thres=thres, ratio=RATIO, mode=0, slots=lanes + 1)
+    _, col = _drive(api, pipe, submits, loop, masks, flags)
+    repeats = 0
+    for i, c in enumerate(col):
+        for k in range(F):
+            t = i * F + k
+            hit = _check_frame(c, k, comp[t], thres, 1)
+            assert int(c["added_label"][k, 0]) == t                      # no black frame: label == frame index
+            if first[t] < t:
+                repeats += 1
+                assert hit and int(c["label"][k]) == int(c["keyframe"][k]) == first[t] == comp[t]["label"], (t, int(c["label"][k]), comp[t]["label"])
+    assert repeats == 4 and loop.ntotal == loop.keyframes == N
+    loop.close(); pipe.close(); fe.close()
+
+
 # ---- (c) behind a quad pipe -------------------------------------------------------------------------------------------------------------------------------------
 # (scene, quarter turns of the rig): a scene seen before comes back turned, so that the view the query sees (main_dir 2) is the stored keyframe's view 2 + turns
 QUAD_SEQ = [(0, 0), (1, 0), (2, 0), (3, 0), (0, 0), (4, 0), (1, 1), (2, 2), (5, 0), (3, 3), (6, 0), (4, 1)]
