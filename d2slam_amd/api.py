@@ -174,6 +174,20 @@ class _LoopConfig(C.Structure):
                 ("timing", C.c_int32), ("max_queries", C.c_int32), ("reserved0", C.c_int32), ("thres", C.c_double), ("ratio", C.c_double), ("reserved", C.c_int32 * 6)]
 
 
+class _WindowConfig(C.Structure):
+    """d2fe_window_config"""
+    _fields_ = [("struct_size", C.c_int32), ("capacity", C.c_int32), ("mode", C.c_int32), ("slots", C.c_int32), ("timing", C.c_int32), ("max_queries", C.c_int32),
+                ("thres", C.c_double), ("ratio", C.c_double), ("reserved", C.c_int32 * 6)]
+
+
+class _WindowResult(C.Structure):
+    """d2fe_window_result"""
+    _fields_ = [("nq", C.c_int32), ("views", C.c_int32), ("cap", C.c_int32), ("capacity", C.c_int32), ("n_window", C.c_int32), ("reserved", C.c_int32),
+                ("keyframe_tag", C.c_void_p), ("keyframe_pos", C.c_void_p), ("dir_a", C.c_void_p), ("dir_b", C.c_void_p), ("sim", C.c_void_p), ("sims", C.c_void_p),
+                ("local_view", C.c_void_p), ("remote_view", C.c_void_p), ("n_match", C.c_void_p), ("q_idx", C.c_void_p), ("t_idx", C.c_void_p), ("dist", C.c_void_p),
+                ("phase_ms", C.c_float * 3), ("reserved1", C.c_int32)]
+
+
 class _LoopResult(C.Structure):
     """d2fe_loop_result"""
     _fields_ = [("ticket", C.c_int64), ("frames", C.c_int32), ("views", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32),
@@ -218,7 +232,9 @@ EXPORTS = [
     "d2fe_quad_exchange_default_config", "d2fe_quad_exchange_create", "d2fe_quad_exchange_destroy", "d2fe_quad_exchange_enqueue", "d2fe_quad_exchange_collect",
     "d2fe_quad_exchange_jobs", "d2fe_quad_exchange_pairs", "d2fe_quad_exchange_block_bytes", "d2fe_quad_exchange_stream", "d2fe_quad_exchange_gathered", "d2fe_quad_exchange_job_layout",
     "d2fe_exchange_default_config", "d2fe_exchange_create", "d2fe_exchange_destroy", "d2fe_exchange_enqueue", "d2fe_exchange_collect", "d2fe_exchange_pairs",
-    "d2fe_exchange_block_bytes", "d2fe_exchange_stream",
+    "d2fe_exchange_block_bytes", "d2fe_exchange_stream", "d2fe_exchange_gathered",
+    "d2fe_window_default_config", "d2fe_window_create", "d2fe_window_create_quad", "d2fe_window_destroy", "d2fe_window_stream", "d2fe_window_push",
+    "d2fe_window_push_host", "d2fe_window_retain", "d2fe_window_retain_plan", "d2fe_window_size", "d2fe_window_tags", "d2fe_window_track_device", "d2fe_window_collect",
     "d2fe_loop_default_config", "d2fe_loop_create", "d2fe_loop_create_quad", "d2fe_loop_destroy", "d2fe_loop_enqueue", "d2fe_loop_collect", "d2fe_loop_ntotal",
     "d2fe_loop_keyframes", "d2fe_loop_stream", "d2fe_loop_query_device", "d2fe_loop_add_host", "d2fe_rccl_load", "d2fe_rccl_path", "d2fe_rccl_unique_id", "d2fe_rccl_comm_init_rank", "d2fe_rccl_comm_destroy"]
 # the development library (lib/libd2fe_hip_dev.so, include/d2fe_debug.h) exports these on top: test hooks and kernel diagnostics
@@ -427,6 +443,20 @@ def _open_library(path, dev):
         lib.d2fe_exchange_pairs.argtypes = [C.c_void_p]
         lib.d2fe_exchange_block_bytes.argtypes = [C.c_void_p]
         lib.d2fe_exchange_stream.argtypes = [C.c_void_p]; lib.d2fe_exchange_stream.restype = C.c_void_p
+        lib.d2fe_exchange_gathered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.d2fe_window_default_config.argtypes = [C.c_void_p]; lib.d2fe_window_default_config.restype = None
+        lib.d2fe_window_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_window_create_quad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_window_destroy.argtypes = [C.c_void_p]; lib.d2fe_window_destroy.restype = None
+        lib.d2fe_window_stream.argtypes = [C.c_void_p]; lib.d2fe_window_stream.restype = C.c_void_p
+        lib.d2fe_window_push.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64]
+        lib.d2fe_window_push_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.d2fe_window_retain.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.d2fe_window_retain_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        lib.d2fe_window_size.argtypes = [C.c_void_p]
+        lib.d2fe_window_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.d2fe_window_track_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        lib.d2fe_window_collect.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.d2fe_loop_default_config.argtypes = [C.c_void_p]; lib.d2fe_loop_default_config.restype = None
         lib.d2fe_loop_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_loop_create_quad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1670,6 +1700,7 @@ class Exchange:
         _check(self._lib.d2fe_exchange_create(pipe._p, C.c_void_p(comm) if comm else None, C.byref(c), C.byref(self._x)))
         self.npairs = int(self._lib.d2fe_exchange_pairs(self._x))
         self.block_bytes = int(self._lib.d2fe_exchange_block_bytes(self._x))
+        self.world, self.rank = int(world), int(rank)
         self.slots, self.timing = int(slots), bool(timing)
         self._res = _ExchangeResult()
 
@@ -1677,6 +1708,12 @@ class Exchange:
     def stream(self):
         """own_stream=True: that hipStream_t (int), else None"""
         return self._lib.d2fe_exchange_stream(self._x)
+
+    def gathered(self, slot):
+        """(fp32 blocks, wire blocks): device addresses of the slot's gathered blocks [world][frames] (d2fe_exchange_gathered)"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self._lib.d2fe_exchange_gathered(self._x, int(slot), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def enqueue(self, ticket, slot):
         _check(self._lib.d2fe_exchange_enqueue(self._x, int(ticket), int(slot)))
@@ -1743,6 +1780,7 @@ class QuadExchange:
         self.njobs = int(self._lib.d2fe_quad_exchange_jobs(self._x))
         self.npairs = int(self._lib.d2fe_quad_exchange_pairs(self._x))
         self.block_bytes = int(self._lib.d2fe_quad_exchange_block_bytes(self._x))
+        self.world, self.rank = int(world), int(rank)
         self.slots, self.timing, self.mode = int(slots), bool(timing), mode
         self._res = _QuadExchangeResult()
 
@@ -1879,6 +1917,154 @@ class LoopQuery:
     def close(self):
         if getattr(self, "_x", None) and self._x.value:
             self._lib.d2fe_loop_destroy(self._x)
+            self._x = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- remote tracking against the keyframe window (include/d2fe.h, d2fe_window_*; csrc/window.hip) ---------------------------------------------------------------
+WINDOW_PHASES = ("gate", "match", "d2h")
+WINDOW_DIRS = (2, 3, 0, 1)       # getMatchedPrevKeyframe's view order of a quadcam keyframe (d2featuretracker.cpp:207)
+
+
+def window_retain_plan(tags, keep):
+    """d2fe_window_retain_plan: [True for every keyframe updatebySldWin's erase loop (:47-57) drops]; tags oldest first.  Needs no device."""
+    t = np.ascontiguousarray(tags, np.int64).reshape(-1); k = np.ascontiguousarray(keep, np.int64).reshape(-1)
+    ev = np.zeros(max(len(t), 1), np.uint8)
+    n = int(load_library().d2fe_window_retain_plan(_ptr(t) if len(t) else None, len(t), _ptr(k) if len(k) else None, len(k), _ptr(ev)))
+    if n < 0:
+        _check(n)
+    assert n == int(ev[:len(t)].sum())
+    return [bool(v) for v in ev[:len(t)]]
+
+
+def window_select(sims, thres):
+    """The gate kernel's selection, restated: sims [n][V] in window order (oldest first) and `dirs` order -> (pos, j) of the smallest (n - 1 - pos) * V + j among the
+    pairs with !(sim < thres), or None"""
+    sims = np.asarray(sims, np.float32)
+    n, V = sims.shape if sims.ndim == 2 else (0, 1)
+    best = None
+    for pos in range(n):
+        for j in range(V):
+            if not (float(sims[pos, j]) < thres):
+                key = (n - 1 - pos) * V + j
+                if best is None or key < best:
+                    best = key
+    return None if best is None else (n - 1 - best // V, best % V)
+
+
+def window_views(views, dir_b):
+    """[(remote view, local view)] of the `views` matcher problems of a hit (trackRemoteFrames :273-284 with dir_cur = 2)"""
+    if views == 1:
+        return [(0, 0)]
+    return [((2 + k) % 4, (dir_b - 2 + (2 + k) % 4) % 4) for k in range(4)]
+
+
+class KeyframeWindow:
+    """d2fe_window_*: the tracker's keyframe window on the device behind a StereoPipe or a QuadPipe, and D2FeatureTracker::trackRemoteFrames for a batch of remote
+    frames -- the NetVLAD walk of getMatchedPrevKeyframe (newest keyframe first, the first pass wins) and matchKNN(keyframe, remote) -- as gate -> match -> D2H on one
+    stream of its own (d2featuretracker.cpp:166-310).  Destroy it before the pipe."""
+
+    def __init__(self, pipe, capacity=12, thres=0.8, ratio=0.8, mode=0, slots=4, timing=False, max_queries=64):
+        self._lib = pipe._lib
+        self._pipe = pipe
+        c = _WindowConfig()
+        self._lib.d2fe_window_default_config(C.byref(c))
+        c.capacity, c.mode, c.slots, c.timing, c.max_queries = int(capacity), int(mode), int(slots), int(bool(timing)), int(max_queries)
+        c.thres, c.ratio = float(thres), float(ratio)
+        self._x = C.c_void_p()
+        quad = isinstance(pipe, QuadPipe)
+        _check((self._lib.d2fe_window_create_quad if quad else self._lib.d2fe_window_create)(pipe._p, C.byref(c), C.byref(self._x)))
+        self.views, self.gate_view = (4, 2) if quad else (1, 0)
+        g = [C.c_int32() for _ in range(4)]
+        _check((self._lib.d2fe_quad_pipe_geometry if quad else self._lib.d2fe_pipe_geometry)(pipe._p, *[C.byref(v) for v in g]))
+        self.frames, self.cap, self.desc_dim, self.netvlad_dim = (int(v.value) for v in g)
+        self.capacity, self.slots, self.timing = int(capacity), int(slots), bool(timing)
+        self._res = _WindowResult()
+
+    @property
+    def stream(self):
+        return self._lib.d2fe_window_stream(self._x)
+
+    def __len__(self):
+        r = int(self._lib.d2fe_window_size(self._x))
+        if r < 0:
+            _check(r)
+        return r
+
+    def tags(self):
+        """the window's tags, oldest first"""
+        t = np.zeros(self.capacity, np.int64)
+        n = int(self._lib.d2fe_window_tags(self._x, _ptr(t), self.capacity))
+        if n < 0:
+            _check(n)
+        return [int(v) for v in t[:n]]
+
+    def push(self, ticket, frame, tag):
+        """frame `frame` of a ticket of the pipe becomes the newest keyframe (asynchronous, device to device); the newest tag again is a no-op"""
+        _check(self._lib.d2fe_window_push(self._x, int(ticket), int(frame), int(tag)))
+
+    def push_host(self, netvlad, desc, n_kp, tag):
+        """the same from host arrays [views][netvlad_dim], [views][cap][desc_dim] (or None when every count is 0), [views]; blocking"""
+        n_kp = np.ascontiguousarray(n_kp, np.int32).reshape(self.views)
+        nv = np.ascontiguousarray(netvlad, np.float32); d = None if desc is None else np.ascontiguousarray(desc, np.float32)
+        _check(self._lib.d2fe_window_push_host(self._x, _ptr(nv), _ptr(d), _ptr(n_kp), int(tag)))
+
+    def retain(self, tags):
+        """updatebySldWin: drops every keyframe whose tag is not listed, except the newest -> how many were dropped (host bookkeeping only)"""
+        t = np.ascontiguousarray(tags, np.int64).reshape(-1)
+        r = int(self._lib.d2fe_window_retain(self._x, _ptr(t) if len(t) else None, len(t)))
+        if r < 0:
+            _check(r)
+        return r
+
+    def track_device(self, d_netvlad, nv_stride, d_desc, desc_stride, d_n_kp, nkp_stride, nq, slot, stream=None):
+        """raw device addresses (ints); row q * views + v of each array is view v of remote frame q, strides in 32-bit words between rows"""
+        _check(self._lib.d2fe_window_track_device(self._x, C.c_void_p(d_netvlad), C.c_size_t(nv_stride), C.c_void_p(d_desc), C.c_size_t(desc_stride), C.c_void_p(d_n_kp),
+                                                  C.c_size_t(nkp_stride), int(nq), int(slot), C.c_void_p(stream or 0)))
+
+    def _track_blocks(self, d_blocks, world, first, nq, slot, stream):
+        cap, G = self.cap, self.netvlad_dim
+        blk = block_words(cap, G)
+        if nq is None:
+            nq = world * self.frames - first
+        base = d_blocks + 4 * blk * first * self.views
+        self.track_device(base + 4 * block_field_offset(cap, G, "netvlad"), blk, base + 4 * block_field_offset(cap, G, "desc"), blk,
+                          base + 4 * block_field_offset(cap, G, "n"), blk, nq, slot, stream)
+        return nq
+
+    def track_exchange(self, exchange, xslot, slot, first=0, nq=None):
+        """the gathered fp32 blocks [world][frames] of slot `xslot` of an Exchange, read in place: frames first .. first + nq of them (default: all of them, this
+        rank's own included), ordered behind what is queued on the exchange's stream (own_stream=False: collect the exchange first).  Returns nq."""
+        return self._track_blocks(exchange.gathered(xslot)[0], exchange.world, first, nq, slot, exchange.stream)
+
+    def track_quad_exchange(self, exchange, xslot, slot, first=0, nq=None):
+        """the same for a QuadExchange: blocks [world][quads][4 views], quad frames first .. first + nq"""
+        return self._track_blocks(exchange.gathered(xslot)[0], exchange.world, first, nq, slot, exchange.stream)
+
+    def collect(self, slot):
+        """blocks until the slot's results are in host memory; numpy VIEWS into the pinned slot (valid until the slot is queued again)"""
+        r = self._res
+        _check(self._lib.d2fe_window_collect(self._x, int(slot), C.byref(r)))
+        nq, V, cap, K = int(r.nq), int(r.views), int(r.cap), int(r.capacity)
+        f, i = np.float32, np.int32
+        out = {"nq": nq, "views": V, "cap": cap, "capacity": K, "n_window": int(r.n_window),
+               "keyframe_tag": _pinned_view(r.keyframe_tag, (2 * nq,), i).view(np.int64), "sim": _pinned_view(r.sim, (nq,), f), "sims": _pinned_view(r.sims, (nq, K, V), f)}
+        for k in ("keyframe_pos", "dir_a", "dir_b"):
+            out[k] = _pinned_view(getattr(r, k), (nq,), i)
+        for k in ("local_view", "remote_view", "n_match"):
+            out[k] = _pinned_view(getattr(r, k), (nq, V), i)
+        out["q_idx"] = _pinned_view(r.q_idx, (nq, V, cap), i); out["t_idx"] = _pinned_view(r.t_idx, (nq, V, cap), i); out["dist"] = _pinned_view(r.dist, (nq, V, cap), f)
+        out["phase_ms"] = [float(v) for v in r.phase_ms] if self.timing else None
+        return out
+
+    def close(self):
+        if getattr(self, "_x", None) and self._x.value:
+            self._lib.d2fe_window_destroy(self._x)
             self._x = C.c_void_p()
 
     def __del__(self):

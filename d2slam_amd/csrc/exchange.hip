@@ -218,6 +218,14 @@ int d2fe_exchange_pairs(d2fe_exchange x) { return x ? x->NR : ctx_fail(D2FE_ERR_
 int d2fe_exchange_block_bytes(d2fe_exchange x) { return x ? (x->int8 ? x->BLKB : 4 * x->BLK) : ctx_fail(D2FE_ERR_INVALID, "null exchange"); }
 void* d2fe_exchange_stream(d2fe_exchange x) { return x ? x->own : nullptr; }
 
+int d2fe_exchange_gathered(d2fe_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks) {
+  if (!x || slot < 0 || slot >= (int)x->slots.size()) return ctx_fail(D2FE_ERR_INVALID, "bad argument");
+  const auto& S = x->slots[slot];
+  if (d_blocks) *d_blocks = S.d_gath;
+  if (d_wire_blocks) *d_wire_blocks = x->int8 ? static_cast<const void*>(S.d_gath_q) : static_cast<const void*>(S.d_gath);
+  return D2FE_OK;
+}
+
 int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
   if (!x || slot < 0 || slot >= (int)x->slots.size()) return ctx_fail(D2FE_ERR_INVALID, "bad argument");
   auto& S = x->slots[slot];

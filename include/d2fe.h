@@ -456,6 +456,9 @@ D2FE_API int d2fe_exchange_collect(d2fe_exchange x, int slot, d2fe_exchange_resu
 D2FE_API int d2fe_exchange_pairs(d2fe_exchange x);
 D2FE_API int d2fe_exchange_block_bytes(d2fe_exchange x);   /* bytes one frame contributes to the all-gather */
 D2FE_API void* d2fe_exchange_stream(d2fe_exchange x);      /* own_stream = 1: that stream (hipStream_t), else NULL */
+/* DEVICE addresses of slot `slot`'s gathered blocks [world][frames]: the fp32 blocks the gate and the matcher read (decoded from the wire form when it is int8) and
+ * the blocks as they crossed the wire (either pointer may be NULL); d2fe_quad_exchange_gathered's contract.  What d2fe_window_track_device reads in place. */
+D2FE_API int d2fe_exchange_gathered(d2fe_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks);
 /* RCCL without any other dependency: rank 0 makes a 128-byte id, every rank gets it by whatever channel D2SLAM has (its LCM bus, a file, MPI), then all ranks call
  * comm_init_rank.  path: a librccl to load (NULL: one the process already holds, else librccl.so.1 / librccl.so on the loader path, else /opt/rocm/lib). */
 D2FE_API int d2fe_rccl_load(const char* path);
@@ -987,6 +990,93 @@ D2FE_API int d2fe_loop_add_host(d2fe_loop x, const float* netvlad, const float* 
  * d_n_kp [nq][V]; they are read in place and stay valid until the slot was collected.  stream: the hipStream_t that produced them (the loop's stream waits for what is
  * queued on it now), or NULL when they are complete.  Same sequence without the append; results with d2fe_loop_collect (ticket = -1). */
 D2FE_API int d2fe_loop_query_device(d2fe_loop x, const float* d_netvlad, const float* d_desc, const int32_t* d_n_kp, int nq, int max_index, int slot, void* stream);
+
+/* ---- Remote tracking against the keyframe window, behind a pipe ------------------------------------------------------------------------------------------
+ * What D2FeatureTracker::trackRemoteFrames (d2frontend/src/d2featuretracker.cpp:237-310) does with a remote frame: it does not match it against the frame of the same
+ * step (the all-to-all mode of d2fe_exchange_* / d2fe_quad_exchange_*) but walks the tracker's keyframe window, current_keyframes, through getMatchedPrevKeyframe
+ * (:166-235) -- newest keyframe first, for a quadcam agent that keyframe's views in the order dirs = {2, 3, 0, 1} -- stops at the FIRST NetVLAD similarity that is not
+ * below track_remote_netvlad_thres, and matches that keyframe against the remote frame (trackRemote -> matchLocalFeatures(prev_frame, frame) -> matchKNN, :312-387).
+ * Here the window lives on the device and a batch of remote frames is tracked by ONE sequence, asynchronous, on ONE stream of the object's own, without a host
+ * synchronisation:
+ *   ONE gate launch (every similarity remote gate view x (keyframe, view), the selection, the per-frame records, the matcher's problem table) -> ONE matcher launch
+ *   (a side: the chosen keyframe's descriptors in place in the store; b side: the remote descriptors in place where the caller left them) -> ONE D2H into pinned
+ *   slot `slot`.
+ * The store: `capacity` slots of NetVLAD [V][netvlad_dim], descriptors [V][cap][desc_dim] (rows >= n_kp zero), n_kp [V] and the caller's 64-bit tag (its frame_id,
+ * >= 0).  V = 1 behind a stereo pipe (view 0, the left image), V = 4 behind a quad pipe.  The window's ORDER (oldest -> newest, as current_keyframes) and the free slots
+ * are host bookkeeping that only the calls below change; the order travels to the gate kernel by value, so a query queued earlier keeps the order it was queued with, and
+ * slot order and window order differ as soon as a freed slot was reused.
+ * Selection.  With pos the position in the window (oldest = 0, n keyframes) and j the place in `dirs` (stereo: j = 0), the chosen pair is the minimum of
+ * (n - 1 - pos) * V + j over the pairs with !(sim < thres) -- the first pass of the reference's walk, NOT the best similarity.  The remote gate view is view 0 (stereo) /
+ * view 2 (quad); the gate looks at NetVLAD vectors only (views without keypoints take part, as in the reference).  Similarities are bit-equal to
+ * d2fe_gate_pairs_device / d2fe_quad_gate_device.
+ * Problems per remote frame, fixed layout: V = 1: (local view 0, remote view 0).  V = 4: k = 0..3 in trackRemoteFrames' order (:273-284): remote view
+ * (2 + k) % 4 against local view (dir_b - 2 + remote view) mod 4 -- the D2FE_QUAD_GATED layout.  A problem with an empty side (:278-279) keeps its place with
+ * n_match = 0; a frame without a hit has n_match = 0 and views -1.  No points and no radius: trackRemote leaves enable_search_in_local false and, without prediction,
+ * passes -1.  Match lists are bit-equal to d2fe_match_knn(keyframe view, remote view) (mode 0) / d2fe_match_crosscheck (mode 1): query = local keyframe, train = remote.
+ * With the caller: tag <-> frame_id, is_lazy_frame / matched_frame (:239), the early return of updatebySldWin for an empty sliding window (:41), the landmark-id and
+ * solver_id bookkeeping (:340-381), remote_min_match_num (:1290), check_essential (a RANSAC), motion prediction (enable_search_local_aera_remote, default false: it
+ * needs the landmark manager), the right-image pair of a stereo agent without lr_lk (:263-268: it depends on the landmark ids of the first pair), SuperGlue.
+ * A refusal queues nothing and leaves the window as it was. */
+typedef struct {
+  int32_t struct_size;          /* sizeof(d2fe_window_config) */
+  int32_t capacity;             /* slots of the window (1..64; max_sld_win_size is 11 in the shipped configs, plus the newest keyframe) */
+  int32_t mode;                 /* 0: matchKNN with `ratio` (enable_knn_match); 1: cross-check (enable_knn_match = 0) */
+  int32_t slots;                /* ring of pinned result slots */
+  int32_t timing;               /* 1: HIP events around the phases (d2fe_window_result.phase_ms) */
+  int32_t max_queries;          /* remote frames one d2fe_window_track_device call may carry (1..256) */
+  double thres;                 /* track_remote_netvlad_thres */
+  double ratio;                 /* knn_match_ratio */
+  int32_t reserved[6];
+} d2fe_window_config;
+typedef struct {            /* HOST pointers into the pinned slot, valid until the slot is queued again */
+  int32_t nq, views, cap, capacity;
+  int32_t n_window, reserved;   /* keyframes in the window as the query was queued */
+  const int64_t* keyframe_tag;  /* [nq] tag of the chosen keyframe, -1 without a hit */
+  const int32_t* keyframe_pos;  /* [nq] its position in the window as queued (oldest = 0), or -1 */
+  const int32_t* dir_a;         /* [nq] the remote gate view (0 / 2), or -1 */
+  const int32_t* dir_b;         /* [nq] the keyframe's view that passed, or -1 */
+  const float* sim;             /* [nq] its similarity (0 without a hit) */
+  const float* sims;            /* [nq][capacity][views] every similarity, window order then `dirs` order; zeros beyond the window */
+  const int32_t* local_view;    /* [nq][views] view of the keyframe, or -1 */
+  const int32_t* remote_view;   /* [nq][views] view of the remote frame, or -1 */
+  const int32_t* n_match;       /* [nq][views] */
+  const int32_t* q_idx;         /* [nq][views][cap] keypoint of the keyframe's view */
+  const int32_t* t_idx;         /* [nq][views][cap] keypoint of the remote view */
+  const float* dist;            /* [nq][views][cap] */
+  float phase_ms[3];            /* timing = 1: gate, match, D2H */
+  int32_t reserved1;
+} d2fe_window_result;
+typedef struct d2fe_window_s* d2fe_window;
+/* defaults: capacity 12, mode 0, 4 slots, timing 0, max_queries 64, thres 0.8, ratio 0.8 */
+D2FE_API void d2fe_window_default_config(d2fe_window_config* c);
+/* the pipe must have NetVLAD on (D2FE_ERR_INVALID otherwise) */
+D2FE_API int d2fe_window_create(d2fe_pipe p, const d2fe_window_config* cfg, d2fe_window* out);
+D2FE_API int d2fe_window_create_quad(d2fe_quad_pipe p, const d2fe_window_config* cfg, d2fe_window* out);
+D2FE_API void d2fe_window_destroy(d2fe_window x);      /* before the pipe */
+D2FE_API void* d2fe_window_stream(d2fe_window x);      /* the window's stream (hipStream_t) */
+/* processFrame's emplace_back (:837), asynchronous: takes the ticket's device view, copies frame `frame` (quad pipe: quad `frame`) of it into a free slot with ONE launch
+ * on the window's stream, releases the view.  A tag equal to the newest keyframe's is a no-op (:806-808, D2FE_OK).  Refused: a full window (D2FE_ERR_TRUNCATED), a tag
+ * that is in the window already, a negative tag, a ticket older than 2 * lanes passes. */
+D2FE_API int d2fe_window_push(d2fe_window x, int64_t ticket, int frame, int64_t tag);
+/* the same from HOST arrays in the layout of the store (netvlad [V][netvlad_dim], desc [V][cap][desc_dim] or NULL when every count is 0, n_kp [V]), as blocking
+ * copies behind the window's stream: for a window that does not start empty, and for tests */
+D2FE_API int d2fe_window_push_host(d2fe_window x, const float* netvlad, const float* desc, const int32_t* n_kp, int64_t tag);
+/* updatebySldWin's erase loop (:47-57): drops every keyframe whose tag is not among tags[0..n), except the newest; the order of the rest is kept.  Returns how many
+ * were dropped.  Host bookkeeping only -- no launch, no synchronisation: a later push into a freed slot is ordered behind earlier queries by the window's stream. */
+D2FE_API int d2fe_window_retain(d2fe_window x, const int64_t* tags, int n);
+/* the same rule without a device: tags[0..n) oldest first, keep[0..nkeep); evict_out[i] = 1 for every keyframe that goes (may be NULL).  Returns how many go.
+ * d2fe_window_retain uses it. */
+D2FE_API int d2fe_window_retain_plan(const int64_t* tags, int n, const int64_t* keep, int nkeep, uint8_t* evict_out);
+D2FE_API int d2fe_window_size(d2fe_window x);
+D2FE_API int d2fe_window_tags(d2fe_window x, int64_t* tags, int cap_tags);      /* oldest first, at most cap_tags of them; returns the window's size */
+/* Tracks nq remote frames.  DEVICE arrays: row q * V + v of each is view v of frame q; the strides count 32-bit words between consecutive rows, so the same call reads
+ * the pipes' dense arrays (strides netvlad_dim, cap * desc_dim, 1) and the exchanges' gathered fp32 blocks in place (all three strides d2fe_block_words, the bases
+ * from d2fe_block_field_offset: fields 3, 0, 4).  Descriptor rows are 16-byte aligned; NetVLAD rows need not be (a block's are only when cap % 4 == 0).  The arrays are
+ * read in place and stay valid until the slot was collected.  stream: the hipStream_t that produced them (the window's stream waits for what is queued on it now), or
+ * NULL when they are complete.  Refused: a slot that has not been collected (D2FE_ERR_NOT_READY), nq outside 1..max_queries. */
+D2FE_API int d2fe_window_track_device(d2fe_window x, const float* d_netvlad, size_t nv_stride, const float* d_desc, size_t desc_stride, const int32_t* d_n_kp,
+                                      size_t nkp_stride, int nq, int slot, void* stream);
+D2FE_API int d2fe_window_collect(d2fe_window x, int slot, d2fe_window_result* out);      /* blocks until the slot's results are in host memory */
 
 /* Test hooks and kernel diagnostics (d2fe_debug_*) are NOT part of this library: they live in the development library
  * (lib/libd2fe_hip_dev.so, built with -DD2FE_DEVTOOLS) and are declared in include/d2fe_debug.h. */

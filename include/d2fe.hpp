@@ -449,6 +449,90 @@ class LoopQuery {
   d2fe_loop x_ = nullptr;
 };
 
+// d2fe_window_* (remote tracking against the keyframe window; include/d2fe.h) with the lifetime of a C++ object: current_keyframes on the device, and what
+// D2FeatureTracker::trackRemoteFrames (d2featuretracker.cpp:237-310) does with a batch of remote frames -- getMatchedPrevKeyframe's walk and matchKNN(keyframe, remote)
+// -- without a host round trip.  Destroy it BEFORE its pipe (declare it after the pipe).  With the caller: frame_id <-> tag, lazy / pre-matched frames, the landmark-id
+// bookkeeping, remote_min_match_num, check_essential, motion prediction, the right-image pair of a stereo agent without lr_lk, SuperGlue.
+struct RemoteTrack {                   // one remote frame of a collected result
+  int64_t keyframe_tag = -1;                                               // frame_id of the matched keyframe, -1: getMatchedPrevKeyframe returned false
+  int keyframe_pos = -1, dir_a = -1, dir_b = -1;                           // position in the window as queued (oldest = 0); dir_cur, dir_prev
+  float similarity = 0.f;
+  std::vector<int> local_view, remote_view;                                // per pair (-1 without a hit)
+  std::vector<std::vector<DMatch>> matches;                                // per pair; queryIdx: keypoint of the keyframe, trainIdx: keypoint of the remote frame
+};
+class KeyframeWindow {
+ public:
+  KeyframeWindow(const StereoPipe& pipe, const d2fe_window_config& cfg) {
+    if (d2fe_window_create(pipe.get(), &cfg, &x_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_window_create: %s\n", d2fe_last_error()); x_ = nullptr; }
+  }
+  KeyframeWindow(const QuadPipe& pipe, const d2fe_window_config& cfg) {
+    if (d2fe_window_create_quad(pipe.get(), &cfg, &x_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_window_create_quad: %s\n", d2fe_last_error()); x_ = nullptr; }
+  }
+  ~KeyframeWindow() { if (x_) d2fe_window_destroy(x_); }
+  KeyframeWindow(const KeyframeWindow&) = delete;
+  KeyframeWindow& operator=(const KeyframeWindow&) = delete;
+  bool ok() const { return x_ != nullptr; }
+  d2fe_window get() const { return x_; }
+  void* stream() const { return x_ ? d2fe_window_stream(x_) : nullptr; }
+  int size() const { return x_ ? d2fe_window_size(x_) : 0; }
+  std::vector<int64_t> tags() const {      // oldest first
+    std::vector<int64_t> t(64);
+    const int n = x_ ? d2fe_window_tags(x_, t.data(), (int)t.size()) : 0;
+    t.resize(n > 0 ? n : 0);
+    return t;
+  }
+  // processFrame's emplace_back: frame `frame` of a ticket becomes the newest keyframe (asynchronous); the newest tag again is a no-op
+  bool push(int64_t ticket, int frame, int64_t tag) {
+    if (x_ && d2fe_window_push(x_, ticket, frame, tag) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_window_push: %s\n", d2fe_last_error());
+    return false;
+  }
+  bool push_host(const float* netvlad, const float* desc, const int32_t* n_kp, int64_t tag) {
+    if (x_ && d2fe_window_push_host(x_, netvlad, desc, n_kp, tag) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_window_push_host: %s\n", d2fe_last_error());
+    return false;
+  }
+  // updatebySldWin: drops what is not listed, except the newest; returns how many went (< 0: an error)
+  int retain(const std::vector<int64_t>& sld_win_tags) { return x_ ? d2fe_window_retain(x_, sld_win_tags.data(), (int)sld_win_tags.size()) : D2FE_ERR_INVALID; }
+  // asynchronous: nq remote frames in DEVICE arrays (row q * views + v, strides in 32-bit words); results arrive in pinned slot `slot`
+  bool track_device(const float* d_netvlad, size_t nv_stride, const float* d_desc, size_t desc_stride, const int32_t* d_n_kp, size_t nkp_stride, int nq, int slot,
+                    void* stream) {
+    if (x_ && d2fe_window_track_device(x_, d_netvlad, nv_stride, d_desc, desc_stride, d_n_kp, nkp_stride, nq, slot, stream) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_window_track_device: %s\n", d2fe_last_error());
+    return false;
+  }
+  // nq frames of gathered fp32 exchange blocks (d2fe_exchange_gathered / d2fe_quad_exchange_gathered), read in place from block `first_block` on
+  bool track_blocks(const float* d_blocks, int first_block, int nq, int cap, int netvlad_dim, int slot, void* stream) {
+    const size_t blk = (size_t)d2fe_block_words(cap, netvlad_dim);
+    const float* b = d_blocks + blk * (size_t)first_block;
+    return track_device(b + d2fe_block_field_offset(cap, netvlad_dim, 3), blk, b, blk, reinterpret_cast<const int32_t*>(b + d2fe_block_field_offset(cap, netvlad_dim, 4)), blk,
+                        nq, slot, stream);
+  }
+  // blocks until the slot's results are in host memory; `out` points into the pinned slot (valid until the slot is queued again)
+  bool collect(int slot, d2fe_window_result& out) {
+    if (x_ && d2fe_window_collect(x_, slot, &out) == D2FE_OK) return true;
+    std::fprintf(stderr, "[d2fe] d2fe_window_collect: %s\n", d2fe_last_error());
+    return false;
+  }
+  // remote frame q of a collected result
+  static RemoteTrack track(const d2fe_window_result& r, int q) {
+    RemoteTrack t;
+    if (q < 0 || q >= r.nq) return t;
+    t.keyframe_tag = r.keyframe_tag[q]; t.keyframe_pos = r.keyframe_pos[q]; t.dir_a = r.dir_a[q]; t.dir_b = r.dir_b[q]; t.similarity = r.sim[q];
+    for (int i = 0; i < r.views; ++i) {
+      const size_t p = (size_t)q * r.views + i, o = p * r.cap;
+      t.local_view.push_back(r.local_view[p]); t.remote_view.push_back(r.remote_view[p]);
+      std::vector<DMatch> m;
+      for (int j = 0; j < r.n_match[p]; ++j) m.emplace_back(r.q_idx[o + j], r.t_idx[o + j], r.dist[o + j]);
+      t.matches.push_back(std::move(m));
+    }
+    return t;
+  }
+
+ private:
+  d2fe_window x_ = nullptr;
+};
+
 // feature_matcher.h:6-11.  `h` replaces the implicit global state of cv::BFMatcher; everything else as in the reference.
 inline std::vector<DMatch> matchKNN(d2fe_handle h, const DescView& desc_a, const DescView& desc_b, double knn_match_ratio = 0.8,
                                     const std::vector<Point2f>& pts_a = std::vector<Point2f>(),
