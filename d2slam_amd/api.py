@@ -947,7 +947,24 @@ class DevFrontEnd(FrontEnd):
         load_library(dev=True).d2fe_debug_regime_reset()
 
 
-class StereoPipe:
+class _Owned:
+    """An object that owns one library object: _HANDLE names the attribute that holds it (a C.c_void_p), _DESTROY the library call that gives it back."""
+    _HANDLE = _DESTROY = None
+
+    def close(self):
+        h = getattr(self, self._HANDLE, None)
+        if h is not None and h.value:
+            getattr(self._lib, self._DESTROY)(h)
+            setattr(self, self._HANDLE, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StereoPipe(_Owned):
     """Frames in flight (include/d2fe.h, d2fe_pipe_*): the per-frame work of D2Frontend::processStereoframe (SuperPoint on both images, NetVLAD on
     the left one, matchKNN L<->R and L<->previous L) for `frames` stereo frames per submit with up to `lanes` submits in flight.
     lr_lk=True (needs match_lr=False): the reference's default stereo path (lr_match_use_lk) -- SuperPoint on the left images only, every left keypoint
@@ -958,6 +975,7 @@ class StereoPipe:
     "track_desc" [F, cap_tracks, D], "track_scores", "track_right_pts" [F, cap_tracks, 2], "track_right_status" [F, cap_tracks] and the counts
     "track_n_tracked_in", "track_n_lost", "track_n_removed_near", "track_n_new" [F] (include/d2fe.h, d2fe_pipe_track_result).
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits)."""
+    _HANDLE, _DESTROY = "_p", "d2fe_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
                  ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
@@ -993,17 +1011,6 @@ class StereoPipe:
         self.lanes, self.frames, self.width, self.height = int(lanes), int(frames), int(width), int(height)
         self._pinned_input = bool(pinned_input)
         self._res = _PipeResult()
-
-    def close(self):
-        if getattr(self, "_p", None) and self._p.value:
-            self._lib.d2fe_pipe_destroy(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def profile_enable(self, mode):
         _check(self._lib.d2fe_pipe_profile_enable(self._p, int(mode)))
@@ -1140,7 +1147,7 @@ def _pinned_view(ptr, shape, dt):
     return np.frombuffer(buf, dtype=dt).reshape(shape)
 
 
-class QuadPipe:
+class QuadPipe(_Owned):
     """Quadcam frames in flight (include/d2fe.h, d2fe_quad_pipe_*): per submit `quads` quad frames of four raw fisheye frames -> ONE undistort launch ->
     SuperPoint and NetVLAD of every view -> the four neighbour pairs (0,1) (1,2) (2,3) (0,3) and the temporal pairs, with up to `lanes` submits in flight.
     maps: per camera (mapx, mapy, gain or None) as [height][width] float32 numpy arrays or device tensors (anything with .data_ptr()); the pipe copies them.
@@ -1148,6 +1155,7 @@ class QuadPipe:
     Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit).
     sp_lk=True (d2fe_quad_track_enable; track_params: a dict of d2fe_track_params fields, a _TrackParams or None for the reference's defaults): the LK-carried
     landmark lists of the four cameras, the neighbour LK tracks and the neighbour matches of the lists; wait() then carries the track_* keys."""
+    _HANDLE, _DESTROY = "_p", "d2fe_quad_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, maps, lanes=4, quads=1, raw_width=1280, raw_height=800, width=800, height=400, cap=None, netvlad=True,
                  match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False,
@@ -1204,17 +1212,6 @@ class QuadPipe:
         """d2fe_quad_track_result_get: the lists of a ticket that wait() has returned"""
         _check(self._lib.d2fe_quad_track_result_get(self._p, C.c_int64(ticket), C.byref(self._track_res)))
         return self._track_res
-
-    def close(self):
-        if getattr(self, "_p", None) and self._p.value:
-            self._lib.d2fe_quad_pipe_destroy(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def submit_ptr(self, raw_ptr, stride=None, camera_stride=None, quad_stride=None):
         """raw host address (e.g. of a pinned torch tensor); image (q, c) at raw_ptr + q * quad_stride + c * camera_stride"""
@@ -1301,8 +1298,9 @@ def block_field_offset(cap, netvlad_dim, field):
     return int(load_library().d2fe_block_field_offset(int(cap), int(netvlad_dim), ["desc", "kps", "scores", "netvlad", "n"].index(field)))
 
 
-class FlatIPDatabase:
+class FlatIPDatabase(_Owned):
     """faiss::IndexFlatIP stand-in for the NetVLAD keyframe database (loop_detector.h:71-72, loop_detector.cpp:254-263,300-350)."""
+    _HANDLE, _DESTROY = "_db", "d2fe_db_destroy"
 
     def __init__(self, fe: FrontEnd, dim: int, capacity: int = 65536):
         self._lib = fe._lib
@@ -1310,17 +1308,6 @@ class FlatIPDatabase:
         self._fe = fe
         _check(self._lib.d2fe_db_create(fe.handle, dim, capacity, C.byref(self._db)))
         self.dim = dim
-
-    def close(self):
-        if self._db.value:
-            self._lib.d2fe_db_destroy(self._db)
-            self._db = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def ntotal(self):
@@ -1354,9 +1341,10 @@ LK_ITERS = 30            # SparsePyrLKOpticalFlow::create(WIN_SIZE, PYR_LEVEL, 3
 WHOLE_IMG_MATCH, LEFT_RIGHT_IMG_MATCH, RIGHT_LEFT_IMG_MATCH = 0, 1, 2   # TrackLRType
 
 
-class LKFrame:
+class LKFrame(_Owned):
     """Device-resident image pyramid = LKImageInfoGPU::pyr (opticaltrack_utils.h:16-23), built by buildImagePyramid
     (opticaltrack_utils.cpp:526-542)."""
+    _HANDLE, _DESTROY = "_f", "d2fe_lk_frame_destroy"
 
     def __init__(self, fe: FrontEnd, gray=None, levels=PYR_LEVEL, d_gray=None, width=None, height=None, stride=None, stream=None):
         self._lib = fe._lib
@@ -1371,17 +1359,6 @@ class LKFrame:
             self.width, self.height = int(width), int(height)
             _check(self._lib.d2fe_lk_frame_create_device(fe.handle, C.c_void_p(d_gray), self.width, self.height,
                                                          int(stride or width), levels, C.c_void_p(stream or 0), C.byref(self._f)))
-
-    def close(self):
-        if self._f.value:
-            self._lib.d2fe_lk_frame_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def level(self, l):
         w, h = self.width, self.height
@@ -1682,10 +1659,11 @@ def rccl_comm_destroy(comm):
         _check(load_library().d2fe_rccl_comm_destroy(C.c_void_p(comm)))
 
 
-class Exchange:
+class Exchange(_Owned):
     """d2fe_exchange_*: pack -> ONE all-gather -> gate -> remote matchKNN -> D2H per ticket of a StereoPipe, queued on the stream of the lane that produced the
     ticket (own_stream=False) or on one stream of its own.  comm: an ncclComm_t address (rccl_comm_init_rank, or D2SLAM's own) or None with `all_gather` =
     a Python callable (user, d_send, d_recv, bytes_per_rank, stream) -> 0 (tests over gloo)."""
+    _HANDLE, _DESTROY = "_x", "d2fe_exchange_destroy"
 
     def __init__(self, pipe, comm=None, world=1, rank=0, wire="fp32", loopback=False, slots=4, own_stream=False, timing=False, gate_thres=0.8, ratio=0.8, all_gather=None):
         self._lib = pipe._lib
@@ -1733,17 +1711,6 @@ class Exchange:
                 "mn": view(r.n_match, C.c_int32, (n,)), "gate_pass": view(r.gate_pass, C.c_int32, (n,)), "sims": view(r.gate_sims, C.c_float, (n,)),
                 "gate_n": int(r.gate_n), "phase_ms": [float(v) for v in r.phase_ms] if self.timing else None}
 
-    def close(self):
-        if getattr(self, "_x", None) and self._x.value:
-            self._lib.d2fe_exchange_destroy(self._x)
-            self._x = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 QUAD_MODE = {"all2all": 0, "gated": 1}
 QUAD_EXCHANGE_PHASES = ("pack_blocks", "all_gather", "decode_prepare", "match_remote", "release_and_d2h")
@@ -1759,11 +1726,12 @@ def quad_exchange_job_layout(world, rank, quads, loopback=False):
     return list(jr[:n]), list(jq[:n])
 
 
-class QuadExchange:
+class QuadExchange(_Owned):
     """d2fe_quad_exchange_*: device view -> pack one block per view -> ONE all-gather -> [int8: decode] -> ONE prepare launch (gate, matcher table, counter) ->
     ONE matcher launch -> release -> ONE D2H per ticket of a QuadPipe, on one stream of its own (own_stream=True) or on the producing lane's stream.  comm: an
     ncclComm_t address (rccl_comm_init_rank, or D2SLAM's own) or None with `all_gather` = a Python callable (user, d_send, d_recv, bytes_per_rank, stream) -> 0.
     Job j = (remote rank, quad frame), rank-major; all2all: problem j * 16 + lv * 4 + rv, gated: problem j * 4 + k (include/d2fe.h has the layout)."""
+    _HANDLE, _DESTROY = "_x", "d2fe_quad_exchange_destroy"
 
     def __init__(self, quad_pipe, comm=None, world=1, rank=0, wire="fp32", mode="all2all", loopback=False, slots=4, own_stream=True, timing=False, gate_thres=0.8,
                  ratio=0.8, all_gather=None):
@@ -1811,17 +1779,6 @@ class QuadExchange:
                 "dir_prev": _pinned_view(r.dir_prev, (nj,), i), "sims": _pinned_view(r.gate_sims, (nj, 4), f), "gate_n": int(r.gate_n),
                 "phase_ms": [float(v) for v in r.phase_ms] if self.timing else None}
 
-    def close(self):
-        if getattr(self, "_x", None) and self._x.value:
-            self._lib.d2fe_quad_exchange_destroy(self._x)
-            self._x = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- loop query behind a pipe (include/d2fe.h, d2fe_loop_*; csrc/loop.hip) -----------------------------------------------------------------------------------
 LOOP_QUERY, LOOP_ADD = 1, 2      # enum D2FE_LOOP_*
@@ -1845,9 +1802,10 @@ def loop_dirs(views, main_dir, dir_old):
     return [((main_dir + i) % views, ((dir_old - main_dir + views) % views + main_dir + i) % views) for i in range(views)]
 
 
-class LoopQuery:
+class LoopQuery(_Owned):
     """d2fe_loop_*: the device keyframe store behind a StereoPipe or a QuadPipe and, per ticket, search + gate -> matchKNN against the stored keyframe -> add, on
     one stream of its own (LoopDetector::processImageArray, loop_detector.cpp:23-215).  Destroy it before the pipe."""
+    _HANDLE, _DESTROY = "_x", "d2fe_loop_destroy"
 
     def __init__(self, pipe, capacity_keyframes=4096, max_index=10, thres=0.6, ratio=0.8, mode=0, slots=4, timing=False, max_queries=64):
         self._lib = pipe._lib
@@ -1914,17 +1872,6 @@ class LoopQuery:
         out["phase_ms"] = [float(v) for v in r.phase_ms] if self.timing else None
         return out
 
-    def close(self):
-        if getattr(self, "_x", None) and self._x.value:
-            self._lib.d2fe_loop_destroy(self._x)
-            self._x = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- remote tracking against the keyframe window (include/d2fe.h, d2fe_window_*; csrc/window.hip) ---------------------------------------------------------------
 WINDOW_PHASES = ("gate", "match", "d2h")
@@ -1964,10 +1911,11 @@ def window_views(views, dir_b):
     return [((2 + k) % 4, (dir_b - 2 + (2 + k) % 4) % 4) for k in range(4)]
 
 
-class KeyframeWindow:
+class KeyframeWindow(_Owned):
     """d2fe_window_*: the tracker's keyframe window on the device behind a StereoPipe or a QuadPipe, and D2FeatureTracker::trackRemoteFrames for a batch of remote
     frames -- the NetVLAD walk of getMatchedPrevKeyframe (newest keyframe first, the first pass wins) and matchKNN(keyframe, remote) -- as gate -> match -> D2H on one
     stream of its own (d2featuretracker.cpp:166-310).  Destroy it before the pipe."""
+    _HANDLE, _DESTROY = "_x", "d2fe_window_destroy"
 
     def __init__(self, pipe, capacity=12, thres=0.8, ratio=0.8, mode=0, slots=4, timing=False, max_queries=64):
         self._lib = pipe._lib
@@ -2062,13 +2010,3 @@ class KeyframeWindow:
         out["phase_ms"] = [float(v) for v in r.phase_ms] if self.timing else None
         return out
 
-    def close(self):
-        if getattr(self, "_x", None) and self._x.value:
-            self._lib.d2fe_window_destroy(self._x)
-            self._x = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

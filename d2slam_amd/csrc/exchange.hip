@@ -18,13 +18,12 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
-#include "rccl_table.h"
+#include "exchange_wire.h"
 
 using namespace d2fe;
 
 namespace d2fe {
-// the dlopen table of librccl (rccl_table.h: shared with quad_exchange.hip, loaded once)
+// the dlopen table of librccl (exchange_wire.h: shared with quad_exchange.hip, loaded once)
 Rccl g_rccl;
 namespace { std::mutex g_rccl_mu; }
 
@@ -53,6 +52,66 @@ int rccl_load(const char* path) {
 int rccl_fail(const char* what, int rc) {
   return ctx_fail(D2FE_ERR_HIP, std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error ") + " (" + std::to_string(rc) + ")");
 }
+
+// ---- the wire half of the two exchanges (exchange_wire.h) ----
+int wire_alloc_blocks(const Wire& w, WireSlot& S) {
+  const size_t nb = (size_t)w.NB * w.BLK, ng = (size_t)w.world * w.NB * w.BLK;
+  HIP_TRY(hipMalloc(&S.d_blocks, sizeof(float) * nb)); HIP_TRY(hipMemset(S.d_blocks, 0, sizeof(float) * nb));
+  HIP_TRY(hipMalloc(&S.d_gath, sizeof(float) * ng)); HIP_TRY(hipMemset(S.d_gath, 0, sizeof(float) * ng));
+  if (w.int8) {
+    HIP_TRY(hipMalloc(&S.d_blocks_q, (size_t)w.NB * w.BLKB)); HIP_TRY(hipMemset(S.d_blocks_q, 0, (size_t)w.NB * w.BLKB));
+    HIP_TRY(hipMalloc(&S.d_gath_q, (size_t)w.world * w.NB * w.BLKB)); HIP_TRY(hipMemset(S.d_gath_q, 0, (size_t)w.world * w.NB * w.BLKB));
+  }
+  return D2FE_OK;
+}
+
+void wire_free_slot(WireSlot& S) {
+  if (S.busy && S.done) (void)hipEventSynchronize(S.done);
+  for (void* q : {(void*)S.d_blocks, (void*)S.d_blocks_q, (void*)S.d_gath, (void*)S.d_gath_q})
+    if (q) (void)hipFree(q);
+  S.free();
+}
+
+void wire_destroy_stream(Wire& w) {
+  if (w.own) { (void)hipStreamSynchronize(w.own); (void)hipStreamDestroy(w.own); }
+}
+
+int wire_gathered(const Wire& w, const WireSlot& S, const float** d_blocks, const void** d_wire_blocks) {
+  if (d_blocks) *d_blocks = S.d_gath;
+  if (d_wire_blocks) *d_wire_blocks = w.int8 ? static_cast<const void*>(S.d_gath_q) : static_cast<const void*>(S.d_gath);
+  return D2FE_OK;
+}
+
+int wire_stream(const Wire& w, int64_t ticket, hipStream_t* st) {
+  void* lane_stream = nullptr;
+  if (!w.own) { const int rc = w.pipe.lane_stream(ticket, &lane_stream); if (rc) return rc; }
+  *st = w.own ? w.own : static_cast<hipStream_t>(lane_stream);
+  return D2FE_OK;
+}
+
+int wire_round(const Wire& w, WireSlot& S, const TicketView& v, hipStream_t st) {
+  const int NB = w.NB, cap = w.cap, G = w.G;
+  const void* send; void* recv; size_t bytes;
+  int r;
+  if (w.int8) {
+    r = d2fe_pack_blocks_int8_device(w.h, v.d_desc, v.d_kps_xy, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, G, S.d_blocks_q, st); if (r) return r;
+    send = S.d_blocks_q; recv = S.d_gath_q; bytes = (size_t)NB * w.BLKB;
+  } else {
+    r = d2fe_pack_blocks_device(w.h, v.d_desc, v.d_kps_xy, v.d_scores, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, G, S.d_blocks, st); if (r) return r;
+    send = S.d_blocks; recv = S.d_gath; bytes = sizeof(float) * (size_t)NB * w.BLK;
+  }
+  r = S.mark(1, st); if (r) return r;
+  if (w.comm) {
+    const int e = g_rccl.AllGather(send, recv, bytes, /* ncclInt8 */ 0, w.comm, st);
+    if (e) return rccl_fail("ncclAllGather", e);
+  } else {
+    r = w.all_gather(w.all_gather_user, send, recv, bytes, st);
+    if (r) return ctx_fail(D2FE_ERR_HIP, "the all-gather callback failed (" + std::to_string(r) + ")");
+  }
+  r = S.mark(2, st); if (r) return r;
+  if (w.int8) { r = d2fe_unpack_blocks_int8_device(w.h, S.d_gath_q, w.world * NB, cap, G, w.wire == D2FE_WIRE_INT8_RENORM256 ? 1 : 0, S.d_gath, st); if (r) return r; }
+  return D2FE_OK;
+}
 }  // namespace d2fe
 
 namespace {
@@ -68,24 +127,13 @@ __global__ void exchange_counts_kernel(const int32_t* __restrict__ own_n, int ow
 }
 }  // namespace
 
-struct d2fe_exchange_s {
-  d2fe_pipe p = nullptr;
-  d2fe_handle h = nullptr;
+struct d2fe_exchange_s : Wire {
   d2fe_exchange_config cfg{};
-  void* comm = nullptr;
-  int F = 0, cap = 0, G = 0, BLK = 0, BLKB = 0, NR = 0, n_off = 0, g_off = 0, own_n_word = 0;
-  bool int8 = false;
+  int F = 0, NR = 0, own_n_word = 0;
   int32_t *d_q_frame = nullptr, *d_rem_blk = nullptr, *d_a_off = nullptr, *d_b_off = nullptr;      // the pair layout (fixed)
   size_t out_words = 0, o_mq = 0, o_mt = 0, o_md = 0, o_mn = 0, o_pass = 0, o_sims = 0, o_np = 0;      // one result record: device copy and pinned slot share the layout
-  struct Slot {
-    float* d_blocks = nullptr; int8_t* d_blocks_q = nullptr; float* d_gath = nullptr; int8_t* d_gath_q = nullptr;
-    int32_t *d_a_cnt = nullptr, *d_b_cnt = nullptr;
-    float* d_out = nullptr; float* pin = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t done = nullptr;
-    bool busy = false; int64_t ticket = -1;
-  };
+  struct Slot : WireSlot { int32_t *d_a_cnt = nullptr, *d_b_cnt = nullptr; };
   std::vector<Slot> slots;
-  hipStream_t own = nullptr;       // cfg.own_stream: the one stream of its own (round 5's placement), else the lanes' streams
 };
 
 extern "C" {
@@ -130,16 +178,12 @@ void d2fe_exchange_destroy(d2fe_exchange x) {
   if (!x) return;
   if (x->h) (void)hipSetDevice(x->h->cfg.device_id);
   for (auto& S : x->slots) {
-    if (S.busy && S.done) (void)hipEventSynchronize(S.done);
-    for (void* q : {(void*)S.d_blocks, (void*)S.d_blocks_q, (void*)S.d_gath, (void*)S.d_gath_q, (void*)S.d_a_cnt, (void*)S.d_b_cnt, (void*)S.d_out})
-      if (q) (void)hipFree(q);
-    if (S.pin) (void)hipHostFree(S.pin);
-    for (auto& e : S.ev) if (e) (void)hipEventDestroy(e);
-    if (S.done) (void)hipEventDestroy(S.done);
+    wire_free_slot(S);
+    for (void* q : {(void*)S.d_a_cnt, (void*)S.d_b_cnt}) if (q) (void)hipFree(q);
   }
   for (void* q : {(void*)x->d_q_frame, (void*)x->d_rem_blk, (void*)x->d_a_off, (void*)x->d_b_off})
     if (q) (void)hipFree(q);
-  if (x->own) (void)hipStreamDestroy(x->own);
+  wire_destroy_stream(*x);
   delete x;
 }
 
@@ -148,10 +192,8 @@ int d2fe_exchange_create(d2fe_pipe p, void* nccl_comm, const d2fe_exchange_confi
   *out = nullptr;
   d2fe_exchange_config cfg;
   d2fe_exchange_default_config(&cfg);
-  memcpy(&cfg, cfg_in, (size_t)std::min<int32_t>(cfg_in->struct_size > 0 ? cfg_in->struct_size : (int32_t)sizeof(cfg), (int32_t)sizeof(cfg)));
-  if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || cfg.slots < 1 || cfg.slots > 64 || cfg.wire < 0 || cfg.wire > 2) return ctx_fail(D2FE_ERR_INVALID, "bad exchange configuration");
-  if (cfg.world == 1 && !cfg.loopback) return ctx_fail(D2FE_ERR_INVALID, "one rank and no loopback: nothing to exchange");
-  if (!nccl_comm && !cfg.all_gather) return ctx_fail(D2FE_ERR_INVALID, "neither an RCCL communicator nor an all-gather callback");
+  take_config(cfg, cfg_in);
+  { const int rc = wire_check_config(cfg, false, nccl_comm, "exchange"); if (rc) return rc; }
   if (nccl_comm) { const int rc = rccl_load(nullptr); if (rc) return rc; }
   int pf = 0, pcap = 0, pdim = 0, pg = 0;
   {
@@ -162,11 +204,8 @@ int d2fe_exchange_create(d2fe_pipe p, void* nccl_comm, const d2fe_exchange_confi
   auto* x = new (std::nothrow) d2fe_exchange_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_exchange_s* x; bool ok = false; ~Guard() { if (!ok) d2fe_exchange_destroy(x); } } guard{x};
-  x->p = p; x->h = d2fe_pipe_handle(p); x->cfg = cfg; x->comm = nccl_comm;
-  x->F = pf; x->cap = pcap; x->G = pg;
-  x->int8 = cfg.wire != D2FE_WIRE_FP32;
-  x->BLK = d2fe_block_words(pcap, pg); x->BLKB = d2fe_block_bytes_int8(pcap, pg);
-  x->n_off = d2fe_block_field_offset(pcap, pg, 4); x->g_off = d2fe_block_field_offset(pcap, pg, 3);
+  x->cfg = cfg; x->F = pf;
+  { const int rc = wire_init(*x, p, nccl_comm, cfg, pf, pcap, pg); if (rc) return rc; }
   if (x->int8 && (pcap * 256 + pg + pcap * 8) % 4) return ctx_fail(D2FE_ERR_UNSUPPORTED, "int8 blocks of this capacity / NetVLAD size do not keep their count word aligned");
   x->own_n_word = x->int8 ? (pcap * 256 + pg + pcap * 8) / 4 : x->n_off;
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
@@ -186,26 +225,15 @@ int d2fe_exchange_create(d2fe_pipe p, void* nccl_comm, const d2fe_exchange_confi
   };
   int rc = up(a_off, &x->d_a_off); rc = rc ? rc : up(b_off, &x->d_b_off); rc = rc ? rc : up(qf, &x->d_q_frame); rc = rc ? rc : up(rb, &x->d_rem_blk);
   if (rc) return rc;
-  auto up64 = [](size_t w) { return (w + 63) / 64 * 64; };
   size_t o = 0;
   x->o_mq = o; o += up64((size_t)NR * pcap); x->o_mt = o; o += up64((size_t)NR * pcap); x->o_md = o; o += up64((size_t)NR * pcap);
   x->o_mn = o; o += up64(NR); x->o_pass = o; o += up64(NR); x->o_sims = o; o += up64(NR); x->o_np = o; o += 64;
   x->out_words = o;
   x->slots.resize(cfg.slots);
   for (auto& S : x->slots) {
-    const size_t nb = (size_t)pf * x->BLK, ng = (size_t)cfg.world * pf * x->BLK;
-    HIP_TRY(hipMalloc(&S.d_blocks, sizeof(float) * nb)); HIP_TRY(hipMemset(S.d_blocks, 0, sizeof(float) * nb));
-    HIP_TRY(hipMalloc(&S.d_gath, sizeof(float) * ng)); HIP_TRY(hipMemset(S.d_gath, 0, sizeof(float) * ng));
-    if (x->int8) {
-      HIP_TRY(hipMalloc(&S.d_blocks_q, (size_t)pf * x->BLKB)); HIP_TRY(hipMemset(S.d_blocks_q, 0, (size_t)pf * x->BLKB));
-      HIP_TRY(hipMalloc(&S.d_gath_q, (size_t)cfg.world * pf * x->BLKB)); HIP_TRY(hipMemset(S.d_gath_q, 0, (size_t)cfg.world * pf * x->BLKB));
-    }
+    if ((rc = wire_alloc_blocks(*x, S)) != D2FE_OK) return rc;
     HIP_TRY(hipMalloc(&S.d_a_cnt, sizeof(int32_t) * std::max(NR, 1))); HIP_TRY(hipMalloc(&S.d_b_cnt, sizeof(int32_t) * std::max(NR, 1)));
-    HIP_TRY(hipMalloc(&S.d_out, sizeof(float) * x->out_words)); HIP_TRY(hipMemset(S.d_out, 0, sizeof(float) * x->out_words));
-    HIP_TRY(hipHostMalloc(&S.pin, sizeof(float) * x->out_words, hipHostMallocDefault));
-    memset(S.pin, 0, sizeof(float) * x->out_words);
-    if (cfg.timing) for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    if ((rc = S.alloc(x->out_words, x->out_words, cfg.timing != 0)) != D2FE_OK) return rc;
   }
   if (cfg.own_stream) HIP_TRY(hipStreamCreateWithFlags(&x->own, hipStreamNonBlocking));
   HIP_TRY(hipDeviceSynchronize());
@@ -220,10 +248,7 @@ void* d2fe_exchange_stream(d2fe_exchange x) { return x ? x->own : nullptr; }
 
 int d2fe_exchange_gathered(d2fe_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks) {
   if (!x || slot < 0 || slot >= (int)x->slots.size()) return ctx_fail(D2FE_ERR_INVALID, "bad argument");
-  const auto& S = x->slots[slot];
-  if (d_blocks) *d_blocks = S.d_gath;
-  if (d_wire_blocks) *d_wire_blocks = x->int8 ? static_cast<const void*>(S.d_gath_q) : static_cast<const void*>(S.d_gath);
-  return D2FE_OK;
+  return wire_gathered(*x, x->slots[slot], d_blocks, d_wire_blocks);
 }
 
 int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
@@ -231,37 +256,14 @@ int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
   auto& S = x->slots[slot];
   if (S.busy) return ctx_fail(D2FE_ERR_NOT_READY, "this slot's previous exchange has not been collected");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  void* lane_stream = nullptr;
-  if (!x->own) { const int rc = d2fe_pipe_lane_stream(x->p, ticket, &lane_stream); if (rc) return rc; }
-  hipStream_t st = x->own ? x->own : static_cast<hipStream_t>(lane_stream);
-  d2fe_pipe_device_result v{};
-  int rc = d2fe_pipe_device_view(x->p, ticket, st, &v);
-  if (rc) return rc;
-  // from here on the view must be released whatever happens (a block with an outstanding view ends the pipe 2 * lanes passes later)
-  auto run = [&]() -> int {
+  hipStream_t st = nullptr;
+  { const int rc = wire_stream(*x, ticket, &st); if (rc) return rc; }
+  const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
     if (v.frames != x->F || v.cap != x->cap || v.desc_dim != 256) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
-    const bool tm = x->cfg.timing != 0;
-    auto mark = [&](int i) -> int { if (tm) HIP_TRY(hipEventRecord(S.ev[i], st)); return D2FE_OK; };
+    auto mark = [&](int i) { return S.mark(i, st); };
     int r = mark(0); if (r) return r;
-    const int F = x->F, cap = x->cap, G = x->G, W = x->cfg.world;
-    const void* send; void* recv; size_t bytes;
-    if (x->int8) {
-      r = d2fe_pack_blocks_int8_device(x->h, v.d_desc, v.d_kps_xy, v.d_n_kp, v.d_netvlad, 0, 1, F, cap, G, S.d_blocks_q, st); if (r) return r;
-      send = S.d_blocks_q; recv = S.d_gath_q; bytes = (size_t)F * x->BLKB;
-    } else {
-      r = d2fe_pack_blocks_device(x->h, v.d_desc, v.d_kps_xy, v.d_scores, v.d_n_kp, v.d_netvlad, 0, 1, F, cap, G, S.d_blocks, st); if (r) return r;
-      send = S.d_blocks; recv = S.d_gath; bytes = sizeof(float) * (size_t)F * x->BLK;
-    }
-    r = mark(1); if (r) return r;
-    if (x->comm) {
-      const int e = g_rccl.AllGather(send, recv, bytes, /* ncclInt8 */ 0, x->comm, st);
-      if (e) return rccl_fail("ncclAllGather", e);
-    } else {
-      r = x->cfg.all_gather(x->cfg.all_gather_user, send, recv, bytes, st);
-      if (r) return ctx_fail(D2FE_ERR_HIP, "the all-gather callback failed (" + std::to_string(r) + ")");
-    }
-    r = mark(2); if (r) return r;
-    if (x->int8) { r = d2fe_unpack_blocks_int8_device(x->h, S.d_gath_q, W * F, cap, G, x->cfg.wire == D2FE_WIRE_INT8_RENORM256 ? 1 : 0, S.d_gath, st); if (r) return r; }
+    r = wire_round(*x, S, v, st); if (r) return r;
+    const int cap = x->cap, G = x->G;
     int32_t* O = reinterpret_cast<int32_t*>(S.d_out);
     if (x->NR > 0) {
       const int32_t* own = x->int8 ? reinterpret_cast<const int32_t*>(S.d_blocks_q) : reinterpret_cast<const int32_t*>(S.d_blocks);
@@ -285,15 +287,10 @@ int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
       r = d2fe_match_batch_device(x->h, &mb, st); if (r) return r;
     }
     return mark(4);
-  };
-  rc = run();
-  const int rr = d2fe_pipe_device_release(x->p, ticket, st);
+  });
   if (rc) return rc;
-  if (rr) return rr;
-  HIP_TRY(hipMemcpyAsync(S.pin, S.d_out, sizeof(float) * x->out_words, hipMemcpyDeviceToHost, st));
-  if (x->cfg.timing) HIP_TRY(hipEventRecord(S.ev[5], st));
-  HIP_TRY(hipEventRecord(S.done, st));
-  S.busy = true; S.ticket = ticket;
+  { const int r = S.finish(st, x->out_words, 5); if (r) return r; }
+  S.ticket = ticket;
   return D2FE_OK;
 }
 
@@ -302,15 +299,13 @@ int d2fe_exchange_collect(d2fe_exchange x, int slot, d2fe_exchange_result* out) 
   auto& S = x->slots[slot];
   if (!S.busy) return ctx_fail(D2FE_ERR_INVALID, "nothing was enqueued on this slot");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  HIP_TRY(hipEventSynchronize(S.done));
+  { const int rc = S.collect_begin(); if (rc) return rc; }
   memset(out, 0, sizeof(*out));
   const int32_t* I = reinterpret_cast<const int32_t*>(S.pin);
   out->ticket = S.ticket; out->npairs = x->NR; out->cap = x->cap;
   out->q_idx = I + x->o_mq; out->t_idx = I + x->o_mt; out->dist = S.pin + x->o_md; out->n_match = I + x->o_mn;
   out->gate_pass = x->G ? I + x->o_pass : nullptr; out->gate_sims = x->G ? S.pin + x->o_sims : nullptr; out->gate_n = x->G ? I[x->o_np] : 0;
-  if (x->cfg.timing)
-    for (int i = 0; i < 5; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, S.ev[i], S.ev[i + 1]) == hipSuccess) out->phase_ms[i] = ms; }
-  S.busy = false;
+  S.phase_ms(out->phase_ms, 5);
   return D2FE_OK;
 }
 

@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "consumer.h"
 
 using namespace d2fe;
 
@@ -242,7 +242,7 @@ hipError_t launch_loop_append(const LoopArgs& a, const LoopFlags& fl, hipStream_
 }  // namespace
 
 struct d2fe_loop_s {
-  d2fe_pipe p = nullptr; d2fe_quad_pipe qp = nullptr;
+  PipeRef pipe;
   d2fe_handle h = nullptr;
   d2fe_loop_config cfg{};
   int F = 0, V = 1, main_dir = 0, cap = 0, D = 0, G = 0, NQ = 0, lanes = 0;
@@ -256,11 +256,7 @@ struct d2fe_loop_s {
   long rows_bound = 0;          // host: upper bound of the device's ntotal
   int64_t last_ticket = -1;
   size_t out_words = 0, o_mq = 0, o_mt = 0, o_md = 0, o_mn = 0, o_queried = 0, o_label = 0, o_sim = 0, o_kf = 0, o_dir_old = 0, o_nt = 0, o_added = 0, o_da = 0, o_db = 0;
-  struct Slot {
-    float* d_out = nullptr; float* pin = nullptr; MatchPairDesc* d_pairs = nullptr; int32_t* d_plan = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t done = nullptr;
-    bool busy = false; int64_t ticket = -1; int frames = 0;
-  };
+  struct Slot : SlotBase { MatchPairDesc* d_pairs = nullptr; int32_t* d_plan = nullptr; int frames = 0; };
   std::vector<Slot> slots;
   hipStream_t st = nullptr;
   hipEvent_t ev_in = nullptr;      // d2fe_loop_query_device: orders the loop's stream behind the producer's
@@ -273,10 +269,8 @@ void loop_destroy(d2fe_loop_s* x) {
   if (x->h) (void)hipSetDevice(x->h->cfg.device_id);
   if (x->st) (void)hipStreamSynchronize(x->st);
   for (auto& S : x->slots) {
-    for (void* q : {(void*)S.d_out, (void*)S.d_pairs, (void*)S.d_plan}) if (q) (void)hipFree(q);
-    if (S.pin) (void)hipHostFree(S.pin);
-    for (auto& e : S.ev) if (e) (void)hipEventDestroy(e);
-    if (S.done) (void)hipEventDestroy(S.done);
+    for (void* q : {(void*)S.d_pairs, (void*)S.d_plan}) if (q) (void)hipFree(q);
+    S.free();
   }
   for (void* q : {(void*)x->d_db, (void*)x->d_row_kf, (void*)x->d_row_dir, (void*)x->d_state, (void*)x->d_store_desc, (void*)x->d_store_nkp, (void*)x->d_best,
                   (void*)x->d_match_scratch})
@@ -286,26 +280,26 @@ void loop_destroy(d2fe_loop_s* x) {
   delete x;
 }
 
-int loop_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_loop_config* cfg_in, d2fe_loop* out) {
-  if ((!p && !qp) || !cfg_in || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+int loop_create(PipeRef pipe, const d2fe_loop_config* cfg_in, d2fe_loop* out) {
+  if (!pipe || !cfg_in || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   *out = nullptr;
   d2fe_loop_config cfg;
   d2fe_loop_default_config(&cfg);
-  memcpy(&cfg, cfg_in, (size_t)std::min<int32_t>(cfg_in->struct_size > 0 ? cfg_in->struct_size : (int32_t)sizeof(cfg), (int32_t)sizeof(cfg)));
+  take_config(cfg, cfg_in);
   if (cfg.capacity_keyframes < 1 || cfg.max_index < 0 || cfg.slots < 1 || cfg.slots > 64 || (cfg.mode != 0 && cfg.mode != 1) || cfg.max_queries < 1 || cfg.max_queries > LOOP_MAXNQ)
     return ctx_fail(D2FE_ERR_INVALID, "bad loop configuration");
   int pf = 0, pcap = 0, pdim = 0, pg = 0;
-  { const int rc = p ? d2fe_pipe_geometry(p, &pf, &pcap, &pdim, &pg) : d2fe_quad_pipe_geometry(qp, &pf, &pcap, &pdim, &pg); if (rc) return rc; }
+  { const int rc = pipe.geometry(&pf, &pcap, &pdim, &pg); if (rc) return rc; }
   if (pg <= 0) return ctx_fail(D2FE_ERR_INVALID, "the loop query needs the pipe's NetVLAD (netvlad = 1)");
   if (pg & 3) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the NetVLAD length must be a multiple of 4");
   if (pf > LOOP_MAXNQ) return ctx_fail(D2FE_ERR_UNSUPPORTED, "more than 256 frames per pass");
   auto* x = new (std::nothrow) d2fe_loop_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_loop_s* x; bool ok = false; ~Guard() { if (!ok) loop_destroy(x); } } guard{x};
-  x->p = p; x->qp = qp; x->h = p ? d2fe_pipe_handle(p) : d2fe_quad_handle(qp); x->cfg = cfg;
-  x->lanes = p ? d2fe_pipe_lanes(p) : d2fe_quad_pipe_lanes(qp);
+  x->pipe = pipe; x->h = pipe.handle(); x->cfg = cfg;
+  x->lanes = pipe.lanes();
   x->F = pf; x->cap = pcap; x->D = pdim; x->G = pg;
-  x->V = p ? 1 : 4; x->main_dir = p ? 0 : 2;      // camera_index_new of queryImageArrayFromDatabase (:358-371)
+  x->V = pipe.views(); x->main_dir = x->V == 4 ? 2 : 0;      // camera_index_new of queryImageArrayFromDatabase (:358-371)
   x->NQ = std::max(pf, cfg.max_queries);
   x->cap_rows = (long)cfg.capacity_keyframes * x->V;
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
@@ -320,7 +314,6 @@ int loop_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_loop_config* cfg_in, 
   HIP_TRY(hipMalloc(&x->d_best, sizeof(unsigned long long) * LOOP_MAXNQ)); HIP_TRY(hipMemset(x->d_best, 0, sizeof(unsigned long long) * LOOP_MAXNQ));
   const size_t msb = match_scratch_bytes(NP, pcap);
   HIP_TRY(hipMalloc(&x->d_match_scratch, msb)); HIP_TRY(hipMemset(x->d_match_scratch, 0, msb));
-  auto up64 = [](size_t w) { return (w + 63) / 64 * 64; };
   size_t o = 0;
   x->o_mq = o; o += up64((size_t)NP * pcap); x->o_mt = o; o += up64((size_t)NP * pcap); x->o_md = o; o += up64((size_t)NP * pcap); x->o_mn = o; o += up64(NP);
   x->o_queried = o; o += up64(NQ); x->o_label = o; o += up64(NQ); x->o_sim = o; o += up64(NQ); x->o_kf = o; o += up64(NQ); x->o_dir_old = o; o += up64(NQ); x->o_nt = o; o += up64(NQ);
@@ -328,13 +321,9 @@ int loop_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_loop_config* cfg_in, 
   x->out_words = o;
   x->slots.resize(cfg.slots);
   for (auto& S : x->slots) {
-    HIP_TRY(hipMalloc(&S.d_out, sizeof(float) * x->out_words)); HIP_TRY(hipMemset(S.d_out, 0, sizeof(float) * x->out_words));
+    { const int rc = S.alloc(x->out_words, x->out_words, cfg.timing != 0); if (rc) return rc; }
     HIP_TRY(hipMalloc(&S.d_pairs, sizeof(MatchPairDesc) * (size_t)NP));
     HIP_TRY(hipMalloc(&S.d_plan, sizeof(int32_t) * (size_t)(2 + NP))); HIP_TRY(hipMemset(S.d_plan, 0, sizeof(int32_t) * (size_t)(2 + NP)));
-    HIP_TRY(hipHostMalloc(&S.pin, sizeof(float) * x->out_words, hipHostMallocDefault));
-    memset(S.pin, 0, sizeof(float) * x->out_words);
-    if (cfg.timing) for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
   }
   HIP_TRY(hipDeviceSynchronize());
   guard.ok = true;
@@ -346,8 +335,7 @@ int loop_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_loop_config* cfg_in, 
 int loop_run(d2fe_loop_s* x, d2fe_loop_s::Slot& S, const float* q_nv, const float* q_desc, const int32_t* q_nkp, int nq, int max_index, const LoopFlags& fl, bool append,
              long rows_bound) {
   hipStream_t st = x->st;
-  const bool tm = x->cfg.timing != 0;
-  auto mark = [&](int i) -> int { if (tm) HIP_TRY(hipEventRecord(S.ev[i], st)); return D2FE_OK; };
+  auto mark = [&](int i) { return S.mark(i, st); };
   int32_t* O = reinterpret_cast<int32_t*>(S.d_out);
   LoopArgs a{};
   a.db = x->d_db; a.row_kf = x->d_row_kf; a.row_dir = x->d_row_dir; a.d_ntotal = x->d_state; a.store_desc = x->d_store_desc; a.store_nkp = x->d_store_nkp;
@@ -361,9 +349,7 @@ int loop_run(d2fe_loop_s* x, d2fe_loop_s::Slot& S, const float* q_nv, const floa
   r = mark(1); if (r) return r;
   MatchArgs m{};
   m.pairs = S.d_pairs; m.npairs = nq * x->V; m.dim = x->D; m.max_n = x->cap; m.mode = x->cfg.mode; m.ratio = x->cfg.ratio; m.radius = -1.0;
-  m.q_idx = O + x->o_mq; m.t_idx = O + x->o_mt; m.dist = S.d_out + x->o_md; m.n_out = O + x->o_mn;
-  match_scratch_carve(x->d_match_scratch, x->NQ * x->V, &m);
-  m.stats = x->h->match_stats; m.ncu = x->h->ncu;
+  match_outputs(m, O + x->o_mq, O + x->o_mt, S.d_out + x->o_md, O + x->o_mn, x->d_match_scratch, x->NQ * x->V, x->h);
   HIP_TRY(launch_match(m, st));
   r = mark(2); if (r) return r;
   if (append) HIP_TRY(launch_loop_append(a, fl, st));
@@ -371,10 +357,9 @@ int loop_run(d2fe_loop_s* x, d2fe_loop_s::Slot& S, const float* q_nv, const floa
 }
 
 int loop_finish(d2fe_loop_s* x, d2fe_loop_s::Slot& S, int64_t ticket, int nq) {
-  HIP_TRY(hipMemcpyAsync(S.pin, S.d_out, sizeof(float) * x->out_words, hipMemcpyDeviceToHost, x->st));
-  if (x->cfg.timing) HIP_TRY(hipEventRecord(S.ev[4], x->st));
-  HIP_TRY(hipEventRecord(S.done, x->st));
-  S.busy = true; S.ticket = ticket; S.frames = nq;
+  const int rc = S.finish(x->st, x->out_words, 4);
+  if (rc) return rc;
+  S.ticket = ticket; S.frames = nq;
   return D2FE_OK;
 }
 
@@ -391,11 +376,11 @@ void d2fe_loop_default_config(d2fe_loop_config* c) {
 
 int d2fe_loop_create(d2fe_pipe p, const d2fe_loop_config* cfg, d2fe_loop* out) {
   if (!p) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  return loop_create(p, nullptr, cfg, out);
+  return loop_create(p, cfg, out);
 }
 int d2fe_loop_create_quad(d2fe_quad_pipe p, const d2fe_loop_config* cfg, d2fe_loop* out) {
   if (!p) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  return loop_create(nullptr, p, cfg, out);
+  return loop_create(p, cfg, out);
 }
 void d2fe_loop_destroy(d2fe_loop x) { loop_destroy(x); }
 
@@ -414,25 +399,12 @@ int d2fe_loop_enqueue(d2fe_loop x, int64_t ticket, int slot, const uint8_t* is_k
   if (x->keyframes + adds > x->cfg.capacity_keyframes) return ctx_fail(D2FE_ERR_TRUNCATED, "the keyframe store is full: nothing was queued");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
   hipStream_t st = x->st;
-  const float *q_nv = nullptr, *q_desc = nullptr; const int32_t* q_nkp = nullptr;
-  int vf = 0, vcap = 0, vd = 0, vg = 0;
-  if (x->p) {
-    d2fe_pipe_device_result v{};
-    const int rc = d2fe_pipe_device_view(x->p, ticket, st, &v);
-    if (rc) return rc;
-    q_nv = v.d_netvlad; q_desc = v.d_desc; q_nkp = v.d_n_kp; vf = v.frames; vcap = v.cap; vd = v.desc_dim; vg = v.netvlad_dim;
-  } else {
-    d2fe_quad_device_result v{};
-    const int rc = d2fe_quad_device_view(x->qp, ticket, st, &v);
-    if (rc) return rc;
-    q_nv = v.d_netvlad; q_desc = v.d_desc; q_nkp = v.d_n_kp; vf = v.quads; vcap = v.cap; vd = v.desc_dim; vg = v.netvlad_dim;
-  }
-  // from here on the view must be released whatever happens
-  int rc = (vf != F || vcap != x->cap || vd != x->D || vg != x->G || !q_nv) ? ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the loop query")
-                                                                             : loop_run(x, S, q_nv, q_desc, q_nkp, F, x->cfg.max_index, fl, true, x->rows_bound + (long)adds * V);
-  const int rr = x->p ? d2fe_pipe_device_release(x->p, ticket, st) : d2fe_quad_device_release(x->qp, ticket, st);
+  const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
+    if (v.frames != F || v.cap != x->cap || v.desc_dim != x->D || v.netvlad_dim != x->G || !v.d_netvlad)
+      return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the loop query");
+    return loop_run(x, S, v.d_netvlad, v.d_desc, v.d_n_kp, F, x->cfg.max_index, fl, true, x->rows_bound + (long)adds * V);
+  });
   if (rc) return rc;
-  if (rr) return rr;
   x->keyframes += adds; x->rows_bound += (long)adds * V; x->last_ticket = ticket;
   return loop_finish(x, S, ticket, F);
 }
@@ -457,16 +429,14 @@ int d2fe_loop_collect(d2fe_loop x, int slot, d2fe_loop_result* out) {
   auto& S = x->slots[slot];
   if (!S.busy) return ctx_fail(D2FE_ERR_INVALID, "nothing was enqueued on this slot");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  HIP_TRY(hipEventSynchronize(S.done));
+  { const int rc = S.collect_begin(); if (rc) return rc; }
   memset(out, 0, sizeof(*out));
   const int32_t* I = reinterpret_cast<const int32_t*>(S.pin);
   out->ticket = S.ticket; out->frames = S.frames; out->views = x->V; out->cap = x->cap;
   out->queried = I + x->o_queried; out->label = I + x->o_label; out->sim = S.pin + x->o_sim; out->keyframe = I + x->o_kf; out->dir_old = I + x->o_dir_old;
   out->ntotal_at_query = I + x->o_nt; out->added_label = I + x->o_added; out->dir_a = I + x->o_da; out->dir_b = I + x->o_db;
   out->n_match = I + x->o_mn; out->q_idx = I + x->o_mq; out->t_idx = I + x->o_mt; out->dist = S.pin + x->o_md;
-  if (x->cfg.timing)
-    for (int i = 0; i < 4; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, S.ev[i], S.ev[i + 1]) == hipSuccess) out->phase_ms[i] = ms; }
-  S.busy = false;
+  S.phase_ms(out->phase_ms, 4);
   return D2FE_OK;
 }
 

@@ -36,7 +36,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "lane_ring.h"
 #include "stream_deal.h"
 
 using namespace d2fe;
@@ -65,21 +65,10 @@ struct d2fe_pipe_s {
   float* d_all = nullptr;            // [64 zero words | K lanes x 2 sets x block]
   MatchPairDesc* d_pairs = nullptr;  // [K][2][C variants: submits of the PREVIOUS pass][C * npp]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;   // per lane: tickets + records
-  struct Lane {
-    d2fe_context* ctx = nullptr;
-    hipStream_t s = nullptr, nv = nullptr;
-    hipEvent_t ev_up = nullptr, ev_nv = nullptr, ev_ext[2] = {nullptr, nullptr}, ev_done = nullptr;
-    // device views of the two result blocks (d2fe_pipe_device_view / _release): views handed out and not released yet; ev_rel = the consumers' last release
-    hipEvent_t ev_rel[2] = {nullptr, nullptr};
-    hipEvent_t ev_chain = nullptr;     // sp_lk: the landmark-list chain of the lane's last pass and the carry copy behind it are complete
-    int views[2] = {0, 0};
-    bool rel_pending[2] = {false, false};
+  struct Lane : LaneBase {
     bool nv_on_side[2] = {false, false};      // the pass that wrote this block ran NetVLAD on the lane's second stream (auto mode decides per pass)
     uint8_t* d_img = nullptr;
-    uint8_t* pin_in = nullptr;
-    float* pin_out[2] = {nullptr, nullptr};
     uint8_t* d_lk = nullptr;           // lr_lk: this lane's pyramid workspace
-    long long rec = -1, synced = -1;   // the pass whose completion ev_done last recorded / the newest pass known to be complete (idle: synced >= rec)
   };
   std::vector<Lane> lanes;
   std::vector<int> first_class, second_class;   // the hardware-pipe class place_streams() measured for each lane's two streams (-1: not measured / no such stream)
@@ -114,8 +103,6 @@ struct d2fe_pipe_s {
 };
 
 namespace {
-
-size_t up64(size_t w) { return (w + 63) / 64 * 64; }
 
 // lr_lk: the reference's tracker constants (PYR_LEVEL opticaltrack_utils.h:10, WIN_SIZE opticaltrack_utils.cpp:25, 30 iterations :239)
 constexpr int LK_LEVELS = 2, LK_WIN = 21, LK_ITERS = 30;
@@ -258,14 +245,6 @@ int place_streams(int device_id, int n_first, int n_second, std::vector<hipStrea
 
 namespace {
 
-int lane_sync(d2fe_pipe_s::Lane& L) {       // called with the pipe's mutex held for the whole wait
-  if (L.synced < L.rec) {
-    HIP_TRY(hipEventSynchronize(L.ev_done));
-    L.synced = L.rec;
-  }
-  return D2FE_OK;
-}
-
 // passes launched and not known to be complete (one hipEventQuery per busy lane); < 0: a HIP error (d2fe_last_error is set)
 int passes_in_flight(d2fe_pipe_s* p) {
   int inflight = 0;
@@ -304,10 +283,8 @@ int pipe_flush(d2fe_pipe_s* p) {
     nv_side = infl <= 1;
   }
   L.nv_on_side[set] = nv_side;
-  // device views of this block (handed out 2 K passes ago): the consumers' stream must be through with it before this pass writes it.  The NetVLAD
-  // stream is ordered behind this wait through ev_up
-  if (L.views[set] > 0) return pipe_fail(D2FE_ERR_INVALID, "a device view of this lane's result block was not released (d2fe_pipe_device_release) within 2 * lanes passes");
-  if (L.rel_pending[set]) { HIP_TRY(hipStreamWaitEvent(s, L.ev_rel[set], 0)); L.rel_pending[set] = false; }
+  rc = lane_block_guard(L, set, "d2fe_pipe_device_release", "passes");
+  if (rc) return rc;
   if (p->cfg.netvlad && p->M > 1) HIP_TRY(hipEventRecord(L.ev_up, s));       // netvlad_group: the pipe's NetVLAD stream waits for this lane's frames
   // NetVLAD of the pass's left images in ONE call (its arithmetic order does not depend on the batch: run_netvlad decides the hidden-channel
   // split per image), C > 1: the left images are every second image of the lane's input buffer
@@ -345,7 +322,7 @@ int pipe_flush(d2fe_pipe_s* p) {
     rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride, nullptr, nullptr, 0, p->tp.levels,
                                      p->tp.win, p->tp.iters, L.d_lk, nullptr, nullptr, s);
     if (rc) return rc;
-    const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+    const auto [pk, pset] = prev_pass_block(k, set, p->K);
     if (P > 0 && p->K > 1) HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_chain, 0));
     const int32_t* cnt = reinterpret_cast<const int32_t*>(B + p->o_cnt);
     for (int f = 0; f < n_left; ++f) {
@@ -373,17 +350,15 @@ int pipe_flush(d2fe_pipe_s* p) {
   }
   if (p->npp > 0) {
     if (p->cfg.match_prev && P > 0 && p->K > 1) {      // the first temporal pair reads the previous pass's block: wait for ITS extraction only
-      const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+      const auto [pk, pset] = prev_pass_block(k, set, p->K);
       HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_ext[pset], 0));
     }
     const int npairs = g * p->npp, maxp = p->C * p->npp;
     MatchArgs m{};
     m.pairs = p->d_pairs + (((size_t)k * 2 + set) * p->C + (p->prev_g - 1)) * maxp;
     m.npairs = npairs; m.dim = p->D; m.max_n = p->cap; m.mode = 0; m.ratio = p->cfg.ratio; m.radius = -1.0;
-    m.q_idx = reinterpret_cast<int32_t*>(B + p->o_mq); m.t_idx = reinterpret_cast<int32_t*>(B + p->o_mt); m.dist = B + p->o_md;
-    m.n_out = reinterpret_cast<int32_t*>(B + p->o_mn);
-    match_scratch_carve(reinterpret_cast<char*>(p->d_match_scratch) + p->match_scratch_lane * k, maxp, &m);
-    m.stats = p->parent->match_stats; m.ncu = L.ctx->ncu;
+    match_outputs(m, reinterpret_cast<int32_t*>(B + p->o_mq), reinterpret_cast<int32_t*>(B + p->o_mt), B + p->o_md, reinterpret_cast<int32_t*>(B + p->o_mn),
+                  reinterpret_cast<char*>(p->d_match_scratch) + p->match_scratch_lane * k, maxp, p->parent, L.ctx->ncu);
     HIP_TRY(launch_match(m, s));
   }
   if (nv_side) HIP_TRY(hipStreamWaitEvent(s, L.ev_nv, 0));
@@ -464,9 +439,7 @@ int pipe_alloc_pairs(d2fe_pipe_s* p) {
       for (int set = 0; set < 2; ++set)
         for (int v = 0; v < C; ++v) {
           float* B = p->block(k, set);
-          // the previous pass: P - 1.  With P = i K + k the set is i & 1; P - 1 = i K + k - 1 (k > 0: same i) or (i - 1) K + K - 1
-          const int pk = k > 0 ? k - 1 : p->K - 1;
-          const int pset = k > 0 ? set : set ^ 1;
+          const auto [pk, pset] = prev_pass_block(k, set, p->K);
           float* PB = p->block(pk, pset);
           MatchPairDesc* row = tab.data() + (((size_t)k * 2 + set) * C + v) * maxp;
           int pi = 0;
@@ -666,14 +639,8 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       int rc2 = clone_lane(h, p->lk ? (int)NL : p->NI, &L.ctx, ms, lane_cus, cfg->netvlad && p->M == 1);      // lr_lk: the networks see the left images only
       if (rc2) { if (ms) (void)hipStreamDestroy(ms); return rc2; }
       L.s = L.ctx->stream;
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_up, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_nv, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_ext[0], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_ext[1], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[0], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&L.ev_rel[1], hipEventDisableTiming));
-      if (p->sp_lk) HIP_TRY(hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming));
+      rc2 = lane_create_events(L, p->sp_lk);
+      if (rc2) return rc2;
       L.d_img = p->d_img_all + (size_t)k * p->NI * p->W * p->H;
       if (p->lk) L.d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
       if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, (size_t)p->W * p->H * p->NI, hipHostMallocDefault));
@@ -710,14 +677,7 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
 void d2fe_pipe_destroy(d2fe_pipe p) {
   if (!p) return;
   (void)hipSetDevice(p->parent->cfg.device_id);
-  for (auto& L : p->lanes) {
-    if (L.s) (void)hipStreamSynchronize(L.s);
-    if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
-    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1], L.ev_chain}) if (e) (void)hipEventDestroy(e);
-    if (L.pin_in) (void)hipHostFree(L.pin_in);
-    for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
-    if (L.ctx) d2fe_destroy(L.ctx);
-  }
+  for (auto& L : p->lanes) lane_destroy(L);
   if (p->gnv) (void)hipStreamSynchronize(p->gnv);
   for (auto e : p->ev_g) if (e) (void)hipEventDestroy(e);
   if (p->gctx) d2fe_destroy(p->gctx);
@@ -732,8 +692,7 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   if (p->d_all) (void)hipFree(p->d_all);
   d2fe_context* parent = p->parent;
   delete p;
-  // a handle destroyed while this pipe was alive was only MARKED (d2fe_destroy): the last pipe to go releases it
-  if (parent->live_pipes.fetch_sub(1) == 1 && parent->doomed.load()) d2fe_destroy(parent);
+  pipe_gone(parent);
 }
 
 int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int stride, size_t image_stride, int64_t* ticket) {
@@ -849,15 +808,8 @@ int d2fe_pipe_wait(d2fe_pipe p, int64_t ticket, d2fe_pipe_result* out) {
   auto& L = p->lanes[k];
   int rc = D2FE_OK;
   if (L.synced < ti.pass) {
-    // block WITHOUT the mutex, so that the other thread can go on submitting.  The event may be recorded again meanwhile (a later pass of this lane):
-    // the wait then covers that record too, and everything the lane recorded up to `rec` is complete either way (one stream, in order)
-    const long long rec = L.rec;
-    hipEvent_t ev = L.ev_done;
-    lk.unlock();
-    const hipError_t e = hipEventSynchronize(ev);
-    lk.lock();
+    const hipError_t e = lane_wait_unlocked(L, lk);
     if (e != hipSuccess) return pipe_fail(D2FE_ERR_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
-    if (L.synced < rec) L.synced = rec;
     if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass + 2 * p->K < p->next_pass)
       return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block was reused while this call waited for it");
   }
@@ -925,15 +877,8 @@ int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_track_resu
   const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
   const float* B = p->lanes[k].pin_out[set];
   const size_t r0 = p->C > 1 ? (size_t)ti.j : 0, capT = (size_t)p->capT;
-  const float* list = B + p->o_list + r0 * p->list_words;
-  auto at = [&](int field) { return list + d2fe_lk_carry_list_offset(p->capT, p->D, field); };
-  const int32_t* hdr = reinterpret_cast<const int32_t*>(at(D2FE_LKC_HDR));
-  out->frames = p->F; out->cap_tracks = p->capT; out->desc_dim = p->D; out->list_words = (int32_t)p->list_words;
-  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
-  out->pts_xy = at(D2FE_LKC_PTS);
-  out->id = reinterpret_cast<const int32_t*>(at(D2FE_LKC_ID)); out->src = reinterpret_cast<const int32_t*>(at(D2FE_LKC_SRC));
-  out->kp = reinterpret_cast<const int32_t*>(at(D2FE_LKC_KP));
-  out->desc = at(D2FE_LKC_DESC); out->scores = at(D2FE_LKC_SCORES);
+  out->frames = p->F;
+  track_list_view(out, B + p->o_list + r0 * p->list_words, p->capT, p->D, p->list_words);
   out->right_xy = B + p->o_rxy + r0 * capT * 2;
   out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_rst) + r0 * capT;
   return D2FE_OK;
@@ -989,18 +934,14 @@ int d2fe_pipe_device_view(d2fe_pipe p, int64_t ticket, void* stream, d2fe_pipe_d
   const int rc = view_locate(p, ticket, true, &k, &set, &j);
   if (rc) return rc;
   auto& L = p->lanes[k];
-  hipStream_t cs = static_cast<hipStream_t>(stream);
-  // SuperPoint of the pass: ev_ext[set] (re-recorded only by the pass that rewrites this block, which view_locate has excluded).  NetVLAD on the lane's second
-  // stream: ev_nv -- a later pass of the lane may have re-recorded it; waiting for that later record is merely later, never earlier
-  HIP_TRY(hipStreamWaitEvent(cs, L.ev_ext[set], 0));
-  if (L.nv_on_side[set]) HIP_TRY(hipStreamWaitEvent(cs, L.ev_nv, 0));
+  const int rcv = lane_view_acquire(L, set, L.nv_on_side[set], static_cast<hipStream_t>(stream));      // (view_locate has excluded a block that is being rewritten)
+  if (rcv) return rcv;
   const float* B = p->block(k, set);
   const size_t cap = p->cap, r0 = p->left_row(j, 0);
   out->frames = p->F; out->cap = p->cap; out->desc_dim = p->D; out->netvlad_dim = p->G;
   out->d_kps_xy = B + p->o_kps + r0 * cap * 2; out->d_scores = B + p->o_scores + r0 * cap; out->d_desc = B + p->o_desc + r0 * cap * p->D;
   out->d_n_kp = reinterpret_cast<const int32_t*>(B + p->o_cnt) + r0;
   out->d_netvlad = p->G ? B + p->o_nv + (p->C > 1 ? (size_t)j : 0) * p->G : nullptr;
-  ++L.views[set];
   return D2FE_OK;
 }
 
@@ -1032,14 +973,7 @@ int d2fe_pipe_device_release(d2fe_pipe p, int64_t ticket, void* stream) {
   int k, set, j;
   const int rc = view_locate(p, ticket, false, &k, &set, &j);
   if (rc) return rc;
-  auto& L = p->lanes[k];
-  if (L.views[set] <= 0) return pipe_fail(D2FE_ERR_INVALID, "no device view of this ticket's block is outstanding");
-  // several consumers may share a block (coalesced submits): the event is re-recorded by each release; the lane waits for the last record, and consumers that
-  // release on DIFFERENT streams must order those streams themselves (documented: one consumer stream per pipe)
-  HIP_TRY(hipEventRecord(L.ev_rel[set], static_cast<hipStream_t>(stream)));
-  L.rel_pending[set] = true;
-  --L.views[set];
-  return D2FE_OK;
+  return lane_view_release(p->lanes[k], set, static_cast<hipStream_t>(stream));
 }
 
 /* HIP-event timing of the lanes' launch sequences (d2fe_profile_enable / d2fe_profile_read of every lane, summed) */

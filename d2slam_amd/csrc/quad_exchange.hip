@@ -14,8 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
-#include "rccl_table.h"
+#include "exchange_wire.h"
 
 using namespace d2fe;
 
@@ -113,29 +112,18 @@ __global__ __launch_bounds__(256) void quad_exchange_prepare_kernel(QuadPrepArgs
   }
 }
 
-size_t up64(size_t w) { return (w + 63) / 64 * 64; }
-
 }  // namespace
 
-struct d2fe_quad_exchange_s {
-  d2fe_quad_pipe p = nullptr;
-  d2fe_handle h = nullptr;
+struct d2fe_quad_exchange_s : Wire {
   d2fe_quad_exchange_config cfg{};
-  void* comm = nullptr;
-  int Q = 0, NI = 0, cap = 0, G = 0, BLK = 0, BLKB = 0, NJ = 0, PPJ = 16, NP = 0, n_off = 0, g_off = 0;
-  bool int8 = false;
+  int Q = 0, NJ = 0, PPJ = 16, NP = 0;
   int32_t *d_job_rank = nullptr, *d_job_quad = nullptr;      // the job layout (fixed)
   // one result record: the device copy and the pinned slot share the layout; the words below d2h_words come from the device, the job list behind them is host-written
   size_t out_words = 0, d2h_words = 0, o_mq = 0, o_mt = 0, o_md = 0, o_mn = 0, o_lv = 0, o_rv = 0, o_dir = 0, o_sims = 0, o_np = 0, o_jr = 0, o_jq = 0;
-  struct Slot {
-    float* d_blocks = nullptr; int8_t* d_blocks_q = nullptr; float* d_gath = nullptr; int8_t* d_gath_q = nullptr;
+  struct Slot : WireSlot {
     int32_t* d_tab = nullptr;        // a_off | b_off | a_cnt | b_cnt, NP words each, then the prepare kernel's two sync words
-    float* d_out = nullptr; float* pin = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t done = nullptr;
-    bool busy = false; int64_t ticket = -1;
   };
   std::vector<Slot> slots;
-  hipStream_t own = nullptr;
 };
 
 extern "C" {
@@ -166,16 +154,12 @@ void d2fe_quad_exchange_destroy(d2fe_quad_exchange x) {
   if (!x) return;
   if (x->h) (void)hipSetDevice(x->h->cfg.device_id);
   for (auto& S : x->slots) {
-    if (S.busy && S.done) (void)hipEventSynchronize(S.done);
-    for (void* q : {(void*)S.d_blocks, (void*)S.d_blocks_q, (void*)S.d_gath, (void*)S.d_gath_q, (void*)S.d_tab, (void*)S.d_out})
-      if (q) (void)hipFree(q);
-    if (S.pin) (void)hipHostFree(S.pin);
-    for (auto& e : S.ev) if (e) (void)hipEventDestroy(e);
-    if (S.done) (void)hipEventDestroy(S.done);
+    wire_free_slot(S);
+    if (S.d_tab) (void)hipFree(S.d_tab);
   }
   for (void* q : {(void*)x->d_job_rank, (void*)x->d_job_quad})
     if (q) (void)hipFree(q);
-  if (x->own) { (void)hipStreamSynchronize(x->own); (void)hipStreamDestroy(x->own); }
+  wire_destroy_stream(*x);
   delete x;
 }
 
@@ -184,12 +168,9 @@ int d2fe_quad_exchange_create(d2fe_quad_pipe p, void* nccl_comm, const d2fe_quad
   *out = nullptr;
   d2fe_quad_exchange_config cfg;
   d2fe_quad_exchange_default_config(&cfg);
-  memcpy(&cfg, cfg_in, (size_t)std::min<int32_t>(cfg_in->struct_size > 0 ? cfg_in->struct_size : (int32_t)sizeof(cfg), (int32_t)sizeof(cfg)));
+  take_config(cfg, cfg_in);
   // the configuration on its own first: none of these checks needs a pipe or a device
-  if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || cfg.slots < 1 || cfg.slots > 64 || cfg.wire < 0 || cfg.wire > 2 || cfg.mode < 0 || cfg.mode > 1)
-    return ctx_fail(D2FE_ERR_INVALID, "bad quad exchange configuration");
-  if (cfg.world == 1 && !cfg.loopback) return ctx_fail(D2FE_ERR_INVALID, "one rank and no loopback: nothing to exchange");
-  if (!nccl_comm && !cfg.all_gather) return ctx_fail(D2FE_ERR_INVALID, "neither an RCCL communicator nor an all-gather callback");
+  { const int rc = wire_check_config(cfg, cfg.mode < 0 || cfg.mode > 1, nccl_comm, "quad exchange"); if (rc) return rc; }
   if (!p) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   int pq = 0, pcap = 0, pdim = 0, pg = 0;
   {
@@ -202,13 +183,9 @@ int d2fe_quad_exchange_create(d2fe_quad_pipe p, void* nccl_comm, const d2fe_quad
   auto* x = new (std::nothrow) d2fe_quad_exchange_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_quad_exchange_s* x; bool ok = false; ~Guard() { if (!ok) d2fe_quad_exchange_destroy(x); } } guard{x};
-  x->p = p; x->h = d2fe_quad_handle(p); x->cfg = cfg; x->comm = nccl_comm;
-  x->Q = pq; x->NI = 4 * pq; x->cap = pcap; x->G = pg;
-  x->int8 = cfg.wire != D2FE_WIRE_FP32;
-  x->BLK = d2fe_block_words(pcap, pg); x->BLKB = d2fe_block_bytes_int8(pcap, pg);
-  if (x->BLK < 0 || x->BLKB < 0) return D2FE_ERR_INVALID;
-  x->n_off = d2fe_block_field_offset(pcap, pg, 4); x->g_off = d2fe_block_field_offset(pcap, pg, 3);
-  if ((long)cfg.world * x->NI * (x->BLK / 256) > 0x7fffffffL / 2) return ctx_fail(D2FE_ERR_INVALID, "the gathered buffer exceeds the matcher's 32-bit row offsets");
+  x->cfg = cfg; x->Q = pq;
+  { const int rc = wire_init(*x, p, nccl_comm, cfg, 4 * pq, pcap, pg); if (rc) return rc; }
+  if ((long)cfg.world * x->NB * (x->BLK / 256) > 0x7fffffffL / 2) return ctx_fail(D2FE_ERR_INVALID, "the gathered buffer exceeds the matcher's 32-bit row offsets");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
   x->NJ = d2fe_quad_exchange_job_layout(cfg.world, cfg.rank, pq, cfg.loopback, nullptr, nullptr, 0);
   if (x->NJ < 1) return ctx_fail(D2FE_ERR_INVALID, "no jobs");
@@ -228,20 +205,10 @@ int d2fe_quad_exchange_create(d2fe_quad_pipe p, void* nccl_comm, const d2fe_quad
   x->out_words = o;
   x->slots.resize(cfg.slots);
   for (auto& S : x->slots) {
-    const size_t nb = (size_t)x->NI * x->BLK, ng = (size_t)cfg.world * x->NI * x->BLK;
-    HIP_TRY(hipMalloc(&S.d_blocks, sizeof(float) * nb)); HIP_TRY(hipMemset(S.d_blocks, 0, sizeof(float) * nb));
-    HIP_TRY(hipMalloc(&S.d_gath, sizeof(float) * ng)); HIP_TRY(hipMemset(S.d_gath, 0, sizeof(float) * ng));
-    if (x->int8) {
-      HIP_TRY(hipMalloc(&S.d_blocks_q, (size_t)x->NI * x->BLKB)); HIP_TRY(hipMemset(S.d_blocks_q, 0, (size_t)x->NI * x->BLKB));
-      HIP_TRY(hipMalloc(&S.d_gath_q, (size_t)cfg.world * x->NI * x->BLKB)); HIP_TRY(hipMemset(S.d_gath_q, 0, (size_t)cfg.world * x->NI * x->BLKB));
-    }
+    { const int rc = wire_alloc_blocks(*x, S); if (rc) return rc; }
     HIP_TRY(hipMalloc(&S.d_tab, sizeof(int32_t) * (4 * (size_t)NP + 2))); HIP_TRY(hipMemset(S.d_tab, 0, sizeof(int32_t) * (4 * (size_t)NP + 2)));
-    HIP_TRY(hipMalloc(&S.d_out, sizeof(float) * x->d2h_words)); HIP_TRY(hipMemset(S.d_out, 0, sizeof(float) * x->d2h_words));
-    HIP_TRY(hipHostMalloc(&S.pin, sizeof(float) * x->out_words, hipHostMallocDefault));
-    memset(S.pin, 0, sizeof(float) * x->out_words);
+    { const int rc = S.alloc(x->d2h_words, x->out_words, cfg.timing != 0); if (rc) return rc; }
     memcpy(S.pin + x->o_jr, jr.data(), sizeof(int32_t) * NJ); memcpy(S.pin + x->o_jq, jq.data(), sizeof(int32_t) * NJ);
-    if (cfg.timing) for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
   }
   if (cfg.own_stream) HIP_TRY(hipStreamCreateWithFlags(&x->own, hipStreamNonBlocking));
   HIP_TRY(hipDeviceSynchronize());
@@ -257,10 +224,7 @@ void* d2fe_quad_exchange_stream(d2fe_quad_exchange x) { return x ? x->own : null
 
 int d2fe_quad_exchange_gathered(d2fe_quad_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks) {
   if (!x || slot < 0 || slot >= (int)x->slots.size()) return ctx_fail(D2FE_ERR_INVALID, "bad argument");
-  const auto& S = x->slots[slot];
-  if (d_blocks) *d_blocks = S.d_gath;
-  if (d_wire_blocks) *d_wire_blocks = x->int8 ? static_cast<const void*>(S.d_gath_q) : static_cast<const void*>(S.d_gath);
-  return D2FE_OK;
+  return wire_gathered(*x, x->slots[slot], d_blocks, d_wire_blocks);
 }
 
 int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
@@ -268,37 +232,14 @@ int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
   auto& S = x->slots[slot];
   if (S.busy) return ctx_fail(D2FE_ERR_NOT_READY, "this slot's previous exchange has not been collected");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  void* lane_stream = nullptr;
-  if (!x->own) { const int rc = d2fe_quad_lane_stream(x->p, ticket, &lane_stream); if (rc) return rc; }
-  hipStream_t st = x->own ? x->own : static_cast<hipStream_t>(lane_stream);
-  d2fe_quad_device_result v{};
-  int rc = d2fe_quad_device_view(x->p, ticket, st, &v);
-  if (rc) return rc;
-  // from here on the view must be released whatever happens (a block with an outstanding view ends the pipe 2 * lanes submits later)
-  auto run = [&]() -> int {
-    if (v.quads != x->Q || v.cap != x->cap || v.desc_dim != 256 || v.netvlad_dim != x->G) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
-    const bool tm = x->cfg.timing != 0;
-    auto mark = [&](int i) -> int { if (tm) HIP_TRY(hipEventRecord(S.ev[i], st)); return D2FE_OK; };
+  hipStream_t st = nullptr;
+  { const int rc = wire_stream(*x, ticket, &st); if (rc) return rc; }
+  const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
+    if (v.frames != x->Q || v.cap != x->cap || v.desc_dim != 256 || v.netvlad_dim != x->G) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
+    auto mark = [&](int i) { return S.mark(i, st); };
     int r = mark(0); if (r) return r;
-    const int NI = x->NI, cap = x->cap, G = x->G, W = x->cfg.world;
-    const void* send; void* recv; size_t bytes;
-    if (x->int8) {
-      r = d2fe_pack_blocks_int8_device(x->h, v.d_desc, v.d_kps_xy, v.d_n_kp, v.d_netvlad, 0, 1, NI, cap, G, S.d_blocks_q, st); if (r) return r;
-      send = S.d_blocks_q; recv = S.d_gath_q; bytes = (size_t)NI * x->BLKB;
-    } else {
-      r = d2fe_pack_blocks_device(x->h, v.d_desc, v.d_kps_xy, v.d_scores, v.d_n_kp, v.d_netvlad, 0, 1, NI, cap, G, S.d_blocks, st); if (r) return r;
-      send = S.d_blocks; recv = S.d_gath; bytes = sizeof(float) * (size_t)NI * x->BLK;
-    }
-    r = mark(1); if (r) return r;
-    if (x->comm) {
-      const int e = g_rccl.AllGather(send, recv, bytes, /* ncclInt8 */ 0, x->comm, st);
-      if (e) return rccl_fail("ncclAllGather", e);
-    } else {
-      r = x->cfg.all_gather(x->cfg.all_gather_user, send, recv, bytes, st);
-      if (r) return ctx_fail(D2FE_ERR_HIP, "the all-gather callback failed (" + std::to_string(r) + ")");
-    }
-    r = mark(2); if (r) return r;
-    if (x->int8) { r = d2fe_unpack_blocks_int8_device(x->h, S.d_gath_q, W * NI, cap, G, x->cfg.wire == D2FE_WIRE_INT8_RENORM256 ? 1 : 0, S.d_gath, st); if (r) return r; }
+    r = wire_round(*x, S, v, st); if (r) return r;
+    const int cap = x->cap, G = x->G;
     int32_t* O = reinterpret_cast<int32_t*>(S.d_out);
     const int NP = x->NP;
     QuadPrepArgs a{};
@@ -318,15 +259,10 @@ int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
     mb.d_q_idx = O + x->o_mq; mb.d_t_idx = O + x->o_mt; mb.d_dist = S.d_out + x->o_md; mb.d_n_out = O + x->o_mn;
     r = d2fe_match_batch_device(x->h, &mb, st); if (r) return r;
     return mark(4);
-  };
-  rc = run();
-  const int rr = d2fe_quad_device_release(x->p, ticket, st);
+  });
   if (rc) return rc;
-  if (rr) return rr;
-  HIP_TRY(hipMemcpyAsync(S.pin, S.d_out, sizeof(float) * x->d2h_words, hipMemcpyDeviceToHost, st));
-  if (x->cfg.timing) HIP_TRY(hipEventRecord(S.ev[5], st));
-  HIP_TRY(hipEventRecord(S.done, st));
-  S.busy = true; S.ticket = ticket;
+  { const int r = S.finish(st, x->d2h_words, 5); if (r) return r; }
+  S.ticket = ticket;
   return D2FE_OK;
 }
 
@@ -335,7 +271,7 @@ int d2fe_quad_exchange_collect(d2fe_quad_exchange x, int slot, d2fe_quad_exchang
   auto& S = x->slots[slot];
   if (!S.busy) return ctx_fail(D2FE_ERR_INVALID, "nothing was enqueued on this slot");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  HIP_TRY(hipEventSynchronize(S.done));
+  { const int rc = S.collect_begin(); if (rc) return rc; }
   memset(out, 0, sizeof(*out));
   const int32_t* I = reinterpret_cast<const int32_t*>(S.pin);
   out->ticket = S.ticket; out->njobs = x->NJ; out->npairs = x->NP; out->pairs_per_job = x->PPJ; out->cap = x->cap;
@@ -343,9 +279,7 @@ int d2fe_quad_exchange_collect(d2fe_quad_exchange x, int slot, d2fe_quad_exchang
   out->q_idx = I + x->o_mq; out->t_idx = I + x->o_mt; out->dist = S.pin + x->o_md; out->n_match = I + x->o_mn;
   out->local_view = I + x->o_lv; out->remote_view = I + x->o_rv;
   out->dir_prev = x->G ? I + x->o_dir : nullptr; out->gate_sims = x->G ? S.pin + x->o_sims : nullptr; out->gate_n = x->G ? I[x->o_np] : 0;
-  if (x->cfg.timing)
-    for (int i = 0; i < 5; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, S.ev[i], S.ev[i + 1]) == hipSuccess) out->phase_ms[i] = ms; }
-  S.busy = false;
+  S.phase_ms(out->phase_ms, 5);
   return D2FE_OK;
 }
 

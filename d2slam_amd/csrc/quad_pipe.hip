@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "lane_ring.h"
 
 using namespace d2fe;
 
@@ -110,8 +110,6 @@ hipError_t launch_quad_undistort(const QuadUndistortArgs& a, hipStream_t s) {
 
 constexpr int NB[4][3] = {{0, 1, 1}, {1, 2, 1}, {2, 3, 1}, {0, 3, 2}};     // quadcam.NEIGHBOURS: (view a, view b, type) 1 LEFT_RIGHT, 2 RIGHT_LEFT
 
-size_t up64(size_t w) { return (w + 63) / 64 * 64; }
-
 }  // namespace
 
 struct d2fe_quad_pipe_s {
@@ -145,20 +143,7 @@ struct d2fe_quad_pipe_s {
   uint8_t* d_trk_pyr = nullptr;        // [4 carried pyramids | K lanes x 4 Q pyramids], pyr_total bytes each
   MatchPairDesc* d_lpairs = nullptr;   // [K][4 Q]: the neighbour pairs of the lists, on the lane's pools
   int32_t* d_lmatch_scratch = nullptr; size_t lmatch_scratch_lane = 0;
-  struct Lane {
-    d2fe_context* ctx = nullptr;
-    hipStream_t s = nullptr, nv = nullptr;
-    hipEvent_t ev_up = nullptr, ev_nv = nullptr, ev_ext[2] = {nullptr, nullptr}, ev_done = nullptr;
-    hipEvent_t ev_chain = nullptr;     // track mode: the landmark-list chain of the lane's last pass and the carry copy behind it are complete
-    uint8_t* d_raw = nullptr;
-    uint8_t* pin_in = nullptr;
-    float* pin_out[2] = {nullptr, nullptr};
-    long long rec = -1, synced = -1;   // the pass whose completion ev_done last recorded / the newest pass known to be complete
-    // device views of the two result blocks (d2fe_quad_device_view / _release): views handed out and not released yet; ev_rel = the consumers' last release
-    hipEvent_t ev_rel[2] = {nullptr, nullptr};
-    int views[2] = {0, 0};
-    bool rel_pending[2] = {false, false};
-  };
+  struct Lane : LaneBase { uint8_t* d_raw = nullptr; };
   std::vector<Lane> lanes;
   std::vector<int> first_class, second_class;
   int n_classes = 0; long long probe_ticks = 0; double probe_turns_us = 0.0;
@@ -176,14 +161,6 @@ struct d2fe_quad_pipe_s {
 
 namespace {
 
-int lane_sync(d2fe_quad_pipe_s::Lane& L) {       // called with the pipe's mutex held
-  if (L.synced < L.rec) {
-    HIP_TRY(hipEventSynchronize(L.ev_done));
-    L.synced = L.rec;
-  }
-  return D2FE_OK;
-}
-
 // the matcher's pair tables of the keypoints; they hold addresses inside the result blocks (d2fe_quad_track_enable moves those and fills the table again)
 void quad_fill_pairs(const d2fe_quad_pipe_s* p, std::vector<MatchPairDesc>& tab) {
   const size_t cap = p->cap, D = p->D, NP = p->NP;
@@ -195,7 +172,8 @@ void quad_fill_pairs(const d2fe_quad_pipe_s* p, std::vector<MatchPairDesc>& tab)
   for (int k = 0; k < p->K; ++k)
     for (int set = 0; set < 2; ++set) {
       float* B = p->block(k, set);
-      float* PB = p->block(k > 0 ? k - 1 : p->K - 1, k > 0 ? set : set ^ 1);
+      const auto [pk, pset] = prev_pass_block(k, set, p->K);
+      float* PB = p->block(pk, pset);
       float* X = p->scratch(k);
       MatchPairDesc* row = tab.data() + ((size_t)k * 2 + set) * NP;
       int pi = 0;
@@ -228,10 +206,8 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
   // by pass P - 2 K + 1 (its temporal pairs), which is complete too: the submit of pass P - K + 1 synchronised with it
   int rc = lane_sync(L);
   if (rc) return rc;
-  // device views of this block (handed out 2 K passes ago): the consumer's stream must be through with it before this pass writes it.  The NetVLAD stream
-  // is ordered behind this wait through ev_up
-  if (L.views[set] > 0) return ctx_fail(D2FE_ERR_INVALID, "a device view of this lane's result block was not released (d2fe_quad_device_release) within 2 * lanes submits");
-  if (L.rel_pending[set]) { HIP_TRY(hipStreamWaitEvent(L.s, L.ev_rel[set], 0)); L.rel_pending[set] = false; }
+  rc = lane_block_guard(L, set, "d2fe_quad_device_release", "submits");
+  if (rc) return rc;
   const size_t rimg = (size_t)p->RW * p->RH, img = (size_t)p->W * p->H;
   const int Q = p->Q, NI = p->NI, W = p->W, H = p->H, RW = p->RW, RH = p->RH;
   hipStream_t s = L.s;
@@ -291,7 +267,7 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
     rc = d2fe_lk_track_stereo_device(L.ctx, und, und + (size_t)2 * Q * img, 2 * Q, W, H, W, img, nullptr, nullptr, 0, p->tp.levels, p->tp.win, p->tp.iters, pyr, nullptr,
                                      nullptr, s);
     if (rc) return rc;
-    const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+    const auto [pk, pset] = prev_pass_block(k, set, p->K);
     if (P > 0 && p->K > 1) HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_chain, 0));
     float* lists = B + p->o_list;
     for (int q = 0; q < Q; ++q) {
@@ -328,10 +304,8 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
     MatchArgs m{};
     m.pairs = p->d_lpairs + (size_t)k * 4 * Q;
     m.npairs = 4 * Q; m.dim = p->D; m.max_n = p->capT; m.mode = 0; m.ratio = p->cfg.ratio; m.radius = -1.0;
-    m.q_idx = reinterpret_cast<int32_t*>(B + p->o_lmq); m.t_idx = reinterpret_cast<int32_t*>(B + p->o_lmt); m.dist = B + p->o_lmd;
-    m.n_out = reinterpret_cast<int32_t*>(B + p->o_lmn);
-    match_scratch_carve(reinterpret_cast<char*>(p->d_lmatch_scratch) + p->lmatch_scratch_lane * k, 4 * Q, &m);
-    m.stats = p->parent->match_stats; m.ncu = L.ctx->ncu;
+    match_outputs(m, reinterpret_cast<int32_t*>(B + p->o_lmq), reinterpret_cast<int32_t*>(B + p->o_lmt), B + p->o_lmd, reinterpret_cast<int32_t*>(B + p->o_lmn),
+                  reinterpret_cast<char*>(p->d_lmatch_scratch) + p->lmatch_scratch_lane * k, 4 * Q, p->parent, L.ctx->ncu);
     HIP_TRY(launch_match(m, s));
     HIP_TRY(launch_remap_matches(m.q_idx, m.t_idx, m.n_out, map_a, map_b, tmap, 4 * Q, p->capT, p->capT, s));
   }
@@ -342,16 +316,14 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
   // 6. ONE matcher launch over the neighbour and the temporal pairs (the counts are read where compaction and extraction wrote them)
   if (p->NP) {
     if (p->n_pr && P > 0 && p->K > 1) {      // the temporal pairs of quad frame 0 read the previous pass's block: wait for ITS extraction only
-      const int pk = k > 0 ? k - 1 : p->K - 1, pset = k > 0 ? set : set ^ 1;
+      const auto [pk, pset] = prev_pass_block(k, set, p->K);
       HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_ext[pset], 0));
     }
     MatchArgs m{};
     m.pairs = p->d_pairs + ((size_t)k * 2 + set) * p->NP;
     m.npairs = p->NP; m.dim = p->D; m.max_n = p->cap; m.mode = 0; m.ratio = p->cfg.ratio; m.radius = -1.0;
-    m.q_idx = reinterpret_cast<int32_t*>(B + p->o_mq); m.t_idx = reinterpret_cast<int32_t*>(B + p->o_mt); m.dist = B + p->o_md;
-    m.n_out = reinterpret_cast<int32_t*>(B + p->o_mn);
-    match_scratch_carve(reinterpret_cast<char*>(p->d_match_scratch) + p->match_scratch_lane * k, p->NP, &m);
-    m.stats = p->parent->match_stats; m.ncu = L.ctx->ncu;
+    match_outputs(m, reinterpret_cast<int32_t*>(B + p->o_mq), reinterpret_cast<int32_t*>(B + p->o_mt), B + p->o_md, reinterpret_cast<int32_t*>(B + p->o_mn),
+                  reinterpret_cast<char*>(p->d_match_scratch) + p->match_scratch_lane * k, p->NP, p->parent, L.ctx->ncu);
     HIP_TRY(launch_match(m, s));
   }
   // 7. neighbour indices back into the full view lists, then ONE D2H
@@ -494,7 +466,7 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
       const int rc2 = clone_lane(h, NI, &L.ctx, ms, 0, p->G > 0);
       if (rc2) { (void)hipStreamDestroy(ms); return rc2; }
       L.s = L.ctx->stream;
-      for (hipEvent_t* e : {&L.ev_up, &L.ev_nv, &L.ev_ext[0], &L.ev_ext[1], &L.ev_done, &L.ev_rel[0], &L.ev_rel[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      { const int rce = lane_create_events(L, false); if (rce) return rce; }      // ev_chain comes with d2fe_quad_track_enable
       L.d_raw = p->d_raw_all + (size_t)k * NI * rimg;
       if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, rimg * NI, hipHostMallocDefault));
       for (int set = 0; set < 2; ++set) HIP_TRY(hipHostMalloc(&L.pin_out[set], sizeof(float) * p->d2h_words, hipHostMallocDefault));
@@ -520,21 +492,13 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
 void d2fe_quad_pipe_destroy(d2fe_quad_pipe p) {
   if (!p) return;
   (void)hipSetDevice(p->parent->cfg.device_id);
-  for (auto& L : p->lanes) {
-    if (L.s) (void)hipStreamSynchronize(L.s);
-    if (L.nv) { (void)hipStreamSynchronize(L.nv); (void)hipStreamDestroy(L.nv); }
-    for (hipEvent_t e : {L.ev_up, L.ev_nv, L.ev_ext[0], L.ev_ext[1], L.ev_done, L.ev_rel[0], L.ev_rel[1], L.ev_chain}) if (e) (void)hipEventDestroy(e);
-    if (L.pin_in) (void)hipHostFree(L.pin_in);
-    for (float* q : L.pin_out) if (q) (void)hipHostFree(q);
-    if (L.ctx) d2fe_destroy(L.ctx);
-  }
+  for (auto& L : p->lanes) lane_destroy(L);
   for (void* q : {(void*)p->d_all, (void*)p->d_scr, (void*)p->d_raw_all, (void*)p->d_maps, (void*)p->d_jobs, (void*)p->d_pairs, (void*)p->d_match_scratch,
                   (void*)p->d_trk, (void*)p->d_trk_pyr, (void*)p->d_lpairs, (void*)p->d_lmatch_scratch})
     if (q) (void)hipFree(q);
   d2fe_context* parent = p->parent;
   delete p;
-  // a handle destroyed while this pipe was alive was only MARKED (d2fe_destroy): the last pipe to go releases it
-  if (parent->live_pipes.fetch_sub(1) == 1 && parent->doomed.load()) d2fe_destroy(parent);
+  pipe_gone(parent);
 }
 
 int d2fe_quad_pipe_submit(d2fe_quad_pipe p, const uint8_t* raw, int stride, size_t camera_stride, size_t quad_stride, int64_t* ticket) {
@@ -561,18 +525,11 @@ int d2fe_quad_pipe_wait(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_pipe_result*
   const int k = (int)(ticket % p->K), set = (int)((ticket / p->K) & 1);
   auto& L = p->lanes[k];
   if (L.synced < ticket) {
-    // block WITHOUT the mutex, so that the other thread can go on submitting; a later pass of the lane may re-record the event meanwhile: the wait then
-    // covers that pass too, and everything the lane recorded up to `rec` is complete either way (one stream, in order)
-    const long long rec = L.rec;
-    hipEvent_t ev = L.ev_done;
-    lk.unlock();
-    const hipError_t e = hipEventSynchronize(ev);
-    lk.lock();
+    const hipError_t e = lane_wait_unlocked(L, lk);
     if (e != hipSuccess) {
       p->failed = D2FE_ERR_HIP; p->failed_msg = std::string("hipEventSynchronize: ") + hipGetErrorString(e);
       return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
     }
-    if (L.synced < rec) L.synced = rec;
     if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block was reused while this call waited for it");
   }
   const float* B = L.pin_out[set];
@@ -707,15 +664,8 @@ int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track
   const auto& L = p->lanes[k];
   if (L.synced < ticket) return ctx_fail(D2FE_ERR_NOT_READY, "d2fe_quad_pipe_wait has not returned this ticket yet");
   const float* B = L.pin_out[set];
-  const float* list = B + p->o_list;
-  auto at = [&](int field) { return list + d2fe_lk_carry_list_offset(p->capT, p->D, field); };
-  const int32_t* hdr = reinterpret_cast<const int32_t*>(at(D2FE_LKC_HDR));
-  out->quads = p->Q; out->cap_tracks = p->capT; out->desc_dim = p->D; out->list_words = (int32_t)p->list_words;
-  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
-  out->pts_xy = at(D2FE_LKC_PTS);
-  out->id = reinterpret_cast<const int32_t*>(at(D2FE_LKC_ID)); out->src = reinterpret_cast<const int32_t*>(at(D2FE_LKC_SRC));
-  out->kp = reinterpret_cast<const int32_t*>(at(D2FE_LKC_KP));
-  out->desc = at(D2FE_LKC_DESC); out->scores = at(D2FE_LKC_SCORES);
+  out->quads = p->Q;
+  track_list_view(out, B + p->o_list, p->capT, p->D, p->list_words);
   out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
   out->lnb_q = reinterpret_cast<const int32_t*>(B + p->o_lmq); out->lnb_t = reinterpret_cast<const int32_t*>(B + p->o_lmt);
   out->lnb_dist = B + p->o_lmd; out->lnb_n = reinterpret_cast<const int32_t*>(B + p->o_lmn);
@@ -754,17 +704,13 @@ int d2fe_quad_device_view(d2fe_quad_pipe p, int64_t ticket, void* stream, d2fe_q
   const int rc = quad_view_locate(p, ticket, &k, &set);
   if (rc) return rc;
   auto& L = p->lanes[k];
-  hipStream_t cs = static_cast<hipStream_t>(stream);
-  // SuperPoint of the pass: ev_ext[set] (re-recorded only by the pass that rewrites this block, which quad_view_locate has excluded).  NetVLAD on the lane's
-  // second stream: ev_nv -- a later pass of the lane may have re-recorded it; waiting for that later record is merely later, never earlier
-  HIP_TRY(hipStreamWaitEvent(cs, L.ev_ext[set], 0));
-  if (p->G) HIP_TRY(hipStreamWaitEvent(cs, L.ev_nv, 0));
+  const int rcv = lane_view_acquire(L, set, p->G > 0, static_cast<hipStream_t>(stream));      // (quad_view_locate has excluded a block that is being rewritten)
+  if (rcv) return rcv;
   const float* B = p->block(k, set);
   out->quads = p->Q; out->cap = p->cap; out->desc_dim = p->D; out->netvlad_dim = p->G;
   out->d_kps_xy = B + p->o_kps; out->d_scores = B + p->o_scores; out->d_desc = B + p->o_desc;
   out->d_n_kp = reinterpret_cast<const int32_t*>(B + p->o_cnt);
   out->d_netvlad = p->G ? B + p->o_nv : nullptr;
-  ++L.views[set];
   return D2FE_OK;
 }
 
@@ -775,12 +721,7 @@ int d2fe_quad_device_release(d2fe_quad_pipe p, int64_t ticket, void* stream) {
   int k, set;
   const int rc = quad_view_locate(p, ticket, &k, &set);
   if (rc) return rc;
-  auto& L = p->lanes[k];
-  if (L.views[set] <= 0) return ctx_fail(D2FE_ERR_INVALID, "no device view of this ticket's block is outstanding");
-  HIP_TRY(hipEventRecord(L.ev_rel[set], static_cast<hipStream_t>(stream)));
-  L.rel_pending[set] = true;
-  --L.views[set];
-  return D2FE_OK;
+  return lane_view_release(p->lanes[k], set, static_cast<hipStream_t>(stream));
 }
 
 int d2fe_quad_lane_stream(d2fe_quad_pipe p, int64_t ticket, void** stream) {

@@ -21,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "consumer.h"
 
 using namespace d2fe;
 
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void window_copy_kernel(const float* __restric
 }  // namespace
 
 struct d2fe_window_s {
-  d2fe_pipe p = nullptr; d2fe_quad_pipe qp = nullptr;
+  PipeRef pipe;
   d2fe_handle h = nullptr;
   d2fe_window_config cfg{};
   int F = 0, V = 1, cap = 0, D = 0, G = 0, NQ = 0;
@@ -174,11 +174,7 @@ struct d2fe_window_s {
   // host bookkeeping: the window oldest first, the tag of every slot, the free slots
   std::vector<int> order; std::vector<int64_t> slot_tag; std::vector<int> free_slots;
   struct Lay { size_t mq = 0, mt = 0, md = 0, mn = 0, lv = 0, rv = 0, tag = 0, pos = 0, da = 0, db = 0, sim = 0, sims = 0, words = 0; };
-  struct Slot {
-    float* d_out = nullptr; float* pin = nullptr; MatchPairDesc* d_pairs = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t done = nullptr;
-    bool busy = false; int nq = 0, n_window = 0; Lay lay;
-  };
+  struct Slot : SlotBase { MatchPairDesc* d_pairs = nullptr; int nq = 0, n_window = 0; Lay lay; };
   std::vector<Slot> slots;
   size_t out_words = 0;
   hipStream_t st = nullptr;
@@ -207,10 +203,8 @@ void window_destroy(d2fe_window_s* x) {
   if (x->h) (void)hipSetDevice(x->h->cfg.device_id);
   if (x->st) (void)hipStreamSynchronize(x->st);
   for (auto& S : x->slots) {
-    for (void* q : {(void*)S.d_out, (void*)S.d_pairs}) if (q) (void)hipFree(q);
-    if (S.pin) (void)hipHostFree(S.pin);
-    for (auto& e : S.ev) if (e) (void)hipEventDestroy(e);
-    if (S.done) (void)hipEventDestroy(S.done);
+    if (S.d_pairs) (void)hipFree(S.d_pairs);
+    S.free();
   }
   for (void* q : {(void*)x->d_nv, (void*)x->d_desc, (void*)x->d_nkp, (void*)x->d_state, (void*)x->d_best, (void*)x->d_match_scratch})
     if (q) (void)hipFree(q);
@@ -219,23 +213,23 @@ void window_destroy(d2fe_window_s* x) {
   delete x;
 }
 
-int window_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_window_config* cfg_in, d2fe_window* out) {
-  if ((!p && !qp) || !cfg_in || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+int window_create(PipeRef pipe, const d2fe_window_config* cfg_in, d2fe_window* out) {
+  if (!pipe || !cfg_in || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   *out = nullptr;
   d2fe_window_config cfg;
   d2fe_window_default_config(&cfg);
-  memcpy(&cfg, cfg_in, (size_t)std::min<int32_t>(cfg_in->struct_size > 0 ? cfg_in->struct_size : (int32_t)sizeof(cfg), (int32_t)sizeof(cfg)));
+  take_config(cfg, cfg_in);
   if (cfg.capacity < 1 || cfg.capacity > WIN_MAXKF || cfg.slots < 1 || cfg.slots > 64 || (cfg.mode != 0 && cfg.mode != 1) || cfg.max_queries < 1 || cfg.max_queries > WIN_MAXNQ)
     return ctx_fail(D2FE_ERR_INVALID, "bad window configuration");
   int pf = 0, pcap = 0, pdim = 0, pg = 0;
-  { const int rc = p ? d2fe_pipe_geometry(p, &pf, &pcap, &pdim, &pg) : d2fe_quad_pipe_geometry(qp, &pf, &pcap, &pdim, &pg); if (rc) return rc; }
+  { const int rc = pipe.geometry(&pf, &pcap, &pdim, &pg); if (rc) return rc; }
   if (pg <= 0) return ctx_fail(D2FE_ERR_INVALID, "the keyframe window needs the pipe's NetVLAD (netvlad = 1)");
   if ((pg & 3) || (pdim & 3)) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the NetVLAD and descriptor lengths must be multiples of 4");
   auto* x = new (std::nothrow) d2fe_window_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_window_s* x; bool ok = false; ~Guard() { if (!ok) window_destroy(x); } } guard{x};
-  x->p = p; x->qp = qp; x->h = p ? d2fe_pipe_handle(p) : d2fe_quad_handle(qp); x->cfg = cfg;
-  x->F = pf; x->cap = pcap; x->D = pdim; x->G = pg; x->V = p ? 1 : 4; x->NQ = cfg.max_queries;
+  x->pipe = pipe; x->h = pipe.handle(); x->cfg = cfg;
+  x->F = pf; x->cap = pcap; x->D = pdim; x->G = pg; x->V = pipe.views(); x->NQ = cfg.max_queries;
   const int V = x->V, NQ = x->NQ, K = cfg.capacity;
   x->slot_tag.assign(K, -1);
   for (int s = K - 1; s >= 0; --s) x->free_slots.push_back(s);      // slot 0 is taken first
@@ -252,12 +246,8 @@ int window_create(d2fe_pipe p, d2fe_quad_pipe qp, const d2fe_window_config* cfg_
   x->out_words = win_layout(NQ, V, pcap, K).words;
   x->slots.resize(cfg.slots);
   for (auto& S : x->slots) {
-    HIP_TRY(hipMalloc(&S.d_out, sizeof(float) * x->out_words)); HIP_TRY(hipMemset(S.d_out, 0, sizeof(float) * x->out_words));
+    { const int rc = S.alloc(x->out_words, x->out_words, cfg.timing != 0); if (rc) return rc; }
     HIP_TRY(hipMalloc(&S.d_pairs, sizeof(MatchPairDesc) * (size_t)NQ * V));
-    HIP_TRY(hipHostMalloc(&S.pin, sizeof(float) * x->out_words, hipHostMallocDefault));
-    memset(S.pin, 0, sizeof(float) * x->out_words);
-    if (cfg.timing) for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
   }
   HIP_TRY(hipDeviceSynchronize());
   guard.ok = true;
@@ -295,11 +285,11 @@ void d2fe_window_default_config(d2fe_window_config* c) {
 
 int d2fe_window_create(d2fe_pipe p, const d2fe_window_config* cfg, d2fe_window* out) {
   if (!p) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  return window_create(p, nullptr, cfg, out);
+  return window_create(p, cfg, out);
 }
 int d2fe_window_create_quad(d2fe_quad_pipe p, const d2fe_window_config* cfg, d2fe_window* out) {
   if (!p) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  return window_create(nullptr, p, cfg, out);
+  return window_create(p, cfg, out);
 }
 void d2fe_window_destroy(d2fe_window x) { window_destroy(x); }
 void* d2fe_window_stream(d2fe_window x) { return x ? x->st : nullptr; }
@@ -345,34 +335,18 @@ int d2fe_window_push(d2fe_window x, int64_t ticket, int frame, int64_t tag) {
   { const int c = window_push_check(x, tag); if (c) return c < 0 ? c : D2FE_OK; }
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
   hipStream_t st = x->st;
-  const float *nv = nullptr, *desc = nullptr; const int32_t* nkp = nullptr;
-  int vf = 0, vcap = 0, vd = 0, vg = 0;
-  if (x->p) {
-    d2fe_pipe_device_result v{};
-    const int rc = d2fe_pipe_device_view(x->p, ticket, st, &v);
-    if (rc) return rc;
-    nv = v.d_netvlad; desc = v.d_desc; nkp = v.d_n_kp; vf = v.frames; vcap = v.cap; vd = v.desc_dim; vg = v.netvlad_dim;
-  } else {
-    d2fe_quad_device_result v{};
-    const int rc = d2fe_quad_device_view(x->qp, ticket, st, &v);
-    if (rc) return rc;
-    nv = v.d_netvlad; desc = v.d_desc; nkp = v.d_n_kp; vf = v.quads; vcap = v.cap; vd = v.desc_dim; vg = v.netvlad_dim;
-  }
-  // from here on the view must be released whatever happens
   const int V = x->V, s = x->free_slots.back();
-  int rc = D2FE_OK;
-  if (vf != x->F || vcap != x->cap || vd != x->D || vg != x->G || !nv) rc = ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the keyframe window");
-  else {
+  const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
+    if (v.frames != x->F || v.cap != x->cap || v.desc_dim != x->D || v.netvlad_dim != x->G || !v.d_netvlad)
+      return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the keyframe window");
     const size_t row = (size_t)frame * V, blk = (size_t)x->cap * x->D;
     const int parts = (int)std::min<size_t>(16, std::max<size_t>(1, blk / 4096));
-    hipLaunchKernelGGL(window_copy_kernel, dim3((unsigned)V, (unsigned)parts), dim3(256), 0, st, nv + row * x->G, desc + row * blk, nkp + row,
+    hipLaunchKernelGGL(window_copy_kernel, dim3((unsigned)V, (unsigned)parts), dim3(256), 0, st, v.d_netvlad + row * x->G, v.d_desc + row * blk, v.d_n_kp + row,
                        x->d_nv + (size_t)s * V * x->G, x->d_desc + (size_t)s * V * blk, x->d_nkp + (size_t)s * V, x->G, x->cap, x->D);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = ctx_fail(D2FE_ERR_HIP, std::string("window_copy_kernel: ") + hipGetErrorString(e));
-  }
-  const int rr = x->p ? d2fe_pipe_device_release(x->p, ticket, st) : d2fe_quad_device_release(x->qp, ticket, st);
+    return e != hipSuccess ? ctx_fail(D2FE_ERR_HIP, std::string("window_copy_kernel: ") + hipGetErrorString(e)) : D2FE_OK;
+  });
   if (rc) return rc;
-  if (rr) return rr;
   window_commit(x, tag);
   return D2FE_OK;
 }
@@ -426,24 +400,20 @@ int d2fe_window_track_device(d2fe_window x, const float* d_netvlad, size_t nv_st
   a.best = x->d_best; a.ticket = x->d_state + 1; a.zero = x->d_state; a.pairs = S.d_pairs;
   a.o_tag = reinterpret_cast<int64_t*>(O + lay.tag); a.o_pos = O + lay.pos; a.o_da = O + lay.da; a.o_db = O + lay.db; a.o_sim = S.d_out + lay.sim; a.o_sims = S.d_out + lay.sims;
   a.o_lv = O + lay.lv; a.o_rv = O + lay.rv;
-  const bool tm = x->cfg.timing != 0;
-  if (tm) HIP_TRY(hipEventRecord(S.ev[0], st));
+  auto mark = [&](int i) { return S.mark(i, st); };
+  int r = mark(0); if (r) return r;
   const unsigned nwg = (unsigned)std::max<long>(1, ((long)nq * n + 3) / 4);
   if (V == 4) hipLaunchKernelGGL(window_gate_kernel<4>, dim3(nwg), dim3(256), 0, st, a, w);
   else hipLaunchKernelGGL(window_gate_kernel<1>, dim3(nwg), dim3(256), 0, st, a, w);
   HIP_TRY(hipGetLastError());
-  if (tm) HIP_TRY(hipEventRecord(S.ev[1], st));
+  r = mark(1); if (r) return r;
   MatchArgs m{};
   m.pairs = S.d_pairs; m.npairs = nq * V; m.dim = x->D; m.max_n = x->cap; m.mode = x->cfg.mode; m.ratio = x->cfg.ratio; m.radius = -1.0;
-  m.q_idx = O + lay.mq; m.t_idx = O + lay.mt; m.dist = S.d_out + lay.md; m.n_out = O + lay.mn;
-  match_scratch_carve(x->d_match_scratch, x->NQ * V, &m);
-  m.stats = x->h->match_stats; m.ncu = x->h->ncu;
+  match_outputs(m, O + lay.mq, O + lay.mt, S.d_out + lay.md, O + lay.mn, x->d_match_scratch, x->NQ * V, x->h);
   HIP_TRY(launch_match(m, st));
-  if (tm) HIP_TRY(hipEventRecord(S.ev[2], st));
-  HIP_TRY(hipMemcpyAsync(S.pin, S.d_out, sizeof(float) * lay.words, hipMemcpyDeviceToHost, st));
-  if (tm) HIP_TRY(hipEventRecord(S.ev[3], st));
-  HIP_TRY(hipEventRecord(S.done, st));
-  S.busy = true; S.nq = nq; S.n_window = n; S.lay = lay;
+  r = mark(2); if (r) return r;
+  r = S.finish(st, lay.words, 3); if (r) return r;      // the words in use: the D2H carries what the query wrote and nothing else
+  S.nq = nq; S.n_window = n; S.lay = lay;
   return D2FE_OK;
 }
 
@@ -452,7 +422,7 @@ int d2fe_window_collect(d2fe_window x, int slot, d2fe_window_result* out) {
   auto& S = x->slots[slot];
   if (!S.busy) return ctx_fail(D2FE_ERR_INVALID, "nothing was queued on this slot");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
-  HIP_TRY(hipEventSynchronize(S.done));
+  { const int rc = S.collect_begin(); if (rc) return rc; }
   memset(out, 0, sizeof(*out));
   const int32_t* I = reinterpret_cast<const int32_t*>(S.pin);
   const auto& l = S.lay;
@@ -460,9 +430,7 @@ int d2fe_window_collect(d2fe_window x, int slot, d2fe_window_result* out) {
   out->keyframe_tag = reinterpret_cast<const int64_t*>(I + l.tag); out->keyframe_pos = I + l.pos; out->dir_a = I + l.da; out->dir_b = I + l.db;
   out->sim = S.pin + l.sim; out->sims = S.pin + l.sims; out->local_view = I + l.lv; out->remote_view = I + l.rv; out->n_match = I + l.mn;
   out->q_idx = I + l.mq; out->t_idx = I + l.mt; out->dist = S.pin + l.md;
-  if (x->cfg.timing)
-    for (int i = 0; i < 3; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, S.ev[i], S.ev[i + 1]) == hipSuccess) out->phase_ms[i] = ms; }
-  S.busy = false;
+  S.phase_ms(out->phase_ms, 3);
   return D2FE_OK;
 }
 

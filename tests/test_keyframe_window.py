@@ -5,7 +5,8 @@
   (b) the threshold itself, in exact arithmetic;
   (c) behind a stereo pipe and a quad pipe: push / retain over several tickets, later tickets tracked in place through the device view and as dense uploads, both
       bitwise equal to the host composition of the existing calls; then one-rank loopback exchanges (fp32 and int8 wire) read in place through track_exchange;
-  (d) the refusals, each leaving the window as it was."""
+  (d) the refusals, each leaving the window as it was;
+  (e) a configuration struct cut short by its struct_size."""
 import ctypes as C
 
 import numpy as np
@@ -464,3 +465,29 @@ def test_window_refusals_leave_the_window_unchanged():
     for t in range(1, 7):                                                      # 2 * lanes + 2 more passes: a view left unreleased by a refusal would refuse one of these
         pipe.wait(pipe.submit(fr[t][0][None], fr[t][1][None]))
     win.close(); pipe.close(); fe.close()
+
+
+# ---- (e) an older caller's shorter configuration struct --------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_a_config_cut_short_by_struct_size_keeps_the_defaults_behind_it():
+    """d2fe_window_create copies min(struct_size, sizeof) bytes of the caller's struct over the defaults: a caller whose struct ends in front of `slots` gets the
+    default four slots, whatever lies in the memory behind its struct (here slots = 0, which a full-size struct is refused for)."""
+    api, fe = _stereo_fe(2)
+    pipe = api.StereoPipe(fe, lanes=2, frames=1, width=W, height=H, cap=CAP, netvlad=True)
+    lib = pipe._lib
+    c = api._WindowConfig()
+    lib.d2fe_window_default_config(C.byref(c))
+    c.slots = 0
+    x = C.c_void_p()
+    with pytest.raises(api.D2FEError, match="bad window configuration"):      # the whole struct is read: slots = 0 is refused
+        api._check(lib.d2fe_window_create(pipe._p, C.byref(c), C.byref(x)))
+    assert not x.value
+    c.struct_size = api._WindowConfig.slots.offset                             # the struct of a caller that does not know `slots`
+    api._check(lib.d2fe_window_create(pipe._p, C.byref(c), C.byref(x)))
+    res = api._WindowResult()
+    with pytest.raises(api.D2FEError, match="nothing was queued"):            # slot 3 exists: four slots
+        api._check(lib.d2fe_window_collect(x, 3, C.byref(res)))
+    with pytest.raises(api.D2FEError, match="bad argument"):                  # slot 4 does not
+        api._check(lib.d2fe_window_collect(x, 4, C.byref(res)))
+    lib.d2fe_window_destroy(x)
+    pipe.close(); fe.close()

@@ -4,8 +4,11 @@ sequence per ticket over a device-resident keyframe store.
       and d2fe_match_knn / d2fe_match_crosscheck;
   (b) behind a stereo pipe, (c) behind a quad pipe: every collected field bitwise against the host composition of the existing calls, frame by frame in causal
       order: d2fe_pipe_wait -> d2fe_db_query_gated -> d2fe_match_knn -> d2fe_db_add;
-  (d) the refusals, each leaving the store as it was.
+  (d) the refusals, each leaving the store as it was;
+  (e) a configuration struct cut short by its struct_size.
 The caller-side precondition of the reference, databaseSize() > match_index_dist (:157), is part of the query on both sides."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -420,3 +423,29 @@ def test_loop_query_refusals_leave_the_store_unchanged():
     for t in range(5, 11):                                                     # 2 * lanes + 2 more passes: a view left unreleased by a refusal would refuse one of these submits
         pipe.wait(sub(pipe, t))
     loop.close(); pipe.close(); fe.close()
+
+
+# ---- (e) an older caller's shorter configuration struct --------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_a_config_cut_short_by_struct_size_keeps_the_defaults_behind_it():
+    """d2fe_loop_create copies min(struct_size, sizeof) bytes of the caller's struct over the defaults: a caller whose struct ends in front of `slots` gets the
+    default four slots, whatever lies in the memory behind its struct (here slots = 0, which a full-size struct is refused for)."""
+    api, fe = _stereo_fe(2)
+    pipe = api.StereoPipe(fe, lanes=2, frames=1, width=W, height=H, cap=CAP, netvlad=True)
+    lib = pipe._lib
+    c = api._LoopConfig()
+    lib.d2fe_loop_default_config(C.byref(c))
+    c.slots = 0
+    x = C.c_void_p()
+    with pytest.raises(api.D2FEError, match="bad loop configuration"):        # the whole struct is read: slots = 0 is refused
+        api._check(lib.d2fe_loop_create(pipe._p, C.byref(c), C.byref(x)))
+    assert not x.value
+    c.struct_size = api._LoopConfig.slots.offset                               # the struct of a caller that does not know `slots`
+    api._check(lib.d2fe_loop_create(pipe._p, C.byref(c), C.byref(x)))
+    res = api._LoopResult()
+    with pytest.raises(api.D2FEError, match="nothing was enqueued"):          # slot 3 exists: four slots
+        api._check(lib.d2fe_loop_collect(x, 3, C.byref(res)))
+    with pytest.raises(api.D2FEError, match="bad argument"):                  # slot 4 does not
+        api._check(lib.d2fe_loop_collect(x, 4, C.byref(res)))
+    lib.d2fe_loop_destroy(x)
+    pipe.close(); fe.close()
