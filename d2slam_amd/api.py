@@ -43,7 +43,8 @@ class _Config(C.Structure):
                 ("max_height", C.c_int32), ("max_batch", C.c_int32), ("max_keypoints", C.c_int32),
                 ("remove_borders", C.c_int32), ("keypoint_threshold", C.c_float), ("postproc", C.c_int32),
                 ("nms_dist", C.c_int32), ("precision", C.c_int32), ("keep_score_map", C.c_int32),
-                ("dense_descriptors", C.c_int32), ("async_tail", C.c_int32), ("reserved", C.c_int32 * 5)]
+                ("dense_descriptors", C.c_int32), ("async_tail", C.c_int32), ("reserved", C.c_int32 * 5),
+                ("exact_order", C.c_int32), ("exact_order_eps", C.c_float), ("exact_order_crops", C.c_int32)]
 
 
 class _ConvParams(C.Structure):
@@ -217,7 +218,7 @@ EXPORTS = [
     "d2fe_quad_gate_device", "d2fe_block_bytes_int8", "d2fe_pack_blocks_int8_device", "d2fe_unpack_blocks_int8_device", "d2fe_half_move_cols",
     "d2fe_half_image_compact_device", "d2fe_remap_matches_device", "d2fe_half_image_filter", "d2fe_undistort", "d2fe_undistort_device",
     "d2fe_db_create", "d2fe_db_destroy", "d2fe_db_ntotal", "d2fe_db_add", "d2fe_db_search", "d2fe_db_query_gated", "d2fe_quantize_int8",
-    "d2fe_dequantize_int8", "d2fe_sync", "d2fe_profile_enable", "d2fe_profile_read", "d2fe_prepare_gray", "d2fe_prepare_gray_device",
+    "d2fe_dequantize_int8", "d2fe_sync", "d2fe_exact_order_stats", "d2fe_profile_enable", "d2fe_profile_read", "d2fe_prepare_gray", "d2fe_prepare_gray_device",
     "d2fe_gen_cylinder_map", "d2fe_gen_cylinder_map_device", "d2fe_gen_pinhole_map", "d2fe_gen_pinhole_map_device", "d2fe_lk_frame_create",
     "d2fe_lk_frame_create_device", "d2fe_lk_frame_destroy", "d2fe_lk_frame_read_level", "d2fe_lk_track", "d2fe_lk_track_batch",
     "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
@@ -324,6 +325,7 @@ def _open_library(path, dev):
         lib.d2fe_destroy.argtypes = [C.c_void_p]
         lib.d2fe_load_superpoint.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_sync.argtypes = [C.c_void_p]
+        lib.d2fe_exact_order_stats.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_match_fallback_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.d2fe_match_fallback_rows.restype = C.c_long
         lib.d2fe_tail_stream.argtypes = [C.c_void_p]
@@ -518,8 +520,10 @@ class SuperPointConfig:
 class FrontEnd:
     """One device context (== one LoopCam's networks, loop_cam.cpp:24-70)."""
 
-    def __init__(self, cfg: SuperPointConfig, dev: bool = False):
-        """dev=True: a handle of the development library (d2fe_debug_* hooks, D2FE_* schedule switches); the product library otherwise."""
+    def __init__(self, cfg: SuperPointConfig, dev: bool = False, exact_order: bool = False, exact_order_eps: float = 0.0, exact_order_crops: int = 0):
+        """dev=True: a handle of the development library (d2fe_debug_* hooks, D2FE_* schedule switches); the product library otherwise.
+        exact_order (PREC_F32_WINO, variant B, max_keypoints >= 1): the keypoint lists equal those of a PREC_F32 handle position by position
+        (include/d2fe.h, d2fe_config::exact_order); exact_order_eps / exact_order_crops: 0 = the library defaults.  Pipes created from the handle inherit it."""
         lib = load_library(dev)
         self.dev = bool(dev)
         c = _Config()
@@ -537,6 +541,9 @@ class FrontEnd:
         c.keep_score_map = int(cfg.keep_score_map)
         c.dense_descriptors = int(cfg.dense_descriptors)
         c.async_tail = int(cfg.async_tail)
+        c.exact_order = int(bool(exact_order))
+        c.exact_order_eps = float(exact_order_eps)
+        c.exact_order_crops = int(exact_order_crops)
         self.cfg = cfg
         self._h = C.c_void_p()
         _check(lib.d2fe_create(C.byref(c), C.byref(self._h)))
@@ -684,6 +691,12 @@ class FrontEnd:
 
     def sync(self):
         _check(self._lib.d2fe_sync(self._h))
+
+    def exact_order_stats(self):
+        """Cumulative exact_order counters of the handle and its pipe lanes: dict(marked, cells, dropped, calls); zeros when the option is off."""
+        v = (C.c_int64 * 4)()
+        _check(self._lib.d2fe_exact_order_stats(self._h, v))
+        return dict(marked=int(v[0]), cells=int(v[1]), dropped=int(v[2]), calls=int(v[3]))
 
     def profile_enable(self, mode):
         """0 off, 1 dominant kernel (conv1b) only, 2 every stage (HIP events on the launch stream)."""

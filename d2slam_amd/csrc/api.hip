@@ -140,6 +140,54 @@ void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool
   }
 }
 
+
+// exact_order (exact_order.hip), between the candidate emission and the selection, on the tail's stream: mark -> slots + crops -> the crop batch through the
+// exact mode's launches (conv1a|conv1b .. conv4b, convPa, convPb, softmax into a dense 88x88 score map per crop) -> patch.  A fixed number of fixed-shape
+// launches: crop slots nobody got run on whatever they held, their scores are never read
+static int run_exact_order(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, int cap, hipStream_t s) {
+  const int C = h->eo_slots, E = 88, E2 = 44, E4 = 22, Ec = 11;
+  const float thr = h->cfg.keypoint_threshold;
+  const int K = h->cfg.max_keypoints < cap ? h->cfg.max_keypoints : cap;
+  HIP_TRY(launch_exact_order_mark(h->cand, h->cand_count, h->cand_cap, n, W, H, K, thr, h->eo_eps, C, h->eo_cell_map, h->eo_cell_list, h->eo_cell_count,
+                                  h->eo_stats, s));
+  HIP_TRY(launch_exact_order_gather(d_gray, stride, (long)image_stride, n, W, H, h->eo_cell_list, h->eo_cell_count, C, h->eo_crops, h->eo_stats, s));
+  // the crop batch's activations, per crop: a1b 44*44*64 | a2a 44*44*64 | a2b 22*22*64 | a3a 22*22*128 | a3b, a4a, a4b 11*11*128 | aP 11*11*256 | logits 121*65 | scores 88*88
+  float* a1b = h->eo_act;
+  float* a2a = a1b + (size_t)C * E2 * E2 * 64;
+  float* a2b = a2a + (size_t)C * E2 * E2 * 64;
+  float* a3a = a2b + (size_t)C * E4 * E4 * 64;
+  float* a3b = a3a + (size_t)C * E4 * E4 * 128;
+  float* a4a = a3b + (size_t)C * Ec * Ec * 128;
+  float* a4b = a4a + (size_t)C * Ec * Ec * 128;
+  float* aP = a4b + (size_t)C * Ec * Ec * 128;
+  float* lg = aP + (size_t)C * Ec * Ec * 256;
+  float* sc = lg + (size_t)C * Ec * Ec * 65;
+  auto conv = [&](ConvShape shape, const Layer& L, const float* in, int ics, long iis, float* out, int ocs, long ois, int hh, int ww, bool pool, bool relu) -> hipError_t {
+    ConvArgs a;
+    a.in = in; a.in_cstride = ics; a.in_coff = 0;
+    a.out = out; a.out_cstride = ocs; a.out_coff = 0;
+    a.cout_real = L.cout; a.wpack = L.wpack; a.bias = L.bias;
+    a.img = h->eo_crops; a.img_stride = E; a.img_istride = (long)E * E; a.w1a = h->w1a; a.b1a = h->b1a;
+    a.H = hh; a.W = ww; a.n_img = C; a.in_img_stride = iis; a.out_img_stride = ois; a.zeros = h->zeros; a.ncu = h->ncu;
+    a.tag = 0; a.ablate = 0; a.work_ctr = nullptr;
+    if (shape == CONV_256_1x1_T4x16) { const hipError_t e = launch_conv1x1_256_65(a, s); if (e != hipErrorNotSupported) return e; }     // convPb: same bits either way
+    return launch_conv(shape, D2FE_PREC_F32, pool, relu, L.cout_pad, a, s);
+  };
+  HIP_TRY(conv(CONV1B_FUSED, h->L[L_X1B], nullptr, 64, 0, a1b, 64, (long)E2 * E2 * 64, E, E, true, true));
+  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X2A], a1b, 64, (long)E2 * E2 * 64, a2a, 64, (long)E2 * E2 * 64, E2, E2, false, true));
+  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X2B], a2a, 64, (long)E2 * E2 * 64, a2b, 64, (long)E4 * E4 * 64, E2, E2, true, true));
+  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X3A], a2b, 64, (long)E4 * E4 * 64, a3a, 128, (long)E4 * E4 * 128, E4, E4, false, true));
+  HIP_TRY(conv(CONV_128_T4x32, h->L[L_X3B], a3a, 128, (long)E4 * E4 * 128, a3b, 128, (long)Ec * Ec * 128, E4, E4, true, true));
+  HIP_TRY(conv(CONV_128_T4x16, h->L[L_X4A], a3b, 128, (long)Ec * Ec * 128, a4a, 128, (long)Ec * Ec * 128, Ec, Ec, false, true));
+  HIP_TRY(conv(CONV_128_T4x16, h->L[L_X4B], a4a, 128, (long)Ec * Ec * 128, a4b, 128, (long)Ec * Ec * 128, Ec, Ec, false, true));
+  HIP_TRY(conv(CONV_128_T4x16, h->L[L_XPA], a4b, 128, (long)Ec * Ec * 128, aP, 256, (long)Ec * Ec * 256, Ec, Ec, false, true));
+  HIP_TRY(conv(CONV_256_1x1_T4x16, h->L[L_PB], aP, 256, (long)Ec * Ec * 256, lg, 65, (long)Ec * Ec * 65, Ec, Ec, false, false));
+  // dense score map only: an infinite threshold emits no candidate and touches no counter
+  HIP_TRY(launch_softmax_cand(lg, 65, Ec, Ec, C, INFINITY, 0, sc, nullptr, h->eo_cell_count, 0, false, s));
+  HIP_TRY(launch_exact_order_patch(h->cand, h->cand_count, h->cand_cap, n, W, H, thr, h->eo_cell_map, h->eo_cell_count, C, sc, s));
+  return D2FE_OK;
+}
+
 // the launch sequence == one TensorRT executeV2 + processOutput of the reference
 int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride,
                    float* d_kps, float* d_scores, float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s,
@@ -219,8 +267,9 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
     HIP_TRY(hipStreamWaitEvent(s_tail, h->ev_trunk[bs], 0));
     s = s_tail;
   }
+  const bool eo = h->eo_slots > 0 && !varA;      // exact_order: candidates down to thr - eps, the uncertain cells re-evaluated with the direct chains
   { ProfScope ps(h, D2FE_PROF_SOFTMAX, s);
-  HIP_TRY(launch_softmax_cand(logits.p, 65, Hc, Wc, n, h->cfg.keypoint_threshold, h->cfg.remove_borders,
+  HIP_TRY(launch_softmax_cand(logits.p, 65, Hc, Wc, n, eo ? h->cfg.keypoint_threshold - h->eo_eps : h->cfg.keypoint_threshold, h->cfg.remove_borders,
                               (h->cfg.keep_score_map || varA || h->cfg.max_keypoints < 0) ? h->semi.p : nullptr,
                               h->cand, h->cand_count, varA ? 0 : h->cand_cap, /*zero_counts=*/tail_elsewhere, s)); }
   if (varA) {
@@ -235,6 +284,7 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
       HIP_TRY(launch_nms2_wrap_fix(h->clist, h->a_ncand, H, W, n, d_kps, d_idx, d_n, cap, s));
   } else {
     ProfScope ps(h, D2FE_PROF_SELECT, s);
+    if (eo) { const int rc = run_exact_order(h, d_gray, n, W, H, stride, image_stride, cap, s); if (rc) return rc; }
     // raster indices and keypoints are in score-map coordinates: (W/8)*8 wide.  Keep-all handles also hand over the dense score map:
     // more keypoints than the in-LDS sort takes are compacted from it in raster order (any count up to the call's capacity)
     HIP_TRY(launch_select_b(h->cand, h->cand_count, h->cand_cap, n, Wc * 8, h->cfg.max_keypoints, cap, 0,
@@ -277,6 +327,8 @@ int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap) {
   // describes the network output for multiples of 8.
   if (((W | H) & 7) && h->cfg.postproc == D2FE_POSTPROC_A)
     return fail(D2FE_ERR_INVALID, "post-processing variant A needs image sizes that are multiples of 8");
+  if (h->eo_slots > 0 && (W < 88 || H < 88 || ((W | H) & 7)))
+    return fail(D2FE_ERR_INVALID, "exact_order needs images of at least 88x88 whose width and height are multiples of 8 (the 88x88 crops share the full image's pool grids)");
   if (stride < W) return fail(D2FE_ERR_INVALID, "stride < width");
   if (cap < 1) return fail(D2FE_ERR_INVALID, "cap < 1");
   return D2FE_OK;
@@ -310,10 +362,17 @@ void d2fe_default_config(d2fe_config* c) {
 namespace d2fe {
 // lane = a context cloned for a pipe (clone_lane): no host-pointer staging (frame upload buffer, output block, pinned mirrors) -- a lane is only ever
 // driven through run_superpoint / run_netvlad on device buffers of the pipe
-static int create_context(const d2fe_config* cfg, d2fe_handle* out, bool lane, hipStream_t adopt = nullptr) {
-  if (!cfg || !out) return fail(D2FE_ERR_INVALID, "null argument");
+static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane, hipStream_t adopt = nullptr) {
+  if (!cfg_in || !out) return fail(D2FE_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (cfg->struct_size != (int32_t)sizeof(d2fe_config)) return fail(D2FE_ERR_INVALID, "d2fe_config size mismatch");
+  // two struct versions: the one that ends behind `reserved` (the exact_order fields are then zero: off) and the current one
+  if (cfg_in->struct_size != (int32_t)sizeof(d2fe_config) && cfg_in->struct_size != (int32_t)offsetof(d2fe_config, exact_order))
+    return fail(D2FE_ERR_INVALID, "d2fe_config size mismatch");
+  d2fe_config cfg_full;
+  memset(&cfg_full, 0, sizeof(cfg_full));
+  memcpy(&cfg_full, cfg_in, (size_t)cfg_in->struct_size);
+  cfg_full.struct_size = (int32_t)sizeof(d2fe_config);
+  const d2fe_config* cfg = &cfg_full;
   if (!(cfg->keypoint_threshold >= 0.f)) return fail(D2FE_ERR_INVALID, "keypoint_threshold must be >= 0 (scores are probabilities)");
   if (cfg->max_width < 16 || cfg->max_height < 16) return fail(D2FE_ERR_INVALID, "max_width/max_height must be at least 16");
   if (cfg->max_batch < 1) return fail(D2FE_ERR_INVALID, "max_batch < 1");
@@ -325,6 +384,14 @@ static int create_context(const d2fe_config* cfg, d2fe_handle* out, bool lane, h
   if ((cfg->max_keypoints < 1 && cfg->max_keypoints != -1) || cfg->max_keypoints > 16384) return fail(D2FE_ERR_INVALID, "max_keypoints must be -1 (keep all) or in 1..16384");
   if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "bad precision");
   if (cfg->postproc != D2FE_POSTPROC_B && cfg->postproc != D2FE_POSTPROC_A) return fail(D2FE_ERR_INVALID, "bad postproc");
+  if (cfg->exact_order) {
+    if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2 is not supported)");
+    if (cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "exact_order needs post-processing variant B (NMS2 of variant A depends on the order in another way)");
+    if (cfg->max_keypoints < 1) return fail(D2FE_ERR_INVALID, "exact_order needs max_keypoints >= 1 (keep-all handles are not supported)");
+    if (!(cfg->exact_order_eps >= 0.f) || std::isinf(cfg->exact_order_eps)) return fail(D2FE_ERR_INVALID, "exact_order_eps must be finite and >= 0 (0 = the default)");
+    if (cfg->exact_order_crops < 0 || cfg->exact_order_crops > 65535) return fail(D2FE_ERR_INVALID, "exact_order_crops must be in 0..65535 (0 = the default)");
+    if (cfg->max_width < 88 || cfg->max_height < 88) return fail(D2FE_ERR_INVALID, "exact_order needs max_width and max_height of at least 88");
+  }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (ndev < 1) return fail(D2FE_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
@@ -398,6 +465,22 @@ static int create_context(const d2fe_config* cfg, d2fe_handle* out, bool lane, h
       HIP_TRY(hipMalloc(&h->a_samp, sizeof(float) * 256 * (size_t)h->a_scap * B));
       HIP_TRY(hipMalloc(&h->a_cn, sizeof(float) * 256 * B));
     }
+    if (cfg->exact_order) {
+      // measured: max |Winograd score - direct score| over the pixels with a direct score > thr / 2; the default is 4x that, one digit
+      h->eo_eps = cfg->exact_order_eps > 0.f ? cfg->exact_order_eps : 9e-6f;
+      // default crop slots: the smallest count in steps of max_batch / 2 at which the 1056-image study (32 images per call, N = 200) drops no cell is 66.5 per image
+      // (2121 cells in its fullest call); at least 136 (134 cells in its fullest image) so that a one-image call drops none either
+      const int C = cfg->exact_order_crops > 0 ? cfg->exact_order_crops : std::max((133 * B + 1) / 2, 136);
+      const size_t ncell = (H / 8) * (W / 8);
+      HIP_TRY(hipMalloc(&h->eo_crops, (size_t)C * 88 * 88));
+      HIP_TRY(hipMemset(h->eo_crops, 0, (size_t)C * 88 * 88));
+      HIP_TRY(hipMalloc(&h->eo_cell_map, sizeof(int) * ncell * B));
+      HIP_TRY(hipMalloc(&h->eo_cell_list, sizeof(int) * (size_t)C * B));
+      HIP_TRY(hipMalloc(&h->eo_cell_count, sizeof(int) * B));
+      HIP_TRY(hipMalloc(&h->eo_act, sizeof(float) * (size_t)C * (2 * 44 * 44 * 64 + 22 * 22 * 64 + 22 * 22 * 128 + 3 * 121 * 128 + 121 * 256 + 121 * 65 + 88 * 88)));
+      if (!lane) { HIP_TRY(hipMalloc(&h->eo_stats, 4 * sizeof(unsigned long long))); HIP_TRY(hipMemset(h->eo_stats, 0, 4 * sizeof(unsigned long long))); }
+      h->eo_slots = C;
+    }
     h->use_graphs = d2fe_dev_env("D2FE_GRAPH", 1) != 0;
     if (lane) { h->use_pinned = false; return D2FE_OK; }
     h->s_cap = h->cfg.max_keypoints > 1024 ? h->cfg.max_keypoints : 1024;      // initial staging capacity per image; grows with the calls (ensure_staging)
@@ -447,7 +530,9 @@ void d2fe_destroy(d2fe_handle h) {
   }
   for (void* p : {(void*)h->cand, (void*)h->s_img, (void*)h->aconf, (void*)h->clist, (void*)h->a_ncand, (void*)h->a_samp, (void*)h->a_cn, h->lk_scratch, (void*)h->zeros, (void*)h->work_ctrs, (void*)h->match_stats, (void*)h->match_stamps, (void*)h->sp_flags, (void*)h->sp_slotmap, (void*)h->sp_cells, (void*)h->sp_count, (void*)h->sp_desc, (void*)h->sp_mid})
     if (p) hipFree(p);
-  for (void* p : {(void*)h->nv_s_img, (void*)h->nv_s_out}) if (p) hipFree(p);
+  for (void* p : {(void*)h->nv_s_img, (void*)h->nv_s_out, (void*)h->eo_crops, (void*)h->eo_cell_map, (void*)h->eo_cell_list, (void*)h->eo_cell_count, (void*)h->eo_act})
+    if (p) hipFree(p);
+  if (h->eo_stats && !h->borrowed) hipFree(h->eo_stats);
   for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
   if (h->nv_stream) { hipStreamSynchronize(h->nv_stream); (void)hipStreamDestroy(h->nv_stream); }
   if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -504,6 +589,11 @@ int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
     rc = rc ? rc : pack_layer(h, h->L[L_PA], {&l[8]}, 256);
     rc = rc ? rc : pack_layer(h, h->L[L_DA32], {&l[10]}, 256, true);
     rc = rc ? rc : pack_layer(h, h->L[L_DB32], {&l[11]}, 256, true);
+  }
+  if (h->eo_slots > 0) {     // exact_order: the detector path once more as direct fp32 fragments (convPb is direct in every fp32 mode)
+    static const int xl[8] = {L_X1B, L_X2A, L_X2B, L_X3A, L_X3B, L_X4A, L_X4B, L_XPA};
+    static const int xpad[8] = {64, 64, 64, 128, 128, 128, 128, 256};
+    for (int i = 0; i < 8; ++i) rc = rc ? rc : pack_layer(h, h->L[xl[i]], {&l[1 + i]}, xpad[i], true);
   }
   if (rc) return rc;
   h->sp_loaded = true;
@@ -753,6 +843,7 @@ int clone_lane(d2fe_context* p, int max_batch, d2fe_context** out, hipStream_t s
   c->sp_loaded = p->sp_loaded;
   c->pca_comp_t = p->pca_comp_t; c->pca_mean = p->pca_mean; c->pca_dims = p->pca_dims;
   c->fuse1a = p->fuse1a; c->wino_dynamic = p->wino_dynamic; c->sp_min_batch = p->sp_min_batch;
+  c->eo_stats = p->eo_stats;      // one set of exact_order counters per parent handle
   if (p->nv_net && with_netvlad) {
     // the network is shared; the activations are the lane's own (no nv_s_img / nv_s_out: the host-pointer NetVLAD calls never run on a lane)
     c->nv_net = p->nv_net;
@@ -1503,6 +1594,18 @@ long d2fe_match_fallback_rows(d2fe_handle h, int reset, long* full_scans) {
   if (reset) { HIP_TRY(hipMemset(h->match_stats, 0, sizeof(v))); HIP_TRY(hipDeviceSynchronize()); }
   if (full_scans) *full_scans = v[0];
   return v[1];
+}
+
+int d2fe_exact_order_stats(d2fe_handle h, int64_t out[4]) {
+  if (!h || !out) return fail(D2FE_ERR_INVALID, "null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!h->eo_stats) return D2FE_OK;
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  HIP_TRY(hipDeviceSynchronize());      // the handle's streams and those of every lane that counts into the same buffer
+  unsigned long long v[4];
+  HIP_TRY(hipMemcpy(v, h->eo_stats, sizeof(v), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
+  return D2FE_OK;
 }
 
 int d2fe_sync(d2fe_handle h) {

@@ -36,7 +36,9 @@ struct Layer {
   int cout = 0, cout_pad = 0, cin = 0, ks = 0;
 };
 
-enum { L_1B = 0, L_2A, L_2B, L_3A, L_3B, L_4A, L_4B, L_PADA, L_PB, L_DB, L_PA, L_DA32, L_DB32, L_COUNT };   // the last three: sparse descriptor head
+enum { L_1B = 0, L_2A, L_2B, L_3A, L_3B, L_4A, L_4B, L_PADA, L_PB, L_DB, L_PA, L_DA32, L_DB32,      // the last three: sparse descriptor head
+       L_X1B, L_X2A, L_X2B, L_X3A, L_X3B, L_X4A, L_X4B, L_XPA,     // exact_order: direct fp32 packings of the eight Winograd layers of the detector path
+       L_COUNT };
 
 struct Tensor {
   float* p = nullptr;
@@ -166,6 +168,11 @@ struct d2fe_context {
   bool sparse_desc = false; int sp_slots = 0; int sp_min_batch = 4;
   uint8_t* sp_flags = nullptr; int32_t* sp_slotmap = nullptr; int32_t* sp_cells = nullptr; int32_t* sp_count = nullptr; float* sp_desc = nullptr;
   float* sp_mid = nullptr; int sp_mid_imgs = 0;      // ReLU(convDa) at the selected cells between the two stages of the split sparse head (passes of <= 4 images)
+  // exact_order (exact_order.hip; cfg.exact_order): eo_slots crops of 88x88 per call through the direct kernels
+  int eo_slots = 0; float eo_eps = 0.f;
+  uint8_t* eo_crops = nullptr; int* eo_cell_map = nullptr; int* eo_cell_list = nullptr; int* eo_cell_count = nullptr;
+  float* eo_act = nullptr;           // the crop batch's activations, carved per layer in run_superpoint
+  unsigned long long* eo_stats = nullptr;      // [4] marked candidates, cells re-evaluated, cells dropped, calls: the parent handle's, shared with its lanes
   void* lk_scratch = nullptr; size_t lk_scratch_bytes = 0;   // grow-only scratch of the LK / detector entry points (lk.hip)
   float* a_samp = nullptr; float* a_cn = nullptr; int a_scap = 0;   // variant A sampling: [batch][a_scap][256] samples, [batch][256] channel norms
   float* pca_comp_t = nullptr; float* pca_mean = nullptr; int pca_dims = 0;

@@ -110,6 +110,18 @@ hipError_t launch_desc_head_sparse(const float* kps_xy, const int32_t* n_kp, int
                                    const float* b_db, uint8_t* flags, int32_t* slotmap, int32_t* cells, int32_t* count,
                                    int max_slots, float* out, float* mid, int mid_imgs, int img_w, int img_h, hipStream_t s);
 
+// ---- exact_order (exact_order.hip): the Winograd mode's keypoint list made equal to the exact mode's ------------------------
+// mark: one workgroup per image over the candidate keys (emitted with score > thr - eps): rule 3 of DESIGN.md section 2, the distinct 8x8 cells of the marked
+// candidates in sorted-list order.  cell_map [n_img][(H/8)*(W/8)], cell_list [n_img][slots], cell_count [n_img], stats [4] (marked, re-evaluated, dropped, calls)
+hipError_t launch_exact_order_mark(const unsigned long long* cand, const int* cand_count, long cand_cap, int n_img, int W, int H, int K, float thr, float eps,
+                                   int slots, int* cell_map, int* cell_list, int* cell_count, unsigned long long* stats, hipStream_t s);
+// gather: slot assignment (image order, then list order) and the 88x88 u8 crops [slots][88*88]; W, H multiples of 8 and >= 88
+hipError_t launch_exact_order_gather(const uint8_t* gray, int stride, long image_stride, int n_img, int W, int H, const int* cell_list, const int* cell_count,
+                                     int slots, uint8_t* crops, unsigned long long* stats, hipStream_t s);
+// patch: the crops' centre-cell scores (crop_scores [slots][88*88]) onto the candidates; candidates whose final score is not > thr leave the list
+hipError_t launch_exact_order_patch(unsigned long long* cand, int* cand_count, long cand_cap, int n_img, int W, int H, float thr, const int* cell_map,
+                                    const int* cell_count, int slots, const float* crop_scores, hipStream_t s);
+
 // variant A (SuperPointONNX path): NMS2-exact and grid_sampler(align_corners=false) sampling with optional PCA
 hipError_t launch_nms2_a(const float* semi, int H, int W, int n_img, float thr, int dist, float* aconf, int* clist,
                          unsigned long long* cand, int* cand_count, long cand_cap, int* ncand, hipStream_t s);

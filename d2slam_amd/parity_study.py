@@ -4,7 +4,10 @@ bench.py, which runs a 128-image subset of it inside every default run: `index_p
 Keypoint and match index sets of the Winograd fp32 mode (`value`) and of the fp16 hi/lo mode against the bitwise-exact direct-convolution fp32 mode on 640x480 frames:
 synthetic stereo pairs plus frames derived from the three real crops of the reference's sample_data/fisheye.jpg that tests/golden/reference_headline.npz carries (flips,
 mirror-padded re-crops, gain changes: real image statistics, no new reference content).  Pairs: synthetic L<->R, real frame <-> the frame shifted by (3, 5) px.
-Symmetric differences of raster-index sets (keypoints per image; matches per pair as (index, index) pairs)."""
+Symmetric differences of raster-index sets (keypoints per image; matches per pair as (index, index) pairs).
+
+order_study(): the ORDER-aware comparison (list positions, not sets) of the plain Winograd mode and of the Winograd mode with exact_order against the exact mode,
+the deviation of the Winograd score maps from the direct ones (what exact_order_eps has to bound) and what exact_order re-evaluates."""
 import os
 
 import numpy as np
@@ -88,3 +91,62 @@ def study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
             plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
             rec["%s_vs_f32_%s" % (name, part)] = compare(sel["f32"], sel[name], lo, hi, plo, phi)
     return rec
+
+
+def _lists_and_maps(api, imgs, thr, N, prec, batch, device_id=0, maps=True, **eo):
+    """per-image raster-index LISTS (in list order) of one mode and, with maps, its dense score maps [NI, H, W] (development library: keep_score_map + debug_read)"""
+    fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=N, input_width=W, input_height=H, max_batch=batch, precision=prec, keypoint_threshold=thr, device_id=device_id,
+                                           keep_score_map=maps), dev=maps, **eo)
+    fe.load_superpoint(weights_for(thr))
+    lists, semi = [], []
+    for i0 in range(0, len(imgs), batch):
+        chunk = imgs[i0:i0 + batch]
+        for k, s, d in fe.extract_batch(chunk, cap=N):
+            lists.append(k[:, 1].astype(np.int64) * W + k[:, 0].astype(np.int64))
+        if maps:
+            semi.append(fe.debug_read("semi", (batch, H, W))[:len(chunk)].copy())
+    stats = fe.exact_order_stats()
+    fe.close()
+    return lists, (np.concatenate(semi) if maps else None), stats
+
+
+def compare_order(ref, other):
+    """position-by-position comparison of per-image index lists against the reference mode's"""
+    pos = imgs_order = imgs_set = 0
+    differing = []
+    for i, (a, b) in enumerate(zip(ref, other)):
+        if len(a) == len(b) and np.array_equal(a, b):
+            continue
+        differing.append(i)
+        if set(a.tolist()) != set(b.tolist()):
+            imgs_set += 1
+        else:
+            imgs_order += 1
+        m = min(len(a), len(b))
+        pos += int((a[:m] != b[:m]).sum()) + abs(len(a) - len(b))
+    return {"keypoints": int(sum(len(a) for a in ref)), "positions_differing": pos, "images_with_an_order_difference_only": imgs_order,
+            "images_with_a_set_difference": imgs_set, "images_differing": differing}
+
+
+def order_study(api, imgs, thr, N, batch=32, device_id=0, eps=0.0, crops=0):
+    """one configuration on the GPU.  The reference of every figure is the exact mode (PREC_F32)."""
+    from d2slam_amd import exact_order as eo
+    l_d, s_d, _ = _lists_and_maps(api, imgs, thr, N, api.PREC_F32, batch, device_id)
+    l_w, s_w, _ = _lists_and_maps(api, imgs, thr, N, api.PREC_F32_WINO, batch, device_id)
+    l_x, _, st = _lists_and_maps(api, imgs, thr, N, api.PREC_F32_WINO, batch, device_id, maps=False, exact_order=True, exact_order_eps=eps, exact_order_crops=crops)
+    strong = s_d > np.float32(thr / 2)
+    dev = np.abs(s_w - s_d)
+    eps_used = eps if eps > 0 else eo.DEFAULT_EPS
+    marked, cells, per_call = [], [], []
+    for i in range(len(imgs)):
+        _, _, m, c = eo.mark(s_w[i], thr, 1, N, eps_used)
+        marked.append(int(m.sum())); cells.append(len(c))
+    for i0 in range(0, len(imgs), batch):
+        per_call.append(sum(cells[i0:i0 + batch]))
+    return {"threshold": thr, "max_keypoints": N, "images": len(imgs), "images_per_call": batch,
+            "score_deviation_max_where_direct_above_half_threshold": float(dev[strong].max()), "score_deviation_max_all_pixels": float(dev.max()),
+            "exact_order_eps": eps_used, "exact_order_crops": crops if crops > 0 else "default",
+            "wino_vs_f32": compare_order(l_d, l_w), "exact_order_vs_f32": compare_order(l_d, l_x),
+            "host_rule": {"marked_per_image_mean": float(np.mean(marked)), "marked_per_image_max": int(max(marked)), "cells_per_image_mean": float(np.mean(cells)),
+                          "cells_per_image_max": int(max(cells)), "cells_per_call_max": int(max(per_call))},
+            "device_stats": st}

@@ -46,7 +46,14 @@ typedef enum {
   D2FE_PREC_F16X2 = 1, /* fp16 hi/lo split operands, 3 x v_mfma_f32_32x32x16_f16, fp32 accumulate (~2^-22 rel.) */
   D2FE_PREC_F32_WINO = 2 /* fp32 throughout; the eight 3x3 layers with Cin >= 64 as Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32
                             (16 instead of 36 multiplies per output and channel pair).  Bitwise equal to the oracle's restatement
-                            of that evaluation order (orc_conv3x3_wino), ~1e-6 relative to the direct chains of D2FE_PREC_F32 */
+                            of that evaluation order (orc_conv3x3_wino), ~1e-6 relative to the direct chains of D2FE_PREC_F32.
+                            Keypoint lists are index-exact against THAT evaluation order only: scores closer than the deviation can swap list
+                            positions, or cross the threshold or the K-th score.  d2fe_config::exact_order (variant B, max_keypoints >= 1) removes
+                            that: count, kps_idx, kps_xy and the list order then equal D2FE_PREC_F32's position by position, PROVIDED
+                            exact_order_eps bounds |Winograd score - direct score| and d2fe_exact_order_stats reports no dropped cell.  It does NOT
+                            cover the descriptors (they stay the Winograd trunk's, <= 1e-5 from exact; matches whose near-ties follow from
+                            descriptor bits may differ), the scores of keypoints outside re-evaluated cells (Winograd bits), variant A,
+                            D2FE_PREC_F16X2 or keep-all handles. */
 } d2fe_precision;
 
 /* Mirrors SuperPointConfig (d2frontend/include/d2frontend/CNN/superpoint_tensorrt.h:17-33) plus the
@@ -77,6 +84,18 @@ typedef struct {
                                  convolutions of the next call; outputs are complete on the tail stream -- enqueue consumers there, or
                                  call d2fe_superpoint_wait_tail(h, stream).  Host-pointer calls are unaffected.  Default 0. */
   int32_t reserved[5];
+  /* -- appended fields: a caller that passes the struct_size of the struct above (up to and including `reserved`) gets zeros here -- */
+  int32_t exact_order;        /* 1 (D2FE_PREC_F32_WINO, variant B, max_keypoints >= 1 only; anything else: D2FE_ERR_INVALID): the keypoint list equals the
+                                 one a D2FE_PREC_F32 handle produces.  Candidates whose list position the Winograd deviation could change (within
+                                 exact_order_eps of the threshold, unless more than max_keypoints candidates lie clear above it; within 2 eps of a
+                                 neighbour in the part of the sorted list that can reach the top K)
+                                 have their 8x8 cell re-evaluated with the direct fmaf chains on an 88x88 crop of the frame; the selection then runs on the
+                                 patched list.  Images must be at least 88x88 with both sizes multiples of 8.  Default 0: nothing changes. */
+  float   exact_order_eps;    /* bound on |Winograd score - direct score|; 0 = the library default 9e-6 = 4 x the largest deviation measured (2.03e-6 over 1056 images at two thresholds, seeded weights).  Negative, NaN or infinite: D2FE_ERR_INVALID */
+  int32_t exact_order_crops;  /* crop slots per call (one per re-evaluated cell; granted in image order, within an image in sorted-list order; a cell
+                                 without a slot keeps its Winograd scores and is counted as dropped); 0 = max(66.5 * max_batch, 136): no drop in the 1056-image study.  EVERY slot
+                                 runs through the direct kernels in every call (1.7 MB of activations each): a smaller count is cheaper, and
+                                 d2fe_exact_order_stats tells whether it was enough */
 } d2fe_config;
 
 /* One conv layer in PyTorch layout: weight [cout][cin][k][k], bias [cout]. */
@@ -1095,6 +1114,9 @@ D2FE_API int d2fe_profile_read(d2fe_handle h, float* ms /*[D2FE_PROF_COUNT]*/, i
 
 /* Synchronise the handle's stream (for timing with device-resident calls). */
 D2FE_API int d2fe_sync(d2fe_handle h);
+/* exact_order counters since d2fe_create, over the handle and every pipe lane created from it: out[0] marked candidates, [1] cells re-evaluated,
+ * [2] cells dropped for lack of crop slots (the guarantee holds for calls that dropped none), [3] calls.  Synchronises the device.  Zeros when the option is off. */
+D2FE_API int d2fe_exact_order_stats(d2fe_handle h, int64_t out[4]);
 
 #ifdef __cplusplus
 }
