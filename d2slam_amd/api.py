@@ -25,7 +25,7 @@ if os.environ.get("D2FE_LIB"):      # developer knob: same-box A/B of two builds
     LIB_PATH = os.path.abspath(os.environ["D2FE_LIB"])
 
 POSTPROC_B, POSTPROC_A = 0, 1
-PREC_F32, PREC_F16X2, PREC_F32_WINO = 0, 1, 2
+PREC_F32, PREC_F16X2, PREC_F32_WINO, PREC_F16 = 0, 1, 2, 3
 ERR_TRUNCATED = -4            # d2fe_status: output capacity too small, n_out holds what was written
 KEEP_ALL_CAP = 1024           # host-pointer staging capacity of a keep-all handle (max_keypoints = -1)
 PROF_STAGES = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPaDa",

@@ -97,10 +97,14 @@ int pack_layer(d2fe_context* h, Layer& L, const std::vector<const d2fe_conv_para
     std::vector<float> pk(packed_weight_floats_wino(cout_pad, cin));
     pack_weights_wino(w.data(), cout, cin, cout_pad, pk.data());
     rc = upload(pk.data(), pk.size() * sizeof(float), &L.wpack);
-  } else if (h->cfg.precision != D2FE_PREC_F16X2 || force_f32) {
+  } else if ((h->cfg.precision != D2FE_PREC_F16X2 && h->cfg.precision != D2FE_PREC_F16) || force_f32) {
     std::vector<float> pk(packed_weight_floats_f32(cout_pad, cin, ks));
     pack_weights_f32(w.data(), cout, cin, ks, cout_pad, pk.data());
     rc = upload(pk.data(), pk.size() * sizeof(float), &L.wpack);
+  } else if (h->cfg.precision == D2FE_PREC_F16) {
+    std::vector<uint16_t> pk(packed_weight_halfs_f16(cout_pad, cin, ks));
+    pack_weights_f16(w.data(), cout, cin, ks, cout_pad, pk.data());
+    rc = upload(pk.data(), pk.size() * sizeof(uint16_t), &L.wpack);
   } else {
     std::vector<uint16_t> pk(packed_weight_halfs_f16x2(cout_pad, cin, ks));
     pack_weights_f16x2(w.data(), cout, cin, ks, cout_pad, pk.data());
@@ -218,7 +222,7 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
     a.tag = (&L == &h->L[L_1B]) ? 1 : 0;
     a.work_ctr = (prec == D2FE_PREC_F32_WINO && h->wino_dynamic) ? h->work_ctrs + (int)(&L - &h->L[0]) : nullptr;
     { static const int ab = d2fe_dev_env("D2FE_ABLATE", 0); a.ablate = ab; }
-    if (prec != D2FE_PREC_F16X2 && shape == CONV_256_1x1_T4x16 && L.cout == 65 && !pool && !relu) {      // convPb
+    if (prec != D2FE_PREC_F16X2 && prec != D2FE_PREC_F16 && shape == CONV_256_1x1_T4x16 && L.cout == 65 && !pool && !relu) {      // convPb
       static const int on = d2fe_dev_env("D2FE_CONV1X1", 1);
       if (on) { const hipError_t e = launch_conv1x1_256_65(a, s); if (e != hipErrorNotSupported) return e; }
     }
@@ -382,10 +386,10 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
   // variant A up to 1024.  A sorted top-K selection takes K <= 16384 (one workgroup's in-LDS bitonic sort); the reference's TensorRT
   // profile (1500 x 1500, superpoint_tensorrt.cpp:50-55) with max_keypoints in the thousands is inside that.
   if ((cfg->max_keypoints < 1 && cfg->max_keypoints != -1) || cfg->max_keypoints > 16384) return fail(D2FE_ERR_INVALID, "max_keypoints must be -1 (keep all) or in 1..16384");
-  if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "bad precision");
+  if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO && cfg->precision != D2FE_PREC_F16) return fail(D2FE_ERR_INVALID, "bad precision");
   if (cfg->postproc != D2FE_POSTPROC_B && cfg->postproc != D2FE_POSTPROC_A) return fail(D2FE_ERR_INVALID, "bad postproc");
   if (cfg->exact_order) {
-    if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2 is not supported)");
+    if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2 and D2FE_PREC_F16 are not supported)");
     if (cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "exact_order needs post-processing variant B (NMS2 of variant A depends on the order in another way)");
     if (cfg->max_keypoints < 1) return fail(D2FE_ERR_INVALID, "exact_order needs max_keypoints >= 1 (keep-all handles are not supported)");
     if (!(cfg->exact_order_eps >= 0.f) || std::isinf(cfg->exact_order_eps)) return fail(D2FE_ERR_INVALID, "exact_order_eps must be finite and >= 0 (0 = the default)");
@@ -439,6 +443,9 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
     // Winograd mode: both heads evaluate the descriptor branch as direct fp32 chains (run_superpoint), so the choice is free of consequences for the
     // bits; measured per call (host to host, 640x480): 1 image 0.44 ms dense / 0.47 sparse, 2 images 0.69 dense / 0.67 sparse
     if (cfg->precision == D2FE_PREC_F32_WINO) h->sp_min_batch = 2;
+    // fp16-operand mode: the dense head would evaluate convDa | convDb with fp16 operands, the sparse head evaluates them as exact fp32 chains -- a frame's
+    // descriptors must not depend on how many images travel with it, so every call takes the sparse head (1 image: 0.03 ms more per call, the figures above)
+    if (cfg->precision == D2FE_PREC_F16) h->sp_min_batch = 1;
     h->sp_min_batch = d2fe_dev_env("D2FE_SPARSE_MIN_BATCH", h->sp_min_batch);
     if (h->sparse_desc) {
       const size_t ncell = (H / 8) * (W / 8);
@@ -1398,7 +1405,8 @@ long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_byte
       {"conv1a", &h->a1a, H * W * 64},           {"conv1b", &h->a1b, (H / 2) * (W / 2) * 64},   {"conv2a", &h->a2a, (H / 2) * (W / 2) * 64},
       {"conv2b", &h->a2b, (H / 4) * (W / 4) * 64},   {"conv3a", &h->a3a, (H / 4) * (W / 4) * 128},  {"conv3b", &h->a3b, (H / 8) * (W / 8) * 128},
       {"conv4a", &h->a4a, (H / 8) * (W / 8) * 128},  {"conv4b", h->last_set ? &h->a4b2 : &h->a4b, (H / 8) * (W / 8) * 128},  {"convPaDa", &h->aPD, (H / 8) * (W / 8) * 512},
-      {"logits", h->last_set ? &h->logits2 : &h->logits, (H / 8) * (W / 8) * 65}, {"desc_raw", h->last_set ? &h->draw2 : &h->draw, (H / 8) * (W / 8) * 256}, {"semi", &h->semi, (H / 8) * (W / 8) * 64}};
+      {"logits", h->last_set ? &h->logits2 : &h->logits, (H / 8) * (W / 8) * 65}, {"desc_raw", h->last_set ? &h->draw2 : &h->draw, (H / 8) * (W / 8) * 256}, {"semi", &h->semi, (H / 8) * (W / 8) * 64},
+      {"convPa", &h->aPD, (H / 8) * (W / 8) * 256}};      // the detector branch alone: what the sparse descriptor head leaves in the convPa|convDa buffer
   if (!strcmp(name, "conv1a") && h->fuse1a) {
     // fused mode never materialises conv1a: evaluate it on demand from the last input frame(s)
     if (!h->a1a.p && alloc_f(h->a1a, (size_t)h->cfg.max_height * h->cfg.max_width * 64, h->cfg.max_batch) != 0)
@@ -1409,6 +1417,8 @@ long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_byte
   if (!strcmp(name, "semi") && !h->cfg.keep_score_map) return fail(D2FE_ERR_NOT_READY, "score map not kept (set keep_score_map)");
   if (h->sparse_desc && h->last_n >= h->sp_min_batch && (!strcmp(name, "desc_raw") || !strcmp(name, "convPaDa")))
     return fail(D2FE_ERR_NOT_READY, "the dense descriptor map does not exist with the sparse descriptor head (set dense_descriptors)");
+  if (!strcmp(name, "convPa") && !(h->sparse_desc && h->last_n >= h->sp_min_batch))
+    return fail(D2FE_ERR_NOT_READY, "convPa alone exists only behind the sparse descriptor head (the dense head writes convPaDa)");
   for (auto& e : tab)
     if (!strcmp(e.nm, name)) {
       const size_t bytes = e.per * n * sizeof(float);

@@ -14,6 +14,7 @@
 // (oracle/d2fe_oracle.c orc_conv), so activations compare bitwise.
 // Fast mode (precision 1): operands split into fp16 hi + lo (x = hi + lo to ~2^-22), three
 // v_mfma_f32_32x32x16_f16 per k-step (hi*hi + hi*lo + lo*hi) into one fp32 accumulator.
+// Plain fp16 operands (precision 3): the hi halves alone, one MFMA per k-step (conv_f16.hip, contract in include/d2fe.h).
 #include "conv_common.h"
 
 namespace d2fe {
@@ -245,11 +246,14 @@ static hipError_t launch_f32_fused1b(int cout_pad, const ConvArgs& a, hipStream_
 }
 
 hipError_t launch_conv_f16x2(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_f16(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
 
 hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
                        hipStream_t s) {
   if (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && shape != CONV1B_FUSED)) return launch_conv_pc(shape, precision, pool, relu, cout_pad, a, s);
   if (precision == 1) return launch_conv_f16x2(shape, pool, relu, cout_pad, a, s);
+  if (precision == 3) return launch_conv_f16(shape, pool, relu, cout_pad, a, s);
+  if (precision != 0) return hipErrorInvalidValue;
   switch (shape) {
     case CONV_64_T8x32:
       if (tune_conv64() == 1) return launch_f32<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);

@@ -1,4 +1,4 @@
-// conv_common.h -- tile geometry and epilogue shared by the fp32 and fp16x2 conv kernels (internal).
+// conv_common.h -- tile geometry and epilogue shared by the fp32, fp16x2 and fp16 conv kernels (internal).
 #pragma once
 #include "kernels.h"
 
@@ -88,7 +88,8 @@ __device__ __forceinline__ void conv1a_octet(const float (&v)[9], const float* _
 // A [32 patch pixels x 10] x [10 x 64] problem per m-tile (K = 9 taps padded to 10): v_mfma_f32_32x32x2_f32 IS the oracle's
 // fmaf chain in (ky,kx) order started from the bias, so the values are bit-identical to conv1a_kernel.  c1w/c1b are this
 // lane's B fragments / bias (conv1a_mfma_load_weights), loaded once per workgroup.  MODE 0 writes fp32 (pixel stride CPF
-// floats), MODE 1 writes the 2^SA-scaled fp16 hi/lo planes (pixel stride CPH halves).  wv/nw: this wave's index / wave count.
+// floats), MODE 1 writes the 2^SA-scaled fp16 hi/lo planes (pixel stride CPH halves), MODE 2 the hi plane alone (D2FE_PREC_F16: lo is never touched).
+// wv/nw: this wave's index / wave count.
 __device__ __forceinline__ void conv1a_mfma_load_weights(const float* __restrict__ w9x64, const float* __restrict__ bias, int lane,
                                                          float (&c1w)[5][2], float (&c1b)[2]) {
 #pragma unroll
@@ -149,8 +150,10 @@ __device__ __forceinline__ void conv1a_mfma_stage(const uint8_t* __restrict__ ip
           const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1;
           hi[pp * CPH + (lane & 31)] = h0;
           hi[pp * CPH + 32 + (lane & 31)] = h1;
-          lo[pp * CPH + (lane & 31)] = (_Float16)(x0 - (float)h0);
-          lo[pp * CPH + 32 + (lane & 31)] = (_Float16)(x1 - (float)h1);
+          if constexpr (MODE == 1) {
+            lo[pp * CPH + (lane & 31)] = (_Float16)(x0 - (float)h0);
+            lo[pp * CPH + 32 + (lane & 31)] = (_Float16)(x1 - (float)h1);
+          }
         }
       }
     }

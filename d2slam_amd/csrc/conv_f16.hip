@@ -10,6 +10,11 @@
 // Same tiling and staging as conv.hip: the (TH+2)x(TW+2)xCin patch is converted once per block while it is
 // staged (global fp32 -> LDS fp16 hi plane + lo plane), and is then read as ds_read_b128 A fragments
 // (pixel stride Cin+8 halves -> the 16-lane groups of ds_read_b128 hit 16 distinct 16-byte slots).
+//
+// SPLIT = false is D2FE_PREC_F16 (contract in include/d2fe.h): the same kernel without the lo halves -- one LDS plane, one weight fragment and ONE
+// MFMA per (m, n, k-step); the accumulator starts at zero and the epilogue is acc * 2^-(SA+SW) + bias.  Tile shapes and the pixel stride are kept;
+// the halved LDS goes into occupancy: twice as many of these one-tile workgroups fit a CU's LDS (4x32x64: 14.7 KB instead of 29.4 KB), which is what
+// hides the staging phase of one workgroup under the MFMA phase of another now that the MFMA phase is a third as long.
 #include "conv_common.h"
 
 namespace d2fe {
@@ -19,7 +24,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int F16_SA = 4;   // activation scale 2^4  (|x| <= 4094 representable; clamped)
 constexpr int F16_SW = 8;   // weight scale 2^8
 
-template <int CIN, int KS, int TH, int TW, int WM, int WN, int MT, int NT, bool POOL, bool RELU, bool FUSE1A = false>
+template <int CIN, int KS, int TH, int TW, int WM, int WN, int MT, int NT, bool POOL, bool RELU, bool FUSE1A = false, bool SPLIT = true>
 __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
   constexpr int P = KS / 2;
   constexpr int PH = TH + KS - 1, PW = TW + KS - 1;
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
     // hi/lo and stored as 8-byte runs.  A patch pixel outside the image (conv1b's padding) gets all taps and the bias slot zeroed.
     static_assert(CIN == 64 && KS == 3 && NTHREADS == 256, "fused prologue is conv1a -> conv1b, four waves");
     constexpr int FR = PH + 2, FC = PW + 2, NMT = (NPIX + 31) / 32;
-    unsigned char* u8p = reinterpret_cast<unsigned char*>(lds + 2 * NPIX * CPH);
+    unsigned char* u8p = reinterpret_cast<unsigned char*>(lds + (SPLIT ? 2 : 1) * NPIX * CPH);
     const uint8_t* ip = a.img + (size_t)img * a.img_istride;
     for (int i = tid; i < FR * FC; i += NTHREADS) {
       const int r = i / FC, c = i - r * FC;
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
           }
           const int off = pidx * CPH + nt * 32 + 8 * q + 4 * hh;
           *reinterpret_cast<f16x4*>(hi + off) = h4;
-          *reinterpret_cast<f16x4*>(lo + off) = l4;
+          if constexpr (SPLIT) *reinterpret_cast<f16x4*>(lo + off) = l4;
         }
       }
     }
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
             l4[j] = (_Float16)(x - (float)h);
           }
           *reinterpret_cast<f16x4*>(hi + pix * CPH + c4 * 4) = h4;
-          *reinterpret_cast<f16x4*>(lo + pix * CPH + c4 * 4) = l4;
+          if constexpr (SPLIT) *reinterpret_cast<f16x4*>(lo + pix * CPH + c4 * 4) = l4;
         }
       }
     }
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
   f32x16 acc[MT][NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
-    const float b = a.bias[(ntile0 + n) * 32 + (lane & 31)] * bscale;
+    const float b = SPLIT ? a.bias[(ntile0 + n) * 32 + (lane & 31)] * bscale : 0.f;
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -167,11 +172,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
     aoff[m] = (py * PW + px) * CPH + 8 * (lane >> 5);
   }
 
-  // packed weights: [ntile][tap][kstep][hi|lo][lane] f16x8;  element i = W[co = ntile*32 + (lane&31)][ci = kstep*16 + 8*(lane>>5) + i][tap]
+  // packed weights: [ntile][tap][kstep][hi|lo][lane] f16x8 (SPLIT = false: no [hi|lo], the hi fragments alone);  element i = W[co = ntile*32 + (lane&31)][ci = kstep*16 + 8*(lane>>5) + i][tap]
+  constexpr int WSTEP = SPLIT ? 128 : 64;   // f16x8 per k-step in the pack
   const f16x8* wp = reinterpret_cast<const f16x8*>(a.wpack);
   const f16x8* wbase[NT];
 #pragma unroll
-  for (int n = 0; n < NT; ++n) wbase[n] = wp + (size_t)(ntile0 + n) * TAPS * KST * 128 + lane;
+  for (int n = 0; n < NT; ++n) wbase[n] = wp + (size_t)(ntile0 + n) * TAPS * KST * WSTEP + lane;
 
   // B fragments are double-buffered in registers in groups of G k-steps (hi and lo): group g+1 is requested from L2
   // before the MFMAs of group g start (sched_barrier keeps hipcc from sinking the loads next to their uses).
@@ -179,15 +185,15 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
   constexpr int GPT = KST / G;
   constexpr int NG = TAPS * GPT;
   static_assert(KST % G == 0, "group size must divide the steps per tap");
-  f16x8 bq[2][G][NT][2];
+  f16x8 bq[2][G][NT][SPLIT ? 2 : 1];
   auto load_grp = [&](int buf, int grp) {
     if (D2FE_ABL(a, 2)) grp = 0;
 #pragma unroll
     for (int j = 0; j < G; ++j)
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
-        bq[buf][j][n][0] = wbase[n][(size_t)(grp * G + j) * 128];
-        bq[buf][j][n][1] = wbase[n][(size_t)(grp * G + j) * 128 + 64];
+        bq[buf][j][n][0] = wbase[n][(size_t)(grp * G + j) * WSTEP];
+        if constexpr (SPLIT) bq[buf][j][n][1] = wbase[n][(size_t)(grp * G + j) * WSTEP + 64];
       }
   };
   auto compute_grp = [&](int buf, int grp) {
@@ -199,14 +205,16 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         ah[m] = *reinterpret_cast<const f16x8*>(hi + aoff[m] + tap_off + j * 16);
-        al[m] = *reinterpret_cast<const f16x8*>(lo + aoff[m] + tap_off + j * 16);
+        if constexpr (SPLIT) al[m] = *reinterpret_cast<const f16x8*>(lo + aoff[m] + tap_off + j * 16);
       }
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bq[buf][j][n][0], acc[m][n], 0, 0, 0);
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bq[buf][j][n][1], acc[m][n], 0, 0, 0);
+          if constexpr (SPLIT) {
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bq[buf][j][n][0], acc[m][n], 0, 0, 0);
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bq[buf][j][n][1], acc[m][n], 0, 0, 0);
+          }
           acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bq[buf][j][n][0], acc[m][n], 0, 0, 0);
         }
     }
@@ -223,19 +231,29 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f16x2_kernel(ConvArgs a) {
   }
   if constexpr (NG & 1) compute_grp(0, NG - 1);
 
-  conv_epilogue<TW, MT, NT, POOL, RELU>(a, acc, 1.0f / bscale, img, ty0, tx0, wm, ntile0, lane);
+  if constexpr (!SPLIT) {      // acc * 2^-(SA+SW) (exact), then + bias: one fma, whose single rounding is the rounding of the sum
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const float b = a.bias[(ntile0 + n) * 32 + (lane & 31)];
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][n][r] = __builtin_fmaf(acc[m][n][r], 1.0f / bscale, b);
+    }
+  }
+  conv_epilogue<TW, MT, NT, POOL, RELU>(a, acc, SPLIT ? 1.0f / bscale : 1.0f, img, ty0, tx0, wm, ntile0, lane);
 }
 
-template <int CIN, int KS, int TH, int TW, int WM, int WN, int MT, int NT>
+template <int CIN, int KS, int TH, int TW, int WM, int WN, int MT, int NT, bool SPLIT = true>
 static hipError_t launch_f16(bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
   constexpr int BN = WN * NT * 32;
-  constexpr size_t lds = (size_t)(TH + KS - 1) * (TW + KS - 1) * (CIN + 8) * sizeof(_Float16) * 2;
+  constexpr size_t lds = (size_t)(TH + KS - 1) * (TW + KS - 1) * (CIN + 8) * sizeof(_Float16) * (SPLIT ? 2 : 1);
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
   dim3 grid(tiles_x * tiles_y, cout_pad / BN, a.n_img), block(WM * WN * 64);
   if (cout_pad % BN) return hipErrorInvalidValue;
 #define D2FE_LAUNCH(PL, RL)                                                                          \
   do {                                                                                               \
-    auto k = conv_f16x2_kernel<CIN, KS, TH, TW, WM, WN, MT, NT, PL, RL>;                             \
+    auto k = conv_f16x2_kernel<CIN, KS, TH, TW, WM, WN, MT, NT, PL, RL, false, SPLIT>;               \
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                             \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
     if (e != hipSuccess) return e;                                                                   \
@@ -251,11 +269,12 @@ static hipError_t launch_f16(bool pool, bool relu, int cout_pad, const ConvArgs&
   return hipGetLastError();
 }
 
+template <bool SPLIT>
 static hipError_t launch_f16_fused1b(int cout_pad, const ConvArgs& a, hipStream_t s) {
   constexpr int TH = 4, TW = 32;
-  constexpr size_t lds = (size_t)(TH + 2) * (TW + 2) * 72 * sizeof(_Float16) * 2 + (TH + 4) * (TW + 4);      // hi/lo patch planes + the frame bytes
+  constexpr size_t lds = (size_t)(TH + 2) * (TW + 2) * 72 * sizeof(_Float16) * (SPLIT ? 2 : 1) + (TH + 4) * (TW + 4);      // hi/lo patch planes (hi alone) + the frame bytes
   if (cout_pad != 64 || !a.img || !a.w1a || !a.b1a) return hipErrorInvalidValue;
-  auto k = conv_f16x2_kernel<64, 3, TH, TW, 2, 2, 2, 1, true, true, true>;
+  auto k = conv_f16x2_kernel<64, 3, TH, TW, 2, 2, 2, 1, true, true, true, SPLIT>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   dim3 grid(((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH), 1, a.n_img), block(256);
@@ -265,13 +284,27 @@ static hipError_t launch_f16_fused1b(int cout_pad, const ConvArgs& a, hipStream_
 
 hipError_t launch_conv_f16x2(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
   switch (shape) {
-    case CONV1B_FUSED:       return launch_f16_fused1b(cout_pad, a, s);
+    case CONV1B_FUSED:       return launch_f16_fused1b<true>(cout_pad, a, s);
     case CONV_64_T8x32:
       if (tune_conv64() == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);
       return launch_f16<64, 3, 8, 32, 4, 1, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x32:     return launch_f16<128, 3, 4, 32, 2, 2, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x16:     return launch_f16<128, 3, 4, 16, 1, 4, 2, 1>(pool, relu, cout_pad, a, s);
     case CONV_256_1x1_T4x16: return launch_f16<256, 1, 4, 16, 1, 4, 2, 1>(pool, relu, cout_pad, a, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// D2FE_PREC_F16: the same shapes, single operands
+hipError_t launch_conv_f16(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
+  switch (shape) {
+    case CONV1B_FUSED:       return launch_f16_fused1b<false>(cout_pad, a, s);
+    case CONV_64_T8x32:
+      if (tune_conv64() == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1, false>(pool, relu, cout_pad, a, s);
+      return launch_f16<64, 3, 8, 32, 4, 1, 2, 2, false>(pool, relu, cout_pad, a, s);
+    case CONV_128_T4x32:     return launch_f16<128, 3, 4, 32, 2, 2, 2, 2, false>(pool, relu, cout_pad, a, s);
+    case CONV_128_T4x16:     return launch_f16<128, 3, 4, 16, 1, 4, 2, 1, false>(pool, relu, cout_pad, a, s);
+    case CONV_256_1x1_T4x16: return launch_f16<256, 1, 4, 16, 1, 4, 2, 1, false>(pool, relu, cout_pad, a, s);
   }
   return hipErrorInvalidValue;
 }
@@ -298,6 +331,27 @@ void pack_weights_f16x2(const float* w, int cout, int cin, int ks, int cout_pad,
             const size_t base = (((size_t)nt * taps + tap) * kst + k) * 128;
             d[(base + lane) * 8 + i] = h;
             d[(base + 64 + lane) * 8 + i] = l;
+          }
+}
+
+// D2FE_PREC_F16: w^ = fp16(2^SW * w) alone, [ntile][tap][kstep][lane] f16x8 -- half the bytes of the split pack
+size_t packed_weight_halfs_f16(int cout_pad, int cin, int ks) { return (size_t)cout_pad * cin * ks * ks; }
+
+void pack_weights_f16(const float* w, int cout, int cin, int ks, int cout_pad, uint16_t* dst) {
+  const int taps = ks * ks, kst = cin / 16;
+  const float sw = (float)(1 << F16_SW);
+  _Float16* d = reinterpret_cast<_Float16*>(dst);
+  for (int nt = 0; nt < cout_pad / 32; ++nt)
+    for (int tap = 0; tap < taps; ++tap)
+      for (int k = 0; k < kst; ++k)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int i = 0; i < 8; ++i) {
+            const int co = nt * 32 + (lane & 31);
+            const int ci = k * 16 + 8 * (lane >> 5) + i;
+            float v = co < cout ? w[((size_t)co * cin + ci) * taps + tap] * sw : 0.f;
+            if (v > 65000.f) v = 65000.f;
+            if (v < -65000.f) v = -65000.f;
+            d[(((size_t)nt * taps + tap) * kst + k) * 512 + lane * 8 + i] = (_Float16)v;
           }
 }
 

@@ -1,4 +1,4 @@
-// conv_pc.hip -- persistent producer/consumer version of the SuperPoint conv kernels (both precisions).
+// conv_pc.hip -- persistent producer/consumer version of the SuperPoint conv kernels (MODE 0 fp32, 1 fp16 hi/lo split, 2 plain fp16 operands).
 //
 // PMC on the one-tile-per-block kernels (conv.hip / conv_f16.hip) showed the matrix pipe busy only 72 % (fp32) and
 // 44 % (fp16x2) of the time: a block alternates a VALU/VMEM-heavy phase (stage the input patch: loads, conv1a
@@ -9,7 +9,10 @@
 // producer wave NC+i land on the same SIMD, whose matrix and vector pipes then run concurrently.
 //
 // Arithmetic is unchanged: the fp32 path is still the oracle's (ky,kx,ci) fmaf chain (bitwise), the fp16x2 path the
-// same hi/lo split.  Tiling: 4x32 pixels x 64 channels (Cin 64, waves 2x2), 4x16 x 128 (Cin 128 and the 1x1 heads,
+// same hi/lo split.  MODE 2 (D2FE_PREC_F16, contract in include/d2fe.h) is MODE 1 without the lo halves: one LDS plane per buffer, one weight
+// fragment per k-step, ONE v_mfma_f32_32x32x16_f16 per (m, n, k-step); the epilogue is acc * 2^-(SA+SW) + bias.  The tiles stay as they are (the
+// workgroup is persistent, one per CU: the halved LDS buys no occupancy here); the registers the lo fragments leave go into a weight ring twice as
+// deep, because a k-step now lasts a third as long and the L2 round trip of a fragment has to be covered by more of them.  Tiling: 4x32 pixels x 64 channels (Cin 64, waves 2x2), 4x16 x 128 (Cin 128 and the 1x1 heads,
 // waves 1x4); 2x2 max-pool stays lane-local for both tile widths.
 #include "conv_common.h"
 #include <cstdio>
@@ -18,7 +21,7 @@
 namespace d2fe {
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-constexpr int PC_SA = 4, PC_SW = 8;   // fp16x2 power-of-two operand scalings (same as conv_f16.hip)
+constexpr int PC_SA = 4, PC_SW = 8;   // fp16x2 / fp16 power-of-two operand scalings (same as conv_f16.hip)
 
 struct PcTile { int img, ty0, tx0, cg; };
 
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
   constexpr int TAPS = KS * KS;
   constexpr int CPF = CIN + 1;           // fp32 pixel stride (floats)
   constexpr int CPH = CIN + 8;           // fp16 pixel stride (halves), per plane
-  constexpr int BUF_BYTES = MODE == 0 ? NPIX * CPF * 4 : NPIX * CPH * 2 * 2;
+  constexpr int BUF_BYTES = MODE == 0 ? NPIX * CPF * 4 : MODE == 1 ? NPIX * CPH * 2 * 2 : NPIX * CPH * 2;
   static_assert(TH * TW == WM * MT * 32, "tile / wave mismatch");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
                 l4[j] = (_Float16)(x - (float)h);
               }
               *reinterpret_cast<f16x4*>(hi + pix * CPH + c4 * 4) = h4;
-              *reinterpret_cast<f16x4*>(lo + pix * CPH + c4 * 4) = l4;
+              if constexpr (MODE == 1) *reinterpret_cast<f16x4*>(lo + pix * CPH + c4 * 4) = l4;
             }
           }
         }
@@ -220,7 +223,10 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
   constexpr int F16_KST = CIN / 16, F16_S = TAPS * F16_KST, F16_R = (F16_S % 9 == 0) ? 9 : 8;
   static_assert(F16_S % F16_R == 0, "ring depth must divide the k-steps of a tile");
   f32x4 bq[2][MODE == 0 ? F32_G : 1][NT];
+  constexpr int F16_R1 = FUSE1A ? F16_R : (F16_S % 18 == 0) ? 18 : 16;      // MODE 2: twice the depth at the same register count (the fused prologue's producers need the registers)
+  static_assert(F16_S % F16_R1 == 0, "ring depth must divide the k-steps of a tile");
   f16x8 ring[MODE == 1 ? F16_R : 1][NT][2];
+  f16x8 ring1[MODE == 2 ? F16_R1 : 1][NT];
   int wcg = -1;
 
   auto compute = [&](const PcTile& T, int buf) {
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
     const float bscale = MODE == 0 ? 1.0f : (float)(1 << (PC_SA + PC_SW));
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
-      const float b = a.bias[(ntile0 + n) * 32 + (lane & 31)] * bscale;
+      const float b = MODE == 2 ? 0.f : a.bias[(ntile0 + n) * 32 + (lane & 31)] * bscale;      // MODE 2 adds the bias in the epilogue
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -288,7 +294,7 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
         __builtin_amdgcn_sched_barrier(0);
         compute_grp(1, g + 1);
       }
-    } else {
+    } else if constexpr (MODE == 1) {
       const _Float16* hi = reinterpret_cast<const _Float16*>(base);
       const _Float16* lo = hi + NPIX * CPH;
       constexpr int KST = F16_KST, S = F16_S, R = F16_R;
@@ -343,9 +349,63 @@ __global__ __launch_bounds__(WM * WN * 128) void conv_pc_kernel(ConvArgs a, int 
             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[st & 1][m], ring[st % R][n][0], acc[m][n], 0, 0, 0);
           }
       }
+    } else {
+      const _Float16* hi = reinterpret_cast<const _Float16*>(base);
+      constexpr int KST = F16_KST, S = F16_S, R = F16_R1;
+      int aoff[MT];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        int py, px;
+        mtile_pixel<TW>(wm * MT + m, lane & 31, py, px);
+        aoff[m] = (py * PW + px) * CPH + 8 * (lane >> 5);
+      }
+      // packed weights: [ntile][tap][kstep][lane] f16x8 (pack_weights_f16: the hi halves alone)
+      const f16x8* wp = reinterpret_cast<const f16x8*>(a.wpack);
+      const f16x8* wbase[NT];
+#pragma unroll
+      for (int n = 0; n < NT; ++n) wbase[n] = wp + (size_t)(ntile0 + n) * TAPS * KST * 64 + lane;
+      auto load_step = [&](int slot, int st) {
+        if (D2FE_ABL(a, 2)) st = 0;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) ring1[slot][n] = wbase[n][(size_t)st * 64];
+      };
+      auto a_off = [&](int st) { const int tap = st / KST, ks = st % KST; return ((tap / KS) * PW + (tap % KS)) * CPH + ks * 16; };
+      f16x8 ah[2][MT];
+      auto load_a = [&](int slot, int st) {
+        const int o = a_off(st);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) ah[slot][m] = *reinterpret_cast<const f16x8*>(hi + aoff[m] + o);
+      };
+      if (wcg != T.cg) {
+#pragma unroll
+        for (int st = 0; st < R - 1; ++st) load_step(st, st % S);
+        wcg = T.cg;
+      }
+      load_a(0, 0);
+#pragma unroll
+      for (int st = 0; st < S; ++st) {
+        load_step((st + R - 1) % R, (st + R - 1) % S);
+        if (st + 1 < S) load_a((st + 1) & 1, st + 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[st & 1][m], ring1[st % R][n], acc[m][n], 0, 0, 0);
+      }
+      // epilogue of the mode: acc * 2^-(SA+SW) (exact), then + bias -- one fma, whose single rounding is the rounding of the sum
+      const float inv = 1.0f / bscale;
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const float b = a.bias[(ntile0 + n) * 32 + (lane & 31)];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[m][n][r] = __builtin_fmaf(acc[m][n][r], inv, b);
+      }
     }
     mark(1);
-    const float oscale = MODE == 0 ? 1.0f : 1.0f / bscale;
+    const float oscale = MODE == 1 ? 1.0f / bscale : 1.0f;
     if constexpr (POOL && TW == 16)
       pc_epilogue_pool16<MT, NT, RELU>(a, acc, oscale, T.img, T.ty0, T.tx0, wm, ntile0, lane);
     else
@@ -391,7 +451,7 @@ template <int MODE, int CIN, int KS, int TH, int TW, int WM, int WN, int MT, int
 static hipError_t launch_pc_one(int cout_pad, const ConvArgs& a, hipStream_t s) {
   constexpr int BN = WN * NT * 32;
   constexpr int NPIX = (TH + KS - 1) * (TW + KS - 1);
-  constexpr size_t buf = MODE == 0 ? (size_t)NPIX * (CIN + 1) * 4 : (size_t)NPIX * (CIN + 8) * 4;
+  constexpr size_t buf = MODE == 0 ? (size_t)NPIX * (CIN + 1) * 4 : MODE == 1 ? (size_t)NPIX * (CIN + 8) * 4 : (size_t)NPIX * (CIN + 8) * 2;
   constexpr size_t lds = 2 * buf;
   static_assert(lds <= 163840, "double-buffered patch does not fit in LDS");
   if (cout_pad % BN) return hipErrorInvalidValue;
@@ -450,8 +510,12 @@ static hipError_t launch_pc_mode(ConvShape shape, bool pool, bool relu, int cout
 }
 
 hipError_t launch_conv_pc(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
-  return precision == 0 ? launch_pc_mode<0>(shape, pool, relu, cout_pad, a, s)
-                        : launch_pc_mode<1>(shape, pool, relu, cout_pad, a, s);
+  switch (precision) {      // d2fe_precision; the Winograd mode (2) has kernels of its own
+    case 0: return launch_pc_mode<0>(shape, pool, relu, cout_pad, a, s);
+    case 1: return launch_pc_mode<1>(shape, pool, relu, cout_pad, a, s);
+    case 3: return launch_pc_mode<2>(shape, pool, relu, cout_pad, a, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace d2fe

@@ -65,7 +65,7 @@ enum ConvShape {
   CONV1B_FUSED,         // conv1a (1->64, from the u8 frame) fused into conv1b's patch staging, + ReLU + 2x2 pool
 };
 
-// precision: 0 = fp32 exact MFMA, 1 = fp16 hi/lo split MFMA
+// precision (d2fe_precision): 0 = fp32 exact MFMA, 1 = fp16 hi/lo split MFMA, 3 = plain fp16 operands (the Winograd mode, 2, has launchers of its own below)
 hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
                        hipStream_t s);
 
@@ -91,6 +91,8 @@ size_t packed_weight_floats_f32(int cout_pad, int cin, int ks);
 void pack_weights_f32(const float* w /*[cout][cin][k][k]*/, int cout, int cin, int ks, int cout_pad, float* dst);
 size_t packed_weight_halfs_f16x2(int cout_pad, int cin, int ks);
 void pack_weights_f16x2(const float* w, int cout, int cin, int ks, int cout_pad, uint16_t* dst);
+size_t packed_weight_halfs_f16(int cout_pad, int cin, int ks);      // D2FE_PREC_F16: the hi halves alone
+void pack_weights_f16(const float* w, int cout, int cin, int ks, int cout_pad, uint16_t* dst);
 
 // ---- post-processing ------------------------------------------------------------------------------
 // softmax(65) -> drop dustbin -> 8x8 unfold; writes dense semi (optional) and appends variant-B candidates

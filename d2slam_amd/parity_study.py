@@ -7,7 +7,10 @@ mirror-padded re-crops, gain changes: real image statistics, no new reference co
 Symmetric differences of raster-index sets (keypoints per image; matches per pair as (index, index) pairs).
 
 order_study(): the ORDER-aware comparison (list positions, not sets) of the plain Winograd mode and of the Winograd mode with exact_order against the exact mode,
-the deviation of the Winograd score maps from the direct ones (what exact_order_eps has to bound) and what exact_order re-evaluates."""
+the deviation of the Winograd score maps from the direct ones (what exact_order_eps has to bound) and what exact_order re-evaluates.
+
+f16_study(): the fp16-operand mode (PREC_F16) against the exact mode -- sets, matches and list positions (tools/f16_study.py, profiles/f16_study.json).  study() is
+unchanged by it: bench.py's in-run subset compares what it always compared."""
 import os
 
 import numpy as np
@@ -90,6 +93,40 @@ def study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
         for part, lo, hi in (("all", 0, NI), ("synthetic", 0, n_syn), ("real_derived", n_syn, NI)):
             plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
             rec["%s_vs_f32_%s" % (name, part)] = compare(sel["f32"], sel[name], lo, hi, plo, phi)
+    return rec
+
+
+def _lists_and_matches(api, imgs, pairs, thr, N, prec, batch=32, device_id=0):
+    """(per-image raster-index lists in list order, per-pair sets of (index, index) matches) of one arithmetic mode"""
+    fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=N, input_width=W, input_height=H, max_batch=batch, precision=prec, keypoint_threshold=thr, device_id=device_id))
+    fe.load_superpoint(weights_for(thr))
+    idx, ds = [], []
+    for i0 in range(0, len(imgs), batch):
+        for k, s, d in fe.extract_batch(imgs[i0:i0 + batch], cap=N):
+            idx.append(k[:, 1].astype(np.int64) * W + k[:, 0].astype(np.int64)); ds.append(d)
+    mt = []
+    for ia, ib in pairs:
+        q, t, _ = fe.match_knn(ds[ia], ds[ib], 0.8)
+        mt.append(set(zip(idx[ia][q].tolist(), idx[ib][t].tolist())))
+    fe.close()
+    return idx, mt
+
+
+def f16_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
+    """one configuration: the fp16-operand mode (PREC_F16) -- and, for scale, the two other fast modes -- against the exact mode: keypoint SETS and match sets
+    (compare) and list POSITIONS (compare_order).  Figures to report, not bounds: fp16 operands carry 11 bits, near-ties far beyond the top-K cut move."""
+    modes = {"f32": api.PREC_F32, "f16": api.PREC_F16, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}
+    got = {name: _lists_and_matches(api, imgs, pairs, thr, N, prec, batch, device_id) for name, prec in modes.items()}
+    as_sets = lambda g: ([set(a.tolist()) for a in g[0]], g[1])
+    NI = len(imgs)
+    rec = {"threshold": thr, "max_keypoints": N, "images": NI, "images_per_call": batch}
+    for name in ("f16", "f16x2", "wino"):
+        for part, lo, hi in (("all", 0, NI), ("synthetic", 0, n_syn), ("real_derived", n_syn, NI)):
+            plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
+            rec["%s_vs_f32_%s" % (name, part)] = compare(as_sets(got["f32"]), as_sets(got[name]), lo, hi, plo, phi)
+        order = compare_order(got["f32"][0], got[name][0])
+        order["images_differing"] = len(order["images_differing"])
+        rec["%s_vs_f32_positions" % name] = order
     return rec
 
 

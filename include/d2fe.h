@@ -44,7 +44,7 @@ typedef enum {
 typedef enum {
   D2FE_PREC_F32 = 0,   /* exact fp32 MFMA (v_mfma_f32_32x32x2_f32): bitwise equal to the oracle's fmaf chains */
   D2FE_PREC_F16X2 = 1, /* fp16 hi/lo split operands, 3 x v_mfma_f32_32x32x16_f16, fp32 accumulate (~2^-22 rel.) */
-  D2FE_PREC_F32_WINO = 2 /* fp32 throughout; the eight 3x3 layers with Cin >= 64 as Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32
+  D2FE_PREC_F32_WINO = 2,/* fp32 throughout; the eight 3x3 layers with Cin >= 64 as Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32
                             (16 instead of 36 multiplies per output and channel pair).  Bitwise equal to the oracle's restatement
                             of that evaluation order (orc_conv3x3_wino), ~1e-6 relative to the direct chains of D2FE_PREC_F32.
                             Keypoint lists are index-exact against THAT evaluation order only: scores closer than the deviation can swap list
@@ -53,7 +53,28 @@ typedef enum {
                             exact_order_eps bounds |Winograd score - direct score| and d2fe_exact_order_stats reports no dropped cell.  It does NOT
                             cover the descriptors (they stay the Winograd trunk's, <= 1e-5 from exact; matches whose near-ties follow from
                             descriptor bits may differ), the scores of keypoints outside re-evaluated cells (Winograd bits), variant A,
-                            D2FE_PREC_F16X2 or keep-all handles. */
+                            D2FE_PREC_F16X2, D2FE_PREC_F16 or keep-all handles. */
+  D2FE_PREC_F16 = 3      /* fp16 OPERANDS, fp32 accumulation: the operand precision the reference's engine may run at (kFP16,
+                            superpoint_tensorrt.cpp:118-122), one v_mfma_f32_32x32x16_f16 per k-step where D2FE_PREC_F16X2 spends three.
+                            Activations between the layers stay fp32 NHWC in memory.  The arithmetic of every layer that D2FE_PREC_F16X2 evaluates
+                            in split form (conv1b .. conv4b, convPa | convDa, the 1x1 heads convPb and -- dense head only -- convDb), with SA = 4, SW = 8:
+                              activation  x^ = fp16(min(max(x * 2^SA, -65000), 65000))   round to nearest even; the inputs are ReLU outputs, so only the
+                                                                                         upper clamp can act (x >= 4062.5)
+                              weight      w^ = fp16(min(max(w * 2^SW, -65000), 65000))   round to nearest even, once, when the weights are loaded
+                              sum         acc = sum over (ky, kx, ci) of x^ * w^         products exact, accumulated in fp32 inside the matrix instruction
+                                                                                         (the order is the instruction's: no bit-exact restatement is promised)
+                              epilogue    y = acc * 2^-(SA+SW) + bias                    the scaling is exact, the bias is the fp32 bias: ONE rounding;
+                                                                                         then ReLU and the 2x2 max-pool as in every mode
+                            fp16 subnormals are KEPT on both operands (gradual underflow: |x * 2^SA| or |w * 2^SW| below 2^-14 keeps fewer than 11
+                            bits, down to the spacing 2^-24; nothing is flushed to zero by the conversion or by the matrix instruction); zero padding is
+                            exact.  The error of one layer against real arithmetic on the ROUNDED operands is bounded by the fp32 summation bound
+                            (9 Cin + 2) * 2^-24 * (sum |x^ w^| * 2^-(SA+SW) + |bias|); the operand rounding itself is 2^-11 relative per operand.
+                            What D2FE_PREC_F16X2 keeps in fp32 stays fp32: conv1a (fused into conv1b's staging, bit-equal to the exact mode),
+                            the sparse descriptor head (convDa, convDb at the keypoints' cells: exact fp32 chains), softmax, selection, sampling.
+                            Handles of this mode take the sparse descriptor head for every call (the dense head would evaluate convDa | convDb with
+                            fp16 operands: only dense_descriptors handles and calls with a capacity beyond 4 x min(max_keypoints, 1024) cells do), so
+                            a frame's outputs do not depend on the entry point, the batch it travels in or the pipe that carries it.
+                            Not available with exact_order. */
 } d2fe_precision;
 
 /* Mirrors SuperPointConfig (d2frontend/include/d2frontend/CNN/superpoint_tensorrt.h:17-33) plus the

@@ -86,6 +86,7 @@ struct SuperPointConfig {
   int32_t max_batch = 2;
   bool fast_mode = false;                // D2FE_PREC_F16X2 instead of the bit-exact fp32 mode
   bool winograd = false;                 // D2FE_PREC_F32_WINO: fp32, 3x3 layers as Winograd F(2x2,3x3) (1.76x the direct mode's throughput)
+  bool fp16_operands = false;            // D2FE_PREC_F16: fp16 operands, fp32 accumulation (the reference engine's kFP16 operand precision); wins over the two above
   bool exact_order = false;              // winograd only, max_keypoints >= 1: the keypoint list (count, indices, order) equals the exact mode's (d2fe_config::exact_order)
   float exact_order_eps = 0.f;           // 0: the library default
   int32_t exact_order_crops = 0;         // crop slots per call; 0: max_batch
@@ -107,7 +108,7 @@ class SuperPoint {
     c.max_width = cfg_.input_width; c.max_height = cfg_.input_height; c.max_batch = cfg_.max_batch;
     c.max_keypoints = cfg_.max_keypoints; c.remove_borders = cfg_.remove_borders; c.keypoint_threshold = cfg_.keypoint_threshold;
     c.postproc = D2FE_POSTPROC_B;
-    c.precision = cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
+    c.precision = cfg_.fp16_operands ? D2FE_PREC_F16 : cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
     c.exact_order = cfg_.exact_order ? 1 : 0; c.exact_order_eps = cfg_.exact_order_eps; c.exact_order_crops = cfg_.exact_order_crops;
     if (d2fe_create(&c, &h_) != D2FE_OK) { report("d2fe_create"); h_ = nullptr; return false; }
     if (d2fe_load_superpoint(h_, &w) != D2FE_OK) { report("d2fe_load_superpoint"); return false; }

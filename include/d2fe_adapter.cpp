@@ -37,8 +37,8 @@ inline d2fe_handle handle_of(const void* obj) {
   auto it = table().find(obj);
   return it == table().end() ? nullptr : it->second.h;
 }
-// precision of the convolutions: D2FE_PREC_F32 (direct fmaf chains, the ABI default), D2FE_PREC_F32_WINO (fp32 Winograd, bench.py's headline mode) or
-// D2FE_PREC_F16X2; one switch for the process, set before build()
+// precision of the convolutions: D2FE_PREC_F32 (direct fmaf chains, the ABI default), D2FE_PREC_F32_WINO (fp32 Winograd, bench.py's headline mode),
+// D2FE_PREC_F16X2 or D2FE_PREC_F16 (fp16 operands); one switch for the process, set before build()
 inline int& precision() { static int p = D2FE_PREC_F32; return p; }
 inline void release(const void* obj) {
   std::lock_guard<std::mutex> g(table_mutex());

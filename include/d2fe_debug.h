@@ -14,7 +14,7 @@ extern "C" {
 #endif
 
 /* Debug/inspection: copy an internal device tensor of the last extract call to the host.
- * names: "conv1a".."conv4b","convPaDa","logits","desc_raw","semi".  Returns bytes copied or <0. */
+ * names: "conv1a".."conv4b","convPaDa","logits","desc_raw","semi"; "convPa" (256 channels) after a call that took the sparse descriptor head.  Returns bytes copied or <0. */
 D2FE_API long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_bytes);
 /* NetVLAD inspection: output of layer `layer` (NHWC fp32, n_images of the handle's maximum size) of the last d2fe_netvlad* call, when the
  * execution plan materialises it -- the last layer of every fused MobileNetV2 block and every unfused layer; D2FE_ERR_NOT_READY for a

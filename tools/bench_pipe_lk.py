@@ -31,7 +31,7 @@ def main():
     from benchlib.pipe_legs import pipe_frames
     from d2slam_amd import api, netvlad as nvm
     from d2slam_amd.weights import synthetic_superpoint_weights
-    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}[args.precision]
+    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO, "f16": api.PREC_F16}[args.precision]
     fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=CAP, input_width=W, input_height=H, max_batch=1, precision=prec))
     fe.load_superpoint(synthetic_superpoint_weights(dustbin_bias=7.5)); fe.load_netvlad(nvm.synthetic_netvlad_weights())
     modes = {"A": dict(lr_lk=False, match_lr=True), "B": dict(lr_lk=True, match_lr=False)}

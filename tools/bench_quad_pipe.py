@@ -42,7 +42,7 @@ def main():
     from d2slam_amd import api, netvlad as nvm, quadcam
     from d2slam_amd.synth import synth_image
     from d2slam_amd.weights import synthetic_superpoint_weights
-    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}[args.precision]
+    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO, "f16": api.PREC_F16}[args.precision]
     sweep = [tuple(int(x) for x in p.split("x")) for p in args.sweep.split(",")]
     qs = sorted({q for _, q in sweep})
     w = dict(synthetic_superpoint_weights(dustbin_bias=7.5))

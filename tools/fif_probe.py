@@ -32,7 +32,7 @@ def main():
     torch.cuda.set_device(0)
     weights = synthetic_superpoint_weights(dustbin_bias=7.5)
     nvw = nvm.synthetic_netvlad_weights()
-    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}[args.precision]
+    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO, "f16": api.PREC_F16}[args.precision]
     frames = [synth_stereo(H, W, seed=s) for s in range(8)]
     res = []
     for pt in args.sweep.split(","):

@@ -28,7 +28,7 @@ def main():
     from d2slam_amd import api, netvlad as nvm
     from d2slam_amd.synth import synth_stereo
     from d2slam_amd.weights import synthetic_superpoint_weights
-    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO}[args.precision]
+    prec = {"f32": api.PREC_F32, "f16x2": api.PREC_F16X2, "wino": api.PREC_F32_WINO, "f16": api.PREC_F16}[args.precision]
     fe = (api.DevFrontEnd if args.dev else api.FrontEnd)(api.SuperPointConfig(max_keypoints=CAP, input_width=W, input_height=H, max_batch=1, precision=prec))
     fe.load_superpoint(synthetic_superpoint_weights(dustbin_bias=7.5))
     if not args.no_netvlad:
