@@ -242,7 +242,8 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
-    "d2fe_debug_netvlad_plan", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset"]
+    "d2fe_debug_netvlad_plan", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
+    "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_nms2_a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -299,6 +300,11 @@ def _open_library(path, dev):
                 getattr(lib, nm).restype = C.c_long
             lib.d2fe_debug_regime_counts.argtypes = [C.c_void_p, C.c_int]
             lib.d2fe_debug_regime_reset.argtypes = []; lib.d2fe_debug_regime_reset.restype = None
+            vp, ci = C.c_void_p, C.c_int
+            lib.d2fe_debug_softmax_cand.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, ci, ci, vp, vp, vp]
+            lib.d2fe_debug_select_b.argtypes = [vp, vp, vp, C.c_long, ci, ci, ci, ci, ci, ci, vp, C.c_float, ci, vp, vp, vp, vp]
+            lib.d2fe_debug_sample_b.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp]
+            lib.d2fe_debug_nms2_a.argtypes = [vp, vp, ci, ci, ci, C.c_float, ci, ci, ci, vp, vp, vp, vp]
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
         lib.d2fe_half_move_cols.argtypes = [C.c_int, C.c_double]
@@ -611,7 +617,7 @@ class FrontEnd:
         desc = np.zeros((n, cap, self.desc_dim), np.float32); cnt = np.zeros(n, np.int32)
         rc = self._lib.d2fe_superpoint_extract_batch(self._h, _ptr(images), n, W, H, W, H * W, _ptr(kps), _ptr(sc),
                                                      _ptr(desc), cap, _ptr(cnt))
-        # D2FE_ERR_TRUNCATED: the strongest `cap` keypoints were written and n_out is valid -- report it, keep the results
+        # D2FE_ERR_TRUNCATED: the first `cap` keypoints in raster order were written and n_out is valid -- report it, keep the results
         self.last_truncated = rc == ERR_TRUNCATED
         if rc != 0 and rc != ERR_TRUNCATED:
             _check(rc)
@@ -940,6 +946,61 @@ class DevFrontEnd(FrontEnd):
 
     def __init__(self, cfg: SuperPointConfig):
         super().__init__(cfg, dev=True)
+
+    # ---- the SuperPoint tail kernels of csrc/postproc.hip on injected tensors (include/d2fe_debug.h; tests/test_postproc_edges.py) ----
+    def debug_softmax_cand(self, logits, thr, border, want_semi=True):
+        """softmax_cand_kernel on logits [n, Hc, Wc, lstride >= 65] (channels 65.. are padding).  Returns (semi [n, 8Hc, 8Wc] or None,
+        [the u64 candidate keys of image i, in the order the kernel left them], counts [n])."""
+        logits = np.ascontiguousarray(logits, np.float32)
+        n, Hc, Wc, lstride = logits.shape
+        semi = np.empty((n, Hc * 8, Wc * 8), np.float32) if want_semi else None
+        cand = np.empty((n, 64 * Hc * Wc), np.uint64); cnt = np.empty(n, np.int32)
+        _check(self._lib.d2fe_debug_softmax_cand(self._h, _ptr(logits), lstride, n, Hc, Wc, float(thr), int(border), int(bool(want_semi)), _ptr(semi),
+                                                 _ptr(cand), _ptr(cnt)))
+        return semi, [cand[i, :min(int(cnt[i]), cand.shape[1])].copy() for i in range(n)], cnt
+
+    def debug_select_b(self, keys, W, H, max_kp, cap, always_sort=False, semi=None, thr=0.0, border=0, counts=None):
+        """select_b_kernel on injected keys: `keys` is a list of u64 arrays, one per image (counts: the cand_count entries, the lists' lengths by default).
+        Returns one (kps_xy [m, 2], scores [m], idx [m]) per image, m = the kernel's n_out."""
+        n = len(keys)
+        cand_cap = max(1, max(len(k) for k in keys))
+        cand = np.zeros((n, cand_cap), np.uint64)
+        for i, k in enumerate(keys):
+            cand[i, :len(k)] = k
+        cnt = np.ascontiguousarray([len(k) for k in keys] if counts is None else counts, np.int32)
+        if semi is not None:
+            semi = np.ascontiguousarray(semi, np.float32).reshape(n, H, W)
+        kps = np.empty((n, cap, 2), np.float32); sc = np.empty((n, cap), np.float32); idx = np.empty((n, cap), np.int32); m = np.empty(n, np.int32)
+        _check(self._lib.d2fe_debug_select_b(self._h, _ptr(cand), _ptr(cnt), cand_cap, n, W, H, int(max_kp), int(cap), int(bool(always_sort)), _ptr(semi),
+                                             float(thr), int(border), _ptr(kps), _ptr(sc), _ptr(idx), _ptr(m)))
+        return [(kps[i, :m[i]].copy(), sc[i, :m[i]].copy(), idx[i, :m[i]].copy()) for i in range(n)]
+
+    def debug_sample_b(self, desc_raw, kps_xy, n_kp, dcoff=0, slotmap=None):
+        """sample_b_kernel.  Dense form: desc_raw [n, Hc, Wc, dstride], read at channel offset dcoff.  Sparse form: desc_raw [n, max_slots, 256] and
+        slotmap [n, Hc, Wc].  kps_xy [n, cap, 2], n_kp [n].  Returns desc [n, cap, 256] (rows at and beyond n_kp are not written)."""
+        desc_raw = np.ascontiguousarray(desc_raw, np.float32); kps_xy = np.ascontiguousarray(kps_xy, np.float32)
+        n_kp = np.ascontiguousarray(n_kp, np.int32)
+        n, cap = kps_xy.shape[0], kps_xy.shape[1]
+        if slotmap is None:
+            _, Hc, Wc, dstride = desc_raw.shape
+            max_slots = 0
+        else:
+            slotmap = np.ascontiguousarray(slotmap, np.int32)
+            _, Hc, Wc = slotmap.shape
+            dstride, max_slots = 256, desc_raw.shape[1]
+        out = np.empty((n, cap, 256), np.float32)
+        _check(self._lib.d2fe_debug_sample_b(self._h, _ptr(desc_raw), dstride, int(dcoff), n, Hc, Wc, _ptr(kps_xy), _ptr(n_kp), cap, _ptr(slotmap), max_slots,
+                                             _ptr(out)))
+        return out
+
+    def debug_nms2_a(self, semi, thr, dist, max_kp, cap):
+        """Variant A's keypoint selection on semi [n, H, W]: nms2_a_kernel, select_b_kernel (always_sort) and the CV_16UC1 wrap.
+        Returns one (kps_xy, scores, idx) per image."""
+        semi = np.ascontiguousarray(semi, np.float32)
+        n, H, W = semi.shape
+        kps = np.empty((n, cap, 2), np.float32); sc = np.empty((n, cap), np.float32); idx = np.empty((n, cap), np.int32); m = np.empty(n, np.int32)
+        _check(self._lib.d2fe_debug_nms2_a(self._h, _ptr(semi), n, H, W, float(thr), int(dist), int(max_kp), int(cap), _ptr(kps), _ptr(sc), _ptr(idx), _ptr(m)))
+        return [(kps[i, :m[i]].copy(), sc[i, :m[i]].copy(), idx[i, :m[i]].copy()) for i in range(n)]
 
     @staticmethod
     def regime_counts(reset=False):

@@ -382,7 +382,7 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
   if (cfg->max_batch < 1) return fail(D2FE_ERR_INVALID, "max_batch < 1");
   // -1 = keep every keypoint above the threshold (SuperPoint::topKeypoints only truncates when k != -1, superpoint_tensorrt.cpp:241-253;
   // NMS2's `i < max_num` is an unsigned compare, superpoint_common.cpp:173): variant B then returns EVERY keypoint above the threshold, in
-  // raster order, up to the call's capacity (any capacity up to H*W; D2FE_ERR_TRUNCATED with the strongest kept if an image had more);
+  // raster order, up to the call's capacity (any capacity up to H*W; D2FE_ERR_TRUNCATED with the first of them in raster order kept if an image had more);
   // variant A up to 1024.  A sorted top-K selection takes K <= 16384 (one workgroup's in-LDS bitonic sort); the reference's TensorRT
   // profile (1500 x 1500, superpoint_tensorrt.cpp:50-55) with max_keypoints in the thousands is inside that.
   if ((cfg->max_keypoints < 1 && cfg->max_keypoints != -1) || cfg->max_keypoints > 16384) return fail(D2FE_ERR_INVALID, "max_keypoints must be -1 (keep all) or in 1..16384");
@@ -808,7 +808,7 @@ static int extract_host(d2fe_handle h, const uint8_t* gray, int n, int width, in
     if (h->pin_nv) memcpy(netvlad_out, h->pin_nv, nv_bytes);
   }
   for (int32_t c : ncand)
-    if (c > dcap) return fail(D2FE_ERR_TRUNCATED, "max_keypoints = -1: an image has more keypoints than the call's capacity; the strongest were kept");
+    if (c > dcap) return fail(D2FE_ERR_TRUNCATED, "max_keypoints = -1: an image has more keypoints than the call's capacity; the first of them in raster order were kept");
   return D2FE_OK;
 }
 
@@ -1542,6 +1542,143 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   return rc;
+}
+
+// ---- the SuperPoint tail kernels of postproc.hip on injected tensors (tests/test_postproc_edges.py): host buffers in and out, the hook's own device
+// buffers, the handle's device and stream, no weights.  Each hook calls the launch_* function of kernels.h with the caller's parameters and nothing else.
+namespace {
+struct DebugBufs {      // device scratch of one hook call: freed when the call returns, whichever way
+  std::vector<void*> owned;
+  ~DebugBufs() { for (void* p : owned) (void)hipFree(p); }
+  // bytes of device memory, filled with `fill` bytes (outputs: 0xff, so that an entry a kernel does not write is no plausible value) or with src
+  hipError_t get(void** out, size_t bytes, const void* src, int fill = 0xff) {
+    *out = nullptr;
+    hipError_t e = hipMalloc(out, bytes ? bytes : 4);
+    if (e != hipSuccess) return e;
+    owned.push_back(*out);
+    if (!bytes) return hipSuccess;
+    return src ? hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) : hipMemset(*out, fill, bytes);
+  }
+};
+constexpr long DEBUG_MAX_PIXELS = 1l << 21;
+}  // namespace
+
+int d2fe_debug_softmax_cand(d2fe_handle h, const float* logits, int lstride, int n, int Hc, int Wc, float thr, int border, int want_semi, float* semi_out,
+                            unsigned long long* cand_out, int* cand_count_out) {
+  if (!h || !logits || !cand_out || !cand_count_out || (want_semi && !semi_out)) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || lstride < 65 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t ncell = (size_t)Hc * Wc, hw = ncell * 64;
+  const long cand_cap = (long)hw;
+  DebugBufs b;
+  float *d_l = nullptr, *d_semi = nullptr;
+  unsigned long long* d_cand = nullptr;
+  int* d_cnt = nullptr;
+  HIP_TRY(b.get((void**)&d_l, sizeof(float) * n * ncell * lstride, logits));
+  if (want_semi) HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());      // the null-stream copies and memsets are not ordered with the handle's non-blocking stream
+  HIP_TRY(launch_softmax_cand(d_l, lstride, Hc, Wc, n, thr, border, d_semi, d_cand, d_cnt, cand_cap, /*zero_counts=*/true, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (want_semi) HIP_TRY(hipMemcpy(semi_out, d_semi, sizeof(float) * n * hw, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cand_out, d_cand, sizeof(unsigned long long) * n * cand_cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cand_count_out, d_cnt, sizeof(int) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int* cand_count, long cand_cap, int n, int W, int H, int max_kp, int cap,
+                        int always_sort, const float* semi_or_null, float thr, int border, float* kps_xy, float* scores, int32_t* kps_idx, int32_t* n_out) {
+  if (!h || !cand || !cand_count || !kps_xy || !scores || !kps_idx || !n_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || W < 1 || H < 1 || cap < 1 || cand_cap < 1 || (long)H * W > DEBUG_MAX_PIXELS || cand_cap > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS)
+    return fail(D2FE_ERR_INVALID, "bad geometry");
+  for (int i = 0; i < n; ++i)
+    if (cand_count[i] < 0 || cand_count[i] > cand_cap) return fail(D2FE_ERR_INVALID, "cand_count entry outside [0, cand_cap]");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t hw = (size_t)H * W;
+  DebugBufs b;
+  unsigned long long* d_cand = nullptr;
+  int* d_cnt = nullptr;
+  float *d_semi = nullptr, *d_kps = nullptr, *d_sc = nullptr;
+  int32_t *d_idx = nullptr, *d_n = nullptr;
+  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, cand));
+  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, cand_count));
+  if (semi_or_null) HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, semi_or_null));
+  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_select_b(d_cand, d_cnt, cand_cap, n, W, max_kp, cap, always_sort, d_semi, H, thr, border, d_kps, d_sc, d_idx, d_n, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(kps_xy, d_kps, sizeof(float) * 2 * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(scores, d_sc, sizeof(float) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(kps_idx, d_idx, sizeof(int32_t) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_out, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                        const int32_t* slotmap_or_null, int max_slots, float* desc_out) {
+  if (!h || !desc_raw || !kps_xy || !n_kp || !desc_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  const size_t ncell = (size_t)Hc * Wc;
+  if (slotmap_or_null) {      // sparse store [img][max_slots][256]: every cell the kernel may look up must name a slot of the store
+    if (max_slots < 1 || max_slots > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "max_slots");
+    for (size_t i = 0; i < (size_t)n * ncell; ++i)
+      if (slotmap_or_null[i] < 0 || slotmap_or_null[i] >= max_slots) return fail(D2FE_ERR_INVALID, "slot map entry outside [0, max_slots)");
+  } else if (dcoff < 0 || (dcoff & 3) || (dstride & 3) || dstride < dcoff + 256 || dstride > 4096) {
+    return fail(D2FE_ERR_INVALID, "dense form: dcoff and dstride are multiples of 4 with dcoff + 256 <= dstride");
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  DebugBufs b;
+  float *d_raw = nullptr, *d_kps = nullptr, *d_desc = nullptr;
+  int32_t *d_n = nullptr, *d_map = nullptr;
+  HIP_TRY(b.get((void**)&d_raw, sizeof(float) * n * (slotmap_or_null ? (size_t)max_slots * 256 : ncell * dstride), desc_raw));
+  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
+  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, n_kp));
+  if (slotmap_or_null) HIP_TRY(b.get((void**)&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
+  HIP_TRY(b.get((void**)&d_desc, sizeof(float) * 256 * n * cap, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_sample_b(d_raw, dstride, dcoff, Hc, Wc, n, d_kps, d_n, cap, d_map, max_slots, d_desc, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * 256 * n * cap, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,
+                      int32_t* kps_idx, int32_t* n_out) {
+  if (!h || !semi || !kps_xy || !scores || !kps_idx || !n_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || H < 1 || W < 1 || cap < 1 || dist < 0 || (long)H * W > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t hw = (size_t)H * W;
+  const long cand_cap = (long)hw;
+  DebugBufs b;
+  float *d_semi = nullptr, *d_aconf = nullptr, *d_kps = nullptr, *d_sc = nullptr;
+  int *d_clist = nullptr, *d_cnt = nullptr, *d_ncand = nullptr;
+  unsigned long long* d_cand = nullptr;
+  int32_t *d_idx = nullptr, *d_n = nullptr;
+  HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, semi));
+  HIP_TRY(b.get((void**)&d_aconf, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get((void**)&d_clist, sizeof(int) * n * hw, nullptr, 0));
+  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get((void**)&d_ncand, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, nullptr, 0));
+  HIP_TRY(hipDeviceSynchronize());
+  // the sequence run_superpoint issues for variant A
+  HIP_TRY(launch_nms2_a(d_semi, H, W, n, thr, dist, d_aconf, d_clist, d_cand, d_cnt, cand_cap, d_ncand, h->stream));
+  HIP_TRY(launch_select_b(d_cand, d_cnt, cand_cap, n, W, max_kp, cap, 1, nullptr, H, thr, 0, d_kps, d_sc, d_idx, d_n, h->stream));
+  if ((long)H * W > 65536) HIP_TRY(launch_nms2_wrap_fix(d_clist, d_ncand, H, W, n, d_kps, d_idx, d_n, cap, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(kps_xy, d_kps, sizeof(float) * 2 * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(scores, d_sc, sizeof(float) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(kps_idx, d_idx, sizeof(int32_t) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_out, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
 }
 
 #endif  // D2FE_DEVTOOLS

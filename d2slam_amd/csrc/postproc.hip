@@ -161,6 +161,7 @@ hipError_t launch_softmax_cand(const float* logits, int lstride, int Hc, int Wc,
 // Variant-B selection (topKeypoints, superpoint_tensorrt.cpp:241-253): one 1024-thread block per image.
 //   count <= K : keep all, in RASTER order (the reference does not sort in this case)
 //   count >  K : the K largest keys, in descending key order (score desc, raster asc on ties)
+//   keep-all (max_kp < 0, where the reference sorts nothing): RASTER order whatever the count; more than `cap` keep the first `cap` of it
 // Exact selection by MSB-first radix select on the unique 64-bit keys, then an in-LDS bitonic sort.
 // -----------------------------------------------------------------------------------------------------
 constexpr int SEL_THREADS = 1024;
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_b_kernel(const unsigned lo
   long n = cand_count[img];
   if (n > cand_cap) n = cand_cap;
   int K = (max_kp < 0) ? cap : min(max_kp, cap);
-  const bool take_all = (n <= K) && !always_sort;   // variant A sorts by confidence even when everything is kept
+  const bool take_all = (n <= K || max_kp < 0) && !always_sort;   // variant A sorts by confidence even when everything is kept
   if (take_all && n > sort_n && semi) {
     // keep-all with more keypoints than the LDS sort takes: raster order straight from the dense score map (same predicate as the
     // candidate list: score > thr, inside the borders), ordered compaction by ballot + prefix
@@ -223,12 +224,14 @@ __global__ __launch_bounds__(SEL_THREADS) void select_b_kernel(const unsigned lo
     return;
   }
   if (K > sort_n) K = sort_n;
-  // When everything is kept the output order is raster (the reference does not sort): sort on the low word
+  // When everything is kept the output order is raster (the reference does not sort): select and sort on the low word
   // (0xFFFFFFFF - idx, descending == idx ascending) and let the score bits ride along in the low half.
+  const bool by_index = take_all;
+  auto key_at = [&](long i) { const unsigned long long k = c[i]; return by_index ? ((k << 32) | (k >> 32)) : k; };
   unsigned long long thresh = 0;  // keep keys >= thresh
   int nk = (int)(n < K ? n : K);
   if (!(take_all && n <= sort_n) && n > K) {
-    // radix select: find the K-th largest key
+    // radix select: find the K-th largest key (keep-all beyond the capacity, without a dense map: the K lowest raster indices)
     unsigned long long prefix = 0, mask = 0;
     int need = K;
     for (int pass = 7; pass >= 0; --pass) {
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_b_kernel(const unsigned lo
       for (int i = tid; i < 256; i += SEL_THREADS) hist[i] = 0;
       __syncthreads();
       for (long i = tid; i < n; i += SEL_THREADS) {
-        const unsigned long long k = c[i];
+        const unsigned long long k = key_at(i);
         if ((k & mask) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xFF)], 1);
       }
       __syncthreads();
@@ -276,16 +279,15 @@ __global__ __launch_bounds__(SEL_THREADS) void select_b_kernel(const unsigned lo
     }
     thresh = prefix;  // at least K (and <= sort_n) keys are >= thresh; the sort below keeps the first K
   }
-  const bool by_index = take_all && n <= sort_n;
   // gather survivors into LDS
   if (tid == 0) s_cnt = 0;
   for (int i = tid; i < sort_n; i += SEL_THREADS) keys[i] = 0;
   __syncthreads();
   for (long i = tid; i < n; i += SEL_THREADS) {
-    const unsigned long long k = c[i];
+    const unsigned long long k = key_at(i);
     if (k >= thresh) {
       const int slot = atomicAdd(&s_cnt, 1);
-      if (slot < sort_n) keys[slot] = by_index ? ((k << 32) | (k >> 32)) : k;
+      if (slot < sort_n) keys[slot] = k;
     }
   }
   __syncthreads();

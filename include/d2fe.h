@@ -87,9 +87,10 @@ typedef struct {
   int32_t max_batch;          /* images per batched call (>= 1) */
   int32_t max_keypoints;      /* SuperPointConfig::max_keypoints: 1..16384 (sorted top-K), or -1 = keep every keypoint above the threshold in raster
                                  order like topKeypoints with k == -1 (superpoint_tensorrt.cpp:241-253)  [params->max_superpoint_cnt].
-                                 Keep-all with MORE keypoints in an image than the call's capacity: D2FE_ERR_TRUNCATED, and the strongest
-                                 min(capacity, 16384) of them are returned in score order (16384 = the in-LDS sort) */
-  int32_t remove_borders;     /* SuperPointConfig::remove_borders (variant B), default 1 */
+                                 Keep-all with MORE keypoints in an image than the call's capacity: D2FE_ERR_TRUNCATED, and the first
+                                 `capacity` of them in raster order are returned (the reference's list, cut where the buffers end) */
+  int32_t remove_borders;     /* SuperPointConfig::remove_borders (variant B), default 1.  With 0, keypoints of the last row and column carry the reference's NaN
+                                 descriptors: their four clipped sampling weights are 0 (superpoint_tensorrt.cpp:255-317) */
   float   keypoint_threshold; /* SuperPointConfig::keypoint_threshold, default 0.015 */
   int32_t postproc;           /* d2fe_postproc */
   int32_t nms_dist;           /* variant A: NMS2 dist_thresh (SuperPointONNX::nms_dist) */

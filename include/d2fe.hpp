@@ -127,7 +127,7 @@ class SuperPoint {
       if (!reserve(cap)) break;
       rc = (!h_ || input.channels != 1) ? (int)D2FE_ERR_INVALID
                                         : d2fe_superpoint_extract(h_, input.data, input.cols, input.rows, (int)input.step, kp_.data(), sc_.data(), de_.data(), (int)cap, &n);
-      // keep-all with more keypoints than the buffers hold: the library has written the strongest `cap`; the reference returns ALL of them, so run again with room
+      // keep-all with more keypoints than the buffers hold: the library has written the first `cap` in raster order; the reference returns ALL of them, so run again with room
       if (rc != D2FE_ERR_TRUNCATED || cfg_.max_keypoints > 0 || cap >= most) break;
       cap = cap * 4 < most ? cap * 4 : most;
     }

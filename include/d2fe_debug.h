@@ -48,6 +48,27 @@ D2FE_API long d2fe_debug_pack_wino(const float* weight /*[cout][cin][3][3]*/, in
 D2FE_API int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W, int cin, const float* weight,
                                      const float* bias, int cout, int pool, int relu, float* out, int iters, float* ms_per_launch);
 
+/* The SuperPoint tail kernels (csrc/postproc.hip) on injected tensors, for tests/test_postproc_edges.py: host buffers in and out, device buffers of the
+ * call's own, the handle's device and stream; no weights needed.  Each hook hands the caller's parameters to the launcher the extractor uses, unchanged.
+ * All of them refuse (D2FE_ERR_INVALID) null pointers, n < 1, Hc or Wc below 2, cap < 1 and maps of more than 2^21 pixels.
+ * Output buffers start as all-ones words on the device, so an entry the kernels do not write comes back as 0xFFFFFFFF.
+ *   softmax_cand: logits [n][Hc*Wc][lstride >= 65] -> semi_out [n][8Hc][8Wc] (when want_semi), cand_out [n][64*Hc*Wc] u64 keys
+ *                 (score_bits << 32) | (0xFFFFFFFF - raster) in no particular order, cand_count_out [n].
+ *   select_b:     cand [n][cand_cap], cand_count [n] (an entry above cand_cap is refused), semi_or_null [n][H][W] -> kps_xy [n][cap][2], scores [n][cap],
+ *                 kps_idx [n][cap], n_out [n]; entries at and beyond n_out are unspecified.
+ *   sample_b:     desc_raw [n][Hc*Wc][dstride] read at channel offset dcoff (slotmap_or_null == NULL), or the sparse store [n][max_slots][256] with
+ *                 slotmap [n][Hc*Wc] (every entry in [0, max_slots)); kps_xy [n][cap][2], n_kp [n] -> desc_out [n][cap][256].
+ *   nms2_a:       semi [n][H][W] -> variant A's keypoints: nms2_a_kernel, select_b_kernel (always_sort, no border), and nms2_wrap_fix_kernel when H*W > 65536. */
+D2FE_API int d2fe_debug_softmax_cand(d2fe_handle h, const float* logits, int lstride, int n, int Hc, int Wc, float thr, int border, int want_semi,
+                                     float* semi_out, unsigned long long* cand_out, int* cand_count_out);
+D2FE_API int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int* cand_count, long cand_cap, int n, int W, int H, int max_kp, int cap,
+                                 int always_sort, const float* semi_or_null, float thr, int border, float* kps_xy, float* scores, int32_t* kps_idx,
+                                 int32_t* n_out);
+D2FE_API int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp,
+                                 int cap, const int32_t* slotmap_or_null, int max_slots, float* desc_out);
+D2FE_API int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,
+                               int32_t* kps_idx, int32_t* n_out);
+
 /* Host-pointer calls replay cached hipGraphs of their launch sequences from the third call with the same geometry on (D2FE_GRAPH=0 in the
  * environment turns that off).  Returns how many graphs the handle holds; *rejected (may be NULL) = geometries whose capture failed and which
  * therefore keep launching kernel by kernel (diagnostic). */

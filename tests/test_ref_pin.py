@@ -244,7 +244,7 @@ def test_hip_match_knn_vs_reference_cpp(api, na, nb, dim, ratio, radius, sigma):
 @pytest.mark.gpu
 def test_hip_keep_all_vs_reference_cpp(api, orc, sp_weights):
     """max_keypoints = -1 (SuperPoint::topKeypoints keeps everything when k == -1, superpoint_tensorrt.cpp:241-253): all keypoints above
-    the threshold, in raster order, like the reference; more than the call's capacity -> D2FE_ERR_TRUNCATED with the strongest kept."""
+    the threshold, in raster order, like the reference; more than the call's capacity -> D2FE_ERR_TRUNCATED with the first `cap` of the reference's raster-ordered list kept (oracle.select_b's clip)."""
     H, W = 120, 160
     img = synth_image(H, W, 14)
     f = orc.superpoint_forward(img, sp_weights)
@@ -256,11 +256,10 @@ def test_hip_keep_all_vs_reference_cpp(api, orc, sp_weights):
     rk, rs, rd = spref.superpoint_post(f["semi"], f["desc"], thr, 1, -1)
     assert 600 < len(rk) < 1024 and np.array_equal(kps, rk) and np.array_equal(sc, rs)
     assert np.abs(desc - rd).max() <= 1e-6
-    # a capacity below the keypoint count: D2FE_ERR_TRUNCATED, reported as a flag, with the 256 STRONGEST keypoints kept
+    # a capacity below the keypoint count: D2FE_ERR_TRUNCATED, reported as a flag, with the FIRST 256 keypoints of the reference's list kept, position by position
     (k2, s2, d2), = fe.extract_batch(img[None], cap=256)
     assert fe.last_truncated and len(k2) == 256
-    order = np.lexsort((np.arange(len(rs)), -rs))[:256]
-    assert {tuple(p) for p in k2} == {tuple(p) for p in rk[order]}
+    assert np.array_equal(k2, rk[:256]) and np.array_equal(s2, rs[:256]) and np.abs(d2 - rd[:256]).max() <= 1e-6
     (k3, _, _), = fe.extract_batch(img[None], cap=1024)
     assert not fe.last_truncated and len(k3) == len(rk)
     fe.close()
