@@ -43,7 +43,7 @@ class _Config(C.Structure):
                 ("max_height", C.c_int32), ("max_batch", C.c_int32), ("max_keypoints", C.c_int32),
                 ("remove_borders", C.c_int32), ("keypoint_threshold", C.c_float), ("postproc", C.c_int32),
                 ("nms_dist", C.c_int32), ("precision", C.c_int32), ("keep_score_map", C.c_int32),
-                ("dense_descriptors", C.c_int32), ("async_tail", C.c_int32), ("reserved", C.c_int32 * 5),
+                ("dense_descriptors", C.c_int32), ("async_tail", C.c_int32), ("variant_b_pca", C.c_int32), ("reserved", C.c_int32 * 4),
                 ("exact_order", C.c_int32), ("exact_order_eps", C.c_float), ("exact_order_crops", C.c_int32)]
 
 
@@ -216,6 +216,8 @@ EXPORTS = [
     "d2fe_netvlad", "d2fe_netvlad_batch", "d2fe_netvlad_device", "d2fe_match_knn", "d2fe_match_crosscheck", "d2fe_match_batch_device",
     "d2fe_match_fallback_rows", "d2fe_block_words", "d2fe_block_field_offset", "d2fe_pack_blocks_device", "d2fe_gate_pairs_device",
     "d2fe_quad_gate_device", "d2fe_block_bytes_int8", "d2fe_pack_blocks_int8_device", "d2fe_unpack_blocks_int8_device", "d2fe_half_move_cols",
+    "d2fe_block_words_d", "d2fe_block_field_offset_d", "d2fe_pack_blocks_device_d", "d2fe_block_bytes_int8_d", "d2fe_pack_blocks_int8_device_d",
+    "d2fe_unpack_blocks_int8_device_d",
     "d2fe_half_image_compact_device", "d2fe_remap_matches_device", "d2fe_half_image_filter", "d2fe_undistort", "d2fe_undistort_device",
     "d2fe_db_create", "d2fe_db_destroy", "d2fe_db_ntotal", "d2fe_db_add", "d2fe_db_search", "d2fe_db_query_gated", "d2fe_quantize_int8",
     "d2fe_dequantize_int8", "d2fe_sync", "d2fe_exact_order_stats", "d2fe_profile_enable", "d2fe_profile_read", "d2fe_prepare_gray", "d2fe_prepare_gray_device",
@@ -243,7 +245,7 @@ DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
     "d2fe_debug_netvlad_plan", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
-    "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_nms2_a"]
+    "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -304,6 +306,7 @@ def _open_library(path, dev):
             lib.d2fe_debug_softmax_cand.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, ci, ci, vp, vp, vp]
             lib.d2fe_debug_select_b.argtypes = [vp, vp, vp, C.c_long, ci, ci, ci, ci, ci, ci, vp, C.c_float, ci, vp, vp, vp, vp]
             lib.d2fe_debug_sample_b.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp]
+            lib.d2fe_debug_sample_b_pca.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, ci, vp]
             lib.d2fe_debug_nms2_a.argtypes = [vp, vp, ci, ci, ci, C.c_float, ci, ci, ci, vp, vp, vp, vp]
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
@@ -526,10 +529,13 @@ class SuperPointConfig:
 class FrontEnd:
     """One device context (== one LoopCam's networks, loop_cam.cpp:24-70)."""
 
-    def __init__(self, cfg: SuperPointConfig, dev: bool = False, exact_order: bool = False, exact_order_eps: float = 0.0, exact_order_crops: int = 0):
+    def __init__(self, cfg: SuperPointConfig, dev: bool = False, exact_order: bool = False, exact_order_eps: float = 0.0, exact_order_crops: int = 0,
+                 variant_b_pca: bool = False):
         """dev=True: a handle of the development library (d2fe_debug_* hooks, D2FE_* schedule switches); the product library otherwise.
         exact_order (PREC_F32_WINO, variant B, max_keypoints >= 1): the keypoint lists equal those of a PREC_F32 handle position by position
-        (include/d2fe.h, d2fe_config::exact_order); exact_order_eps / exact_order_crops: 0 = the library defaults.  Pipes created from the handle inherit it."""
+        (include/d2fe.h, d2fe_config::exact_order); exact_order_eps / exact_order_crops: 0 = the library defaults.  Pipes created from the handle inherit it.
+        variant_b_pca (variant B only): set_pca is accepted and every extract call, pipe, list, store and exchange of the handle carries rows of pca_dims
+        floats (include/d2fe.h, d2fe_config::variant_b_pca); False: variant B refuses a PCA, as the reference's live path ignores it."""
         lib = load_library(dev)
         self.dev = bool(dev)
         c = _Config()
@@ -550,6 +556,7 @@ class FrontEnd:
         c.exact_order = int(bool(exact_order))
         c.exact_order_eps = float(exact_order_eps)
         c.exact_order_crops = int(exact_order_crops)
+        c.variant_b_pca = int(bool(variant_b_pca))
         self.cfg = cfg
         self._h = C.c_void_p()
         _check(lib.d2fe_create(C.byref(c), C.byref(self._h)))
@@ -593,7 +600,9 @@ class FrontEnd:
         _check(self._lib.d2fe_load_superpoint(self._h, C.byref(sw)))
 
     def set_pca(self, comp, mean):
-        """comp [pca_dims,256] (CSV layout of superpoint_onnx.cpp:47-53), mean [256]; variant A only."""
+        """comp [pca_dims,256] (CSV layout of superpoint_onnx.cpp:47-53), mean [256]; comp=None switches the PCA off.  Variant A (pca_dims 1..256), or a
+        variant-B handle created with variant_b_pca=True (pca_dims 4..256, a multiple of 4); any other variant-B handle raises D2FE_ERR_UNSUPPORTED.
+        desc_dim is pca_dims afterwards.  Refused while pipes of the handle are alive."""
         if comp is None:
             _check(self._lib.d2fe_set_superpoint_pca(self._h, None, None, 0))
             return
@@ -881,23 +890,23 @@ class FrontEnd:
                                                C.byref(n)))
         return q[:n.value].copy(), t[:n.value].copy(), d[:n.value].copy()
 
-    def pack_blocks_device(self, d_desc, d_kps, d_scores, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim, d_blocks, stream=None):
-        """One exchange block per frame (desc | kps | scores | netvlad | n), raw device addresses; see include/d2fe.h."""
-        _check(self._lib.d2fe_pack_blocks_device(self._h, C.c_void_p(d_desc), C.c_void_p(d_kps), C.c_void_p(d_scores), C.c_void_p(d_n),
-                                                 C.c_void_p(d_netvlad or 0), int(row0), int(row_step), int(nframes), int(cap), int(netvlad_dim),
-                                                 C.c_void_p(d_blocks), C.c_void_p(stream or 0)))
+    def pack_blocks_device(self, d_desc, d_kps, d_scores, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim, d_blocks, stream=None, desc_dim=256):
+        """One exchange block per frame (desc | kps | scores | netvlad | n), raw device addresses; desc_dim: floats per descriptor row; see include/d2fe.h."""
+        _check(self._lib.d2fe_pack_blocks_device_d(self._h, C.c_void_p(d_desc), C.c_void_p(d_kps), C.c_void_p(d_scores), C.c_void_p(d_n),
+                                                   C.c_void_p(d_netvlad or 0), int(row0), int(row_step), int(nframes), int(cap), int(desc_dim), int(netvlad_dim),
+                                                   C.c_void_p(d_blocks), C.c_void_p(stream or 0)))
 
-    def pack_blocks_int8_device(self, d_desc, d_kps, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim, d_blocks, stream=None):
+    def pack_blocks_int8_device(self, d_desc, d_kps, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim, d_blocks, stream=None, desc_dim=256):
         """Exchange blocks in the reference's int8 wire precision (VisualImageDesc::toLCM); raw device addresses."""
         V = C.c_void_p
-        _check(self._lib.d2fe_pack_blocks_int8_device(self._h, V(d_desc), V(d_kps), V(d_n), V(d_netvlad or 0), int(row0), int(row_step), int(nframes),
-                                                      int(cap), int(netvlad_dim), V(d_blocks), V(stream or 0)))
+        _check(self._lib.d2fe_pack_blocks_int8_device_d(self._h, V(d_desc), V(d_kps), V(d_n), V(d_netvlad or 0), int(row0), int(row_step), int(nframes),
+                                                        int(cap), int(desc_dim), int(netvlad_dim), V(d_blocks), V(stream or 0)))
 
-    def unpack_blocks_int8_device(self, d_blocks_int8, nblocks, cap, netvlad_dim, d_blocks, renorm=0, stream=None):
-        """Gathered int8 blocks -> fp32 block layout with the reference's decode (renorm 0) or per-descriptor re-normalisation (1)."""
+    def unpack_blocks_int8_device(self, d_blocks_int8, nblocks, cap, netvlad_dim, d_blocks, renorm=0, stream=None, desc_dim=256):
+        """Gathered int8 blocks -> fp32 block layout with the reference's decode (renorm 0) or every descriptor re-normalised over its row (1)."""
         V = C.c_void_p
-        _check(self._lib.d2fe_unpack_blocks_int8_device(self._h, V(d_blocks_int8), int(nblocks), int(cap), int(netvlad_dim), int(renorm), V(d_blocks),
-                                                        V(stream or 0)))
+        _check(self._lib.d2fe_unpack_blocks_int8_device_d(self._h, V(d_blocks_int8), int(nblocks), int(cap), int(desc_dim), int(netvlad_dim), int(renorm),
+                                                          V(d_blocks), V(stream or 0)))
 
     def gate_pairs_device(self, d_q, q_stride, d_db, db_stride, dim, d_pair_q, d_pair_db, npairs, thres, d_cnt_inout=None, d_pass=None,
                           d_sims=None, d_n_pass=None, stream=None):
@@ -991,6 +1000,26 @@ class DevFrontEnd(FrontEnd):
         out = np.empty((n, cap, 256), np.float32)
         _check(self._lib.d2fe_debug_sample_b(self._h, _ptr(desc_raw), dstride, int(dcoff), n, Hc, Wc, _ptr(kps_xy), _ptr(n_kp), cap, _ptr(slotmap), max_slots,
                                              _ptr(out)))
+        return out
+
+    def debug_sample_b_pca(self, desc_raw, kps_xy, n_kp, comp, mean, dcoff=0, slotmap=None):
+        """sample_b_pca_kernel: debug_sample_b's arguments plus comp [pca_dims, 256] and mean [256].  Returns desc [n, cap, pca_dims]."""
+        self._need_dev("debug_sample_b_pca")
+        desc_raw = np.ascontiguousarray(desc_raw, np.float32); kps_xy = np.ascontiguousarray(kps_xy, np.float32)
+        n_kp = np.ascontiguousarray(n_kp, np.int32)
+        comp = np.ascontiguousarray(comp, np.float32); mean = np.ascontiguousarray(mean, np.float32)
+        assert comp.ndim == 2 and comp.shape[1] == 256 and mean.shape == (256,)
+        n, cap = kps_xy.shape[0], kps_xy.shape[1]
+        if slotmap is None:
+            _, Hc, Wc, dstride = desc_raw.shape
+            max_slots = 0
+        else:
+            slotmap = np.ascontiguousarray(slotmap, np.int32)
+            _, Hc, Wc = slotmap.shape
+            dstride, max_slots = 256, desc_raw.shape[1]
+        out = np.empty((n, cap, comp.shape[0]), np.float32)
+        _check(self._lib.d2fe_debug_sample_b_pca(self._h, _ptr(desc_raw), dstride, int(dcoff), n, Hc, Wc, _ptr(kps_xy), _ptr(n_kp), cap, _ptr(slotmap), max_slots,
+                                                 _ptr(comp), _ptr(mean), comp.shape[0], _ptr(out)))
         return out
 
     def debug_nms2_a(self, semi, thr, dist, max_kp, cap):
@@ -1357,19 +1386,19 @@ class QuadPipe(_Owned):
         return out
 
 
-def block_words(cap, netvlad_dim):
-    """Float words of one exchange block (include/d2fe.h, d2fe_block_words); callable without a GPU."""
-    return int(load_library().d2fe_block_words(int(cap), int(netvlad_dim)))
+def block_words(cap, netvlad_dim, desc_dim=256):
+    """Float words of one exchange block (include/d2fe.h, d2fe_block_words_d); callable without a GPU."""
+    return int(load_library().d2fe_block_words_d(int(cap), int(desc_dim), int(netvlad_dim)))
 
 
-def block_bytes_int8(cap, netvlad_dim):
-    """Bytes of one int8 exchange block (include/d2fe.h, d2fe_block_bytes_int8)."""
-    return int(load_library().d2fe_block_bytes_int8(int(cap), int(netvlad_dim)))
+def block_bytes_int8(cap, netvlad_dim, desc_dim=256):
+    """Bytes of one int8 exchange block (include/d2fe.h, d2fe_block_bytes_int8_d)."""
+    return int(load_library().d2fe_block_bytes_int8_d(int(cap), int(desc_dim), int(netvlad_dim)))
 
 
-def block_field_offset(cap, netvlad_dim, field):
+def block_field_offset(cap, netvlad_dim, field, desc_dim=256):
     """Word offset of a block field: 'desc', 'kps', 'scores', 'netvlad', 'n'."""
-    return int(load_library().d2fe_block_field_offset(int(cap), int(netvlad_dim), ["desc", "kps", "scores", "netvlad", "n"].index(field)))
+    return int(load_library().d2fe_block_field_offset_d(int(cap), int(desc_dim), int(netvlad_dim), ["desc", "kps", "scores", "netvlad", "n"].index(field)))
 
 
 class FlatIPDatabase(_Owned):
@@ -2050,13 +2079,13 @@ class KeyframeWindow(_Owned):
                                                   C.c_size_t(nkp_stride), int(nq), int(slot), C.c_void_p(stream or 0)))
 
     def _track_blocks(self, d_blocks, world, first, nq, slot, stream):
-        cap, G = self.cap, self.netvlad_dim
-        blk = block_words(cap, G)
+        cap, G, D = self.cap, self.netvlad_dim, self.desc_dim
+        blk = block_words(cap, G, D)
         if nq is None:
             nq = world * self.frames - first
         base = d_blocks + 4 * blk * first * self.views
-        self.track_device(base + 4 * block_field_offset(cap, G, "netvlad"), blk, base + 4 * block_field_offset(cap, G, "desc"), blk,
-                          base + 4 * block_field_offset(cap, G, "n"), blk, nq, slot, stream)
+        self.track_device(base + 4 * block_field_offset(cap, G, "netvlad", D), blk, base + 4 * block_field_offset(cap, G, "desc", D), blk,
+                          base + 4 * block_field_offset(cap, G, "n", D), blk, nq, slot, stream)
         return nq
 
     def track_exchange(self, exchange, xslot, slot, first=0, nq=None):

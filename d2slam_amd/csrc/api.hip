@@ -301,7 +301,8 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
       HIP_TRY(launch_sample_a(draw.p, 256, 0, Hc, Wc, W, H, n, d_kps, d_n, cap, h->pca_dims ? h->pca_comp_t : nullptr,
                               h->pca_mean, h->pca_dims, h->a_samp, h->a_scap, h->a_cn, nullptr, 0, d_desc, s));
     else
-      HIP_TRY(launch_sample_b(draw.p, 256, 0, Hc, Wc, n, d_kps, d_n, cap, nullptr, 0, d_desc, s));
+      HIP_TRY(launch_sample_b(draw.p, 256, 0, Hc, Wc, n, d_kps, d_n, cap, nullptr, 0, h->pca_dims ? h->pca_comp_t : nullptr, h->pca_mean, h->pca_dims,
+                              d_desc, s));
   } else {
     { ProfScope ps(h, D2FE_PROF_CONVDB, s);
       HIP_TRY(launch_desc_head_sparse(d_kps, d_n, cap, Hc, Wc, n, a4b.p, 128, (long)Hc * Wc * 128, h->L[L_DA32].wpack, h->L[L_DA32].bias,
@@ -312,12 +313,17 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
       HIP_TRY(launch_sample_a(h->sp_desc, 256, 0, Hc, Wc, W, H, n, d_kps, d_n, cap, h->pca_dims ? h->pca_comp_t : nullptr,
                               h->pca_mean, h->pca_dims, h->a_samp, h->a_scap, h->a_cn, h->sp_slotmap, h->sp_slots, d_desc, s));
     else
-      HIP_TRY(launch_sample_b(h->sp_desc, 256, 0, Hc, Wc, n, d_kps, d_n, cap, h->sp_slotmap, h->sp_slots, d_desc, s));
+      HIP_TRY(launch_sample_b(h->sp_desc, 256, 0, Hc, Wc, n, d_kps, d_n, cap, h->sp_slotmap, h->sp_slots, h->pca_dims ? h->pca_comp_t : nullptr,
+                              h->pca_mean, h->pca_dims, d_desc, s));
   }
   h->last_w = W; h->last_h = H; h->last_n = n;
   h->last_gray = d_gray; h->last_stride = stride; h->last_istride = image_stride;
   return D2FE_OK;
 }
+
+// floats per descriptor row of every extract call, pipe and list of the handle: pca_dims can only be non-zero where the PCA is applied (variant A, or variant B
+// with d2fe_config.variant_b_pca: d2fe_set_superpoint_pca refuses every other handle)
+int desc_dim_of(const d2fe_context* h) { return h->pca_dims ? h->pca_dims : 256; }
 
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap) {
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
@@ -388,6 +394,8 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
   if ((cfg->max_keypoints < 1 && cfg->max_keypoints != -1) || cfg->max_keypoints > 16384) return fail(D2FE_ERR_INVALID, "max_keypoints must be -1 (keep all) or in 1..16384");
   if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO && cfg->precision != D2FE_PREC_F16) return fail(D2FE_ERR_INVALID, "bad precision");
   if (cfg->postproc != D2FE_POSTPROC_B && cfg->postproc != D2FE_POSTPROC_A) return fail(D2FE_ERR_INVALID, "bad postproc");
+  if (cfg->variant_b_pca != 0 && cfg->variant_b_pca != 1) return fail(D2FE_ERR_INVALID, "variant_b_pca must be 0 or 1");
+  if (cfg->variant_b_pca && cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "variant_b_pca is an option of post-processing variant B (variant A applies the PCA without it)");
   if (cfg->exact_order) {
     if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2 and D2FE_PREC_F16 are not supported)");
     if (cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "exact_order needs post-processing variant B (NMS2 of variant A depends on the order in another way)");
@@ -612,8 +620,11 @@ int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean,
   if (h) graphs_clear(h);
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
   if (pca_dims < 0 || pca_dims > 256 || (pca_dims > 0 && (!comp || !mean))) return fail(D2FE_ERR_INVALID, "bad PCA arguments");
-  if (pca_dims > 0 && h->cfg.postproc != D2FE_POSTPROC_A)
+  if (pca_dims > 0 && h->cfg.postproc != D2FE_POSTPROC_A && !h->cfg.variant_b_pca)
     return fail(D2FE_ERR_UNSUPPORTED, "PCA is only applied by post-processing variant A (the reference's variant B never applies it)");
+  // variant B's rows feed the matcher, the pipes and the exchange blocks directly: their length keeps the matcher's 16-byte row alignment
+  if (pca_dims > 0 && h->cfg.postproc == D2FE_POSTPROC_B && (pca_dims < 4 || (pca_dims & 3)))
+    return fail(D2FE_ERR_INVALID, "variant B takes pca_dims in 4..256 that are multiples of 4 (the matcher's row alignment), or 0 to switch the PCA off");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (h->pca_comp_t) { hipFree(h->pca_comp_t); h->pca_comp_t = nullptr; }
@@ -633,7 +644,7 @@ int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean,
 
 int d2fe_desc_dim(d2fe_handle h) {
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  return (h->cfg.postproc == D2FE_POSTPROC_A && h->pca_dims) ? h->pca_dims : 256;
+  return desc_dim_of(h);
 }
 
 int d2fe_superpoint_extract_device(d2fe_handle h, const uint8_t* d_gray, int n, int width, int height, int stride,
@@ -710,7 +721,7 @@ static int extract_host(d2fe_handle h, const uint8_t* gray, int n, int width, in
   // the call's capacity, bounded by what can exist: H*W candidates (keep-all) or the configured maximum
   const long most = h->cfg.max_keypoints > 0 ? h->cfg.max_keypoints : (long)height * width;
   const int dcap = cap < most ? cap : (int)most;
-  const size_t D = (h->cfg.postproc == D2FE_POSTPROC_A && h->pca_dims) ? (size_t)h->pca_dims : 256;
+  const size_t D = (size_t)desc_dim_of(h);
   // outputs of the call, contiguous in one device block: kps [n][dcap][2] | scores [n][dcap] | desc [n][dcap][D] | counts [n] | idx [n][dcap]
   const size_t out_bytes = sizeof(float) * (size_t)n * dcap * (3 + D) + sizeof(int32_t) * n;
   const size_t need = out_bytes + sizeof(int32_t) * (size_t)n * dcap;
@@ -1095,24 +1106,33 @@ int d2fe_dequantize_int8(d2fe_handle h, const int8_t* q, int n, int landmark_num
   return codec_run(h, q, (size_t)n, out, sizeof(float) * (size_t)n, n, landmark_num, false);
 }
 
-int d2fe_block_field_offset(int cap, int netvlad_dim, int field) {
-  if (cap < 1 || netvlad_dim < 0 || field < 0 || field > 4) return fail(D2FE_ERR_INVALID, "bad argument");
-  const int off[5] = {0, cap * 256, cap * 258, cap * 259, cap * 259 + netvlad_dim};
+// desc_dim: 4..256, a multiple of 4 (rows stay 16-byte aligned behind the descriptors of a block)
+static bool block_dim_ok(int desc_dim) { return desc_dim >= 4 && desc_dim <= 256 && !(desc_dim & 3); }
+int d2fe_block_field_offset_d(int cap, int desc_dim, int netvlad_dim, int field) {
+  if (cap < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || field < 0 || field > 4) return fail(D2FE_ERR_INVALID, "bad argument");
+  const int off[5] = {0, cap * desc_dim, cap * (desc_dim + 2), cap * (desc_dim + 3), cap * (desc_dim + 3) + netvlad_dim};
   return off[field];
 }
-int d2fe_block_words(int cap, int netvlad_dim) {
-  if (cap < 1 || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad argument");
-  return (cap * 259 + netvlad_dim + 1 + 255) / 256 * 256;
+int d2fe_block_field_offset(int cap, int netvlad_dim, int field) { return d2fe_block_field_offset_d(cap, 256, netvlad_dim, field); }
+int d2fe_block_words_d(int cap, int desc_dim, int netvlad_dim) {
+  if (cap < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad argument");
+  return (cap * (desc_dim + 3) + netvlad_dim + 1 + 255) / 256 * 256;
+}
+int d2fe_block_words(int cap, int netvlad_dim) { return d2fe_block_words_d(cap, 256, netvlad_dim); }
+int d2fe_pack_blocks_device_d(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const float* d_scores, const int32_t* d_n,
+                              const float* d_netvlad, int row0, int row_step, int nframes, int cap, int desc_dim, int netvlad_dim, float* d_blocks,
+                              void* stream) {
+  if (!h || !d_desc || !d_kps_xy || !d_scores || !d_n || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
+  if (nframes < 1 || cap < 1 || row0 < 0 || row_step < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  HIP_TRY(launch_pack_blocks(d_desc, d_kps_xy, d_scores, d_n, d_netvlad, row0, row_step, nframes, cap, desc_dim, netvlad_dim,
+                             d2fe_block_words_d(cap, desc_dim, netvlad_dim), d_blocks, stream ? (hipStream_t)stream : h->stream));
+  return D2FE_OK;
 }
 int d2fe_pack_blocks_device(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const float* d_scores, const int32_t* d_n,
                             const float* d_netvlad, int row0, int row_step, int nframes, int cap, int netvlad_dim, float* d_blocks,
                             void* stream) {
-  if (!h || !d_desc || !d_kps_xy || !d_scores || !d_n || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
-  if (nframes < 1 || cap < 1 || row0 < 0 || row_step < 1 || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad geometry");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(launch_pack_blocks(d_desc, d_kps_xy, d_scores, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim,
-                             d2fe_block_words(cap, netvlad_dim), d_blocks, stream ? (hipStream_t)stream : h->stream));
-  return D2FE_OK;
+  return d2fe_pack_blocks_device_d(h, d_desc, d_kps_xy, d_scores, d_n, d_netvlad, row0, row_step, nframes, cap, 256, netvlad_dim, d_blocks, stream);
 }
 int d2fe_gate_pairs_device(d2fe_handle h, const float* d_q, size_t q_stride, const float* d_db, size_t db_stride, int dim,
                            const int32_t* d_pair_q, const int32_t* d_pair_db, int npairs, double thres, int32_t* d_cnt_inout,
@@ -1125,29 +1145,38 @@ int d2fe_gate_pairs_device(d2fe_handle h, const float* d_q, size_t q_stride, con
   return D2FE_OK;
 }
 
-int d2fe_block_bytes_int8(int cap, int netvlad_dim) {
-  if (cap < 1 || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad argument");
-  return (cap * 256 + netvlad_dim + cap * 8 + 4 + 63) / 64 * 64;
+int d2fe_block_bytes_int8_d(int cap, int desc_dim, int netvlad_dim) {
+  if (cap < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad argument");
+  return (cap * desc_dim + netvlad_dim + cap * 8 + 4 + 63) / 64 * 64;
+}
+int d2fe_block_bytes_int8(int cap, int netvlad_dim) { return d2fe_block_bytes_int8_d(cap, 256, netvlad_dim); }
+int d2fe_pack_blocks_int8_device_d(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const int32_t* d_n, const float* d_netvlad,
+                                   int row0, int row_step, int nframes, int cap, int desc_dim, int netvlad_dim, int8_t* d_blocks, void* stream) {
+  if (!h || !d_desc || !d_kps_xy || !d_n || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
+  if (nframes < 1 || cap < 1 || row0 < 0 || row_step < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad geometry");
+  if (((uintptr_t)d_desc & 15) || ((uintptr_t)d_blocks & 3)) return fail(D2FE_ERR_INVALID, "d_desc must be 16-byte aligned, d_blocks 4-byte aligned");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  HIP_TRY(launch_pack_blocks_int8(d_desc, d_kps_xy, d_n, d_netvlad, row0, row_step, nframes, cap, desc_dim, netvlad_dim,
+                                  d2fe_block_bytes_int8_d(cap, desc_dim, netvlad_dim), d_blocks, stream ? (hipStream_t)stream : h->stream));
+  return D2FE_OK;
 }
 int d2fe_pack_blocks_int8_device(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const int32_t* d_n, const float* d_netvlad,
                                  int row0, int row_step, int nframes, int cap, int netvlad_dim, int8_t* d_blocks, void* stream) {
-  if (!h || !d_desc || !d_kps_xy || !d_n || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
-  if (nframes < 1 || cap < 1 || row0 < 0 || row_step < 1 || netvlad_dim < 0 || (netvlad_dim & 3)) return fail(D2FE_ERR_INVALID, "bad geometry");
-  if (((uintptr_t)d_desc & 15) || ((uintptr_t)d_blocks & 3)) return fail(D2FE_ERR_INVALID, "d_desc must be 16-byte aligned, d_blocks 4-byte aligned");
+  return d2fe_pack_blocks_int8_device_d(h, d_desc, d_kps_xy, d_n, d_netvlad, row0, row_step, nframes, cap, 256, netvlad_dim, d_blocks, stream);
+}
+int d2fe_unpack_blocks_int8_device_d(d2fe_handle h, const int8_t* d_blocks_int8, int nblocks, int cap, int desc_dim, int netvlad_dim, int renorm,
+                                     float* d_blocks, void* stream) {
+  if (!h || !d_blocks_int8 || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
+  if (nblocks < 1 || cap < 1 || !block_dim_ok(desc_dim) || netvlad_dim < 0 || (netvlad_dim & 3) || (renorm != 0 && renorm != 1)) return fail(D2FE_ERR_INVALID, "bad geometry");
+  if (((uintptr_t)d_blocks & 15) || ((uintptr_t)d_blocks_int8 & 3)) return fail(D2FE_ERR_INVALID, "d_blocks must be 16-byte aligned, d_blocks_int8 4-byte aligned");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(launch_pack_blocks_int8(d_desc, d_kps_xy, d_n, d_netvlad, row0, row_step, nframes, cap, netvlad_dim,
-                                  d2fe_block_bytes_int8(cap, netvlad_dim), d_blocks, stream ? (hipStream_t)stream : h->stream));
+  HIP_TRY(launch_unpack_blocks_int8(d_blocks_int8, nblocks, cap, desc_dim, netvlad_dim, d2fe_block_bytes_int8_d(cap, desc_dim, netvlad_dim),
+                                    d2fe_block_words_d(cap, desc_dim, netvlad_dim), renorm, d_blocks, stream ? (hipStream_t)stream : h->stream));
   return D2FE_OK;
 }
 int d2fe_unpack_blocks_int8_device(d2fe_handle h, const int8_t* d_blocks_int8, int nblocks, int cap, int netvlad_dim, int renorm,
                                    float* d_blocks, void* stream) {
-  if (!h || !d_blocks_int8 || !d_blocks) return fail(D2FE_ERR_INVALID, "null argument");
-  if (nblocks < 1 || cap < 1 || netvlad_dim < 0 || (netvlad_dim & 3) || (renorm != 0 && renorm != 1)) return fail(D2FE_ERR_INVALID, "bad geometry");
-  if (((uintptr_t)d_blocks & 15) || ((uintptr_t)d_blocks_int8 & 3)) return fail(D2FE_ERR_INVALID, "d_blocks must be 16-byte aligned, d_blocks_int8 4-byte aligned");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(launch_unpack_blocks_int8(d_blocks_int8, nblocks, cap, netvlad_dim, d2fe_block_bytes_int8(cap, netvlad_dim),
-                                    d2fe_block_words(cap, netvlad_dim), renorm, d_blocks, stream ? (hipStream_t)stream : h->stream));
-  return D2FE_OK;
+  return d2fe_unpack_blocks_int8_device_d(h, d_blocks_int8, nblocks, cap, 256, netvlad_dim, renorm, d_blocks, stream);
 }
 
 int d2fe_quad_gate_device(d2fe_handle h, const float* d_local, size_t local_stride, const float* d_remote, size_t remote_stride, int dim,
@@ -1618,8 +1647,9 @@ int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int
   return D2FE_OK;
 }
 
-int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
-                        const int32_t* slotmap_or_null, int max_slots, float* desc_out) {
+// comp == nullptr: d2fe_debug_sample_b (rows of 256 floats); else d2fe_debug_sample_b_pca (rows of pca_dims floats)
+static int debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                          const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean, int pca_dims, float* desc_out) {
   if (!h || !desc_raw || !kps_xy || !n_kp || !desc_out) return fail(D2FE_ERR_INVALID, "null argument");
   if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
   const size_t ncell = (size_t)Hc * Wc;
@@ -1638,12 +1668,32 @@ int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int d
   HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
   HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, n_kp));
   if (slotmap_or_null) HIP_TRY(b.get((void**)&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
-  HIP_TRY(b.get((void**)&d_desc, sizeof(float) * 256 * n * cap, nullptr));
+  const size_t D = comp ? (size_t)pca_dims : 256;
+  float *d_comp_t = nullptr, *d_mean = nullptr;
+  if (comp) {      // the transposed layout d2fe_set_superpoint_pca uploads: comp_t [256][pca_dims]
+    std::vector<float> t((size_t)256 * pca_dims);
+    for (int j = 0; j < pca_dims; ++j)
+      for (int c = 0; c < 256; ++c) t[(size_t)c * pca_dims + j] = comp[(size_t)j * 256 + c];
+    HIP_TRY(b.get((void**)&d_comp_t, sizeof(float) * t.size(), t.data()));
+    HIP_TRY(b.get((void**)&d_mean, sizeof(float) * 256, mean));
+  }
+  HIP_TRY(b.get((void**)&d_desc, sizeof(float) * D * n * cap, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(launch_sample_b(d_raw, dstride, dcoff, Hc, Wc, n, d_kps, d_n, cap, d_map, max_slots, d_desc, h->stream));
+  HIP_TRY(launch_sample_b(d_raw, dstride, dcoff, Hc, Wc, n, d_kps, d_n, cap, d_map, max_slots, d_comp_t, d_mean, comp ? pca_dims : 0, d_desc, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * 256 * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * D * n * cap, hipMemcpyDeviceToHost));
   return D2FE_OK;
+}
+
+int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                        const int32_t* slotmap_or_null, int max_slots, float* desc_out) {
+  return debug_sample_b(h, desc_raw, dstride, dcoff, n, Hc, Wc, kps_xy, n_kp, cap, slotmap_or_null, max_slots, nullptr, nullptr, 0, desc_out);
+}
+
+int d2fe_debug_sample_b_pca(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                            const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean, int pca_dims, float* desc_out) {
+  if (!comp || !mean || pca_dims < 1 || pca_dims > 256) return fail(D2FE_ERR_INVALID, "comp, mean and pca_dims in 1..256 are required");
+  return debug_sample_b(h, desc_raw, dstride, dcoff, n, Hc, Wc, kps_xy, n_kp, cap, slotmap_or_null, max_slots, comp, mean, pca_dims, desc_out);
 }
 
 int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,

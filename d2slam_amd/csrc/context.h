@@ -205,6 +205,7 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
                    float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s, hipStream_t s_tail = nullptr, int bs = 0);
 int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_out, hipStream_t s);
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap);
+int desc_dim_of(const d2fe_context* h);      // floats per descriptor row: 256, or pca_dims where a PCA is set (d2fe_desc_dim)
 int nv_check(d2fe_context* h, int n, int W, int H, int stride);
 // a second context on the same device that BORROWS the parent's packed weights (SuperPoint, NetVLAD, PCA matrices) and owns its own
 // activations, scratch, counters and streams: one lane of the frames-in-flight pipeline.  d2fe_destroy() of a lane leaves the weights alone;

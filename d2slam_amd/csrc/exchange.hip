@@ -90,14 +90,14 @@ int wire_stream(const Wire& w, int64_t ticket, hipStream_t* st) {
 }
 
 int wire_round(const Wire& w, WireSlot& S, const TicketView& v, hipStream_t st) {
-  const int NB = w.NB, cap = w.cap, G = w.G;
+  const int NB = w.NB, cap = w.cap, D = w.D, G = w.G;
   const void* send; void* recv; size_t bytes;
   int r;
   if (w.int8) {
-    r = d2fe_pack_blocks_int8_device(w.h, v.d_desc, v.d_kps_xy, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, G, S.d_blocks_q, st); if (r) return r;
+    r = d2fe_pack_blocks_int8_device_d(w.h, v.d_desc, v.d_kps_xy, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, D, G, S.d_blocks_q, st); if (r) return r;
     send = S.d_blocks_q; recv = S.d_gath_q; bytes = (size_t)NB * w.BLKB;
   } else {
-    r = d2fe_pack_blocks_device(w.h, v.d_desc, v.d_kps_xy, v.d_scores, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, G, S.d_blocks, st); if (r) return r;
+    r = d2fe_pack_blocks_device_d(w.h, v.d_desc, v.d_kps_xy, v.d_scores, v.d_n_kp, v.d_netvlad, 0, 1, NB, cap, D, G, S.d_blocks, st); if (r) return r;
     send = S.d_blocks; recv = S.d_gath; bytes = sizeof(float) * (size_t)NB * w.BLK;
   }
   r = S.mark(1, st); if (r) return r;
@@ -109,7 +109,7 @@ int wire_round(const Wire& w, WireSlot& S, const TicketView& v, hipStream_t st) 
     if (r) return ctx_fail(D2FE_ERR_HIP, "the all-gather callback failed (" + std::to_string(r) + ")");
   }
   r = S.mark(2, st); if (r) return r;
-  if (w.int8) { r = d2fe_unpack_blocks_int8_device(w.h, S.d_gath_q, w.world * NB, cap, G, w.wire == D2FE_WIRE_INT8_RENORM256 ? 1 : 0, S.d_gath, st); if (r) return r; }
+  if (w.int8) { r = d2fe_unpack_blocks_int8_device_d(w.h, S.d_gath_q, w.world * NB, cap, D, G, w.wire == D2FE_WIRE_INT8_RENORM256 ? 1 : 0, S.d_gath, st); if (r) return r; }
   return D2FE_OK;
 }
 }  // namespace d2fe
@@ -200,18 +200,18 @@ int d2fe_exchange_create(d2fe_pipe p, void* nccl_comm, const d2fe_exchange_confi
     const int rc = d2fe_pipe_geometry(p, &pf, &pcap, &pdim, &pg);
     if (rc) return rc;
   }
-  if (pdim != 256) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the exchange blocks hold 256-float descriptors (a pipe with descriptor PCA cannot be exchanged)");
+  if (pdim < 4 || pdim > 256 || (pdim & 3)) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the exchange blocks hold descriptors of 4..256 floats, a multiple of 4");
   auto* x = new (std::nothrow) d2fe_exchange_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_exchange_s* x; bool ok = false; ~Guard() { if (!ok) d2fe_exchange_destroy(x); } } guard{x};
   x->cfg = cfg; x->F = pf;
-  { const int rc = wire_init(*x, p, nccl_comm, cfg, pf, pcap, pg); if (rc) return rc; }
-  if (x->int8 && (pcap * 256 + pg + pcap * 8) % 4) return ctx_fail(D2FE_ERR_UNSUPPORTED, "int8 blocks of this capacity / NetVLAD size do not keep their count word aligned");
-  x->own_n_word = x->int8 ? (pcap * 256 + pg + pcap * 8) / 4 : x->n_off;
+  { const int rc = wire_init(*x, p, nccl_comm, cfg, pf, pcap, pdim, pg); if (rc) return rc; }
+  if ((long)cfg.world * pf * x->rows > 0x7fffffffL / 2) return ctx_fail(D2FE_ERR_INVALID, "the gathered buffer exceeds the matcher's 32-bit row offsets");
+  x->own_n_word = x->int8 ? (pcap * pdim + pg + pcap * 8) / 4 : x->n_off;
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
   // pair layout: local left frame f against the frame with the same time index of every other rank, rank-major (swarm.remote_pair_layout)
   std::vector<int32_t> a_off, b_off, qf, rb;
-  const int rows = x->BLK / 256;
+  const int rows = x->rows;
   for (int r = 0; r < cfg.world; ++r) {
     if (r == cfg.rank && !cfg.loopback) continue;
     for (int f = 0; f < pf; ++f) { a_off.push_back(f * pcap); b_off.push_back((r * pf + f) * rows); qf.push_back(f); rb.push_back(r * pf + f); }
@@ -259,7 +259,7 @@ int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
   hipStream_t st = nullptr;
   { const int rc = wire_stream(*x, ticket, &st); if (rc) return rc; }
   const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
-    if (v.frames != x->F || v.cap != x->cap || v.desc_dim != 256) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
+    if (v.frames != x->F || v.cap != x->cap || v.desc_dim != x->D) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
     auto mark = [&](int i) { return S.mark(i, st); };
     int r = mark(0); if (r) return r;
     r = wire_round(*x, S, v, st); if (r) return r;
@@ -282,7 +282,7 @@ int d2fe_exchange_enqueue(d2fe_exchange x, int64_t ticket, int slot) {
     if (x->NR > 0) {
       d2fe_match_batch mb{};
       mb.d_a = v.d_desc; mb.d_b = S.d_gath; mb.d_a_off = x->d_a_off; mb.d_b_off = x->d_b_off; mb.d_a_cnt = S.d_a_cnt; mb.d_b_cnt = S.d_b_cnt;
-      mb.npairs = x->NR; mb.dim = 256; mb.max_n = cap; mb.mode = 0; mb.ratio = x->cfg.ratio; mb.radius = -1.0;
+      mb.npairs = x->NR; mb.dim = x->D; mb.max_n = cap; mb.mode = 0; mb.ratio = x->cfg.ratio; mb.radius = -1.0;
       mb.d_q_idx = O + x->o_mq; mb.d_t_idx = O + x->o_mt; mb.d_dist = S.d_out + x->o_md; mb.d_n_out = O + x->o_mn;
       r = d2fe_match_batch_device(x->h, &mb, st); if (r) return r;
     }

@@ -39,7 +39,8 @@ struct Wire {
   void* comm = nullptr;                                                    // ncclComm_t, or null: the callback
   d2fe_all_gather_fn all_gather = nullptr; void* all_gather_user = nullptr;
   int world = 1, wire = D2FE_WIRE_FP32;
-  int NB = 0, cap = 0, G = 0;                                              // blocks this rank sends per round (stereo: frames; quad: 4 * quads), their geometry
+  int NB = 0, cap = 0, D = 256, G = 0;                                     // blocks this rank sends per round (stereo: frames; quad: 4 * quads), their geometry (D: floats per descriptor row)
+  int rows = 0;                                                            // descriptor rows (of D floats) one fp32 block spans: the matcher's offsets count them
   int BLK = 0, BLKB = 0, n_off = 0, g_off = 0;                             // words of an fp32 block, bytes of an int8 one, the count and NetVLAD fields of an fp32 block
   bool int8 = false;
   hipStream_t own = nullptr;       // cfg.own_stream: the one stream of its own (round 5's placement), else the lanes' streams
@@ -54,15 +55,20 @@ int wire_check_config(const Cfg& cfg, bool own_bad, const void* nccl_comm, const
   if (!nccl_comm && !cfg.all_gather) return ctx_fail(D2FE_ERR_INVALID, "neither an RCCL communicator nor an all-gather callback");
   return D2FE_OK;
 }
-// the geometry of the blocks of a pipe with n_blocks rows of `cap` keypoints and a G-float NetVLAD descriptor per round
+// the geometry of the blocks of a pipe with n_blocks rows of `cap` keypoints of D floats and a G-float NetVLAD descriptor per round
 template <class Cfg>
-int wire_init(Wire& w, PipeRef pipe, void* nccl_comm, const Cfg& cfg, int n_blocks, int cap, int G) {
+int wire_init(Wire& w, PipeRef pipe, void* nccl_comm, const Cfg& cfg, int n_blocks, int cap, int D, int G) {
   w.pipe = pipe; w.h = pipe.handle(); w.comm = nccl_comm; w.all_gather = cfg.all_gather; w.all_gather_user = cfg.all_gather_user;
   w.world = cfg.world; w.wire = cfg.wire; w.int8 = cfg.wire != D2FE_WIRE_FP32;
-  w.NB = n_blocks; w.cap = cap; w.G = G;
-  w.BLK = d2fe_block_words(cap, G); w.BLKB = d2fe_block_bytes_int8(cap, G);
-  if (w.BLK < 0 || w.BLKB < 0) return D2FE_ERR_INVALID;      // d2fe_block_words has said why
-  w.n_off = d2fe_block_field_offset(cap, G, 4); w.g_off = d2fe_block_field_offset(cap, G, 3);
+  w.NB = n_blocks; w.cap = cap; w.D = D; w.G = G;
+  w.BLK = d2fe_block_words_d(cap, D, G); w.BLKB = d2fe_block_bytes_int8_d(cap, D, G);
+  if (w.BLK < 0 || w.BLKB < 0) return D2FE_ERR_INVALID;      // d2fe_block_words_d has said why
+  // the matcher addresses the b side in place, in rows of D floats from the start of the gathered buffer: every block must start on a row (256 % D == 0: D = 4 .. 256
+  // in powers of two, 64 among them; any other width that happens to divide the block)
+  if (w.BLK % D) return ctx_fail(D2FE_ERR_UNSUPPORTED, "blocks of " + std::to_string(w.BLK) + " words do not start on a descriptor row of " + std::to_string(D) + " floats: the matcher cannot read them in place");
+  w.rows = w.BLK / D;
+  if (w.int8 && (cap * D + G + cap * 8) % 4) return ctx_fail(D2FE_ERR_UNSUPPORTED, "int8 blocks of this capacity / descriptor width / NetVLAD size do not keep their count word aligned");
+  w.n_off = d2fe_block_field_offset_d(cap, D, G, 4); w.g_off = d2fe_block_field_offset_d(cap, D, G, 3);
   return D2FE_OK;
 }
 int wire_alloc_blocks(const Wire& w, WireSlot& S);      // the blocks of one slot, zeroed

@@ -350,6 +350,44 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 __device__ __forceinline__ int clipi(int v, int mx) { return v < 0 ? 0 : (v < mx - 1 ? v : mx - 1); }
 
+// The PCA tail of one keypoint's descriptor, one wave: computeDescriptors' (T - mean) * comp^T followed by the row L2 (superpoint_common.cpp:76-85).  Shared by
+// variant A (finish_a_kernel) and by variant B with d2fe_config.variant_b_pca (sample_b_pca_kernel), so that the two cannot drift apart.
+//   t    : the 256 centred values d[c] - mean[c], in LDS, written by this wave
+//   comp : comp(c4, j) = the four entries comp_t[4 c4 .. 4 c4 + 3][j] -- global memory in A, a staged column tile in B
+//   [j0, j1): the output columns this call covers (A: all of them; B: one 64-column tile per call, ascending); out: the keypoint's row of pca_dims floats
+// Lane l (and l + 64, ...) owns column j: a[j] = ((0 + t[0] * comp[0][j]) + t[1] * comp[1][j]) + ..., c ascending, every product and every sum rounded to fp32.
+// pca_dims <= 64 (every shipped configuration): s2 = the xor-butterfly sum of a[j]^2 over the wave, out[j] = a[j] / sqrtf(s2).  Above 64 the unnormalised
+// a[j] go to `out` first and the call that covers the last column reads them back: each lane sums ITS columns' squares ascending, then the butterfly, then divides.
+// No guards: a NaN input row, or t == 0, gives NaN in every component -- as the reference's expression does.
+template <class Comp>
+__device__ __forceinline__ void pca_tail(const float* t, Comp comp, int j0, int j1, int pca_dims, int lane, float* __restrict__ out) {
+  for (int jb = j0; jb < j1; jb += 64) {
+    const int j = jb + lane;
+    float a = 0.f;
+    if (j < pca_dims)
+      for (int c4 = 0; c4 < 64; ++c4) {
+        const f32x4 w = comp(c4, j);
+        const f32x4 tv = *reinterpret_cast<const f32x4*>(t + 4 * c4);
+        a += tv[0] * w[0]; a += tv[1] * w[1]; a += tv[2] * w[2]; a += tv[3] * w[3];
+      }
+    const float s2 = wave_sum(j < pca_dims ? a * a : 0.f);
+    if (pca_dims <= 64) {
+      const float n2 = __builtin_sqrtf(s2);
+      if (j < pca_dims) out[j] = a / n2;
+    } else {
+      if (j < pca_dims) out[j] = a;
+    }
+  }
+  if (pca_dims > 64 && j1 >= pca_dims) {
+    __builtin_amdgcn_wave_barrier();
+    float s2 = 0.f;
+    for (int j = lane; j < pca_dims; j += 64) { const float a = out[j]; s2 += a * a; }
+    s2 = wave_sum(s2);
+    const float n2 = __builtin_sqrtf(s2);
+    for (int j = lane; j < pca_dims; j += 64) out[j] = out[j] / n2;
+  }
+}
+
 // The four corner cells and weights of one keypoint -- literal transcription of the reference's mixed float/double arithmetic
 // (normalize_keypoints + grid_sample, superpoint_tensorrt.cpp:255-310; see orc_sample_b).  Shared by the sampler and by the
 // kernel that marks which cells of the descriptor map are needed at all.
@@ -378,16 +416,10 @@ __device__ __forceinline__ SampleBCorners sample_b_corners(float x, float y, int
 
 // slotmap == nullptr: desc_raw is the dense map [img][Hc*Wc][dstride] (+dcoff).  slotmap != nullptr: desc_raw is the SPARSE
 // descriptor store [img][max_slots][256] and slotmap[img][cell] the slot of a cell (desc_head_sparse_kernel).
-__global__ __launch_bounds__(256) void sample_b_kernel(const float* __restrict__ desc_raw, int dstride, int dcoff, int Hc,
-                                                       int Wc, const float* __restrict__ kps_xy,
-                                                       const int32_t* __restrict__ n_kp, int cap,
-                                                       const int32_t* __restrict__ slotmap, int max_slots,
-                                                       float* __restrict__ desc_out) {
-  const int img = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (k >= n_kp[img] || k >= cap) return;
-  const size_t o = (size_t)img * cap + k;
+// One keypoint, one wave: lane l returns the channels 4 l .. 4 l + 3 of the sampled, row-normalised descriptor (o = img * cap + k).
+__device__ __forceinline__ f32x4 sample_b_row(const float* __restrict__ desc_raw, int dstride, int dcoff, int Hc, int Wc,
+                                              const float* __restrict__ kps_xy, const int32_t* __restrict__ slotmap, int max_slots, int img,
+                                              size_t o, int lane) {
   const SampleBCorners c = sample_b_corners(kps_xy[2 * o], kps_xy[2 * o + 1], Hc, Wc);
   f32x4 v[4];
   float nrm[4];
@@ -414,7 +446,73 @@ __global__ __launch_bounds__(256) void sample_b_kernel(const float* __restrict__
   const float ninv = (float)(1.0 / (double)__builtin_sqrtf(ss));
 #pragma unroll
   for (int j = 0; j < 4; ++j) d[j] = d[j] * ninv;
+  return d;
+}
+
+__global__ __launch_bounds__(256) void sample_b_kernel(const float* __restrict__ desc_raw, int dstride, int dcoff, int Hc,
+                                                       int Wc, const float* __restrict__ kps_xy,
+                                                       const int32_t* __restrict__ n_kp, int cap,
+                                                       const int32_t* __restrict__ slotmap, int max_slots,
+                                                       float* __restrict__ desc_out) {
+  const int img = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= n_kp[img] || k >= cap) return;
+  const size_t o = (size_t)img * cap + k;
+  const f32x4 d = sample_b_row(desc_raw, dstride, dcoff, Hc, Wc, kps_xy, slotmap, max_slots, img, o, lane);
   *reinterpret_cast<f32x4*>(desc_out + o * 256 + lane * 4) = d;
+}
+
+// Variant B with the descriptor PCA (d2fe_config.variant_b_pca): sample_b_row's 256 values -- the bits sample_b_kernel writes -- go through variant A's
+// tail (pca_tail) instead of to memory.  finish_a_kernel streams comp_t [256][pca_dims] from L2 once per keypoint (64 KB per wave at 64 dims); here a workgroup
+// stages one 64-column tile of it in LDS ONCE and walks PCAB_K keypoints through it, four per wave: 4 KB of L2 traffic per keypoint.  pca_dims above 64: one
+// tile after the other, the centred rows kept in LDS in between.  64 KB tile + 16 KB rows: two workgroups per CU.
+// Tile layout: tile[c4][lane] = f32x4 {comp_t[4 c4 + e][j0 + lane]}: lane l reads 16 bytes at (c4 * 64 + l) * 16 -- within each of ds_read_b128's 16-lane groups
+// the lanes are distinct modulo 16, so the 64 banks are each touched once: conflict-free, 256 B/clk; the centred row is read as a 16-byte broadcast.
+// A keypoint's chain does not depend on which workgroup, wave or launch carries it: its bits are independent of batch, entry point and pipe shape.
+constexpr int PCAB_K = 16;
+__global__ __launch_bounds__(256) void sample_b_pca_kernel(const float* __restrict__ desc_raw, int dstride, int dcoff, int Hc, int Wc,
+                                                           const float* __restrict__ kps_xy, const int32_t* __restrict__ n_kp, int cap,
+                                                           const int32_t* __restrict__ slotmap, int max_slots,
+                                                           const float* __restrict__ comp_t, const float* __restrict__ mean, int pca_dims,
+                                                           float* __restrict__ desc_out) {
+  __shared__ f32x4 tile[64 * 64];
+  __shared__ __attribute__((aligned(16))) float st[PCAB_K][256];
+  const int img = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nk = min(n_kp[img], cap);
+  const int k0 = blockIdx.x * PCAB_K;
+  if (k0 >= nk) return;                                   // workgroup-uniform: nothing below is reached by a part of the workgroup only
+  const f32x4 m4 = *reinterpret_cast<const f32x4*>(mean + lane * 4);
+#pragma unroll 1
+  for (int i = 0; i < PCAB_K / 4; ++i) {
+    const int kk = i * 4 + wv, k = k0 + kk;
+    if (k >= nk) continue;
+    const f32x4 d = sample_b_row(desc_raw, dstride, dcoff, Hc, Wc, kps_xy, slotmap, max_slots, img, (size_t)img * cap + k, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) st[kk][lane * 4 + j] = d[j] - m4[j];
+  }
+  for (int j0 = 0; j0 < pca_dims; j0 += 64) {
+    __syncthreads();                                      // the previous tile has been read by every wave
+    const int wdt = min(64, pca_dims - j0);
+    for (int i = tid; i < 64 * 64; i += 256) {
+      const int c4 = i >> 6, jl = i & 63;
+      f32x4 w = {0.f, 0.f, 0.f, 0.f};
+      if (jl < wdt) {
+        const float* p = comp_t + (size_t)(4 * c4) * pca_dims + j0 + jl;
+        w = f32x4{p[0], p[pca_dims], p[2 * (size_t)pca_dims], p[3 * (size_t)pca_dims]};
+      }
+      tile[i] = w;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int i = 0; i < PCAB_K / 4; ++i) {
+      const int kk = i * 4 + wv, k = k0 + kk;
+      if (k >= nk) continue;
+      pca_tail(st[kk], [&](int c4, int) { return tile[c4 * 64 + lane]; }, j0, j0 + wdt, pca_dims, lane,
+               desc_out + ((size_t)img * cap + k) * pca_dims);
+    }
+  }
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -733,8 +831,15 @@ hipError_t launch_desc_head_sparse(const float* kps_xy, const int32_t* n_kp, int
   return hipGetLastError();
 }
 
+// comp_t != nullptr (pca_dims in 1..256): desc_out is [n_img][cap][pca_dims], written by sample_b_pca_kernel
 hipError_t launch_sample_b(const float* desc_raw, int dstride, int dcoff, int Hc, int Wc, int n_img, const float* kps_xy,
-                           const int32_t* n_kp, int cap, const int32_t* slotmap, int max_slots, float* desc_out, hipStream_t s) {
+                           const int32_t* n_kp, int cap, const int32_t* slotmap, int max_slots, const float* comp_t, const float* mean,
+                           int pca_dims, float* desc_out, hipStream_t s) {
+  if (comp_t) {
+    hipLaunchKernelGGL(sample_b_pca_kernel, dim3((cap + PCAB_K - 1) / PCAB_K, n_img), dim3(256), 0, s, desc_raw, dstride, dcoff, Hc, Wc, kps_xy, n_kp,
+                       cap, slotmap, max_slots, comp_t, mean, pca_dims, desc_out);
+    return hipGetLastError();
+  }
   dim3 grid((cap + 3) / 4, n_img), block(256);
   hipLaunchKernelGGL(sample_b_kernel, grid, block, 0, s, desc_raw, dstride, dcoff, Hc, Wc, kps_xy, n_kp, cap, slotmap, max_slots,
                      desc_out);
@@ -923,7 +1028,7 @@ __global__ __launch_bounds__(256) void finish_a_kernel(const float* __restrict__
                                                        const int32_t* __restrict__ n_kp, int cap, int scap,
                                                        const float* __restrict__ comp_t, const float* __restrict__ mean,
                                                        int pca_dims, float* __restrict__ desc_out) {
-  __shared__ float sd[4][256];
+  __shared__ __attribute__((aligned(16))) float sd[4][256];
   const int img = blockIdx.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int k = blockIdx.x * 4 + wv;
@@ -944,29 +1049,10 @@ __global__ __launch_bounds__(256) void finish_a_kernel(const float* __restrict__
 #pragma unroll
   for (int j = 0; j < 4; ++j) sd[wv][lane * 4 + j] = d[j] - mean[lane * 4 + j];
   __builtin_amdgcn_wave_barrier();
-  // lane j (and j+64, ...) computes output component j
-  for (int j0 = 0; j0 < pca_dims; j0 += 64) {
-    const int j = j0 + lane;
-    float a = 0.f;
-    if (j < pca_dims)
-      for (int c = 0; c < 256; ++c) a += sd[wv][c] * comp_t[(size_t)c * pca_dims + j];
-    float s2 = wave_sum(j < pca_dims ? a * a : 0.f);
-    // pca_dims <= 64 in every shipped config; for larger dims the norm needs all chunks: accumulate first
-    if (pca_dims <= 64) {
-      const float n2 = __builtin_sqrtf(s2);
-      if (j < pca_dims) desc_out[o * pca_dims + j] = a / n2;
-    } else {
-      if (j < pca_dims) desc_out[o * pca_dims + j] = a;
-    }
-  }
-  if (pca_dims > 64) {
-    __builtin_amdgcn_wave_barrier();
-    float s2 = 0.f;
-    for (int j = lane; j < pca_dims; j += 64) { const float a = desc_out[o * pca_dims + j]; s2 += a * a; }
-    s2 = wave_sum(s2);
-    const float n2 = __builtin_sqrtf(s2);
-    for (int j = lane; j < pca_dims; j += 64) desc_out[o * pca_dims + j] = desc_out[o * pca_dims + j] / n2;
-  }
+  pca_tail(sd[wv], [&](int c4, int j) {
+             const float* p = comp_t + (size_t)(4 * c4) * pca_dims + j;
+             return f32x4{p[0], p[pca_dims], p[2 * (size_t)pca_dims], p[3 * (size_t)pca_dims]};
+           }, 0, pca_dims, pca_dims, lane, desc_out + o * pca_dims);
 }
 
 // samp: scratch [n_img][scap][256]; cn: scratch [n_img][256]

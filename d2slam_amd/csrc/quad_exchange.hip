@@ -31,7 +31,7 @@ struct QuadPrepArgs {
   const int32_t* loc_n;         // the view's d_n_kp [4 Q]
   const float* gath;            // gathered fp32 blocks [world][4 Q][blk_words]
   const int32_t* job_rank; const int32_t* job_quad;      // [njobs]
-  int njobs, Q, cap, G, blk_words, g_off, n_off, gated, vec_l, vec_r;
+  int njobs, Q, cap, G, blk_words, blk_rows, g_off, n_off, gated, vec_l, vec_r;      // blk_rows: descriptor rows one block spans (blk_words / desc_dim)
   double thres;
   int32_t *a_off, *b_off, *a_cnt, *b_cnt;                // the matcher's problem table [njobs * (16 | 4)]
   int32_t *local_view, *remote_view;                     // [njobs * (16 | 4)]
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void quad_exchange_prepare_kernel(QuadPrepArgs
       const int lrow = lrow0 + (on ? lv : 0), rblk = rblk0 + (on ? rv : 0);
       const int na = a.loc_n[lrow], nb = reinterpret_cast<const int32_t*>(a.gath)[(size_t)rblk * a.blk_words + a.n_off];
       a.a_off[p] = lrow * a.cap;
-      a.b_off[p] = rblk * (a.blk_words >> 8);
+      a.b_off[p] = rblk * a.blk_rows;
       a.a_cnt[p] = on ? max(0, min(na, a.cap)) : 0;
       a.b_cnt[p] = on ? max(0, min(nb, a.cap)) : 0;
       a.local_view[p] = on ? lv : -1;
@@ -178,14 +178,14 @@ int d2fe_quad_exchange_create(d2fe_quad_pipe p, void* nccl_comm, const d2fe_quad
     if (rc) return rc;
   }
   if (cfg.mode == D2FE_QUAD_GATED && pg == 0) return ctx_fail(D2FE_ERR_INVALID, "gated mode needs the pipe's NetVLAD (d2fe_quad_pipe_config.netvlad = 1)");
-  if (pdim != 256) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the exchange blocks hold 256-float descriptors (a pipe with descriptor PCA cannot be exchanged)");
+  if (pdim < 4 || pdim > 256 || (pdim & 3)) return ctx_fail(D2FE_ERR_UNSUPPORTED, "the exchange blocks hold descriptors of 4..256 floats, a multiple of 4");
   if (nccl_comm) { const int rc = rccl_load(nullptr); if (rc) return rc; }
   auto* x = new (std::nothrow) d2fe_quad_exchange_s();
   if (!x) return ctx_fail(D2FE_ERR_HIP, "out of memory");
   struct Guard { d2fe_quad_exchange_s* x; bool ok = false; ~Guard() { if (!ok) d2fe_quad_exchange_destroy(x); } } guard{x};
   x->cfg = cfg; x->Q = pq;
-  { const int rc = wire_init(*x, p, nccl_comm, cfg, 4 * pq, pcap, pg); if (rc) return rc; }
-  if ((long)cfg.world * x->NB * (x->BLK / 256) > 0x7fffffffL / 2) return ctx_fail(D2FE_ERR_INVALID, "the gathered buffer exceeds the matcher's 32-bit row offsets");
+  { const int rc = wire_init(*x, p, nccl_comm, cfg, 4 * pq, pcap, pdim, pg); if (rc) return rc; }
+  if ((long)cfg.world * x->NB * x->rows > 0x7fffffffL / 2) return ctx_fail(D2FE_ERR_INVALID, "the gathered buffer exceeds the matcher's 32-bit row offsets");
   HIP_TRY(hipSetDevice(x->h->cfg.device_id));
   x->NJ = d2fe_quad_exchange_job_layout(cfg.world, cfg.rank, pq, cfg.loopback, nullptr, nullptr, 0);
   if (x->NJ < 1) return ctx_fail(D2FE_ERR_INVALID, "no jobs");
@@ -235,7 +235,7 @@ int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
   hipStream_t st = nullptr;
   { const int rc = wire_stream(*x, ticket, &st); if (rc) return rc; }
   const int rc = with_view(x->pipe, ticket, st, [&](const TicketView& v) -> int {
-    if (v.frames != x->Q || v.cap != x->cap || v.desc_dim != 256 || v.netvlad_dim != x->G) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
+    if (v.frames != x->Q || v.cap != x->cap || v.desc_dim != x->D || v.netvlad_dim != x->G) return ctx_fail(D2FE_ERR_INVALID, "the pipe's geometry changed under the exchange");
     auto mark = [&](int i) { return S.mark(i, st); };
     int r = mark(0); if (r) return r;
     r = wire_round(*x, S, v, st); if (r) return r;
@@ -244,7 +244,7 @@ int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
     const int NP = x->NP;
     QuadPrepArgs a{};
     a.loc_nv = v.d_netvlad; a.loc_n = v.d_n_kp; a.gath = S.d_gath; a.job_rank = x->d_job_rank; a.job_quad = x->d_job_quad;
-    a.njobs = x->NJ; a.Q = x->Q; a.cap = cap; a.G = G; a.blk_words = x->BLK; a.g_off = x->g_off; a.n_off = x->n_off; a.gated = x->cfg.mode == D2FE_QUAD_GATED ? 1 : 0;
+    a.njobs = x->NJ; a.Q = x->Q; a.cap = cap; a.G = G; a.blk_words = x->BLK; a.blk_rows = x->rows; a.g_off = x->g_off; a.n_off = x->n_off; a.gated = x->cfg.mode == D2FE_QUAD_GATED ? 1 : 0;
     a.vec_l = G && !((uintptr_t)v.d_netvlad & 15) && !(G & 3) ? 1 : 0;
     a.vec_r = G && !((uintptr_t)(S.d_gath + x->g_off) & 15) && !(x->BLK & 3) ? 1 : 0;
     a.thres = x->cfg.gate_thres;
@@ -255,7 +255,7 @@ int d2fe_quad_exchange_enqueue(d2fe_quad_exchange x, int64_t ticket, int slot) {
     r = mark(3); if (r) return r;
     d2fe_match_batch mb{};
     mb.d_a = v.d_desc; mb.d_b = S.d_gath; mb.d_a_off = a.a_off; mb.d_b_off = a.b_off; mb.d_a_cnt = a.a_cnt; mb.d_b_cnt = a.b_cnt;
-    mb.npairs = NP; mb.dim = 256; mb.max_n = cap; mb.mode = 0; mb.ratio = x->cfg.ratio; mb.radius = -1.0;
+    mb.npairs = NP; mb.dim = x->D; mb.max_n = cap; mb.mode = 0; mb.ratio = x->cfg.ratio; mb.radius = -1.0;
     mb.d_q_idx = O + x->o_mq; mb.d_t_idx = O + x->o_mt; mb.d_dist = S.d_out + x->o_md; mb.d_n_out = O + x->o_mn;
     r = d2fe_match_batch_device(x->h, &mb, st); if (r) return r;
     return mark(4);

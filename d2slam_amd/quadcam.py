@@ -39,7 +39,8 @@ class QuadcamChain:
         # descriptor / point pools in rows of `cap`: [0, NI) current views, [NI, 2NI) previous views, [2NI, 2NI + 8Q) half-image jobs
         NJ = 8 * Q
         self.NJ = NJ
-        self.desc = torch.zeros((2 * NI + NJ, cap, 256), dtype=f32, device=dev)
+        self.D = fe.desc_dim                     # floats per descriptor row: the handle's (a descriptor PCA narrows it)
+        self.desc = torch.zeros((2 * NI + NJ, cap, self.D), dtype=f32, device=dev)
         self.pts = torch.zeros((2 * NI + NJ, cap, 2), dtype=f32, device=dev)
         self.cnt = torch.zeros((2 * NI + NJ,), dtype=i32, device=dev)
         self.scores = torch.zeros((NI, cap), dtype=f32, device=dev)
@@ -86,17 +87,17 @@ class QuadcamChain:
         fe, torch, NI, cap = self.fe, self.torch, self.NI, self.cap
         job0 = 2 * NI
         fe.half_image_compact_device(self.desc.data_ptr(), self.pts.data_ptr(), self.cnt.data_ptr(), self.job_row.data_ptr(), self.job_left.data_ptr(),
-                                     self.job_shift.data_ptr(), self.NJ, cap, 256, self.UW, self.fov,
+                                     self.job_shift.data_ptr(), self.NJ, cap, self.D, self.UW, self.fov,
                                      self.desc[job0:].data_ptr(), self.pts[job0:].data_ptr(), self.maps.data_ptr(), self.cnt[job0:].data_ptr(), stream=st)
         torch.index_select(self.cnt, 0, self.a_row, out=self.a_cnt); torch.index_select(self.cnt, 0, self.b_row, out=self.b_cnt)
         nb = self.n_nb
         # neighbour pairs: radius gate on the shifted points; temporal pairs: whole image, no gate (two launches: the radius is per call)
         fe.match_batch_device(self.desc.data_ptr(), self.desc.data_ptr(), self.a_off.data_ptr(), self.b_off.data_ptr(), self.a_cnt.data_ptr(),
-                              self.b_cnt.data_ptr(), nb, 256, cap, self.mq.data_ptr(), self.mt.data_ptr(), self.md.data_ptr(), self.mn.data_ptr(),
+                              self.b_cnt.data_ptr(), nb, self.D, cap, self.mq.data_ptr(), self.mt.data_ptr(), self.md.data_ptr(), self.mn.data_ptr(),
                               mode=0, ratio=self.ratio, radius=self.radius, d_pts_a=self.pts.data_ptr(), d_pts_b=self.pts.data_ptr(), stream=st)
         fe.remap_matches_device(self.mq.data_ptr(), self.mt.data_ptr(), self.mn.data_ptr(), self.map_a.data_ptr(), self.map_b.data_ptr(),
                                 self.maps.data_ptr(), nb, cap, cap, stream=st)
         nt = self.NP - nb
         fe.match_batch_device(self.desc.data_ptr(), self.desc.data_ptr(), self.a_off[nb:].data_ptr(), self.b_off[nb:].data_ptr(),
-                              self.a_cnt[nb:].data_ptr(), self.b_cnt[nb:].data_ptr(), nt, 256, cap, self.mq[nb:].data_ptr(), self.mt[nb:].data_ptr(),
+                              self.a_cnt[nb:].data_ptr(), self.b_cnt[nb:].data_ptr(), nt, self.D, cap, self.mq[nb:].data_ptr(), self.mt[nb:].data_ptr(),
                               self.md[nb:].data_ptr(), self.mn[nb:].data_ptr(), mode=0, ratio=self.ratio, radius=-1.0, stream=st)

@@ -21,18 +21,19 @@ import torch
 import torch.distributed as dist
 
 
-def block_words(cap: int, netvlad_dim: int) -> int:
-    """Mirror of d2fe_block_words (api.hip): float words of one block."""
-    return (cap * 259 + netvlad_dim + 1 + 255) // 256 * 256
+def block_words(cap: int, netvlad_dim: int, desc_dim: int = 256) -> int:
+    """Mirror of d2fe_block_words_d (api.hip): float words of one block of desc_dim-float descriptors."""
+    return (cap * (desc_dim + 3) + netvlad_dim + 1 + 255) // 256 * 256
 
 
-def block_bytes_int8(cap: int, netvlad_dim: int) -> int:
-    """Mirror of d2fe_block_bytes_int8: desc_q[cap][256] | netvlad_q[G] | kps f32[cap][2] | n int32, padded to 64 bytes."""
-    return (cap * 256 + netvlad_dim + cap * 8 + 4 + 63) // 64 * 64
+def block_bytes_int8(cap: int, netvlad_dim: int, desc_dim: int = 256) -> int:
+    """Mirror of d2fe_block_bytes_int8_d: desc_q[cap][D] | netvlad_q[G] | kps f32[cap][2] | n int32, padded to 64 bytes."""
+    return (cap * desc_dim + netvlad_dim + cap * 8 + 4 + 63) // 64 * 64
 
 
-def block_field_offset(cap: int, netvlad_dim: int, field: str) -> int:
-    return {"desc": 0, "kps": cap * 256, "scores": cap * 258, "netvlad": cap * 259, "n": cap * 259 + netvlad_dim}[field]
+def block_field_offset(cap: int, netvlad_dim: int, field: str, desc_dim: int = 256) -> int:
+    return {"desc": 0, "kps": cap * desc_dim, "scores": cap * (desc_dim + 2), "netvlad": cap * (desc_dim + 3),
+            "n": cap * (desc_dim + 3) + netvlad_dim}[field]
 
 
 class PairList:

@@ -105,7 +105,14 @@ typedef struct {
                                  (softmax .. descriptors) on the handle's tail stream (d2fe_tail_stream), so that it runs UNDER the
                                  convolutions of the next call; outputs are complete on the tail stream -- enqueue consumers there, or
                                  call d2fe_superpoint_wait_tail(h, stream).  Host-pointer calls are unaffected.  Default 0. */
-  int32_t reserved[5];
+  int32_t variant_b_pca;      /* 1 (variant B only; on a variant-A handle D2FE_ERR_INVALID at create: A needs no opt-in): d2fe_set_superpoint_pca is accepted and the
+                                 sampled descriptors go through variant A's PCA tail (the projection the reference's variant B loads and never applies,
+                                 superpoint_tensorrt.cpp:400-448): every extract call, pipe, list, store and exchange of the handle then carries
+                                 rows of pca_dims floats.  Works with every precision, exact_order, keep-all, the dense and the sparse descriptor head and
+                                 async_tail.  0 (default): variant B refuses a PCA with D2FE_ERR_UNSUPPORTED, as the reference's live path ignores it.
+                                 The field takes the first of the five ints that were reserved (zero in every struct d2fe_default_config has filled): the struct
+                                 keeps its size, so a program compiled against an earlier header -- whose d2fe_config d2fe_default_config fills -- runs unchanged. */
+  int32_t reserved[4];
   /* -- appended fields: a caller that passes the struct_size of the struct above (up to and including `reserved`) gets zeros here -- */
   int32_t exact_order;        /* 1 (D2FE_PREC_F32_WINO, variant B, max_keypoints >= 1 only; anything else: D2FE_ERR_INVALID): the keypoint list equals the
                                  one a D2FE_PREC_F32 handle produces.  Candidates whose list position the Winograd deviation could change (within
@@ -146,10 +153,14 @@ D2FE_API void d2fe_destroy(d2fe_handle h);
  * weights are copied, re-packed into MFMA fragment order and cached on the device. */
 D2FE_API int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w);
 
-/* Optional PCA of the local descriptors (variant A only, as in the reference: computeDescriptors,
- * superpoint_common.cpp:76-85; the variant-B path never applies it).
+/* Optional PCA of the local descriptors: variant A as in the reference (computeDescriptors, superpoint_common.cpp:76-85); variant B only on a
+ * handle created with d2fe_config.variant_b_pca = 1 (the reference's variant-B path loads the matrices and never applies them, SURVEY.md F6:
+ * without the opt-in a variant-B handle answers D2FE_ERR_UNSUPPORTED).  Both variants share one tail: t = d - mean, a[j] = the fp32 chain over
+ * c = 0..255 ascending of t[c] * comp[j][c] from 0 (each product and sum rounded), out[j] = a[j] / sqrtf(sum a[j]^2); no guards -- a NaN row
+ * (remove_borders = 0) or d == mean gives NaN in every component.  A keypoint's bits do not depend on batch, entry point or pipe shape.
  * comp: [pca_dims][256] row-major (the CSV layout read by superpoint_onnx.cpp:47-53), mean: [256].
- * pca_dims = 0 disables.  d2fe_desc_dim() returns the per-keypoint descriptor length of extract calls (256 or pca_dims). */
+ * pca_dims = 0 disables; variant A takes 1..256, variant B 4..256 in multiples of 4 (the matcher's row alignment; anything else D2FE_ERR_INVALID).
+ * d2fe_desc_dim() returns the per-keypoint descriptor length of extract calls (256 or pca_dims).  Refused while pipes are alive. */
 D2FE_API int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean, int pca_dims);
 D2FE_API int d2fe_desc_dim(d2fe_handle h);
 
@@ -461,6 +472,8 @@ D2FE_API d2fe_handle d2fe_pipe_handle(d2fe_pipe p);
  * The communicator is an RCCL ncclComm_t made by the caller (ncclCommInitRank in D2SLAM's own start-up code, or d2fe_rccl_comm_init_rank below: librccl is loaded
  * with dlopen, only when these entry points are used); every rank must enqueue its tickets in the same order.  A caller without RCCL (tests over gloo on one GPU)
  * passes comm = NULL and an all_gather callback.  Pair p = (rank-major over the OTHER ranks r, then frame f): local left frame f against frame f of rank r. */
+/* D2FE_WIRE_INT8_RENORM256: the int8 wire with every decoded descriptor re-normalised over the row (the pipe's desc_dim floats: 256 without a descriptor PCA, which is
+ * where the name comes from) */
 typedef enum { D2FE_WIRE_FP32 = 0, D2FE_WIRE_INT8 = 1, D2FE_WIRE_INT8_RENORM256 = 2 } d2fe_wire;
 typedef int (*d2fe_all_gather_fn)(void* user, const void* d_send, void* d_recv, size_t bytes_per_rank, void* stream);   /* 0 = ok; must be complete or stream-ordered on return */
 typedef struct {
@@ -498,7 +511,8 @@ D2FE_API int d2fe_exchange_pairs(d2fe_exchange x);
 D2FE_API int d2fe_exchange_block_bytes(d2fe_exchange x);   /* bytes one frame contributes to the all-gather */
 D2FE_API void* d2fe_exchange_stream(d2fe_exchange x);      /* own_stream = 1: that stream (hipStream_t), else NULL */
 /* DEVICE addresses of slot `slot`'s gathered blocks [world][frames]: the fp32 blocks the gate and the matcher read (decoded from the wire form when it is int8) and
- * the blocks as they crossed the wire (either pointer may be NULL); d2fe_quad_exchange_gathered's contract.  What d2fe_window_track_device reads in place. */
+ * the blocks as they crossed the wire (either pointer may be NULL); d2fe_quad_exchange_gathered's contract.  What d2fe_window_track_device reads in place.
+ * The blocks take the pipe's descriptor width (d2fe_pipe_geometry): their size and fields are d2fe_block_words_d / d2fe_block_field_offset_d(cap, desc_dim, G, ...). */
 D2FE_API int d2fe_exchange_gathered(d2fe_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks);
 /* RCCL without any other dependency: rank 0 makes a 128-byte id, every rank gets it by whatever channel D2SLAM has (its LCM bus, a file, MPI), then all ranks call
  * comm_init_rank.  path: a librccl to load (NULL: one the process already holds, else librccl.so.1 / librccl.so on the loader path, else /opt/rocm/lib). */
@@ -691,30 +705,44 @@ D2FE_API int d2fe_good_features_to_track(d2fe_handle h, d2fe_lk_frame f, int max
 /* ---- cross-agent exchange --------------------------------------------------------------------------------
  * Replaces the LCM broadcast of a keyframe's image descriptor (d2frontend/src/loop_net.cpp:24-87: landmark positions, scores,
  * SuperPoint descriptors, NetVLAD descriptor) by one fixed-capacity block per frame, so that the exchange is ONE all-gather:
- *   block (float words) = desc[cap][256] | kps[cap][2] | scores[cap] | netvlad[G] | n (int32) | zero padding to a multiple of 256.
+ *   block (float words) = desc[cap][D] | kps[cap][2] | scores[cap] | netvlad[G] | n (int32) | zero padding to a multiple of 256.
  * Descriptors come first and the size is a multiple of 256 words: a gathered block's descriptors are addressable by
- * d2fe_match_batch_device (offsets in rows of `dim` floats) without unpacking. */
+ * d2fe_match_batch_device (offsets in rows of `dim` floats) without unpacking -- wherever D divides the block size (every power of two).
+ * D = 256 in the plain functions; the _d forms take desc_dim = 4..256, a multiple of 4 (d2fe_desc_dim of a handle with a descriptor PCA), and
+ * are the plain ones at 256: same sizes, same bits. */
 D2FE_API int d2fe_block_words(int cap, int netvlad_dim);                 /* words of one block */
 D2FE_API int d2fe_block_field_offset(int cap, int netvlad_dim, int field);   /* word offset of field 0 desc, 1 kps, 2 scores, 3 netvlad, 4 n */
+D2FE_API int d2fe_block_words_d(int cap, int desc_dim, int netvlad_dim);
+D2FE_API int d2fe_block_field_offset_d(int cap, int desc_dim, int netvlad_dim, int field);
 /* Packs nframes frames of a d2fe_superpoint_extract_device result (dense [rows][cap][...] arrays; frame f is row row0 + f*row_step)
  * and of a d2fe_netvlad_device result (d_netvlad [nframes][G], may be NULL) into d_blocks [nframes][d2fe_block_words]. */
 D2FE_API int d2fe_pack_blocks_device(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const float* d_scores,
                                      const int32_t* d_n, const float* d_netvlad, int row0, int row_step, int nframes, int cap,
                                      int netvlad_dim, float* d_blocks, void* stream);
+D2FE_API int d2fe_pack_blocks_device_d(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const float* d_scores,
+                                       const int32_t* d_n, const float* d_netvlad, int row0, int row_step, int nframes, int cap,
+                                       int desc_dim, int netvlad_dim, float* d_blocks, void* stream);
 /* The same block in the reference's WIRE precision.  VisualImageDesc::toLCM quantises the descriptors to int8 before the broadcast
  * (d2common/include/d2common/d2frontend_types.h:228-237: one float maximum over the frame's landmark descriptors; :260-268: the NetVLAD
  * vector with a double maximum; scores are not sent) and the receiving constructor decodes them (:319-338: q / 127.0, the first
  * landmark_num 32-float segments re-normalised -- the reference's hard-coded 32 --, the NetVLAD vector normalised as a whole).
- *   int8 block (bytes) = desc_q[cap][256] | netvlad_q[G] | kps f32[cap][2] | n int32 | zero padding to a multiple of 64   (3.9x smaller)
+ *   int8 block (bytes) = desc_q[cap][D] | netvlad_q[G] | kps f32[cap][2] | n int32 | zero padding to a multiple of 64   (3.9x smaller)
  * d2fe_pack_blocks_int8_device = the quantisation, on the sender; d2fe_unpack_blocks_int8_device expands gathered int8 blocks into the
- * fp32 block layout above (scores = 0) with the decode arithmetic: renorm 0 = as the reference (landmark_num = n), 1 = every descriptor
- * re-normalised over its 256 floats.  Gate and matcher then read exactly what a receiving agent of the reference would hold. */
+ * fp32 block layout above (scores = 0) with the decode arithmetic: renorm 0 = as the reference (landmark_num = n: the first n 32-float segments
+ * of the flat array -- at D = 64 half a descriptor each, so only the first n / 2 rows are re-normalised, the reference's bug included), 1 = every
+ * descriptor re-normalised over the row (its D floats).  Gate and matcher then read exactly what a receiving agent of the reference would hold. */
 D2FE_API int d2fe_block_bytes_int8(int cap, int netvlad_dim);
 D2FE_API int d2fe_pack_blocks_int8_device(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const int32_t* d_n,
                                           const float* d_netvlad, int row0, int row_step, int nframes, int cap, int netvlad_dim,
                                           int8_t* d_blocks, void* stream);
 D2FE_API int d2fe_unpack_blocks_int8_device(d2fe_handle h, const int8_t* d_blocks_int8, int nblocks, int cap, int netvlad_dim, int renorm,
                                             float* d_blocks, void* stream);
+D2FE_API int d2fe_block_bytes_int8_d(int cap, int desc_dim, int netvlad_dim);
+D2FE_API int d2fe_pack_blocks_int8_device_d(d2fe_handle h, const float* d_desc, const float* d_kps_xy, const int32_t* d_n,
+                                            const float* d_netvlad, int row0, int row_step, int nframes, int cap, int desc_dim, int netvlad_dim,
+                                            int8_t* d_blocks, void* stream);
+D2FE_API int d2fe_unpack_blocks_int8_device_d(d2fe_handle h, const int8_t* d_blocks_int8, int nblocks, int cap, int desc_dim, int netvlad_dim,
+                                              int renorm, float* d_blocks, void* stream);
 /* NetVLAD gate of a pair list.  Replaces the similarity test of D2FeatureTracker::getMatchedPrevKeyframe
  * (d2frontend/src/d2featuretracker.cpp:185-203: `vlad_desc.dot(vlad_desc_remote) < track_remote_netvlad_thres` rejects) and of
  * LoopDetector::queryIndexFromDatabase (loop_detector.cpp:339).  Pair p compares row d_pair_q[p] of d_q (rows q_stride words apart)
@@ -900,7 +928,9 @@ D2FE_API d2fe_handle d2fe_quad_handle(d2fe_quad_pipe p);
  *   mode 1, gated  : 4 problems per job, index j * 4 + k, in trackRemoteFrames' order: remote view a = (2 + k) % 4, local view (dir_b - 2 + a) mod 4.  A job that
  *                    fails the gate has n_match = 0 for its four problems and local_view = remote_view = -1.  Needs NetVLAD (else D2FE_ERR_INVALID).
  * gate_sims / dir_prev are bit-equal to d2fe_quad_gate_device on the same vectors (local: the view's d_netvlad, remote: the netvlad field of the gathered fp32
- * blocks).  A pipe with descriptor PCA (desc_dim != 256) is D2FE_ERR_UNSUPPORTED. */
+ * blocks).  The blocks take the pipe's descriptor width (d2fe_quad_pipe_geometry: 256, or the PCA width of a variant_b_pca handle): sizes and fields are those of the
+ * _d layout functions; a width that does not divide the block size (the matcher reads the blocks in place, in rows) is D2FE_ERR_UNSUPPORTED -- 64 and every other
+ * power of two divide it. */
 typedef enum { D2FE_QUAD_ALL2ALL = 0, D2FE_QUAD_GATED = 1 } d2fe_quad_exchange_mode;
 typedef struct {
   int32_t struct_size;
@@ -946,7 +976,7 @@ D2FE_API int d2fe_quad_exchange_block_bytes(d2fe_quad_exchange x);   /* bytes on
 D2FE_API void* d2fe_quad_exchange_stream(d2fe_quad_exchange x);      /* own_stream = 1: that stream (hipStream_t), else NULL */
 /* DEVICE pointers of the slot's gathered blocks [world][4 * quads] (either may be NULL): *d_blocks = the fp32 blocks gate and matcher read (for an int8 wire: the
  * decode), *d_wire_blocks = the blocks as they crossed the wire (fp32: the same pointer).  The remote keypoints a t_idx refers to are in there
- * (d2fe_block_field_offset).  Complete once the slot was collected; valid until the slot is enqueued again. */
+ * (d2fe_block_field_offset_d with the pipe's desc_dim; d2fe_block_field_offset at 256).  Complete once the slot was collected; valid until the slot is enqueued again. */
 D2FE_API int d2fe_quad_exchange_gathered(d2fe_quad_exchange x, int slot, const float** d_blocks, const void** d_wire_blocks);
 /* The job list of one rank without a device: job_rank[j] / job_quad[j] for j < min(njobs, cap_jobs) (either array may be NULL); returns njobs =
  * (world - 1, or world with loopback) * quads, or D2FE_ERR_INVALID.  d2fe_quad_exchange_create builds its table with this function. */
@@ -1111,8 +1141,8 @@ D2FE_API int d2fe_window_retain_plan(const int64_t* tags, int n, const int64_t* 
 D2FE_API int d2fe_window_size(d2fe_window x);
 D2FE_API int d2fe_window_tags(d2fe_window x, int64_t* tags, int cap_tags);      /* oldest first, at most cap_tags of them; returns the window's size */
 /* Tracks nq remote frames.  DEVICE arrays: row q * V + v of each is view v of frame q; the strides count 32-bit words between consecutive rows, so the same call reads
- * the pipes' dense arrays (strides netvlad_dim, cap * desc_dim, 1) and the exchanges' gathered fp32 blocks in place (all three strides d2fe_block_words, the bases
- * from d2fe_block_field_offset: fields 3, 0, 4).  Descriptor rows are 16-byte aligned; NetVLAD rows need not be (a block's are only when cap % 4 == 0).  The arrays are
+ * the pipes' dense arrays (strides netvlad_dim, cap * desc_dim, 1) and the exchanges' gathered fp32 blocks in place (all three strides d2fe_block_words_d, the bases
+ * from d2fe_block_field_offset_d: fields 3, 0, 4, with the window's desc_dim; the plain functions at 256).  Descriptor rows are 16-byte aligned; NetVLAD rows need not be (a block's are only when cap % 4 == 0).  The arrays are
  * read in place and stay valid until the slot was collected.  stream: the hipStream_t that produced them (the window's stream waits for what is queued on it now), or
  * NULL when they are complete.  Refused: a slot that has not been collected (D2FE_ERR_NOT_READY), nq outside 1..max_queries. */
 D2FE_API int d2fe_window_track_device(d2fe_window x, const float* d_netvlad, size_t nv_stride, const float* d_desc, size_t desc_stride, const int32_t* d_n_kp,

@@ -90,6 +90,7 @@ struct SuperPointConfig {
   bool exact_order = false;              // winograd only, max_keypoints >= 1: the keypoint list (count, indices, order) equals the exact mode's (d2fe_config::exact_order)
   float exact_order_eps = 0.f;           // 0: the library default
   int32_t exact_order_crops = 0;         // crop slots per call; 0: max_batch
+  bool descriptor_pca = false;           // d2fe_config::variant_b_pca: setDescriptorPCA is accepted and infer() returns pca_dims floats per keypoint (params->enable_pca_superpoint)
 };
 
 class SuperPoint {
@@ -110,6 +111,7 @@ class SuperPoint {
     c.postproc = D2FE_POSTPROC_B;
     c.precision = cfg_.fp16_operands ? D2FE_PREC_F16 : cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
     c.exact_order = cfg_.exact_order ? 1 : 0; c.exact_order_eps = cfg_.exact_order_eps; c.exact_order_crops = cfg_.exact_order_crops;
+    c.variant_b_pca = cfg_.descriptor_pca ? 1 : 0;
     if (d2fe_create(&c, &h_) != D2FE_OK) { report("d2fe_create"); h_ = nullptr; return false; }
     if (d2fe_load_superpoint(h_, &w) != D2FE_OK) { report("d2fe_load_superpoint"); return false; }
     return true;
@@ -142,6 +144,13 @@ class SuperPoint {
     return true;
   }
 
+  // the projection the reference loads in its constructor (pca_comp_T / pca_mean, superpoint_tensorrt.cpp:27-38) and never applies: comp [pca_dims][256]
+  // row-major, mean [256], pca_dims 4..256 in multiples of 4 (0: off).  After build(), before any pipe is created; needs SuperPointConfig::descriptor_pca
+  bool setDescriptorPCA(const float* comp, const float* mean, int pca_dims) {
+    if (!h_ || d2fe_set_superpoint_pca(h_, comp, mean, pca_dims) != D2FE_OK) { report("d2fe_set_superpoint_pca"); return false; }
+    return true;
+  }
+  int descriptorDim() const { return h_ ? d2fe_desc_dim(h_) : 256; }
   d2fe_handle handle() const { return h_; }
   // exact_order counters since build(): marked candidates, cells re-evaluated, cells dropped for lack of crop slots, calls (d2fe_exact_order_stats)
   bool exactOrderStats(int64_t out[4]) const { return h_ && d2fe_exact_order_stats(h_, out) == D2FE_OK; }
@@ -509,11 +518,12 @@ class KeyframeWindow {
     return false;
   }
   // nq frames of gathered fp32 exchange blocks (d2fe_exchange_gathered / d2fe_quad_exchange_gathered), read in place from block `first_block` on
-  bool track_blocks(const float* d_blocks, int first_block, int nq, int cap, int netvlad_dim, int slot, void* stream) {
-    const size_t blk = (size_t)d2fe_block_words(cap, netvlad_dim);
+  // (desc_dim: the descriptor width of the pipes behind the exchange and the window -- 256, or the PCA width)
+  bool track_blocks(const float* d_blocks, int first_block, int nq, int cap, int netvlad_dim, int slot, void* stream, int desc_dim = 256) {
+    const size_t blk = (size_t)d2fe_block_words_d(cap, desc_dim, netvlad_dim);
     const float* b = d_blocks + blk * (size_t)first_block;
-    return track_device(b + d2fe_block_field_offset(cap, netvlad_dim, 3), blk, b, blk, reinterpret_cast<const int32_t*>(b + d2fe_block_field_offset(cap, netvlad_dim, 4)), blk,
-                        nq, slot, stream);
+    return track_device(b + d2fe_block_field_offset_d(cap, desc_dim, netvlad_dim, 3), blk, b, blk,
+                        reinterpret_cast<const int32_t*>(b + d2fe_block_field_offset_d(cap, desc_dim, netvlad_dim, 4)), blk, nq, slot, stream);
   }
   // blocks until the slot's results are in host memory; `out` points into the pinned slot (valid until the slot is queued again)
   bool collect(int slot, d2fe_window_result& out) {

@@ -66,6 +66,11 @@ D2FE_API int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, 
                                  int32_t* n_out);
 D2FE_API int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp,
                                  int cap, const int32_t* slotmap_or_null, int max_slots, float* desc_out);
+/* sample_b with the descriptor PCA behind it (sample_b_pca_kernel, what a d2fe_config.variant_b_pca handle launches): comp [pca_dims][256], mean [256],
+ * pca_dims in 1..256 -> desc_out [n][cap][pca_dims] */
+D2FE_API int d2fe_debug_sample_b_pca(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy,
+                                     const int32_t* n_kp, int cap, const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean,
+                                     int pca_dims, float* desc_out);
 D2FE_API int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,
                                int32_t* kps_idx, int32_t* n_out);
 
