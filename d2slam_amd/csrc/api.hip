@@ -1,6 +1,8 @@
-// api.hip -- C ABI (include/d2fe.h) of libd2fe_hip.so: context, device buffers, weight packing and the
-// launch sequence of the SuperPoint / matcher kernels.  Host code only; kernels live in conv.hip,
-// conv_f16.hip, postproc.hip and match.hip.  There is deliberately NO CPU fallback in this library.
+// api.hip -- C ABI (include/d2fe.h) of libd2fe_hip.so: handle lifecycle, SuperPoint's host side (weight
+// packing, the launch sequence of an extract call), the host and device extract entry points, the matcher,
+// the "next rows", the debug hooks and profiling.  Host code only: NetVLAD's host side is netvlad_host.hip,
+// the kernels live in the other translation units (kernels.h lists their launchers).  There is deliberately
+// NO CPU fallback in this library.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +21,7 @@
 #include "context.h"
 #ifdef D2FE_DEVTOOLS
 #include "../../include/d2fe_debug.h"
+#include "sp_plan.h"
 #endif
 
 using namespace d2fe;
@@ -59,7 +62,26 @@ int upload(const void* src, size_t bytes, void** dst) {
 // launch-regime record (kernels.h: D2FE_REGIME): process-wide, written by the launchers from any thread (pipe lanes)
 namespace {
 std::atomic<long long> g_regime[D2FE_REGIME_COUNT];
-}
+
+// The one owner of a debug hook's device buffers: hands out a pointer, remembers it and frees everything when the call returns, whichever way
+struct DevPool {
+  std::vector<void*> owned;
+  DevPool() = default; DevPool(const DevPool&) = delete; DevPool& operator=(const DevPool&) = delete;
+  ~DevPool() { for (void* p : owned) (void)hipFree(p); }
+  // bytes of device memory, filled with `fill` bytes (outputs: 0xff, so that an entry a kernel does not write is no plausible value) or with src
+  template <class T>
+  hipError_t get(T** out, size_t bytes, const void* src, int fill = 0xff) {
+    void* p = nullptr;
+    *out = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
+    if (e != hipSuccess) return e;
+    owned.push_back(p);
+    *out = static_cast<T*>(p);
+    if (!bytes) return hipSuccess;
+    return src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipMemset(p, fill, bytes);
+  }
+};
+}  // namespace
 namespace d2fe {
 void regime_note(int regime) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].fetch_add(1, std::memory_order_relaxed); }
 void regime_set(int regime, long long value) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].store(value, std::memory_order_relaxed); }
@@ -1428,19 +1450,12 @@ long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_byte
   if (!h || !name || !dst) return fail(D2FE_ERR_INVALID, "null argument");
   if (h->last_n == 0) return fail(D2FE_ERR_NOT_READY, "no extract call yet");
   hipSetDevice(h->cfg.device_id);
-  const size_t H = h->last_h, W = h->last_w, n = h->last_n;
-  struct { const char* nm; Tensor* t; size_t per; } tab[] = {
-      // pooled sizes floor (sizes need not be multiples of 8)
-      {"conv1a", &h->a1a, H * W * 64},           {"conv1b", &h->a1b, (H / 2) * (W / 2) * 64},   {"conv2a", &h->a2a, (H / 2) * (W / 2) * 64},
-      {"conv2b", &h->a2b, (H / 4) * (W / 4) * 64},   {"conv3a", &h->a3a, (H / 4) * (W / 4) * 128},  {"conv3b", &h->a3b, (H / 8) * (W / 8) * 128},
-      {"conv4a", &h->a4a, (H / 8) * (W / 8) * 128},  {"conv4b", h->last_set ? &h->a4b2 : &h->a4b, (H / 8) * (W / 8) * 128},  {"convPaDa", &h->aPD, (H / 8) * (W / 8) * 512},
-      {"logits", h->last_set ? &h->logits2 : &h->logits, (H / 8) * (W / 8) * 65}, {"desc_raw", h->last_set ? &h->draw2 : &h->draw, (H / 8) * (W / 8) * 256}, {"semi", &h->semi, (H / 8) * (W / 8) * 64},
-      {"convPa", &h->aPD, (H / 8) * (W / 8) * 256}};      // the detector branch alone: what the sparse descriptor head leaves in the convPa|convDa buffer
+  const int H = h->last_h, W = h->last_w, n = h->last_n;
   if (!strcmp(name, "conv1a") && h->fuse1a) {
     // fused mode never materialises conv1a: evaluate it on demand from the last input frame(s)
     if (!h->a1a.p && alloc_f(h->a1a, (size_t)h->cfg.max_height * h->cfg.max_width * 64, h->cfg.max_batch) != 0)
       return fail(D2FE_ERR_HIP, "hipMalloc conv1a debug buffer");
-    if (launch_conv1a(h->last_gray, h->last_stride, (long)h->last_istride, (int)H, (int)W, (int)n, h->w1a, h->b1a, h->a1a.p, h->stream) != hipSuccess)
+    if (launch_conv1a(h->last_gray, h->last_stride, (long)h->last_istride, H, W, n, h->w1a, h->b1a, h->a1a.p, h->stream) != hipSuccess)
       return fail(D2FE_ERR_HIP, "conv1a debug launch");
   }
   if (!strcmp(name, "semi") && !h->cfg.keep_score_map) return fail(D2FE_ERR_NOT_READY, "score map not kept (set keep_score_map)");
@@ -1448,15 +1463,23 @@ long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_byte
     return fail(D2FE_ERR_NOT_READY, "the dense descriptor map does not exist with the sparse descriptor head (set dense_descriptors)");
   if (!strcmp(name, "convPa") && !(h->sparse_desc && h->last_n >= h->sp_min_batch))
     return fail(D2FE_ERR_NOT_READY, "convPa alone exists only behind the sparse descriptor head (the dense head writes convPaDa)");
-  for (auto& e : tab)
-    if (!strcmp(e.nm, name)) {
-      const size_t bytes = e.per * n * sizeof(float);
-      if (bytes > max_bytes) return fail(D2FE_ERR_TRUNCATED, "destination too small");
-      if (hipStreamSynchronize(h->stream) != hipSuccess || (h->tail_stream && hipStreamSynchronize(h->tail_stream) != hipSuccess)) return fail(D2FE_ERR_HIP, "sync");
-      if (hipMemcpy(dst, e.t->p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
-      return (long)bytes;
-    }
-  return fail(D2FE_ERR_INVALID, "unknown tensor name");
+  // a layer's output under its own name, sized by the plan (sp_plan.h: the pools floor, sizes need not be multiples of 8); convPa: the detector branch alone, what the
+  // sparse descriptor head leaves in the convPa | convDa buffer; the heads' outputs under their names
+  const Tensor* const act[SP_PA + 1] = {&h->a1a, &h->a1b, &h->a2a, &h->a2b, &h->a3a, &h->a3b, &h->a4a, h->last_set ? &h->a4b2 : &h->a4b, &h->aPD};
+  const float* src = nullptr;
+  size_t per = 0;
+  for (int i = SP_1A; i <= SP_PA; ++i)
+    if (!strcmp(name, SP_PLAN[i].name)) { src = act[i]->p; per = sp_out_floats(i, H, W); }
+  const struct { const char* nm; const Tensor* t; int ch; } heads[] = {
+      {"convPaDa", &h->aPD, SP_PADA_COUT}, {"logits", h->last_set ? &h->logits2 : &h->logits, 65}, {"desc_raw", h->last_set ? &h->draw2 : &h->draw, 256}, {"semi", &h->semi, 64}};
+  for (auto& e : heads)
+    if (!strcmp(name, e.nm)) { src = e.t->p; per = sp_floats(SP_CELL_LEVEL, e.ch, H, W); }
+  if (!src) return fail(D2FE_ERR_INVALID, "unknown tensor name");
+  const size_t bytes = per * n * sizeof(float);
+  if (bytes > max_bytes) return fail(D2FE_ERR_TRUNCATED, "destination too small");
+  if (hipStreamSynchronize(h->stream) != hipSuccess || (h->tail_stream && hipStreamSynchronize(h->tail_stream) != hipSuccess)) return fail(D2FE_ERR_HIP, "sync");
+  if (hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
+  return (long)bytes;
 }
 
 // Host-side half of the Winograd mode, callable without a GPU: U = G g G^T in the kernels' fragment order (see pack_weights_wino).
@@ -1533,17 +1556,14 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
     if (wctr) { const hipError_t e = hipMemsetAsync(wctr, 0, sizeof(int), h->stream); if (e != hipSuccess) return e; }
     return launch_conv_wino(cin, pool != 0, relu != 0, cout_pad, ca, h->stream);
   };
+  DevPool b;
   float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = [&]() -> int {
-    HIP_TRY(hipMalloc(&d_in, in_fl * 4));
-    HIP_TRY(hipMalloc(&d_out, out_fl * 4));
-    HIP_TRY(hipMalloc(&d_w, pk.size() * 4));
-    HIP_TRY(hipMalloc(&d_b, bp.size() * 4));
-    HIP_TRY(hipMemcpy(d_in, in, in_fl * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_w, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out, 0xff, out_fl * 4));
+    HIP_TRY(b.get(&d_in, in_fl * 4, in));
+    HIP_TRY(b.get(&d_out, out_fl * 4, nullptr));
+    HIP_TRY(b.get(&d_w, pk.size() * 4, pk.data()));
+    HIP_TRY(b.get(&d_b, bp.size() * 4, bp.data()));
     HIP_TRY(hipDeviceSynchronize());      // the null-stream memset is not ordered with the handle's non-blocking stream
     ConvArgs a{};
     a.in = d_in; a.in_cstride = cin; a.in_coff = 0; a.out = d_out; a.out_cstride = cout; a.out_coff = 0;
@@ -1567,7 +1587,6 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
     }
     return D2FE_OK;
   }();
-  for (void* p : {(void*)d_in, (void*)d_out, (void*)d_w, (void*)d_b}) if (p) hipFree(p);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   return rc;
@@ -1576,19 +1595,6 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
 // ---- the SuperPoint tail kernels of postproc.hip on injected tensors (tests/test_postproc_edges.py): host buffers in and out, the hook's own device
 // buffers, the handle's device and stream, no weights.  Each hook calls the launch_* function of kernels.h with the caller's parameters and nothing else.
 namespace {
-struct DebugBufs {      // device scratch of one hook call: freed when the call returns, whichever way
-  std::vector<void*> owned;
-  ~DebugBufs() { for (void* p : owned) (void)hipFree(p); }
-  // bytes of device memory, filled with `fill` bytes (outputs: 0xff, so that an entry a kernel does not write is no plausible value) or with src
-  hipError_t get(void** out, size_t bytes, const void* src, int fill = 0xff) {
-    *out = nullptr;
-    hipError_t e = hipMalloc(out, bytes ? bytes : 4);
-    if (e != hipSuccess) return e;
-    owned.push_back(*out);
-    if (!bytes) return hipSuccess;
-    return src ? hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) : hipMemset(*out, fill, bytes);
-  }
-};
 constexpr long DEBUG_MAX_PIXELS = 1l << 21;
 }  // namespace
 
@@ -1599,14 +1605,14 @@ int d2fe_debug_softmax_cand(d2fe_handle h, const float* logits, int lstride, int
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   const size_t ncell = (size_t)Hc * Wc, hw = ncell * 64;
   const long cand_cap = (long)hw;
-  DebugBufs b;
+  DevPool b;
   float *d_l = nullptr, *d_semi = nullptr;
   unsigned long long* d_cand = nullptr;
   int* d_cnt = nullptr;
-  HIP_TRY(b.get((void**)&d_l, sizeof(float) * n * ncell * lstride, logits));
-  if (want_semi) HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, nullptr));
-  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
-  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, nullptr));
+  HIP_TRY(b.get(&d_l, sizeof(float) * n * ncell * lstride, logits));
+  if (want_semi) HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, nullptr));
   HIP_TRY(hipDeviceSynchronize());      // the null-stream copies and memsets are not ordered with the handle's non-blocking stream
   HIP_TRY(launch_softmax_cand(d_l, lstride, Hc, Wc, n, thr, border, d_semi, d_cand, d_cnt, cand_cap, /*zero_counts=*/true, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1625,18 +1631,18 @@ int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int
     if (cand_count[i] < 0 || cand_count[i] > cand_cap) return fail(D2FE_ERR_INVALID, "cand_count entry outside [0, cand_cap]");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   const size_t hw = (size_t)H * W;
-  DebugBufs b;
+  DevPool b;
   unsigned long long* d_cand = nullptr;
   int* d_cnt = nullptr;
   float *d_semi = nullptr, *d_kps = nullptr, *d_sc = nullptr;
   int32_t *d_idx = nullptr, *d_n = nullptr;
-  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, cand));
-  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, cand_count));
-  if (semi_or_null) HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, semi_or_null));
-  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_sc, sizeof(float) * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_idx, sizeof(int32_t) * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, nullptr));
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, cand));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, cand_count));
+  if (semi_or_null) HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, semi_or_null));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get(&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(launch_select_b(d_cand, d_cnt, cand_cap, n, W, max_kp, cap, always_sort, d_semi, H, thr, border, d_kps, d_sc, d_idx, d_n, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1661,23 +1667,23 @@ static int debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int
     return fail(D2FE_ERR_INVALID, "dense form: dcoff and dstride are multiples of 4 with dcoff + 256 <= dstride");
   }
   HIP_TRY(hipSetDevice(h->cfg.device_id));
-  DebugBufs b;
+  DevPool b;
   float *d_raw = nullptr, *d_kps = nullptr, *d_desc = nullptr;
   int32_t *d_n = nullptr, *d_map = nullptr;
-  HIP_TRY(b.get((void**)&d_raw, sizeof(float) * n * (slotmap_or_null ? (size_t)max_slots * 256 : ncell * dstride), desc_raw));
-  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
-  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, n_kp));
-  if (slotmap_or_null) HIP_TRY(b.get((void**)&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
+  HIP_TRY(b.get(&d_raw, sizeof(float) * n * (slotmap_or_null ? (size_t)max_slots * 256 : ncell * dstride), desc_raw));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, n_kp));
+  if (slotmap_or_null) HIP_TRY(b.get(&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
   const size_t D = comp ? (size_t)pca_dims : 256;
   float *d_comp_t = nullptr, *d_mean = nullptr;
   if (comp) {      // the transposed layout d2fe_set_superpoint_pca uploads: comp_t [256][pca_dims]
     std::vector<float> t((size_t)256 * pca_dims);
     for (int j = 0; j < pca_dims; ++j)
       for (int c = 0; c < 256; ++c) t[(size_t)c * pca_dims + j] = comp[(size_t)j * 256 + c];
-    HIP_TRY(b.get((void**)&d_comp_t, sizeof(float) * t.size(), t.data()));
-    HIP_TRY(b.get((void**)&d_mean, sizeof(float) * 256, mean));
+    HIP_TRY(b.get(&d_comp_t, sizeof(float) * t.size(), t.data()));
+    HIP_TRY(b.get(&d_mean, sizeof(float) * 256, mean));
   }
-  HIP_TRY(b.get((void**)&d_desc, sizeof(float) * D * n * cap, nullptr));
+  HIP_TRY(b.get(&d_desc, sizeof(float) * D * n * cap, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(launch_sample_b(d_raw, dstride, dcoff, Hc, Wc, n, d_kps, d_n, cap, d_map, max_slots, d_comp_t, d_mean, comp ? pca_dims : 0, d_desc, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1703,21 +1709,21 @@ int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, flo
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   const size_t hw = (size_t)H * W;
   const long cand_cap = (long)hw;
-  DebugBufs b;
+  DevPool b;
   float *d_semi = nullptr, *d_aconf = nullptr, *d_kps = nullptr, *d_sc = nullptr;
   int *d_clist = nullptr, *d_cnt = nullptr, *d_ncand = nullptr;
   unsigned long long* d_cand = nullptr;
   int32_t *d_idx = nullptr, *d_n = nullptr;
-  HIP_TRY(b.get((void**)&d_semi, sizeof(float) * n * hw, semi));
-  HIP_TRY(b.get((void**)&d_aconf, sizeof(float) * n * hw, nullptr));
-  HIP_TRY(b.get((void**)&d_clist, sizeof(int) * n * hw, nullptr, 0));
-  HIP_TRY(b.get((void**)&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
-  HIP_TRY(b.get((void**)&d_cnt, sizeof(int) * n, nullptr, 0));
-  HIP_TRY(b.get((void**)&d_ncand, sizeof(int) * n, nullptr, 0));
-  HIP_TRY(b.get((void**)&d_kps, sizeof(float) * 2 * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_sc, sizeof(float) * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_idx, sizeof(int32_t) * n * cap, nullptr));
-  HIP_TRY(b.get((void**)&d_n, sizeof(int32_t) * n, nullptr, 0));
+  HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, semi));
+  HIP_TRY(b.get(&d_aconf, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get(&d_clist, sizeof(int) * n * hw, nullptr, 0));
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get(&d_ncand, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get(&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, nullptr, 0));
   HIP_TRY(hipDeviceSynchronize());
   // the sequence run_superpoint issues for variant A
   HIP_TRY(launch_nms2_a(d_semi, H, W, n, thr, dist, d_aconf, d_clist, d_cand, d_cnt, cand_cap, d_ncand, h->stream));
@@ -1768,9 +1774,6 @@ int d2fe_debug_graph_count(d2fe_handle h, int* rejected) {
   return n;
 }
 
-#endif
-
-#ifdef D2FE_DEVTOOLS
 /* development builds: the wall_clock64() phase stamps [workgroup][16] of the last d2fe_match_batch_device launch made with D2FE_MATCH_STAMPS set */
 D2FE_API long d2fe_debug_match_stamps(d2fe_handle h, unsigned long long* dst, long max_wgs) {
   if (!h || !dst || !h->match_stamps) return fail(D2FE_ERR_NOT_READY, "no stamped launch yet (D2FE_MATCH_STAMPS)");

@@ -1,5 +1,6 @@
 // context.h -- the device context behind d2fe_handle and the launch sequences shared by the translation units that implement
-// include/d2fe.h (api.hip: the entry points; pipe.hip: the frames-in-flight pipeline).  Internal.
+// include/d2fe.h (api.hip: handle lifecycle, SuperPoint's host side and the entry points; netvlad_host.hip: NetVLAD's host side; lk.hip, lk_carry.hip: the trackers;
+// pipe.hip, quad_pipe.hip: the frames-in-flight pipelines; exchange.hip, quad_exchange.hip, loop.hip, window.hip: the consumers behind them).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -171,7 +172,7 @@ struct d2fe_context {
   // exact_order (exact_order.hip; cfg.exact_order): eo_slots crops of 88x88 per call through the direct kernels
   int eo_slots = 0; float eo_eps = 0.f;
   uint8_t* eo_crops = nullptr; int* eo_cell_map = nullptr; int* eo_cell_list = nullptr; int* eo_cell_count = nullptr;
-  float* eo_act = nullptr;           // the crop batch's activations, carved per layer in run_superpoint
+  float* eo_act = nullptr;           // the crop batch's activations, carved per layer in run_exact_order (api.hip)
   unsigned long long* eo_stats = nullptr;      // [4] marked candidates, cells re-evaluated, cells dropped, calls: the parent handle's, shared with its lanes
   void* lk_scratch = nullptr; size_t lk_scratch_bytes = 0;   // grow-only scratch of the LK / detector entry points (lk.hip)
   float* a_samp = nullptr; float* a_cn = nullptr; int a_scap = 0;   // variant A sampling: [batch][a_scap][256] samples, [batch][256] channel norms
