@@ -95,6 +95,11 @@ class _PipeConfig(C.Structure):
                 ("ratio", C.c_double), ("radius_lr", C.c_double), ("radius_prev", C.c_double), ("cu_partition", C.c_int32), ("netvlad_inline", C.c_int32), ("coalesce", C.c_int32), ("lane_cus", C.c_int32), ("netvlad_group", C.c_int32), ("coalesce_depth", C.c_int32), ("lr_lk", C.c_int32), ("sp_lk", C.c_int32)]
 
 
+class _PipeCamera(C.Structure):
+    """d2fe_pipe_camera: the one-camera configurations of a pipe (d2fe_pipe_create_camera)"""
+    _fields_ = [("struct_size", C.c_int32), ("mono", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _PipeResult(C.Structure):
     _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
                 ("kps_xy", C.c_void_p), ("scores", C.c_void_p), ("desc", C.c_void_p), ("n_kp", C.c_void_p), ("netvlad", C.c_void_p),
@@ -117,6 +122,11 @@ class _PipeTrackResult(C.Structure):
                 ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p),
                 ("pts_xy", C.c_void_p), ("id", C.c_void_p), ("src", C.c_void_p), ("kp", C.c_void_p), ("desc", C.c_void_p), ("scores", C.c_void_p),
                 ("right_xy", C.c_void_p), ("right_status", C.c_void_p)]
+
+
+class _PipeDepthResult(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("cap_tracks", C.c_int32), ("reserved", C.c_int32), ("kp_depth_mm", C.c_void_p),
+                ("track_depth_mm", C.c_void_p)]
 
 
 class _PipeDeviceResult(C.Structure):
@@ -225,7 +235,7 @@ EXPORTS = [
     "d2fe_lk_frame_create_device", "d2fe_lk_frame_destroy", "d2fe_lk_frame_read_level", "d2fe_lk_track", "d2fe_lk_track_batch",
     "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
     "d2fe_track_default_params", "d2fe_lk_carry_list_bytes", "d2fe_lk_carry_list_offset", "d2fe_lk_carry_step_device", "d2fe_pipe_track_result_get",
-    "d2fe_pipe_set_track_params", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
+    "d2fe_pipe_set_track_params", "d2fe_pipe_camera_default", "d2fe_pipe_create_camera", "d2fe_pipe_submit_depth", "d2fe_pipe_depth_result_get", "d2fe_depth_at_device", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -416,6 +426,13 @@ def _open_library(path, dev):
         lib.d2fe_pipe_classify_stream.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         lib.d2fe_pipe_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         lib.d2fe_pipe_wait.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_pipe_camera_default.argtypes = [C.c_void_p]
+        lib.d2fe_pipe_camera_default.restype = None
+        lib.d2fe_pipe_create_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_submit_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.d2fe_pipe_depth_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_depth_at_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_device_view.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_device_release.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -1077,12 +1094,16 @@ class StereoPipe(_Owned):
     wait() then returns, instead of lk_*, per frame f: "track_n" [F], "track_pts" [F, cap_tracks, 2], "track_id" / "track_src" / "track_kp" [F, cap_tracks],
     "track_desc" [F, cap_tracks, D], "track_scores", "track_right_pts" [F, cap_tracks, 2], "track_right_status" [F, cap_tracks] and the counts
     "track_n_tracked_in", "track_n_lost", "track_n_removed_near", "track_n_new" [F] (include/d2fe.h, d2fe_pipe_track_result).
+    mono=True (needs match_lr=False, lr_lk=False): ONE camera per frame, the reference's MONOCULAR configuration -- submit(left) without a right image; the result
+    keeps its [2 F] rows, the right ones with n_kp = 0.  With sp_lk=True the list is carried on the one image and "track_right_pts" / "track_right_status" are None.
+    depth=True (needs mono=True): PINHOLE_DEPTH -- submit(left, depth=...) with a uint16 depth frame per gray frame; wait() then also returns "kp_depth_mm"
+    [F, cap] uint16 (the value under every keypoint, 0 beyond n_kp) and, with sp_lk, "track_depth_mm" [F, cap_tracks] (None otherwise).
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits)."""
     _HANDLE, _DESTROY = "_p", "d2fe_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
                  ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
-                 lr_lk=False, sp_lk=False, track_params=None):
+                 lr_lk=False, sp_lk=False, track_params=None, mono=False, depth=False):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _PipeConfig()
@@ -1095,12 +1116,20 @@ class StereoPipe(_Owned):
         c.netvlad_inline = 2 if netvlad_inline is None else int(bool(netvlad_inline))      # None: auto (inline when lanes > 2)
         c.lr_lk = int(bool(lr_lk))
         c.sp_lk = int(bool(sp_lk))
+        cam = _PipeCamera()
+        self._lib.d2fe_pipe_camera_default(C.byref(cam))
+        cam.mono, cam.depth = int(bool(mono)), int(bool(depth))
+        self._mono, self._depth = bool(mono), bool(depth)
+        self._depth_res = _PipeDepthResult()
         self._lr_lk = bool(lr_lk)
         self._sp_lk = bool(sp_lk)
         self._lk_res = _PipeLKResult()
         self._track_res = _PipeTrackResult()
         self._p = C.c_void_p()
-        _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
+        if mono or depth:
+            _check(self._lib.d2fe_pipe_create_camera(fe.handle, C.byref(c), C.byref(cam), C.byref(self._p)))
+        else:
+            _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
         if track_params is not None:
             try:
                 self.set_track_params(track_params)
@@ -1130,16 +1159,37 @@ class StereoPipe(_Owned):
                                           int(image_stride or self.width * self.height), C.byref(t)))
         return int(t.value)
 
-    def submit(self, left, right):
-        """left, right: u8 [frames, H, W] (or [H, W] when frames == 1).  The library copies the frames into its own pinned staging before this returns
+    def submit_depth_ptr(self, gray_ptr, depth_ptr, stride=None, depth_stride=None, image_stride=None, depth_image_stride=None):
+        """d2fe_pipe_submit_depth on raw host addresses; the depth strides are in bytes"""
+        t = C.c_int64()
+        ds = int(depth_stride or 2 * self.width)
+        _check(self._lib.d2fe_pipe_submit_depth(self._p, C.c_void_p(gray_ptr), C.c_void_p(depth_ptr), int(stride or self.width), ds,
+                                                int(image_stride or self.width * self.height), int(depth_image_stride or ds * self.height), C.byref(t)))
+        return int(t.value)
+
+    def submit(self, left, right=None, depth=None):
+        """left, right: u8 [frames, H, W] (or [H, W] when frames == 1); a mono pipe takes right=None, a depth pipe depth = u16 [frames, H, W] (a view whose rows are
+        further apart than the image is wide is passed on with its strides).  The library copies the frames into its own pinned staging before this returns
         (pinned_input = 0), so the arrays -- and any contiguous temporaries made here -- are not referenced afterwards.  A pipe created with
         pinned_input=True DMAs straight from the caller's memory until the ticket has been waited for: that contract (page-locked memory that
         stays alive and unchanged) cannot be kept for numpy arrays, so it is refused here -- use submit_ptr with memory you own."""
         if self._pinned_input:
             raise ValueError("StereoPipe(pinned_input=True): submit() takes numpy arrays, which are neither page-locked nor kept alive until wait(); "
                              "use submit_ptr() with page-locked memory that outlives the ticket")
-        left = np.ascontiguousarray(left, np.uint8); right = np.ascontiguousarray(right, np.uint8)
-        return self.submit_ptr(left.ctypes.data, right.ctypes.data)
+        left = np.ascontiguousarray(left, np.uint8)
+        if depth is not None:
+            if right is not None:
+                raise ValueError("submit(left, depth=...) belongs to a mono pipe: no right image")
+            depth = np.asarray(depth)
+            if depth.dtype != np.uint16:
+                raise TypeError("depth frames are uint16")
+            d3 = depth if depth.ndim == 3 else depth[None]
+            if d3.strides[2] != 2 or d3.strides[1] < 2 * d3.shape[2] or (d3.shape[0] > 1 and d3.strides[0] < d3.strides[1] * d3.shape[1]):
+                d3 = np.ascontiguousarray(d3)
+            return self.submit_depth_ptr(left.ctypes.data, d3.ctypes.data, depth_stride=d3.strides[1], depth_image_stride=max(d3.strides[0], d3.strides[1] * d3.shape[1]))
+        if right is not None:
+            right = np.ascontiguousarray(right, np.uint8)
+        return self.submit_ptr(left.ctypes.data, None if right is None else right.ctypes.data)
 
     def stream_placement(self):
         """(classes, n_classes) of d2fe_pipe_stream_placement: classes[k] = (hardware-pipe class of lane k's own stream, of its second stream)."""
@@ -1219,12 +1269,22 @@ class StereoPipe(_Owned):
             for k in ("id", "src", "kp"):
                 out["track_" + k] = per_list(getattr(t, k), (T,), np.int32)
             out["track_right_pts"] = view(t.right_xy, (F, T, 2), np.float32)
-            out["track_right_status"] = np.frombuffer((C.c_uint8 * (F * T)).from_address(t.right_status), dtype=np.uint8).reshape(F, T)
+            out["track_right_status"] = np.frombuffer((C.c_uint8 * (F * T)).from_address(t.right_status), dtype=np.uint8).reshape(F, T) if t.right_status else None
         elif self._lr_lk:
             lk = self.lk_result_raw(ticket)
             out["lk_pts"] = view(lk.pts_xy, (F, cap, 2), np.float32)
             out["lk_status"] = np.frombuffer((C.c_uint8 * (F * cap)).from_address(lk.status), dtype=np.uint8).reshape(F, cap)
+        if self._depth:
+            d = self.depth_result_raw(ticket)
+            out["kp_depth_mm"] = np.frombuffer((C.c_uint16 * (F * cap)).from_address(d.kp_depth_mm), dtype=np.uint16).reshape(F, cap)
+            T = d.cap_tracks
+            out["track_depth_mm"] = np.frombuffer((C.c_uint16 * (F * T)).from_address(d.track_depth_mm), dtype=np.uint16).reshape(F, T) if d.track_depth_mm else None
         return out
+
+    def depth_result_raw(self, ticket):
+        """d2fe_pipe_depth_result_get: the depth values of a ticket that wait() has returned (depth pipes)"""
+        _check(self._lib.d2fe_pipe_depth_result_get(self._p, C.c_int64(ticket), C.byref(self._depth_res)))
+        return self._depth_res
 
     def lk_result_raw(self, ticket):
         """d2fe_pipe_lk_result_get: the left -> right LK tracks of a ticket that wait() has returned (lr_lk pipes)"""
@@ -1240,6 +1300,14 @@ class StereoPipe(_Owned):
     def set_track_params(self, tp):
         """d2fe_pipe_set_track_params: only before the first submit"""
         _check(self._lib.d2fe_pipe_set_track_params(self._p, C.byref(track_params(**tp) if isinstance(tp, dict) else tp)))
+
+
+def depth_at_device(fe, d_depth, width, height, depth_stride, depth_image_stride, d_pts_xy, pts_stride, d_n, n_lists, cap, d_out, stream=None):
+    """d2fe_depth_at_device on raw device addresses (ints): n_lists point lists [cap][2] float32 (pts_stride floats apart) against n_lists uint16 depth images (strides
+    in bytes), counts d_n [n_lists] int32, values to d_out [n_lists][cap] uint16 -- depth[cvRound(y)][cvRound(x)], 0 outside the image, for NaN and for slots >= n.
+    Asynchronous on `stream` (None: the handle's)."""
+    _check(fe._lib.d2fe_depth_at_device(fe.handle, C.c_void_p(d_depth), int(width), int(height), int(depth_stride), int(depth_image_stride), C.c_void_p(d_pts_xy),
+                                        int(pts_stride), C.c_void_p(d_n), int(n_lists), int(cap), C.c_void_p(d_out), C.c_void_p(stream or 0)))
 
 
 def _pinned_view(ptr, shape, dt):

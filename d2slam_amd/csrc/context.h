@@ -239,6 +239,16 @@ const char* lk_carry_check_params(const d2fe_track_params* tp);
 int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int width, int height, const d2fe_track_params& tp, const float* d_lists, int desc_dim,
                           float* d_right_xy, uint8_t* d_right_status, hipStream_t s);
 
+// lk.hip, for the mono pipe's sp_lk mode: the pyramids of n_frames images alone (no right images), image f's at f * (half of d2fe_lk_stereo_workspace_bytes(1, ..))
+int lk_pyramids_launch(d2fe_context* h, const uint8_t* d_img, int n_frames, int width, int height, int stride, size_t image_stride, int levels, void* d_workspace,
+                       hipStream_t s);
+
+// depth.hip: depth_gather_kernel over up to two segments of point lists (the pipe: the pass's keypoint rows and, with sp_lk, its landmark lists) in ONE launch.
+// List l of a segment reads depth image l, its points at pts + l * pts_stride floats, its count at n[l * n_stride], and writes out[l * cap .. + cap)
+struct DepthSeg { const float* pts; size_t pts_stride; const int32_t* n; size_t n_stride; int cap; uint16_t* out; };
+int depth_gather_launch(d2fe_context* h, const uint16_t* d_depth, int W, int H, size_t depth_stride_px, size_t depth_image_stride_px, int n_lists, const DepthSeg* segs,
+                        int n_segs, hipStream_t s);
+
 struct ProfScope {
   d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
   ProfScope(d2fe_context* h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {

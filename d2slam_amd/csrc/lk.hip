@@ -474,6 +474,35 @@ size_t d2fe_lk_stereo_workspace_bytes(int n_frames, int width, int height, int l
   return 2 * (size_t)n_frames * total;
 }
 
+// the pyramids of n_frames images alone (the mono pipe's sp_lk chain): the launches d2fe_lk_track_stereo_device issues for its left half, image f's pyramid at
+// f * total in d_workspace (half of d2fe_lk_stereo_workspace_bytes); arguments as checked there
+extern "C++" {
+namespace d2fe {
+int lk_pyramids_launch(d2fe_context* h, const uint8_t* d_img, int n_frames, int width, int height, int stride, size_t image_stride, int levels, void* d_workspace,
+                       hipStream_t s) {
+  if (!h || !d_img || !d_workspace) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (width < 16 || height < 16 || levels < 0 || levels > 7 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
+  if (stride < width || (n_frames > 1 && image_stride < (size_t)stride * (height - 1) + width)) return ctx_fail(D2FE_ERR_INVALID, "bad stride / image stride");
+  if (n_frames < 1 || n_frames > 65535) return ctx_fail(D2FE_ERR_INVALID, "n_frames must be 1..65535");
+  LK_TRY(hipSetDevice(ctx_device(h)));
+  int off[9], ws[9], hs[9], o = 0;
+  for (int l = 0, w = width, hh = height; l <= levels; ++l) { off[l] = o; ws[l] = w; hs[l] = hh; o += w * hh; w = (w + 1) / 2; hh = (hh + 1) / 2; }
+  PyrBatchArgs a{};
+  a.left = d_img; a.right = nullptr; a.src_stride = (size_t)stride; a.src_image_stride = image_stride;      // blockIdx.z < n: the kernel never reads a.right
+  a.ws = static_cast<uint8_t*>(d_workspace); a.total = (size_t)o; a.n = n_frames;
+  for (int l = 1; l <= (levels > 0 ? levels : 1); ++l) {
+    a.first = l == 1;
+    a.src_off = off[l - 1]; a.sw = ws[l - 1]; a.sh = hs[l - 1];
+    a.dw = (a.sw + 1) / 2; a.dh = (a.sh + 1) / 2; a.dst_off = l <= levels ? off[l] : -1;
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(pyr_down_batch_kernel, dim3((a.dw + 63) / 64, (a.dh + 3) / 4, n_frames), dim3(256), 0, s, a);
+  }
+  LK_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+}  // namespace d2fe
+}  // extern "C++"
+
 int d2fe_lk_track_stereo_device(d2fe_handle h, const uint8_t* d_left, const uint8_t* d_right, int n_frames, int width, int height, int stride,
                                 size_t image_stride, const float* d_kps_xy, const int32_t* d_n_kp, int cap, int levels, int win, int iters,
                                 void* d_workspace, float* d_pts_xy, uint8_t* d_status, void* stream) {

@@ -26,6 +26,13 @@
 // lane, in the very workspace this pass has just overwritten, so every pass ends its chain with a device copy of its last left pyramid into ONE pipe-owned buffer; the
 // lane's ev_chain, recorded behind the copy, is what the next pass's first step waits for (a strict chain: the buffer's reader and its next writer are the same
 // stream).  ONE launch then tracks the list entries of all frames left -> right; the per-keypoint launch of lr_lk is not issued.
+//
+// d2fe_pipe_camera::mono (d2fe_pipe_create_camera; the reference's MONOCULAR configuration): there is no right image.  The lane's input buffer, its pinned staging and its activations hold F * C images (image
+// rows 0 .. F * C - 1, tight), the networks run as in the lr_lk branch and the result block keeps its [2 F] rows, the right ones untouched (n_kp = 0).  With sp_lk only the
+// pyramids of the one image are built (lk_pyramids_launch) and the left -> right launch is not issued.
+// d2fe_pipe_camera::depth (PINHOLE_DEPTH, with mono): a 16-bit depth frame travels beside every gray frame (a second input buffer and staging of the same row order), and ONE
+// depth_gather_kernel launch per pass (depth.hip), behind the SuperPoint tail and the sp_lk chain and in front of the D2H, writes the value under every keypoint
+// (o_kpd: [F * C][cap] uint16) and every list entry (o_trd: [F * C][capT] uint16) into the result block, inside d2h_words.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,7 +54,11 @@ struct d2fe_pipe_s {
   // K lanes; a PASS = the g <= C consecutive submits that run as one launch sequence on one lane (C = cfg.coalesce; C > 1 needs F = 1).
   // Image / output row order of a pass: C == 1: L_0 .. L_(F-1), R_0 .. R_(F-1); C > 1: L, R of submit 0, L, R of submit 1, ... (a pass of g
   // submits is a prefix, so every address is fixed at creation whatever g turns out to be)
-  int K = 0, F = 0, C = 1, NI = 0, W = 0, H = 0, cap = 0, D = 256, G = 0, npp = 0;      // NI: images per full pass; npp: matcher pairs per submit
+  int K = 0, F = 0, C = 1, NI = 0, W = 0, H = 0, cap = 0, D = 256, G = 0, npp = 0;      // NI: result rows per full pass (2 F C); npp: matcher pairs per submit
+  int NIM = 0;                       // images per full pass in the lane's input buffer: NI, mono: F * C
+  bool mono = false, depth = false;
+  size_t o_kpd = 0, o_trd = 0;       // depth: uint16 [F * C][cap] and, with sp_lk, [F * C][capT] (inside d2h_words)
+  uint16_t* d_dep_all = nullptr;     // depth: the lanes' depth input buffers, lane k at k * NIM images
   // block layout (float words from the block base; every array starts on a 64-word boundary)
   size_t o_desc = 0, o_kps = 0, o_scores = 0, o_nv = 0, o_cnt = 0, o_mn = 0, o_mq = 0, o_mt = 0, o_md = 0, o_idx = 0, blk_words = 0, d2h_words = 0;
   // lr_lk: the tracks [F * C][cap][2] floats and [F * C][cap] bytes (inside d2h_words); coalesce > 1: SuperPoint writes the g left images of a pass to the compact
@@ -69,6 +80,8 @@ struct d2fe_pipe_s {
     bool nv_on_side[2] = {false, false};      // the pass that wrote this block ran NetVLAD on the lane's second stream (auto mode decides per pass)
     uint8_t* d_img = nullptr;
     uint8_t* d_lk = nullptr;           // lr_lk: this lane's pyramid workspace
+    uint16_t* d_dep = nullptr;         // depth: this lane's depth frames, in the row order of d_img
+    uint16_t* pin_dep = nullptr;       // depth without pinned_input: their pinned staging
   };
   std::vector<Lane> lanes;
   std::vector<int> first_class, second_class;   // the hardware-pipe class place_streams() measured for each lane's two streams (-1: not measured / no such stream)
@@ -100,6 +113,7 @@ struct d2fe_pipe_s {
   float* block(int lane, int set) const { return d_all + 64 + ((size_t)lane * 2 + set) * blk_words; }
   int left_row(int j, int f) const { return C > 1 ? 2 * j : f; }
   int right_row(int j, int f) const { return C > 1 ? 2 * j + 1 : F + f; }
+  int img_row(int j, int f) const { return mono ? (C > 1 ? j : f) : left_row(j, f); }      // where the left image of (submit j, frame f) sits in the lane's input buffer
 };
 
 namespace {
@@ -269,9 +283,10 @@ int pipe_flush(d2fe_pipe_s* p) {
   const int F = p->F, W = p->W, H = p->H;
   hipStream_t s = L.s;
   float* B = p->block(k, set);
-  const int n_left = p->C > 1 ? g : F, n_img = p->lk ? n_left : 2 * n_left;      // images SuperPoint sees
-  const bool staged = p->lk && p->C > 1;
-  const size_t left_stride = p->C > 1 ? 2 * img : img;
+  const bool left_only = p->lk || p->mono;
+  const int n_left = p->C > 1 ? g : F, n_img = left_only ? n_left : 2 * n_left;      // images SuperPoint sees
+  const bool staged = left_only && p->C > 1;
+  const size_t left_stride = p->C > 1 && !p->mono ? 2 * img : img;
   int rc;
   // Where this pass's NetVLAD runs.  The device runs FOUR busy streams of a process side by side and makes a fifth take turns (d2fe_pipe_create), so in auto mode a pass
   // takes the lane's second stream (SuperPoint and NetVLAD beside each other: the shortest latency of one frame) only while that keeps the busy streams at four or fewer,
@@ -319,8 +334,9 @@ int pipe_flush(d2fe_pipe_s* p) {
   }
   if (p->sp_lk) {
     // the pyramids of the pass (the same two launches), then the landmark list: one step per left frame in time order, the carry copy, ONE left -> right launch
-    rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride, nullptr, nullptr, 0, p->tp.levels,
-                                     p->tp.win, p->tp.iters, L.d_lk, nullptr, nullptr, s);
+    if (p->mono) rc = lk_pyramids_launch(L.ctx, L.d_img, n_left, W, H, W, left_stride, p->tp.levels, L.d_lk, s);
+    else rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride, nullptr, nullptr, 0, p->tp.levels,
+                                          p->tp.win, p->tp.iters, L.d_lk, nullptr, nullptr, s);
     if (rc) return rc;
     const auto [pk, pset] = prev_pass_block(k, set, p->K);
     if (P > 0 && p->K > 1) HIP_TRY(hipStreamWaitEvent(s, p->lanes[pk].ev_chain, 0));
@@ -339,7 +355,23 @@ int pipe_flush(d2fe_pipe_s* p) {
     }
     HIP_TRY(hipMemcpyAsync(p->d_carry_pyr, L.d_lk + (size_t)(n_left - 1) * p->pyr_total, p->pyr_total, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipEventRecord(L.ev_chain, s));
-    rc = lk_carry_right_launch(L.ctx, L.d_lk, n_left, W, H, p->tp, B + p->o_list, p->D, B + p->o_rxy, reinterpret_cast<uint8_t*>(B + p->o_rst), s);
+    if (!p->mono) {
+      rc = lk_carry_right_launch(L.ctx, L.d_lk, n_left, W, H, p->tp, B + p->o_list, p->D, B + p->o_rxy, reinterpret_cast<uint8_t*>(B + p->o_rst), s);
+      if (rc) return rc;
+    }
+  }
+  if (p->depth) {
+    // the depth under every keypoint of the pass's n_left frames (C > 1: the compact staging rows) and, with sp_lk, under every list entry: ONE launch
+    DepthSeg seg[2];
+    seg[0] = DepthSeg{staged ? B + p->o_skps : B + p->o_kps, (size_t)p->cap * 2, reinterpret_cast<const int32_t*>(staged ? B + p->o_scnt : B + p->o_cnt), 1, p->cap,
+                      reinterpret_cast<uint16_t*>(B + p->o_kpd)};
+    if (p->sp_lk) {
+      const float* lists = B + p->o_list;
+      seg[1] = DepthSeg{lists + d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_PTS), p->list_words,
+                        reinterpret_cast<const int32_t*>(lists + d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_HDR)), p->list_words, p->capT,
+                        reinterpret_cast<uint16_t*>(B + p->o_trd)};
+    }
+    rc = depth_gather_launch(L.ctx, L.d_dep, W, H, (size_t)W, img, n_left, seg, p->sp_lk ? 2 : 1, s);
     if (rc) return rc;
   }
   if (nv_side) {
@@ -394,12 +426,18 @@ int pipe_alloc_blocks(d2fe_pipe_s* p) {
     p->capT = p->tp.total_feature_num + 1;
     p->list_words = d2fe_lk_carry_list_bytes(p->capT, p->D) / sizeof(float);
     p->o_list = o; o += NL * p->list_words;
-    p->o_rxy = o; o += up64(NL * p->capT * 2);
-    p->o_rst = o; o += up64((NL * p->capT + 3) / 4);
+    if (!p->mono) {
+      p->o_rxy = o; o += up64(NL * p->capT * 2);
+      p->o_rst = o; o += up64((NL * p->capT + 3) / 4);
+    }
+  }
+  if (p->depth) {
+    p->o_kpd = o; o += up64((NL * cap + 1) / 2);
+    if (p->sp_lk) { p->o_trd = o; o += up64((NL * p->capT + 1) / 2); }
   }
   p->d2h_words = o;
   p->o_idx = o; o += up64(NI * cap);
-  if (p->lk && C > 1) {
+  if ((p->lk || p->mono) && C > 1) {
     p->o_sdesc = o; o += up64(NL * cap * p->D);
     p->o_skps = o; o += up64(NL * cap * 2);
     p->o_sscores = o; o += up64(NL * cap);
@@ -472,7 +510,7 @@ int pipe_flush_group(d2fe_pipe_s* p, long long upto) {
   const size_t img = (size_t)p->W * p->H;
   for (int i = 0; i < n; ++i) HIP_TRY(hipStreamWaitEvent(p->gnv, p->lanes[k0 + i].ev_up, 0));
   float* d_out = p->d_gnv + ((size_t)gset * p->K + k0) * p->G;
-  const int rc = run_netvlad(p->gctx, p->d_img_all + (size_t)k0 * p->NI * img, n, p->W, p->H, p->W, (size_t)p->NI * img, d_out, p->gnv);
+  const int rc = run_netvlad(p->gctx, p->d_img_all + (size_t)k0 * p->NIM * img, n, p->W, p->H, p->W, (size_t)p->NIM * img, d_out, p->gnv);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(p->pin_gnv + ((size_t)gset * p->K + k0) * p->G, d_out, sizeof(float) * (size_t)n * p->G, hipMemcpyDeviceToHost, p->gnv));
   HIP_TRY(hipEventRecord(p->ev_g[slot], p->gnv));
@@ -532,10 +570,20 @@ void d2fe_pipe_default_config(d2fe_pipe_config* c) {
   c->netvlad_inline = 2;      // auto
 }
 
-int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out) {
+void d2fe_pipe_camera_default(d2fe_pipe_camera* c) {
+  memset(c, 0, sizeof(*c));
+  c->struct_size = (int32_t)sizeof(d2fe_pipe_camera);
+}
+
+int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2fe_pipe_camera* cam, d2fe_pipe* out);
+int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out) { return d2fe_pipe_create_camera(h, cfg, nullptr, out); }
+
+int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2fe_pipe_camera* cam, d2fe_pipe* out) {
   if (!h || !cfg || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(d2fe_pipe_config)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_config size mismatch");
+  if (cam && cam->struct_size != (int32_t)sizeof(d2fe_pipe_camera)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_camera size mismatch");
+  const int mono = cam ? cam->mono : 0, depth = cam ? cam->depth : 0;
   if (!h->sp_loaded) return pipe_fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
   if (cfg->netvlad && !h->nv_net) return pipe_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
   if (cfg->lanes < 1 || cfg->lanes > 16 || cfg->frames < 1 || cfg->frames > 4096) return pipe_fail(D2FE_ERR_INVALID, "lanes must be 1..16, frames >= 1");
@@ -550,7 +598,13 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   if (cfg->lr_lk && cfg->match_lr) return pipe_fail(D2FE_ERR_INVALID, "lr_lk = 1 needs match_lr = 0: SuperPoint does not run on the right image, so it has no descriptors to match");
   if (cfg->lr_lk && (cfg->width < 16 || cfg->height < 16)) return pipe_fail(D2FE_ERR_INVALID, "lr_lk needs frames of at least 16 x 16");
   if (cfg->sp_lk != 0 && cfg->sp_lk != 1) return pipe_fail(D2FE_ERR_INVALID, "sp_lk must be 0 or 1");
-  if (cfg->sp_lk && !cfg->lr_lk) return pipe_fail(D2FE_ERR_INVALID, "sp_lk = 1 needs lr_lk = 1: the landmark list is tracked on the pyramids the lr_lk stage builds");
+  if (mono != 0 && mono != 1) return pipe_fail(D2FE_ERR_INVALID, "mono must be 0 or 1");
+  if (depth != 0 && depth != 1) return pipe_fail(D2FE_ERR_INVALID, "depth must be 0 or 1");
+  if (mono && (cfg->match_lr || cfg->lr_lk)) return pipe_fail(D2FE_ERR_INVALID, "mono = 1 needs match_lr = 0 and lr_lk = 0: there is no right image");
+  if (depth && !mono) return pipe_fail(D2FE_ERR_INVALID, "depth = 1 needs mono = 1: a depth frame belongs to the one gray frame");
+  if (cfg->sp_lk && !cfg->lr_lk && !mono)
+    return pipe_fail(D2FE_ERR_INVALID, "sp_lk = 1 needs lr_lk = 1 or mono = 1: the landmark list is tracked on the pyramids the lr_lk stage (or the mono pipe) builds");
+  if (cfg->sp_lk && (cfg->width < 16 || cfg->height < 16)) return pipe_fail(D2FE_ERR_INVALID, "sp_lk needs frames of at least 16 x 16");
   if (h->cfg.max_keypoints < 0) return pipe_fail(D2FE_ERR_UNSUPPORTED, "keep-all handles (max_keypoints = -1) are served by the single-call entry points");
   if (cfg->width > h->cfg.max_width || cfg->height > h->cfg.max_height) return pipe_fail(D2FE_ERR_INVALID, "frame size exceeds the handle's maximum");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
@@ -560,11 +614,12 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
   p->M = M;
   p->lk = cfg->lr_lk != 0;
   p->sp_lk = cfg->sp_lk != 0;
+  p->mono = mono != 0; p->depth = depth != 0;
   d2fe_track_default_params(&p->tp);
   if (p->sp_lk) p->pyr_total = d2fe_lk_stereo_workspace_bytes(1, cfg->width, cfg->height, LK_LEVELS) / 2;
   p->nv_inline = cfg->netvlad_inline == 1;
   p->nv_auto = cfg->netvlad_inline == 2 && cfg->lanes > 2;      // one or two lanes: never more than four busy streams, the second stream always
-  p->K = cfg->lanes; p->F = cfg->frames; p->C = C; p->NI = 2 * cfg->frames * C; p->W = cfg->width; p->H = cfg->height;
+  p->K = cfg->lanes; p->F = cfg->frames; p->C = C; p->NI = 2 * cfg->frames * C; p->NIM = p->mono ? cfg->frames * C : p->NI; p->W = cfg->width; p->H = cfg->height;
   p->cap = cfg->cap < h->cfg.max_keypoints ? cfg->cap : h->cfg.max_keypoints;
   p->D = d2fe_desc_dim(h);
   p->G = cfg->netvlad ? d2fe_netvlad_dim(h) : 0;
@@ -581,9 +636,10 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       const int rcb = pipe_alloc_blocks(p);
       if (rcb) return rcb;
     }
-    HIP_TRY(hipMalloc(&p->d_img_all, (size_t)p->W * p->H * p->NI * p->K));
-    if (p->lk) {
-      p->lk_ws_lane = (d2fe_lk_stereo_workspace_bytes((int)NL, p->W, p->H, LK_LEVELS) + 255) / 256 * 256;
+    HIP_TRY(hipMalloc(&p->d_img_all, (size_t)p->W * p->H * p->NIM * p->K));
+    if (p->depth) HIP_TRY(hipMalloc(&p->d_dep_all, sizeof(uint16_t) * p->W * p->H * p->NIM * p->K));
+    if (p->lk || (p->mono && p->sp_lk)) {      // mono: the pyramids of the one image
+      p->lk_ws_lane = (d2fe_lk_stereo_workspace_bytes((int)NL, p->W, p->H, LK_LEVELS) / (p->mono ? 2 : 1) + 255) / 256 * 256;
       HIP_TRY(hipMalloc(&p->d_lk_ws, p->lk_ws_lane * p->K));
     }
     if (p->M > 1) {
@@ -636,14 +692,18 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
       // for a share of the device leave workgroup slots on every CU to the other lanes
       if (!lane_cus && cfg->lane_cus > 0 && cfg->lane_cus < h->ncu) lane_cus = cfg->lane_cus;
       if (!masked) { ms = spare.first[k]; spare.first[k] = nullptr; if (nv_streams) { L.nv = spare.second[k]; spare.second[k] = nullptr; } }
-      int rc2 = clone_lane(h, p->lk ? (int)NL : p->NI, &L.ctx, ms, lane_cus, cfg->netvlad && p->M == 1);      // lr_lk: the networks see the left images only
+      int rc2 = clone_lane(h, p->lk || p->mono ? (int)NL : p->NI, &L.ctx, ms, lane_cus, cfg->netvlad && p->M == 1);      // lr_lk: the networks see the left images only
       if (rc2) { if (ms) (void)hipStreamDestroy(ms); return rc2; }
       L.s = L.ctx->stream;
       rc2 = lane_create_events(L, p->sp_lk);
       if (rc2) return rc2;
-      L.d_img = p->d_img_all + (size_t)k * p->NI * p->W * p->H;
-      if (p->lk) L.d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
-      if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, (size_t)p->W * p->H * p->NI, hipHostMallocDefault));
+      L.d_img = p->d_img_all + (size_t)k * p->NIM * p->W * p->H;
+      if (p->d_lk_ws) L.d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
+      if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_in, (size_t)p->W * p->H * p->NIM, hipHostMallocDefault));
+      if (p->depth) {
+        L.d_dep = p->d_dep_all + (size_t)k * p->NIM * p->W * p->H;
+        if (!cfg->pinned_input) HIP_TRY(hipHostMalloc(&L.pin_dep, sizeof(uint16_t) * p->W * p->H * p->NIM, hipHostMallocDefault));
+      }
       rc2 = pipe_alloc_pinned(p, L);
       if (rc2) return rc2;
     }
@@ -677,7 +737,8 @@ int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out)
 void d2fe_pipe_destroy(d2fe_pipe p) {
   if (!p) return;
   (void)hipSetDevice(p->parent->cfg.device_id);
-  for (auto& L : p->lanes) lane_destroy(L);
+  for (auto& L : p->lanes) { lane_destroy(L); if (L.pin_dep) (void)hipHostFree(L.pin_dep); }
+  if (p->d_dep_all) (void)hipFree(p->d_dep_all);
   if (p->gnv) (void)hipStreamSynchronize(p->gnv);
   for (auto e : p->ev_g) if (e) (void)hipEventDestroy(e);
   if (p->gctx) d2fe_destroy(p->gctx);
@@ -695,9 +756,17 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   pipe_gone(parent);
 }
 
-int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int stride, size_t image_stride, int64_t* ticket) {
-  if (!p || !left || !right || !ticket) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+// d2fe_pipe_submit and d2fe_pipe_submit_depth (depth != NULL: strides in bytes).  The argument refusals in front of the lock queue nothing and do not end the pipe
+static int pipe_submit_impl(d2fe_pipe p, const uint8_t* left, const uint8_t* right, const uint16_t* depth, int stride, size_t depth_stride, size_t image_stride,
+                            size_t depth_image_stride, int64_t* ticket) {
+  if (!p || !left || !ticket) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  if (p->depth && !depth) return pipe_fail(D2FE_ERR_INVALID, "this pipe was created with depth = 1: submit frames with d2fe_pipe_submit_depth");
+  if (!p->depth && depth) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_submit_depth needs a pipe created with depth = 1");
+  if (!p->mono && !right) return pipe_fail(D2FE_ERR_INVALID, "null argument (a stereo pipe needs the right image; one camera: d2fe_pipe_create_camera with mono = 1)");
+  if (p->mono && right) return pipe_fail(D2FE_ERR_INVALID, "a mono pipe takes right = NULL");
   if (stride < p->W) return pipe_fail(D2FE_ERR_INVALID, "stride < width");
+  if (depth && (depth_stride % 2 || depth_image_stride % 2 || depth_stride < (size_t)2 * p->W || (p->F > 1 && depth_image_stride < depth_stride * (p->H - 1) + (size_t)2 * p->W)))
+    return pipe_fail(D2FE_ERR_INVALID, "bad depth stride / image stride (bytes, even, depth_stride >= 2 * width)");
   HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call and accepts no more work (destroy it): " + p->failed_msg);
@@ -738,12 +807,12 @@ int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int
   // frames of this submit -> the lane's input buffer at the rows of submit j (H2D is issued at once: it travels while the pass fills).  Left and right frames that are
   // one contiguous run on the host AND in the lane's buffer (C == 1: rows [0, F) | [F, 2F); C > 1: rows 2j, 2j + 1) travel as ONE copy: a DMA costs ~10 us of
   // set-up whatever its size, and a one-frame pass waits for it
-  const bool one_run = p->cfg.pinned_input && stride == W && image_stride == img && right == left + img * F &&
-                       p->right_row(j, 0) == p->left_row(j, 0) + (size_t)F;
+  const bool pair_run = !p->mono && p->right_row(j, 0) == p->left_row(j, 0) + F;      // the two sides of a submit are consecutive rows of the lane's buffer
+  const bool one_run = p->cfg.pinned_input && stride == W && image_stride == img && right == left + img * F && pair_run;
   if (one_run) HIP_TRY(hipMemcpyAsync(L.d_img + (size_t)p->left_row(j, 0) * img, left, 2 * img * F, hipMemcpyHostToDevice, s));
-  for (int side = 0; side < 2 && !one_run; ++side) {
+  for (int side = 0; side < (p->mono ? 1 : 2) && !one_run; ++side) {
     const uint8_t* src = side ? right : left;
-    const size_t row0 = side ? p->right_row(j, 0) : p->left_row(j, 0);       // the F images of a side are consecutive rows (C > 1: F = 1)
+    const size_t row0 = side ? p->right_row(j, 0) : p->img_row(j, 0);       // the F images of a side are consecutive rows (C > 1: F = 1)
     uint8_t* dst = L.d_img + row0 * img;
     if (p->cfg.pinned_input) {
       if (stride == W && image_stride == img) HIP_TRY(hipMemcpyAsync(dst, src, img * F, hipMemcpyHostToDevice, s));
@@ -757,10 +826,27 @@ int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int
         else for (int y = 0; y < H; ++y) memcpy(stage + f * img + (size_t)y * W, sf + (size_t)y * stride, W);
       }
       // the staging buffer has the lane buffer's row order: after the right side was staged, both sides of a submit are one run
-      if (side == 0 && p->right_row(j, 0) == p->left_row(j, 0) + (size_t)F) continue;
-      if (side == 1 && p->right_row(j, 0) == p->left_row(j, 0) + (size_t)F)
+      if (side == 0 && pair_run) continue;
+      if (side == 1 && pair_run)
         HIP_TRY(hipMemcpyAsync(L.d_img + (size_t)p->left_row(j, 0) * img, L.pin_in + (size_t)p->left_row(j, 0) * img, 2 * img * F, hipMemcpyHostToDevice, s));
       else HIP_TRY(hipMemcpyAsync(dst, stage, img * F, hipMemcpyHostToDevice, s));
+    }
+  }
+  if (depth) {      // the depth frames of this submit, to the rows of its gray frames
+    const size_t row0 = p->img_row(j, 0), db = 2 * img;       // bytes of a tight depth image
+    uint16_t* dst = L.d_dep + row0 * img;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(depth);
+    if (p->cfg.pinned_input) {
+      if (depth_stride == (size_t)2 * W && depth_image_stride == db) HIP_TRY(hipMemcpyAsync(dst, src, db * F, hipMemcpyHostToDevice, s));
+      else for (int f = 0; f < F; ++f) HIP_TRY(hipMemcpy2DAsync(dst + f * img, (size_t)2 * W, src + f * depth_image_stride, depth_stride, (size_t)2 * W, H, hipMemcpyHostToDevice, s));
+    } else {
+      uint8_t* stage = reinterpret_cast<uint8_t*>(L.pin_dep + row0 * img);
+      for (int f = 0; f < F; ++f) {
+        const uint8_t* sf = src + f * depth_image_stride;
+        if (depth_stride == (size_t)2 * W) memcpy(stage + f * db, sf, db);
+        else for (int y = 0; y < H; ++y) memcpy(stage + f * db + (size_t)y * 2 * W, sf + (size_t)y * depth_stride, (size_t)2 * W);
+      }
+      HIP_TRY(hipMemcpyAsync(dst, stage, db * F, hipMemcpyHostToDevice, s));
     }
   }
   auto& ti = p->tinfo[(size_t)(t % (long long)p->tinfo.size())];
@@ -787,6 +873,16 @@ int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int
   }();
   if (rc_all != D2FE_OK) { p->failed = rc_all; p->failed_msg = d2fe_last_error(); }
   return rc_all;
+}
+
+int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int stride, size_t image_stride, int64_t* ticket) {
+  return pipe_submit_impl(p, left, right, nullptr, stride, 0, image_stride, 0, ticket);
+}
+
+int d2fe_pipe_submit_depth(d2fe_pipe p, const uint8_t* gray, const uint16_t* depth, int stride, int depth_stride, size_t image_stride, size_t depth_image_stride,
+                           int64_t* ticket) {
+  if (!depth || depth_stride < 0) return pipe_fail(D2FE_ERR_INVALID, "null depth image / negative depth stride");
+  return pipe_submit_impl(p, gray, nullptr, depth, stride, (size_t)depth_stride, image_stride, depth_image_stride, ticket);
 }
 
 int d2fe_pipe_wait(d2fe_pipe p, int64_t ticket, d2fe_pipe_result* out) {
@@ -879,8 +975,30 @@ int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_track_resu
   const size_t r0 = p->C > 1 ? (size_t)ti.j : 0, capT = (size_t)p->capT;
   out->frames = p->F;
   track_list_view(out, B + p->o_list + r0 * p->list_words, p->capT, p->D, p->list_words);
-  out->right_xy = B + p->o_rxy + r0 * capT * 2;
-  out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_rst) + r0 * capT;
+  if (!p->mono) {       // a mono pipe has no right image: both stay NULL
+    out->right_xy = B + p->o_rxy + r0 * capT * 2;
+    out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_rst) + r0 * capT;
+  }
+  return D2FE_OK;
+}
+
+int d2fe_pipe_depth_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_depth_result* out) {
+  if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (!p->depth) return pipe_fail(D2FE_ERR_UNSUPPORTED, "this pipe was created without depth: it has no depth frames");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
+  const auto ti = p->tinfo[(size_t)(ticket % (long long)p->tinfo.size())];
+  if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass < 0 || ti.pass + 2 * p->K < p->next_pass)
+    return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the depth values within 2 * lanes passes");
+  if (!ti.waited) return pipe_fail(D2FE_ERR_NOT_READY, "d2fe_pipe_wait has not returned this ticket yet");
+  const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
+  const float* B = p->lanes[k].pin_out[set];
+  const size_t r0 = p->C > 1 ? (size_t)ti.j : 0;
+  out->frames = p->F; out->cap = p->cap; out->cap_tracks = p->sp_lk ? p->capT : 0;
+  out->kp_depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_kpd) + r0 * p->cap;
+  if (p->sp_lk) out->track_depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_trd) + r0 * p->capT;
   return D2FE_OK;
 }
 

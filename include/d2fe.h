@@ -349,7 +349,7 @@ typedef struct {
                                image has no descriptors: D2FE_ERR_INVALID otherwise).  Works with any lanes / frames, netvlad, match_prev, pinned_input,
                                coalesce, coalesce_depth, netvlad_inline, netvlad_group, lane_cus and cu_partition (the LK launches run on the lane's own
                                stream, CU-masked or not).  0 (d2fe_pipe_default_config): SuperPoint on both images, as before */
-  int32_t sp_lk;            /* 1 (needs lr_lk = 1, D2FE_ERR_INVALID otherwise; the two together are the reference's defaults): the OTHER half of the reference's stereo
+  int32_t sp_lk;            /* 1 (needs lr_lk = 1 or mono = 1, D2FE_ERR_INVALID otherwise; sp_lk with lr_lk are the reference's defaults): the OTHER half of the reference's stereo
                                tracker, sp_track_use_lk = true (d2featuretracker.h:63): the temporal association is the LK-carried landmark list of
                                D2FeatureTracker::trackLK(frame) (d2featuretracker.cpp:472-621), kept on the DEVICE and carried across frames, passes and lanes: per left
                                frame one d2fe_lk_carry_step_device (track the previous list, reduceVector, removeNearPoints, replenish from the frame's SuperPoint
@@ -359,7 +359,9 @@ typedef struct {
                                lists travel with the pass's one D2H and are read with d2fe_pipe_track_result_get; d2fe_pipe_lk_result_get is D2FE_ERR_UNSUPPORTED (the
                                per-keypoint left -> right launch is not issued).  d2fe_pipe_result is bit-identical to the same pipe with sp_lk = 0 (match_prev stays
                                available).  Parameters: d2fe_pipe_set_track_params before the first submit (the reference's defaults otherwise).  Works with any
-                               lanes / frames and every other option; frames are chained in submit order.  0 (d2fe_pipe_default_config): off */
+                               lanes / frames and every other option; frames are chained in submit order.  0 (d2fe_pipe_default_config): off.
+                               With d2fe_pipe_camera::mono = 1 in place of lr_lk = 1: the same chain on the pyramids of the one image (only those are built: half the workspace); the
+                               left -> right launch is not issued, d2fe_pipe_track_result::right_xy / right_status are NULL */
 } d2fe_pipe_config;
 typedef struct {            /* HOST pointers into the lane's pinned block; valid until 2 * lanes further submits */
   int32_t frames, cap, desc_dim, netvlad_dim;
@@ -380,6 +382,32 @@ typedef struct {            /* HOST pointers into the lane's pinned block, same 
   const float* pts_xy;      /* [frames][cap][2]  right-image position of left keypoint i of frame f */
   const uint8_t* status;    /* [frames][cap]     1: forward && reverse && |prev - reverse| <= 0.5 && inBorder (opticaltrack_utils.cpp:260-272) */
 } d2fe_pipe_lk_result;
+/* The camera configurations with ONE camera per frame (the reference has five, d2basetypes.h:40-46; the stereo pipe above is STEREO_PINHOLE).  d2fe_pipe_config is a
+ * closed struct of 96 bytes (its last two ints went to lr_lk and sp_lk, and its size is checked strictly), so the two options live in a struct of their own, handed to
+ * d2fe_pipe_create_camera beside the pipe's configuration.  d2fe_pipe_create(h, cfg, out) is d2fe_pipe_create_camera(h, cfg, NULL, out): a stereo pipe, as before. */
+typedef struct {
+  int32_t struct_size;      /* sizeof(d2fe_pipe_camera), checked strictly */
+  int32_t mono;             /* 1: ONE camera per frame -- the reference's MONOCULAR configuration (d2basetypes.h:40-46; config/gopro, config/visensor_f9p): SuperPoint
+                               and NetVLAD on the one image (LoopCam::generateImageDescriptor, loop_cam.cpp:259-331), matchKNN against the previous frame
+                               (D2FeatureTracker::track, d2featuretracker.cpp:105-107) or, with sp_lk, the LK-carried list.  Needs match_lr = 0 and lr_lk = 0
+                               (D2FE_ERR_INVALID otherwise).  d2fe_pipe_submit takes right = NULL (a non-NULL right image is D2FE_ERR_INVALID; it queues nothing and does
+                               not end the pipe).  A lane uploads, stages and holds activations for frames * coalesce images, not twice that.  d2fe_pipe_result and
+                               d2fe_pipe_device_result keep their [2 frames] layout exactly as with lr_lk: the rows of "right" images have n_kp = 0 in every pass, on
+                               the device too, lr_* are NULL, and the left rows, NetVLAD and the prev_* lists are bit-identical to the stereo pipe with match_lr = 0
+                               on the same left frames -- so d2fe_exchange_*, d2fe_loop_*, d2fe_window_* and the device views work on a mono pipe unchanged.  Works
+                               with lanes, frames, netvlad, match_prev, pinned_input, coalesce, coalesce_depth, netvlad_inline, netvlad_group, lane_cus and
+                               cu_partition.  0 (d2fe_pipe_camera_default): a stereo pipe, as before */
+  int32_t depth;            /* 1 (needs mono = 1, D2FE_ERR_INVALID otherwise): the reference's PINHOLE_DEPTH configuration -- every frame comes with a 16-bit depth
+                               image of the same width x height (LoopCam::generateGrayDepthImageDescriptor, loop_cam.cpp:333-441).  Frames enter through
+                               d2fe_pipe_submit_depth (plain d2fe_pipe_submit is D2FE_ERR_INVALID on such a pipe, d2fe_pipe_submit_depth on every other pipe; neither
+                               refusal ends the pipe); the depth frames travel like the gray ones (pinned staging unless pinned_input, H2D on the lane's stream).  ONE
+                               launch per pass behind the SuperPoint tail (with sp_lk: behind the chain) reads the depth under every keypoint and every list entry; the
+                               values travel with the pass's one D2H and are read with d2fe_pipe_depth_result_get.  Every other result is bit-identical to the same
+                               pipe with depth = 0.  0 (d2fe_pipe_camera_default): off */
+  int32_t reserved;         /* 0 */
+} d2fe_pipe_camera;
+D2FE_API void d2fe_pipe_camera_default(d2fe_pipe_camera* cam);      /* struct_size, mono = 0, depth = 0 */
+D2FE_API int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2fe_pipe_camera* cam /* NULL: stereo */, d2fe_pipe* out);
 D2FE_API void d2fe_pipe_default_config(d2fe_pipe_config* cfg);
 D2FE_API int d2fe_pipe_create(d2fe_handle h, const d2fe_pipe_config* cfg, d2fe_pipe* out);
 D2FE_API void d2fe_pipe_destroy(d2fe_pipe p);
@@ -391,7 +419,7 @@ D2FE_API int d2fe_pipe_stream_placement(d2fe_pipe p, int32_t* classes /*[2 * lan
 /* d2fe_profile_enable / d2fe_profile_read over all lanes (sums) */
 D2FE_API int d2fe_pipe_profile_enable(d2fe_pipe p, int mode);
 D2FE_API int d2fe_pipe_profile_read(d2fe_pipe p, float* ms /*[D2FE_PROF_COUNT]*/, int32_t* launches /*[D2FE_PROF_COUNT]*/);
-/* left / right: `frames` gray u8 images each, image f at + f * image_stride, rows `stride` bytes apart.  Returns at once with a ticket
+/* left / right: `frames` gray u8 images each, image f at + f * image_stride, rows `stride` bytes apart (a mono pipe, d2fe_pipe_camera::mono = 1: right is NULL).  Returns at once with a ticket
  * (0, 1, 2, ...).  Blocks only when the ticket's lane still holds the pass submitted `lanes` passes ago that nobody waited for. */
 D2FE_API int d2fe_pipe_submit(d2fe_pipe p, const uint8_t* left, const uint8_t* right, int stride, size_t image_stride, int64_t* ticket);
 /* Blocks until the ticket's frame is complete on the host (launching its pass first if coalescing still holds it back).  Tickets may be waited
@@ -417,8 +445,8 @@ typedef struct {            /* HOST pointers into the lane's pinned block, same 
   const int32_t* id; const int32_t* src; const int32_t* kp;      /* per list: [cap_tracks] at + f * list_words */
   const float* desc;                 /* per list: [cap_tracks][desc_dim] at desc + f * list_words */
   const float* scores;               /* per list: [cap_tracks] at scores + f * list_words */
-  const float* right_xy;             /* [frames][cap_tracks][2], contiguous (NOT strided by list_words) */
-  const uint8_t* right_status;       /* [frames][cap_tracks], contiguous */
+  const float* right_xy;             /* [frames][cap_tracks][2], contiguous (NOT strided by list_words); NULL on a mono pipe */
+  const uint8_t* right_status;       /* [frames][cap_tracks], contiguous; NULL on a mono pipe */
 } d2fe_pipe_track_result;
 D2FE_API int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_track_result* out);
 /* sp_lk = 1: replaces the reference's default tracker parameters (d2fe_track_default_params).  Accepted only before the first submit (D2FE_ERR_INVALID afterwards,
@@ -426,6 +454,32 @@ D2FE_API int d2fe_pipe_track_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_t
  * total_feature_num + 1 > 1024); a refusal leaves the pipe as it was. */
 struct d2fe_track_params_s;
 D2FE_API int d2fe_pipe_set_track_params(d2fe_pipe p, const struct d2fe_track_params_s* tp);
+/* depth = 1: d2fe_pipe_submit with a depth frame per gray frame.  gray as `left` of d2fe_pipe_submit; depth: `frames` images of uint16_t, width x height, image f at
+ * + f * depth_image_stride BYTES, rows depth_stride BYTES apart (both even, depth_stride >= 2 * width).  With pinned_input both pointers are page-locked and stay
+ * valid until the ticket was waited for. */
+D2FE_API int d2fe_pipe_submit_depth(d2fe_pipe p, const uint8_t* gray, const uint16_t* depth, int stride, int depth_stride, size_t image_stride,
+                                    size_t depth_image_stride, int64_t* ticket);
+/* depth = 1: the depth values of a ticket that d2fe_pipe_wait has returned (D2FE_ERR_NOT_READY before that, D2FE_ERR_UNSUPPORTED on a pipe without depth).
+ * Value contract: for a point (x, y) the value is depth[iy][ix] with ix = cvRound(x), iy = cvRound(y); cvRound rounds half to even (2.5 -> 2, 3.5 -> 4,
+ * -0.5 -> 0), which is what cv::Mat::at<ushort>(cv::Point2f) does through Point_<float> -> Point_<int> -> saturate_cast<int> (upstream OpenCV behaviour, not part
+ * of the reference tree; the reference's reads are loop_cam.cpp:382 and d2featuretracker.cpp:790-798).  If ix or iy falls outside the image, or a coordinate is NaN,
+ * the value is 0: the reference would read out of bounds there, and 0 fails its dep > DEPTH_NEAR_THRES test.  Values are raw (millimetres for a RealSense): the
+ * / 1000.0, DEPTH_NEAR_THRES / DEPTH_FAR_THRES, liftProjective, pt3d = pose_cam * (pt2d_norm * dep) and depth = pt3dcam.norm() stay with the caller
+ * (INTEGRATION.md). */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
+  int32_t frames, cap, cap_tracks, reserved;
+  const uint16_t* kp_depth_mm;       /* [frames][cap]: the value under keypoint i of frame f (d2fe_pipe_result::kps_xy row f); slots >= n_kp[f] hold 0 */
+  const uint16_t* track_depth_mm;    /* sp_lk: [frames][cap_tracks], contiguous: the value under list entry i of frame f at its position in that frame
+                                        (d2fe_pipe_track_result::pts_xy); slots >= n hold 0.  NULL without sp_lk */
+} d2fe_pipe_depth_result;
+D2FE_API int d2fe_pipe_depth_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_depth_result* out);
+/* The single-call form of the same lookup (what the pipe launches): n_lists point lists against n_lists depth images, asynchronous on `stream` (a hipStream_t; NULL:
+ * the handle's stream), no host synchronisation.  List l: depth image l at d_depth + l * depth_image_stride BYTES (rows depth_stride BYTES apart, both even), points
+ * d_pts_xy + l * pts_stride floats as [cap][2], count d_n[l] (read on the device, clamped to 0..cap), values to d_out[l * cap .. l * cap + cap): the value contract
+ * above for slots < d_n[l], 0 for the others.  All pointers are device memory. */
+D2FE_API int d2fe_depth_at_device(d2fe_handle h, const uint16_t* d_depth, int width, int height, size_t depth_stride, size_t depth_image_stride,
+                                  const float* d_pts_xy, size_t pts_stride /*floats between lists*/, const int32_t* d_n, int n_lists, int cap, uint16_t* d_out,
+                                  void* stream);
 
 /* Device-side consumers of a ticket's results: the cross-agent exchange (pack -> all-gather -> gate -> remote matching; the reference broadcasts
  * the frame it has just extracted, loop_net.cpp:24-87, d2featuretracker.cpp:237-310) runs on a stream of its OWN, behind the extraction of the ticket and beside the

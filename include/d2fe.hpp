@@ -202,7 +202,9 @@ class MobileNetVLAD {
 // cfg.sp_lk = 1 (sp_track_use_lk, with lr_lk the reference's defaults): the frame's LK-carried landmark list, what D2FeatureTracker::trackLK(frame) leaves in
 // LKImageInfo (d2featuretracker.cpp:472-621) -- entry i at pts[i] with the pipe-wide id[i]; src[i] = its index in the previous frame's list (-1: discovered in this
 // frame from SuperPoint keypoint kp[i] of kps_left); desc / scores are the SuperPoint row of its discovery frame; right[i] / right_status[i] its left -> right track
+// a mono pipe (d2fe_pipe_camera::mono): right / right_status stay empty.  A depth pipe (::depth): depth_mm[i] = the raw 16-bit depth under pts[i] (see StereoFrameResult::depth_mm)
 struct StereoTrackList {
+  std::vector<uint16_t> depth_mm;
   std::vector<Point2f> pts, right;
   std::vector<int32_t> id, src, kp;
   std::vector<float> scores, desc;                   // desc: [n][desc_dim]
@@ -221,16 +223,33 @@ struct StereoFrameResult {
   std::vector<Point2f> lk_right;
   std::vector<uint8_t> lk_status;
   StereoTrackList tracks;                            // cfg.sp_lk = 1 (lk_right / lk_status then stay empty: the list entries are what is tracked into the right image)
+  // a depth pipe (d2fe_pipe_camera::depth, PINHOLE_DEPTH): depth_mm[i] = depth.at<unsigned short>(kps_left[i]) of the frame's depth image (loop_cam.cpp:382), i.e. the pixel at
+  // (cvRound(x), cvRound(y)), 0 outside the image; the / 1000.0, the DEPTH_NEAR_THRES / DEPTH_FAR_THRES test and liftProjective stay with the caller
+  std::vector<uint16_t> depth_mm;
+};
+// borrowed view of a CV_16UC1 cv::Mat (a depth image); step in bytes
+struct DepthView {
+  const uint16_t* data = nullptr;
+  int rows = 0, cols = 0;
+  size_t step = 0;
+  DepthView() = default;
+  DepthView(const uint16_t* d, int rows_, int cols_, size_t step_ = 0) : data(d), rows(rows_), cols(cols_), step(step_ ? step_ : (size_t)cols_ * 2) {}
+#ifdef D2FE_WITH_OPENCV
+  DepthView(const cv::Mat& m) : data(m.type() == CV_16UC1 ? m.ptr<uint16_t>() : nullptr), rows(m.rows), cols(m.cols), step(m.step) {}
+#endif
 };
 class StereoPipe {
  public:
   // cfg: d2fe_pipe_default_config() + the fields the caller sets (lanes, width, height, cap, netvlad, coalesce, coalesce_depth, lr_lk (with match_lr = 0), ...);
-  // frames is forced to 1.  cfg.sp_lk = 1 (with lr_lk = 1): tp replaces the reference's tracker parameters (d2fe_track_default_params)
-  StereoPipe(d2fe_handle h, d2fe_pipe_config cfg, const d2fe_track_params* tp = nullptr) {
+  // frames is forced to 1.  cfg.sp_lk = 1 (with lr_lk = 1 or mono = 1): tp replaces the reference's tracker parameters (d2fe_track_default_params).
+  // cam (d2fe_pipe_camera_default + the fields the caller sets): cam->mono = 1 (MONOCULAR; cfg.match_lr = 0): submit(left); cam->mono = cam->depth = 1
+  // (PINHOLE_DEPTH): submit(left, depth).  NULL: a stereo pipe
+  StereoPipe(d2fe_handle h, d2fe_pipe_config cfg, const d2fe_track_params* tp = nullptr, const d2fe_pipe_camera* cam = nullptr) {
     cfg.frames = 1;
+    depth_ = cam && cam->depth != 0;
     sp_lk_ = cfg.sp_lk != 0;
     lr_lk_ = cfg.lr_lk != 0 && !sp_lk_;
-    if (d2fe_pipe_create(h, &cfg, &p_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_create: %s\n", d2fe_last_error()); p_ = nullptr; }
+    if (d2fe_pipe_create_camera(h, &cfg, cam, &p_) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_create: %s\n", d2fe_last_error()); p_ = nullptr; }
     if (p_ && tp && d2fe_pipe_set_track_params(p_, tp) != D2FE_OK) {
       std::fprintf(stderr, "[d2fe] d2fe_pipe_set_track_params: %s\n", d2fe_last_error());
       d2fe_pipe_destroy(p_); p_ = nullptr;
@@ -246,6 +265,23 @@ class StereoPipe {
     int64_t t = -1;
     if (!p_ || left.channels != 1 || right.channels != 1 || left.step != right.step) return -1;
     if (d2fe_pipe_submit(p_, left.data, right.data, (int)left.step, 0, &t) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_submit: %s\n", d2fe_last_error()); return -1; }
+    return t;
+  }
+  // a mono pipe (cam->mono = 1): the one image of the frame
+  int64_t submit(const ImageView& left) {
+    int64_t t = -1;
+    if (!p_ || left.channels != 1) return -1;
+    if (d2fe_pipe_submit(p_, left.data, nullptr, (int)left.step, 0, &t) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_submit: %s\n", d2fe_last_error()); return -1; }
+    return t;
+  }
+  // a depth pipe (cam->mono = cam->depth = 1): the gray image and its 16-bit depth image of the same size
+  int64_t submit(const ImageView& left, const DepthView& depth) {
+    int64_t t = -1;
+    if (!p_ || left.channels != 1 || !depth.data || depth.rows != left.rows || depth.cols != left.cols) return -1;
+    if (d2fe_pipe_submit_depth(p_, left.data, depth.data, (int)left.step, (int)depth.step, 0, 0, &t) != D2FE_OK) {
+      std::fprintf(stderr, "[d2fe] d2fe_pipe_submit_depth: %s\n", d2fe_last_error());
+      return -1;
+    }
     return t;
   }
   bool wait(int64_t ticket, StereoFrameResult& out) {
@@ -281,11 +317,18 @@ class StereoPipe {
       if (d2fe_pipe_track_result_get(p_, ticket, &tr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_track_result_get: %s\n", d2fe_last_error()); return false; }
       StereoTrackList& t = out.tracks;
       const int n = tr.n[0];
-      for (int j = 0; j < n; ++j) { t.pts.emplace_back(tr.pts_xy[2 * j], tr.pts_xy[2 * j + 1]); t.right.emplace_back(tr.right_xy[2 * j], tr.right_xy[2 * j + 1]); }
+      for (int j = 0; j < n; ++j) { t.pts.emplace_back(tr.pts_xy[2 * j], tr.pts_xy[2 * j + 1]); if (tr.right_xy) t.right.emplace_back(tr.right_xy[2 * j], tr.right_xy[2 * j + 1]); }
       t.id.assign(tr.id, tr.id + n); t.src.assign(tr.src, tr.src + n); t.kp.assign(tr.kp, tr.kp + n);
       t.scores.assign(tr.scores, tr.scores + n); t.desc.assign(tr.desc, tr.desc + (size_t)n * tr.desc_dim);
-      t.right_status.assign(tr.right_status, tr.right_status + n);
+      if (tr.right_status) t.right_status.assign(tr.right_status, tr.right_status + n);
       t.n_tracked_in = tr.n_tracked_in[0]; t.n_lost = tr.n_lost[0]; t.n_removed_near = tr.n_removed_near[0]; t.n_new = tr.n_new[0];
+    }
+    out.depth_mm.clear();
+    if (depth_) {
+      d2fe_pipe_depth_result dr;
+      if (d2fe_pipe_depth_result_get(p_, ticket, &dr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_depth_result_get: %s\n", d2fe_last_error()); return false; }
+      out.depth_mm.assign(dr.kp_depth_mm, dr.kp_depth_mm + r.n_kp[0]);
+      if (dr.track_depth_mm) out.tracks.depth_mm.assign(dr.track_depth_mm, dr.track_depth_mm + out.tracks.pts.size());
     }
     return true;
   }
@@ -303,7 +346,7 @@ class StereoPipe {
 
  private:
   d2fe_pipe p_ = nullptr;
-  bool lr_lk_ = false, sp_lk_ = false;
+  bool lr_lk_ = false, sp_lk_ = false, depth_ = false;
 };
 
 // trackEnable(): the LK-carried landmark list of one view of a quad frame (what D2FeatureTracker::trackLK(frame) leaves in keyframe_lk_infos[frame_id][c] with
