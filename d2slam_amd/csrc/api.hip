@@ -1,8 +1,7 @@
-// api.hip -- C ABI (include/d2fe.h) of libd2fe_hip.so: handle lifecycle, SuperPoint's host side (weight
-// packing, the launch sequence of an extract call), the host and device extract entry points, the matcher,
-// the "next rows", the debug hooks and profiling.  Host code only: NetVLAD's host side is netvlad_host.hip,
-// the kernels live in the other translation units (kernels.h lists their launchers).  There is deliberately
-// NO CPU fallback in this library.
+// api.hip -- C ABI (include/d2fe.h) of libd2fe_hip.so: handle lifecycle, the host and device extract entry
+// points, the matcher, the "next rows", the debug hooks and profiling.  Host code only: SuperPoint's host side
+// is superpoint_host.hip, NetVLAD's netvlad_host.hip, the kernels live in the other translation units
+// (kernels.h lists their launchers).  There is deliberately NO CPU fallback in this library.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,7 +20,6 @@
 #include "context.h"
 #ifdef D2FE_DEVTOOLS
 #include "../../include/d2fe_debug.h"
-#include "sp_plan.h"
 #endif
 
 using namespace d2fe;
@@ -62,87 +60,12 @@ int upload(const void* src, size_t bytes, void** dst) {
 // launch-regime record (kernels.h: D2FE_REGIME): process-wide, written by the launchers from any thread (pipe lanes)
 namespace {
 std::atomic<long long> g_regime[D2FE_REGIME_COUNT];
-
-// The one owner of a debug hook's device buffers: hands out a pointer, remembers it and frees everything when the call returns, whichever way
-struct DevPool {
-  std::vector<void*> owned;
-  DevPool() = default; DevPool(const DevPool&) = delete; DevPool& operator=(const DevPool&) = delete;
-  ~DevPool() { for (void* p : owned) (void)hipFree(p); }
-  // bytes of device memory, filled with `fill` bytes (outputs: 0xff, so that an entry a kernel does not write is no plausible value) or with src
-  template <class T>
-  hipError_t get(T** out, size_t bytes, const void* src, int fill = 0xff) {
-    void* p = nullptr;
-    *out = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
-    if (e != hipSuccess) return e;
-    owned.push_back(p);
-    *out = static_cast<T*>(p);
-    if (!bytes) return hipSuccess;
-    return src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipMemset(p, fill, bytes);
-  }
-};
 }  // namespace
 namespace d2fe {
 void regime_note(int regime) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].fetch_add(1, std::memory_order_relaxed); }
 void regime_set(int regime, long long value) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].store(value, std::memory_order_relaxed); }
 }  // namespace d2fe
 #endif
-
-namespace {
-
-int alloc_f(Tensor& t, size_t per_img, int batch) {
-  t.per_img = per_img;
-  HIP_TRY(hipMalloc(&t.p, per_img * batch * sizeof(float)));
-  return D2FE_OK;
-}
-
-// pack one conv (or a channel-concatenation of convs sharing the input) into the kernel's fragment order
-int pack_layer(d2fe_context* h, Layer& L, const std::vector<const d2fe_conv_params*>& parts, int cout_pad, bool force_f32 = false) {
-  const int cin = parts[0]->cin, ks = parts[0]->ksize;
-  int cout = 0;
-  for (auto* p : parts) cout += p->cout;
-  std::vector<float> w((size_t)cout * cin * ks * ks), b(cout_pad, 0.f);
-  size_t wo = 0;
-  int bo = 0;
-  for (auto* p : parts) {
-    const size_t n = (size_t)p->cout * cin * ks * ks;
-    memcpy(w.data() + wo, p->weight, n * sizeof(float));
-    memcpy(b.data() + bo, p->bias, p->cout * sizeof(float));
-    wo += n;
-    bo += p->cout;
-  }
-  L.cout = cout; L.cout_pad = cout_pad; L.cin = cin; L.ks = ks;
-  if (L.wpack) { hipFree(L.wpack); L.wpack = nullptr; }
-  if (L.bias) { hipFree(L.bias); L.bias = nullptr; }
-  int rc;
-  if (h->cfg.precision == D2FE_PREC_F32_WINO && ks == 3 && cin >= 64 && !force_f32) {
-    std::vector<float> pk(packed_weight_floats_wino(cout_pad, cin));
-    pack_weights_wino(w.data(), cout, cin, cout_pad, pk.data());
-    rc = upload(pk.data(), pk.size() * sizeof(float), &L.wpack);
-  } else if ((h->cfg.precision != D2FE_PREC_F16X2 && h->cfg.precision != D2FE_PREC_F16) || force_f32) {
-    std::vector<float> pk(packed_weight_floats_f32(cout_pad, cin, ks));
-    pack_weights_f32(w.data(), cout, cin, ks, cout_pad, pk.data());
-    rc = upload(pk.data(), pk.size() * sizeof(float), &L.wpack);
-  } else if (h->cfg.precision == D2FE_PREC_F16) {
-    std::vector<uint16_t> pk(packed_weight_halfs_f16(cout_pad, cin, ks));
-    pack_weights_f16(w.data(), cout, cin, ks, cout_pad, pk.data());
-    rc = upload(pk.data(), pk.size() * sizeof(uint16_t), &L.wpack);
-  } else {
-    std::vector<uint16_t> pk(packed_weight_halfs_f16x2(cout_pad, cin, ks));
-    pack_weights_f16x2(w.data(), cout, cin, ks, cout_pad, pk.data());
-    rc = upload(pk.data(), pk.size() * sizeof(uint16_t), &L.wpack);
-  }
-  if (rc) return rc;
-  return upload(b.data(), b.size() * sizeof(float), reinterpret_cast<void**>(&L.bias));
-}
-
-int check_layer(const d2fe_conv_params& p, int cout, int cin, int ks, const char* name) {
-  if (!p.weight || !p.bias || p.cout != cout || p.cin != cin || p.ksize != ks)
-    return fail(D2FE_ERR_INVALID, std::string("superpoint layer ") + name + ": unexpected shape");
-  return D2FE_OK;
-}
-
-}  // namespace
 
 namespace d2fe {
 void graphs_clear(d2fe_context* h) {
@@ -164,206 +87,6 @@ void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool
     h->last_w = st.last_w; h->last_h = st.last_h; h->last_n = st.last_n; h->last_set = st.last_set;
     h->last_gray = st.last_gray; h->last_stride = st.last_stride; h->last_istride = st.last_istride;
   }
-}
-
-
-// exact_order (exact_order.hip), between the candidate emission and the selection, on the tail's stream: mark -> slots + crops -> the crop batch through the
-// exact mode's launches (conv1a|conv1b .. conv4b, convPa, convPb, softmax into a dense 88x88 score map per crop) -> patch.  A fixed number of fixed-shape
-// launches: crop slots nobody got run on whatever they held, their scores are never read
-static int run_exact_order(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, int cap, hipStream_t s) {
-  const int C = h->eo_slots, E = 88, E2 = 44, E4 = 22, Ec = 11;
-  const float thr = h->cfg.keypoint_threshold;
-  const int K = h->cfg.max_keypoints < cap ? h->cfg.max_keypoints : cap;
-  HIP_TRY(launch_exact_order_mark(h->cand, h->cand_count, h->cand_cap, n, W, H, K, thr, h->eo_eps, C, h->eo_cell_map, h->eo_cell_list, h->eo_cell_count,
-                                  h->eo_stats, s));
-  HIP_TRY(launch_exact_order_gather(d_gray, stride, (long)image_stride, n, W, H, h->eo_cell_list, h->eo_cell_count, C, h->eo_crops, h->eo_stats, s));
-  // the crop batch's activations, per crop: a1b 44*44*64 | a2a 44*44*64 | a2b 22*22*64 | a3a 22*22*128 | a3b, a4a, a4b 11*11*128 | aP 11*11*256 | logits 121*65 | scores 88*88
-  float* a1b = h->eo_act;
-  float* a2a = a1b + (size_t)C * E2 * E2 * 64;
-  float* a2b = a2a + (size_t)C * E2 * E2 * 64;
-  float* a3a = a2b + (size_t)C * E4 * E4 * 64;
-  float* a3b = a3a + (size_t)C * E4 * E4 * 128;
-  float* a4a = a3b + (size_t)C * Ec * Ec * 128;
-  float* a4b = a4a + (size_t)C * Ec * Ec * 128;
-  float* aP = a4b + (size_t)C * Ec * Ec * 128;
-  float* lg = aP + (size_t)C * Ec * Ec * 256;
-  float* sc = lg + (size_t)C * Ec * Ec * 65;
-  auto conv = [&](ConvShape shape, const Layer& L, const float* in, int ics, long iis, float* out, int ocs, long ois, int hh, int ww, bool pool, bool relu) -> hipError_t {
-    ConvArgs a;
-    a.in = in; a.in_cstride = ics; a.in_coff = 0;
-    a.out = out; a.out_cstride = ocs; a.out_coff = 0;
-    a.cout_real = L.cout; a.wpack = L.wpack; a.bias = L.bias;
-    a.img = h->eo_crops; a.img_stride = E; a.img_istride = (long)E * E; a.w1a = h->w1a; a.b1a = h->b1a;
-    a.H = hh; a.W = ww; a.n_img = C; a.in_img_stride = iis; a.out_img_stride = ois; a.zeros = h->zeros; a.ncu = h->ncu;
-    a.tag = 0; a.ablate = 0; a.work_ctr = nullptr;
-    if (shape == CONV_256_1x1_T4x16) { const hipError_t e = launch_conv1x1_256_65(a, s); if (e != hipErrorNotSupported) return e; }     // convPb: same bits either way
-    return launch_conv(shape, D2FE_PREC_F32, pool, relu, L.cout_pad, a, s);
-  };
-  HIP_TRY(conv(CONV1B_FUSED, h->L[L_X1B], nullptr, 64, 0, a1b, 64, (long)E2 * E2 * 64, E, E, true, true));
-  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X2A], a1b, 64, (long)E2 * E2 * 64, a2a, 64, (long)E2 * E2 * 64, E2, E2, false, true));
-  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X2B], a2a, 64, (long)E2 * E2 * 64, a2b, 64, (long)E4 * E4 * 64, E2, E2, true, true));
-  HIP_TRY(conv(CONV_64_T8x32, h->L[L_X3A], a2b, 64, (long)E4 * E4 * 64, a3a, 128, (long)E4 * E4 * 128, E4, E4, false, true));
-  HIP_TRY(conv(CONV_128_T4x32, h->L[L_X3B], a3a, 128, (long)E4 * E4 * 128, a3b, 128, (long)Ec * Ec * 128, E4, E4, true, true));
-  HIP_TRY(conv(CONV_128_T4x16, h->L[L_X4A], a3b, 128, (long)Ec * Ec * 128, a4a, 128, (long)Ec * Ec * 128, Ec, Ec, false, true));
-  HIP_TRY(conv(CONV_128_T4x16, h->L[L_X4B], a4a, 128, (long)Ec * Ec * 128, a4b, 128, (long)Ec * Ec * 128, Ec, Ec, false, true));
-  HIP_TRY(conv(CONV_128_T4x16, h->L[L_XPA], a4b, 128, (long)Ec * Ec * 128, aP, 256, (long)Ec * Ec * 256, Ec, Ec, false, true));
-  HIP_TRY(conv(CONV_256_1x1_T4x16, h->L[L_PB], aP, 256, (long)Ec * Ec * 256, lg, 65, (long)Ec * Ec * 65, Ec, Ec, false, false));
-  // dense score map only: an infinite threshold emits no candidate and touches no counter
-  HIP_TRY(launch_softmax_cand(lg, 65, Ec, Ec, C, INFINITY, 0, sc, nullptr, h->eo_cell_count, 0, false, s));
-  HIP_TRY(launch_exact_order_patch(h->cand, h->cand_count, h->cand_cap, n, W, H, thr, h->eo_cell_map, h->eo_cell_count, C, sc, s));
-  return D2FE_OK;
-}
-
-// the launch sequence == one TensorRT executeV2 + processOutput of the reference
-int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride,
-                   float* d_kps, float* d_scores, float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s,
-                   hipStream_t s_tail, int bs) {
-  // s: the convolutions ("trunk"); s_tail (default: s): softmax, selection, descriptor head, sampling ("tail"); bs: buffer set
-  Tensor& a4b = bs ? h->a4b2 : h->a4b;
-  Tensor& logits = bs ? h->logits2 : h->logits;
-  Tensor& draw = bs ? h->draw2 : h->draw;
-  h->last_set = bs;
-  const int prec = h->cfg.precision;
-  // One memset per pass: the Winograd work counters and (when the post-processing runs on this same stream) the per-image candidate
-  // counters behind them.  async_tail: the previous call's tail may still be reading ITS counts, so the tail zeroes them itself, in stream order.
-  const bool tail_elsewhere = s_tail && s_tail != s;
-  const bool wctr = prec == D2FE_PREC_F32_WINO && h->wino_dynamic;
-  if (wctr || !tail_elsewhere)
-    // the cleared range is padded to a multiple of 64 ints (256 B; the allocation is): the runtime splits a memset whose size is not a multiple of its fill width
-    // into an aligned fill and a tail fill -- two ~5 us kernels in front of every pass instead of one (kernel trace of a one-frame pass, round 5)
-    HIP_TRY(hipMemsetAsync(wctr ? h->work_ctrs : h->cand_count, 0, ((wctr ? 64 : 0) + (tail_elsewhere ? 0 : (n + 63) / 64 * 64)) * sizeof(int), s));
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8;
-  auto conv = [&](ConvShape shape, const Layer& L, const float* in, int ics, int ico, long iis, float* out, int ocs,
-                  long ois, int hh, int ww, bool pool, bool relu, int oco = 0, bool direct = false) -> hipError_t {
-    ConvArgs a;
-    a.in = in; a.in_cstride = ics; a.in_coff = ico;
-    a.out = out; a.out_cstride = ocs; a.out_coff = oco;
-    a.cout_real = L.cout; a.wpack = L.wpack; a.bias = L.bias;
-    a.img = d_gray; a.img_stride = stride; a.img_istride = (long)image_stride; a.w1a = h->w1a; a.b1a = h->b1a;
-    a.H = hh; a.W = ww; a.n_img = n; a.in_img_stride = iis; a.out_img_stride = ois; a.zeros = h->zeros; a.ncu = h->ncu;
-    a.tag = (&L == &h->L[L_1B]) ? 1 : 0;
-    a.work_ctr = (prec == D2FE_PREC_F32_WINO && h->wino_dynamic) ? h->work_ctrs + (int)(&L - &h->L[0]) : nullptr;
-    { static const int ab = d2fe_dev_env("D2FE_ABLATE", 0); a.ablate = ab; }
-    if (prec != D2FE_PREC_F16X2 && prec != D2FE_PREC_F16 && shape == CONV_256_1x1_T4x16 && L.cout == 65 && !pool && !relu) {      // convPb
-      static const int on = d2fe_dev_env("D2FE_CONV1X1", 1);
-      if (on) { const hipError_t e = launch_conv1x1_256_65(a, s); if (e != hipErrorNotSupported) return e; }
-    }
-    if (prec == D2FE_PREC_F32_WINO)   // 3x3 layers: Winograd kernels; the 1x1 heads (and `direct`: convDa of the dense head): the exact fp32 kernels
-      return shape == CONV1B_FUSED ? launch_conv_wino_fused1b(L.cout_pad, a, s)
-             : (L.ks == 3 && !direct) ? launch_conv_wino(L.cin, pool, relu, L.cout_pad, a, s) : launch_conv(shape, D2FE_PREC_F32, pool, relu, L.cout_pad, a, s);
-    return launch_conv(shape, prec, pool, relu, L.cout_pad, a, s);
-  };
-  if (h->fuse1a) {
-    ProfScope ps(h, D2FE_PROF_CONV1B, s);
-    HIP_TRY(conv(CONV1B_FUSED, h->L[L_1B], nullptr, 64, 0, 0, h->a1b.p, 64, (long)H2 * W2 * 64, H, W, true, true));
-  } else {
-    { ProfScope ps(h, D2FE_PROF_CONV1A, s); HIP_TRY(launch_conv1a(d_gray, stride, (long)image_stride, H, W, n, h->w1a, h->b1a, h->a1a.p, s)); }
-    { ProfScope ps(h, D2FE_PROF_CONV1B, s); HIP_TRY(conv(CONV_64_T8x32, h->L[L_1B], h->a1a.p, 64, 0, (long)H * W * 64, h->a1b.p, 64, (long)H2 * W2 * 64, H, W, true, true)); }
-  }
-  { ProfScope ps(h, D2FE_PROF_CONV2A, s); HIP_TRY(conv(CONV_64_T8x32, h->L[L_2A], h->a1b.p, 64, 0, (long)H2 * W2 * 64, h->a2a.p, 64, (long)H2 * W2 * 64, H2, W2, false, true)); }
-  { ProfScope ps(h, D2FE_PROF_CONV2B, s); HIP_TRY(conv(CONV_64_T8x32, h->L[L_2B], h->a2a.p, 64, 0, (long)H2 * W2 * 64, h->a2b.p, 64, (long)H4 * W4 * 64, H2, W2, true, true)); }
-  { ProfScope ps(h, D2FE_PROF_CONV3A, s); HIP_TRY(conv(CONV_64_T8x32, h->L[L_3A], h->a2b.p, 64, 0, (long)H4 * W4 * 64, h->a3a.p, 128, (long)H4 * W4 * 128, H4, W4, false, true)); }
-  { ProfScope ps(h, D2FE_PROF_CONV3B, s); HIP_TRY(conv(CONV_128_T4x32, h->L[L_3B], h->a3a.p, 128, 0, (long)H4 * W4 * 128, h->a3b.p, 128, (long)Hc * Wc * 128, H4, W4, true, true)); }
-  { ProfScope ps(h, D2FE_PROF_CONV4A, s); HIP_TRY(conv(CONV_128_T4x16, h->L[L_4A], h->a3b.p, 128, 0, (long)Hc * Wc * 128, h->a4a.p, 128, (long)Hc * Wc * 128, Hc, Wc, false, true)); }
-  { ProfScope ps(h, D2FE_PROF_CONV4B, s); HIP_TRY(conv(CONV_128_T4x16, h->L[L_4B], h->a4a.p, 128, 0, (long)Hc * Wc * 128, a4b.p, 128, (long)Hc * Wc * 128, Hc, Wc, false, true)); }
-  // both paths give identical bits; with fewer than 4 images per call the dense head is quicker (the sparse kernels are
-  // latency-bound with so few 32-cell workgroups in flight; measured per step, exact mode: 2 images 1.079 ms dense / 1.096 sparse,
-  // 4 images 1.877 / 1.862, 8 images 3.42 / 3.28, 16 images 6.48 / 6.20)
-  const bool sparse = h->sparse_desc && n >= h->sp_min_batch && 4 * (long)cap <= h->sp_slots;      // a larger capacity than the sparse store was sized for: dense head
-  if (sparse) {
-    // detector head only (convPa 128->256, convPb); the descriptor head is evaluated after keypoint selection, at the needed cells
-    { ProfScope ps(h, D2FE_PROF_CONVPADA, s); HIP_TRY(conv(CONV_128_T4x16, h->L[L_PA], a4b.p, 128, 0, (long)Hc * Wc * 128, h->aPD.p, 256, (long)Hc * Wc * 256, Hc, Wc, false, true)); }
-    { ProfScope ps(h, D2FE_PROF_CONVPB, s); HIP_TRY(conv(CONV_256_1x1_T4x16, h->L[L_PB], h->aPD.p, 256, 0, (long)Hc * Wc * 256, logits.p, 65, (long)Hc * Wc * 65, Hc, Wc, false, false)); }
-  } else {
-    if (prec == D2FE_PREC_F32_WINO && h->sparse_desc) {
-      // Winograd mode, dense head (calls with fewer images than the sparse head pays for): the detector branch convPa as a Winograd layer, the
-      // descriptor branch convDa as DIRECT fp32 chains -- the arithmetic of the sparse head -- so that a frame's descriptors are the same bits
-      // whichever head a call takes (1-image call, 64-image batch, any pass of the frames-in-flight pipe)
-      ProfScope ps(h, D2FE_PROF_CONVPADA, s);
-      HIP_TRY(conv(CONV_128_T4x16, h->L[L_PA], a4b.p, 128, 0, (long)Hc * Wc * 128, h->aPD.p, 512, (long)Hc * Wc * 512, Hc, Wc, false, true));
-      HIP_TRY(conv(CONV_128_T4x16, h->L[L_DA32], a4b.p, 128, 0, (long)Hc * Wc * 128, h->aPD.p, 512, (long)Hc * Wc * 512, Hc, Wc, false, true, 256, true));
-    } else
-    { ProfScope ps(h, D2FE_PROF_CONVPADA, s); HIP_TRY(conv(CONV_128_T4x16, h->L[L_PADA], a4b.p, 128, 0, (long)Hc * Wc * 128, h->aPD.p, 512, (long)Hc * Wc * 512, Hc, Wc, false, true)); }
-    { ProfScope ps(h, D2FE_PROF_CONVPB, s); HIP_TRY(conv(CONV_256_1x1_T4x16, h->L[L_PB], h->aPD.p, 512, 0, (long)Hc * Wc * 512, logits.p, 65, (long)Hc * Wc * 65, Hc, Wc, false, false)); }
-    { ProfScope ps(h, D2FE_PROF_CONVDB, s); HIP_TRY(conv(CONV_256_1x1_T4x16, h->L[L_DB], h->aPD.p, 512, 256, (long)Hc * Wc * 512, draw.p, 256, (long)Hc * Wc * 256, Hc, Wc, false, false)); }
-  }
-  const bool varA = h->cfg.postproc == D2FE_POSTPROC_A;
-  if (s_tail && s_tail != s) {       // trunk done -> tail may start; from here on everything is issued on the tail stream
-    HIP_TRY(hipEventRecord(h->ev_trunk[bs], s));
-    HIP_TRY(hipStreamWaitEvent(s_tail, h->ev_trunk[bs], 0));
-    s = s_tail;
-  }
-  const bool eo = h->eo_slots > 0 && !varA;      // exact_order: candidates down to thr - eps, the uncertain cells re-evaluated with the direct chains
-  { ProfScope ps(h, D2FE_PROF_SOFTMAX, s);
-  HIP_TRY(launch_softmax_cand(logits.p, 65, Hc, Wc, n, eo ? h->cfg.keypoint_threshold - h->eo_eps : h->cfg.keypoint_threshold, h->cfg.remove_borders,
-                              (h->cfg.keep_score_map || varA || h->cfg.max_keypoints < 0) ? h->semi.p : nullptr,
-                              h->cand, h->cand_count, varA ? 0 : h->cand_cap, /*zero_counts=*/tail_elsewhere, s)); }
-  if (varA) {
-    // getKeyPoints + NMS2 (superpoint_common.cpp:12-40,107-177): border = 0, sorted by confidence, max_num
-    ProfScope ps(h, D2FE_PROF_SELECT, s);
-    HIP_TRY(launch_nms2_a(h->semi.p, H, W, n, h->cfg.keypoint_threshold, h->cfg.nms_dist, h->aconf, h->clist, h->cand,
-                          h->cand_count, h->cand_cap, h->a_ncand, s));
-    // variant A's sampling scratch holds a_scap keypoints per image: keep-all (max_keypoints = -1) means "up to a_scap" here
-    HIP_TRY(launch_select_b(h->cand, h->cand_count, h->cand_cap, n, W, h->cfg.max_keypoints < 0 ? h->a_scap : h->cfg.max_keypoints, cap, 1, nullptr, H,
-                            h->cfg.keypoint_threshold, 0, d_kps, d_scores, d_idx, d_n, s));
-    if ((long)H * W > 65536)     // the reference's CV_16UC1 index map wraps above 65 536 candidates; reproduced (no-op below that)
-      HIP_TRY(launch_nms2_wrap_fix(h->clist, h->a_ncand, H, W, n, d_kps, d_idx, d_n, cap, s));
-  } else {
-    ProfScope ps(h, D2FE_PROF_SELECT, s);
-    if (eo) { const int rc = run_exact_order(h, d_gray, n, W, H, stride, image_stride, cap, s); if (rc) return rc; }
-    // raster indices and keypoints are in score-map coordinates: (W/8)*8 wide.  Keep-all handles also hand over the dense score map:
-    // more keypoints than the in-LDS sort takes are compacted from it in raster order (any count up to the call's capacity)
-    HIP_TRY(launch_select_b(h->cand, h->cand_count, h->cand_cap, n, Wc * 8, h->cfg.max_keypoints, cap, 0,
-                            (h->cfg.keep_score_map || h->cfg.max_keypoints < 0) ? h->semi.p : nullptr, Hc * 8, h->cfg.keypoint_threshold,
-                            h->cfg.remove_borders, d_kps, d_scores, d_idx, d_n, s));
-  }
-  if (!sparse) {
-    ProfScope ps(h, D2FE_PROF_SAMPLE, s);
-    if (varA)
-      HIP_TRY(launch_sample_a(draw.p, 256, 0, Hc, Wc, W, H, n, d_kps, d_n, cap, h->pca_dims ? h->pca_comp_t : nullptr,
-                              h->pca_mean, h->pca_dims, h->a_samp, h->a_scap, h->a_cn, nullptr, 0, d_desc, s));
-    else
-      HIP_TRY(launch_sample_b(draw.p, 256, 0, Hc, Wc, n, d_kps, d_n, cap, nullptr, 0, h->pca_dims ? h->pca_comp_t : nullptr, h->pca_mean, h->pca_dims,
-                              d_desc, s));
-  } else {
-    { ProfScope ps(h, D2FE_PROF_CONVDB, s);
-      HIP_TRY(launch_desc_head_sparse(d_kps, d_n, cap, Hc, Wc, n, a4b.p, 128, (long)Hc * Wc * 128, h->L[L_DA32].wpack, h->L[L_DA32].bias,
-                                      h->L[L_DB32].wpack, h->L[L_DB32].bias, h->sp_flags, h->sp_slotmap, h->sp_cells, h->sp_count,
-                                      h->sp_slots, h->sp_desc, h->sp_mid, h->sp_mid_imgs, varA ? W : 0, varA ? H : 0, s)); }
-    ProfScope ps(h, D2FE_PROF_SAMPLE, s);
-    if (varA)
-      HIP_TRY(launch_sample_a(h->sp_desc, 256, 0, Hc, Wc, W, H, n, d_kps, d_n, cap, h->pca_dims ? h->pca_comp_t : nullptr,
-                              h->pca_mean, h->pca_dims, h->a_samp, h->a_scap, h->a_cn, h->sp_slotmap, h->sp_slots, d_desc, s));
-    else
-      HIP_TRY(launch_sample_b(h->sp_desc, 256, 0, Hc, Wc, n, d_kps, d_n, cap, h->sp_slotmap, h->sp_slots, h->pca_dims ? h->pca_comp_t : nullptr,
-                              h->pca_mean, h->pca_dims, d_desc, s));
-  }
-  h->last_w = W; h->last_h = H; h->last_n = n;
-  h->last_gray = d_gray; h->last_stride = stride; h->last_istride = image_stride;
-  return D2FE_OK;
-}
-
-// floats per descriptor row of every extract call, pipe and list of the handle: pca_dims can only be non-zero where the PCA is applied (variant A, or variant B
-// with d2fe_config.variant_b_pca: d2fe_set_superpoint_pca refuses every other handle)
-int desc_dim_of(const d2fe_context* h) { return h->pca_dims ? h->pca_dims : 256; }
-
-int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap) {
-  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  if (!h->sp_loaded) return fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
-  if (n < 1 || n > h->cfg.max_batch) return fail(D2FE_ERR_INVALID, "batch size out of range");
-  if (W < 16 || H < 16 || W > h->cfg.max_width || H > h->cfg.max_height || (long)W * H > (long)h->cfg.max_width * h->cfg.max_height)
-    return fail(D2FE_ERR_INVALID, "image size must be at least 16x16 and within the configured maximum");
-  // Sizes that are not multiples of 8 (the reference's TensorRT profile admits 100x100 .. 1500x1500, superpoint_tensorrt.cpp:50-55): the
-  // three 2x2 max-pools floor, the score map is (H/8)*8 x (W/8)*8 and keypoints live in ITS coordinates, as processOutput reads
-  // semi_dims_ (:331-336).  Variant A sizes its cv::Mat views from the configured width/height (superpoint_onnx.cpp:86-94), which only
-  // describes the network output for multiples of 8.
-  if (((W | H) & 7) && h->cfg.postproc == D2FE_POSTPROC_A)
-    return fail(D2FE_ERR_INVALID, "post-processing variant A needs image sizes that are multiples of 8");
-  if (h->eo_slots > 0 && (W < 88 || H < 88 || ((W | H) & 7)))
-    return fail(D2FE_ERR_INVALID, "exact_order needs images of at least 88x88 whose width and height are multiples of 8 (the 88x88 crops share the full image's pool grids)");
-  if (stride < W) return fail(D2FE_ERR_INVALID, "stride < width");
-  if (cap < 1) return fail(D2FE_ERR_INVALID, "cap < 1");
-  return D2FE_OK;
 }
 
 }  // namespace d2fe
@@ -434,90 +157,25 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
   d2fe_context* h = new d2fe_context();
   h->cfg = *cfg;
   const int rc_alloc = [&]() -> int {
-  // conv1a is evaluated inside conv1b's staging in every mode (the Winograd kernel runs it on the matrix pipe): the 78.6 MB/image
-  // activation never exists.  D2FE_FUSE1A=0 falls back to a stand-alone conv1a kernel (bit-identical; kept for A/B measurements).
-  h->fuse1a = d2fe_dev_env("D2FE_FUSE1A", 1) != 0;
     // (a lane that is handed its stream does not create one first: no stream is created that is not needed, see place_streams in pipe.hip)
     if (adopt) h->stream = adopt; else HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const size_t H = cfg->max_height, W = cfg->max_width;
     const int B = cfg->max_batch;
-    int rc = 0;
-    if (!h->fuse1a) rc |= alloc_f(h->a1a, H * W * 64, B);   // the fused path never materialises conv1a (78.6 MB per image); debug reads allocate it on demand
-    rc |= alloc_f(h->a1b, H * W * 16, B);
-    rc |= alloc_f(h->a2a, H * W * 16, B);
-    rc |= alloc_f(h->a2b, H * W * 4, B);
-    rc |= alloc_f(h->a3a, H * W * 8, B);
-    rc |= alloc_f(h->a3b, H * W * 2, B);
-    rc |= alloc_f(h->a4a, H * W * 2, B);
-    rc |= alloc_f(h->a4b, H * W * 2, B);
-    rc |= alloc_f(h->aPD, H * W * 8, B);
-    rc |= alloc_f(h->logits, (H / 8) * (W / 8) * 65, B);
-    rc |= alloc_f(h->draw, H * W * 4, B);
-    rc |= alloc_f(h->semi, H * W, B);
-    if (rc) return D2FE_ERR_HIP;
-    h->cand_cap = (long)(H * W);
-    HIP_TRY(hipMalloc(&h->cand, sizeof(unsigned long long) * h->cand_cap * B));
-    // the per-image candidate counters sit directly behind the 64 Winograd work counters: ONE memset clears both at the start of a pass
-    HIP_TRY(hipMalloc(&h->work_ctrs, (64 + ((size_t)B + 63) / 64 * 64) * sizeof(int)));      // counts padded to 64 ints: see the memset of a pass (run_superpoint)
-    HIP_TRY(hipMemset(h->work_ctrs, 0, (64 + ((size_t)B + 63) / 64 * 64) * sizeof(int)));
-    h->cand_count = h->work_ctrs + 64;
+    { const int rc = h->sp_run.alloc(*cfg); if (rc) return rc; }
+    if (!lane) {      // a lane shares its parent's network (clone_lane)
+      h->sp_net = std::make_shared<SpNet>();
+      if (cfg->exact_order) HIP_TRY(h->sp_net->pool.get(&h->sp_net->eo_stats, 4 * sizeof(unsigned long long), nullptr, 0));
+    }
     if (cfg->async_tail) {
       HIP_TRY(hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking));
       for (int i = 0; i < 2; ++i) {
         HIP_TRY(hipEventCreateWithFlags(&h->ev_trunk[i], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_tail[i], hipEventDisableTiming));
       }
-      if (alloc_f(h->a4b2, H * W * 2, B) || alloc_f(h->logits2, (H / 8) * (W / 8) * 65, B) || alloc_f(h->draw2, H * W * 4, B)) return D2FE_ERR_HIP;
     }
-    h->sparse_desc = !cfg->dense_descriptors;
-    // Winograd mode: both heads evaluate the descriptor branch as direct fp32 chains (run_superpoint), so the choice is free of consequences for the
-    // bits; measured per call (host to host, 640x480): 1 image 0.44 ms dense / 0.47 sparse, 2 images 0.69 dense / 0.67 sparse
-    if (cfg->precision == D2FE_PREC_F32_WINO) h->sp_min_batch = 2;
-    // fp16-operand mode: the dense head would evaluate convDa | convDb with fp16 operands, the sparse head evaluates them as exact fp32 chains -- a frame's
-    // descriptors must not depend on how many images travel with it, so every call takes the sparse head (1 image: 0.03 ms more per call, the figures above)
-    if (cfg->precision == D2FE_PREC_F16) h->sp_min_batch = 1;
-    h->sp_min_batch = d2fe_dev_env("D2FE_SPARSE_MIN_BATCH", h->sp_min_batch);
-    if (h->sparse_desc) {
-      const size_t ncell = (H / 8) * (W / 8);
-      h->sp_slots = 4 * (cfg->max_keypoints < 0 || cfg->max_keypoints > 1024 ? 1024 : cfg->max_keypoints);   // <= 4 corner cells per keypoint; larger calls take the dense head
-      HIP_TRY(hipMalloc(&h->sp_flags, ncell * B));
-      HIP_TRY(hipMalloc(&h->sp_slotmap, sizeof(int32_t) * ncell * B));
-      HIP_TRY(hipMalloc(&h->sp_cells, sizeof(int32_t) * (size_t)h->sp_slots * B));
-      HIP_TRY(hipMalloc(&h->sp_count, sizeof(int32_t) * B));
-      HIP_TRY(hipMalloc(&h->sp_desc, sizeof(float) * 256 * (size_t)h->sp_slots * B));
-      h->sp_mid_imgs = B < 4 ? B : 4;
-      HIP_TRY(hipMalloc(&h->sp_mid, sizeof(float) * 256 * (size_t)h->sp_slots * h->sp_mid_imgs));
-    }
-    HIP_TRY(hipMalloc(&h->zeros, 1024));
-    HIP_TRY(hipMemset(h->zeros, 0, 1024));
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, cfg->device_id) == hipSuccess && v > 0) h->ncu = h->ncu_dev = v; }
     HIP_TRY(hipMalloc(&h->match_stats, 4 * sizeof(int32_t)));
     HIP_TRY(hipMemset(h->match_stats, 0, 4 * sizeof(int32_t)));
-    h->wino_dynamic = d2fe_dev_env("D2FE_WINO_DYNAMIC", 1) != 0;
-    if (cfg->postproc == D2FE_POSTPROC_A) {
-      HIP_TRY(hipMalloc(&h->aconf, sizeof(float) * H * W * B));
-      HIP_TRY(hipMalloc(&h->clist, sizeof(int) * H * W * B));
-      HIP_TRY(hipMalloc(&h->a_ncand, sizeof(int) * B));
-      h->a_scap = h->cfg.max_keypoints > 0 ? h->cfg.max_keypoints : 1024;   // variant A: select keeps at most min(max_keypoints, call capacity); keep-all: 1024
-      HIP_TRY(hipMalloc(&h->a_samp, sizeof(float) * 256 * (size_t)h->a_scap * B));
-      HIP_TRY(hipMalloc(&h->a_cn, sizeof(float) * 256 * B));
-    }
-    if (cfg->exact_order) {
-      // measured: max |Winograd score - direct score| over the pixels with a direct score > thr / 2; the default is 4x that, one digit
-      h->eo_eps = cfg->exact_order_eps > 0.f ? cfg->exact_order_eps : 9e-6f;
-      // default crop slots: the smallest count in steps of max_batch / 2 at which the 1056-image study (32 images per call, N = 200) drops no cell is 66.5 per image
-      // (2121 cells in its fullest call); at least 136 (134 cells in its fullest image) so that a one-image call drops none either
-      const int C = cfg->exact_order_crops > 0 ? cfg->exact_order_crops : std::max((133 * B + 1) / 2, 136);
-      const size_t ncell = (H / 8) * (W / 8);
-      HIP_TRY(hipMalloc(&h->eo_crops, (size_t)C * 88 * 88));
-      HIP_TRY(hipMemset(h->eo_crops, 0, (size_t)C * 88 * 88));
-      HIP_TRY(hipMalloc(&h->eo_cell_map, sizeof(int) * ncell * B));
-      HIP_TRY(hipMalloc(&h->eo_cell_list, sizeof(int) * (size_t)C * B));
-      HIP_TRY(hipMalloc(&h->eo_cell_count, sizeof(int) * B));
-      HIP_TRY(hipMalloc(&h->eo_act, sizeof(float) * (size_t)C * (2 * 44 * 44 * 64 + 22 * 22 * 64 + 22 * 22 * 128 + 3 * 121 * 128 + 121 * 256 + 121 * 65 + 88 * 88)));
-      if (!lane) { HIP_TRY(hipMalloc(&h->eo_stats, 4 * sizeof(unsigned long long))); HIP_TRY(hipMemset(h->eo_stats, 0, 4 * sizeof(unsigned long long))); }
-      h->eo_slots = C;
-    }
     h->use_graphs = d2fe_dev_env("D2FE_GRAPH", 1) != 0;
     if (lane) { h->use_pinned = false; return D2FE_OK; }
     h->s_cap = h->cfg.max_keypoints > 1024 ? h->cfg.max_keypoints : 1024;      // initial staging capacity per image; grows with the calls (ensure_staging)
@@ -559,17 +217,10 @@ void d2fe_destroy(d2fe_handle h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->tail_stream) { hipStreamSynchronize(h->tail_stream); (void)hipStreamDestroy(h->tail_stream); }
   for (int i = 0; i < 2; ++i) { if (h->ev_trunk[i]) (void)hipEventDestroy(h->ev_trunk[i]); if (h->ev_tail[i]) (void)hipEventDestroy(h->ev_tail[i]); }
-  for (Tensor* t : {&h->a1a, &h->a1b, &h->a2a, &h->a2b, &h->a3a, &h->a3b, &h->a4a, &h->a4b, &h->aPD, &h->logits, &h->draw, &h->semi, &h->a4b2, &h->logits2, &h->draw2})
-    if (t->p) hipFree(t->p);
-  if (!h->borrowed) {
-    for (auto& L : h->L) { if (L.wpack) hipFree(L.wpack); if (L.bias) hipFree(L.bias); }
-    for (void* p : {(void*)h->w1a, (void*)h->b1a, (void*)h->pca_comp_t, (void*)h->pca_mean}) if (p) hipFree(p);
-  }
-  for (void* p : {(void*)h->cand, (void*)h->s_img, (void*)h->aconf, (void*)h->clist, (void*)h->a_ncand, (void*)h->a_samp, (void*)h->a_cn, h->lk_scratch, (void*)h->zeros, (void*)h->work_ctrs, (void*)h->match_stats, (void*)h->match_stamps, (void*)h->sp_flags, (void*)h->sp_slotmap, (void*)h->sp_cells, (void*)h->sp_count, (void*)h->sp_desc, (void*)h->sp_mid})
+  h->sp_run.release();
+  h->sp_net.reset();
+  for (void* p : {(void*)h->s_img, h->lk_scratch, (void*)h->match_stats, (void*)h->match_stamps, (void*)h->nv_s_img, (void*)h->nv_s_out})
     if (p) hipFree(p);
-  for (void* p : {(void*)h->nv_s_img, (void*)h->nv_s_out, (void*)h->eo_crops, (void*)h->eo_cell_map, (void*)h->eo_cell_list, (void*)h->eo_cell_count, (void*)h->eo_act})
-    if (p) hipFree(p);
-  if (h->eo_stats && !h->borrowed) hipFree(h->eo_stats);
   for (auto& kv : h->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
   if (h->nv_stream) { hipStreamSynchronize(h->nv_stream); (void)hipStreamDestroy(h->nv_stream); }
   if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -582,91 +233,6 @@ void d2fe_destroy(d2fe_handle h) {
   for (auto e : h->prof_pool) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
-}
-
-int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
-  if (h) graphs_clear(h);
-  if (!h || !w) return fail(D2FE_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  static const struct { const char* name; int cout, cin, ks; } spec[D2FE_SP_NUM_LAYERS] = {
-      {"conv1a", 64, 1, 3},    {"conv1b", 64, 64, 3},   {"conv2a", 64, 64, 3},   {"conv2b", 64, 64, 3},
-      {"conv3a", 128, 64, 3},  {"conv3b", 128, 128, 3}, {"conv4a", 128, 128, 3}, {"conv4b", 128, 128, 3},
-      {"convPa", 256, 128, 3}, {"convPb", 65, 256, 1},  {"convDa", 256, 128, 3}, {"convDb", 256, 256, 1}};
-  for (int i = 0; i < D2FE_SP_NUM_LAYERS; ++i) {
-    int rc = check_layer(w->layer[i], spec[i].cout, spec[i].cin, spec[i].ks, spec[i].name);
-    if (rc) return rc;
-  }
-  h->sp_loaded = false;
-  // conv1a: [64][1][3][3] -> [9][64]
-  {
-    std::vector<float> t(9 * 64);
-    for (int co = 0; co < 64; ++co)
-      for (int k = 0; k < 9; ++k) t[k * 64 + co] = w->layer[0].weight[co * 9 + k];
-    if (h->w1a) { hipFree(h->w1a); h->w1a = nullptr; }
-    if (h->b1a) { hipFree(h->b1a); h->b1a = nullptr; }
-    int rc = upload(t.data(), t.size() * sizeof(float), reinterpret_cast<void**>(&h->w1a));
-    if (rc) return rc;
-    rc = upload(w->layer[0].bias, 64 * sizeof(float), reinterpret_cast<void**>(&h->b1a));
-    if (rc) return rc;
-  }
-  const d2fe_conv_params* l = w->layer;
-  int rc = 0;
-  rc = rc ? rc : pack_layer(h, h->L[L_1B], {&l[1]}, 64);
-  rc = rc ? rc : pack_layer(h, h->L[L_2A], {&l[2]}, 64);
-  rc = rc ? rc : pack_layer(h, h->L[L_2B], {&l[3]}, 64);
-  rc = rc ? rc : pack_layer(h, h->L[L_3A], {&l[4]}, 128);
-  rc = rc ? rc : pack_layer(h, h->L[L_3B], {&l[5]}, 128);
-  rc = rc ? rc : pack_layer(h, h->L[L_4A], {&l[6]}, 128);
-  rc = rc ? rc : pack_layer(h, h->L[L_4B], {&l[7]}, 128);
-  rc = rc ? rc : pack_layer(h, h->L[L_PADA], {&l[8], &l[10]}, 512);  // convPa | convDa share their input
-  rc = rc ? rc : pack_layer(h, h->L[L_PB], {&l[9]}, 128);
-  rc = rc ? rc : pack_layer(h, h->L[L_DB], {&l[11]}, 256);
-  if (h->sparse_desc) {   // detector head alone in the mode's precision; descriptor head always as exact fp32 fragments
-    rc = rc ? rc : pack_layer(h, h->L[L_PA], {&l[8]}, 256);
-    rc = rc ? rc : pack_layer(h, h->L[L_DA32], {&l[10]}, 256, true);
-    rc = rc ? rc : pack_layer(h, h->L[L_DB32], {&l[11]}, 256, true);
-  }
-  if (h->eo_slots > 0) {     // exact_order: the detector path once more as direct fp32 fragments (convPb is direct in every fp32 mode)
-    static const int xl[8] = {L_X1B, L_X2A, L_X2B, L_X3A, L_X3B, L_X4A, L_X4B, L_XPA};
-    static const int xpad[8] = {64, 64, 64, 128, 128, 128, 128, 256};
-    for (int i = 0; i < 8; ++i) rc = rc ? rc : pack_layer(h, h->L[xl[i]], {&l[1 + i]}, xpad[i], true);
-  }
-  if (rc) return rc;
-  h->sp_loaded = true;
-  return D2FE_OK;
-}
-
-int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean, int pca_dims) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
-  if (h) graphs_clear(h);
-  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  if (pca_dims < 0 || pca_dims > 256 || (pca_dims > 0 && (!comp || !mean))) return fail(D2FE_ERR_INVALID, "bad PCA arguments");
-  if (pca_dims > 0 && h->cfg.postproc != D2FE_POSTPROC_A && !h->cfg.variant_b_pca)
-    return fail(D2FE_ERR_UNSUPPORTED, "PCA is only applied by post-processing variant A (the reference's variant B never applies it)");
-  // variant B's rows feed the matcher, the pipes and the exchange blocks directly: their length keeps the matcher's 16-byte row alignment
-  if (pca_dims > 0 && h->cfg.postproc == D2FE_POSTPROC_B && (pca_dims < 4 || (pca_dims & 3)))
-    return fail(D2FE_ERR_INVALID, "variant B takes pca_dims in 4..256 that are multiples of 4 (the matcher's row alignment), or 0 to switch the PCA off");
-  HIP_TRY(hipSetDevice(h->cfg.device_id));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->pca_comp_t) { hipFree(h->pca_comp_t); h->pca_comp_t = nullptr; }
-  if (h->pca_mean) { hipFree(h->pca_mean); h->pca_mean = nullptr; }
-  h->pca_dims = 0;
-  if (pca_dims == 0) return D2FE_OK;
-  std::vector<float> t((size_t)256 * pca_dims);
-  for (int j = 0; j < pca_dims; ++j)
-    for (int c = 0; c < 256; ++c) t[(size_t)c * pca_dims + j] = comp[(size_t)j * 256 + c];
-  int rc = upload(t.data(), t.size() * sizeof(float), reinterpret_cast<void**>(&h->pca_comp_t));
-  if (rc) return rc;
-  rc = upload(mean, 256 * sizeof(float), reinterpret_cast<void**>(&h->pca_mean));
-  if (rc) return rc;
-  h->pca_dims = pca_dims;
-  return D2FE_OK;
-}
-
-int d2fe_desc_dim(d2fe_handle h) {
-  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  return desc_dim_of(h);
 }
 
 int d2fe_superpoint_extract_device(d2fe_handle h, const uint8_t* d_gray, int n, int width, int height, int stride,
@@ -802,7 +368,7 @@ static int extract_host(d2fe_handle h, const uint8_t* gray, int n, int width, in
   });
   if (rc) return rc;
   std::vector<int32_t> ncand(h->cfg.max_keypoints < 0 ? n : 0);
-  if (!ncand.empty()) HIP_TRY(hipMemcpyAsync(ncand.data(), h->cand_count, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  if (!ncand.empty()) HIP_TRY(hipMemcpyAsync(ncand.data(), h->sp_run.cand_count, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
   if (h->use_pinned && h->pin_out && out_bytes <= h->pin_out_bytes) {
     // ONE D2H of the whole block into pinned memory, one synchronisation, then the rows that exist go to the caller's arrays
     HIP_TRY(hipMemcpyAsync(h->pin_out, h->s_out, out_bytes, hipMemcpyDeviceToHost, s));
@@ -876,14 +442,9 @@ int clone_lane(d2fe_context* p, int max_batch, d2fe_context** out, hipStream_t s
   d2fe_handle c = nullptr;
   int rc = create_context(&cfg, &c, true, stream);       // on failure the stream stays the caller's (create_context un-adopts it below)
   if (rc) return rc;
-  c->borrowed = true;
   if (ncu > 0) c->ncu = ncu;
-  c->w1a = p->w1a; c->b1a = p->b1a;
-  for (int i = 0; i < L_COUNT; ++i) c->L[i] = p->L[i];
-  c->sp_loaded = p->sp_loaded;
-  c->pca_comp_t = p->pca_comp_t; c->pca_mean = p->pca_mean; c->pca_dims = p->pca_dims;
-  c->fuse1a = p->fuse1a; c->wino_dynamic = p->wino_dynamic; c->sp_min_batch = p->sp_min_batch;
-  c->eo_stats = p->eo_stats;      // one set of exact_order counters per parent handle
+  c->sp_net = p->sp_net;      // the network is shared, exact_order's counters with it: one set per parent handle
+  c->sp_run.fuse1a = p->sp_run.fuse1a; c->sp_run.wino_dynamic = p->sp_run.wino_dynamic; c->sp_run.sp_min_batch = p->sp_run.sp_min_batch;
   if (p->nv_net && with_netvlad) {
     // the network is shared; the activations are the lane's own (no nv_s_img / nv_s_out: the host-pointer NetVLAD calls never run on a lane)
     c->nv_net = p->nv_net;
@@ -1446,42 +1007,6 @@ void d2fe_debug_regime_reset(void) {
   for (auto& c : g_regime) c.store(0, std::memory_order_relaxed);
 }
 
-long d2fe_debug_read(d2fe_handle h, const char* name, void* dst, size_t max_bytes) {
-  if (!h || !name || !dst) return fail(D2FE_ERR_INVALID, "null argument");
-  if (h->last_n == 0) return fail(D2FE_ERR_NOT_READY, "no extract call yet");
-  hipSetDevice(h->cfg.device_id);
-  const int H = h->last_h, W = h->last_w, n = h->last_n;
-  if (!strcmp(name, "conv1a") && h->fuse1a) {
-    // fused mode never materialises conv1a: evaluate it on demand from the last input frame(s)
-    if (!h->a1a.p && alloc_f(h->a1a, (size_t)h->cfg.max_height * h->cfg.max_width * 64, h->cfg.max_batch) != 0)
-      return fail(D2FE_ERR_HIP, "hipMalloc conv1a debug buffer");
-    if (launch_conv1a(h->last_gray, h->last_stride, (long)h->last_istride, H, W, n, h->w1a, h->b1a, h->a1a.p, h->stream) != hipSuccess)
-      return fail(D2FE_ERR_HIP, "conv1a debug launch");
-  }
-  if (!strcmp(name, "semi") && !h->cfg.keep_score_map) return fail(D2FE_ERR_NOT_READY, "score map not kept (set keep_score_map)");
-  if (h->sparse_desc && h->last_n >= h->sp_min_batch && (!strcmp(name, "desc_raw") || !strcmp(name, "convPaDa")))
-    return fail(D2FE_ERR_NOT_READY, "the dense descriptor map does not exist with the sparse descriptor head (set dense_descriptors)");
-  if (!strcmp(name, "convPa") && !(h->sparse_desc && h->last_n >= h->sp_min_batch))
-    return fail(D2FE_ERR_NOT_READY, "convPa alone exists only behind the sparse descriptor head (the dense head writes convPaDa)");
-  // a layer's output under its own name, sized by the plan (sp_plan.h: the pools floor, sizes need not be multiples of 8); convPa: the detector branch alone, what the
-  // sparse descriptor head leaves in the convPa | convDa buffer; the heads' outputs under their names
-  const Tensor* const act[SP_PA + 1] = {&h->a1a, &h->a1b, &h->a2a, &h->a2b, &h->a3a, &h->a3b, &h->a4a, h->last_set ? &h->a4b2 : &h->a4b, &h->aPD};
-  const float* src = nullptr;
-  size_t per = 0;
-  for (int i = SP_1A; i <= SP_PA; ++i)
-    if (!strcmp(name, SP_PLAN[i].name)) { src = act[i]->p; per = sp_out_floats(i, H, W); }
-  const struct { const char* nm; const Tensor* t; int ch; } heads[] = {
-      {"convPaDa", &h->aPD, SP_PADA_COUT}, {"logits", h->last_set ? &h->logits2 : &h->logits, 65}, {"desc_raw", h->last_set ? &h->draw2 : &h->draw, 256}, {"semi", &h->semi, 64}};
-  for (auto& e : heads)
-    if (!strcmp(name, e.nm)) { src = e.t->p; per = sp_floats(SP_CELL_LEVEL, e.ch, H, W); }
-  if (!src) return fail(D2FE_ERR_INVALID, "unknown tensor name");
-  const size_t bytes = per * n * sizeof(float);
-  if (bytes > max_bytes) return fail(D2FE_ERR_TRUNCATED, "destination too small");
-  if (hipStreamSynchronize(h->stream) != hipSuccess || (h->tail_stream && hipStreamSynchronize(h->tail_stream) != hipSuccess)) return fail(D2FE_ERR_HIP, "sync");
-  if (hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
-  return (long)bytes;
-}
-
 // Host-side half of the Winograd mode, callable without a GPU: U = G g G^T in the kernels' fragment order (see pack_weights_wino).
 long d2fe_debug_pack_wino(const float* weight, int cout, int cin, float* out, long max_floats) {
   if (!weight || !out || cout < 1 || cin < 8 || (cin & 7)) return fail(D2FE_ERR_INVALID, "bad argument");
@@ -1551,7 +1076,7 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
   pack_weights_wino(weight, cout, cin, cout_pad, pk.data());
   memcpy(bp.data(), bias, sizeof(float) * cout);
   // as a pass of run_superpoint: the work counter is zero when the launch starts (the last of the handle's 64, which no layer of the network uses)
-  int* const wctr = h->wino_dynamic ? h->work_ctrs + 63 : nullptr;
+  int* const wctr = h->sp_run.wino_dynamic ? h->sp_run.work_ctrs + 63 : nullptr;
   auto launch = [&](const ConvArgs& ca) {
     if (wctr) { const hipError_t e = hipMemsetAsync(wctr, 0, sizeof(int), h->stream); if (e != hipSuccess) return e; }
     return launch_conv_wino(cin, pool != 0, relu != 0, cout_pad, ca, h->stream);
@@ -1568,7 +1093,7 @@ int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W,
     ConvArgs a{};
     a.in = d_in; a.in_cstride = cin; a.in_coff = 0; a.out = d_out; a.out_cstride = cout; a.out_coff = 0;
     a.cout_real = cout; a.wpack = d_w; a.bias = d_b; a.H = H; a.W = W; a.n_img = n;
-    a.in_img_stride = (long)H * W * cin; a.out_img_stride = (long)Ho * Wo * cout; a.zeros = h->zeros; a.ncu = h->ncu;
+    a.in_img_stride = (long)H * W * cin; a.out_img_stride = (long)Ho * Wo * cout; a.zeros = h->sp_run.zeros; a.ncu = h->ncu;
     a.ablate = d2fe_dev_env("D2FE_ABLATE", 0);
     a.work_ctr = wctr;
     HIP_TRY(launch(a));
@@ -1799,11 +1324,11 @@ long d2fe_match_fallback_rows(d2fe_handle h, int reset, long* full_scans) {
 int d2fe_exact_order_stats(d2fe_handle h, int64_t out[4]) {
   if (!h || !out) return fail(D2FE_ERR_INVALID, "null argument");
   out[0] = out[1] = out[2] = out[3] = 0;
-  if (!h->eo_stats) return D2FE_OK;
+  if (!h->sp_net->eo_stats) return D2FE_OK;
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   HIP_TRY(hipDeviceSynchronize());      // the handle's streams and those of every lane that counts into the same buffer
   unsigned long long v[4];
-  HIP_TRY(hipMemcpy(v, h->eo_stats, sizeof(v), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v, h->sp_net->eo_stats, sizeof(v), hipMemcpyDeviceToHost));
   for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
   return D2FE_OK;
 }

@@ -1,5 +1,5 @@
 // context.h -- the device context behind d2fe_handle and the launch sequences shared by the translation units that implement
-// include/d2fe.h (api.hip: handle lifecycle, SuperPoint's host side and the entry points; netvlad_host.hip: NetVLAD's host side; lk.hip, lk_carry.hip: the trackers;
+// include/d2fe.h (api.hip: handle lifecycle and the entry points; superpoint_host.hip: SuperPoint's host side; netvlad_host.hip: NetVLAD's host side; lk.hip, lk_carry.hip: the trackers;
 // pipe.hip, quad_pipe.hip: the frames-in-flight pipelines; exchange.hip, quad_exchange.hip, loop.hip, window.hip: the consumers behind them).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 
 #include "../../include/d2fe.h"
 #include "kernels.h"
+#include "sp_plan.h"
 
 namespace d2fe {
 int ctx_fail(int code, const std::string& msg);
@@ -37,14 +38,78 @@ struct Layer {
   int cout = 0, cout_pad = 0, cin = 0, ks = 0;
 };
 
-enum { L_1B = 0, L_2A, L_2B, L_3A, L_3B, L_4A, L_4B, L_PADA, L_PB, L_DB, L_PA, L_DA32, L_DB32,      // the last three: sparse descriptor head
-       L_X1B, L_X2A, L_X2B, L_X3A, L_X3B, L_X4A, L_X4B, L_XPA,     // exact_order: direct fp32 packings of the eight Winograd layers of the detector path
-       L_COUNT };
-
-struct Tensor {
-  float* p = nullptr;
-  size_t per_img = 0;  // floats per image at max size
+// The one owner of a set of device buffers: hands out a pointer, remembers it and frees everything when it goes (SpNet, SpRun; a debug hook's buffers, whichever
+// way the hook returns)
+struct DevPool {
+  std::vector<void*> owned;
+  DevPool() = default; DevPool(const DevPool&) = delete; DevPool& operator=(const DevPool&) = delete;
+  ~DevPool() { clear(); }
+  void clear() { for (void* p : owned) (void)hipFree(p); owned.clear(); }
+  // one pointer back early (a re-upload replaces it); nullptr: nothing
+  void give_back(void* p) {
+    for (size_t i = 0; p && i < owned.size(); ++i) if (owned[i] == p) { (void)hipFree(p); owned.erase(owned.begin() + i); return; }
+  }
+  template <class T>
+  hipError_t alloc(T** out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
+    if (e == hipSuccess) owned.push_back(p);
+    *out = static_cast<T*>(p);
+    return e;
+  }
+  // bytes of device memory, filled with `fill` bytes (outputs: 0xff, so that an entry a kernel does not write is no plausible value) or with src
+  template <class T>
+  hipError_t get(T** out, size_t bytes, const void* src, int fill = 0xff) {
+    const hipError_t e = alloc(out, bytes);
+    if (e != hipSuccess || !bytes) return e;
+    return src ? hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) : hipMemset(*out, fill, bytes);
+  }
 };
+
+// ---- SuperPoint (superpoint_host.hip; the network itself is sp_plan.h) ----
+// what d2fe_load_superpoint / d2fe_set_superpoint_pca build: a parent handle shares it with its pipeline lanes, and both calls change it in place (they refuse
+// while pipes are alive); owns its device memory
+struct SpNet {
+  bool sp_loaded = false;
+  float* w1a = nullptr;  // [9][64]
+  float* b1a = nullptr;
+  Layer L[L_COUNT];
+  float* pca_comp_t = nullptr; float* pca_mean = nullptr; int pca_dims = 0;
+  unsigned long long* eo_stats = nullptr;      // exact_order: [4] marked candidates, cells re-evaluated, cells dropped, calls -- one set per parent handle
+  DevPool pool;      // (makes the net non-copyable; its destructor frees the device memory)
+};
+// what one context owns to run the network: SpRun::pool holds every pointer below
+struct SpBufs {
+  bool fuse1a = true;      // conv1a fused into conv1b's staging (D2FE_FUSE1A=0 keeps the stand-alone conv1a kernel)
+  bool wino_dynamic = true;    // D2FE_WINO_DYNAMIC=0: static round-robin split of the work items
+  // activations (NHWC fp32), a buffer per layer so that d2fe_debug_read can inspect any of them: act[plan layer] for conv1a (the stand-alone conv1a kernel and
+  // debug reads only) .. conv4b; act[SP_PA]: the heads' convPa | convDa buffer
+  float* act[SP_PA + 1] = {};
+  float *logits = nullptr, *draw = nullptr, *semi = nullptr;
+  // async_tail: the post-processing (softmax .. descriptors) of call k runs on tail_stream under the convolutions of call k+1,
+  // so the three tensors the tail reads exist twice (buffer set = call parity) and events order trunk / tail / reuse
+  float *a4b2 = nullptr, *logits2 = nullptr, *draw2 = nullptr;
+  unsigned long long* cand = nullptr;
+  long cand_cap = 0;
+  int* work_ctrs = nullptr;    // one work-item counter per Winograd layer, zeroed at the start of every network pass (ConvArgs::work_ctr)
+  int* cand_count = nullptr;   // work_ctrs + 64: ONE memset clears both
+  float* zeros = nullptr;      // 1 KiB of zeros (ConvArgs::zeros)
+  // sparse descriptor head (variant B unless cfg.dense_descriptors): cell flags, cell -> slot map, slot -> cell list, counts, descriptors
+  bool sparse_desc = false; int sp_slots = 0; int sp_min_batch = 4;
+  uint8_t* sp_flags = nullptr; int32_t* sp_slotmap = nullptr; int32_t* sp_cells = nullptr; int32_t* sp_count = nullptr; float* sp_desc = nullptr;
+  float* sp_mid = nullptr; int sp_mid_imgs = 0;      // ReLU(convDa) at the selected cells between the two stages of the split sparse head (passes of <= 4 images)
+  float* aconf = nullptr; int* clist = nullptr; int* a_ncand = nullptr;     // variant A scratch
+  float* a_samp = nullptr; float* a_cn = nullptr; int a_scap = 0;   // variant A sampling: [batch][a_scap][256] samples, [batch][256] channel norms
+  // exact_order (exact_order.hip; cfg.exact_order): eo_slots crops of 88x88 per call through the direct kernels
+  int eo_slots = 0; float eo_eps = 0.f;
+  uint8_t* eo_crops = nullptr; int* eo_cell_map = nullptr; int* eo_cell_list = nullptr; int* eo_cell_count = nullptr;
+  float* eo_act = nullptr;           // the crop batch's activations, laid out by sp_crop_layout
+};
+struct SpRun : SpBufs {
+  DevPool pool;
+  int alloc(const d2fe_config& cfg);
+  void release() { pool.clear(); static_cast<SpBufs&>(*this) = SpBufs(); }
+};      // (non-copyable through `pool`, whose destructor releases)
 
 // ---- NetVLAD (netvlad_host.hip) ----
 // One launch form of the execution plan over the flat layer list: fused MobileNetV2 blocks (netvlad_fused.hip, netvlad_pair.hip) where the pattern
@@ -116,33 +181,22 @@ struct NvRun {
 struct d2fe_context {
   d2fe_config cfg;
   hipStream_t stream = nullptr;
-  bool sp_loaded = false;
-  bool borrowed = false;       // a pipeline lane (clone_lane): the packed weights belong to the parent context
   std::atomic<bool> doomed{false};    // d2fe_destroy was called while pipes were alive: the last d2fe_pipe_destroy releases the handle
   std::atomic<int> live_pipes{0};   // pipes created from this handle and not destroyed yet: their lanes read THIS handle's packed weights, so d2fe_destroy,
                                // d2fe_load_* and d2fe_set_*_pca refuse (D2FE_ERR_INVALID) while it is non-zero
-  float* w1a = nullptr;  // [9][64]
-  float* b1a = nullptr;
-  d2fe::Layer L[d2fe::L_COUNT];
-  // activations (NHWC fp32), separate buffer per layer so that d2fe_debug_read can inspect any of them
-  d2fe::Tensor a1a, a1b, a2a, a2b, a3a, a3b, a4a, a4b, aPD, logits, draw, semi;
-  // async_tail: the post-processing (softmax .. descriptors) of call k runs on tail_stream under the convolutions of call k+1,
-  // so the three tensors the tail reads exist twice (buffer set = call parity) and events order trunk / tail / reuse
-  d2fe::Tensor a4b2, logits2, draw2;
+  // SuperPoint: the network (shared with the pipeline lanes) and this context's buffers
+  std::shared_ptr<d2fe::SpNet> sp_net;
+  d2fe::SpRun sp_run;
+  // async_tail: the handle's second stream and the events that order trunk / tail / buffer reuse (SpBufs)
   hipStream_t tail_stream = nullptr;
   hipEvent_t ev_trunk[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
   int parity = 0, last_set = 0;
-  unsigned long long* cand = nullptr;
-  int* cand_count = nullptr;
-  long cand_cap = 0;
   // staging for the host-pointer API
   uint8_t* s_img = nullptr;
   int s_cap = 0;
   // last call geometry (for debug reads)
   int last_w = 0, last_h = 0, last_n = 0;
   const uint8_t* last_gray = nullptr; int last_stride = 0; size_t last_istride = 0;
-  float* aconf = nullptr; int* clist = nullptr; int* a_ncand = nullptr;     // variant A scratch
-  float* zeros = nullptr;      // 1 KiB of zeros (ConvArgs::zeros)
   // host-pointer calls: pinned host staging (one DMA in, one DMA out per call) and cached hipGraphs of the launch sequences.
   // The reference calls infer / inference with ONE image at 15-30 Hz (loop_cam.cpp:609-616): at that batch the ~10 us the command
   // processor spends between two dependent launches and the per-copy latency of pageable D2H copies are a third of a call.
@@ -163,25 +217,11 @@ struct d2fe_context {
   int ncu_dev = 256;           // compute units of cfg.device_id: decisions that fix an arithmetic order use this one
   unsigned long long* match_stamps = nullptr;   // development builds: [4096][16] phase stamps of the last d2fe_match_batch_device launch
   int32_t* match_stats = nullptr;   // [4] matcher counters: [0] queries that took the exact fallback scan (MatchArgs::stats)
-  int* work_ctrs = nullptr;    // one work-item counter per Winograd layer, zeroed at the start of every network pass (ConvArgs::work_ctr)
-  bool wino_dynamic = true;    // D2FE_WINO_DYNAMIC=0: static round-robin split of the work items
-  // sparse descriptor head (variant B unless cfg.dense_descriptors): cell flags, cell -> slot map, slot -> cell list, counts, descriptors
-  bool sparse_desc = false; int sp_slots = 0; int sp_min_batch = 4;
-  uint8_t* sp_flags = nullptr; int32_t* sp_slotmap = nullptr; int32_t* sp_cells = nullptr; int32_t* sp_count = nullptr; float* sp_desc = nullptr;
-  float* sp_mid = nullptr; int sp_mid_imgs = 0;      // ReLU(convDa) at the selected cells between the two stages of the split sparse head (passes of <= 4 images)
-  // exact_order (exact_order.hip; cfg.exact_order): eo_slots crops of 88x88 per call through the direct kernels
-  int eo_slots = 0; float eo_eps = 0.f;
-  uint8_t* eo_crops = nullptr; int* eo_cell_map = nullptr; int* eo_cell_list = nullptr; int* eo_cell_count = nullptr;
-  float* eo_act = nullptr;           // the crop batch's activations, carved per layer in run_exact_order (api.hip)
-  unsigned long long* eo_stats = nullptr;      // [4] marked candidates, cells re-evaluated, cells dropped, calls: the parent handle's, shared with its lanes
   void* lk_scratch = nullptr; size_t lk_scratch_bytes = 0;   // grow-only scratch of the LK / detector entry points (lk.hip)
-  float* a_samp = nullptr; float* a_cn = nullptr; int a_scap = 0;   // variant A sampling: [batch][a_scap][256] samples, [batch][256] channel norms
-  float* pca_comp_t = nullptr; float* pca_mean = nullptr; int pca_dims = 0;
   // NetVLAD: the network (shared with the pipeline lanes), this context's buffers and the host-pointer staging of d2fe_netvlad(_batch)
   std::shared_ptr<d2fe::NvNet> nv_net;
   d2fe::NvRun nv_run;
   uint8_t* nv_s_img = nullptr; float* nv_s_out = nullptr;
-  bool fuse1a = true;      // conv1a fused into conv1b's staging (D2FE_FUSE1A=0 keeps the stand-alone conv1a kernel)
   // host-pointer matcher: pool of (stream, scratch) slots so that concurrent callers (the reference calls matchKNN from three
   // threads) neither share state nor pay hipStreamCreate / hipMalloc / hipFree (a device-wide sync) per call
   struct MatchSlot { hipStream_t stream = nullptr; char* buf = nullptr; char* pin = nullptr; size_t bytes = 0; bool busy = false; };
@@ -200,7 +240,7 @@ struct d2fe_context {
 
 
 namespace d2fe {
-// launch sequences (api.hip, netvlad_host.hip).  run_superpoint == one TensorRT executeV2 + processOutput of the reference; run_netvlad == one
+// launch sequences (superpoint_host.hip, netvlad_host.hip).  run_superpoint == one TensorRT executeV2 + processOutput of the reference; run_netvlad == one
 // MobileNetVLADONNX::inference.  Both only enqueue work on the given stream(s)
 int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_kps, float* d_scores,
                    float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s, hipStream_t s_tail = nullptr, int bs = 0);
@@ -208,9 +248,8 @@ int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap);
 int desc_dim_of(const d2fe_context* h);      // floats per descriptor row: 256, or pca_dims where a PCA is set (d2fe_desc_dim)
 int nv_check(d2fe_context* h, int n, int W, int H, int stride);
-// a second context on the same device that BORROWS the parent's packed weights (SuperPoint, NetVLAD, PCA matrices) and owns its own
-// activations, scratch, counters and streams: one lane of the frames-in-flight pipeline.  d2fe_destroy() of a lane leaves the weights alone;
-// the parent must outlive its lanes and must not reload weights while they exist
+// a second context on the same device that SHARES the parent's networks (SpNet, NvNet: packed weights, PCA matrices) and owns its own
+// activations, scratch, counters and streams: one lane of the frames-in-flight pipeline.  The parent must not reload weights while lanes exist
 // `stream` (optional): the lane's launch stream, e.g. one created with a CU mask (the lane then owns it); `ncu` (optional): the compute units that
 // stream may use -- the persistent kernels size their grids on it
 // with_netvlad: the lane will run NetVLAD itself (its own activation buffers); a lane never gets the host-pointer staging of d2fe_create
@@ -222,7 +261,7 @@ hipError_t create_stream_beside(int device_id, hipStream_t beside, hipStream_t* 
 // on different ones too -- the lanes of d2fe_pipe_create and d2fe_quad_pipe_create.  first_class / second_class / n_classes: what was measured (-1 / 0: nothing)
 int place_streams(int device_id, int n_first, int n_second, std::vector<hipStream_t>& first, std::vector<hipStream_t>& second, std::vector<int>& first_class,
                   std::vector<int>& second_class, int* n_classes, long long* probe_ticks, double* probe_turns_us);
-// helpers of the entry points (api.hip) that netvlad_host.hip shares
+// helpers of the entry points (api.hip) that superpoint_host.hip and netvlad_host.hip share
 int fail(int code, const std::string& msg);      // records d2fe_last_error(), returns `code`
 int upload(const void* src, size_t bytes, void** dst);
 // host image(s) -> the handle's device staging, tight rows: through the pinned staging buffer (CPU row copy + ONE DMA) or, when that
@@ -251,8 +290,8 @@ int depth_gather_launch(d2fe_context* h, const uint16_t* d_depth, int W, int H, 
 
 struct ProfScope {
   d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
-  ProfScope(d2fe_context* h_, int stage_, hipStream_t s_) : h(h_), stage(stage_), s(s_) {
-    on = h->prof_mode == 2 || (h->prof_mode == 1 && (stage == D2FE_PROF_CONV1B || stage == D2FE_PROF_NETVLAD));
+  ProfScope(d2fe_context* h_, int stage_, hipStream_t s_, bool want = true) : h(h_), stage(stage_), s(s_) {      // want = false: a scope that records nothing
+    on = want && (h->prof_mode == 2 || (h->prof_mode == 1 && (stage == D2FE_PROF_CONV1B || stage == D2FE_PROF_NETVLAD)));
     if (!on) return;
     if (h->prof_used + 2 > h->prof_pool.size()) {
       for (int i = 0; i < 64; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { on = false; return; } h->prof_pool.push_back(e); }
