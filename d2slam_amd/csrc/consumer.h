@@ -22,7 +22,7 @@ void take_config(Cfg& cfg, const Cfg* cfg_in) {
 inline void match_outputs(MatchArgs& m, int32_t* q_idx, int32_t* t_idx, float* dist, int32_t* n_out, void* scratch, int pair_cap, const d2fe_context* h, int ncu = 0) {
   m.q_idx = q_idx; m.t_idx = t_idx; m.dist = dist; m.n_out = n_out;
   match_scratch_carve(scratch, pair_cap, &m);
-  m.stats = h->match_stats; m.ncu = ncu ? ncu : h->ncu;
+  m.stats = h->match.stats; m.ncu = ncu ? ncu : h->ncu;
 }
 
 // what d2fe_pipe_device_result and d2fe_quad_device_result share; frames: stereo frames or quad frames, the arrays hold frames * views rows

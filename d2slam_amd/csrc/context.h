@@ -1,10 +1,9 @@
 // context.h -- the device context behind d2fe_handle and the launch sequences shared by the translation units that implement
-// include/d2fe.h (api.hip: handle lifecycle and the entry points; superpoint_host.hip: SuperPoint's host side; netvlad_host.hip: NetVLAD's host side; lk.hip, lk_carry.hip: the trackers;
+// include/d2fe.h (api.hip: handle lifecycle and the extract entry points; superpoint_host.hip: SuperPoint's host side; netvlad_host.hip: NetVLAD's host side; match_host.hip: the
+// matcher's; next_host.hip: the "next rows"; debug_hooks.hip: the development library's hooks on injected tensors; lk.hip, lk_carry.hip: the trackers;
 // pipe.hip, quad_pipe.hip: the frames-in-flight pipelines; exchange.hip, quad_exchange.hip, loop.hip, window.hip: the consumers behind them).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#include <atomic>
 
 #include <array>
 #include <deque>
@@ -15,6 +14,7 @@
 #include <vector>
 
 #include "../../include/d2fe.h"
+#include "handle_life.h"
 #include "kernels.h"
 #include "sp_plan.h"
 
@@ -176,14 +176,79 @@ struct NvRun {
   NvRun() = default; NvRun(const NvRun&) = delete; NvRun& operator=(const NvRun&) = delete; ~NvRun() { release(); }
 };
 
+// ---- the matcher's host side (match_host.hip) ----
+struct MatchHost {
+  // host-pointer matcher: pool of (stream, scratch) slots so that concurrent callers (the reference calls matchKNN from three
+  // threads) neither share state nor pay hipStreamCreate / hipMalloc / hipFree (a device-wide sync) per call
+  struct Slot {
+    hipStream_t stream = nullptr; char* buf = nullptr; char* pin = nullptr; size_t bytes = 0; bool busy = false;
+    int grow(size_t want, bool pinned);      // by the call that holds the slot, OUTSIDE the lock (hipFree / hipHostFree synchronise the device)
+  };
+  // one call's hold on a slot: a free one or a new one (with its stream) under the lock, given back on scope exit.  slot == nullptr: no stream could be created
+  struct Lease {
+    MatchHost& m; Slot* slot = nullptr;
+    explicit Lease(MatchHost& m_);
+    ~Lease() { if (slot) { std::lock_guard<std::mutex> lk(m.mu); slot->busy = false; } }
+  };
+  // device-API matcher scratch (cand4), one per caller stream: calls on different streams may overlap on the GPU
+  struct Scratch { hipStream_t stream = nullptr; int32_t* cand4 = nullptr; size_t bytes = 0; int npairs = 0; };
+  std::deque<Slot> slots;          // deque: growing it never relocates the slots other threads are using
+  std::deque<Scratch> scratch;
+  std::mutex mu;
+  int32_t* stats = nullptr;        // [4] matcher counters: [0] queries that took the exact fallback scan (MatchArgs::stats)
+  unsigned long long* stamps = nullptr;   // development builds: [4096][16] phase stamps of the last d2fe_match_batch_device launch
+  void release();                  // drains and destroys the slot streams, frees every buffer
+  ~MatchHost() { release(); }
+};
+
+// ---- what only a handle of d2fe_create has (a pipe lane is driven through run_superpoint / run_netvlad on device buffers of the pipe) ----
+// staging of the host-pointer extract and NetVLAD calls: the frame upload buffers and output blocks on the device (pool), their pinned mirrors (one DMA in, one
+// DMA out per call), and d2fe_extract_all*'s second stream.  The reference calls infer / inference with ONE image at 15-30 Hz (loop_cam.cpp:609-616): at that
+// batch the per-copy latency of pageable D2H copies is a sizeable part of a call
+struct HostStage {
+  DevPool pool;
+  uint8_t* s_img = nullptr;
+  float* s_out = nullptr;      // [kps | scores | desc | n | idx] of a host-pointer extract call, contiguous -> ONE D2H of the first four
+  size_t s_out_bytes = 0;
+  uint8_t* nv_s_img = nullptr; float* nv_s_out = nullptr;      // d2fe_netvlad(_batch): from d2fe_load_netvlad on
+  uint8_t* pin_in = nullptr; size_t pin_in_bytes = 0;
+  float* pin_out = nullptr; size_t pin_out_bytes = 0;
+  float* pin_nv = nullptr; size_t pin_nv_bytes = 0;
+  // d2fe_extract_all*: NetVLAD of the same uploaded frame(s) on a second stream, beside SuperPoint
+  hipStream_t nv_stream = nullptr; hipEvent_t ev_up = nullptr;
+  // *p becomes a device buffer of `bytes` (the old one is freed first)
+  template <class T>
+  hipError_t dev(T** p, size_t bytes) { pool.give_back(*p); *p = nullptr; return pool.alloc(p, bytes); }
+  // *p becomes a pinned buffer of `bytes`, *have its size.  Not fatal: false leaves nullptr and 0, and the pageable path serves the call
+  template <class T>
+  bool pinned(T** p, size_t* have, size_t bytes) {
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *have = 0;
+    if (hipHostMalloc(p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+    *have = bytes;
+    return true;
+  }
+  ~HostStage() {      // (the device buffers go with `pool`)
+    if (nv_stream) { (void)hipStreamSynchronize(nv_stream); (void)hipStreamDestroy(nv_stream); }
+    if (ev_up) (void)hipEventDestroy(ev_up);
+    for (void* p : {(void*)pin_in, (void*)pin_out, (void*)pin_nv}) if (p) (void)hipHostFree(p);
+  }
+};
+
+// grow-only device scratch of the LK / detector and "next rows" host-pointer entry points (ctx_scratch)
+struct GrowScratch {
+  void* p = nullptr; size_t bytes = 0;
+  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+  ~GrowScratch() { release(); }
+};
+
 }  // namespace d2fe
 
 struct d2fe_context {
   d2fe_config cfg;
   hipStream_t stream = nullptr;
-  std::atomic<bool> doomed{false};    // d2fe_destroy was called while pipes were alive: the last d2fe_pipe_destroy releases the handle
-  std::atomic<int> live_pipes{0};   // pipes created from this handle and not destroyed yet: their lanes read THIS handle's packed weights, so d2fe_destroy,
-                               // d2fe_load_* and d2fe_set_*_pca refuse (D2FE_ERR_INVALID) while it is non-zero
+  d2fe::HandleLife life;       // pipes created from this handle and not destroyed yet: their lanes read THIS handle's packed weights, so d2fe_load_* and
+                               // d2fe_set_*_pca refuse (D2FE_ERR_INVALID) while there are any, and d2fe_destroy is deferred to the last of them
   // SuperPoint: the network (shared with the pipeline lanes) and this context's buffers
   std::shared_ptr<d2fe::SpNet> sp_net;
   d2fe::SpRun sp_run;
@@ -191,22 +256,13 @@ struct d2fe_context {
   hipStream_t tail_stream = nullptr;
   hipEvent_t ev_trunk[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
   int parity = 0, last_set = 0;
-  // staging for the host-pointer API
-  uint8_t* s_img = nullptr;
-  int s_cap = 0;
+  std::unique_ptr<d2fe::HostStage> stage;      // staging for the host-pointer API (null on a lane)
   // last call geometry (for debug reads)
   int last_w = 0, last_h = 0, last_n = 0;
   const uint8_t* last_gray = nullptr; int last_stride = 0; size_t last_istride = 0;
-  // host-pointer calls: pinned host staging (one DMA in, one DMA out per call) and cached hipGraphs of the launch sequences.
-  // The reference calls infer / inference with ONE image at 15-30 Hz (loop_cam.cpp:609-616): at that batch the ~10 us the command
-  // processor spends between two dependent launches and the per-copy latency of pageable D2H copies are a third of a call.
-  uint8_t* pin_in = nullptr; size_t pin_in_bytes = 0;
-  float* pin_out = nullptr; size_t pin_out_bytes = 0;
-  float* s_out = nullptr;      // device: [kps | scores | desc | n | idx] of a host-pointer extract call, contiguous -> ONE D2H of the first four
-  size_t s_out_bytes = 0;
+  // host-pointer calls: cached hipGraphs of the launch sequences (at one image per call the ~10 us the command processor spends between two dependent
+  // launches are a sizeable part of a call) and pinned staging
   bool use_graphs = true, use_pinned = true;       // D2FE_GRAPH=0 / D2FE_PINNED=0 switch them off (A/B measurements)
-  // d2fe_extract_all*: NetVLAD of the same uploaded frame(s) on a second stream, beside SuperPoint
-  hipStream_t nv_stream = nullptr; hipEvent_t ev_up = nullptr; float* pin_nv = nullptr; size_t pin_nv_bytes = 0;
   // host-side bookkeeping a launch sequence leaves behind (what the debug reads and the next NetVLAD step consult): saved when a sequence is
   // captured, restored on every replay, so that a replay leaves the handle exactly as a direct run of the same geometry would
   struct HostState { int last_w = 0, last_h = 0, last_n = 0, last_set = 0; const uint8_t* last_gray = nullptr; int last_stride = 0; size_t last_istride = 0;
@@ -215,21 +271,11 @@ struct d2fe_context {
   std::map<std::array<long, 6>, GraphEntry> graphs;
   int ncu = 256;               // compute units this context sizes its persistent grids for: the device's (d2fe_create) or a pipeline lane's share
   int ncu_dev = 256;           // compute units of cfg.device_id: decisions that fix an arithmetic order use this one
-  unsigned long long* match_stamps = nullptr;   // development builds: [4096][16] phase stamps of the last d2fe_match_batch_device launch
-  int32_t* match_stats = nullptr;   // [4] matcher counters: [0] queries that took the exact fallback scan (MatchArgs::stats)
-  void* lk_scratch = nullptr; size_t lk_scratch_bytes = 0;   // grow-only scratch of the LK / detector entry points (lk.hip)
-  // NetVLAD: the network (shared with the pipeline lanes), this context's buffers and the host-pointer staging of d2fe_netvlad(_batch)
+  d2fe::MatchHost match;
+  d2fe::GrowScratch scratch;
+  // NetVLAD: the network (shared with the pipeline lanes) and this context's buffers
   std::shared_ptr<d2fe::NvNet> nv_net;
   d2fe::NvRun nv_run;
-  uint8_t* nv_s_img = nullptr; float* nv_s_out = nullptr;
-  // host-pointer matcher: pool of (stream, scratch) slots so that concurrent callers (the reference calls matchKNN from three
-  // threads) neither share state nor pay hipStreamCreate / hipMalloc / hipFree (a device-wide sync) per call
-  struct MatchSlot { hipStream_t stream = nullptr; char* buf = nullptr; char* pin = nullptr; size_t bytes = 0; bool busy = false; };
-  std::deque<MatchSlot> match_slots;     // deque: growing it never relocates the slots other threads are using
-  std::mutex match_mu;
-  // device-API matcher scratch (cand4), one per caller stream: calls on different streams may overlap on the GPU
-  struct MatchScratch { hipStream_t stream = nullptr; int32_t* cand4 = nullptr; size_t bytes = 0; int npairs = 0; };
-  std::deque<MatchScratch> m_scratch;
   // profiling (HIP events on the launch stream)
   int prof_mode = 0;
   std::vector<hipEvent_t> prof_pool;
@@ -261,9 +307,10 @@ hipError_t create_stream_beside(int device_id, hipStream_t beside, hipStream_t* 
 // on different ones too -- the lanes of d2fe_pipe_create and d2fe_quad_pipe_create.  first_class / second_class / n_classes: what was measured (-1 / 0: nothing)
 int place_streams(int device_id, int n_first, int n_second, std::vector<hipStream_t>& first, std::vector<hipStream_t>& second, std::vector<int>& first_class,
                   std::vector<int>& second_class, int* n_classes, long long* probe_ticks, double* probe_turns_us);
-// helpers of the entry points (api.hip) that superpoint_host.hip and netvlad_host.hip share
+// helpers of the entry points (api.hip) that the other host units share
 int fail(int code, const std::string& msg);      // records d2fe_last_error(), returns `code`
 int upload(const void* src, size_t bytes, void** dst);
+int ctx_scratch(d2fe_handle h, size_t bytes, void** out);      // at least `bytes` of the handle's grow-only device scratch (GrowScratch)
 // host image(s) -> the handle's device staging, tight rows: through the pinned staging buffer (CPU row copy + ONE DMA) or, when that
 // is off, with pageable 2D copies
 int upload_frames(d2fe_context* h, uint8_t* d_dst, const uint8_t* gray, int n, int width, int height, int stride, size_t image_stride, hipStream_t s);

@@ -1,0 +1,301 @@
+// debug_hooks.hip -- the development library's hooks (include/d2fe_debug.h) that need nothing of the handle but its device and stream: the launch-regime
+// record, the host-side packings, one Winograd layer, the SuperPoint tail kernels on injected tensors, the count of captured launch sequences.  (The hooks that
+// read a unit's own state back live with that state: d2fe_debug_read in superpoint_host.hip, the NetVLAD ones in netvlad_host.hip, the matcher's stamps in
+// match_host.hip.)  The whole unit compiles to nothing for the product library.
+#ifdef D2FE_DEVTOOLS
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "../../include/d2fe_debug.h"
+
+using namespace d2fe;
+
+// launch-regime record (kernels.h: D2FE_REGIME): process-wide, written by the launchers from any thread (pipe lanes)
+namespace {
+std::atomic<long long> g_regime[D2FE_REGIME_COUNT];
+}  // namespace
+namespace d2fe {
+void regime_note(int regime) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].fetch_add(1, std::memory_order_relaxed); }
+void regime_set(int regime, long long value) { if (regime >= 0 && regime < D2FE_REGIME_COUNT) g_regime[regime].store(value, std::memory_order_relaxed); }
+}  // namespace d2fe
+
+extern "C" {
+
+int d2fe_debug_regime_counts(long long* out, int max) {
+  for (int i = 0; out && i < max && i < D2FE_REGIME_COUNT; ++i) out[i] = g_regime[i].load(std::memory_order_relaxed);
+  return D2FE_REGIME_COUNT;
+}
+void d2fe_debug_regime_reset(void) {
+  for (auto& c : g_regime) c.store(0, std::memory_order_relaxed);
+}
+
+// Host-side half of the Winograd mode, callable without a GPU: U = G g G^T in the kernels' fragment order (see pack_weights_wino).
+long d2fe_debug_pack_wino(const float* weight, int cout, int cin, float* out, long max_floats) {
+  if (!weight || !out || cout < 1 || cin < 8 || (cin & 7)) return fail(D2FE_ERR_INVALID, "bad argument");
+  const int cout_pad = (cout + 63) / 64 * 64;
+  const size_t n = packed_weight_floats_wino(cout_pad, cin);
+  if ((long)n > max_floats) return fail(D2FE_ERR_TRUNCATED, "destination too small");
+  pack_weights_wino(weight, cout, cin, cout_pad, out);
+  return (long)n;
+}
+
+// Tile shape the NetVLAD block launchers pick for an Ho x Wo output map (no GPU needed; tests/test_netvlad_pack_cpu.py sweeps it against the kernels' limits):
+// kind 0 nv_pblock_kernel (stride 1), kind 1 nv_fpair_kernel (first block; c0_stride = stride of the first conv), kind 2 nv_xblock_kernel (stride = 1 or 2).
+int d2fe_debug_netvlad_tile(int kind, int Ho, int Wo, int stride, int* th, int* tw) {
+  if (!th || !tw || Ho < 1 || Wo < 1 || stride < 1 || stride > 2) return fail(D2FE_ERR_INVALID, "bad argument");
+  if (kind == 0) nv_pblock_tile(Ho, Wo, th, tw, 0);
+  else if (kind == 1) nv_pblock_tile(Ho, Wo, th, tw, stride);
+  else if (kind == 2) nv_xblock_tile(Ho, Wo, stride, th, tw);
+  else return fail(D2FE_ERR_INVALID, "kind");
+  return D2FE_OK;
+}
+
+// Host-side weight packing of the NetVLAD block kernels, callable without a GPU (tests/test_netvlad_pack_cpu.py):
+//   kind 0 expand record of nv_pblock_kernel (pack_nv_expand_pair)      kind 1 depthwise + project record of nv_pblock / nv_fpair (pack_nv_dwproj_pair)
+//   kind 2 expand record of nv_xblock_kernel (pack_nv_expand_perm)      kind 3 depthwise + project record of nv_xblock_kernel (pack_nv_dwproj_x)
+//   kind 4 expand record of nv_tail_kernel (pack_nv_expand_tail)        kind 5 project record of nv_tail_kernel (pack_nv_proj_t)
+// we [chid][cin], be [chid], wd [chid][9], bd [chid], wp [cout][chid]; returns the number of floats written or <0.
+long d2fe_debug_pack_netvlad(int kind, const float* we, const float* be, const float* wd, const float* bd, const float* wp, int cin, int chid,
+                             int cout, float* out, long max_floats) {
+  if (!out || cin < 8 || (cin & 7) || chid < 16 || (chid & 15) || cout < 1) return fail(D2FE_ERR_INVALID, "bad argument");
+  const int nt = kind <= 1 ? nv_pblock_ntiles(cout) : nv_block_ntiles(cout);
+  if (nt < 0) return fail(D2FE_ERR_UNSUPPORTED, "cout");
+  size_t n = 0;
+  switch (kind) {
+    case 0: n = pack_nv_expand_pair_floats(chid, cin); break;
+    case 1: n = pack_nv_dwproj_pair_floats(chid, nt); break;
+    case 2: if (!nv_xblock_supported(cin, chid, cout, 1)) return fail(D2FE_ERR_UNSUPPORTED, "shape"); n = pack_nv_expand_perm_floats(chid, cin); break;
+    case 3: case 5: n = pack_nv_dwproj_floats(chid, nt); break;
+    case 4: if (!nv_tail_supported(cin, cout)) return fail(D2FE_ERR_UNSUPPORTED, "shape"); n = pack_nv_expand_floats(chid, cin); break;
+    default: return fail(D2FE_ERR_INVALID, "kind");
+  }
+  if ((long)n > max_floats) return fail(D2FE_ERR_TRUNCATED, "destination too small");
+  if (((kind == 0 || kind == 2 || kind == 4) && (!we || !be)) || ((kind == 1 || kind == 3) && (!wd || !bd || !wp)) || (kind == 5 && !wp))
+    return fail(D2FE_ERR_INVALID, "null weights");
+  switch (kind) {
+    case 0: pack_nv_expand_pair(we, be, chid, cin, out); break;
+    case 1: pack_nv_dwproj_pair(wd, bd, wp, cout, chid, nt, out); break;
+    case 2: pack_nv_expand_perm(we, be, chid, cin, out); break;
+    case 3: pack_nv_dwproj_x(wd, bd, wp, cout, chid, nt, out); break;
+    case 4: pack_nv_expand_tail(we, be, chid, cin, out); break;
+    case 5: pack_nv_proj_t(wp, cout, chid, nt, out); break;
+  }
+  return (long)n;
+}
+
+// One 3x3 layer through the Winograd kernels, host buffers in and out (layer-level parity tests and timing; not a product path).
+int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int H, int W, int cin, const float* weight, const float* bias,
+                            int cout, int pool, int relu, float* out, int iters, float* ms_per_launch) {
+  if (!h || !in || !weight || !bias || !out) return fail(D2FE_ERR_INVALID, "null argument");
+  if ((cin != 64 && cin != 128) || cout < 1 || n < 1 || H < 2 || W < 2 || (pool && ((H | W) & 1)) || !relu)
+    return fail(D2FE_ERR_INVALID, "unsupported layer shape");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const int cout_pad = (cout + 63) / 64 * 64;
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+  const size_t in_fl = (size_t)n * H * W * cin, out_fl = (size_t)n * Ho * Wo * cout;
+  if ((size_t)H * W * cin * 4 >= (1ull << 31)) return fail(D2FE_ERR_INVALID, "image too large");
+  std::vector<float> pk(packed_weight_floats_wino(cout_pad, cin)), bp(cout_pad, 0.f);
+  pack_weights_wino(weight, cout, cin, cout_pad, pk.data());
+  memcpy(bp.data(), bias, sizeof(float) * cout);
+  // as a pass of run_superpoint: the work counter is zero when the launch starts (the last of the handle's 64, which no layer of the network uses)
+  int* const wctr = h->sp_run.wino_dynamic ? h->sp_run.work_ctrs + 63 : nullptr;
+  auto launch = [&](const ConvArgs& ca) {
+    if (wctr) { const hipError_t e = hipMemsetAsync(wctr, 0, sizeof(int), h->stream); if (e != hipSuccess) return e; }
+    return launch_conv_wino(cin, pool != 0, relu != 0, cout_pad, ca, h->stream);
+  };
+  DevPool b;
+  float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = [&]() -> int {
+    HIP_TRY(b.get(&d_in, in_fl * 4, in));
+    HIP_TRY(b.get(&d_out, out_fl * 4, nullptr));
+    HIP_TRY(b.get(&d_w, pk.size() * 4, pk.data()));
+    HIP_TRY(b.get(&d_b, bp.size() * 4, bp.data()));
+    HIP_TRY(hipDeviceSynchronize());      // the null-stream memset is not ordered with the handle's non-blocking stream
+    ConvArgs a{};
+    a.in = d_in; a.in_cstride = cin; a.in_coff = 0; a.out = d_out; a.out_cstride = cout; a.out_coff = 0;
+    a.cout_real = cout; a.wpack = d_w; a.bias = d_b; a.H = H; a.W = W; a.n_img = n;
+    a.in_img_stride = (long)H * W * cin; a.out_img_stride = (long)Ho * Wo * cout; a.zeros = h->sp_run.zeros; a.ncu = h->ncu;
+    a.ablate = d2fe_dev_env("D2FE_ABLATE", 0);
+    a.work_ctr = wctr;
+    HIP_TRY(launch(a));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, d_out, out_fl * 4, hipMemcpyDeviceToHost));
+    if (iters > 0 && ms_per_launch) {
+      HIP_TRY(hipEventCreate(&e0));
+      HIP_TRY(hipEventCreate(&e1));
+      HIP_TRY(hipEventRecord(e0, h->stream));
+      for (int i = 0; i < iters; ++i) HIP_TRY(launch(a));
+      HIP_TRY(hipEventRecord(e1, h->stream));
+      HIP_TRY(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+      *ms_per_launch = ms / iters;
+    }
+    return D2FE_OK;
+  }();
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+
+// ---- the SuperPoint tail kernels of postproc.hip on injected tensors (tests/test_postproc_edges.py): host buffers in and out, the hook's own device
+// buffers, the handle's device and stream, no weights.  Each hook calls the launch_* function of kernels.h with the caller's parameters and nothing else.
+namespace {
+constexpr long DEBUG_MAX_PIXELS = 1l << 21;
+}  // namespace
+
+int d2fe_debug_softmax_cand(d2fe_handle h, const float* logits, int lstride, int n, int Hc, int Wc, float thr, int border, int want_semi, float* semi_out,
+                            unsigned long long* cand_out, int* cand_count_out) {
+  if (!h || !logits || !cand_out || !cand_count_out || (want_semi && !semi_out)) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || lstride < 65 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t ncell = (size_t)Hc * Wc, hw = ncell * 64;
+  const long cand_cap = (long)hw;
+  DevPool b;
+  float *d_l = nullptr, *d_semi = nullptr;
+  unsigned long long* d_cand = nullptr;
+  int* d_cnt = nullptr;
+  HIP_TRY(b.get(&d_l, sizeof(float) * n * ncell * lstride, logits));
+  if (want_semi) HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());      // the null-stream copies and memsets are not ordered with the handle's non-blocking stream
+  HIP_TRY(launch_softmax_cand(d_l, lstride, Hc, Wc, n, thr, border, d_semi, d_cand, d_cnt, cand_cap, /*zero_counts=*/true, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (want_semi) HIP_TRY(hipMemcpy(semi_out, d_semi, sizeof(float) * n * hw, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cand_out, d_cand, sizeof(unsigned long long) * n * cand_cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cand_count_out, d_cnt, sizeof(int) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int* cand_count, long cand_cap, int n, int W, int H, int max_kp, int cap,
+                        int always_sort, const float* semi_or_null, float thr, int border, float* kps_xy, float* scores, int32_t* kps_idx, int32_t* n_out) {
+  if (!h || !cand || !cand_count || !kps_xy || !scores || !kps_idx || !n_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || W < 1 || H < 1 || cap < 1 || cand_cap < 1 || (long)H * W > DEBUG_MAX_PIXELS || cand_cap > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS)
+    return fail(D2FE_ERR_INVALID, "bad geometry");
+  for (int i = 0; i < n; ++i)
+    if (cand_count[i] < 0 || cand_count[i] > cand_cap) return fail(D2FE_ERR_INVALID, "cand_count entry outside [0, cand_cap]");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t hw = (size_t)H * W;
+  DevPool b;
+  unsigned long long* d_cand = nullptr;
+  int* d_cnt = nullptr;
+  float *d_semi = nullptr, *d_kps = nullptr, *d_sc = nullptr;
+  int32_t *d_idx = nullptr, *d_n = nullptr;
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, cand));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, cand_count));
+  if (semi_or_null) HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, semi_or_null));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get(&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_select_b(d_cand, d_cnt, cand_cap, n, W, max_kp, cap, always_sort, d_semi, H, thr, border, d_kps, d_sc, d_idx, d_n, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(kps_xy, d_kps, sizeof(float) * 2 * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(scores, d_sc, sizeof(float) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(kps_idx, d_idx, sizeof(int32_t) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_out, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+// comp == nullptr: d2fe_debug_sample_b (rows of 256 floats); else d2fe_debug_sample_b_pca (rows of pca_dims floats)
+static int debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                          const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean, int pca_dims, float* desc_out) {
+  if (!h || !desc_raw || !kps_xy || !n_kp || !desc_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  const size_t ncell = (size_t)Hc * Wc;
+  if (slotmap_or_null) {      // sparse store [img][max_slots][256]: every cell the kernel may look up must name a slot of the store
+    if (max_slots < 1 || max_slots > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "max_slots");
+    for (size_t i = 0; i < (size_t)n * ncell; ++i)
+      if (slotmap_or_null[i] < 0 || slotmap_or_null[i] >= max_slots) return fail(D2FE_ERR_INVALID, "slot map entry outside [0, max_slots)");
+  } else if (dcoff < 0 || (dcoff & 3) || (dstride & 3) || dstride < dcoff + 256 || dstride > 4096) {
+    return fail(D2FE_ERR_INVALID, "dense form: dcoff and dstride are multiples of 4 with dcoff + 256 <= dstride");
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  DevPool b;
+  float *d_raw = nullptr, *d_kps = nullptr, *d_desc = nullptr;
+  int32_t *d_n = nullptr, *d_map = nullptr;
+  HIP_TRY(b.get(&d_raw, sizeof(float) * n * (slotmap_or_null ? (size_t)max_slots * 256 : ncell * dstride), desc_raw));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, n_kp));
+  if (slotmap_or_null) HIP_TRY(b.get(&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
+  const size_t D = comp ? (size_t)pca_dims : 256;
+  float *d_comp_t = nullptr, *d_mean = nullptr;
+  if (comp) {      // the transposed layout d2fe_set_superpoint_pca uploads: comp_t [256][pca_dims]
+    std::vector<float> t((size_t)256 * pca_dims);
+    for (int j = 0; j < pca_dims; ++j)
+      for (int c = 0; c < 256; ++c) t[(size_t)c * pca_dims + j] = comp[(size_t)j * 256 + c];
+    HIP_TRY(b.get(&d_comp_t, sizeof(float) * t.size(), t.data()));
+    HIP_TRY(b.get(&d_mean, sizeof(float) * 256, mean));
+  }
+  HIP_TRY(b.get(&d_desc, sizeof(float) * D * n * cap, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_sample_b(d_raw, dstride, dcoff, Hc, Wc, n, d_kps, d_n, cap, d_map, max_slots, d_comp_t, d_mean, comp ? pca_dims : 0, d_desc, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * D * n * cap, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                        const int32_t* slotmap_or_null, int max_slots, float* desc_out) {
+  return debug_sample_b(h, desc_raw, dstride, dcoff, n, Hc, Wc, kps_xy, n_kp, cap, slotmap_or_null, max_slots, nullptr, nullptr, 0, desc_out);
+}
+
+int d2fe_debug_sample_b_pca(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                            const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean, int pca_dims, float* desc_out) {
+  if (!comp || !mean || pca_dims < 1 || pca_dims > 256) return fail(D2FE_ERR_INVALID, "comp, mean and pca_dims in 1..256 are required");
+  return debug_sample_b(h, desc_raw, dstride, dcoff, n, Hc, Wc, kps_xy, n_kp, cap, slotmap_or_null, max_slots, comp, mean, pca_dims, desc_out);
+}
+
+int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,
+                      int32_t* kps_idx, int32_t* n_out) {
+  if (!h || !semi || !kps_xy || !scores || !kps_idx || !n_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || H < 1 || W < 1 || cap < 1 || dist < 0 || (long)H * W > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t hw = (size_t)H * W;
+  const long cand_cap = (long)hw;
+  DevPool b;
+  float *d_semi = nullptr, *d_aconf = nullptr, *d_kps = nullptr, *d_sc = nullptr;
+  int *d_clist = nullptr, *d_cnt = nullptr, *d_ncand = nullptr;
+  unsigned long long* d_cand = nullptr;
+  int32_t *d_idx = nullptr, *d_n = nullptr;
+  HIP_TRY(b.get(&d_semi, sizeof(float) * n * hw, semi));
+  HIP_TRY(b.get(&d_aconf, sizeof(float) * n * hw, nullptr));
+  HIP_TRY(b.get(&d_clist, sizeof(int) * n * hw, nullptr, 0));
+  HIP_TRY(b.get(&d_cand, sizeof(unsigned long long) * n * cand_cap, nullptr));
+  HIP_TRY(b.get(&d_cnt, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get(&d_ncand, sizeof(int) * n, nullptr, 0));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, nullptr));
+  HIP_TRY(b.get(&d_sc, sizeof(float) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_idx, sizeof(int32_t) * n * cap, nullptr));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, nullptr, 0));
+  HIP_TRY(hipDeviceSynchronize());
+  // the sequence run_superpoint issues for variant A
+  HIP_TRY(launch_nms2_a(d_semi, H, W, n, thr, dist, d_aconf, d_clist, d_cand, d_cnt, cand_cap, d_ncand, h->stream));
+  HIP_TRY(launch_select_b(d_cand, d_cnt, cand_cap, n, W, max_kp, cap, 1, nullptr, H, thr, 0, d_kps, d_sc, d_idx, d_n, h->stream));
+  if ((long)H * W > 65536) HIP_TRY(launch_nms2_wrap_fix(d_clist, d_ncand, H, W, n, d_kps, d_idx, d_n, cap, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(kps_xy, d_kps, sizeof(float) * 2 * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(scores, d_sc, sizeof(float) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(kps_idx, d_idx, sizeof(int32_t) * n * cap, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_out, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_graph_count(d2fe_handle h, int* rejected) {
+  if (!h) return fail(D2FE_ERR_INVALID, "null handle");
+  int n = 0, bad = 0;
+  for (auto& kv : h->graphs) { n += kv.second.exec != nullptr; bad += kv.second.bad; }
+  if (rejected) *rejected = bad;
+  return n;
+}
+
+}  // extern "C"
+#endif  // D2FE_DEVTOOLS

@@ -7,7 +7,7 @@
 //      (s_w >= s_w[K-1] - 2 eps, or everything when there are fewer than K), every candidate within 2 eps of a sorted neighbour;
 //   2. collect the distinct 8x8 cells of the marked candidates, in sorted-list order, and hand out the call's crop slots in image order;
 //   3. GATHER an 88x88 crop of the u8 frame around every cell that got a slot (84 pixels is the receptive field of a score cell);
-//      ... the crops run through the direct convolution kernels as one batch of 88x88 images (api.hip) ...
+//      ... the crops run through the direct convolution kernels as one batch of 88x88 images (superpoint_host.hip) ...
 //   4. PATCH the direct scores of the re-evaluated cells onto the candidates and drop those whose final score is not > thr.
 // The ordinary selection (select_b_kernel) then runs on the patched list.  Fixed launch shapes, no host synchronisation.
 #include <limits.h>

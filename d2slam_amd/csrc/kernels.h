@@ -22,7 +22,7 @@ static inline int d2fe_dev_env(const char*, int dflt) { return dflt; }
 // note to nothing: no symbol, no counter, no branch.
 #ifdef D2FE_DEVTOOLS
 #include "../../include/d2fe_debug.h"
-namespace d2fe { void regime_note(int regime); void regime_set(int regime, long long value); }      // api.hip
+namespace d2fe { void regime_note(int regime); void regime_set(int regime, long long value); }      // debug_hooks.hip
 #define D2FE_REGIME(r) ::d2fe::regime_note(r)
 #define D2FE_REGIME_SET(r, v) ::d2fe::regime_set(r, v)
 #else

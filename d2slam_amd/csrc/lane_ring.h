@@ -46,7 +46,7 @@ inline void lane_destroy(LaneBase& L) {
 
 // the end of a pipe's destroy, behind `delete p`: a handle destroyed while this pipe was alive was only MARKED (d2fe_destroy): the last pipe to go releases it
 inline void pipe_gone(d2fe_context* parent) {
-  if (parent->live_pipes.fetch_sub(1) == 1 && parent->doomed.load()) d2fe_destroy(parent);
+  if (parent->life.pipe_gone()) d2fe_destroy(parent);
 }
 
 inline int lane_sync(LaneBase& L) {       // called with the pipe's mutex held for the whole wait

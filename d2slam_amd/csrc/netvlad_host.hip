@@ -372,7 +372,7 @@ int nv_check(d2fe_context* h, int n, int W, int H, int stride) {
 extern "C" {
 
 int d2fe_load_netvlad(d2fe_handle h, const d2fe_netvlad_weights* w) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
+  if (h && h->life.pipes() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
   if (h) graphs_clear(h);
   if (!h || !w || !w->layers || w->n_layers < 1) return fail(D2FE_ERR_INVALID, "null argument");
   if (!w->pre_w || !w->pre_b || !w->assign_w || !w->assign_b || !w->centroids) return fail(D2FE_ERR_INVALID, "null head weights");
@@ -418,8 +418,9 @@ int d2fe_load_netvlad(d2fe_handle h, const d2fe_netvlad_weights* w) {
     const int r = h->nv_run.alloc(*net, B);
     if (r) return r;
     if (net->knobs.stamp_step >= 0) HIP_TRY(hipMalloc(&h->nv_run.stamps, sizeof(unsigned long long) * 32 * 32768));
-    if (!h->nv_s_img) HIP_TRY(hipMalloc(&h->nv_s_img, (size_t)h->cfg.max_width * h->cfg.max_height * B));
-    if (!h->nv_s_out) HIP_TRY(hipMalloc(&h->nv_s_out, sizeof(float) * 8192 * B));
+    HostStage& stg = *h->stage;
+    if (!stg.nv_s_img) HIP_TRY(stg.dev(&stg.nv_s_img, (size_t)h->cfg.max_width * h->cfg.max_height * B));
+    if (!stg.nv_s_out) HIP_TRY(stg.dev(&stg.nv_s_out, sizeof(float) * 8192 * B));
     return D2FE_OK;
   }();
   if (rc) { h->nv_run.release(); return rc; }
@@ -484,7 +485,7 @@ int d2fe_debug_netvlad_plan(const d2fe_nv_layer* layers, int n_layers, int proj_
 #endif  // D2FE_DEVTOOLS
 
 int d2fe_set_netvlad_pca(d2fe_handle h, const float* comp, const float* mean, int m) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
+  if (h && h->life.pipes() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
   if (h) graphs_clear(h);
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
   if (!h->nv_net) return fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
@@ -525,18 +526,19 @@ int d2fe_netvlad_batch(d2fe_handle h, const uint8_t* gray, int n, int width, int
   if (!gray || !out) return fail(D2FE_ERR_INVALID, "null pointer");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   hipStream_t s = h->stream;
-  rc = upload_frames(h, h->nv_s_img, gray, n, width, height, stride, image_stride, s);
+  HostStage& stg = *h->stage;
+  rc = upload_frames(h, stg.nv_s_img, gray, n, width, height, stride, image_stride, s);
   if (rc) return rc;
   rc = run_cached(h, {2, n, width, height, (long)h->nv_net->pca_m, 0}, s, [&](hipStream_t st) {
-    return run_netvlad(h, h->nv_s_img, n, width, height, width, (size_t)width * height, h->nv_s_out, st);
+    return run_netvlad(h, stg.nv_s_img, n, width, height, width, (size_t)width * height, stg.nv_s_out, st);
   });
   if (rc) return rc;
   const int G = d2fe_netvlad_dim(h);
   const size_t bytes = sizeof(float) * (size_t)G * n;
-  const bool pinned = h->use_pinned && h->pin_out && bytes <= h->pin_out_bytes;      // one D2H into the pinned staging, or straight into `out`
-  HIP_TRY(hipMemcpyAsync(pinned ? (void*)h->pin_out : (void*)out, h->nv_s_out, bytes, hipMemcpyDeviceToHost, s));
+  const bool pinned = h->use_pinned && stg.pin_out && bytes <= stg.pin_out_bytes;      // one D2H into the pinned staging, or straight into `out`
+  HIP_TRY(hipMemcpyAsync(pinned ? (void*)stg.pin_out : (void*)out, stg.nv_s_out, bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (pinned) memcpy(out, h->pin_out, bytes);
+  if (pinned) memcpy(out, stg.pin_out, bytes);
   return D2FE_OK;
 }
 

@@ -610,7 +610,7 @@ int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   d2fe_pipe_s* p = new d2fe_pipe_s();
   p->parent = h; p->cfg = *cfg;
-  h->live_pipes.fetch_add(1);        // from here on d2fe_pipe_destroy (every failure path below goes through it or through `delete p` + the decrement) gives it back
+  h->life.pipe_added();        // from here on d2fe_pipe_destroy (every failure path below goes through it or through `delete p` + pipe_gone) gives it back
   p->M = M;
   p->lk = cfg->lr_lk != 0;
   p->sp_lk = cfg->sp_lk != 0;
@@ -627,8 +627,8 @@ int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2
   p->tinfo.resize((size_t)2 * p->K * C + C);
   {
     int rc = check_geometry(h, 1, p->W, p->H, p->W, p->cap);
-    if (rc) { h->live_pipes.fetch_sub(1); delete p; return rc; }
-    if (cfg->netvlad) { rc = nv_check(h, 1, p->W, p->H, p->W); if (rc) { h->live_pipes.fetch_sub(1); delete p; return rc; } }
+    if (rc) { delete p; pipe_gone(h); return rc; }
+    if (cfg->netvlad) { rc = nv_check(h, 1, p->W, p->H, p->W); if (rc) { delete p; pipe_gone(h); return rc; } }
   }
   const size_t NL = (size_t)p->F * C;
   const int rc = [&]() -> int {

@@ -393,7 +393,7 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
   HIP_TRY(hipSetDevice(h->cfg.device_id));
   d2fe_quad_pipe_s* p = new d2fe_quad_pipe_s();
   p->parent = h; p->cfg = *cfg;
-  h->live_pipes.fetch_add(1);        // the stereo pipes' accounting: d2fe_quad_pipe_destroy (every failure path below goes through it) gives it back
+  h->life.pipe_added();        // the stereo pipes' accounting: d2fe_quad_pipe_destroy (every failure path below goes through it) gives it back
   p->K = cfg->lanes; p->Q = cfg->quads; p->NI = NI; p->RW = cfg->raw_width; p->RH = cfg->raw_height; p->W = cfg->width; p->H = cfg->height;
   p->cap = cfg->cap; p->D = d2fe_desc_dim(h); p->G = cfg->netvlad ? d2fe_netvlad_dim(h) : 0;
   p->n_nb = cfg->match_neighbour ? 4 * p->Q : 0; p->n_pr = cfg->match_prev ? 4 * p->Q : 0; p->NP = p->n_nb + p->n_pr;

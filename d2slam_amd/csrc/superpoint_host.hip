@@ -335,7 +335,7 @@ int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap) {
 extern "C" {
 
 int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
+  if (h && h->life.pipes() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
   if (h) graphs_clear(h);
   if (!h || !w) return fail(D2FE_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device_id));
@@ -366,7 +366,7 @@ int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
 }
 
 int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean, int pca_dims) {
-  if (h && h->live_pipes.load() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
+  if (h && h->life.pipes() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before loading weights or PCA matrices");
   if (h) graphs_clear(h);
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
   if (pca_dims < 0 || pca_dims > 256 || (pca_dims > 0 && (!comp || !mean))) return fail(D2FE_ERR_INVALID, "bad PCA arguments");

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 
 def block_words(cap: int, netvlad_dim: int, desc_dim: int = 256) -> int:
-    """Mirror of d2fe_block_words_d (api.hip): float words of one block of desc_dim-float descriptors."""
+    """Mirror of d2fe_block_words_d (next_host.hip): float words of one block of desc_dim-float descriptors."""
     return (cap * (desc_dim + 3) + netvlad_dim + 1 + 255) // 256 * 256
 
 

@@ -41,7 +41,7 @@ D2FE_API int d2fe_debug_netvlad_plan(const d2fe_nv_layer* layers, int n_layers, 
  * conv's), 2 nv_xblock_kernel (stride 1 or 2). */
 D2FE_API int d2fe_debug_netvlad_tile(int kind, int Ho, int Wo, int stride, int* th, int* tw);
 /* The host-side weight packing of the NetVLAD block kernels (needs no GPU; tests/test_netvlad_pack_cpu.py): kind 0..5 = expand / depthwise + project
- * records of nv_pblock_kernel, nv_xblock_kernel, nv_tail_kernel (see csrc/api.hip).  Returns the number of floats written or <0. */
+ * records of nv_pblock_kernel, nv_xblock_kernel, nv_tail_kernel (see csrc/debug_hooks.hip).  Returns the number of floats written or <0. */
 D2FE_API long d2fe_debug_pack_netvlad(int kind, const float* we, const float* be, const float* wd, const float* bd, const float* wp, int cin, int chid,
                                       int cout, float* out, long max_floats);
 D2FE_API long d2fe_debug_pack_wino(const float* weight /*[cout][cin][3][3]*/, int cout, int cin, float* out, long max_floats);

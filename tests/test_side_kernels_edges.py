@@ -11,7 +11,7 @@ import functools
 import numpy as np
 import pytest
 
-DB_MAXK = 1024                            # csrc/api.hip
+DB_MAXK = 1024                            # csrc/next_host.hip
 DIMS = (4, 260, 1024, 4100, 8192)
 NTOTALS = (1, 3, 5, 1029)                 # 1029: above the 1024-thread stride of the top-k scan, no multiple of the 4 rows of a workgroup
 BATCHED = ((8, 1024), (8, 2048), (4, 4096), (2, 8192))      # (nq, dim): the most queries a call takes; the others stage exactly 64 KiB
