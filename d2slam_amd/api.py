@@ -117,6 +117,20 @@ class _TrackParams(C.Structure):
                 ("reserved", C.c_int32), ("feature_min_dist", C.c_double)]
 
 
+class _FlowParams(C.Structure):
+    """d2fe_flow_params: the parameters of the flow landmarks (enable_lk_optical_flow without sp_track_use_lk)"""
+    _fields_ = [("struct_size", C.c_int32), ("superpoint", C.c_int32), ("track", _TrackParams), ("fast_cols", C.c_int32), ("fast_rows", C.c_int32),
+                ("fast_threshold", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _PipeFlowResult(C.Structure):
+    """d2fe_pipe_flow_result: the flow lists of a ticket (d2fe_pipe_flow_enable)"""
+    _fields_ = [("frames", C.c_int32), ("cap_tracks", C.c_int32), ("list_words", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p), ("lack", C.c_void_p),
+                ("num", C.c_void_p), ("n_cand", C.c_void_p), ("pts_xy", C.c_void_p), ("id", C.c_void_p), ("src", C.c_void_p), ("right_xy", C.c_void_p),
+                ("right_status", C.c_void_p), ("depth_mm", C.c_void_p)]
+
+
 class _PipeTrackResult(C.Structure):
     _fields_ = [("frames", C.c_int32), ("cap_tracks", C.c_int32), ("desc_dim", C.c_int32), ("list_words", C.c_int32),
                 ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p),
@@ -236,6 +250,8 @@ EXPORTS = [
     "d2fe_lk_stereo_workspace_bytes", "d2fe_lk_track_stereo_device", "d2fe_pipe_lk_result_get",
     "d2fe_track_default_params", "d2fe_lk_carry_list_bytes", "d2fe_lk_carry_list_offset", "d2fe_lk_carry_step_device", "d2fe_pipe_track_result_get",
     "d2fe_pipe_set_track_params", "d2fe_pipe_camera_default", "d2fe_pipe_create_camera", "d2fe_pipe_submit_depth", "d2fe_pipe_depth_result_get", "d2fe_depth_at_device", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
+    "d2fe_flow_default_params", "d2fe_lk_flow_list_bytes", "d2fe_lk_flow_list_offset", "d2fe_lk_flow_scratch_bytes", "d2fe_detect_fast_device", "d2fe_lk_flow_step_device",
+    "d2fe_pipe_flow_enable", "d2fe_pipe_flow_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -409,6 +425,20 @@ def _open_library(path, dev):
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_lk_carry_neighbour_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_int,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_flow_default_params.argtypes = [C.c_void_p]
+        lib.d2fe_flow_default_params.restype = None
+        lib.d2fe_lk_flow_list_bytes.argtypes = [C.c_int]
+        lib.d2fe_lk_flow_list_bytes.restype = C.c_size_t
+        lib.d2fe_lk_flow_list_offset.argtypes = [C.c_int, C.c_int]
+        lib.d2fe_lk_flow_list_offset.restype = C.c_long
+        lib.d2fe_lk_flow_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.d2fe_lk_flow_scratch_bytes.restype = C.c_size_t
+        lib.d2fe_detect_fast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_lk_flow_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_flow_enable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_flow_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_quad_track_enable.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_quad_track_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_set_track_params.argtypes = [C.c_void_p, C.c_void_p]
@@ -1089,6 +1119,10 @@ class StereoPipe(_Owned):
     the left one, matchKNN L<->R and L<->previous L) for `frames` stereo frames per submit with up to `lanes` submits in flight.
     lr_lk=True (needs match_lr=False): the reference's default stereo path (lr_match_use_lk) -- SuperPoint on the left images only, every left keypoint
     tracked into the right image with pyramidal LK inside the pass; wait() then also returns "lk_pts" [F, cap, 2] and "lk_status" [F, cap].
+    flow_lk=True | "only" (d2fe_pipe_flow_enable; needs lr_lk=True or mono=True, excludes sp_lk; flow_params: a dict of flow_params() keywords or a _FlowParams): the
+    flow landmarks, the FAST-replenished LK list, beside SuperPoint or ("only": superpoint = 0, needs netvlad=False, match_prev=False) as the whole front end.  wait()
+    then also returns per frame f "flow_n", "flow_n_tracked_in", "flow_n_lost", "flow_n_removed_near", "flow_n_new", "flow_lack", "flow_num", "flow_n_cand" [F],
+    "flow_pts" [F, cap_tracks, 2], "flow_id" / "flow_src" [F, cap_tracks], "flow_right_pts" / "flow_right_status" (None on a mono pipe), "flow_depth_mm" (None without depth).
     sp_lk=True (needs lr_lk=True; together the reference's defaults, sp_track_use_lk): the LK-carried landmark list of D2FeatureTracker::trackLK is kept on the
     device and carried across frames, passes and lanes; track_params (a dict of d2fe_track_params fields, or track_params()) replaces the reference's defaults.
     wait() then returns, instead of lk_*, per frame f: "track_n" [F], "track_pts" [F, cap_tracks, 2], "track_id" / "track_src" / "track_kp" [F, cap_tracks],
@@ -1103,7 +1137,7 @@ class StereoPipe(_Owned):
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
                  ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
-                 lr_lk=False, sp_lk=False, track_params=None, mono=False, depth=False):
+                 lr_lk=False, sp_lk=False, track_params=None, mono=False, depth=False, flow_lk=False, flow_params=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _PipeConfig()
@@ -1130,12 +1164,18 @@ class StereoPipe(_Owned):
             _check(self._lib.d2fe_pipe_create_camera(fe.handle, C.byref(c), C.byref(cam), C.byref(self._p)))
         else:
             _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
-        if track_params is not None:
-            try:
+        self._flow = False
+        self._flow_res = _PipeFlowResult()
+        try:
+            if track_params is not None:
                 self.set_track_params(track_params)
-            except Exception:
-                self.close()
-                raise
+            if flow_lk:
+                if flow_lk not in (True, "only"):
+                    raise ValueError('flow_lk is False, True (beside SuperPoint) or "only" (superpoint = 0)')
+                self.flow_enable(flow_params, superpoint=0 if flow_lk == "only" else 1)
+        except Exception:
+            self.close()
+            raise
         if not hasattr(fe, "_pipes"):
             import weakref
             fe._pipes = weakref.WeakSet()
@@ -1274,6 +1314,17 @@ class StereoPipe(_Owned):
             lk = self.lk_result_raw(ticket)
             out["lk_pts"] = view(lk.pts_xy, (F, cap, 2), np.float32)
             out["lk_status"] = np.frombuffer((C.c_uint8 * (F * cap)).from_address(lk.status), dtype=np.uint8).reshape(F, cap)
+        if self._flow:
+            t = self.flow_result_raw(ticket)
+            T, lw, base = t.cap_tracks, t.list_words, t.n          # the header of frame 0's list is the lowest address of the lists
+            words = np.frombuffer((C.c_int32 * (F * lw)).from_address(base), dtype=np.int32).reshape(F, lw)
+            flist = lambda ptr, shape, dt: words[:, (ptr - base) // 4:(ptr - base) // 4 + int(np.prod(shape))].view(dt).reshape((F,) + tuple(shape))
+            for k in ("n", "n_tracked_in", "n_lost", "n_removed_near", "n_new", "lack", "num", "n_cand"):
+                out["flow_" + k] = flist(getattr(t, k), (1,), np.int32)[:, 0]
+            out["flow_pts"] = flist(t.pts_xy, (T, 2), np.float32); out["flow_id"] = flist(t.id, (T,), np.int32); out["flow_src"] = flist(t.src, (T,), np.int32)
+            out["flow_right_pts"] = view(t.right_xy, (F, T, 2), np.float32)
+            out["flow_right_status"] = np.frombuffer((C.c_uint8 * (F * T)).from_address(t.right_status), dtype=np.uint8).reshape(F, T) if t.right_status else None
+            out["flow_depth_mm"] = np.frombuffer((C.c_uint16 * (F * T)).from_address(t.depth_mm), dtype=np.uint16).reshape(F, T) if t.depth_mm else None
         if self._depth:
             d = self.depth_result_raw(ticket)
             out["kp_depth_mm"] = np.frombuffer((C.c_uint16 * (F * cap)).from_address(d.kp_depth_mm), dtype=np.uint16).reshape(F, cap)
@@ -1291,6 +1342,19 @@ class StereoPipe(_Owned):
         _check(self._lib.d2fe_pipe_lk_result_get(self._p, C.c_int64(ticket), C.byref(self._lk_res)))
         return self._lk_res
 
+
+    def flow_enable(self, fp=None, superpoint=None):
+        """d2fe_pipe_flow_enable: once, before the first submit (fp: a dict of flow_params() keywords, a _FlowParams, or None for the reference's defaults)"""
+        fp = flow_params(**fp) if isinstance(fp, dict) else fp if fp is not None else flow_params()
+        if superpoint is not None:
+            fp.superpoint = int(superpoint)
+        _check(self._lib.d2fe_pipe_flow_enable(self._p, C.byref(fp)))
+        self._flow = True
+
+    def flow_result_raw(self, ticket):
+        """d2fe_pipe_flow_result_get: the flow lists of a ticket that wait() has returned (D2FE_ERR_UNSUPPORTED without the mode)"""
+        _check(self._lib.d2fe_pipe_flow_result_get(self._p, C.c_int64(ticket), C.byref(self._flow_res)))
+        return self._flow_res
 
     def track_result_raw(self, ticket):
         """d2fe_pipe_track_result_get: the landmark lists of a ticket that wait() has returned (sp_lk pipes)"""
@@ -1640,6 +1704,79 @@ def lk_carry_neighbour(fe: FrontEnd, d_pyr, pyr_stride, quads, width, height, un
     tp = tp if tp is not None else track_params()
     _check(fe._lib.d2fe_lk_carry_neighbour_device(fe.handle, d_pyr, int(pyr_stride), int(quads), int(width), int(height), float(undistort_fov), d_lists,
                                                   int(list_stride), int(desc_dim), C.byref(tp), d_nb_xy, d_nb_status, stream))
+
+
+# ---- the flow landmarks (enable_lk_optical_flow without sp_track_use_lk): the FAST-replenished LK list on the device ----
+FLOW_FIELDS = ["hdr", "pts", "id", "src", "trk_xy", "trk_status"]      # the fields of LKC_FIELDS a flow list has
+
+
+def flow_params(**kw):
+    """d2fe_flow_params with the reference's defaults (d2fe_flow_default_params); keywords replace its own fields (superpoint, fast_cols, fast_rows,
+    fast_threshold) or those of its d2fe_track_params (total_feature_num, levels, win, iters, near_lk_thread_rate, feature_min_dist)"""
+    fp = _FlowParams()
+    load_library().d2fe_flow_default_params(C.byref(fp))
+    for k, v in kw.items():
+        if k in ("superpoint", "fast_cols", "fast_rows", "fast_threshold"):
+            setattr(fp, k, int(v))
+        elif k in dict(_TrackParams._fields_) and k != "reserved":
+            setattr(fp.track, k, v)
+        else:
+            raise TypeError("d2fe_flow_params has no field %r" % k)
+    return fp
+
+
+def lk_flow_cap_tracks(fp):
+    """the capacity of the list d2fe_lk_flow_step_device keeps for these parameters: max(total_feature_num, 1)"""
+    return max(int(fp.track.total_feature_num), 1)
+
+
+def lk_flow_list_bytes(cap_tracks):
+    """d2fe_lk_flow_list_bytes (host arithmetic): one flow-list block"""
+    return int(load_library().d2fe_lk_flow_list_bytes(int(cap_tracks)))
+
+
+def lk_flow_list_offset(cap_tracks, field):
+    """d2fe_lk_flow_list_offset: 32-bit words from the block base to `field` (a name of LKC_FIELDS or its index); -1 for a field a flow list lacks"""
+    return int(load_library().d2fe_lk_flow_list_offset(int(cap_tracks), LKC_FIELDS.index(field) if isinstance(field, str) else int(field)))
+
+
+def lk_flow_scratch_bytes(width, height, cap_tracks, cols=3, rows=4):
+    """d2fe_lk_flow_scratch_bytes (host arithmetic): score map + candidate pool of the device detector"""
+    return int(load_library().d2fe_lk_flow_scratch_bytes(int(width), int(height), int(cap_tracks), int(cols), int(rows)))
+
+
+def lk_flow_list_views(block, cap_tracks):
+    """dict of numpy views into a HOST copy of one flow-list block (lk_flow_list_bytes bytes), and the header's counts by name"""
+    w = np.ascontiguousarray(block).view(np.int32).reshape(-1)
+    T = int(cap_tracks)
+    shapes = {"hdr": ((64,), np.int32), "pts": ((T, 2), np.float32), "id": ((T,), np.int32), "src": ((T,), np.int32), "trk_xy": ((T, 2), np.float32)}
+    out = {}
+    for k, (shape, dt) in shapes.items():
+        o = lk_flow_list_offset(T, k)
+        out[k] = w[o:o + int(np.prod(shape))].view(dt).reshape(shape)
+    o = lk_flow_list_offset(T, "trk_status")
+    out["trk_status"] = w[o:o + (T + 3) // 4].view(np.uint8)[:T]
+    h = out["hdr"]
+    out.update(n=int(h[0]), n_tracked_in=int(h[1]), n_lost=int(h[2]), n_removed_near=int(h[3]), n_new=int(h[4]), next_id=int(h[6]), lack=int(h[7]), num=int(h[8]),
+               n_cand=int(h[9]))
+    return out
+
+
+def detect_fast_device(fe: FrontEnd, d_pyr, width, height, d_features, cap_tracks, d_xy, d_response, cap, d_n, d_scratch, cols=3, rows=4, threshold=10, stream=None):
+    """detectFastByRegion without the host (d2fe_detect_fast_device); arguments are raw device addresses (ints): level 0 of a pyramid, ONE int32 `features`,
+    the outputs xy [cap, 2] float32, response [cap] int32 (or None), n [1] int32, and lk_flow_scratch_bytes of 16-byte aligned scratch.  Only enqueues on `stream`."""
+    _check(fe._lib.d2fe_detect_fast_device(fe.handle, d_pyr, int(width), int(height), d_features, int(cap_tracks), int(cols), int(rows), int(threshold), d_xy,
+                                           d_response or None, int(cap), d_n, d_scratch, stream))
+
+
+def lk_flow_step_device(fe: FrontEnd, d_prev_pyr, d_cur_pyr, width, height, d_prev_list, d_cur_list, d_kps_xy, d_n_kp, kp_cap, d_next_id, d_scratch, fp=None,
+                        stream=None):
+    """One frame of the flow landmarks on the device (d2fe_lk_flow_step_device); arguments are raw device addresses (ints), as for lk_carry_step: the pyramids, the
+    previous and the current flow-list block (zeroed once), the keypoints extract_device left for the current frame (or None / kp_cap = 0), one int32 next_id,
+    the detector's scratch.  Five launches, only enqueued on `stream`."""
+    fp = fp if fp is not None else flow_params()
+    _check(fe._lib.d2fe_lk_flow_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(width), int(height), d_prev_list, d_cur_list, d_kps_xy or None, d_n_kp or None,
+                                            int(kp_cap), C.byref(fp), d_next_id, d_scratch, stream))
 
 
 class _LKPair(C.Structure):

@@ -1,6 +1,6 @@
 // context.h -- the device context behind d2fe_handle and the launch sequences shared by the translation units that implement
 // include/d2fe.h (api.hip: handle lifecycle and the extract entry points; superpoint_host.hip: SuperPoint's host side; netvlad_host.hip: NetVLAD's host side; match_host.hip: the
-// matcher's; next_host.hip: the "next rows"; debug_hooks.hip: the development library's hooks on injected tensors; lk.hip, lk_carry.hip: the trackers;
+// matcher's; next_host.hip: the "next rows"; debug_hooks.hip: the development library's hooks on injected tensors; lk.hip, lk_carry.hip, lk_flow.hip: the trackers;
 // pipe.hip, quad_pipe.hip: the frames-in-flight pipelines; exchange.hip, quad_exchange.hip, loop.hip, window.hip: the consumers behind them).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -322,8 +322,12 @@ void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool
 // lk_carry.hip, for the pipe's sp_lk mode: what d2fe_lk_carry_step_device would refuse (nullptr: nothing), and trackLK(left, right) over the lists of a pass --
 // n_frames list blocks, consecutive in d_lists, against the pass's stereo workspace (d2fe_lk_track_stereo_device), ONE launch
 const char* lk_carry_check_params(const d2fe_track_params* tp);
+// (desc_dim = 0: flow lists, cap_tracks = max(total_feature_num, 1))
 int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int width, int height, const d2fe_track_params& tp, const float* d_lists, int desc_dim,
                           float* d_right_xy, uint8_t* d_right_status, hipStream_t s);
+
+// lk_flow.hip, for the pipe's flow mode: what d2fe_lk_flow_step_device would refuse for these parameters and this geometry, as a message (nullptr: nothing)
+const char* lk_flow_check_params(const d2fe_flow_params* fp, int width, int height);
 
 // lk.hip, for the mono pipe's sp_lk mode: the pyramids of n_frames images alone (no right images), image f's at f * (half of d2fe_lk_stereo_workspace_bytes(1, ..))
 int lk_pyramids_launch(d2fe_context* h, const uint8_t* d_img, int n_frames, int width, int height, int stride, size_t image_stride, int levels, void* d_workspace,

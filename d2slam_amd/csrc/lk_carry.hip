@@ -21,36 +21,11 @@
 #include "context.h"
 #include "kernels.h"
 #include "lk_device.h"
+#include "lk_list_device.h"
 
 namespace d2fe {
 
 namespace {
-
-constexpr int LKC_MAX = 1024;      // cap_tracks the finishing workgroup's LDS is sized for
-
-// list block layout (words from the block base; include/d2fe.h)
-struct CarryLayout {
-  int cap, D;
-  long off[D2FE_LKC_FIELDS];
-  long words;
-};
-__host__ __device__ inline long lkc_up64(long w) { return (w + 63) / 64 * 64; }
-inline CarryLayout carry_layout(int cap, int D) {
-  CarryLayout l{};
-  l.cap = cap; l.D = D;
-  long o = 0;
-  l.off[D2FE_LKC_HDR] = o; o += 64;
-  l.off[D2FE_LKC_PTS] = o; o += lkc_up64(2L * cap);
-  l.off[D2FE_LKC_ID] = o; o += lkc_up64(cap);
-  l.off[D2FE_LKC_SRC] = o; o += lkc_up64(cap);
-  l.off[D2FE_LKC_KP] = o; o += lkc_up64(cap);
-  l.off[D2FE_LKC_SCORES] = o; o += lkc_up64(cap);
-  l.off[D2FE_LKC_DESC] = o; o += lkc_up64((long)cap * D);
-  l.off[D2FE_LKC_TRK_XY] = o; o += lkc_up64(2L * cap);
-  l.off[D2FE_LKC_TRK_STATUS] = o; o += lkc_up64((cap + 3) / 4);
-  l.words = o;
-  return l;
-}
 
 struct LkCarryArgs {
   const uint8_t* prev_pyr; const uint8_t* cur_pyr;
@@ -64,25 +39,6 @@ struct LkCarryArgs {
   int* next_id;
 };
 
-// cv::norm(a - b) < thr for Point2f a, b: float differences, sqrt((double)dx * dx + (double)dy * dy) < thr.  The products are exact in double and the sum is rounded once,
-// so s is the reference's number whatever its compiler contracts.  sqrt is correctly rounded and monotonic: s >= thr^2 (real) gives sqrt(s) >= thr, and an s below
-// thr^2 by more than a few ulps cannot round up to thr -- only the band around thr^2 needs the double-precision square root itself
-__device__ __forceinline__ bool nearer(float ax, float ay, float bx, float by, double thr, double lo, double hi) {
-  const float dx = ax - bx, dy = ay - by;
-  const double s = (double)dx * (double)dx + (double)dy * (double)dy;
-  if (s < lo) return true;
-  if (s > hi) return false;
-  return __builtin_sqrt(s) < thr;
-}
-
-// LDS writes of one lane, read by the other lanes of the SAME wave in the next step: the wave runs in lockstep and its LDS operations complete in order; this keeps
-// the compiler from moving accesses across the point
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Steps b-e for one list, run by the workgroup whose ticket said it arrived last (256 threads, the list's scratch in the caller's LDS).  QUAD (the four-camera launch,
 // lk_carry_quad_step_kernel): the ids of the NEW entries, header word 6 and *next_id belong to the launch's last finisher, which knows the new entries of the lower
 // cameras; they are left alone here, and so is header word 7 of camera 0's list (keep7), the quad-level ticket
@@ -95,42 +51,9 @@ __device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, f
   uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
   // ---- b-d on wave 0
   if (wave == 0) {
-    // b. reduceVector: order-preserving compaction by status, 64 entries a round
+    // b-c. reduceVector and removeNearPoints (lk_list_device.h, shared with the flow list)
     int cnt = 0;
-    for (int base = 0; base < n_prev; base += 64) {
-      const int i = base + lane;
-      bool ok = false;
-      float x = 0.f, y = 0.f;
-      if (i < n_prev) {
-        ok = __hip_atomic_load(trk_st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        x = __hip_atomic_load(trk_xy + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        y = __hip_atomic_load(trk_xy + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const unsigned long long bal = __ballot(ok);
-      if (ok) {
-        const int k = cnt + __popcll(bal & ((1ull << lane) - 1ull));
-        s_x[k] = x; s_y[k] = y; s_src[k] = i; s_kp[k] = -1;
-      }
-      cnt += __popcll(bal);
-    }
-    wave_lds_sync();
-    // c. removeNearPoints, in place (the kept prefix never passes the candidate)
-    int m = 0;
-    {
-      const double thr = c.near_thr, t2 = thr * thr, lo = t2 * (1.0 - 1e-12), hi = t2 * (1.0 + 1e-12);
-      for (int i = 0; i < cnt; ++i) {
-        const float px = s_x[i], py = s_y[i];
-        const int src = s_src[i];
-        bool hit = false;
-        for (int j = lane; j < m; j += 64) hit = hit || nearer(px, py, s_x[j], s_y[j], thr, lo, hi);
-        if (__ballot(hit) == 0ull) {
-          wave_lds_sync();        // every lane has read entry i before slot m <= i is rewritten
-          if (lane == 0) { s_x[m] = px; s_y[m] = py; s_src[m] = src; }
-          ++m;
-          wave_lds_sync();
-        }
-      }
-    }
+    const int m = list_reduce_prune(trk_xy, trk_st, n_prev, c.near_thr, s_x, s_y, s_src, lane, cnt);
     // d. replenish from the frame's SuperPoint keypoints
     int len = m;
     {
@@ -166,7 +89,7 @@ __device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, f
   const float* pdesc = c.prev + c.lay.off[D2FE_LKC_DESC];
   for (int k = tid; k < cap; k += 256) {
     const bool live = k < len, old = k < m;
-    const int sk = live ? s_src[k] : 0, kk = live ? s_kp[k] : 0;
+    const int sk = live ? s_src[k] : 0, kk = !live ? 0 : old ? -1 : s_kp[k];
     pts[2 * k] = live ? s_x[k] : 0.f; pts[2 * k + 1] = live ? s_y[k] : 0.f;
     id[k] = !live ? 0 : old ? pid[sk] : id0 + (k - m);
     src[k] = sk; kp[k] = kk;
@@ -270,10 +193,7 @@ __global__ __launch_bounds__(256) void lk_carry_right_kernel(LkCarryRightArgs s)
 }
 
 void pyr_geometry(LkPairDev& P, int width, int height, int levels, size_t* total) {
-  int o = 0;
-  for (int l = 0, w = width, hh = height; l <= levels; ++l) { P.off[l] = o; P.ws[l] = w; P.hs[l] = hh; o += w * hh; w = (w + 1) / 2; hh = (hh + 1) / 2; }
-  P.levels = levels; P.w = width; P.h = height; P.type = 0; P.move_cols = 0.f;
-  if (total) *total = (size_t)o;
+  lk_pyr_geometry(P, width, height, levels, total);
 }
 
 
@@ -422,7 +342,7 @@ int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int 
                           float* d_right_xy, uint8_t* d_right_status, hipStream_t s) {
   LkCarryRightArgs r{};
   pyr_geometry(r.P, width, height, tp.levels, &r.total);
-  const CarryLayout lay = carry_layout(tp.total_feature_num + 1, desc_dim);
+  const CarryLayout lay = desc_dim > 0 ? carry_layout(tp.total_feature_num + 1, desc_dim) : carry_layout(tp.total_feature_num > 1 ? tp.total_feature_num : 1, 0);
   r.ws = ws; r.n_frames = n_frames; r.cap = lay.cap; r.win = tp.win; r.iters = tp.iters;
   r.lists = d_lists; r.list_words = lay.words; r.off_pts = lay.off[D2FE_LKC_PTS];
   r.cur_pts = d_right_xy; r.status = d_right_status;

@@ -1,5 +1,6 @@
 // lk_device.h -- the device functions of the sparse pyramidal LK tracker (cv::cuda::SparsePyrLKOpticalFlow, evaluation order of oracle/d2fe_oracle_lk.c), shared by
-// the translation units that launch them: lk.hip (d2fe_lk_track*, the stereo tracks) and lk_carry.hip (the LK-carried landmark list).  One 64-lane wave per point.  Internal.
+// the translation units that launch them: lk.hip (d2fe_lk_track*, the stereo tracks), lk_carry.hip (the LK-carried landmark list) and lk_flow.hip (the flow list).
+// One 64-lane wave per point.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,435 @@
+// lk_flow.hip -- the flow landmarks of enable_lk_optical_flow without sp_track_use_lk on the device (include/d2fe.h, d2fe_lk_flow_step_device, d2fe_detect_fast_device).
+//   D2FeatureTracker::trackLK(frame)   d2frontend/src/d2featuretracker.cpp:472-621: track the previous list (opticalflowTrackPyr, opticaltrack_utils.cpp:173-279), reduceVector,
+//                                      removeNearPoints, then detectPoints(..., use_fast = true) (:375-442) against landmarks2D() = the SuperPoint keypoints + the tracked entries
+//   detectFastByRegion                 opticaltrack_utils.cpp:444-493: FAST per region, sorted by response, the first `features`
+//
+// MI355X mapping.  One frame = FIVE launches, whatever the list holds:
+//   1. lk_flow_step_kernel   one 64-lane wave per entry of the previous list tracks it (lk_bidir, lk_device.h); the last workgroup to arrive runs b-c (list_reduce_prune,
+//                            lk_list_device.h: the code of the SuperPoint list), writes the tracked entries and decides `lack` and `num` into the list header
+//   2. fast_clear_kernel     score map and candidate count to zero
+//   3. fast_region_kernel    } fast_device.h, the kernels of d2fe_detect_fast_by_region; `features` is header word `num`, read on the device
+//   4. fast_nonmax_kernel    }
+//   5. lk_flow_merge_kernel  ONE workgroup: exact top-`num` of the candidate pool in (response, order) order, the distance filter of detectPoints, the new entries
+// Launches 2-5 read `num` first and return when it is 0 (the steady state: the list is full enough), so a frame that does not detect costs launch 1 and four empty grids.
+// The host sort of d2fe_detect_fast_by_region becomes fast_select_sorted: the candidates carry a unique key of 40 significant bits -- the response in bits 32..39 (a FAST score is at most 254, so 8 bits hold it) above ~order in bits 0..31 --
+// and five 8-bit histogram passes, which cover exactly bits 0..39, find the K-th largest key over the pool exactly; the K candidates at or above it are compacted into LDS (ballot + one LDS atomic per wave) and each
+// is ranked by counting the larger keys (K <= 2048: 2 x 2048 broadcast LDS reads a thread).  The merge then tests every selected candidate against the keypoints and the
+// tracked entries in parallel (a thread per candidate) and only the test against the candidates accepted before it runs in order, on one wave, as the replenish loop of
+// lk_carry.hip does.  LDS of launch 5: 16 KB keys + 8 KB indices + 8 KB order + 8 KB list + 2 KB flags + 1 KB histogram = 43 KB of the CU's 160 KB.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/d2fe.h"
+#include "context.h"
+#include "kernels.h"
+#include "fast_device.h"
+#include "lk_device.h"
+#include "lk_list_device.h"
+
+namespace d2fe {
+
+namespace {
+
+constexpr int FLOW_KMAX = 2 * LKC_MAX;      // candidates the selection keeps: num <= 2 * total_feature_num
+
+// header words of a flow list behind the seven of the carry list (include/d2fe.h)
+enum { FLOW_HDR_LACK = 7, FLOW_HDR_NUM = 8, FLOW_HDR_CAND = 9 };
+
+struct FlowScratch {
+  int* score; int4* pool; int* count;
+  int pool_cap;
+  size_t bytes;
+};
+inline FlowScratch flow_scratch(void* base, int width, int height, int cap_tracks, int cols, int rows) {
+  FlowScratch f{};
+  const size_t sbytes = (sizeof(int) * (size_t)width * height + 15) / 16 * 16;      // keeps the int4 pool 16-byte aligned
+  f.pool_cap = cols * rows * 2 * cap_tracks;
+  char* b = static_cast<char*>(base);
+  f.score = reinterpret_cast<int*>(b);
+  f.pool = reinterpret_cast<int4*>(b + sbytes);
+  f.count = reinterpret_cast<int*>(b + sbytes + sizeof(int4) * (size_t)f.pool_cap);
+  f.bytes = sbytes + sizeof(int4) * (size_t)f.pool_cap + 16;
+  return f;
+}
+
+__global__ __launch_bounds__(256) void fast_clear_kernel(const int* __restrict__ d_features, int4* __restrict__ score4, int n4, int* __restrict__ count) {
+  if (d_features[0] <= 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n4) score4[i] = int4{0, 0, 0, 0};
+  if (i == 0) count[0] = 0;
+}
+
+// 40 significant bits (response <= 254 in bits 32..39, ~order in bits 0..31): larger = earlier, response descending, then order ascending
+__device__ __forceinline__ unsigned long long fast_key(const int4& c) {
+  return ((unsigned long long)(unsigned)c.z << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c.w);
+}
+
+// LDS of the selection (one workgroup of 1024 threads)
+struct SelectLds {
+  unsigned long long key[FLOW_KMAX];
+  int idx[FLOW_KMAX], ord[FLOW_KMAX];
+  int hist[256];
+  unsigned long long prefix;
+  int need, cnt;
+};
+
+// The first K = min(features, N, FLOW_KMAX) of the pool's N candidates in the order of detectFastByRegion's sort: L.ord[0 .. K) are their pool indices.  Exact for any
+// N: the keys are unique (order is the pixel), so exactly K keys are >= the K-th largest.  Every thread of the workgroup calls it; the result is visible on return
+__device__ __forceinline__ int fast_select_sorted(const int4* __restrict__ pool, int N, int features, SelectLds& L) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int K = min(min(features, N), FLOW_KMAX);
+  unsigned long long T = 0ull;
+  if (K < N) {
+    if (tid == 0) { L.prefix = 0ull; L.need = K; }
+    for (int shift = 32; shift >= 0; shift -= 8) {
+      if (tid < 256) L.hist[tid] = 0;
+      __syncthreads();
+      const unsigned long long prefix = L.prefix;
+      for (int i = tid; i < N; i += 1024) {
+        const unsigned long long k = fast_key(pool[i]);
+        if ((k >> (shift + 8)) == prefix) atomicAdd(&L.hist[(int)((k >> shift) & 255ull)], 1);
+      }
+      __syncthreads();
+      if (tid < 64) {      // wave 0: the bin, from the top, in which the cumulative count reaches `need`; lane l owns bins 255 - 4 l .. 252 - 4 l
+        int c[4], s = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = L.hist[255 - (4 * lane + j)]; s += c[j]; }
+        int incl = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+        const int need = L.need;
+        int above = incl - s;
+        if (above < need && need <= incl) {      // exactly one lane
+          int j = 0;
+          while (above + c[j] < need) { above += c[j]; ++j; }
+          L.prefix = (prefix << 8) | (unsigned long long)(255 - (4 * lane + j));
+          L.need = need - above;
+        }
+      }
+      __syncthreads();
+    }
+    T = L.prefix;
+  }
+  // compaction of the K selected candidates (any order), then the rank of each among them
+  if (tid == 0) L.cnt = 0;
+  __syncthreads();
+  for (int base = 0; base < N; base += 1024) {
+    const int i = base + tid;
+    unsigned long long k = 0ull;
+    bool sel = false;
+    if (i < N) { k = fast_key(pool[i]); sel = k >= T; }
+    const unsigned long long bal = __ballot(sel);
+    int wbase = 0;
+    if (lane == 0 && bal) wbase = atomicAdd(&L.cnt, __popcll(bal));
+    wbase = __shfl(wbase, 0, 64);
+    const int slot = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+    if (sel && slot < K) { L.key[slot] = k; L.idx[slot] = i; }
+  }
+  __syncthreads();
+  for (int i = tid; i < K; i += 1024) {
+    const unsigned long long mine = L.key[i];
+    int r = 0;
+    for (int j = 0; j < K; ++j) r += L.key[j] > mine ? 1 : 0;
+    L.ord[r] = L.idx[i];
+  }
+  __syncthreads();
+  return K;
+}
+
+// launch 4 of d2fe_detect_fast_device: the selection alone, into the caller's arrays
+__global__ __launch_bounds__(1024) void fast_select_kernel(const int* __restrict__ d_features, const int4* __restrict__ pool, const int* __restrict__ count, int pool_cap,
+                                                           int max_features, float* __restrict__ xy, int* __restrict__ response, int cap, int* __restrict__ n_out) {
+  __shared__ SelectLds L;
+  const int features = min(d_features[0], max_features);
+  if (features <= 0) {
+    if (threadIdx.x == 0) n_out[0] = 0;
+    return;
+  }
+  const int K = fast_select_sorted(pool, min(count[0], pool_cap), min(features, cap), L);
+  for (int k = threadIdx.x; k < K; k += 1024) {
+    const int4 c = pool[L.ord[k]];
+    xy[2 * k] = (float)c.x; xy[2 * k + 1] = (float)c.y;
+    if (response) response[k] = c.z;
+  }
+  if (threadIdx.x == 0) n_out[0] = K;
+}
+
+struct LkFlowArgs {
+  const uint8_t* prev_pyr; const uint8_t* cur_pyr;
+  LkPairDev P;                      // geometry only
+  int win, iters;
+  const float* prev; float* cur;    // list blocks
+  CarryLayout lay;                  // D = 0
+  const float* kps; const int* n_kp; int kp_cap;      // kp_cap = 0: no SuperPoint keypoints
+  int total;                        // total_feature_num
+  double near_thr, min_dist;
+  int* next_id;
+  const int4* pool; const int* count; int pool_cap;
+};
+
+__device__ __forceinline__ int flow_n_kp(const LkFlowArgs& c) {
+  int n_kp = c.kp_cap > 0 ? __builtin_amdgcn_readfirstlane(c.n_kp[0]) : 0;
+  return n_kp < 0 ? 0 : n_kp > c.kp_cap ? c.kp_cap : n_kp;
+}
+
+// launch 1: steps a-c and the decision of detectPoints
+__global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) {
+  __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
+  __shared__ int s_src[LKC_MAX];
+  __shared__ int s_cnt[4];          // [1] survivors of the tracker, [2] survivors of removeNearPoints, [3] this workgroup arrived last
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cap = c.lay.cap;
+  const int* phdr = reinterpret_cast<const int*>(c.prev);
+  int* hdr = reinterpret_cast<int*>(c.cur);
+  float* trk_xy = c.cur + c.lay.off[D2FE_LKC_TRK_XY];
+  uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
+  const float* ppts = c.prev + c.lay.off[D2FE_LKC_PTS];
+  int n_prev = __builtin_amdgcn_readfirstlane(phdr[0]);
+  n_prev = n_prev < 0 ? 0 : n_prev > cap ? cap : n_prev;
+
+  // ---- a. track: one wave per entry of the previous list
+  const int slot = blockIdx.x * 4 + wave;
+  if (slot < n_prev) {
+    LkArgs a{};
+    a.win = c.win; a.iters = c.iters;
+    const float ppx = ppts[2 * slot], ppy = ppts[2 * slot + 1];
+    float cx, cy;
+    const int ok = lk_bidir(a, c.P, c.prev_pyr, c.cur_pyr, ppx, ppy, cx, cy, lane);
+    if (lane == 0) { trk_xy[2 * slot] = cx; trk_xy[2 * slot + 1] = cy; trk_st[slot] = (uint8_t)ok; }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // the wave's stores have left before its workgroup arrives
+  }
+  // ---- ticket (the pattern of lk_carry_step_kernel): the last workgroup to arrive acquires everybody's stores and finishes the list
+  __syncthreads();
+  if (tid == 0) {
+    const int old = __hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = old == (int)gridDim.x - 1;
+    if (last) __hip_atomic_store(hdr + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch that writes this block
+    s_cnt[3] = last;
+  }
+  __syncthreads();
+  if (!s_cnt[3]) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+
+  // ---- b-c on wave 0
+  if (wave == 0) {
+    int cnt = 0;
+    const int m = list_reduce_prune(trk_xy, trk_st, n_prev, c.near_thr, s_x, s_y, s_src, lane, cnt);
+    if (lane == 0) { s_cnt[1] = cnt; s_cnt[2] = m; }
+  }
+  __syncthreads();
+  // ---- the tracked entries (step e's first half), zeros behind them
+  const int cnt = s_cnt[1], m = s_cnt[2];
+  float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
+  int* id = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_ID]);
+  int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
+  const int* pid = reinterpret_cast<const int*>(c.prev + c.lay.off[D2FE_LKC_ID]);
+  for (int k = tid; k < cap; k += 256) {
+    const bool live = k < m;
+    const int sk = live ? s_src[k] : 0;
+    pts[2 * k] = live ? s_x[k] : 0.f; pts[2 * k + 1] = live ? s_y[k] : 0.f;
+    id[k] = live ? pid[sk] : 0;
+    src[k] = sk;
+    if (k >= n_prev) { trk_xy[2 * k] = 0.f; trk_xy[2 * k + 1] = 0.f; trk_st[k] = 0; }
+  }
+  // ---- d, the decision (opticaltrack_utils.cpp:379-392): detect when more than a quarter is missing, twice the shortfall when anything exists
+  if (tid == 0) {
+    const int have = flow_n_kp(c) + m;
+    const int lack = c.total - have;
+    const int num = lack > c.total / 4 ? (have > 0 ? 2 * lack : lack) : 0;
+    hdr[0] = m; hdr[1] = n_prev; hdr[2] = n_prev - cnt; hdr[3] = cnt - m; hdr[4] = 0;
+    hdr[6] = *c.next_id;
+    hdr[FLOW_HDR_LACK] = lack; hdr[FLOW_HDR_NUM] = num; hdr[FLOW_HDR_CAND] = 0;
+  }
+  if (tid >= 10 && tid < 64) hdr[tid] = 0;
+}
+
+// launch 5: the rest of step d and the new entries of step e
+__global__ __launch_bounds__(1024) void lk_flow_merge_kernel(LkFlowArgs c) {
+  __shared__ SelectLds L;
+  __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];      // the tracked entries, then the accepted candidates
+  __shared__ uint8_t s_blocked[FLOW_KMAX];
+  __shared__ int s_acc;
+  int* hdr = reinterpret_cast<int*>(c.cur);
+  const int num = hdr[FLOW_HDR_NUM];
+  if (num <= 0) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int m = hdr[0], lack = hdr[FLOW_HDR_LACK], n_kp = flow_n_kp(c);
+  const int id0 = *c.next_id;
+  float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
+  const int K = fast_select_sorted(c.pool, min(c.count[0], c.pool_cap), num, L);
+  // the selected candidates in order (over the keys, which the ranking no longer needs) and the tracked entries
+  float* s_cx = reinterpret_cast<float*>(L.key);
+  float* s_cy = s_cx + FLOW_KMAX;
+  for (int k = tid; k < K; k += 1024) {
+    const int4 p = c.pool[L.ord[k]];
+    s_cx[k] = (float)p.x; s_cy[k] = (float)p.y;
+  }
+  for (int k = tid; k < m; k += 1024) { s_x[k] = pts[2 * k]; s_y[k] = pts[2 * k + 1]; }
+  __syncthreads();
+  // a candidate nearer than feature_min_dist to a keypoint or to a tracked entry is out whatever the order: a thread per candidate
+  const double thr = c.min_dist, t2 = thr * thr, lo = t2 * (1.0 - 1e-12), hi = t2 * (1.0 + 1e-12);
+  for (int k = tid; k < K; k += 1024) {
+    const float px = s_cx[k], py = s_cy[k];
+    bool hit = false;
+    for (int j = 0; j < n_kp && !hit; ++j) hit = nearer(px, py, c.kps[2 * j], c.kps[2 * j + 1], thr, lo, hi);
+    for (int j = 0; j < m && !hit; ++j) hit = nearer(px, py, s_x[j], s_y[j], thr, lo, hi);
+    s_blocked[k] = hit ? 1 : 0;
+  }
+  __syncthreads();
+  // the candidates accepted before it: in order, on one wave, until `lack` are in (m + lack <= total_feature_num <= cap_tracks)
+  if (tid < 64) {
+    int acc = 0;
+    for (int k = 0; k < K && acc < lack; ++k) {
+      if (s_blocked[k]) continue;
+      const float px = s_cx[k], py = s_cy[k];
+      bool hit = false;
+      for (int j = lane; j < acc; j += 64) hit = hit || nearer(px, py, s_x[m + j], s_y[m + j], thr, lo, hi);
+      if (__ballot(hit) == 0ull) {
+        if (lane == 0) { s_x[m + acc] = px; s_y[m + acc] = py; }
+        ++acc;
+        wave_lds_sync();
+      }
+    }
+    if (lane == 0) s_acc = acc;
+  }
+  __syncthreads();       // also: every thread has read *next_id
+  const int acc = s_acc;
+  int* id = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_ID]);
+  int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
+  for (int e = tid; e < acc; e += 1024) {
+    pts[2 * (m + e)] = s_x[m + e]; pts[2 * (m + e) + 1] = s_y[m + e];
+    id[m + e] = id0 + e; src[m + e] = -1;
+  }
+  if (tid == 0) {
+    hdr[0] = m + acc; hdr[4] = acc; hdr[6] = id0 + acc; hdr[FLOW_HDR_CAND] = K;
+    *c.next_id = id0 + acc;
+  }
+}
+
+const char* flow_check_geometry(int width, int height, int cap_tracks, int cols, int rows, int threshold) {
+  if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return "bad pyramid geometry";
+  if (cap_tracks < 1 || cap_tracks > LKC_MAX) return "cap_tracks must be 1..1024";
+  if (cols < 1 || rows < 1 || cols * rows > 64 || threshold < 0 || threshold > 254) return "bad FAST parameters (cols * rows 1..64, threshold 0..254)";
+  if (width / cols < 7 || height / rows < 7) return "a FAST region must be at least 7 x 7";
+  return nullptr;
+}
+
+// launches 2-5 of the step (score clear, FAST scores, non-max; the caller adds the selection) on level 0 of a pyramid; d_features is read on the device
+void fast_device_launch(d2fe_context* h, const uint8_t* d_pyr, int width, int height, const int* d_features, int cap_tracks, int cols, int rows, int threshold,
+                        const FlowScratch& f, hipStream_t s) {
+  const int sw = width / cols, sh = height / rows;
+  const int n4 = (int)(((size_t)width * height + 3) / 4);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_clear_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, d_features, reinterpret_cast<int4*>(f.score), n4, f.count);
+  }
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_region_kernel, dim3(cols * rows), dim3(1024), 0, s, d_pyr, width, sw, sh, rows, d_features, 2 * cap_tracks, threshold, f.score, width);
+  }
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_nonmax_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, f.score, width, height, sw, sh, cols, rows, f.pool, f.pool_cap, f.count,
+                       d_features);
+  }
+}
+
+}  // namespace
+
+hipStream_t ctx_stream(d2fe_handle h);
+int ctx_device(d2fe_handle h);
+
+const char* lk_flow_check_params(const d2fe_flow_params* fp, int width, int height) {
+  if (!fp) return "null flow parameters";
+  if (fp->struct_size != (int32_t)sizeof(d2fe_flow_params)) return "d2fe_flow_params.struct_size";
+  if (const char* why = lk_carry_check_params(&fp->track)) return why;
+  if (fp->superpoint != 0 && fp->superpoint != 1) return "superpoint must be 0 or 1";
+  return flow_check_geometry(width, height, fp->track.total_feature_num > 1 ? fp->track.total_feature_num : 1, fp->fast_cols, fp->fast_rows, fp->fast_threshold);
+}
+
+}  // namespace d2fe
+
+using namespace d2fe;
+
+extern "C" {
+
+void d2fe_flow_default_params(d2fe_flow_params* fp) {
+  if (!fp) return;
+  fp->struct_size = (int32_t)sizeof(d2fe_flow_params);
+  fp->superpoint = 1;
+  d2fe_track_default_params(&fp->track);
+  fp->fast_cols = 3; fp->fast_rows = 4; fp->fast_threshold = 10; fp->reserved = 0;
+}
+
+size_t d2fe_lk_flow_list_bytes(int cap_tracks) {
+  if (cap_tracks < 1 || cap_tracks > LKC_MAX) return 0;
+  return sizeof(float) * (size_t)carry_layout(cap_tracks, 0).words;
+}
+
+long d2fe_lk_flow_list_offset(int cap_tracks, int field) {
+  if (cap_tracks < 1 || cap_tracks > LKC_MAX || field < 0 || field >= D2FE_LKC_FIELDS) return -1;
+  return carry_layout(cap_tracks, 0).off[field];
+}
+
+size_t d2fe_lk_flow_scratch_bytes(int width, int height, int cap_tracks, int cols, int rows) {
+  if (flow_check_geometry(width, height, cap_tracks, cols, rows, 0)) return 0;
+  return flow_scratch(nullptr, width, height, cap_tracks, cols, rows).bytes;
+}
+
+int d2fe_detect_fast_device(d2fe_handle h, const uint8_t* d_pyr, int width, int height, const int32_t* d_features, int cap_tracks, int cols, int rows, int threshold,
+                            float* d_xy, int32_t* d_response, int cap, int32_t* d_n, void* d_scratch, void* stream) {
+  if (!h || !d_pyr || !d_features || !d_xy || !d_n || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = flow_check_geometry(width, height, cap_tracks, cols, rows, threshold)) return ctx_fail(D2FE_ERR_INVALID, why);
+  if (cap < 1 || ((uintptr_t)d_scratch & 15u)) return ctx_fail(D2FE_ERR_INVALID, "cap must be >= 1, the scratch 16-byte aligned");
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  const FlowScratch f = flow_scratch(d_scratch, width, height, cap_tracks, cols, rows);
+  fast_device_launch(h, d_pyr, width, height, d_features, cap_tracks, cols, rows, threshold, f, s);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_select_kernel, dim3(1), dim3(1024), 0, s, d_features, f.pool, f.count, f.pool_cap, 2 * cap_tracks, d_xy, d_response, cap, d_n);
+  }
+  HIP_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+
+int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list, void* d_cur_list,
+                             const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp, int32_t* d_next_id, void* d_scratch, void* stream) {
+  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_list || !d_cur_list || !fp || !d_next_id || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = lk_flow_check_params(fp, width, height)) return ctx_fail(D2FE_ERR_INVALID, why);
+  const d2fe_track_params& tp = fp->track;
+  const int cap_tracks = tp.total_feature_num > 1 ? tp.total_feature_num : 1;
+  if (d_prev_list == d_cur_list) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current list must be different blocks");
+  if ((uintptr_t)d_scratch & 15u) return ctx_fail(D2FE_ERR_INVALID, "the scratch must be 16-byte aligned");
+  if (kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "kp_cap must be 0..16384");
+  if (!fp->superpoint) kp_cap = 0;
+  if (kp_cap > 0 && (!d_kps_xy || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  const FlowScratch f = flow_scratch(d_scratch, width, height, cap_tracks, fp->fast_cols, fp->fast_rows);
+  LkFlowArgs c{};
+  lk_pyr_geometry(c.P, width, height, tp.levels, nullptr);
+  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp.win; c.iters = tp.iters;
+  c.prev = static_cast<const float*>(d_prev_list); c.cur = static_cast<float*>(d_cur_list);
+  c.lay = carry_layout(cap_tracks, 0);
+  c.kps = d_kps_xy; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
+  c.total = tp.total_feature_num; c.near_thr = (double)tp.near_lk_thread_rate; c.min_dist = tp.feature_min_dist;
+  c.next_id = d_next_id;
+  c.pool = f.pool; c.count = f.count; c.pool_cap = f.pool_cap;
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_flow_step_kernel, dim3((cap_tracks + 3) / 4), dim3(256), 0, s, c);
+  }
+  // detectFastByRegion(img, num, cols = fast_rows', rows = fast_cols'): the caller's fast_cols / fast_rows are already the detector's cols / rows (3, 4)
+  const int* d_num = reinterpret_cast<const int*>(d_cur_list) + FLOW_HDR_NUM;
+  fast_device_launch(h, d_cur_pyr, width, height, d_num, cap_tracks, fp->fast_cols, fp->fast_rows, fp->fast_threshold, f, s);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_flow_merge_kernel, dim3(1), dim3(1024), 0, s, c);
+  }
+  HIP_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+
+}  // extern "C"

@@ -73,6 +73,13 @@ struct d2fe_pipe_s {
   size_t list_words = 0, o_list = 0, o_rxy = 0, o_rst = 0, pyr_total = 0;
   uint8_t* d_carry_pyr = nullptr;    // the last left pyramid of the last launched pass
   int32_t* d_next_id = nullptr;
+  // flow (d2fe_pipe_flow_enable; excludes sp_lk): per left frame of a pass one flow-list block (d2fe_lk_flow_list_bytes) at o_flist, on a stereo pipe the right tracks
+  // [F * C][capF][2] floats and [F * C][capF] bytes, with depth uint16 [F * C][capF] -- all inside d2h_words.  The chain state (d_carry_pyr, d_next_id, ev_chain) is sp_lk's
+  bool flow = false;
+  d2fe_flow_params fp{};
+  int capF = 0;
+  size_t flist_words = 0, o_flist = 0, o_frxy = 0, o_frst = 0, o_fdep = 0;
+  void* d_flow_scratch = nullptr;    // the detector's score map and candidate pool: one, the chain serialises the steps
   float* d_all = nullptr;            // [64 zero words | K lanes x 2 sets x block]
   MatchPairDesc* d_pairs = nullptr;  // [K][2][C variants: submits of the PREVIOUS pass][C * npp]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;   // per lane: tickets + records
@@ -307,16 +314,17 @@ int pipe_flush(d2fe_pipe_s* p) {
   // Launch order on the host: SuperPoint FIRST.  Its 13 dependent launches are the long pole of a pass (0.58 ms of kernels for one stereo pair against NetVLAD's
   // 0.25-0.3 ms beside it), and enqueuing NetVLAD's 27 launches costs ~0.12 ms of host time: issued first (rounds 3-4) they held conv1b back by that much in a
   // pass of one frame.  NetVLAD on the lane's second stream still only waits for the frames (ev_up)
+  const bool networks = !(p->flow && !p->fp.superpoint);      // flow only: neither network runs, every n_kp row keeps the zero of creation
   if (nv_side) HIP_TRY(hipEventRecord(L.ev_up, s));
   else if (p->cfg.netvlad && p->M == 1) {        // inline: ONE stream per lane, NetVLAD in front of SuperPoint (behind it measured 8 % slower at four lanes: 1869 vs 2039)
     rc = netvlad(s);
     if (rc) return rc;
   }
-  if (!staged) {
+  if (networks && !staged) {
     rc = run_superpoint(L.ctx, L.d_img, n_img, W, H, W, img, B + p->o_kps, B + p->o_scores, B + p->o_desc, reinterpret_cast<int32_t*>(B + p->o_idx), p->cap,
                         reinterpret_cast<int32_t*>(B + p->o_cnt), s);
     if (rc) return rc;
-  } else {
+  } else if (networks) {
     rc = run_superpoint(L.ctx, L.d_img, n_img, W, H, W, left_stride, B + p->o_skps, B + p->o_sscores, B + p->o_sdesc, reinterpret_cast<int32_t*>(B + p->o_sidx), p->cap,
                         reinterpret_cast<int32_t*>(B + p->o_scnt), s);
     if (rc) return rc;
@@ -332,9 +340,13 @@ int pipe_flush(d2fe_pipe_s* p) {
                                      LK_LEVELS, LK_WIN, LK_ITERS, L.d_lk, B + p->o_lkp, reinterpret_cast<uint8_t*>(B + p->o_lks), s);
     if (rc) return rc;
   }
-  if (p->sp_lk) {
-    // the pyramids of the pass (the same two launches), then the landmark list: one step per left frame in time order, the carry copy, ONE left -> right launch
-    if (p->mono) rc = lk_pyramids_launch(L.ctx, L.d_img, n_left, W, H, W, left_stride, p->tp.levels, L.d_lk, s);
+  if (p->sp_lk || p->flow) {
+    // the pyramids of the pass (the same two launches; a flow pass on a stereo pipe has them from the lr_lk launch above), then the landmark list -- the LK-carried
+    // SuperPoint list of sp_lk or the flow list, one chain for both: one step per left frame in time order, the carry copy, ONE left -> right launch
+    const d2fe_track_params& tp = p->flow ? p->fp.track : p->tp;
+    const size_t o_list = p->flow ? p->o_flist : p->o_list, list_words = p->flow ? p->flist_words : p->list_words;
+    if (p->mono) rc = lk_pyramids_launch(L.ctx, L.d_img, n_left, W, H, W, left_stride, tp.levels, L.d_lk, s);
+    else if (p->flow) rc = D2FE_OK;
     else rc = d2fe_lk_track_stereo_device(L.ctx, L.d_img, L.d_img + (p->C > 1 ? img : (size_t)F * img), n_left, W, H, W, left_stride, nullptr, nullptr, 0, p->tp.levels,
                                           p->tp.win, p->tp.iters, L.d_lk, nullptr, nullptr, s);
     if (rc) return rc;
@@ -344,19 +356,25 @@ int pipe_flush(d2fe_pipe_s* p) {
     for (int f = 0; f < n_left; ++f) {
       // previous list / pyramid: the frame before in this pass; f = 0: the previous pass's last list (its last submit is prev_g - 1) and the carried pyramid;
       // the very first frame reads the 64 zero words in front of the blocks (the empty list) and tracks nothing
-      const float* prev_list = f > 0 ? B + p->o_list + (size_t)(f - 1) * p->list_words
-                                     : P > 0 ? p->block(pk, pset) + p->o_list + (size_t)((p->C > 1 ? p->prev_g : F) - 1) * p->list_words : p->d_all;
+      const float* prev_list = f > 0 ? B + o_list + (size_t)(f - 1) * list_words
+                                     : P > 0 ? p->block(pk, pset) + o_list + (size_t)((p->C > 1 ? p->prev_g : F) - 1) * list_words : p->d_all;
       const uint8_t* prev_pyr = f > 0 ? L.d_lk + (size_t)(f - 1) * p->pyr_total : p->d_carry_pyr;
       const size_t r = (size_t)p->left_row(f, f);        // C > 1: frame f is submit f (row 2 f); C == 1: row f
-      rc = d2fe_lk_carry_step_device(L.ctx, prev_pyr, L.d_lk + (size_t)f * p->pyr_total, W, H, prev_list, B + p->o_list + (size_t)f * p->list_words, p->D,
-                                     B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap, B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp,
-                                     p->d_next_id, s);
+      float* cur_list = B + o_list + (size_t)f * list_words;
+      const uint8_t* cur_pyr = L.d_lk + (size_t)f * p->pyr_total;
+      if (p->flow)
+        rc = d2fe_lk_flow_step_device(L.ctx, prev_pyr, cur_pyr, W, H, prev_list, cur_list, B + p->o_kps + r * p->cap * 2, cnt + r, p->cap, &p->fp, p->d_next_id,
+                                      p->d_flow_scratch, s);
+      else
+        rc = d2fe_lk_carry_step_device(L.ctx, prev_pyr, cur_pyr, W, H, prev_list, cur_list, p->D, B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap,
+                                       B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp, p->d_next_id, s);
       if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(p->d_carry_pyr, L.d_lk + (size_t)(n_left - 1) * p->pyr_total, p->pyr_total, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipEventRecord(L.ev_chain, s));
     if (!p->mono) {
-      rc = lk_carry_right_launch(L.ctx, L.d_lk, n_left, W, H, p->tp, B + p->o_list, p->D, B + p->o_rxy, reinterpret_cast<uint8_t*>(B + p->o_rst), s);
+      rc = lk_carry_right_launch(L.ctx, L.d_lk, n_left, W, H, tp, B + o_list, p->flow ? 0 : p->D, B + (p->flow ? p->o_frxy : p->o_rxy),
+                                 reinterpret_cast<uint8_t*>(B + (p->flow ? p->o_frst : p->o_rst)), s);
       if (rc) return rc;
     }
   }
@@ -371,7 +389,12 @@ int pipe_flush(d2fe_pipe_s* p) {
                         reinterpret_cast<const int32_t*>(lists + d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_HDR)), p->list_words, p->capT,
                         reinterpret_cast<uint16_t*>(B + p->o_trd)};
     }
-    rc = depth_gather_launch(L.ctx, L.d_dep, W, H, (size_t)W, img, n_left, seg, p->sp_lk ? 2 : 1, s);
+    if (p->flow) {
+      const float* lists = B + p->o_flist;
+      seg[1] = DepthSeg{lists + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_PTS), p->flist_words, reinterpret_cast<const int32_t*>(lists), p->flist_words, p->capF,
+                        reinterpret_cast<uint16_t*>(B + p->o_fdep)};
+    }
+    rc = depth_gather_launch(L.ctx, L.d_dep, W, H, (size_t)W, img, n_left, seg, p->sp_lk || p->flow ? 2 : 1, s);
     if (rc) return rc;
   }
   if (nv_side) {
@@ -434,6 +457,16 @@ int pipe_alloc_blocks(d2fe_pipe_s* p) {
   if (p->depth) {
     p->o_kpd = o; o += up64((NL * cap + 1) / 2);
     if (p->sp_lk) { p->o_trd = o; o += up64((NL * p->capT + 1) / 2); }
+  }
+  if (p->flow) {
+    p->capF = p->fp.track.total_feature_num > 1 ? p->fp.track.total_feature_num : 1;
+    p->flist_words = d2fe_lk_flow_list_bytes(p->capF) / sizeof(float);
+    p->o_flist = o; o += NL * p->flist_words;
+    if (!p->mono) {
+      p->o_frxy = o; o += up64(NL * p->capF * 2);
+      p->o_frst = o; o += up64((NL * p->capF + 3) / 4);
+    }
+    if (p->depth) { p->o_fdep = o; o += up64((NL * p->capF + 1) / 2); }
   }
   p->d2h_words = o;
   p->o_idx = o; o += up64(NI * cap);
@@ -748,6 +781,7 @@ void d2fe_pipe_destroy(d2fe_pipe p) {
   if (p->d_lk_ws) (void)hipFree(p->d_lk_ws);
   if (p->d_carry_pyr) (void)hipFree(p->d_carry_pyr);
   if (p->d_next_id) (void)hipFree(p->d_next_id);
+  if (p->d_flow_scratch) (void)hipFree(p->d_flow_scratch);
   if (p->d_pairs) (void)hipFree(p->d_pairs);
   if (p->d_match_scratch) (void)hipFree(p->d_match_scratch);
   if (p->d_all) (void)hipFree(p->d_all);
@@ -999,6 +1033,77 @@ int d2fe_pipe_depth_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_depth_resu
   out->frames = p->F; out->cap = p->cap; out->cap_tracks = p->sp_lk ? p->capT : 0;
   out->kp_depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_kpd) + r0 * p->cap;
   if (p->sp_lk) out->track_depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_trd) + r0 * p->capT;
+  return D2FE_OK;
+}
+
+int d2fe_pipe_flow_enable(d2fe_pipe p, const d2fe_flow_params* fp) {
+  if (!p) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  d2fe_flow_params def;
+  d2fe_flow_default_params(&def);
+  if (!fp) fp = &def;
+  if (!p->lk && !p->mono) return pipe_fail(D2FE_ERR_INVALID, "the flow landmarks need lr_lk = 1 or mono = 1: the list is tracked on the pyramids such a pipe builds");
+  if (p->sp_lk) return pipe_fail(D2FE_ERR_INVALID, "the flow landmarks exclude sp_lk: the reference runs one of the two branches (d2featuretracker.cpp:556-614)");
+  if (const char* why = lk_flow_check_params(fp, p->W, p->H)) return pipe_fail(D2FE_ERR_INVALID, why);
+  if (fp->track.levels != LK_LEVELS) return pipe_fail(D2FE_ERR_INVALID, "levels must be 2 (PYR_LEVEL): the lanes' pyramid workspaces are that deep");
+  if (!fp->superpoint && (p->cfg.netvlad || p->cfg.match_prev)) return pipe_fail(D2FE_ERR_INVALID, "superpoint = 0 needs a pipe created with netvlad = 0 and match_prev = 0: no network runs");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->next_ticket > 0) return pipe_fail(D2FE_ERR_INVALID, "the flow landmarks are switched on before the first submit");
+  if (p->flow) return pipe_fail(D2FE_ERR_INVALID, "the flow landmarks are already switched on");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  // a failure below leaves the pipe without result blocks: final, like a failed submit
+  p->flow = true; p->fp = *fp; p->fp.reserved = 0; p->fp.track.reserved = 0;
+  p->pyr_total = d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, LK_LEVELS) / 2;
+  const int rc = [&]() -> int {
+    if (!p->d_lk_ws) {      // a mono pipe without sp_lk has built no pyramids so far
+      p->lk_ws_lane = (d2fe_lk_stereo_workspace_bytes(p->F * p->C, p->W, p->H, LK_LEVELS) / 2 + 255) / 256 * 256;
+      HIP_TRY(hipMalloc(&p->d_lk_ws, p->lk_ws_lane * p->K));
+      for (int k = 0; k < p->K; ++k) p->lanes[k].d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
+    }
+    for (auto& L : p->lanes) if (!L.ev_chain) HIP_TRY(hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&p->d_carry_pyr, p->pyr_total));
+    HIP_TRY(hipMemset(p->d_carry_pyr, 0, p->pyr_total));
+    HIP_TRY(hipMalloc(&p->d_next_id, 64));
+    HIP_TRY(hipMemset(p->d_next_id, 0, 64));
+    const int capF = p->fp.track.total_feature_num > 1 ? p->fp.track.total_feature_num : 1;
+    HIP_TRY(hipMalloc(&p->d_flow_scratch, d2fe_lk_flow_scratch_bytes(p->W, p->H, capF, p->fp.fast_cols, p->fp.fast_rows)));
+    int rc2 = pipe_alloc_blocks(p);
+    for (auto& L : p->lanes) if (rc2 == D2FE_OK) rc2 = pipe_alloc_pinned(p, L);
+    if (rc2 == D2FE_OK) rc2 = pipe_alloc_pairs(p);
+    if (rc2 == D2FE_OK && hipDeviceSynchronize() != hipSuccess) rc2 = pipe_fail(D2FE_ERR_HIP, "hipDeviceSynchronize");      // the blocks are zeroed on the null stream
+    return rc2;
+  }();
+  if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
+  return rc;
+}
+
+int d2fe_pipe_flow_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_flow_result* out) {
+  if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (!p->flow) return pipe_fail(D2FE_ERR_UNSUPPORTED, "d2fe_pipe_flow_enable was not called on this pipe: it carries no flow landmarks");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
+  const auto ti = p->tinfo[(size_t)(ticket % (long long)p->tinfo.size())];
+  if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass < 0 || ti.pass + 2 * p->K < p->next_pass)
+    return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the lists within 2 * lanes passes");
+  if (!ti.waited) return pipe_fail(D2FE_ERR_NOT_READY, "d2fe_pipe_wait has not returned this ticket yet");
+  const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
+  const float* B = p->lanes[k].pin_out[set];
+  const size_t r0 = p->C > 1 ? (size_t)ti.j : 0, T = (size_t)p->capF;
+  const float* list = B + p->o_flist + r0 * p->flist_words;
+  const int32_t* hdr = reinterpret_cast<const int32_t*>(list);
+  out->frames = p->F; out->cap_tracks = p->capF; out->list_words = (int32_t)p->flist_words;
+  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
+  out->lack = hdr + 7; out->num = hdr + 8; out->n_cand = hdr + 9;
+  out->pts_xy = list + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_PTS);
+  out->id = hdr + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_ID);
+  out->src = hdr + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_SRC);
+  if (!p->mono) {
+    out->right_xy = B + p->o_frxy + r0 * T * 2;
+    out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_frst) + r0 * T;
+  }
+  if (p->depth) out->depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_fdep) + r0 * T;
   return D2FE_OK;
 }
 

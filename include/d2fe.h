@@ -745,6 +745,74 @@ D2FE_API int d2fe_lk_carry_quad_step_device(d2fe_handle h, const uint8_t* d_prev
 D2FE_API int d2fe_lk_carry_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov,
                                             const void* d_lists, size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy,
                                             uint8_t* d_nb_status, void* stream);
+/* The FLOW landmarks (enable_lk_optical_flow without sp_track_use_lk; the whole front end of config/gopro/gopro.yaml and config/visensor_f9p/visensor_f9p.yaml, which
+ * set max_superpoint_cnt: 0) for ONE camera and ONE frame, on the device: the second list D2FeatureTracker::trackLK(frame) (d2featuretracker.cpp:472-621) keeps.
+ *   a-c. as d2fe_lk_carry_step_device (the same device code): track every entry of the previous list, reduceVector, removeNearPoints; m entries survive;
+ *   d.   detectPoints(img, n_pts, cur_pts, require = total_feature_num, ..., use_fast = true) (opticaltrack_utils.cpp:375-442) with cur_pts = landmarks2D() = the frame's
+ *        SuperPoint keypoints kps[0 .. n_kp) followed by the m tracked entries: lack = total_feature_num - (n_kp + m); only if lack > total_feature_num / 4 (integer
+ *        division, strict) num = lack, doubled when n_kp + m > 0, candidates = detectFastByRegion(img, num, cols = fast_cols, rows = fast_rows) at fast_threshold in the
+ *        order d2fe_detect_fast_by_region fixes (response descending, region-major raster order ascending); a candidate is skipped when cv::norm(candidate - q) <
+ *        feature_min_dist (float difference, squares and sqrt in double) for any q of cur_pts or any candidate accepted before it; stop at `lack` accepted;
+ *   e.   the new list = the m tracked entries (id kept, src = index in the previous list), then the accepted candidates (id = next_id++, src = -1).  The SuperPoint
+ *        keypoints only block candidates, they are not in the list; n <= total_feature_num.
+ * The LIST is a block of d2fe_lk_flow_list_bytes(cap_tracks) bytes, cap_tracks = max(total_feature_num, 1) (0 outside 1..1024), laid out by the rules of the carry list
+ * with the fields a flow entry has: d2fe_lk_flow_list_offset(cap_tracks, field) for D2FE_LKC_HDR, _PTS, _ID, _SRC, _TRK_XY, _TRK_STATUS; -1 for _KP, _SCORES, _DESC and
+ * a bad field.  Header words 0-6 as in the carry list ([0] n, [1] n_tracked_in, [2] n_lost, [3] n_removed_near, [4] n_new, [5] arrival counter, [6] next_id after this
+ * frame), then [7] lack, [8] num (0: the frame did not detect), [9] the candidates that reached the merge (min(num, what FAST found)); rest 0.  The zero-once rule, the
+ * all-zero empty list and d_prev_list != d_cur_list hold as there.  d2fe_flow_params.superpoint = 0 (flow only): the keypoint arguments are ignored, n_kp = 0.
+ * d_scratch: d2fe_lk_flow_scratch_bytes(width, height, cap_tracks, fast_cols, fast_rows) bytes, 16-byte aligned (host arithmetic, 0 for what the call refuses): the
+ * score map and the candidate pool for num up to 2 * cap_tracks; its content between calls does not matter.
+ * FIVE launches per frame whatever the list holds -- (1) track + b-c + the decision in the last workgroup to arrive, (2) score-map clear, (3) FAST scores, (4) non-max,
+ * (5) selection + merge + new entries -- of which 2-5 read `num` from the header and return at once when it is 0.  Everything is read on the device: the call only
+ * enqueues on `stream` (NULL: the handle's stream), no allocation, no synchronisation.  D2FE_ERR_INVALID: what d2fe_lk_carry_step_device refuses, fast_cols * fast_rows
+ * outside 1..64, a region (width / fast_cols) x (height / fast_rows) below 7 x 7, fast_threshold outside 0..254, a struct_size that is not this header's.
+ *
+ * d2fe_detect_fast_device: detectFastByRegion without the host, launches 2-4 and the selection alone (FOUR launches): level 0 of the pyramid at d_pyr, `features` read
+ * from ONE int32 in device memory and clamped to 2 * cap_tracks (what the scratch holds); d_xy [cap][2], d_response [cap] (may be NULL) and d_n [1] receive
+ * min(features, found, cap) candidates in the order and with the bits of d2fe_detect_fast_by_region.  features <= 0: d_n = 0, nothing else is written, every kernel
+ * returns at once.  The host sort is an exact selection on a unique key of 40 significant bits (the response in bits 32..39 -- a FAST score is at most 254 -- above ~order in
+ * bits 0..31; five 8-bit passes cover bits 0..39), correct for any candidate count up to cols * rows * features. */
+typedef struct d2fe_flow_params_s {
+  int32_t struct_size;            /* sizeof(d2fe_flow_params), checked strictly */
+  int32_t superpoint;             /* 1: beside SuperPoint (its keypoints block candidates); 0: flow only (max_superpoint_cnt: 0) */
+  d2fe_track_params track;        /* total_feature_num = max_cnt, levels, win, iters, near_lk_thread_rate, feature_min_dist */
+  int32_t fast_cols, fast_rows;   /* 3, 4   the detector's cols / rows: the reference hands fast_rows = 3 to the parameter named cols (opticaltrack_utils.cpp:394-396) */
+  int32_t fast_threshold;         /* 10    opticaltrack_utils.cpp:451-452 */
+  int32_t reserved;               /* zero */
+} d2fe_flow_params;
+D2FE_API void d2fe_flow_default_params(d2fe_flow_params* fp);
+D2FE_API size_t d2fe_lk_flow_list_bytes(int cap_tracks);
+D2FE_API long d2fe_lk_flow_list_offset(int cap_tracks, int field);
+D2FE_API size_t d2fe_lk_flow_scratch_bytes(int width, int height, int cap_tracks, int cols, int rows);
+D2FE_API int d2fe_detect_fast_device(d2fe_handle h, const uint8_t* d_pyr, int width, int height, const int32_t* d_features, int cap_tracks, int cols, int rows,
+                                     int threshold, float* d_xy, int32_t* d_response, int cap, int32_t* d_n, void* d_scratch, void* stream);
+D2FE_API int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list,
+                                      void* d_cur_list, const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp, int32_t* d_next_id,
+                                      void* d_scratch, void* stream);
+/* The flow landmarks IN THE STEREO / MONO PIPE.  d2fe_pipe_config and d2fe_pipe_camera are closed structs, so the mode is switched on by a call before the first
+ * submit (as d2fe_quad_track_enable does for the quad pipe): d2fe_pipe_flow_enable(p, fp) (fp NULL: d2fe_flow_default_params).  It needs a pipe that builds
+ * pyramids (lr_lk = 1 or mono = 1), is refused with sp_lk (the reference's two branches exclude each other, d2featuretracker.cpp:556-614), after the first submit, for
+ * fp->track.levels != 2, for what d2fe_lk_flow_step_device refuses, and with fp->superpoint = 0 on a pipe created with netvlad or match_prev; a refusal
+ * (D2FE_ERR_INVALID) leaves the pipe as it was and usable.  Per left frame of a pass ONE d2fe_lk_flow_step_device (five launches, D2FE_PROF_LK) in time order behind the
+ * pass's pyramids, on the chain sp_lk uses: the previous list is read where the previous pass left it, the last pyramid is carried in a pipe-owned copy, the lanes
+ * wait for each other's chain event, ids come from the pipe's one counter; one pipe-owned detector scratch serves all lanes because the chain serialises the steps.
+ * On a stereo pipe ONE more launch tracks the flow entries of all frames of the pass left -> right (trackLK(left, right), :697-752); the per-keypoint launch of lr_lk
+ * stays.  superpoint = 0 (gopro.yaml / visensor_f9p.yaml): a pass launches neither network and no matcher, every n_kp row stays 0 on the device too; the lanes'
+ * activation buffers stay allocated (freeing them needs a create-time switch the closed structs do not have).  With depth the pass's one depth_gather_kernel launch
+ * takes one more segment over the flow lists.  The lists [frames * coalesce], the right tracks and the depth values sit in front of d2h_words, inside the pass's one
+ * D2H; a pipe that never enables the mode keeps its layout, allocations, launches and results.  d2fe_pipe_flow_result_get (after d2fe_pipe_wait; D2FE_ERR_UNSUPPORTED on
+ * a pipe without the mode): the pointers address frame 0 of the ticket; frame f's list arrays are f * list_words 32-bit words further, right_xy [frames][cap_tracks][2],
+ * right_status and depth_mm [frames][cap_tracks] are dense (NULL on a mono pipe / without depth). */
+typedef struct {
+  int32_t frames, cap_tracks, list_words, reserved;
+  const int32_t *n, *n_tracked_in, *n_lost, *n_removed_near, *n_new, *lack, *num, *n_cand;
+  const float* pts_xy;             /* [cap_tracks][2] */
+  const int32_t *id, *src;         /* [cap_tracks] */
+  const float* right_xy; const uint8_t* right_status;
+  const uint16_t* depth_mm;
+} d2fe_pipe_flow_result;
+D2FE_API int d2fe_pipe_flow_enable(d2fe_pipe p, const d2fe_flow_params* fp);
+D2FE_API int d2fe_pipe_flow_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_flow_result* out);
 /* detectFastByRegion (opticaltrack_utils.cpp:444-493): cv::cuda::FastFeatureDetector(threshold, nonmax, TYPE_9_16,
  * max_npoints = features) on each of the cols x rows regions of level 0, sorted by response, top `features`.
  * response (optional) receives the FAST scores. */

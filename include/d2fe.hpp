@@ -211,6 +211,17 @@ struct StereoTrackList {
   std::vector<uint8_t> right_status;
   int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0;
 };
+// StereoPipe::flowEnable (d2fe_pipe_flow_enable): the frame's FLOW landmarks, the second list of D2FeatureTracker::trackLK(frame) (enable_lk_optical_flow without
+// sp_track_use_lk; d2featuretracker.cpp:472-621 with detectPoints(use_fast)) -- entry i at pts[i] with the pipe-wide id[i]; src[i] = its index in the previous
+// frame's list, -1: detected in this frame; right[i] / right_status[i] its left -> right track (empty on a mono pipe); depth_mm[i] on a depth pipe.  lack / num / n_cand:
+// what detectPoints decided (num = 0: the frame did not detect)
+struct StereoFlowList {
+  std::vector<Point2f> pts, right;
+  std::vector<int32_t> id, src;
+  std::vector<uint8_t> right_status;
+  std::vector<uint16_t> depth_mm;
+  int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0, lack = 0, num = 0, n_cand = 0;
+};
 struct StereoFrameResult {
   std::vector<Point2f> kps_left, kps_right;
   std::vector<float> scores_left, scores_right;
@@ -222,6 +233,7 @@ struct StereoFrameResult {
   // sits in the right image when lk_status[i] != 0 (what trackLK, d2featuretracker.cpp:697-752, hands to reduceVector); kps_right / left_right stay empty
   std::vector<Point2f> lk_right;
   std::vector<uint8_t> lk_status;
+  StereoFlowList flow;                               // StereoPipe::flowEnable
   StereoTrackList tracks;                            // cfg.sp_lk = 1 (lk_right / lk_status then stay empty: the list entries are what is tracked into the right image)
   // a depth pipe (d2fe_pipe_camera::depth, PINHOLE_DEPTH): depth_mm[i] = depth.at<unsigned short>(kps_left[i]) of the frame's depth image (loop_cam.cpp:382), i.e. the pixel at
   // (cvRound(x), cvRound(y)), 0 outside the image; the / 1000.0, the DEPTH_NEAR_THRES / DEPTH_FAR_THRES test and liftProjective stay with the caller
@@ -260,6 +272,14 @@ class StereoPipe {
   StereoPipe& operator=(const StereoPipe&) = delete;
   bool ok() const { return p_ != nullptr; }
   d2fe_pipe get() const { return p_; }
+  // the flow landmarks (d2fe_pipe_flow_enable): once, before the first submit, on a pipe with lr_lk = 1 or mono = 1 and without sp_lk; fp NULL: the reference's
+  // defaults; fp->superpoint = 0 (max_superpoint_cnt: 0, needs netvlad = match_prev = 0): no network runs.  A refusal leaves the pipe as it was
+  bool flowEnable(const d2fe_flow_params* fp = nullptr) {
+    if (!p_) return false;
+    if (d2fe_pipe_flow_enable(p_, fp) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_flow_enable: %s\n", d2fe_last_error()); return false; }
+    flow_ = true;
+    return true;
+  }
   // returns the ticket (>= 0) or -1
   int64_t submit(const ImageView& left, const ImageView& right) {
     int64_t t = -1;
@@ -323,6 +343,19 @@ class StereoPipe {
       if (tr.right_status) t.right_status.assign(tr.right_status, tr.right_status + n);
       t.n_tracked_in = tr.n_tracked_in[0]; t.n_lost = tr.n_lost[0]; t.n_removed_near = tr.n_removed_near[0]; t.n_new = tr.n_new[0];
     }
+    out.flow = StereoFlowList();
+    if (flow_) {
+      d2fe_pipe_flow_result fr;
+      if (d2fe_pipe_flow_result_get(p_, ticket, &fr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_flow_result_get: %s\n", d2fe_last_error()); return false; }
+      StereoFlowList& t = out.flow;
+      const int n = fr.n[0];
+      for (int j = 0; j < n; ++j) { t.pts.emplace_back(fr.pts_xy[2 * j], fr.pts_xy[2 * j + 1]); if (fr.right_xy) t.right.emplace_back(fr.right_xy[2 * j], fr.right_xy[2 * j + 1]); }
+      t.id.assign(fr.id, fr.id + n); t.src.assign(fr.src, fr.src + n);
+      if (fr.right_status) t.right_status.assign(fr.right_status, fr.right_status + n);
+      if (fr.depth_mm) t.depth_mm.assign(fr.depth_mm, fr.depth_mm + n);
+      t.n_tracked_in = fr.n_tracked_in[0]; t.n_lost = fr.n_lost[0]; t.n_removed_near = fr.n_removed_near[0]; t.n_new = fr.n_new[0];
+      t.lack = fr.lack[0]; t.num = fr.num[0]; t.n_cand = fr.n_cand[0];
+    }
     out.depth_mm.clear();
     if (depth_) {
       d2fe_pipe_depth_result dr;
@@ -346,7 +379,7 @@ class StereoPipe {
 
  private:
   d2fe_pipe p_ = nullptr;
-  bool lr_lk_ = false, sp_lk_ = false, depth_ = false;
+  bool lr_lk_ = false, sp_lk_ = false, depth_ = false, flow_ = false;
 };
 
 // trackEnable(): the LK-carried landmark list of one view of a quad frame (what D2FeatureTracker::trackLK(frame) leaves in keyframe_lk_infos[frame_id][c] with
