@@ -270,7 +270,7 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
-    "d2fe_debug_netvlad_plan", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
+    "d2fe_debug_netvlad_plan", "d2fe_debug_netvlad_shapes", "d2fe_debug_netvlad_features", "d2fe_debug_netvlad_groups", "d2fe_debug_netvlad_slots", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
     "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
@@ -1077,6 +1077,59 @@ class DevFrontEnd(FrontEnd):
         kps = np.empty((n, cap, 2), np.float32); sc = np.empty((n, cap), np.float32); idx = np.empty((n, cap), np.int32); m = np.empty(n, np.int32)
         _check(self._lib.d2fe_debug_nms2_a(self._h, _ptr(semi), n, H, W, float(thr), int(dist), int(max_kp), int(cap), _ptr(kps), _ptr(sc), _ptr(idx), _ptr(m)))
         return [(kps[i, :m[i]].copy(), sc[i, :m[i]].copy(), idx[i, :m[i]].copy()) for i in range(n)]
+
+    # ---- NetVLAD inspection (include/d2fe_debug.h; tests/test_netvlad_shapes*.py) ----
+    @staticmethod
+    def netvlad_shapes(family):
+        """[(NK, NT)] nv_pblock_kernel is compiled for: family 0 every shape, 1 the shapes that also exist with merged groups.  Needs no handle and no GPU."""
+        lib = load_library(dev=True)
+        n = int(lib.d2fe_debug_netvlad_shapes(int(family), None, 0))
+        if n < 0:
+            raise D2FEError(n, "d2fe_debug_netvlad_shapes(%d)" % family)
+        out = (C.c_int * (2 * max(n, 1)))()
+        assert int(lib.d2fe_debug_netvlad_shapes(int(family), out, n)) == n
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
+
+    @staticmethod
+    def netvlad_plan(layers, proj_dim):
+        """[(kind, first layer, last layer, halves)] of the execution plan d2fe_load_netvlad builds for this layer list (dicts of kind, cin, cout, stride, act,
+        res; weights not needed) under the D2FE_NV_* switches of the environment.  Needs no handle and no GPU."""
+        lib = load_library(dev=True)
+        kinds = {"conv": 0, "pw": 1, "dw": 2}
+        arr = (_NvLayer * len(layers))(*[_NvLayer(kinds[l["kind"]], l["cin"], l["cout"], l["stride"], l["act"], l["res"], None, None) for l in layers])
+        out = (C.c_int * (4 * 64))()
+        n = int(lib.d2fe_debug_netvlad_plan(arr, len(layers), int(proj_dim), out, 64))
+        if n < 0:
+            _check(n)
+        return [tuple(int(v) for v in out[4 * i:4 * i + 4]) for i in range(min(n, 64))]
+
+    def debug_netvlad_features(self, shape):
+        """The pre-projected features [n, positions, proj_dim] the VLAD stage of the last netvlad call read (partial slabs added in slab order)."""
+        self._need_dev("debug_netvlad_features")
+        out = np.empty(shape, np.float32)
+        self._lib.d2fe_debug_netvlad_features.restype = C.c_long
+        r = int(self._lib.d2fe_debug_netvlad_features(self._h, int(shape[0]), _ptr(out), C.c_size_t(out.nbytes)))
+        if r < 0:
+            _check(r)
+        assert r == out.nbytes, (r, out.nbytes)
+        return out
+
+    def debug_netvlad_groups(self, layer):
+        """(hidden-channel groups that wrote `layer` in the last netvlad call, partial slabs left in memory: 1 once the slab sum ran); layer -1: the features"""
+        self._need_dev("debug_netvlad_groups")
+        out = (C.c_int * 2)()
+        _check(int(self._lib.d2fe_debug_netvlad_groups(self._h, int(layer), out)))
+        return int(out[0]), int(out[1])
+
+    @staticmethod
+    def netvlad_slots(cin, cout, ncu, nbuf=1):
+        """nv_pblock_slots: resident workgroups of the pixel-pair block shape on a device of ncu compute units.  Needs no handle and no GPU."""
+        lib = load_library(dev=True)
+        lib.d2fe_debug_netvlad_slots.restype = C.c_long
+        r = int(lib.d2fe_debug_netvlad_slots(int(cin), int(cout), int(ncu), int(nbuf)))
+        if r < 0:
+            raise D2FEError(r, "d2fe_debug_netvlad_slots")
+        return r
 
     @staticmethod
     def regime_counts(reset=False):

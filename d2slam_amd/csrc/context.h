@@ -162,7 +162,7 @@ struct NvNet {
   NvNet() = default; NvNet(const NvNet&) = delete; NvNet& operator=(const NvNet&) = delete; ~NvNet();
 };
 // a tensor of the last call = the sum of `n` partial slabs `stride` floats apart
-struct NvSlabs { int n = 1; long stride = 0; };
+struct NvSlabs { int n = 1; long stride = 0; int groups = 1; };     // groups: the hidden-channel groups that wrote it (n = 1 again once the slab sum ran)
 // the host-side bookkeeping a NetVLAD call leaves behind (what the next step of the call and the debug reads consult)
 struct NvLast { std::vector<NvSlabs> layer; NvSlabs feat; int stamp_wgs = 0; };
 // what one context owns to run the network: its activations and the bookkeeping of its last call

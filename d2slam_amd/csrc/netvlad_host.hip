@@ -272,7 +272,7 @@ int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int
       // (the hidden-channel split is decided on ONE image's pixel count whatever the batch: see the block steps below)
       nv_groups(((long)ch * cw + 127) / 128, a.Chid / 16, net.feat_gmax, &groups, &cpg, kn.tail_blocks);
       a.cpg = cpg; a.out = run.feat_buf; a.out_slab_stride = a.P * a.Cout;
-      run.last.feat = {groups, a.out_slab_stride};
+      run.last.feat = {groups, a.out_slab_stride, groups};
       if (k == NvKind::Tail) HIP_TRY(launch_nv_tail(a, groups, s));
       else HIP_TRY(launch_nv_block(a, true, 2, n, groups, s));
       // no slab sum here: the VLAD stage reads every feature exactly once and adds the slabs, in slab order, while it stages them
@@ -317,7 +317,7 @@ int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int
       if (kn.merge && tiles * groups > slots && tiles * ((groups + tree - 1) / tree) * 2 >= (h->ncu_dev > 0 ? h->ncu_dev : 256)) { a.gmerge = tree; wgroups = (groups + tree - 1) / tree; }
     }
     NvSlabs& slabs = run.last.layer[st.l1];
-    slabs = {wgroups, a.out_slab_stride};
+    slabs = {wgroups, a.out_slab_stride, groups};
     a.ncu = h->ncu; a.tpw = kn.front_tpw; a.nbuf = kn.nbuf;
     if ((int)si == kn.stamp_step && run.stamps && (tiles * wgroups <= 32768)) {
       HIP_TRY(hipMemsetAsync(run.stamps, 0, sizeof(unsigned long long) * 32 * 32768, s));
@@ -464,6 +464,38 @@ long d2fe_debug_netvlad_layer(d2fe_handle h, int layer, int n_images, void* dst,
     }
   }
   return (long)bytes;
+}
+
+/* test hook: the pre-projected features [n_images][np][proj_dim] of the last d2fe_netvlad* call (the input of the VLAD stage), partial slabs added in
+ * slab order as that stage adds them; the caller passes images of the handle's maximum size, as for d2fe_debug_netvlad_layer. */
+long d2fe_debug_netvlad_features(d2fe_handle h, int n_images, void* dst, size_t max_bytes) {
+  if (!h || !dst || !h->nv_net || !h->nv_run.feat_buf || n_images < 1 || n_images > h->cfg.max_batch) return fail(D2FE_ERR_INVALID, "bad argument");
+  const auto& l = h->nv_net->layers.back();
+  const float* feat = h->nv_run.feat_buf;
+  const NvSlabs sl = h->nv_run.last.feat;
+  const size_t bytes = sizeof(float) * (size_t)n_images * l.oh * l.ow * h->nv_net->proj;
+  if (bytes > max_bytes) return fail(D2FE_ERR_TRUNCATED, "destination too small");
+  if (sl.n > 1 && (size_t)sl.stride * sizeof(float) != bytes) return fail(D2FE_ERR_INVALID, "n_images differs from the last call");
+  hipSetDevice(h->cfg.device_id);
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dst, feat, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
+  if (sl.n > 1) {
+    std::vector<float> tmp(bytes / sizeof(float));
+    float* o = static_cast<float*>(dst);
+    for (int s = 1; s < sl.n; ++s) {
+      if (hipMemcpy(tmp.data(), feat + (size_t)s * sl.stride, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2FE_ERR_HIP, "D2H");
+      for (size_t i = 0; i < tmp.size(); ++i) o[i] += tmp[i];
+    }
+  }
+  return (long)bytes;
+}
+
+/* test hook: how the last d2fe_netvlad* call wrote layer `layer` (-1: the pre-projected features): out[0] = hidden-channel groups of the step that wrote it,
+ * out[1] = partial slabs left in memory (1 once the slab-sum launch ran, or for a merged launch's running total) */
+int d2fe_debug_netvlad_groups(d2fe_handle h, int layer, int* out) {
+  if (!h || !out || !h->nv_net || !h->nv_run.feat_buf || layer < -1 || layer >= (int)h->nv_net->layers.size()) return fail(D2FE_ERR_INVALID, "bad argument");
+  const NvSlabs sl = layer < 0 ? h->nv_run.last.feat : h->nv_run.last.layer[layer];
+  out[0] = sl.groups; out[1] = sl.n;
+  return D2FE_OK;
 }
 
 /* test hook: the execution plan d2fe_load_netvlad would build for this layer list and proj_dim under the D2FE_NV_* switches of the environment

@@ -797,3 +797,27 @@ hipError_t launch_nv_pblock(const NvBlockArgs& a_in, int n, int groups, hipStrea
 }
 
 }  // namespace d2fe
+
+#ifdef D2FE_DEVTOOLS      /* development library only: include/d2fe_debug.h */
+/* test hook: the (NK, NT) pairs the dispatch above has kernels for, from the same X-macros (family 0 NVP_SHAPES, 1 NVP_MERGE_SHAPES); needs no GPU */
+extern "C" int d2fe_debug_netvlad_shapes(int family, int* out, int max) {
+  if (family < 0 || family > 1 || max < 0 || (max > 0 && !out)) return D2FE_ERR_INVALID;
+  int n = 0;
+  auto put = [&](int nk, int nt) { if (n < max) { out[2 * n] = nk; out[2 * n + 1] = nt; } ++n; };
+  if (family == 0) {
+#define X(K, T) put(K, T);
+    NVP_SHAPES(X)
+#undef X
+  } else {
+#define X(K, T, M) put(K, T);
+    NVP_MERGE_SHAPES(X)
+#undef X
+  }
+  return n;
+}
+/* test hook: nv_pblock_slots, the resident workgroups run_netvlad compares a pixel-pair launch with (needs no GPU) */
+extern "C" long d2fe_debug_netvlad_slots(int cin, int cout, int ncu, int nbuf) {
+  if (cin < 4 || (cin & 3) || d2fe::nv_pblock_halves(cout) < 0 || cout < 1 || nbuf < 1 || nbuf > 2) return D2FE_ERR_INVALID;
+  return d2fe::nv_pblock_slots(cin, cout, ncu, nbuf);
+}
+#endif  // D2FE_DEVTOOLS

@@ -30,6 +30,18 @@ D2FE_API long d2fe_debug_netvlad_stamps(d2fe_handle h, unsigned long long* dst, 
  * 6 nv_xblock_kernel, 7 nv_pblock_kernel (`halves` launches), 8 nv_fpair_kernel, 9 the last pw + the pre-projection (nv_tail_kernel), 10 the same
  * through nv_block_kernel. */
 D2FE_API int d2fe_debug_netvlad_plan(const d2fe_nv_layer* layers, int n_layers, int proj_dim, int* out, int max_steps);
+/* The (NK = Cin / 4, NT = 16-channel output tiles) pairs nv_pblock_kernel is compiled for, generated from the X-macros its dispatch uses (needs no GPU):
+ * family 0 every shape, family 1 the shapes that also exist with merged groups.  Writes (NK, NT) per shape, at most `max` shapes, and returns the number of shapes or <0. */
+D2FE_API int d2fe_debug_netvlad_shapes(int family, int* out, int max);
+/* NetVLAD inspection: the pre-projected features [n_images][positions][proj_dim] the VLAD stage of the last d2fe_netvlad* call read, partial slabs added in
+ * slab order (images of the handle's maximum size, as for d2fe_debug_netvlad_layer).  Returns bytes copied or <0. */
+D2FE_API long d2fe_debug_netvlad_features(d2fe_handle h, int n_images, void* dst, size_t max_bytes);
+/* How the last d2fe_netvlad* call wrote layer `layer` (-1: the pre-projected features): out[0] = the hidden-channel groups of the step that wrote it,
+ * out[1] = the partial slabs left in memory (1 once the slab-sum launch ran).  Returns 0 or <0. */
+D2FE_API int d2fe_debug_netvlad_groups(d2fe_handle h, int layer, int* out);
+/* nv_pblock_slots: the workgroups of the pixel-pair block shape (Cin, Cout) resident at once on a device of `ncu` compute units with `nbuf` E buffers, which
+ * run_netvlad compares a launch with when it merges groups (needs no GPU).  Returns the count or <0. */
+D2FE_API long d2fe_debug_netvlad_slots(int cin, int cout, int ncu, int nbuf);
 /* One 3x3 / pad 1 layer (cin 64 or 128, ReLU, optional 2x2 max-pool) through the Winograd kernels of D2FE_PREC_F32_WINO, host
  * NHWC buffers in and out; iters > 0 also times `iters` back-to-back launches (HIP events on the handle's stream).  For the
  * layer-level parity tests (tests/test_wino.py, tests/test_launch_regimes.py) and tools/; the product path is d2fe_superpoint_extract*.  Like a pass
