@@ -271,7 +271,8 @@ DEBUG_EXPORTS = [
     "d2fe_debug_graph_count", "d2fe_debug_read", "d2fe_debug_netvlad_layer", "d2fe_debug_netvlad_stamps", "d2fe_debug_pack_wino",
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
     "d2fe_debug_netvlad_plan", "d2fe_debug_netvlad_shapes", "d2fe_debug_netvlad_features", "d2fe_debug_netvlad_groups", "d2fe_debug_netvlad_slots", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
-    "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a"]
+    "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a",
+    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -334,6 +335,8 @@ def _open_library(path, dev):
             lib.d2fe_debug_sample_b.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp]
             lib.d2fe_debug_sample_b_pca.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, ci, vp]
             lib.d2fe_debug_nms2_a.argtypes = [vp, vp, ci, ci, ci, C.c_float, ci, ci, ci, vp, vp, vp, vp]
+            lib.d2fe_debug_desc_head_sparse.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+            lib.d2fe_debug_sample_a.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, ci, vp, vp, ci, vp]
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
         lib.d2fe_half_move_cols.argtypes = [C.c_int, C.c_double]
@@ -1077,6 +1080,49 @@ class DevFrontEnd(FrontEnd):
         kps = np.empty((n, cap, 2), np.float32); sc = np.empty((n, cap), np.float32); idx = np.empty((n, cap), np.int32); m = np.empty(n, np.int32)
         _check(self._lib.d2fe_debug_nms2_a(self._h, _ptr(semi), n, H, W, float(thr), int(dist), int(max_kp), int(cap), _ptr(kps), _ptr(sc), _ptr(idx), _ptr(m)))
         return [(kps[i, :m[i]].copy(), sc[i, :m[i]].copy(), idx[i, :m[i]].copy()) for i in range(n)]
+
+    # ---- the sparse descriptor head and variant A's descriptor tail on injected tensors (include/d2fe_debug.h; tests/test_desc_head_edges.py) ----
+    def debug_desc_head_sparse(self, x, kps_xy, n_kp, max_slots, w_da, b_da, w_db, b_db, with_mid=False, img_w=0, img_h=0):
+        """launch_desc_head_sparse on x [n, Hc, Wc, x_cstride >= 128] (channels 128.. are padding), kps_xy [n, cap, 2], n_kp [n]; w_da [256, 128, 3, 3],
+        w_db [256, 256, 1, 1].  img_w = 0: variant B's corners, else variant A's.  Returns (store [n, max_slots, 256], slotmap [n, Hc, Wc], cells [n, max_slots],
+        count [n]); what the kernels did not write holds all-ones words."""
+        x = np.ascontiguousarray(x, np.float32); kps_xy = np.ascontiguousarray(kps_xy, np.float32); n_kp = np.ascontiguousarray(n_kp, np.int32)
+        w_da = np.ascontiguousarray(w_da, np.float32); b_da = np.ascontiguousarray(b_da, np.float32)
+        w_db = np.ascontiguousarray(w_db, np.float32); b_db = np.ascontiguousarray(b_db, np.float32)
+        assert w_da.shape == (256, 128, 3, 3) and w_db.shape == (256, 256, 1, 1) and b_da.shape == (256,) and b_db.shape == (256,)
+        n, Hc, Wc, xs = x.shape
+        cap = kps_xy.shape[1]
+        assert kps_xy.shape == (n, cap, 2) and n_kp.shape == (n,)
+        ms = max(int(max_slots), 1)
+        store = np.empty((n, ms, 256), np.float32); slotmap = np.empty((n, Hc, Wc), np.int32)
+        cells = np.empty((n, ms), np.int32); count = np.empty(n, np.int32)
+        _check(self._lib.d2fe_debug_desc_head_sparse(self._h, _ptr(x), xs, n, Hc, Wc, _ptr(kps_xy), _ptr(n_kp), cap, int(max_slots), int(bool(with_mid)),
+                                                     int(img_w), int(img_h), _ptr(w_da), _ptr(b_da), _ptr(w_db), _ptr(b_db), _ptr(slotmap), _ptr(cells),
+                                                     _ptr(count), _ptr(store)))
+        return store, slotmap, cells, count
+
+    def debug_sample_a(self, desc_raw, kps_xy, n_kp, img_w, img_h, scap=None, dcoff=0, slotmap=None, comp=None, mean=None):
+        """Variant A's computeDescriptors (sample_a_kernel, chan_norm_a_kernel, finish_a_kernel); desc_raw / slotmap as for debug_sample_b, scap = keypoints
+        per image of the sampling scratch (cap by default), comp [pca_dims, 256] with mean [256] or None.  Returns desc [n, cap, pca_dims or 256]."""
+        desc_raw = np.ascontiguousarray(desc_raw, np.float32); kps_xy = np.ascontiguousarray(kps_xy, np.float32)
+        n_kp = np.ascontiguousarray(n_kp, np.int32)
+        n, cap = kps_xy.shape[0], kps_xy.shape[1]
+        if slotmap is None:
+            _, Hc, Wc, dstride = desc_raw.shape
+            max_slots = 0
+        else:
+            slotmap = np.ascontiguousarray(slotmap, np.int32)
+            _, Hc, Wc = slotmap.shape
+            dstride, max_slots = 256, desc_raw.shape[1]
+        pd = 0
+        if comp is not None:
+            comp = np.ascontiguousarray(comp, np.float32); mean = np.ascontiguousarray(mean, np.float32)
+            assert comp.ndim == 2 and comp.shape[1] == 256 and mean.shape == (256,)
+            pd = comp.shape[0]
+        out = np.empty((n, cap, pd or 256), np.float32)
+        _check(self._lib.d2fe_debug_sample_a(self._h, _ptr(desc_raw), dstride, int(dcoff), n, Hc, Wc, int(img_w), int(img_h), _ptr(kps_xy), _ptr(n_kp), cap,
+                                             int(cap if scap is None else scap), _ptr(slotmap), max_slots, _ptr(comp), _ptr(mean), pd, _ptr(out)))
+        return out
 
     # ---- NetVLAD inspection (include/d2fe_debug.h; tests/test_netvlad_shapes*.py) ----
     @staticmethod

@@ -1,11 +1,12 @@
 // debug_hooks.hip -- the development library's hooks (include/d2fe_debug.h) that need nothing of the handle but its device and stream: the launch-regime
-// record, the host-side packings, one Winograd layer, the SuperPoint tail kernels on injected tensors, the count of captured launch sequences.  (The hooks that
-// read a unit's own state back live with that state: d2fe_debug_read in superpoint_host.hip, the NetVLAD ones in netvlad_host.hip, the matcher's stamps in
-// match_host.hip.)  The whole unit compiles to nothing for the product library.
+// record, the host-side packings, one Winograd layer, the SuperPoint tail kernels, the sparse descriptor head and variant A's descriptor tail on injected
+// tensors, the count of captured launch sequences.  (The hooks that read a unit's own state back live with that state: d2fe_debug_read in
+// superpoint_host.hip, the NetVLAD ones in netvlad_host.hip, the matcher's stamps in match_host.hip.)  The whole unit compiles to nothing for the product library.
 #ifdef D2FE_DEVTOOLS
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -205,16 +206,74 @@ int d2fe_debug_select_b(d2fe_handle h, const unsigned long long* cand, const int
   return D2FE_OK;
 }
 
+// The cells a sampler looks up for one keypoint, restated on the host from the reference lines sample_b_corners and sample_a_origin (postproc.hip) cite; host and
+// device code are both compiled with -ffp-contract=off.  img_w > 0: variant A's corners, -1 where one is padding; else variant B's clipped corners.
+static void lookup_cells(float x, float y, int Hc, int Wc, int img_w, int img_h, int cell[4]) {
+  float ix, iy;
+  if (img_w > 0) {
+    const float gx = 2.0f * x / (float)img_w - 1.0f, gy = 2.0f * y / (float)img_h - 1.0f;
+    ix = ((gx + 1.0f) * (float)Wc - 1.0f) / 2.0f;
+    iy = ((gy + 1.0f) * (float)Hc - 1.0f) / 2.0f;
+  } else {
+    float k0 = (float)((double)(x - 4.0f) + 0.5), k1 = (float)((double)(y - 4.0f) + 0.5);
+    k0 = (float)((double)k0 / ((double)(Wc * 8 - 4) - 0.5));
+    k1 = (float)((double)k1 / ((double)(Hc * 8 - 4) - 0.5));
+    k0 = k0 * 2.0f - 1.0f;
+    k1 = k1 * 2.0f - 1.0f;
+    ix = ((k0 + 1.0f) / 2.0f) * (float)(Wc - 1);
+    iy = ((k1 + 1.0f) / 2.0f) * (float)(Hc - 1);
+  }
+  // (int)floorf as the device converts: NaN -> 0, out of range -> saturated (here: to just outside the map, which clips and tests the same)
+  auto fl = [](float v, int n) { const float f = floorf(v); return f != f ? 0 : f < -2.f ? -2 : f > (float)(n + 1) ? n + 1 : (int)f; };
+  auto clip = [](int v, int n) { return v < 0 ? 0 : (v < n - 1 ? v : n - 1); };
+  int x0 = fl(ix, Wc), y0 = fl(iy, Hc);
+  if (img_w <= 0) { x0 = clip(x0, Wc); y0 = clip(y0, Hc); }
+  for (int q = 0; q < 4; ++q) {
+    int xx = x0 + (q & 1), yy = y0 + (q >> 1);
+    if (img_w <= 0) { xx = clip(xx, Wc); yy = clip(yy, Hc); }
+    cell[q] = (xx >= 0 && xx < Wc && yy >= 0 && yy < Hc) ? yy * Wc + xx : -1;
+  }
+}
+
+// The slot map of a sampler hook: an entry names a slot of the store or is -1 (no slot, as the sparse head leaves a cell it did not compute), and every cell the
+// first kmax keypoints of a list look up names a slot.
+static int check_slotmap(const int32_t* slotmap, int max_slots, int n, int Hc, int Wc, int img_w, int img_h, const float* kps_xy, const int32_t* n_kp, int cap,
+                         int kmax) {
+  if (max_slots < 1 || max_slots > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "max_slots");
+  const size_t ncell = (size_t)Hc * Wc;
+  for (size_t i = 0; i < (size_t)n * ncell; ++i)
+    if (slotmap[i] < -1 || slotmap[i] >= max_slots) return fail(D2FE_ERR_INVALID, "slot map entry outside [-1, max_slots)");
+  for (int img = 0; img < n; ++img)
+    for (int k = 0; k < n_kp[img] && k < kmax; ++k) {
+      int cell[4];
+      lookup_cells(kps_xy[2 * ((size_t)img * cap + k)], kps_xy[2 * ((size_t)img * cap + k) + 1], Hc, Wc, img_w, img_h, cell);
+      for (int q = 0; q < 4; ++q)
+        if (cell[q] >= 0 && slotmap[img * ncell + cell[q]] < 0) return fail(D2FE_ERR_INVALID, "a cell the sampler looks up has no slot");
+    }
+  return D2FE_OK;
+}
+
+// The sparse store [rows][256] of a sampler hook, uploaded behind one guard row of all-ones words (NaN): should the device look a cell up that check_slotmap did
+// not foresee, its entry of -1 reads the guard row (image 0) or the previous image's last slot, not memory in front of the allocation.
+static hipError_t sparse_store_upload(DevPool& b, float** out, const float* src, size_t rows) {
+  float* base = nullptr;
+  hipError_t e = b.alloc(&base, sizeof(float) * 256 * (rows + 1));
+  if (e != hipSuccess) return e;
+  e = hipMemset(base, 0xff, sizeof(float) * 256);
+  if (e != hipSuccess) return e;
+  *out = base + 256;
+  return hipMemcpy(*out, src, sizeof(float) * 256 * rows, hipMemcpyHostToDevice);
+}
+
 // comp == nullptr: d2fe_debug_sample_b (rows of 256 floats); else d2fe_debug_sample_b_pca (rows of pca_dims floats)
 static int debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
                           const int32_t* slotmap_or_null, int max_slots, const float* comp, const float* mean, int pca_dims, float* desc_out) {
   if (!h || !desc_raw || !kps_xy || !n_kp || !desc_out) return fail(D2FE_ERR_INVALID, "null argument");
   if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "bad geometry");
   const size_t ncell = (size_t)Hc * Wc;
-  if (slotmap_or_null) {      // sparse store [img][max_slots][256]: every cell the kernel may look up must name a slot of the store
-    if (max_slots < 1 || max_slots > DEBUG_MAX_PIXELS) return fail(D2FE_ERR_INVALID, "max_slots");
-    for (size_t i = 0; i < (size_t)n * ncell; ++i)
-      if (slotmap_or_null[i] < 0 || slotmap_or_null[i] >= max_slots) return fail(D2FE_ERR_INVALID, "slot map entry outside [0, max_slots)");
+  if (slotmap_or_null) {      // sparse store [img][max_slots][256]
+    const int rc = check_slotmap(slotmap_or_null, max_slots, n, Hc, Wc, 0, 0, kps_xy, n_kp, cap, cap);
+    if (rc) return rc;
   } else if (dcoff < 0 || (dcoff & 3) || (dstride & 3) || dstride < dcoff + 256 || dstride > 4096) {
     return fail(D2FE_ERR_INVALID, "dense form: dcoff and dstride are multiples of 4 with dcoff + 256 <= dstride");
   }
@@ -222,7 +281,8 @@ static int debug_sample_b(d2fe_handle h, const float* desc_raw, int dstride, int
   DevPool b;
   float *d_raw = nullptr, *d_kps = nullptr, *d_desc = nullptr;
   int32_t *d_n = nullptr, *d_map = nullptr;
-  HIP_TRY(b.get(&d_raw, sizeof(float) * n * (slotmap_or_null ? (size_t)max_slots * 256 : ncell * dstride), desc_raw));
+  if (slotmap_or_null) HIP_TRY(sparse_store_upload(b, &d_raw, desc_raw, (size_t)n * max_slots));
+  else HIP_TRY(b.get(&d_raw, sizeof(float) * n * ncell * dstride, desc_raw));
   HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
   HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, n_kp));
   if (slotmap_or_null) HIP_TRY(b.get(&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
@@ -286,6 +346,97 @@ int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, flo
   HIP_TRY(hipMemcpy(scores, d_sc, sizeof(float) * n * cap, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(kps_idx, d_idx, sizeof(int32_t) * n * cap, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(n_out, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+// ---- the sparse descriptor head and variant A's descriptor tail on injected tensors (tests/test_desc_head_edges.py) ----
+namespace {
+constexpr long DEBUG_MAX_HEAD_CELLS = 1l << 17;      // cells per call: above launch_desc_head_sparse's 60 Ki threshold between its two mark / compact forms
+}  // namespace
+
+int d2fe_debug_desc_head_sparse(d2fe_handle h, const float* x, int x_cstride, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                                int max_slots, int with_mid, int img_w, int img_h, const float* w_da, const float* b_da, const float* w_db, const float* b_db,
+                                int32_t* slotmap_out, int32_t* cells_out, int32_t* count_out, float* store_out) {
+  if (!h || !x || !kps_xy || !n_kp || !w_da || !b_da || !w_db || !b_db || !slotmap_out || !cells_out || !count_out || !store_out)
+    return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || cap > DEBUG_MAX_PIXELS || max_slots < 1 || max_slots > DEBUG_MAX_PIXELS || x_cstride < 128 || (x_cstride & 3) ||
+      x_cstride > 4096 || (long)n * Hc * Wc > DEBUG_MAX_HEAD_CELLS || img_w < 0 || (img_w > 0 && img_h < 1))
+    return fail(D2FE_ERR_INVALID, "bad geometry");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  const size_t ncell = (size_t)Hc * Wc;
+  // the fragments of the L_DA32 / L_DB32 records (superpoint_host.hip)
+  std::vector<float> pa(packed_weight_floats_f32(256, 128, 3)), pb(packed_weight_floats_f32(256, 256, 1));
+  pack_weights_f32(w_da, 256, 128, 3, 256, pa.data());
+  pack_weights_f32(w_db, 256, 256, 1, 256, pb.data());
+  const int mid_imgs = with_mid ? (n < 4 ? n : 4) : 0;
+  DevPool b;
+  float *d_x = nullptr, *d_kps = nullptr, *d_wa = nullptr, *d_ba = nullptr, *d_wb = nullptr, *d_bb = nullptr, *d_store = nullptr, *d_mid = nullptr;
+  int32_t *d_n = nullptr, *d_map = nullptr, *d_cells = nullptr, *d_cnt = nullptr;
+  uint8_t* d_flags = nullptr;
+  HIP_TRY(b.get(&d_x, sizeof(float) * n * ncell * x_cstride, x));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, n_kp));
+  HIP_TRY(b.get(&d_wa, sizeof(float) * pa.size(), pa.data()));
+  HIP_TRY(b.get(&d_ba, sizeof(float) * 256, b_da));
+  HIP_TRY(b.get(&d_wb, sizeof(float) * pb.size(), pb.data()));
+  HIP_TRY(b.get(&d_bb, sizeof(float) * 256, b_db));
+  HIP_TRY(b.get(&d_flags, n * ncell, nullptr));
+  HIP_TRY(b.get(&d_map, sizeof(int32_t) * n * ncell, nullptr));
+  HIP_TRY(b.get(&d_cells, sizeof(int32_t) * n * max_slots, nullptr));
+  HIP_TRY(b.get(&d_cnt, sizeof(int32_t) * n, nullptr));
+  HIP_TRY(b.get(&d_store, sizeof(float) * 256 * n * max_slots, nullptr));
+  if (mid_imgs) HIP_TRY(b.get(&d_mid, sizeof(float) * 256 * mid_imgs * max_slots, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_desc_head_sparse(d_kps, d_n, cap, Hc, Wc, n, d_x, x_cstride, (long)ncell * x_cstride, d_wa, d_ba, d_wb, d_bb, d_flags, d_map, d_cells, d_cnt,
+                                  max_slots, d_store, d_mid, mid_imgs, img_w, img_h, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(slotmap_out, d_map, sizeof(int32_t) * n * ncell, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cells_out, d_cells, sizeof(int32_t) * n * max_slots, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(count_out, d_cnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(store_out, d_store, sizeof(float) * 256 * n * max_slots, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_sample_a(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, int img_w, int img_h, const float* kps_xy,
+                        const int32_t* n_kp, int cap, int scap, const int32_t* slotmap_or_null, int max_slots, const float* comp_or_null, const float* mean,
+                        int pca_dims, float* desc_out) {
+  if (!h || !desc_raw || !kps_xy || !n_kp || !desc_out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (n < 1 || Hc < 2 || Wc < 2 || cap < 1 || scap < 1 || img_w < 1 || img_h < 1 || (long)Hc * Wc * 64 > DEBUG_MAX_PIXELS || cap > DEBUG_MAX_PIXELS ||
+      scap > DEBUG_MAX_PIXELS)
+    return fail(D2FE_ERR_INVALID, "bad geometry");
+  if (comp_or_null && (!mean || pca_dims < 1 || pca_dims > 256)) return fail(D2FE_ERR_INVALID, "comp needs mean and pca_dims in 1..256");
+  const size_t ncell = (size_t)Hc * Wc;
+  if (slotmap_or_null) {
+    const int rc = check_slotmap(slotmap_or_null, max_slots, n, Hc, Wc, img_w, img_h, kps_xy, n_kp, cap, cap < scap ? cap : scap);
+    if (rc) return rc;
+  } else if (dcoff < 0 || (dcoff & 3) || (dstride & 3) || dstride < dcoff + 256 || dstride > 4096) {
+    return fail(D2FE_ERR_INVALID, "dense form: dcoff and dstride are multiples of 4 with dcoff + 256 <= dstride");
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  DevPool b;
+  float *d_raw = nullptr, *d_kps = nullptr, *d_desc = nullptr, *d_samp = nullptr, *d_cn = nullptr, *d_comp_t = nullptr, *d_mean = nullptr;
+  int32_t *d_n = nullptr, *d_map = nullptr;
+  if (slotmap_or_null) HIP_TRY(sparse_store_upload(b, &d_raw, desc_raw, (size_t)n * max_slots));
+  else HIP_TRY(b.get(&d_raw, sizeof(float) * n * ncell * dstride, desc_raw));
+  HIP_TRY(b.get(&d_kps, sizeof(float) * 2 * n * cap, kps_xy));
+  HIP_TRY(b.get(&d_n, sizeof(int32_t) * n, n_kp));
+  if (slotmap_or_null) HIP_TRY(b.get(&d_map, sizeof(int32_t) * n * ncell, slotmap_or_null));
+  const size_t D = comp_or_null ? (size_t)pca_dims : 256;
+  if (comp_or_null) {      // the transposed layout d2fe_set_superpoint_pca uploads: comp_t [256][pca_dims]
+    std::vector<float> t((size_t)256 * pca_dims);
+    for (int j = 0; j < pca_dims; ++j)
+      for (int c = 0; c < 256; ++c) t[(size_t)c * pca_dims + j] = comp_or_null[(size_t)j * 256 + c];
+    HIP_TRY(b.get(&d_comp_t, sizeof(float) * t.size(), t.data()));
+    HIP_TRY(b.get(&d_mean, sizeof(float) * 256, mean));
+  }
+  HIP_TRY(b.get(&d_samp, sizeof(float) * 256 * n * scap, nullptr));
+  HIP_TRY(b.get(&d_cn, sizeof(float) * 256 * n, nullptr));
+  HIP_TRY(b.get(&d_desc, sizeof(float) * D * n * cap, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_sample_a(d_raw, dstride, dcoff, Hc, Wc, img_w, img_h, n, d_kps, d_n, cap, d_comp_t, d_mean, comp_or_null ? pca_dims : 0, d_samp, scap, d_cn,
+                          d_map, max_slots, d_desc, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * D * n * cap, hipMemcpyDeviceToHost));
   return D2FE_OK;
 }
 

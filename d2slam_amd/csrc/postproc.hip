@@ -815,6 +815,9 @@ hipError_t launch_desc_head_sparse(const float* kps_xy, const int32_t* n_kp, int
   a.x = x; a.x_cstride = x_cstride; a.x_img_stride = x_img_stride; a.w_da = w_da; a.b_da = b_da; a.w_db = w_db; a.b_db = b_db;
   a.cells = cells; a.count = count; a.max_slots = max_slots; a.Hc = Hc; a.Wc = Wc; a.out = out; a.mid = mid;
   const int slots = std::min(max_slots, 4 * cap);
+  // the form by (n_img, mid): n_img >= 8 -> <2,8,0>; n_img <= 4 with a mid of at least n_img images -> the split pair <1,4,1> / <1,4,2>; everything else --
+  // 5 to 7 images, or up to 4 without a mid -> <1,8,0>.  tests/test_desc_head_edges.py (HEAD_FORMS) reaches each of them through d2fe_debug_desc_head_sparse
+  // with (n, with_mid) = (1, 1) and (4, 1) | (4, 0) and (5, any) | (8, any), and restates this rule on the host.
   if (n_img >= 8) {
     constexpr size_t lds = sizeof(float) * (64 * 257 + 64);
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(desc_head_sparse_kernel<2, 8, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

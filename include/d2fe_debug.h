@@ -69,7 +69,8 @@ D2FE_API int d2fe_debug_conv3x3_wino(d2fe_handle h, const float* in, int n, int 
  *   select_b:     cand [n][cand_cap], cand_count [n] (an entry above cand_cap is refused), semi_or_null [n][H][W] -> kps_xy [n][cap][2], scores [n][cap],
  *                 kps_idx [n][cap], n_out [n]; entries at and beyond n_out are unspecified.
  *   sample_b:     desc_raw [n][Hc*Wc][dstride] read at channel offset dcoff (slotmap_or_null == NULL), or the sparse store [n][max_slots][256] with
- *                 slotmap [n][Hc*Wc] (every entry in [0, max_slots)); kps_xy [n][cap][2], n_kp [n] -> desc_out [n][cap][256].
+ *                 slotmap [n][Hc*Wc] (every entry in [-1, max_slots); -1 = no slot, as the sparse head leaves a cell it did not compute; every cell the
+ *                 lists look up, worked out on the host, must name a slot); kps_xy [n][cap][2], n_kp [n] -> desc_out [n][cap][256].
  *   nms2_a:       semi [n][H][W] -> variant A's keypoints: nms2_a_kernel, select_b_kernel (always_sort, no border), and nms2_wrap_fix_kernel when H*W > 65536. */
 D2FE_API int d2fe_debug_softmax_cand(d2fe_handle h, const float* logits, int lstride, int n, int Hc, int Wc, float thr, int border, int want_semi,
                                      float* semi_out, unsigned long long* cand_out, int* cand_count_out);
@@ -85,6 +86,24 @@ D2FE_API int d2fe_debug_sample_b_pca(d2fe_handle h, const float* desc_raw, int d
                                      int pca_dims, float* desc_out);
 D2FE_API int d2fe_debug_nms2_a(d2fe_handle h, const float* semi, int n, int H, int W, float thr, int dist, int max_kp, int cap, float* kps_xy, float* scores,
                                int32_t* kps_idx, int32_t* n_out);
+
+/* The sparse descriptor head and variant A's descriptor tail (csrc/postproc.hip) on injected tensors, for tests/test_desc_head_edges.py; buffers, refusals and
+ * the all-ones start of every output as for the hooks above.
+ *   desc_head_sparse: launch_desc_head_sparse -- mark and compact (one launch up to 60 Ki cells, two above), then convDa + ReLU + convDb at the marked cells.
+ *                 x [n][Hc*Wc][x_cstride] (a multiple of 4, at least 128; channels 128.. are padding), kps_xy [n][cap][2], n_kp [n]; w_da [256][128][3][3],
+ *                 b_da [256], w_db [256][256][1][1], b_db [256], packed here as the extractor packs them.  img_w == 0: variant B's corner rule; else variant
+ *                 A's for an img_w x img_h image.  with_mid != 0 hands the launcher a `mid` buffer of min(n, 4) images, 0 none: the launcher's own rule picks
+ *                 the kernel form from (n, with_mid).  -> slotmap_out [n][Hc*Wc], cells_out [n][max_slots], count_out [n], store_out [n][max_slots][256].
+ *                 At most 2^17 cells per call; max_slots >= 1.
+ *   sample_a:     sample_a_kernel, chan_norm_a_kernel, finish_a_kernel.  desc_raw / slotmap_or_null / max_slots as for sample_b; img_w, img_h >= 1;
+ *                 scap >= 1 = keypoints per image of the sampling scratch; comp_or_null [pca_dims][256] with mean [256] and pca_dims in 1..256, or NULL
+ *                 -> desc_out [n][cap][pca_dims or 256]. */
+D2FE_API int d2fe_debug_desc_head_sparse(d2fe_handle h, const float* x, int x_cstride, int n, int Hc, int Wc, const float* kps_xy, const int32_t* n_kp, int cap,
+                                         int max_slots, int with_mid, int img_w, int img_h, const float* w_da, const float* b_da, const float* w_db,
+                                         const float* b_db, int32_t* slotmap_out, int32_t* cells_out, int32_t* count_out, float* store_out);
+D2FE_API int d2fe_debug_sample_a(d2fe_handle h, const float* desc_raw, int dstride, int dcoff, int n, int Hc, int Wc, int img_w, int img_h, const float* kps_xy,
+                                 const int32_t* n_kp, int cap, int scap, const int32_t* slotmap_or_null, int max_slots, const float* comp_or_null,
+                                 const float* mean, int pca_dims, float* desc_out);
 
 /* Host-pointer calls replay cached hipGraphs of their launch sequences from the third call with the same geometry on (D2FE_GRAPH=0 in the
  * environment turns that off).  Returns how many graphs the handle holds; *rejected (may be NULL) = geometries whose capture failed and which
