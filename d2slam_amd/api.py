@@ -175,6 +175,14 @@ class _QuadTrackResult(C.Structure):
                 ("lnb_q", C.c_void_p), ("lnb_t", C.c_void_p), ("lnb_dist", C.c_void_p), ("lnb_n", C.c_void_p)]
 
 
+class _QuadFlowResult(C.Structure):
+    """d2fe_quad_flow_result: the flow lists and neighbour tracks of a quad ticket (d2fe_quad_flow_enable)"""
+    _fields_ = [("quads", C.c_int32), ("cap_tracks", C.c_int32), ("list_words", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_void_p), ("n_tracked_in", C.c_void_p), ("n_lost", C.c_void_p), ("n_removed_near", C.c_void_p), ("n_new", C.c_void_p), ("lack", C.c_void_p),
+                ("num", C.c_void_p), ("n_cand", C.c_void_p), ("pts_xy", C.c_void_p), ("id", C.c_void_p), ("src", C.c_void_p),
+                ("nb_lk_xy", C.c_void_p), ("nb_lk_status", C.c_void_p)]
+
+
 class _QuadDeviceResult(C.Structure):
     _fields_ = [("quads", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
                 ("d_kps_xy", C.c_void_p), ("d_scores", C.c_void_p), ("d_desc", C.c_void_p), ("d_n_kp", C.c_void_p), ("d_netvlad", C.c_void_p)]
@@ -252,6 +260,7 @@ EXPORTS = [
     "d2fe_pipe_set_track_params", "d2fe_pipe_camera_default", "d2fe_pipe_create_camera", "d2fe_pipe_submit_depth", "d2fe_pipe_depth_result_get", "d2fe_depth_at_device", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
     "d2fe_flow_default_params", "d2fe_lk_flow_list_bytes", "d2fe_lk_flow_list_offset", "d2fe_lk_flow_scratch_bytes", "d2fe_detect_fast_device", "d2fe_lk_flow_step_device",
     "d2fe_pipe_flow_enable", "d2fe_pipe_flow_result_get",
+    "d2fe_lk_flow_quad_step_device", "d2fe_lk_flow_neighbour_device", "d2fe_quad_flow_enable", "d2fe_quad_flow_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -442,6 +451,12 @@ def _open_library(path, dev):
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_flow_enable.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_flow_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_lk_flow_quad_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.d2fe_lk_flow_neighbour_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_flow_enable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_flow_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_quad_track_enable.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_quad_track_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_set_track_params.argtypes = [C.c_void_p, C.c_void_p]
@@ -1488,12 +1503,16 @@ class QuadPipe(_Owned):
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits).
     Temporal pairs: view c of quad frame q against view c of quad frame q - 1 (q = 0: the last quad frame of the previous submit).
     sp_lk=True (d2fe_quad_track_enable; track_params: a dict of d2fe_track_params fields, a _TrackParams or None for the reference's defaults): the LK-carried
-    landmark lists of the four cameras, the neighbour LK tracks and the neighbour matches of the lists; wait() then carries the track_* keys."""
+    landmark lists of the four cameras, the neighbour LK tracks and the neighbour matches of the lists; wait() then carries the track_* keys.
+    flow_lk=True (d2fe_quad_flow_enable; excludes sp_lk; flow_params: a dict of flow_params() keywords, a _FlowParams or None for the reference's defaults): the flow
+    landmarks of the four cameras beside SuperPoint and their neighbour LK tracks; wait() then also returns per list (q, c) "flow_n", "flow_n_tracked_in",
+    "flow_n_lost", "flow_n_removed_near", "flow_n_new", "flow_lack", "flow_num", "flow_n_cand" [quads, 4], "flow_pts" [quads, 4, cap_tracks, 2], "flow_id" /
+    "flow_src" [quads, 4, cap_tracks], and "flow_nb_lk_xy" [quads, 4, cap_tracks, 2] / "flow_nb_lk_status" [quads, 4, cap_tracks] per neighbour pair."""
     _HANDLE, _DESTROY = "_p", "d2fe_quad_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, maps, lanes=4, quads=1, raw_width=1280, raw_height=800, width=800, height=400, cap=None, netvlad=True,
                  match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False,
-                 sp_lk=False, track_params=None):
+                 sp_lk=False, track_params=None, flow_lk=False, flow_params=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _QuadPipeConfig()
@@ -1528,13 +1547,28 @@ class QuadPipe(_Owned):
         self._pinned_input = bool(pinned_input)
         self._res = _QuadPipeResult()
         self._track_res = _QuadTrackResult()
+        self._flow_res = _QuadFlowResult()
         self._sp_lk = False
-        if sp_lk:
-            try:
+        self._flow = False
+        try:
+            if sp_lk:
                 self.track_enable(track_params)
-            except Exception:
-                self.close()
-                raise
+            if flow_lk:
+                self.flow_enable(flow_params)
+        except Exception:
+            self.close()
+            raise
+
+    def flow_enable(self, fp=None):
+        """d2fe_quad_flow_enable: once, before the first submit (fp: a dict of flow_params() keywords, a _FlowParams, or None for the reference's defaults)"""
+        fp = flow_params(**fp) if isinstance(fp, dict) else fp
+        _check(self._lib.d2fe_quad_flow_enable(self._p, C.byref(fp) if fp is not None else None))
+        self._flow = True
+
+    def flow_result_raw(self, ticket):
+        """d2fe_quad_flow_result_get: the flow lists of a ticket that wait() has returned (D2FE_ERR_UNSUPPORTED without the mode)"""
+        _check(self._lib.d2fe_quad_flow_result_get(self._p, C.c_int64(ticket), C.byref(self._flow_res)))
+        return self._flow_res
 
     def track_enable(self, tp=None):
         """d2fe_quad_track_enable: once, before the first submit (tp: dict of d2fe_track_params fields, a _TrackParams, or None for the defaults)"""
@@ -1614,6 +1648,18 @@ class QuadPipe(_Owned):
             for k in ("q", "t"):
                 out["track_lnb_" + k] = _pinned_view(getattr(t, "lnb_" + k), (Q, 4, T), i)
             out["track_lnb_dist"] = _pinned_view(t.lnb_dist, (Q, 4, T), f); out["track_lnb_n"] = _pinned_view(t.lnb_n, (Q, 4), i)
+        if self._flow:
+            t = self.flow_result_raw(ticket)
+            T, lw = t.cap_tracks, t.list_words
+
+            def flist(ptr, shape, dt):         # as per_list above, over the flow-list blocks
+                base = _pinned_view(ptr, ((Q * 4 - 1) * lw + int(np.prod(shape or (1,))),), dt)
+                return np.lib.stride_tricks.as_strided(base, (Q, 4) + tuple(shape), (16 * lw, 4 * lw) + tuple(np.zeros(shape, dt).strides), writeable=False)
+            for k in ("n", "n_tracked_in", "n_lost", "n_removed_near", "n_new", "lack", "num", "n_cand"):
+                out["flow_" + k] = flist(getattr(t, k), (), i)
+            out["flow_pts"] = flist(t.pts_xy, (T, 2), f); out["flow_id"] = flist(t.id, (T,), i); out["flow_src"] = flist(t.src, (T,), i)
+            out["flow_nb_lk_xy"] = _pinned_view(t.nb_lk_xy, (Q, 4, T, 2), f)
+            out["flow_nb_lk_status"] = np.frombuffer((C.c_uint8 * (Q * 4 * T)).from_address(t.nb_lk_status), dtype=np.uint8).reshape(Q, 4, T)
         return out
 
 
@@ -1876,6 +1922,24 @@ def lk_flow_step_device(fe: FrontEnd, d_prev_pyr, d_cur_pyr, width, height, d_pr
     fp = fp if fp is not None else flow_params()
     _check(fe._lib.d2fe_lk_flow_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(width), int(height), d_prev_list, d_cur_list, d_kps_xy or None, d_n_kp or None,
                                             int(kp_cap), C.byref(fp), d_next_id, d_scratch, stream))
+
+
+def lk_flow_quad_step_device(fe: FrontEnd, d_prev_pyr, d_cur_pyr, pyr_stride, width, height, d_prev_lists, d_cur_lists, list_stride, d_kps_xy, d_n_kp, kp_cap,
+                             d_next_id, d_scratch, scratch_stride, fp=None, stream=None):
+    """The four cameras' flow lists of one quad frame in FIVE launches (d2fe_lk_flow_quad_step_device): camera c's lists / pyramids / detector scratch are
+    c * list_stride words / c * pyr_stride bytes / c * scratch_stride bytes behind the bases, its keypoints row c of the dense [4][kp_cap] extract outputs.  The bytes
+    of four lk_flow_step_device calls in camera order."""
+    fp = fp if fp is not None else flow_params()
+    _check(fe._lib.d2fe_lk_flow_quad_step_device(fe.handle, d_prev_pyr, d_cur_pyr, int(pyr_stride), int(width), int(height), d_prev_lists, d_cur_lists, int(list_stride),
+                                                 d_kps_xy or None, d_n_kp or None, int(kp_cap), C.byref(fp), d_next_id, d_scratch, int(scratch_stride), stream))
+
+
+def lk_flow_neighbour_device(fe: FrontEnd, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, d_nb_xy, d_nb_status, tp=None, stream=None):
+    """trackLK(left, right, type) of the four neighbour pairs of `quads` quad frames over device-resident FLOW lists, ONE launch (d2fe_lk_flow_neighbour_device):
+    d_nb_xy [quads][4][cap_tracks][2] float32, d_nb_status [quads][4][cap_tracks] uint8 with cap_tracks = max(total_feature_num, 1), written for every slot."""
+    tp = tp if tp is not None else track_params()
+    _check(fe._lib.d2fe_lk_flow_neighbour_device(fe.handle, d_pyr, int(pyr_stride), int(quads), int(width), int(height), float(undistort_fov), d_lists,
+                                                 int(list_stride), C.byref(tp), d_nb_xy, d_nb_status, stream))
 
 
 class _LKPair(C.Structure):

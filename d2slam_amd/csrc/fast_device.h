@@ -31,15 +31,13 @@ __device__ __forceinline__ int fast_strength(const uint8_t* __restrict__ p, int 
 }
 
 // one workgroup per region: raster scan of the region interior in chunks of 1024 pixels; the first `features` corners (raster
-// order -- the deterministic stand-in for the CUDA detector's atomics-ordered max_npoints cap) get their score written
-__global__ __launch_bounds__(1024) void fast_region_kernel(const uint8_t* __restrict__ img, int stride, int sw, int sh, int rows,
-                                                           const int* __restrict__ d_features, int features, int threshold, int* __restrict__ score, int w) {
-  // the count of the device detector: read where the step before left it, never above the `features` its candidate pool was sized for; <= 0: nothing to do
-  if (d_features) features = min(features, __builtin_amdgcn_readfirstlane(d_features[0]));
-  if (features <= 0) return;
+// order -- the deterministic stand-in for the CUDA detector's atomics-ordered max_npoints cap) get their score written.  The bodies are device functions so that
+// lk_flow.hip's four-camera launches run them with one camera's image, count and score map; the single-image kernels below only call them
+__device__ __forceinline__ void fast_region_body(const uint8_t* __restrict__ img, int stride, int sw, int sh, int rows, int features, int threshold,
+                                                 int* __restrict__ score, int w, int region) {
   __shared__ int wsum[16];
   __shared__ int s_base;
-  const int region = blockIdx.x, ri = region / rows, rj = region % rows;
+  const int ri = region / rows, rj = region % rows;
   const int x0 = sw * ri, y0 = sh * rj;
   const int iw = sw - 6, ih = sh - 6;
   if (iw <= 0 || ih <= 0) return;
@@ -71,12 +69,17 @@ __global__ __launch_bounds__(1024) void fast_region_kernel(const uint8_t* __rest
   }
 }
 
-// non-max suppression (strictly greater than the 8 neighbours) + emit {x, y, response, order}
-__global__ __launch_bounds__(256) void fast_nonmax_kernel(const int* __restrict__ score, int w, int h, int sw, int sh, int cols,
-                                                          int rows, int4* __restrict__ out, int cap, int* __restrict__ count,
-                                                          const int* __restrict__ d_features) {
-  if (d_features && d_features[0] <= 0) return;
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+__global__ __launch_bounds__(1024) void fast_region_kernel(const uint8_t* __restrict__ img, int stride, int sw, int sh, int rows,
+                                                           const int* __restrict__ d_features, int features, int threshold, int* __restrict__ score, int w) {
+  // the count of the device detector: read where the step before left it, never above the `features` its candidate pool was sized for; <= 0: nothing to do
+  if (d_features) features = min(features, __builtin_amdgcn_readfirstlane(d_features[0]));
+  if (features <= 0) return;
+  fast_region_body(img, stride, sw, sh, rows, features, threshold, score, w, blockIdx.x);
+}
+
+// non-max suppression (strictly greater than the 8 neighbours) + emit {x, y, response, order}: pixel (x, y) of one score map
+__device__ __forceinline__ void fast_nonmax_body(const int* __restrict__ score, int w, int h, int sw, int sh, int cols, int rows, int4* __restrict__ out, int cap,
+                                                 int* __restrict__ count, int x, int y) {
   if (x < 1 || y < 1 || x >= w - 1 || y >= h - 1) return;
   const int s = score[(size_t)y * w + x];
   if (s <= 0) return;
@@ -88,6 +91,13 @@ __global__ __launch_bounds__(256) void fast_nonmax_kernel(const int* __restrict_
     const int k = atomicAdd(count, 1);
     if (k < cap) out[k] = int4{x, y, s, order};
   }
+}
+
+__global__ __launch_bounds__(256) void fast_nonmax_kernel(const int* __restrict__ score, int w, int h, int sw, int sh, int cols,
+                                                          int rows, int4* __restrict__ out, int cap, int* __restrict__ count,
+                                                          const int* __restrict__ d_features) {
+  if (d_features && d_features[0] <= 0) return;
+  fast_nonmax_body(score, w, h, sw, sh, cols, rows, out, cap, count, blockIdx.x * 64 + (threadIdx.x & 63), blockIdx.y * 4 + (threadIdx.x >> 6));
 }
 
 }  // namespace

@@ -439,27 +439,52 @@ int d2fe_lk_carry_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, con
   return D2FE_OK;
 }
 
-int d2fe_lk_carry_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
-                                   size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
+namespace {
+// what the two neighbour launches share: the checks and the kernel's arguments; desc_dim = 0: flow lists (cap_tracks = max(total_feature_num, 1), no descriptors)
+int neighbour_args(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists, size_t list_stride,
+                   int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, LkCarryNbArgs& r) {
   if (!h || !d_pyr || !d_lists || !tp || !d_nb_xy || !d_nb_status) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
   if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
-  if (quads < 1 || quads > 16383 || desc_dim < 1 || desc_dim > 65536 || !(undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
-  LkCarryNbArgs r{};
+  if (quads < 1 || quads > 16383 || desc_dim < 0 || desc_dim > 65536 || !(undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
   size_t total = 0;
   pyr_geometry(r.P, width, height, tp->levels, &total);
-  const CarryLayout lay = carry_layout(tp->total_feature_num + 1, desc_dim);
+  const CarryLayout lay = desc_dim > 0 ? carry_layout(tp->total_feature_num + 1, desc_dim) : carry_layout(tp->total_feature_num > 1 ? tp->total_feature_num : 1, 0);
   if (list_stride < (size_t)lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one list block");
   if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
-  HIP_TRY(hipSetDevice(ctx_device(h)));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
   r.pyr = d_pyr; r.pyr_stride = pyr_stride; r.quads = quads; r.cap = lay.cap; r.win = tp->win; r.iters = tp->iters;
   r.move_cols = d2fe_half_move_cols(width, undistort_fov);
   r.lists = static_cast<const float*>(d_lists); r.list_stride = (long)list_stride; r.off_pts = lay.off[D2FE_LKC_PTS];
   r.xy = d_nb_xy; r.status = d_nb_status;
+  return D2FE_OK;
+}
+}  // namespace
+
+int d2fe_lk_carry_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
+                                   size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
+  if (desc_dim < 1) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
+  LkCarryNbArgs r{};
+  if (const int rc = neighbour_args(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, desc_dim, tp, d_nb_xy, d_nb_status, r)) return rc;
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
-    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((lay.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
+    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((r.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
+  }
+  HIP_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+
+// the same kernel over flow lists (lk_flow.hip), which carry no descriptors
+int d2fe_lk_flow_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
+                                  size_t list_stride, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
+  LkCarryNbArgs r{};
+  if (const int rc = neighbour_args(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, 0, tp, d_nb_xy, d_nb_status, r)) return rc;
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((r.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
   }
   HIP_TRY(hipGetLastError());
   return D2FE_OK;

@@ -16,6 +16,12 @@
 // is ranked by counting the larger keys (K <= 2048: 2 x 2048 broadcast LDS reads a thread).  The merge then tests every selected candidate against the keypoints and the
 // tracked entries in parallel (a thread per candidate) and only the test against the candidates accepted before it runs in order, on one wave, as the replenish loop of
 // lk_carry.hip does.  LDS of launch 5: 16 KB keys + 8 KB indices + 8 KB order + 8 KB list + 2 KB flags + 1 KB histogram = 43 KB of the CU's 160 KB.
+//
+// The quadcam form (d2fe_lk_flow_quad_step_device; trackLocalFrames without sp_track_use_lk): the same five launches with the camera as a grid dimension -- launch 1 is
+// (slots / 4, 4 cameras) workgroups with a ticket per camera, launches 2-4 run fast_device.h's bodies on the camera's own image, `num`, score map, pool and count,
+// launch 5 is four workgroups of 1024 (43 KB of LDS each) that select and merge side by side and then take a quad-level ticket (header word 10 of camera 0's list), whose
+// last arrival hands the ids out in camera order from the one counter.  Every byte equals four single steps in camera order; a quad frame in which no camera detects
+// costs launch 1 and four empty grids.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -173,8 +179,8 @@ __device__ __forceinline__ int flow_n_kp(const LkFlowArgs& c) {
   return n_kp < 0 ? 0 : n_kp > c.kp_cap ? c.kp_cap : n_kp;
 }
 
-// launch 1: steps a-c and the decision of detectPoints
-__global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) {
+// launch 1: steps a-c and the decision of detectPoints, for workgroup bx of the nblocks that step this list
+__device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, int bx, int nblocks) {
   __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
   __shared__ int s_src[LKC_MAX];
   __shared__ int s_cnt[4];          // [1] survivors of the tracker, [2] survivors of removeNearPoints, [3] this workgroup arrived last
@@ -189,7 +195,7 @@ __global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) {
   n_prev = n_prev < 0 ? 0 : n_prev > cap ? cap : n_prev;
 
   // ---- a. track: one wave per entry of the previous list
-  const int slot = blockIdx.x * 4 + wave;
+  const int slot = bx * 4 + wave;
   if (slot < n_prev) {
     LkArgs a{};
     a.win = c.win; a.iters = c.iters;
@@ -203,7 +209,7 @@ __global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) {
   __syncthreads();
   if (tid == 0) {
     const int old = __hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == (int)gridDim.x - 1;
+    const int last = old == nblocks - 1;
     if (last) __hip_atomic_store(hdr + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch that writes this block
     s_cnt[3] = last;
   }
@@ -244,18 +250,21 @@ __global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) {
   if (tid >= 10 && tid < 64) hdr[tid] = 0;
 }
 
-// launch 5: the rest of step d and the new entries of step e
-__global__ __launch_bounds__(1024) void lk_flow_merge_kernel(LkFlowArgs c) {
+__global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) { flow_step_body(c, blockIdx.x, gridDim.x); }
+
+// launch 5: the rest of step d and the new entries of step e, for a list whose `num` is > 0.  QUAD (the four-camera launch, lk_flow_quad_merge_kernel): the ids of the new
+// entries, header word 6 and *next_id belong to the launch's last finisher, which knows the new entries of the lower cameras; they are left alone here
+template <bool QUAD>
+__device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c) {
   __shared__ SelectLds L;
   __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];      // the tracked entries, then the accepted candidates
   __shared__ uint8_t s_blocked[FLOW_KMAX];
   __shared__ int s_acc;
   int* hdr = reinterpret_cast<int*>(c.cur);
   const int num = hdr[FLOW_HDR_NUM];
-  if (num <= 0) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int m = hdr[0], lack = hdr[FLOW_HDR_LACK], n_kp = flow_n_kp(c);
-  const int id0 = *c.next_id;
+  const int id0 = QUAD ? 0 : *c.next_id;
   float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
   const int K = fast_select_sorted(c.pool, min(c.count[0], c.pool_cap), num, L);
   // the selected candidates in order (over the keys, which the ranking no longer needs) and the tracked entries
@@ -299,12 +308,115 @@ __global__ __launch_bounds__(1024) void lk_flow_merge_kernel(LkFlowArgs c) {
   int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
   for (int e = tid; e < acc; e += 1024) {
     pts[2 * (m + e)] = s_x[m + e]; pts[2 * (m + e) + 1] = s_y[m + e];
-    id[m + e] = id0 + e; src[m + e] = -1;
+    if (!QUAD) id[m + e] = id0 + e;
+    src[m + e] = -1;
   }
   if (tid == 0) {
-    hdr[0] = m + acc; hdr[4] = acc; hdr[6] = id0 + acc; hdr[FLOW_HDR_CAND] = K;
-    *c.next_id = id0 + acc;
+    hdr[0] = m + acc; hdr[4] = acc; hdr[FLOW_HDR_CAND] = K;
+    if (!QUAD) { hdr[6] = id0 + acc; *c.next_id = id0 + acc; }
   }
+}
+
+__global__ __launch_bounds__(1024) void lk_flow_merge_kernel(LkFlowArgs c) {
+  if (reinterpret_cast<const int*>(c.cur)[FLOW_HDR_NUM] <= 0) return;
+  flow_merge_body<false>(c);
+}
+
+// ---- the quadcam form ---------------------------------------------------------------------------------------------------------------------------------------
+// trackLocalFrames without sp_track_use_lk (d2featuretracker.cpp:121-133): track(images[c]) for c = 0..3 steps four flow lists per quad frame, and every new landmark
+// takes its id from ONE counter in camera order.  Four single steps are twenty launches on a chain that is serial by the algorithm; here the five launches each take
+// the camera as a grid dimension.  Camera c's lists, pyramids, keypoint row and detector scratch (its own score map, pool and count) are c strides behind camera 0's
+struct LkFlowQuadArgs {
+  LkFlowArgs c;                     // camera 0
+  long list_stride;                 // words between the cameras' lists (previous and current)
+  size_t pyr_stride;                // bytes between the cameras' pyramids (previous and current)
+  size_t scratch_stride;            // bytes between the cameras' detector scratches
+};
+constexpr int FLOW_HDR_QUAD = 10;   // header word of CAMERA 0's current list: the quad-level arrival counter of launch 5 (a "rest 0" word of include/d2fe.h; left zero)
+
+__device__ __forceinline__ LkFlowArgs flow_camera(const LkFlowQuadArgs& q, int cam) {
+  LkFlowArgs c = q.c;
+  c.prev += (size_t)cam * q.list_stride; c.cur += (size_t)cam * q.list_stride;
+  c.prev_pyr += (size_t)cam * q.pyr_stride; c.cur_pyr += (size_t)cam * q.pyr_stride;
+  if (c.kp_cap > 0) { c.kps += (size_t)cam * c.kp_cap * 2; c.n_kp += cam; }      // rows of the dense [4][kp_cap] extract outputs
+  c.pool = reinterpret_cast<const int4*>(reinterpret_cast<const char*>(c.pool) + (size_t)cam * q.scratch_stride);
+  c.count = reinterpret_cast<const int*>(reinterpret_cast<const char*>(c.count) + (size_t)cam * q.scratch_stride);
+  return c;
+}
+
+// launch 1, grid (cap_tracks / 4, 4): camera blockIdx.y's workgroups take that camera's ticket (header word 5 of ITS list); word 6 of every header is next_id BEFORE the
+// quad frame, which is what four single steps leave when no camera detects
+__global__ __launch_bounds__(256) void lk_flow_quad_step_kernel(LkFlowQuadArgs q) { flow_step_body(flow_camera(q, blockIdx.y), blockIdx.x, gridDim.x); }
+
+// launches 2-4 over four cameras: fast_clear_kernel, fast_region_kernel and fast_nonmax_kernel with the camera as a grid dimension; each camera reads its OWN `num`
+struct FastQuadArgs {
+  const uint8_t* pyr; size_t pyr_stride;        // level 0 of camera 0's current pyramid
+  const int* num; long list_stride;             // header word `num` of camera 0's current list
+  int* score; int4* pool; int* count; size_t scratch_stride;
+  int width, height, sw, sh, cols, rows, features, threshold, pool_cap, n4;
+};
+template <typename T>
+__device__ __forceinline__ T* fast_quad_at(T* p, int cam, size_t stride) { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + (size_t)cam * stride); }
+
+__global__ __launch_bounds__(256) void fast_quad_clear_kernel(FastQuadArgs a) {
+  const int cam = blockIdx.y;
+  if (a.num[(size_t)cam * a.list_stride] <= 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n4) reinterpret_cast<int4*>(fast_quad_at(a.score, cam, a.scratch_stride))[i] = int4{0, 0, 0, 0};
+  if (i == 0) fast_quad_at(a.count, cam, a.scratch_stride)[0] = 0;
+}
+
+__global__ __launch_bounds__(1024) void fast_quad_region_kernel(FastQuadArgs a) {
+  const int cam = blockIdx.y;
+  const int features = min(a.features, __builtin_amdgcn_readfirstlane(a.num[(size_t)cam * a.list_stride]));
+  if (features <= 0) return;
+  fast_region_body(a.pyr + (size_t)cam * a.pyr_stride, a.width, a.sw, a.sh, a.rows, features, a.threshold, fast_quad_at(a.score, cam, a.scratch_stride), a.width, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void fast_quad_nonmax_kernel(FastQuadArgs a) {
+  const int cam = blockIdx.z;
+  if (a.num[(size_t)cam * a.list_stride] <= 0) return;
+  fast_nonmax_body(fast_quad_at(a.score, cam, a.scratch_stride), a.width, a.height, a.sw, a.sh, a.cols, a.rows, fast_quad_at(a.pool, cam, a.scratch_stride), a.pool_cap,
+                   fast_quad_at(a.count, cam, a.scratch_stride), blockIdx.x * 64 + (threadIdx.x & 63), blockIdx.y * 4 + (threadIdx.x >> 6));
+}
+
+// launch 5, four workgroups: workgroup c selects and merges for camera c (nothing when its `num` is 0), then the four take the quad-level ticket and the last one reads
+// the four counts of new entries and hands the ids out: camera c's k-th new entry gets next_id + (new entries of cameras < c) + k, header word 6 of camera c is
+// next_id after that camera, as four single steps in camera order leave them.  The workgroups can sit on different XCDs: agent-scope release / acquire around the ticket
+__global__ __launch_bounds__(1024) void lk_flow_quad_merge_kernel(LkFlowQuadArgs q) {
+  __shared__ int s_last;
+  const int tid = threadIdx.x, cam = blockIdx.x;
+  float* cur0 = q.c.cur;
+  int any = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) any |= reinterpret_cast<const int*>(cur0 + (size_t)k * q.list_stride)[FLOW_HDR_NUM] > 0 ? 1 : 0;
+  if (!any) return;                 // the steady state: launch 1 left every header as four single steps do
+  const LkFlowArgs c = flow_camera(q, cam);
+  if (reinterpret_cast<const int*>(c.cur)[FLOW_HDR_NUM] > 0) flow_merge_body<true>(c);
+  // ---- the quad-level ticket: the list of this camera has left before its workgroup arrives
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  int* qt = reinterpret_cast<int*>(cur0) + FLOW_HDR_QUAD;
+  if (tid == 0) {
+    const int old = __hip_atomic_fetch_add(qt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = old == 3;
+    if (last) __hip_atomic_store(qt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = last;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  int base = *c.next_id;
+  for (int k = 0; k < 4; ++k) {
+    int* h = reinterpret_cast<int*>(cur0 + (size_t)k * q.list_stride);
+    const int len = __hip_atomic_load(h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), fresh = __hip_atomic_load(h + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int* id = h + c.lay.off[D2FE_LKC_ID];
+    for (int e = len - fresh + tid; e < len; e += 1024) id[e] = base + (e - (len - fresh));
+    base += fresh;
+    if (tid == 0) h[6] = base;
+  }
+  __syncthreads();       // every thread has read *next_id
+  if (tid == 0) *c.next_id = base;
 }
 
 const char* flow_check_geometry(int width, int height, int cap_tracks, int cols, int rows, int threshold) {
@@ -332,6 +444,22 @@ void fast_device_launch(d2fe_context* h, const uint8_t* d_pyr, int width, int he
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(fast_nonmax_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, f.score, width, height, sw, sh, cols, rows, f.pool, f.pool_cap, f.count,
                        d_features);
+  }
+}
+
+// launches 2-4 of the quad step: one grid each over the four cameras
+void fast_quad_launch(d2fe_context* h, const FastQuadArgs& a, hipStream_t s) {
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_quad_clear_kernel, dim3((a.n4 + 255) / 256, 4), dim3(256), 0, s, a);
+  }
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_quad_region_kernel, dim3(a.cols * a.rows, 4), dim3(1024), 0, s, a);
+  }
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(fast_quad_nonmax_kernel, dim3((a.width + 63) / 64, (a.height + 3) / 4, 4), dim3(256), 0, s, a);
   }
 }
 
@@ -427,6 +555,59 @@ int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uin
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_flow_merge_kernel, dim3(1), dim3(1024), 0, s, c);
+  }
+  HIP_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+
+int d2fe_lk_flow_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, size_t pyr_stride, int width, int height, const void* d_prev_lists,
+                                  void* d_cur_lists, size_t list_stride, const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp,
+                                  int32_t* d_next_id, void* d_scratch, size_t scratch_stride, void* stream) {
+  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_lists || !d_cur_lists || !fp || !d_next_id || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = lk_flow_check_params(fp, width, height)) return ctx_fail(D2FE_ERR_INVALID, why);
+  const d2fe_track_params& tp = fp->track;
+  const int cap_tracks = tp.total_feature_num > 1 ? tp.total_feature_num : 1;
+  if (kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "kp_cap must be 0..16384");
+  if (!fp->superpoint) kp_cap = 0;
+  if (kp_cap > 0 && (!d_kps_xy || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
+  LkFlowQuadArgs q{};
+  LkFlowArgs& c = q.c;
+  size_t total = 0;
+  lk_pyr_geometry(c.P, width, height, tp.levels, &total);
+  c.lay = carry_layout(cap_tracks, 0);
+  const FlowScratch f = flow_scratch(d_scratch, width, height, cap_tracks, fp->fast_cols, fp->fast_rows);
+  if (list_stride < (size_t)c.lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one flow list block");
+  if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
+  if (((uintptr_t)d_scratch & 15u) || (scratch_stride & 15u) || scratch_stride < f.bytes || scratch_stride > (1ul << 40))
+    return ctx_fail(D2FE_ERR_INVALID, "the scratch must be 16-byte aligned, scratch_stride (bytes) a multiple of 16 and at least d2fe_lk_flow_scratch_bytes");
+  {   // the four previous lists against the four current ones: no block may be both
+    const char* a = static_cast<const char*>(d_prev_lists); const char* b = static_cast<const char*>(d_cur_lists);
+    const size_t span = sizeof(float) * (3 * list_stride + (size_t)c.lay.words);
+    if (a < b + span && b < a + span) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current lists must not overlap");
+  }
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp.win; c.iters = tp.iters;
+  c.prev = static_cast<const float*>(d_prev_lists); c.cur = static_cast<float*>(d_cur_lists);
+  c.kps = d_kps_xy; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
+  c.total = tp.total_feature_num; c.near_thr = (double)tp.near_lk_thread_rate; c.min_dist = tp.feature_min_dist;
+  c.next_id = d_next_id;
+  c.pool = f.pool; c.count = f.count; c.pool_cap = f.pool_cap;
+  q.list_stride = (long)list_stride; q.pyr_stride = pyr_stride; q.scratch_stride = scratch_stride;
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_flow_quad_step_kernel, dim3((cap_tracks + 3) / 4, 4), dim3(256), 0, s, q);
+  }
+  FastQuadArgs a{};
+  a.pyr = d_cur_pyr; a.pyr_stride = pyr_stride;
+  a.num = reinterpret_cast<const int*>(d_cur_lists) + FLOW_HDR_NUM; a.list_stride = (long)list_stride;
+  a.score = f.score; a.pool = f.pool; a.count = f.count; a.scratch_stride = scratch_stride;
+  a.width = width; a.height = height; a.sw = width / fp->fast_cols; a.sh = height / fp->fast_rows; a.cols = fp->fast_cols; a.rows = fp->fast_rows;
+  a.features = 2 * cap_tracks; a.threshold = fp->fast_threshold; a.pool_cap = f.pool_cap; a.n4 = (int)(((size_t)width * height + 3) / 4);
+  fast_quad_launch(h, a, s);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_flow_quad_merge_kernel, dim3(4), dim3(1024), 0, s, q);
   }
   HIP_TRY(hipGetLastError());
   return D2FE_OK;

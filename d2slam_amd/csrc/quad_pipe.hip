@@ -18,6 +18,12 @@
 // (d2fe_lk_carry_neighbour_device), and the lists go through the half-image compaction (reading the list blocks in place), ONE matcher launch and the remap, like the
 // keypoints.  The mode's arrays are appended to the result block in front of d2h_words, so they travel in the pass's one D2H; a pipe that never enables the mode
 // keeps the layout and the allocations it had.
+//
+// d2fe_quad_flow_enable (flow_lk: enable_lk_optical_flow without sp_track_use_lk, the reference's config/quadcam/quadcam_single.yaml, quadcam_multi.yaml and
+// quadcam_multi_rt.yaml; excludes the mode above): the same pyramids and the same chain, but the lists are the FLOW lists of lk_flow.hip -- per quad frame ONE
+// d2fe_lk_flow_quad_step_device (five launches for the four cameras) on the keypoints of that quad frame, with ONE pipe-owned detector scratch of four cameras that all
+// lanes share because the chain serialises the steps -- and ONE d2fe_lk_flow_neighbour_device over the pass's lists.  No matchKNN of the lists: flow entries carry no
+// descriptors.  The lists and the neighbour tracks sit where sp_lk puts its own (o_list, o_nbxy, o_nbst), in front of d2h_words.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -142,6 +148,13 @@ struct d2fe_quad_pipe_s {
   float* d_trk = nullptr;              // [4 empty lists | 64 words: next_id | K lanes x tscr_words]
   uint8_t* d_trk_pyr = nullptr;        // [4 carried pyramids | K lanes x 4 Q pyramids], pyr_total bytes each
   MatchPairDesc* d_lpairs = nullptr;   // [K][4 Q]: the neighbour pairs of the lists, on the lane's pools
+  // d2fe_quad_flow_enable: 4 Q flow-list blocks at o_list and the neighbour tracks at o_nbxy / o_nbst (capT = max(total_feature_num, 1)); d_trk is [4 empty lists | 64
+  // words: next_id], d_trk_pyr as above.  trk and flow exclude each other
+  bool flow = false;
+  bool flow_split = false;             // D2FE_QUAD_FLOW_SPLIT of the development library: four single-camera steps per quad frame (a measurement, not an option)
+  d2fe_flow_params fp{};
+  uint8_t* d_flow_scratch = nullptr;   // [4 cameras][flow_scratch_stride]: score map, candidate pool and count of each camera
+  size_t flow_scratch_stride = 0;
   int32_t* d_lmatch_scratch = nullptr; size_t lmatch_scratch_lane = 0;
   struct Lane : LaneBase { uint8_t* d_raw = nullptr; };
   std::vector<Lane> lanes;
@@ -260,11 +273,12 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
   const int32_t* map_a = job_left + 16 * Q;
   const int32_t* map_b = map_a + 4 * Q;
   int32_t* jmap = reinterpret_cast<int32_t*>(X + p->x_jmap);
-  if (p->trk) {
+  if (p->trk || p->flow) {
     // the pyramids of the pass's 4 Q views (view i of the lane's scratch = image i of the workspace), then the landmark lists: ONE step per quad frame in time order,
     // the carry copy, ONE launch for the neighbour tracks of every list
+    const d2fe_track_params& tp = p->flow ? p->fp.track : p->tp;
     uint8_t* pyr = p->lane_pyr(k);
-    rc = d2fe_lk_track_stereo_device(L.ctx, und, und + (size_t)2 * Q * img, 2 * Q, W, H, W, img, nullptr, nullptr, 0, p->tp.levels, p->tp.win, p->tp.iters, pyr, nullptr,
+    rc = d2fe_lk_track_stereo_device(L.ctx, und, und + (size_t)2 * Q * img, 2 * Q, W, H, W, img, nullptr, nullptr, 0, tp.levels, tp.win, tp.iters, pyr, nullptr,
                                      nullptr, s);
     if (rc) return rc;
     const auto [pk, pset] = prev_pass_block(k, set, p->K);
@@ -284,16 +298,31 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
         if (rc) return rc;
         continue;
       }
-      rc = d2fe_lk_carry_quad_step_device(L.ctx, prev_pyr, pyr + r * p->pyr_total, p->pyr_total, W, H, prev_lists, lists + r * p->list_words, p->list_words, p->D,
-                                          B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap, B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp,
-                                          p->next_id(), s);
+      if (p->flow && p->flow_split) {      // development library only (tools/bench_quad_pipe_flow.py): the chain composed from four single-camera steps, the same bits
+        for (int c = 0; c < 4 && !rc; ++c)
+          rc = d2fe_lk_flow_step_device(L.ctx, prev_pyr + c * p->pyr_total, pyr + (r + c) * p->pyr_total, W, H, prev_lists + c * p->list_words,
+                                        lists + (r + c) * p->list_words, B + p->o_kps + (r + c) * p->cap * 2, cnt + r + c, p->cap, &p->fp, p->next_id(),
+                                        p->d_flow_scratch + c * p->flow_scratch_stride, s);
+      } else if (p->flow) {
+        rc = d2fe_lk_flow_quad_step_device(L.ctx, prev_pyr, pyr + r * p->pyr_total, p->pyr_total, W, H, prev_lists, lists + r * p->list_words, p->list_words,
+                                           B + p->o_kps + r * p->cap * 2, cnt + r, p->cap, &p->fp, p->next_id(), p->d_flow_scratch, p->flow_scratch_stride, s);
+      } else {
+        rc = d2fe_lk_carry_quad_step_device(L.ctx, prev_pyr, pyr + r * p->pyr_total, p->pyr_total, W, H, prev_lists, lists + r * p->list_words, p->list_words, p->D,
+                                            B + p->o_kps + r * p->cap * 2, B + p->o_scores + r * p->cap, B + p->o_desc + r * p->cap * p->D, cnt + r, p->cap, &p->tp,
+                                            p->next_id(), s);
+      }
       if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(p->carry_pyr(), pyr + (size_t)(Q - 1) * 4 * p->pyr_total, 4 * p->pyr_total, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipEventRecord(L.ev_chain, s));
-    rc = d2fe_lk_carry_neighbour_device(L.ctx, pyr, p->pyr_total, Q, W, H, p->cfg.undistort_fov, lists, p->list_words, p->D, &p->tp, B + p->o_nbxy,
-                                        reinterpret_cast<uint8_t*>(B + p->o_nbst), s);
+    rc = p->flow ? d2fe_lk_flow_neighbour_device(L.ctx, pyr, p->pyr_total, Q, W, H, p->cfg.undistort_fov, lists, p->list_words, &tp, B + p->o_nbxy,
+                                                 reinterpret_cast<uint8_t*>(B + p->o_nbst), s)
+                 : d2fe_lk_carry_neighbour_device(L.ctx, pyr, p->pyr_total, Q, W, H, p->cfg.undistort_fov, lists, p->list_words, p->D, &p->tp, B + p->o_nbxy,
+                                                  reinterpret_cast<uint8_t*>(B + p->o_nbst), s);
     if (rc) return rc;
+  }
+  if (p->trk) {
+    float* lists = B + p->o_list;
     // matchLocalFeatures on the lists: the compaction reads the list blocks in place (descriptors, points and count of list r are r * list_words further on), the
     // same jobs and shifts as the keypoints'; ONE matcher launch over the 4 Q pairs, then the remap
     float* T = p->tscratch(k);
@@ -494,7 +523,7 @@ void d2fe_quad_pipe_destroy(d2fe_quad_pipe p) {
   (void)hipSetDevice(p->parent->cfg.device_id);
   for (auto& L : p->lanes) lane_destroy(L);
   for (void* q : {(void*)p->d_all, (void*)p->d_scr, (void*)p->d_raw_all, (void*)p->d_maps, (void*)p->d_jobs, (void*)p->d_pairs, (void*)p->d_match_scratch,
-                  (void*)p->d_trk, (void*)p->d_trk_pyr, (void*)p->d_lpairs, (void*)p->d_lmatch_scratch})
+                  (void*)p->d_trk, (void*)p->d_trk_pyr, (void*)p->d_lpairs, (void*)p->d_lmatch_scratch, (void*)p->d_flow_scratch})
     if (q) (void)hipFree(q);
   d2fe_context* parent = p->parent;
   delete p;
@@ -562,6 +591,7 @@ int d2fe_quad_track_enable(d2fe_quad_pipe p, const d2fe_track_params* tp_in) {
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
   if (p->trk) return ctx_fail(D2FE_ERR_INVALID, "the mode is already on");
+  if (p->flow) return ctx_fail(D2FE_ERR_INVALID, "sp_lk excludes the flow landmarks: the reference runs one of the two branches (d2featuretracker.cpp:556-614)");
   if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_track_enable comes before the first submit");
   HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
   const int Q = p->Q, K = p->K, capT = tp.total_feature_num + 1;
@@ -669,6 +699,107 @@ int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track
   out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
   out->lnb_q = reinterpret_cast<const int32_t*>(B + p->o_lmq); out->lnb_t = reinterpret_cast<const int32_t*>(B + p->o_lmt);
   out->lnb_dist = B + p->o_lmd; out->lnb_n = reinterpret_cast<const int32_t*>(B + p->o_lmn);
+  return D2FE_OK;
+}
+
+int d2fe_quad_flow_enable(d2fe_quad_pipe p, const d2fe_flow_params* fp_in) {
+  if (!p) return ctx_fail(D2FE_ERR_INVALID, "null pipe");
+  d2fe_flow_params fp;
+  if (fp_in) fp = *fp_in; else d2fe_flow_default_params(&fp);
+  if (const char* why = lk_flow_check_params(&fp, p->W, p->H)) return ctx_fail(D2FE_ERR_INVALID, why);
+  fp.reserved = 0; fp.track.reserved = 0;
+  if (fp.track.levels != 2) return ctx_fail(D2FE_ERR_INVALID, "levels must be 2 (PYR_LEVEL): the lanes' pyramids are that deep");
+  if (!fp.superpoint)
+    return ctx_fail(D2FE_ERR_INVALID, "superpoint must be 1: no quadcam configuration of the reference sets max_superpoint_cnt: 0 (flow-only pipes are the stereo / mono ones)");
+  if (!(p->cfg.undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "undistort_fov must be > 0 (move_cols of the neighbour tracks)");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->flow) return ctx_fail(D2FE_ERR_INVALID, "the flow landmarks are already switched on");
+  if (p->trk) return ctx_fail(D2FE_ERR_INVALID, "the flow landmarks exclude sp_lk: the reference runs one of the two branches (d2featuretracker.cpp:556-614)");
+  if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_flow_enable comes before the first submit");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  const int Q = p->Q, K = p->K, capF = fp.track.total_feature_num > 1 ? fp.track.total_feature_num : 1;
+  const size_t T = (size_t)capF, NI = (size_t)p->NI;
+  const size_t lw = d2fe_lk_flow_list_bytes(capF) / sizeof(float);
+  const size_t pyr_total = d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, fp.track.levels) / 2;
+  const size_t scr = d2fe_lk_flow_scratch_bytes(p->W, p->H, capF, fp.fast_cols, fp.fast_rows);
+  if (!lw || !pyr_total || !scr) return ctx_fail(D2FE_ERR_INVALID, "bad list, pyramid or detector geometry");
+  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
+  size_t o = p->d2h_words;
+  const size_t o_list = o; o += NI * lw;
+  const size_t o_nbxy = o; o += up64(NI * T * 2);
+  const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
+  const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap);
+  // everything new first; the pipe changes only when all of it is there
+  struct Fresh {
+    float* d_all = nullptr; float* d_trk = nullptr; uint8_t* d_pyr = nullptr; uint8_t* d_scr = nullptr;
+    std::vector<float*> pin; std::vector<hipEvent_t> ev; bool keep = false;
+    ~Fresh() {
+      if (keep) return;
+      for (void* q : {(void*)d_all, (void*)d_trk, (void*)d_pyr, (void*)d_scr}) if (q) (void)hipFree(q);
+      for (float* q : pin) if (q) (void)hipHostFree(q);
+      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+  } f;
+  const size_t all_words = 64 + (size_t)K * 2 * blk_words, trk_words = 4 * lw + 64;
+  const size_t pyr_bytes = (4 + (size_t)K * NI) * pyr_total;
+  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
+  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // no keypoints, empty lists, every arrival counter zero
+  HIP_TRY(hipMalloc(&f.d_trk, sizeof(float) * trk_words));
+  HIP_TRY(hipMemset(f.d_trk, 0, sizeof(float) * trk_words));        // the four empty lists in front of the first quad frame, next_id = 0
+  HIP_TRY(hipMalloc(&f.d_pyr, pyr_bytes));
+  HIP_TRY(hipMemset(f.d_pyr, 0, pyr_bytes));
+  HIP_TRY(hipMalloc(&f.d_scr, 4 * scr));                             // its content between steps does not matter
+  f.pin.assign((size_t)2 * K, nullptr); f.ev.assign((size_t)K, nullptr);
+  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
+  for (int k = 0; k < K; ++k) HIP_TRY(hipEventCreateWithFlags(&f.ev[k], hipEventDisableTiming));
+  HIP_TRY(hipDeviceSynchronize());        // the memsets ran on the null stream, which the lanes' streams do not wait for
+  // ---- commit: nothing has been submitted, so no stream holds an address of the old blocks
+  f.keep = true;
+  (void)hipFree(p->d_all);
+  p->d_all = f.d_all; p->d_trk = f.d_trk; p->d_trk_pyr = f.d_pyr; p->d_flow_scratch = f.d_scr; p->flow_scratch_stride = scr;
+  for (int k = 0; k < K; ++k) {
+    auto& L = p->lanes[k];
+    for (int set = 0; set < 2; ++set) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = f.pin[(size_t)2 * k + set]; }
+    L.ev_chain = f.ev[k];
+  }
+  p->fp = fp; p->capT = capF; p->list_words = lw; p->pyr_total = pyr_total; p->tscr_words = 0;
+  p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst;
+  p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
+  p->flow = true;
+  p->flow_split = d2fe_dev_env("D2FE_QUAD_FLOW_SPLIT", 0) != 0;
+  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
+    std::vector<MatchPairDesc> tab;
+    quad_fill_pairs(p, tab);
+    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
+      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+    }
+  }
+  return D2FE_OK;
+}
+
+int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_result* out) {
+  if (!p || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->flow) return ctx_fail(D2FE_ERR_UNSUPPORTED, "d2fe_quad_flow_enable was not called on this pipe: it carries no flow landmarks");
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "unknown ticket");
+  if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the lists within 2 * lanes submits");
+  const int k = (int)(ticket % p->K), set = (int)((ticket / p->K) & 1);
+  const auto& L = p->lanes[k];
+  if (L.synced < ticket) return ctx_fail(D2FE_ERR_NOT_READY, "d2fe_quad_pipe_wait has not returned this ticket yet");
+  const float* B = L.pin_out[set];
+  const float* list = B + p->o_list;
+  const int32_t* hdr = reinterpret_cast<const int32_t*>(list);
+  out->quads = p->Q; out->cap_tracks = p->capT; out->list_words = (int32_t)p->list_words;
+  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
+  out->lack = hdr + 7; out->num = hdr + 8; out->n_cand = hdr + 9;
+  out->pts_xy = list + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_PTS);
+  out->id = hdr + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_ID);
+  out->src = hdr + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_SRC);
+  out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
   return D2FE_OK;
 }
 

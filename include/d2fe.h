@@ -789,7 +789,31 @@ D2FE_API int d2fe_detect_fast_device(d2fe_handle h, const uint8_t* d_pyr, int wi
 D2FE_API int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list,
                                       void* d_cur_list, const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp, int32_t* d_next_id,
                                       void* d_scratch, void* stream);
-/* The flow landmarks IN THE STEREO / MONO PIPE.  d2fe_pipe_config and d2fe_pipe_camera are closed structs, so the mode is switched on by a call before the first
+/* The quadcam forms of the flow landmarks (trackLocalFrames WITHOUT sp_track_use_lk, d2featuretracker.cpp:121-133: config/quadcam/quadcam_single.yaml, quadcam_multi.yaml,
+ * quadcam_multi_rt.yaml).
+ * d2fe_lk_flow_quad_step_device: the flow lists of the FOUR cameras of one quad frame in FIVE launches, whatever the lists hold.  The addressing of
+ * d2fe_lk_carry_quad_step_device: camera c's previous / current list is c * list_stride 32-bit words behind d_prev_lists / d_cur_lists (list_stride >= one flow list
+ * block), its previous / current pyramid c * pyr_stride bytes behind d_prev_pyr / d_cur_pyr, its keypoints row c of the dense d_kps_xy [4][kp_cap][2] and d_n_kp [4] (the
+ * rows of one quad frame of d2fe_quad_device_result), its detector scratch c * scratch_stride bytes behind d_scratch (scratch_stride a multiple of 16 and >=
+ * d2fe_lk_flow_scratch_bytes(...)): a score map, a candidate pool and a count of its own per camera.
+ *   (1) grid (cap_tracks / 4, 4): one wave per entry of camera blockIdx.y's previous list; the camera's last workgroup (ticket: header word 5 of ITS current list)
+ *       finishes its list and decides its `lack` and `num`;
+ *   (2)-(4) score-map clear, FAST scores, non-max with the camera as a grid dimension: every camera reads its OWN `num` and returns when it is 0;
+ *   (5) four workgroups, one per camera: selection and merge of that camera; the four then take a quad-level ticket -- header word 10 of CAMERA 0's current list, one
+ *       of the "rest 0" words of a flow header, zero between launches like word 5 -- and the last one hands the ids out.
+ * A camera whose `num` is 0 adds nothing but keeps its place in the order; when all four are 0 (the steady state) launches 2-5 return at once.  Every byte of the
+ * four list blocks and *d_next_id equal four d2fe_lk_flow_step_device calls for cameras 0, 1, 2, 3 in that order with the same d_next_id: camera c's k-th new entry
+ * gets next_id + (new entries of cameras < c) + k, header word 6 of camera c is next_id after that camera, whichever workgroups finish last.  Only enqueues: no
+ * allocation, no synchronisation, no memset.  D2FE_ERR_INVALID: what d2fe_lk_flow_step_device refuses, strides too small or misaligned, a current list overlapping a
+ * previous one.
+ * d2fe_lk_flow_neighbour_device: d2fe_lk_carry_neighbour_device (the same kernel) over FLOW lists: cap_tracks = max(tp->total_feature_num, 1), list_stride >= one flow
+ * list block; d_nb_xy [quads][4][cap_tracks][2] and d_nb_status [quads][4][cap_tracks] are written for every slot.  ONE launch, only enqueues. */
+D2FE_API int d2fe_lk_flow_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, size_t pyr_stride, int width, int height,
+                                           const void* d_prev_lists, void* d_cur_lists, size_t list_stride, const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap,
+                                           const d2fe_flow_params* fp, int32_t* d_next_id, void* d_scratch, size_t scratch_stride, void* stream);
+D2FE_API int d2fe_lk_flow_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov,
+                                           const void* d_lists, size_t list_stride, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream);
+/* The flow landmarks IN THE STEREO / MONO PIPE. d2fe_pipe_config and d2fe_pipe_camera are closed structs, so the mode is switched on by a call before the first
  * submit (as d2fe_quad_track_enable does for the quad pipe): d2fe_pipe_flow_enable(p, fp) (fp NULL: d2fe_flow_default_params).  It needs a pipe that builds
  * pyramids (lr_lk = 1 or mono = 1), is refused with sp_lk (the reference's two branches exclude each other, d2featuretracker.cpp:556-614), after the first submit, for
  * fp->track.levels != 2, for what d2fe_lk_flow_step_device refuses, and with fp->superpoint = 0 on a pipe created with netvlad or match_prev; a refusal
@@ -1005,6 +1029,32 @@ typedef struct {            /* HOST pointers into the lane's pinned block, same 
 } d2fe_quad_track_result;
 D2FE_API int d2fe_quad_track_enable(d2fe_quad_pipe p, const d2fe_track_params* tp);
 D2FE_API int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track_result* out);
+/* flow_lk for the quad pipe: the reference's quadcam tracker with enable_lk_optical_flow = 1, sp_track_use_lk = 0 and max_superpoint_cnt > 0
+ * (config/quadcam/quadcam_single.yaml, quadcam_multi.yaml, quadcam_multi_rt.yaml): SuperPoint and the flow landmarks together.  d2fe_quad_flow_enable(p, fp) (fp = NULL:
+ * d2fe_flow_default_params) switches the mode on and allocates what it needs; d2fe_quad_pipe_config is closed and keeps its size.  It is accepted once, before the
+ * first submit; D2FE_ERR_INVALID after the first submit, a second time, together with d2fe_quad_track_enable in either order (the reference runs one of the two
+ * branches, d2featuretracker.cpp:556-614), for fp->track.levels != 2, for fp->superpoint = 0 (no quadcam configuration has max_superpoint_cnt: 0; flow-only pipes are
+ * the stereo / mono ones) and for what d2fe_lk_flow_quad_step_device refuses at the view size; a refusal leaves the pipe as it was and usable, and a pipe the call
+ * never succeeded on keeps its layout, allocations, launches and results.  Per submit, behind the SuperPoint results of the pass and on the lane's own streams:
+ *   the pyramids of the 4 * quads undistorted views -> for q = 0 .. quads - 1 ONE d2fe_lk_flow_quad_step_device (five launches) on the keypoints of quad frame q, on
+ *   the chain sp_lk uses (the predecessor of q = 0 is the last quad frame of the previous SUBMIT: its lists read in place, its four pyramids from a pipe-owned copy
+ *   behind the previous pass's chain event; ONE pipe-owned id counter; ONE pipe-owned scratch of four cameras that all lanes share, because the chain serialises the
+ *   steps) -> ONE d2fe_lk_flow_neighbour_device over the pass's flow lists -> everything in the pass's ONE D2H.
+ * No matchKNN of the lists: flow entries have no descriptors, and the keypoint-based nb_* / prev_* of d2fe_quad_pipe_result (match_neighbour / match_prev) are this
+ * mode's matchKNN.  d2fe_quad_flow_result_get after d2fe_quad_pipe_wait (D2FE_ERR_NOT_READY before it, D2FE_ERR_UNSUPPORTED on a pipe without the mode): list (q, c)
+ * is (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the convention of d2fe_quad_track_result); the list of camera a that a neighbour pair
+ * tracks is the list AFTER this frame's step.  Results are bit-identical for every (lanes, quads).
+ * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
+  int32_t quads, cap_tracks, list_words, reserved;
+  const int32_t *n, *n_tracked_in, *n_lost, *n_removed_near, *n_new, *lack, *num, *n_cand;      /* per list */
+  const float* pts_xy;               /* per list: [cap_tracks][2] */
+  const int32_t *id, *src;           /* per list: [cap_tracks] */
+  const float* nb_lk_xy;             /* [quads][4][cap_tracks][2], contiguous: neighbour pair n, slot i of list a */
+  const uint8_t* nb_lk_status;       /* [quads][4][cap_tracks] */
+} d2fe_quad_flow_result;
+D2FE_API int d2fe_quad_flow_enable(d2fe_quad_pipe p, const d2fe_flow_params* fp);
+D2FE_API int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_result* out);
 /* The pipe's undistort step on its own: ONE launch for 4 cameras x quads raw frames (image (q, c) at d_raw + q * quad_stride + c * camera_stride), maps
  * as above with device = 1 and every map pointer 16-byte aligned; view (q, c) is written to d_dst + (q * 4 + c) * dw * dh.  Same bytes as
  * d2fe_undistort_device camera by camera. */

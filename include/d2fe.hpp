@@ -397,6 +397,19 @@ struct QuadNeighbourTracks {
   std::vector<uint8_t> lk_status;
   std::vector<DMatch> matches;
 };
+// flowEnable(): the FLOW landmarks of one view of a quad frame (the second list D2FeatureTracker::trackLK(frame) keeps beside SuperPoint, enable_lk_optical_flow
+// without sp_track_use_lk: config/quadcam/quadcam_single.yaml) -- the fields of StereoFlowList without the right track -- and one neighbour pair (a, b): lk[i] is
+// where entry i of flow list a sits in view b when lk_status[i] != 0 (trackLK(left, right, type), d2featuretracker.cpp:697-752).  Flow entries carry no descriptors:
+// the pair's matchKNN is the keypoint-based nb_* of d2fe_quad_pipe_result
+struct QuadFlowList {
+  std::vector<Point2f> pts;
+  std::vector<int32_t> id, src;
+  int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0, lack = 0, num = 0, n_cand = 0;
+};
+struct QuadFlowNeighbourTracks {
+  std::vector<Point2f> lk;
+  std::vector<uint8_t> lk_status;
+};
 
 // d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
 class QuadPipe {
@@ -436,6 +449,36 @@ class QuadPipe {
       for (int j = 0; j < n; ++j) t.lk.emplace_back(tr.nb_lk_xy[(i * T + j) * 2], tr.nb_lk_xy[(i * T + j) * 2 + 1]);
       t.lk_status.assign(tr.nb_lk_status + i * T, tr.nb_lk_status + i * T + n);
       for (int j = 0; j < tr.lnb_n[i]; ++j) t.matches.emplace_back(tr.lnb_q[i * T + j], tr.lnb_t[i * T + j], tr.lnb_dist[i * T + j]);
+    }
+    return true;
+  }
+  // d2fe_quad_flow_enable (enable_lk_optical_flow without sp_track_use_lk, beside SuperPoint): once, before the first submit, never together with trackEnable;
+  // fp = nullptr: the reference's parameters (d2fe_flow_default_params)
+  bool flowEnable(const d2fe_flow_params* fp = nullptr) {
+    if (!p_ || d2fe_quad_flow_enable(p_, fp) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_flow_enable: %s\n", d2fe_last_error()); return false; }
+    return true;
+  }
+  // the flow lists of a ticket that d2fe_quad_pipe_wait has returned: lists[q * 4 + c] = view c of quad frame q, nb[q * 4 + n] = neighbour pair n = (0,1) (1,2) (2,3) (0,3)
+  bool flow(int64_t ticket, std::vector<QuadFlowList>& lists, std::vector<QuadFlowNeighbourTracks>& nb) const {
+    d2fe_quad_flow_result fr;
+    if (!p_ || d2fe_quad_flow_result_get(p_, ticket, &fr) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_flow_result_get: %s\n", d2fe_last_error()); return false; }
+    static const int view_a[4] = {0, 1, 2, 0};
+    const size_t T = (size_t)fr.cap_tracks, lw = (size_t)fr.list_words;
+    lists.assign((size_t)4 * fr.quads, QuadFlowList()); nb.assign((size_t)4 * fr.quads, QuadFlowNeighbourTracks());
+    for (size_t i = 0; i < lists.size(); ++i) {
+      QuadFlowList& t = lists[i];
+      const size_t o = i * lw;
+      const int n = fr.n[o];
+      for (int j = 0; j < n; ++j) t.pts.emplace_back(fr.pts_xy[o + 2 * j], fr.pts_xy[o + 2 * j + 1]);
+      t.id.assign(fr.id + o, fr.id + o + n); t.src.assign(fr.src + o, fr.src + o + n);
+      t.n_tracked_in = fr.n_tracked_in[o]; t.n_lost = fr.n_lost[o]; t.n_removed_near = fr.n_removed_near[o]; t.n_new = fr.n_new[o];
+      t.lack = fr.lack[o]; t.num = fr.num[o]; t.n_cand = fr.n_cand[o];
+    }
+    for (size_t i = 0; i < nb.size(); ++i) {
+      QuadFlowNeighbourTracks& t = nb[i];
+      const int n = fr.n[(i / 4 * 4 + view_a[i % 4]) * lw];
+      for (int j = 0; j < n; ++j) t.lk.emplace_back(fr.nb_lk_xy[(i * T + j) * 2], fr.nb_lk_xy[(i * T + j) * 2 + 1]);
+      t.lk_status.assign(fr.nb_lk_status + i * T, fr.nb_lk_status + i * T + n);
     }
     return true;
   }
