@@ -281,7 +281,7 @@ DEBUG_EXPORTS = [
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
     "d2fe_debug_netvlad_plan", "d2fe_debug_netvlad_shapes", "d2fe_debug_netvlad_features", "d2fe_debug_netvlad_groups", "d2fe_debug_netvlad_slots", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
     "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a",
-    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a"]
+    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a", "d2fe_debug_conv_layer", "d2fe_debug_conv1a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -346,6 +346,8 @@ def _open_library(path, dev):
             lib.d2fe_debug_nms2_a.argtypes = [vp, vp, ci, ci, ci, C.c_float, ci, ci, ci, vp, vp, vp, vp]
             lib.d2fe_debug_desc_head_sparse.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
             lib.d2fe_debug_sample_a.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, ci, vp, vp, ci, vp]
+            lib.d2fe_debug_conv_layer.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            lib.d2fe_debug_conv1a.argtypes = [vp, ci, vp, ci, C.c_longlong, C.c_longlong, ci, ci, ci, vp, vp, vp, C.c_longlong]
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
         lib.d2fe_half_move_cols.argtypes = [C.c_int, C.c_double]
@@ -550,6 +552,12 @@ def _open_library(path, dev):
         lib.d2fe_rccl_comm_init_rank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.d2fe_rccl_comm_destroy.argtypes = [C.c_void_p]
     return lib
+
+
+class _DebugConv(C.Structure):      # d2fe_debug_conv of include/d2fe_debug.h
+    _fields_ = [(k, C.c_int32) for k in ("family", "precision", "shape", "conv64_tile", "pool", "relu", "n", "H", "W", "cout", "in_cstride", "in_coff",
+                                         "out_cstride", "out_coff", "img_stride", "ncu")] + \
+               [(k, C.c_int64) for k in ("in_img_stride", "in_floats", "out_img_stride", "out_floats", "img_istride", "img_bytes")]
 
 
 def _check(rc):
@@ -1137,6 +1145,42 @@ class DevFrontEnd(FrontEnd):
         out = np.empty((n, cap, pd or 256), np.float32)
         _check(self._lib.d2fe_debug_sample_a(self._h, _ptr(desc_raw), dstride, int(dcoff), n, Hc, Wc, int(img_w), int(img_h), _ptr(kps_xy), _ptr(n_kp), cap,
                                              int(cap if scap is None else scap), _ptr(slotmap), max_slots, _ptr(comp), _ptr(mean), pd, _ptr(out)))
+        return out
+
+    # ---- one layer of the direct SuperPoint conv kernels on injected tensors (include/d2fe_debug.h; tests/test_conv_layer_edges.py) ----
+    def debug_conv_layer(self, family, precision, shape, weight, bias, n, H, W, out, out_cstride, out_coff, out_img_stride, x=None, in_cstride=0, in_coff=0,
+                         in_img_stride=0, pool=False, relu=True, conv64_tile=1, ncu=0, frames=None, img_stride=0, img_istride=0, w1a=None, b1a=None,
+                         status=False):
+        """d2fe_debug_conv_layer.  x: the WHOLE input buffer (any shape, fp32), out: the WHOLE pre-filled output buffer -- a copy comes back with what the
+        kernels wrote and the caller's values everywhere else.  weight [cout, cin, k, k], bias [cout]; shape 4 (CONV1B_FUSED) takes frames (u8, whole buffer) with
+        w1a [64, 1, 3, 3] and b1a [64] instead of x.  Raises D2FEError (code -1 refused, -5 family 3: the launcher does not take the tensors); status=True returns (code, out) instead."""
+        weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
+        assert weight.ndim == 4 and bias.shape == (weight.shape[0],)
+        out = np.array(out, np.float32, order="C")
+        if x is not None:
+            x = np.ascontiguousarray(x, np.float32)
+        if frames is not None:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            w1a = np.ascontiguousarray(w1a, np.float32); b1a = np.ascontiguousarray(b1a, np.float32)
+            assert w1a.shape == (64, 1, 3, 3) and b1a.shape == (64,)
+        p = _DebugConv(int(family), int(precision), int(shape), int(conv64_tile), int(bool(pool)), int(bool(relu)), int(n), int(H), int(W), weight.shape[0],
+                       int(in_cstride), int(in_coff), int(out_cstride), int(out_coff), int(img_stride), int(ncu), int(in_img_stride),
+                       0 if x is None else x.size, int(out_img_stride), out.size, int(img_istride), 0 if frames is None else frames.size)
+        rc = int(self._lib.d2fe_debug_conv_layer(self._h, C.byref(p), _ptr(weight), _ptr(bias), _ptr(x), _ptr(out), _ptr(frames), _ptr(w1a), _ptr(b1a)))
+        if status:
+            return rc, out
+        _check(rc)
+        return out
+
+    def debug_conv1a(self, kernel, frames, img_stride, img_istride, n, H, W, w1a, b1a, out):
+        """d2fe_debug_conv1a: kernel 0 conv1a_mfma_kernel, 1 conv1a_kernel, -1 launch_conv1a's pick.  frames: the whole u8 buffer; out: the whole pre-filled
+        buffer of at least n * H * W * 64 floats, returned as a copy with what the kernel wrote."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        w1a = np.ascontiguousarray(w1a, np.float32); b1a = np.ascontiguousarray(b1a, np.float32)
+        assert w1a.shape == (64, 1, 3, 3) and b1a.shape == (64,)
+        out = np.array(out, np.float32, order="C")
+        _check(self._lib.d2fe_debug_conv1a(self._h, int(kernel), _ptr(frames), int(img_stride), int(img_istride), frames.size, int(n), int(H), int(W), _ptr(w1a),
+                                           _ptr(b1a), _ptr(out), out.size))
         return out
 
     # ---- NetVLAD inspection (include/d2fe_debug.h; tests/test_netvlad_shapes*.py) ----

@@ -245,18 +245,18 @@ static hipError_t launch_f32_fused1b(int cout_pad, const ConvArgs& a, hipStream_
   return hipGetLastError();
 }
 
-hipError_t launch_conv_f16x2(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
-hipError_t launch_conv_f16(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_f16x2(ConvShape shape, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_f16(ConvShape shape, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
 
-hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
-                       hipStream_t s) {
-  if (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && shape != CONV1B_FUSED)) return launch_conv_pc(shape, precision, pool, relu, cout_pad, a, s);
-  if (precision == 1) return launch_conv_f16x2(shape, pool, relu, cout_pad, a, s);
-  if (precision == 3) return launch_conv_f16(shape, pool, relu, cout_pad, a, s);
+// the one-tile-per-workgroup kernels (conv.hip / conv_f16.hip); conv64_tile: 1 = the 4x32 tile for CONV_64_T8x32, else 8x32
+hipError_t launch_conv_tile(ConvShape shape, int precision, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a,
+                            hipStream_t s) {
+  if (precision == 1) return launch_conv_f16x2(shape, conv64_tile, pool, relu, cout_pad, a, s);
+  if (precision == 3) return launch_conv_f16(shape, conv64_tile, pool, relu, cout_pad, a, s);
   if (precision != 0) return hipErrorInvalidValue;
   switch (shape) {
     case CONV_64_T8x32:
-      if (tune_conv64() == 1) return launch_f32<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);
+      if (conv64_tile == 1) return launch_f32<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);
       return launch_f32<64, 3, 8, 32, 4, 1, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x32:     return launch_f32<128, 3, 4, 32, 2, 2, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x16:     return launch_f32<128, 3, 4, 16, 1, 4, 2, 1>(pool, relu, cout_pad, a, s);
@@ -264,6 +264,12 @@ hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int
     case CONV1B_FUSED:       return launch_f32_fused1b(cout_pad, a, s);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
+                       hipStream_t s) {
+  if (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && shape != CONV1B_FUSED)) return launch_conv_pc(shape, precision, pool, relu, cout_pad, a, s);
+  return launch_conv_tile(shape, precision, tune_conv64(), pool, relu, cout_pad, a, s);
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -382,10 +388,9 @@ __global__ __launch_bounds__(256) void conv1a_mfma_kernel(const uint8_t* __restr
   }
 }
 
-hipError_t launch_conv1a(const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
-                         const float* w9x64, const float* bias, float* out, hipStream_t s) {
-  static int valu = -1;
-  if (valu < 0) valu = d2fe_dev_env("D2FE_CONV1A_VALU", 0);   // 1: the VALU kernel (A/B timing)
+// valu != 0: conv1a_kernel, else conv1a_mfma_kernel
+hipError_t launch_conv1a_kernel(int valu, const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
+                                const float* w9x64, const float* bias, float* out, hipStream_t s) {
   if (valu) {
     dim3 grid((W + 63) / 64, H, n), block(256);
     hipLaunchKernelGGL(conv1a_kernel, grid, block, 0, s, img, stride, img_stride_bytes, H, W, w9x64, bias, out);
@@ -397,6 +402,13 @@ hipError_t launch_conv1a(const uint8_t* img, int stride, long img_stride_bytes, 
   hipLaunchKernelGGL(conv1a_mfma_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, img, stride, img_stride_bytes, H, W,
                      tiles_x, total, w9x64, bias, out);
   return hipGetLastError();
+}
+
+hipError_t launch_conv1a(const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
+                         const float* w9x64, const float* bias, float* out, hipStream_t s) {
+  static int valu = -1;
+  if (valu < 0) valu = d2fe_dev_env("D2FE_CONV1A_VALU", 0);   // 1: the VALU kernel (A/B timing)
+  return launch_conv1a_kernel(valu, img, stride, img_stride_bytes, H, W, n, w9x64, bias, out, s);
 }
 
 }  // namespace d2fe

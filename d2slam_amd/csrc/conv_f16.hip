@@ -282,11 +282,11 @@ static hipError_t launch_f16_fused1b(int cout_pad, const ConvArgs& a, hipStream_
   return hipGetLastError();
 }
 
-hipError_t launch_conv_f16x2(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
+hipError_t launch_conv_f16x2(ConvShape shape, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
   switch (shape) {
     case CONV1B_FUSED:       return launch_f16_fused1b<true>(cout_pad, a, s);
     case CONV_64_T8x32:
-      if (tune_conv64() == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);
+      if (conv64_tile == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1>(pool, relu, cout_pad, a, s);
       return launch_f16<64, 3, 8, 32, 4, 1, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x32:     return launch_f16<128, 3, 4, 32, 2, 2, 2, 2>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x16:     return launch_f16<128, 3, 4, 16, 1, 4, 2, 1>(pool, relu, cout_pad, a, s);
@@ -296,11 +296,11 @@ hipError_t launch_conv_f16x2(ConvShape shape, bool pool, bool relu, int cout_pad
 }
 
 // D2FE_PREC_F16: the same shapes, single operands
-hipError_t launch_conv_f16(ConvShape shape, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
+hipError_t launch_conv_f16(ConvShape shape, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s) {
   switch (shape) {
     case CONV1B_FUSED:       return launch_f16_fused1b<false>(cout_pad, a, s);
     case CONV_64_T8x32:
-      if (tune_conv64() == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1, false>(pool, relu, cout_pad, a, s);
+      if (conv64_tile == 1) return launch_f16<64, 3, 4, 32, 2, 2, 2, 1, false>(pool, relu, cout_pad, a, s);
       return launch_f16<64, 3, 8, 32, 4, 1, 2, 2, false>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x32:     return launch_f16<128, 3, 4, 32, 2, 2, 2, 2, false>(pool, relu, cout_pad, a, s);
     case CONV_128_T4x16:     return launch_f16<128, 3, 4, 16, 1, 4, 2, 1, false>(pool, relu, cout_pad, a, s);

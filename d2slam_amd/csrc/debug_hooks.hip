@@ -1,5 +1,5 @@
 // debug_hooks.hip -- the development library's hooks (include/d2fe_debug.h) that need nothing of the handle but its device and stream: the launch-regime
-// record, the host-side packings, one Winograd layer, the SuperPoint tail kernels, the sparse descriptor head and variant A's descriptor tail on injected
+// record, the host-side packings, one Winograd layer, one layer of the direct conv kernels and the stand-alone conv1a, the SuperPoint tail kernels, the sparse descriptor head and variant A's descriptor tail on injected
 // tensors, the count of captured launch sequences.  (The hooks that read a unit's own state back live with that state: d2fe_debug_read in
 // superpoint_host.hip, the NetVLAD ones in netvlad_host.hip, the matcher's stamps in match_host.hip.)  The whole unit compiles to nothing for the product library.
 #ifdef D2FE_DEVTOOLS
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "context.h"
+#include "conv_common.h"      // tune_conv_pc, tune_conv64: the switches launch_conv reads
 #include "../../include/d2fe_debug.h"
 
 using namespace d2fe;
@@ -437,6 +438,166 @@ int d2fe_debug_sample_a(d2fe_handle h, const float* desc_raw, int dstride, int d
                           d_map, max_slots, d_desc, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(desc_out, d_desc, sizeof(float) * D * n * cap, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+// ---- one layer of the direct SuperPoint conv kernels on injected tensors (tests/test_conv_layer_edges.py) ----
+namespace {
+constexpr long DEBUG_MAX_CONV_FLOATS = 1l << 26;      // floats per caller buffer: far below the 2^31 bytes the epilogues' 32-bit offsets cover
+
+struct ConvGeom { int cin, ks, bn; };
+// Cin, kernel size and the channels per workgroup (BN: cout_pad is a multiple of it) of a shape; the same in the one-tile and the persistent kernels
+ConvGeom conv_geom(int shape) {
+  switch (shape) {
+    case CONV_64_T8x32:      return {64, 3, 64};
+    case CONV_128_T4x32:     return {128, 3, 128};
+    case CONV_128_T4x16:     return {128, 3, 128};
+    case CONV_256_1x1_T4x16: return {256, 1, 128};
+    case CONV1B_FUSED:       return {64, 3, 64};
+  }
+  return {0, 0, 0};
+}
+// the (shape, pool, relu) combinations the launchers compile: launch_conv_tile (launch_f32 / launch_f16: pool only on the 32-wide two-m-tile shapes; the
+// fused shape is pool + ReLU) and launch_pc_mode's table
+bool conv_compiled(int family, int shape, bool pool, bool relu) {
+  if (shape == CONV1B_FUSED) return pool && relu;
+  if (family == 1) return !pool || shape == CONV_64_T8x32 || shape == CONV_128_T4x32;
+  switch (shape) {
+    case CONV_64_T8x32:      return relu;
+    case CONV_128_T4x32:     return pool && relu;
+    case CONV_128_T4x16:     return !pool && relu;
+    case CONV_256_1x1_T4x16: return !pool && !relu;
+  }
+  return false;
+}
+}  // namespace
+
+int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out, const uint8_t* frames,
+                          const float* w1a, const float* b1a) {
+  if (!h || !p || !weight || !bias || !out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (p->family < 0 || p->family > 3 || (p->precision != 0 && p->precision != 1 && p->precision != 3) || p->shape < 0 || p->shape > CONV1B_FUSED)
+    return fail(D2FE_ERR_INVALID, "family, precision or shape");
+  const bool pool = p->pool != 0, relu = p->relu != 0, fused = p->shape == CONV1B_FUSED;
+  // family 0 = what conv() of superpoint_host.hip does in this process: convPb's own kernel first (fp32 modes, D2FE_CONV1X1), then launch_conv, which
+  // takes the persistent or the one-tile kernels by D2FE_CONV_PC and the Cin-64 tile by D2FE_CONV64_TILE
+  int family = p->family, conv64_tile = p->conv64_tile;
+  if (family == 0) {
+    family = (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && !fused)) ? 2 : 1;
+    conv64_tile = tune_conv64();
+  }
+  const bool try_1x1 = p->family == 0 && p->precision == 0 && p->shape == CONV_256_1x1_T4x16 && p->cout == 65 && !pool && !relu && d2fe_dev_env("D2FE_CONV1X1", 1);
+  if (p->family == 3) {
+    if (p->precision != 0 || p->shape != CONV_256_1x1_T4x16 || pool || relu) return fail(D2FE_ERR_INVALID, "family 3 is the fp32 1x1 layer without pool and ReLU");
+  } else if (!conv_compiled(family, p->shape, pool, relu)) {
+    return fail(D2FE_ERR_INVALID, "no kernel of this family is compiled for the shape with this pool / relu");
+  }
+  if (family == 1 && conv64_tile != 0 && conv64_tile != 1) return fail(D2FE_ERR_INVALID, "conv64_tile is 0 or 1");
+  const ConvGeom g = conv_geom(p->shape);
+  const int n = p->n, H = p->H, W = p->W, cout = p->cout;
+  if (n < 1 || n > 64 || H < 1 || W < 1 || H > 4096 || W > 4096 || (pool && (H < 2 || W < 2)) || cout < 1 || cout > 1024 || (fused && cout > 64))
+    return fail(D2FE_ERR_INVALID, "bad geometry");
+  const int cout_pad = (cout + g.bn - 1) / g.bn * g.bn;      // the rule of sp_plan.h: whole workgroups of channels
+  const int ncu = p->ncu > 0 ? p->ncu : h->ncu;
+  if (p->ncu < 0 || ncu < 1 || ncu > 4096) return fail(D2FE_ERR_INVALID, "ncu");
+  const long hw = (long)H * W, ohw = pool ? (long)(H / 2) * (W / 2) : hw;
+  // every address the kernels can form lies inside the caller's buffers: pixel (img, y, x) channel c of the input is in[img * in_img_stride + (y * W + x) *
+  // in_cstride + in_coff + c] for c < Cin (float4 loads of whole aligned groups of four of these), of the output out[img * out_img_stride + (y * Wo + x) *
+  // out_cstride + out_coff + c] for c < cout; the frame byte (img, y, x) is frames[img * img_istride + y * img_stride + x]
+  if (p->out_floats < 1 || p->out_floats > DEBUG_MAX_CONV_FLOATS || p->out_cstride < 1 || p->out_coff < 0 || p->out_img_stride < 0 ||
+      p->out_img_stride > DEBUG_MAX_CONV_FLOATS || p->out_cstride > 65536 || p->out_coff > 65536 || (n > 1 && p->out_img_stride < ohw * p->out_cstride) ||
+      (n - 1) * p->out_img_stride + (ohw - 1) * p->out_cstride + p->out_coff + cout > p->out_floats || ohw * p->out_cstride >= (1l << 29))
+    return fail(D2FE_ERR_INVALID, "the output tensor does not fit the output buffer");
+  if (fused) {
+    if (!frames || !w1a || !b1a) return fail(D2FE_ERR_INVALID, "CONV1B_FUSED needs frames and the conv1a weights");
+    if (p->img_bytes < 1 || p->img_bytes > 4 * DEBUG_MAX_CONV_FLOATS || p->img_stride < 1 || p->img_stride > 65536 || p->img_istride < 0 ||
+        p->img_istride > 4 * DEBUG_MAX_CONV_FLOATS || (n - 1) * p->img_istride + (long)(H - 1) * p->img_stride + W > p->img_bytes)
+      return fail(D2FE_ERR_INVALID, "the frames do not fit the frame buffer");
+  } else {
+    if (!in) return fail(D2FE_ERR_INVALID, "null input");
+    if (p->in_floats < 1 || p->in_floats > DEBUG_MAX_CONV_FLOATS || p->in_cstride < 1 || p->in_coff < 0 || p->in_img_stride < 0 ||
+        p->in_img_stride > DEBUG_MAX_CONV_FLOATS || p->in_cstride > 65536 || p->in_coff > 65536 ||
+        (n - 1) * p->in_img_stride + (hw - 1) * p->in_cstride + p->in_coff + g.cin > p->in_floats)
+      return fail(D2FE_ERR_INVALID, "the input tensor does not fit the input buffer");
+    // float4 loads (launch_conv1x1_256_65 refuses a misaligned tensor itself: family 3 leaves that answer to it)
+    if (p->family != 3 && ((p->in_cstride & 3) || (p->in_coff & 3) || (p->in_img_stride & 3)))
+      return fail(D2FE_ERR_INVALID, "in_cstride, in_coff and in_img_stride are multiples of 4 floats");
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  // weights and bias as pack_layer of superpoint_host.hip prepares them
+  std::vector<float> pf, bp(cout_pad, 0.f), t1a;
+  std::vector<uint16_t> ph;
+  memcpy(bp.data(), bias, sizeof(float) * cout);
+  if (p->precision == 0) { pf.resize(packed_weight_floats_f32(cout_pad, g.cin, g.ks)); pack_weights_f32(weight, cout, g.cin, g.ks, cout_pad, pf.data()); }
+  else if (p->precision == 1) { ph.resize(packed_weight_halfs_f16x2(cout_pad, g.cin, g.ks)); pack_weights_f16x2(weight, cout, g.cin, g.ks, cout_pad, ph.data()); }
+  else { ph.resize(packed_weight_halfs_f16(cout_pad, g.cin, g.ks)); pack_weights_f16(weight, cout, g.cin, g.ks, cout_pad, ph.data()); }
+  DevPool b;
+  float *d_in = nullptr, *d_out = nullptr, *d_b = nullptr, *d_w1a = nullptr, *d_b1a = nullptr, *d_zero = nullptr;
+  void* d_w = nullptr;
+  uint8_t* d_img = nullptr;
+  if (fused) {
+    t1a.resize(9 * 64);      // [64][1][3][3] -> [9][64], as d2fe_load_superpoint
+    for (int co = 0; co < 64; ++co)
+      for (int k = 0; k < 9; ++k) t1a[k * 64 + co] = w1a[co * 9 + k];
+    HIP_TRY(b.get(&d_img, (size_t)p->img_bytes, frames));
+    HIP_TRY(b.get(&d_w1a, sizeof(float) * t1a.size(), t1a.data()));
+    HIP_TRY(b.get(&d_b1a, sizeof(float) * 64, b1a));
+  } else {
+    HIP_TRY(b.get(&d_in, sizeof(float) * p->in_floats, in));
+  }
+  HIP_TRY(b.get(&d_out, sizeof(float) * p->out_floats, out));      // the caller's pre-filled buffer: what no kernel writes comes back as it went in
+  if (p->precision == 0) HIP_TRY(b.get(&d_w, sizeof(float) * pf.size(), pf.data()));
+  else HIP_TRY(b.get(&d_w, sizeof(uint16_t) * ph.size(), ph.data()));
+  HIP_TRY(b.get(&d_b, sizeof(float) * bp.size(), bp.data()));
+  HIP_TRY(b.get(&d_zero, sizeof(float) * 256, nullptr, 0));
+  HIP_TRY(hipDeviceSynchronize());      // the null-stream copies and memsets are not ordered with the handle's non-blocking stream
+  ConvArgs a{};
+  a.in = d_in; a.in_cstride = p->in_cstride; a.in_coff = p->in_coff; a.out = d_out; a.out_cstride = p->out_cstride; a.out_coff = p->out_coff;
+  a.cout_real = cout; a.wpack = d_w; a.bias = d_b; a.H = H; a.W = W; a.n_img = n;
+  a.in_img_stride = (long)p->in_img_stride; a.out_img_stride = (long)p->out_img_stride;
+  a.img = d_img; a.img_stride = p->img_stride; a.img_istride = (long)p->img_istride; a.w1a = d_w1a; a.b1a = d_b1a;
+  a.zeros = d_zero; a.ncu = ncu; a.tag = 0; a.ablate = 0;
+  const ConvShape shape = (ConvShape)p->shape;
+  hipError_t e = hipErrorNotSupported;
+  if (p->family == 3 || try_1x1) e = launch_conv1x1_256_65(a, h->stream);
+  if (p->family == 3 && e == hipErrorNotSupported) {      // nothing was launched: the caller gets the device copy of its buffer back all the same
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, d_out, sizeof(float) * p->out_floats, hipMemcpyDeviceToHost));
+    return fail(D2FE_ERR_UNSUPPORTED, "launch_conv1x1_256_65 does not take these tensors");
+  }
+  if (p->family == 0 && e == hipErrorNotSupported) e = launch_conv(shape, p->precision, pool, relu, cout_pad, a, h->stream);
+  else if (p->family == 1) e = launch_conv_tile(shape, p->precision, conv64_tile, pool, relu, cout_pad, a, h->stream);
+  else if (p->family == 2) e = launch_conv_pc(shape, p->precision, pool, relu, cout_pad, a, h->stream);
+  HIP_TRY(e);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(float) * p->out_floats, hipMemcpyDeviceToHost));
+  return D2FE_OK;
+}
+
+int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,
+                      const float* w1a, const float* b1a, float* out, long long out_floats) {
+  if (!h || !frames || !w1a || !b1a || !out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (kernel < -1 || kernel > 1 || n < 1 || n > 64 || H < 1 || W < 1 || H > 4096 || W > 4096 || img_stride < 1 || img_stride > 65536 || img_istride < 0 ||
+      img_bytes < 1 || img_bytes > 4 * DEBUG_MAX_CONV_FLOATS || img_istride > 4 * DEBUG_MAX_CONV_FLOATS ||
+      (n - 1) * img_istride + (long long)(H - 1) * img_stride + W > img_bytes)
+    return fail(D2FE_ERR_INVALID, "bad geometry, or the frames do not fit the frame buffer");
+  const long long need = (long long)n * H * W * 64;      // both kernels write [n][H][W][64], dense
+  if (out_floats < need || out_floats > DEBUG_MAX_CONV_FLOATS) return fail(D2FE_ERR_INVALID, "the output does not fit the output buffer");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  std::vector<float> t(9 * 64);
+  for (int co = 0; co < 64; ++co)
+    for (int k = 0; k < 9; ++k) t[k * 64 + co] = w1a[co * 9 + k];
+  DevPool b;
+  uint8_t* d_img = nullptr;
+  float *d_w = nullptr, *d_b = nullptr, *d_out = nullptr;
+  HIP_TRY(b.get(&d_img, (size_t)img_bytes, frames));
+  HIP_TRY(b.get(&d_w, sizeof(float) * t.size(), t.data()));
+  HIP_TRY(b.get(&d_b, sizeof(float) * 64, b1a));
+  HIP_TRY(b.get(&d_out, sizeof(float) * out_floats, out));
+  HIP_TRY(hipDeviceSynchronize());
+  if (kernel < 0) HIP_TRY(launch_conv1a(d_img, img_stride, (long)img_istride, H, W, n, d_w, d_b, d_out, h->stream));
+  else HIP_TRY(launch_conv1a_kernel(kernel, d_img, img_stride, (long)img_istride, H, W, n, d_w, d_b, d_out, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost));
   return D2FE_OK;
 }
 

@@ -68,6 +68,9 @@ enum ConvShape {
 // precision (d2fe_precision): 0 = fp32 exact MFMA, 1 = fp16 hi/lo split MFMA, 3 = plain fp16 operands (the Winograd mode, 2, has launchers of its own below)
 hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
                        hipStream_t s);
+// the part of launch_conv behind D2FE_CONV_PC: the one-tile-per-workgroup kernels (conv.hip, conv_f16.hip).  conv64_tile: 1 = the 4x32 tile for CONV_64_T8x32
+// (launch_conv passes D2FE_CONV64_TILE, default 1), anything else the 8x32 tile
+hipError_t launch_conv_tile(ConvShape shape, int precision, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
 
 // convPb (1x1, 256 -> 65) in the fp32 modes: 64 cell channels on the matrix pipe + the dustbin on the vector pipe (conv1x1.hip); same bits as
 // the generic kernels; hipErrorNotSupported when the tensors are not flat pixel lists
@@ -85,6 +88,9 @@ void pack_weights_wino(const float* w /*[cout][cin][3][3]*/, int cout, int cin, 
 // conv1a: u8 gray [n][H][stride] -> NHWC fp32 [n][H][W][64], fused (float)u8 * (1/255), bias, ReLU.
 hipError_t launch_conv1a(const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
                          const float* w9x64 /*[9][64]*/, const float* bias, float* out, hipStream_t s);
+// the same with the kernel named: valu != 0 conv1a_kernel, 0 conv1a_mfma_kernel (launch_conv1a passes D2FE_CONV1A_VALU, default 0)
+hipError_t launch_conv1a_kernel(int valu, const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
+                                const float* w9x64, const float* bias, float* out, hipStream_t s);
 
 // host-side packing helpers (fragment order of the kernels above)
 size_t packed_weight_floats_f32(int cout_pad, int cin, int ks);

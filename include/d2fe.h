@@ -43,7 +43,21 @@ typedef enum {
 
 typedef enum {
   D2FE_PREC_F32 = 0,   /* exact fp32 MFMA (v_mfma_f32_32x32x2_f32): bitwise equal to the oracle's fmaf chains */
-  D2FE_PREC_F16X2 = 1, /* fp16 hi/lo split operands, 3 x v_mfma_f32_32x32x16_f16, fp32 accumulate (~2^-22 rel.) */
+  D2FE_PREC_F16X2 = 1, /* fp16 hi/lo split operands, 3 x v_mfma_f32_32x32x16_f16, fp32 accumulate (~2^-22 rel.).  The arithmetic of every layer from
+                            conv1b on (conv1a stays the exact fp32 chain, fused into conv1b's staging), with SA = 4, SW = 8:
+                              activation  xs = min(max(x * 2^SA, -65000), 65000) in fp32 (the scaling is exact; behind the fused conv1a only the upper
+                                          clamp exists, its input being a ReLU output), hi_x = fp16(xs) round to nearest even, lo_x = fp16(xs - hi_x): the
+                                          residual is exact in fp32 and its conversion rounds to nearest even, so hi_x + lo_x = xs whenever the residual is an fp16
+                                          number; otherwise |xs - hi_x - lo_x| <= max(2^-22 |xs|, 2^-25): half a unit of lo_x, which is 2^-11 of a
+                                          residual of at most 2^-11 |xs| while lo_x is normal, and half the subnormal spacing 2^-24 below that
+                              weight      ws = min(max(w * 2^SW, -65000), 65000), hi_w, lo_w likewise, once, when the weights are loaded
+                              sum         acc = bias * 2^(SA+SW) + sum over (ky, kx, ci) of (lo_x hi_w + hi_x lo_w + hi_x hi_w): THREE products per operand
+                                          pair, each exact, accumulated in fp32 inside the matrix instruction (the order is the instruction's: no bit-exact
+                                          restatement is promised); lo_x lo_w is DROPPED (<= 2^-22 relative to the product)
+                              epilogue    y = acc * 2^-(SA+SW) (exact), then ReLU and the 2x2 max-pool as in every mode
+                            fp16 subnormals are kept on hi and lo (nothing is flushed by the conversions or by the matrix instruction); zero padding is
+                            exact.  The error of one layer against real arithmetic on the split operands is bounded by the fp32 summation bound
+                            (3 K + 2) * 2^-24 * (sum (|hi hi| + |hi lo| + |lo hi|) * 2^-(SA+SW) + |bias|), K = 9 Cin (Cin for the 1x1 heads). */
   D2FE_PREC_F32_WINO = 2,/* fp32 throughout; the eight 3x3 layers with Cin >= 64 as Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32
                             (16 instead of 36 multiplies per output and channel pair).  Bitwise equal to the oracle's restatement
                             of that evaluation order (orc_conv3x3_wino), ~1e-6 relative to the direct chains of D2FE_PREC_F32.

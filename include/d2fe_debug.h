@@ -105,6 +105,40 @@ D2FE_API int d2fe_debug_sample_a(d2fe_handle h, const float* desc_raw, int dstri
                                  const int32_t* n_kp, int cap, int scap, const int32_t* slotmap_or_null, int max_slots, const float* comp_or_null,
                                  const float* mean, int pca_dims, float* desc_out);
 
+/* ONE layer of the direct SuperPoint conv kernels (csrc/conv.hip, conv_f16.hip, conv_pc.hip, conv1x1.hip) on injected tensors, for
+ * tests/test_conv_layer_edges.py: host buffers in and out, device buffers of the call's own, the handle's device and stream.  The hook packs the weights as
+ * d2fe_load_superpoint does for the precision, fills ConvArgs from the caller's numbers and calls the launcher, nothing else.
+ *   family     0 what the extractor's conv() does in this process (convPb's own kernel where it applies and D2FE_CONV1X1 allows, else launch_conv under
+ *                D2FE_CONV_PC / D2FE_CONV64_TILE), 1 the one-tile kernels (launch_conv_tile), 2 the persistent kernels (launch_conv_pc), 3 launch_conv1x1_256_65
+ *   precision  0 D2FE_PREC_F32, 1 D2FE_PREC_F16X2, 3 D2FE_PREC_F16
+ *   shape      ConvShape of csrc/kernels.h: 0 Cin 64 3x3, 1 Cin 128 3x3 (32-wide tile), 2 Cin 128 3x3 (16-wide tile), 3 Cin 256 1x1, 4 conv1a fused into conv1b
+ *   conv64_tile  family 1, shape 0: 1 the 4x32 tile, 0 the 8x32 tile
+ *   n, H, W    images and the conv's spatial size (the output is H/2 x W/2, floor, with pool); cout real channels, padded here to whole workgroups
+ *   in         the caller's WHOLE input buffer of in_floats floats: channel c of pixel (img, y, x) at img * in_img_stride + (y * W + x) * in_cstride + in_coff + c
+ *   out        the caller's WHOLE pre-filled output buffer of out_floats floats, addressed likewise: it is uploaded first and downloaded whole, so what the
+ *              kernels do not write keeps the caller's values
+ *   frames     shape 4 only: u8 frames, byte (img, y, x) at img * img_istride + y * img_stride + x, img_bytes in all; w1a [64][1][3][3], b1a [64]
+ *   ncu        copied into ConvArgs::ncu (0: the handle's device): the persistent kernels size their grids on it
+ * weight [cout][cin][k][k], bias [cout].  Refused with D2FE_ERR_INVALID before anything is launched: a (family, shape, pool, relu) the launchers do not compile,
+ * strides and offsets of the input that are no multiples of 4 floats (the kernels load float4), and any tensor whose last address lies outside its buffer.
+ * Family 3 returns D2FE_ERR_UNSUPPORTED where the launcher answers hipErrorNotSupported (nothing launched; alignment is the launcher's own test there). */
+typedef struct d2fe_debug_conv {
+  int32_t family, precision, shape, conv64_tile, pool, relu;
+  int32_t n, H, W, cout;
+  int32_t in_cstride, in_coff;
+  int32_t out_cstride, out_coff;
+  int32_t img_stride, ncu;
+  int64_t in_img_stride, in_floats;
+  int64_t out_img_stride, out_floats;
+  int64_t img_istride, img_bytes;
+} d2fe_debug_conv;
+D2FE_API int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out,
+                                   const uint8_t* frames, const float* w1a, const float* b1a);
+/* The stand-alone conv1a (1 -> 64, 3x3, ReLU) on injected frames: kernel 0 conv1a_mfma_kernel, 1 conv1a_kernel, -1 launch_conv1a's own pick (D2FE_CONV1A_VALU).
+ * frames as above; out is the caller's whole pre-filled buffer of out_floats >= n * H * W * 64 floats, uploaded first and downloaded whole. */
+D2FE_API int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,
+                               const float* w1a, const float* b1a, float* out, long long out_floats);
+
 /* Host-pointer calls replay cached hipGraphs of their launch sequences from the third call with the same geometry on (D2FE_GRAPH=0 in the
  * environment turns that off).  Returns how many graphs the handle holds; *rejected (may be NULL) = geometries whose capture failed and which
  * therefore keep launching kernel by kernel (diagnostic). */
