@@ -322,7 +322,9 @@ void host_state_restore(d2fe_context* h, const d2fe_context::HostState& st, bool
 // lk_carry.hip, for the pipe's sp_lk mode: what d2fe_lk_carry_step_device would refuse (nullptr: nothing), and trackLK(left, right) over the lists of a pass --
 // n_frames list blocks, consecutive in d_lists, against the pass's stereo workspace (d2fe_lk_track_stereo_device), ONE launch
 const char* lk_carry_check_params(const d2fe_track_params* tp);
-// (desc_dim = 0: flow lists, cap_tracks = max(total_feature_num, 1))
+// the capacity of a flow list: detectPoints fills it up to total_feature_num, and a list block holds at least one slot
+inline int flow_cap_tracks(const d2fe_track_params& tp) { return tp.total_feature_num > 1 ? tp.total_feature_num : 1; }
+// (desc_dim = 0: flow lists, cap_tracks = flow_cap_tracks)
 int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int width, int height, const d2fe_track_params& tp, const float* d_lists, int desc_dim,
                           float* d_right_xy, uint8_t* d_right_status, hipStream_t s);
 

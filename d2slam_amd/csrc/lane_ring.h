@@ -112,4 +112,16 @@ void track_list_view(Out* out, const float* list, int cap_tracks, int desc_dim, 
   out->desc = at(D2FE_LKC_DESC); out->scores = at(D2FE_LKC_SCORES);
 }
 
+// the same for the flow-list fields of d2fe_pipe_flow_result and d2fe_quad_flow_result
+template <class Out>
+void flow_list_view(Out* out, const float* list, int cap_tracks, size_t list_words) {
+  const int32_t* hdr = reinterpret_cast<const int32_t*>(list);
+  out->cap_tracks = cap_tracks; out->list_words = (int32_t)list_words;
+  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
+  out->lack = hdr + 7; out->num = hdr + 8; out->n_cand = hdr + 9;
+  out->pts_xy = list + d2fe_lk_flow_list_offset(cap_tracks, D2FE_LKC_PTS);
+  out->id = hdr + d2fe_lk_flow_list_offset(cap_tracks, D2FE_LKC_ID);
+  out->src = hdr + d2fe_lk_flow_list_offset(cap_tracks, D2FE_LKC_SRC);
+}
+
 }  // namespace d2fe

@@ -5,7 +5,10 @@
 //   trackLK(left, right)               :697-752 with sp_track_use_lk: the LIST entries (not the SuperPoint keypoints) are tracked left -> right
 //
 // MI355X mapping.  One frame = ONE launch (lk_carry_step_kernel): one 64-lane wave per list slot runs the bidirectional track (lk_bidir over lk.hip's lk_calc, lk_device.h), four
-// waves to a workgroup; every workgroup then takes an agent-scope ticket in the output list's header and the last one to arrive runs steps b-e for the whole list.  The
+// waves to a workgroup; every workgroup then takes an agent-scope ticket in the output list's header and the last one to arrive runs steps b-e for the whole list.
+// The split: step a with the ticket, steps b-c, the per-camera view of the kernel's arguments, the quad-level id hand-out and the entry points' shared refusals are
+// lk_list_device.h's, one copy for this list and the flow list (lk_flow.hip); here are step d (the replenishment from the SuperPoint keypoints) and step e in
+// carry_step_body, which the single kernel runs on camera 0's view and the quad kernel on blockIdx.y's, and the left -> right and neighbour launches over the lists.  The
 // alternative, a second launch of one workgroup, puts one more dependent launch per frame on a chain that is serial by the algorithm (frame f + 1 needs frame f's
 // list), against one atomic per workgroup here; the gap between two dependent launches was not measured for this kernel, and the
 // two-launch form was not built.
@@ -27,28 +30,31 @@ namespace d2fe {
 
 namespace {
 
-struct LkCarryArgs {
-  const uint8_t* prev_pyr; const uint8_t* cur_pyr;
-  LkPairDev P;                      // geometry only
-  int win, iters;
-  const float* prev; float* cur;    // list blocks
-  CarryLayout lay;
-  const float* kps; const float* kp_scores; const float* kp_desc; const int* n_kp; int kp_cap;
-  int total;                        // total_feature_num
-  double near_thr, min_dist;        // near_lk_thread_rate widened to double; feature_min_dist
-  int* next_id;
-};
+struct LkCarryArgs : LkListArgs { const float* kp_scores; const float* kp_desc; };       // the keypoints' scores and descriptor rows beside LkListArgs::kps
 
-// Steps b-e for one list, run by the workgroup whose ticket said it arrived last (256 threads, the list's scratch in the caller's LDS).  QUAD (the four-camera launch,
-// lk_carry_quad_step_kernel): the ids of the NEW entries, header word 6 and *next_id belong to the launch's last finisher, which knows the new entries of the lower
-// cameras; they are left alone here, and so is header word 7 of camera 0's list (keep7), the quad-level ticket
+// the camera's view (lk_list_device.h) with its rows of the scores and the descriptors
+struct CarryCamera : ListCamera { const float* kp_scores; const float* kp_desc; };
+__device__ __forceinline__ CarryCamera carry_camera(const LkCarryArgs& c, int cam, long list_stride, size_t pyr_stride) {
+  CarryCamera v{list_camera(c, cam, list_stride, pyr_stride), c.kp_scores, c.kp_desc};
+  if (c.kp_cap > 0) { v.kp_scores += (size_t)cam * c.kp_cap; v.kp_desc += (size_t)cam * c.kp_cap * c.lay.D; }
+  return v;
+}
+
+// One list's step for workgroup bx of the nblocks that step it (256 threads): step a and the ticket (list_track_and_arrive, lk_list_device.h), then steps b-e on the
+// workgroup that arrived last, which alone returns true.  s_cnt: [0] list length, [1] survivors of the tracker, [2] survivors of removeNearPoints, [3] the ticket's flag.
+// QUAD (the four-camera launch, lk_carry_quad_step_kernel): the ids of the NEW entries, header word 6 and *next_id belong to the launch's last finisher, which knows the
+// new entries of the lower cameras; they are left alone here, and so is header word 7 of camera 0's list (keep7), the quad-level ticket
 template <bool QUAD>
-__device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, float* s_x, float* s_y, int* s_src, int* s_kp, int* s_cnt, bool keep7) {
+__device__ __forceinline__ bool carry_step_body(const LkCarryArgs& c, const CarryCamera& v, int bx, int nblocks, bool keep7, int* s_cnt) {
+  __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
+  __shared__ int s_src[LKC_MAX], s_kp[LKC_MAX];
+  int n_prev;
+  if (!list_track_and_arrive(c, v, bx, nblocks, s_cnt + 3, n_prev)) return false;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cap = c.lay.cap, D = c.lay.D;
-  int* hdr = reinterpret_cast<int*>(c.cur);
-  float* trk_xy = c.cur + c.lay.off[D2FE_LKC_TRK_XY];
-  uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
+  int* hdr = reinterpret_cast<int*>(v.cur);
+  float* trk_xy = v.cur + c.lay.off[D2FE_LKC_TRK_XY];
+  uint8_t* trk_st = reinterpret_cast<uint8_t*>(v.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
   // ---- b-d on wave 0
   if (wave == 0) {
     // b-c. reduceVector and removeNearPoints (lk_list_device.h, shared with the flow list)
@@ -57,12 +63,11 @@ __device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, f
     // d. replenish from the frame's SuperPoint keypoints
     int len = m;
     {
-      int n_kp = c.kp_cap > 0 ? __builtin_amdgcn_readfirstlane(c.n_kp[0]) : 0;
-      n_kp = n_kp < 0 ? 0 : n_kp > c.kp_cap ? c.kp_cap : n_kp;
+      const int n_kp = list_n_kp(c, v);
       const double thr = c.min_dist, t2 = thr * thr, lo = t2 * (1.0 - 1e-12), hi = t2 * (1.0 + 1e-12);
       for (int i = 0; i < n_kp; ++i) {
         if (len > c.total) break;
-        const float kx = c.kps[2 * i], ky = c.kps[2 * i + 1];
+        const float kx = v.kps[2 * i], ky = v.kps[2 * i + 1];
         bool hit = false;
         for (int j = lane; j < len; j += 64) hit = hit || nearer(s_x[j], s_y[j], kx, ky, thr, lo, hi);
         if (__ballot(hit) == 0ull) {
@@ -78,28 +83,28 @@ __device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, f
   // ---- e. the list: ids, descriptors and scores of the discovery frame, zeros behind the end
   const int len = s_cnt[0], cnt = s_cnt[1], m = s_cnt[2];
   const int id0 = QUAD ? 0 : *c.next_id;
-  float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
-  int* id = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_ID]);
-  int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
-  int* kp = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_KP]);
-  float* scores = c.cur + c.lay.off[D2FE_LKC_SCORES];
-  float* desc = c.cur + c.lay.off[D2FE_LKC_DESC];
-  const int* pid = reinterpret_cast<const int*>(c.prev + c.lay.off[D2FE_LKC_ID]);
-  const float* pscores = c.prev + c.lay.off[D2FE_LKC_SCORES];
-  const float* pdesc = c.prev + c.lay.off[D2FE_LKC_DESC];
+  float* pts = v.cur + c.lay.off[D2FE_LKC_PTS];
+  int* id = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_ID]);
+  int* src = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_SRC]);
+  int* kp = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_KP]);
+  float* scores = v.cur + c.lay.off[D2FE_LKC_SCORES];
+  float* desc = v.cur + c.lay.off[D2FE_LKC_DESC];
+  const int* pid = reinterpret_cast<const int*>(v.prev + c.lay.off[D2FE_LKC_ID]);
+  const float* pscores = v.prev + c.lay.off[D2FE_LKC_SCORES];
+  const float* pdesc = v.prev + c.lay.off[D2FE_LKC_DESC];
   for (int k = tid; k < cap; k += 256) {
     const bool live = k < len, old = k < m;
     const int sk = live ? s_src[k] : 0, kk = !live ? 0 : old ? -1 : s_kp[k];
     pts[2 * k] = live ? s_x[k] : 0.f; pts[2 * k + 1] = live ? s_y[k] : 0.f;
     id[k] = !live ? 0 : old ? pid[sk] : id0 + (k - m);
     src[k] = sk; kp[k] = kk;
-    scores[k] = !live ? 0.f : old ? pscores[sk] : c.kp_scores[kk];
+    scores[k] = !live ? 0.f : old ? pscores[sk] : v.kp_scores[kk];
     if (k >= n_prev) { trk_xy[2 * k] = 0.f; trk_xy[2 * k + 1] = 0.f; trk_st[k] = 0; }
   }
   for (int k = wave; k < cap; k += 4) {          // a descriptor row per wave
     float* dst = desc + (size_t)k * D;
     if (k < len) {
-      const float* from = k < m ? pdesc + (size_t)s_src[k] * D : c.kp_desc + (size_t)s_kp[k] * D;
+      const float* from = k < m ? pdesc + (size_t)s_src[k] * D : v.kp_desc + (size_t)s_kp[k] * D;
       for (int e = lane; e < D; e += 64) dst[e] = from[e];
     } else {
       for (int e = lane; e < D; e += 64) dst[e] = 0.f;
@@ -114,48 +119,12 @@ __device__ __forceinline__ void carry_finish(const LkCarryArgs& c, int n_prev, f
     }
   }
   if (tid >= (keep7 ? 8 : 7) && tid < 64) hdr[tid] = 0;
+  return true;
 }
 
 __global__ __launch_bounds__(256) void lk_carry_step_kernel(LkCarryArgs c) {
-  __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
-  __shared__ int s_src[LKC_MAX], s_kp[LKC_MAX];
-  __shared__ int s_cnt[4];          // [0] list length, [1] survivors of the tracker, [2] survivors of removeNearPoints, [3] this workgroup arrived last
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cap = c.lay.cap;
-  const int* phdr = reinterpret_cast<const int*>(c.prev);
-  int* hdr = reinterpret_cast<int*>(c.cur);
-  float* trk_xy = c.cur + c.lay.off[D2FE_LKC_TRK_XY];
-  uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
-  const float* ppts = c.prev + c.lay.off[D2FE_LKC_PTS];
-  int n_prev = __builtin_amdgcn_readfirstlane(phdr[0]);
-  n_prev = n_prev < 0 ? 0 : n_prev > cap ? cap : n_prev;
-
-  // ---- a. track: one wave per entry of the previous list (the body of lk_track_stereo_kernel, lk.hip)
-  const int slot = blockIdx.x * 4 + wave;
-  if (slot < n_prev) {
-    LkArgs a{};
-    a.win = c.win; a.iters = c.iters;
-    const LkPairDev& P = c.P;
-    const float ppx = ppts[2 * slot], ppy = ppts[2 * slot + 1];
-    float cx, cy;
-    const int ok = lk_bidir(a, P, c.prev_pyr, c.cur_pyr, ppx, ppy, cx, cy, lane);
-    if (lane == 0) { trk_xy[2 * slot] = cx; trk_xy[2 * slot + 1] = cy; trk_st[slot] = (uint8_t)ok; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // the wave's stores have left before its workgroup arrives
-  }
-  // ---- ticket (the pattern of match.hip): the last workgroup to arrive acquires everybody's stores and finishes the list
-  __syncthreads();
-  if (tid == 0) {
-    const int old = __hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == (int)gridDim.x - 1;
-    if (last) __hip_atomic_store(hdr + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch that writes this block
-    s_cnt[3] = last;
-  }
-  __syncthreads();
-  if (!s_cnt[3]) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-
-  // ---- b-e
-  carry_finish<false>(c, n_prev, s_x, s_y, s_src, s_kp, s_cnt, false);
+  __shared__ int s_cnt[4];
+  carry_step_body<false>(c, carry_camera(c, 0, 0, 0), blockIdx.x, gridDim.x, false, s_cnt);
 }
 
 // trackLK(left, right) on the lists of a pass: one wave per (frame, list slot); frame f's list is f * list_words further on, its pyramids are images f and n_frames + f
@@ -192,19 +161,13 @@ __global__ __launch_bounds__(256) void lk_carry_right_kernel(LkCarryRightArgs s)
   }
 }
 
-void pyr_geometry(LkPairDev& P, int width, int height, int levels, size_t* total) {
-  lk_pyr_geometry(P, width, height, levels, total);
-}
-
-
 // ---- the quadcam forms -------------------------------------------------------------------------------------------------------------------------------------
 // trackLocalFrames with sp_track_use_lk (d2featuretracker.cpp:121-133): track(images[c]) for c = 0..3 steps four lists per quad frame, and every new landmark takes
 // its id from ONE counter in camera order.  Four launches of lk_carry_step_kernel are four links of a chain that is serial by the algorithm; here ONE launch of
 // (slots / 4, 4 cameras) workgroups steps the four lists side by side (4 * cap_tracks waves: 604 for the reference's 151 slots, fewer than the card holds).  Camera c's
-// workgroups take that camera's ticket (header word 5 of ITS list) and its last workgroup runs b-e for its list, all but the ids of the new entries.  The four
-// finishers then take a second ticket, header word 7 of CAMERA 0's current list (zero between launches, like word 5; camera 0's finisher leaves it alone), and the
-// last of them reads the four counts of new entries and hands the ids out: camera c's k-th new entry gets next_id + (new entries of cameras < c) + k, header word 6
-// of camera c is next_id after that camera, as four launches in camera order would leave them
+// workgroups run carry_step_body on that camera's view: they take its ticket (header word 5 of ITS list) and its last workgroup runs b-e for its list, all but the ids
+// of the new entries.  The four finishers then take a second ticket, header word 7 of CAMERA 0's current list (camera 0's finisher leaves it alone), and the last of
+// them hands the ids out (quad_hand_out_ids, lk_list_device.h)
 struct LkCarryQuadArgs {
   LkCarryArgs c;                    // camera 0
   long list_stride;                 // words between the cameras' lists (previous and current)
@@ -212,75 +175,9 @@ struct LkCarryQuadArgs {
 };
 
 __global__ __launch_bounds__(256) void lk_carry_quad_step_kernel(LkCarryQuadArgs q) {
-  __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
-  __shared__ int s_src[LKC_MAX], s_kp[LKC_MAX];
   __shared__ int s_cnt[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cam = blockIdx.y;
-  LkCarryArgs c = q.c;
-  const int cap = c.lay.cap, D = c.lay.D;
-  float* cur0 = q.c.cur;
-  c.prev += (size_t)cam * q.list_stride; c.cur += (size_t)cam * q.list_stride;
-  c.prev_pyr += (size_t)cam * q.pyr_stride; c.cur_pyr += (size_t)cam * q.pyr_stride;
-  if (c.kp_cap > 0) {               // rows of the dense [4][kp_cap] extract outputs
-    c.kps += (size_t)cam * c.kp_cap * 2; c.kp_scores += (size_t)cam * c.kp_cap; c.kp_desc += (size_t)cam * c.kp_cap * D; c.n_kp += cam;
-  }
-  const int* phdr = reinterpret_cast<const int*>(c.prev);
-  int* hdr = reinterpret_cast<int*>(c.cur);
-  float* trk_xy = c.cur + c.lay.off[D2FE_LKC_TRK_XY];
-  uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
-  const float* ppts = c.prev + c.lay.off[D2FE_LKC_PTS];
-  int n_prev = __builtin_amdgcn_readfirstlane(phdr[0]);
-  n_prev = n_prev < 0 ? 0 : n_prev > cap ? cap : n_prev;
-
-  // ---- a. track: one wave per entry of the camera's previous list
-  const int slot = blockIdx.x * 4 + wave;
-  if (slot < n_prev) {
-    LkArgs a{};
-    a.win = c.win; a.iters = c.iters;
-    const float ppx = ppts[2 * slot], ppy = ppts[2 * slot + 1];
-    float cx, cy;
-    const int ok = lk_bidir(a, c.P, c.prev_pyr, c.cur_pyr, ppx, ppy, cx, cy, lane);
-    if (lane == 0) { trk_xy[2 * slot] = cx; trk_xy[2 * slot + 1] = cy; trk_st[slot] = (uint8_t)ok; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  }
-  // ---- the camera's ticket
-  __syncthreads();
-  if (tid == 0) {
-    const int old = __hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == (int)gridDim.x - 1;
-    if (last) __hip_atomic_store(hdr + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_cnt[3] = last;
-  }
-  __syncthreads();
-  if (!s_cnt[3]) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  carry_finish<true>(c, n_prev, s_x, s_y, s_src, s_kp, s_cnt, cam == 0);
-
-  // ---- the quad-level ticket: the list of this camera has left before its finisher arrives
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  int* qt = reinterpret_cast<int*>(cur0) + 7;
-  if (tid == 0) {
-    const int old = __hip_atomic_fetch_add(qt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == 3;
-    if (last) __hip_atomic_store(qt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_cnt[3] = last;
-  }
-  __syncthreads();
-  if (!s_cnt[3]) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  int base = *c.next_id;
-  for (int k = 0; k < 4; ++k) {
-    int* h = reinterpret_cast<int*>(cur0 + (size_t)k * q.list_stride);
-    const int len = __hip_atomic_load(h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), fresh = __hip_atomic_load(h + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int* id = h + c.lay.off[D2FE_LKC_ID];
-    for (int e = len - fresh + tid; e < len; e += 256) id[e] = base + (e - (len - fresh));
-    base += fresh;
-    if (tid == 0) h[6] = base;
-  }
-  __syncthreads();       // every thread has read *next_id
-  if (tid == 0) *c.next_id = base;
+  if (!carry_step_body<true>(q.c, carry_camera(q.c, blockIdx.y, q.list_stride, q.pyr_stride), blockIdx.x, gridDim.x, blockIdx.y == 0, s_cnt)) return;
+  quad_hand_out_ids(q.c.cur, q.list_stride, 7, q.c.lay.off[D2FE_LKC_ID], q.c.next_id, s_cnt + 3);
 }
 
 // trackLK(left, right, type) of trackLocalFrames (d2featuretracker.cpp:128-132,697-752) for the lists of `quads` quad frames: one wave per (quad frame, neighbour pair,
@@ -341,8 +238,8 @@ const char* lk_carry_check_params(const d2fe_track_params* tp) {
 int lk_carry_right_launch(d2fe_context* h, const uint8_t* ws, int n_frames, int width, int height, const d2fe_track_params& tp, const float* d_lists, int desc_dim,
                           float* d_right_xy, uint8_t* d_right_status, hipStream_t s) {
   LkCarryRightArgs r{};
-  pyr_geometry(r.P, width, height, tp.levels, &r.total);
-  const CarryLayout lay = desc_dim > 0 ? carry_layout(tp.total_feature_num + 1, desc_dim) : carry_layout(tp.total_feature_num > 1 ? tp.total_feature_num : 1, 0);
+  lk_pyr_geometry(r.P, width, height, tp.levels, &r.total);
+  const CarryLayout lay = list_layout(tp, desc_dim);
   r.ws = ws; r.n_frames = n_frames; r.cap = lay.cap; r.win = tp.win; r.iters = tp.iters;
   r.lists = d_lists; r.list_words = lay.words; r.off_pts = lay.off[D2FE_LKC_PTS];
   r.cur_pts = d_right_xy; r.status = d_right_status;
@@ -376,25 +273,55 @@ long d2fe_lk_carry_list_offset(int cap_tracks, int desc_dim, int field) {
   return carry_layout(cap_tracks, desc_dim).off[field];
 }
 
+namespace {
+// what the two step entry points share: their refusals and the kernel's arguments
+int carry_step_args(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev, void* d_cur, int desc_dim,
+                    const float* d_kps_xy, const float* d_kp_scores, const float* d_kp_desc, const int32_t* d_n_kp, int kp_cap, const d2fe_track_params* tp,
+                    int32_t* d_next_id, LkCarryArgs& c, size_t* pyr_total) {
+  if (!tp) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
+  if (desc_dim < 1 || desc_dim > 65536 || kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "desc_dim must be 1..65536, kp_cap 0..16384");
+  if (kp_cap > 0 && (!d_kp_scores || !d_kp_desc)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
+  c.kp_scores = d_kp_scores; c.kp_desc = d_kp_desc;
+  return list_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev, d_cur, list_layout(*tp, desc_dim), d_kps_xy, d_n_kp, kp_cap, true, *tp, d_next_id, c, pyr_total);
+}
+
+// what the two neighbour launches share: the checks, the kernel's arguments and the launch; desc_dim = 0: flow lists (no descriptors)
+int lk_neighbour_launch(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
+                        size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
+  if (!h || !d_pyr || !d_lists || !tp || !d_nb_xy || !d_nb_status) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
+  if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
+  if (quads < 1 || quads > 16383 || desc_dim < 0 || desc_dim > 65536 || !(undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
+  LkCarryNbArgs r{};
+  size_t total = 0;
+  lk_pyr_geometry(r.P, width, height, tp->levels, &total);
+  const CarryLayout lay = list_layout(*tp, desc_dim);
+  if (list_stride < (size_t)lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one list block");
+  if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
+  r.pyr = d_pyr; r.pyr_stride = pyr_stride; r.quads = quads; r.cap = lay.cap; r.win = tp->win; r.iters = tp->iters;
+  r.move_cols = d2fe_half_move_cols(width, undistort_fov);
+  r.lists = static_cast<const float*>(d_lists); r.list_stride = (long)list_stride; r.off_pts = lay.off[D2FE_LKC_PTS];
+  r.xy = d_nb_xy; r.status = d_nb_status;
+  HIP_TRY(hipSetDevice(ctx_device(h)));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
+  {
+    ProfScope ps(h, D2FE_PROF_LK, s);
+    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((r.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
+  }
+  HIP_TRY(hipGetLastError());
+  return D2FE_OK;
+}
+}  // namespace
+
 int d2fe_lk_carry_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list, void* d_cur_list,
                               int desc_dim, const float* d_kps_xy, const float* d_kp_scores, const float* d_kp_desc, const int32_t* d_n_kp, int kp_cap,
                               const d2fe_track_params* tp, int32_t* d_next_id, void* stream) {
-  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_list || !d_cur_list || !tp || !d_next_id) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
-  if (d_prev_list == d_cur_list) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current list must be different blocks");
-  if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
-  if (desc_dim < 1 || desc_dim > 65536 || kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "desc_dim must be 1..65536, kp_cap 0..16384");
-  if (kp_cap > 0 && (!d_kps_xy || !d_kp_scores || !d_kp_desc || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
+  LkCarryArgs c{};
+  if (const int rc = carry_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev_list, d_cur_list, desc_dim, d_kps_xy, d_kp_scores, d_kp_desc, d_n_kp, kp_cap, tp,
+                                     d_next_id, c, nullptr)) return rc;
   HIP_TRY(hipSetDevice(ctx_device(h)));
   hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  LkCarryArgs c{};
-  pyr_geometry(c.P, width, height, tp->levels, nullptr);
-  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp->win; c.iters = tp->iters;
-  c.prev = static_cast<const float*>(d_prev_list); c.cur = static_cast<float*>(d_cur_list);
-  c.lay = carry_layout(tp->total_feature_num + 1, desc_dim);
-  c.kps = d_kps_xy; c.kp_scores = d_kp_scores; c.kp_desc = d_kp_desc; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
-  c.total = tp->total_feature_num; c.near_thr = (double)tp->near_lk_thread_rate; c.min_dist = tp->feature_min_dist;
-  c.next_id = d_next_id;
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_carry_step_kernel, dim3((c.lay.cap + 3) / 4), dim3(256), 0, s, c);
@@ -406,31 +333,15 @@ int d2fe_lk_carry_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const ui
 int d2fe_lk_carry_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, size_t pyr_stride, int width, int height, const void* d_prev_lists,
                                    void* d_cur_lists, size_t list_stride, int desc_dim, const float* d_kps_xy, const float* d_kp_scores, const float* d_kp_desc,
                                    const int32_t* d_n_kp, int kp_cap, const d2fe_track_params* tp, int32_t* d_next_id, void* stream) {
-  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_lists || !d_cur_lists || !tp || !d_next_id) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
-  if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
-  if (desc_dim < 1 || desc_dim > 65536 || kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "desc_dim must be 1..65536, kp_cap 0..16384");
-  if (kp_cap > 0 && (!d_kps_xy || !d_kp_scores || !d_kp_desc || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
   LkCarryQuadArgs q{};
   LkCarryArgs& c = q.c;
   size_t total = 0;
-  pyr_geometry(c.P, width, height, tp->levels, &total);
-  c.lay = carry_layout(tp->total_feature_num + 1, desc_dim);
-  if (list_stride < (size_t)c.lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one list block");
-  if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
-  {   // the four previous lists against the four current ones: no block may be both
-    const char* a = static_cast<const char*>(d_prev_lists); const char* b = static_cast<const char*>(d_cur_lists);
-    const size_t span = sizeof(float) * (3 * list_stride + (size_t)c.lay.words);
-    if (a < b + span && b < a + span) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current lists must not overlap");
-  }
+  if (const int rc = carry_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev_lists, d_cur_lists, desc_dim, d_kps_xy, d_kp_scores, d_kp_desc, d_n_kp, kp_cap, tp,
+                                     d_next_id, c, &total)) return rc;
+  if (const int rc = list_quad_check(c, list_stride, pyr_stride, total)) return rc;
+  q.list_stride = (long)list_stride; q.pyr_stride = pyr_stride;
   HIP_TRY(hipSetDevice(ctx_device(h)));
   hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp->win; c.iters = tp->iters;
-  c.prev = static_cast<const float*>(d_prev_lists); c.cur = static_cast<float*>(d_cur_lists);
-  c.kps = d_kps_xy; c.kp_scores = d_kp_scores; c.kp_desc = d_kp_desc; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
-  c.total = tp->total_feature_num; c.near_thr = (double)tp->near_lk_thread_rate; c.min_dist = tp->feature_min_dist;
-  c.next_id = d_next_id;
-  q.list_stride = (long)list_stride; q.pyr_stride = pyr_stride;
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_carry_quad_step_kernel, dim3((c.lay.cap + 3) / 4, 4), dim3(256), 0, s, q);
@@ -439,55 +350,16 @@ int d2fe_lk_carry_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, con
   return D2FE_OK;
 }
 
-namespace {
-// what the two neighbour launches share: the checks and the kernel's arguments; desc_dim = 0: flow lists (cap_tracks = max(total_feature_num, 1), no descriptors)
-int neighbour_args(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists, size_t list_stride,
-                   int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, LkCarryNbArgs& r) {
-  if (!h || !d_pyr || !d_lists || !tp || !d_nb_xy || !d_nb_status) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  if (const char* why = lk_carry_check_params(tp)) return ctx_fail(D2FE_ERR_INVALID, why);
-  if (width < 16 || height < 16 || (size_t)width * height > (1u << 28)) return ctx_fail(D2FE_ERR_INVALID, "bad pyramid geometry");
-  if (quads < 1 || quads > 16383 || desc_dim < 0 || desc_dim > 65536 || !(undistort_fov > 0.0)) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
-  size_t total = 0;
-  pyr_geometry(r.P, width, height, tp->levels, &total);
-  const CarryLayout lay = desc_dim > 0 ? carry_layout(tp->total_feature_num + 1, desc_dim) : carry_layout(tp->total_feature_num > 1 ? tp->total_feature_num : 1, 0);
-  if (list_stride < (size_t)lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one list block");
-  if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
-  r.pyr = d_pyr; r.pyr_stride = pyr_stride; r.quads = quads; r.cap = lay.cap; r.win = tp->win; r.iters = tp->iters;
-  r.move_cols = d2fe_half_move_cols(width, undistort_fov);
-  r.lists = static_cast<const float*>(d_lists); r.list_stride = (long)list_stride; r.off_pts = lay.off[D2FE_LKC_PTS];
-  r.xy = d_nb_xy; r.status = d_nb_status;
-  return D2FE_OK;
-}
-}  // namespace
-
 int d2fe_lk_carry_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
                                    size_t list_stride, int desc_dim, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
   if (desc_dim < 1) return ctx_fail(D2FE_ERR_INVALID, "quads must be 1..16383, desc_dim 1..65536, undistort_fov > 0");
-  LkCarryNbArgs r{};
-  if (const int rc = neighbour_args(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, desc_dim, tp, d_nb_xy, d_nb_status, r)) return rc;
-  HIP_TRY(hipSetDevice(ctx_device(h)));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  {
-    ProfScope ps(h, D2FE_PROF_LK, s);
-    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((r.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
-  }
-  HIP_TRY(hipGetLastError());
-  return D2FE_OK;
+  return lk_neighbour_launch(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, desc_dim, tp, d_nb_xy, d_nb_status, stream);
 }
 
 // the same kernel over flow lists (lk_flow.hip), which carry no descriptors
 int d2fe_lk_flow_neighbour_device(d2fe_handle h, const uint8_t* d_pyr, size_t pyr_stride, int quads, int width, int height, double undistort_fov, const void* d_lists,
                                   size_t list_stride, const d2fe_track_params* tp, float* d_nb_xy, uint8_t* d_nb_status, void* stream) {
-  LkCarryNbArgs r{};
-  if (const int rc = neighbour_args(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, 0, tp, d_nb_xy, d_nb_status, r)) return rc;
-  HIP_TRY(hipSetDevice(ctx_device(h)));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  {
-    ProfScope ps(h, D2FE_PROF_LK, s);
-    hipLaunchKernelGGL(lk_carry_neighbour_kernel, dim3((r.cap + 3) / 4, 4, quads), dim3(256), 0, s, r);
-  }
-  HIP_TRY(hipGetLastError());
-  return D2FE_OK;
+  return lk_neighbour_launch(h, d_pyr, pyr_stride, quads, width, height, undistort_fov, d_lists, list_stride, 0, tp, d_nb_xy, d_nb_status, stream);
 }
 
 }  // extern "C"

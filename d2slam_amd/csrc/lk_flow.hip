@@ -4,8 +4,10 @@
 //   detectFastByRegion                 opticaltrack_utils.cpp:444-493: FAST per region, sorted by response, the first `features`
 //
 // MI355X mapping.  One frame = FIVE launches, whatever the list holds:
-//   1. lk_flow_step_kernel   one 64-lane wave per entry of the previous list tracks it (lk_bidir, lk_device.h); the last workgroup to arrive runs b-c (list_reduce_prune,
-//                            lk_list_device.h: the code of the SuperPoint list), writes the tracked entries and decides `lack` and `num` into the list header
+//   1. lk_flow_step_kernel   one 64-lane wave per entry of the previous list tracks it and the workgroups take the list's ticket (list_track_and_arrive); the last
+//                            workgroup to arrive runs b-c (list_reduce_prune), writes the tracked entries and decides `lack` and `num` into the list header.  Both
+//                            functions, the per-camera view of the arguments (ListCamera), the quad-level id hand-out and the entry points' shared refusals are
+//                            lk_list_device.h's: one copy for this list and the SuperPoint list (lk_carry.hip)
 //   2. fast_clear_kernel     score map and candidate count to zero
 //   3. fast_region_kernel    } fast_device.h, the kernels of d2fe_detect_fast_by_region; `features` is header word `num`, read on the device
 //   4. fast_nonmax_kernel    }
@@ -161,61 +163,27 @@ __global__ __launch_bounds__(1024) void fast_select_kernel(const int* __restrict
   if (threadIdx.x == 0) n_out[0] = K;
 }
 
-struct LkFlowArgs {
-  const uint8_t* prev_pyr; const uint8_t* cur_pyr;
-  LkPairDev P;                      // geometry only
-  int win, iters;
-  const float* prev; float* cur;    // list blocks
-  CarryLayout lay;                  // D = 0
-  const float* kps; const int* n_kp; int kp_cap;      // kp_cap = 0: no SuperPoint keypoints
-  int total;                        // total_feature_num
-  double near_thr, min_dist;
-  int* next_id;
-  const int4* pool; const int* count; int pool_cap;
-};
+struct LkFlowArgs : LkListArgs { const int4* pool; const int* count; int pool_cap; };      // lay.D = 0; the detector's candidate pool beside LkListArgs
 
-__device__ __forceinline__ int flow_n_kp(const LkFlowArgs& c) {
-  int n_kp = c.kp_cap > 0 ? __builtin_amdgcn_readfirstlane(c.n_kp[0]) : 0;
-  return n_kp < 0 ? 0 : n_kp > c.kp_cap ? c.kp_cap : n_kp;
+// the camera's view (lk_list_device.h) with its candidate pool and count, which lie in the camera's own detector scratch
+struct FlowCamera : ListCamera { const int4* pool; const int* count; };
+__device__ __forceinline__ FlowCamera flow_camera(const LkFlowArgs& c, int cam, long list_stride, size_t pyr_stride, size_t scratch_stride) {
+  return FlowCamera{list_camera(c, cam, list_stride, pyr_stride), reinterpret_cast<const int4*>(reinterpret_cast<const char*>(c.pool) + (size_t)cam * scratch_stride),
+                    reinterpret_cast<const int*>(reinterpret_cast<const char*>(c.count) + (size_t)cam * scratch_stride)};
 }
 
 // launch 1: steps a-c and the decision of detectPoints, for workgroup bx of the nblocks that step this list
-__device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, int bx, int nblocks) {
+__device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, const ListCamera& v, int bx, int nblocks) {
   __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];
   __shared__ int s_src[LKC_MAX];
   __shared__ int s_cnt[4];          // [1] survivors of the tracker, [2] survivors of removeNearPoints, [3] this workgroup arrived last
+  int n_prev;
+  if (!list_track_and_arrive(c, v, bx, nblocks, s_cnt + 3, n_prev)) return;      // step a and the ticket (lk_list_device.h)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cap = c.lay.cap;
-  const int* phdr = reinterpret_cast<const int*>(c.prev);
-  int* hdr = reinterpret_cast<int*>(c.cur);
-  float* trk_xy = c.cur + c.lay.off[D2FE_LKC_TRK_XY];
-  uint8_t* trk_st = reinterpret_cast<uint8_t*>(c.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
-  const float* ppts = c.prev + c.lay.off[D2FE_LKC_PTS];
-  int n_prev = __builtin_amdgcn_readfirstlane(phdr[0]);
-  n_prev = n_prev < 0 ? 0 : n_prev > cap ? cap : n_prev;
-
-  // ---- a. track: one wave per entry of the previous list
-  const int slot = bx * 4 + wave;
-  if (slot < n_prev) {
-    LkArgs a{};
-    a.win = c.win; a.iters = c.iters;
-    const float ppx = ppts[2 * slot], ppy = ppts[2 * slot + 1];
-    float cx, cy;
-    const int ok = lk_bidir(a, c.P, c.prev_pyr, c.cur_pyr, ppx, ppy, cx, cy, lane);
-    if (lane == 0) { trk_xy[2 * slot] = cx; trk_xy[2 * slot + 1] = cy; trk_st[slot] = (uint8_t)ok; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // the wave's stores have left before its workgroup arrives
-  }
-  // ---- ticket (the pattern of lk_carry_step_kernel): the last workgroup to arrive acquires everybody's stores and finishes the list
-  __syncthreads();
-  if (tid == 0) {
-    const int old = __hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == nblocks - 1;
-    if (last) __hip_atomic_store(hdr + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch that writes this block
-    s_cnt[3] = last;
-  }
-  __syncthreads();
-  if (!s_cnt[3]) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  int* hdr = reinterpret_cast<int*>(v.cur);
+  float* trk_xy = v.cur + c.lay.off[D2FE_LKC_TRK_XY];
+  uint8_t* trk_st = reinterpret_cast<uint8_t*>(v.cur + c.lay.off[D2FE_LKC_TRK_STATUS]);
 
   // ---- b-c on wave 0
   if (wave == 0) {
@@ -226,10 +194,10 @@ __device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, int bx, int 
   __syncthreads();
   // ---- the tracked entries (step e's first half), zeros behind them
   const int cnt = s_cnt[1], m = s_cnt[2];
-  float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
-  int* id = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_ID]);
-  int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
-  const int* pid = reinterpret_cast<const int*>(c.prev + c.lay.off[D2FE_LKC_ID]);
+  float* pts = v.cur + c.lay.off[D2FE_LKC_PTS];
+  int* id = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_ID]);
+  int* src = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_SRC]);
+  const int* pid = reinterpret_cast<const int*>(v.prev + c.lay.off[D2FE_LKC_ID]);
   for (int k = tid; k < cap; k += 256) {
     const bool live = k < m;
     const int sk = live ? s_src[k] : 0;
@@ -240,7 +208,7 @@ __device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, int bx, int 
   }
   // ---- d, the decision (opticaltrack_utils.cpp:379-392): detect when more than a quarter is missing, twice the shortfall when anything exists
   if (tid == 0) {
-    const int have = flow_n_kp(c) + m;
+    const int have = list_n_kp(c, v) + m;
     const int lack = c.total - have;
     const int num = lack > c.total / 4 ? (have > 0 ? 2 * lack : lack) : 0;
     hdr[0] = m; hdr[1] = n_prev; hdr[2] = n_prev - cnt; hdr[3] = cnt - m; hdr[4] = 0;
@@ -250,28 +218,28 @@ __device__ __forceinline__ void flow_step_body(const LkFlowArgs& c, int bx, int 
   if (tid >= 10 && tid < 64) hdr[tid] = 0;
 }
 
-__global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) { flow_step_body(c, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void lk_flow_step_kernel(LkFlowArgs c) { flow_step_body(c, list_camera(c, 0, 0, 0), blockIdx.x, gridDim.x); }
 
 // launch 5: the rest of step d and the new entries of step e, for a list whose `num` is > 0.  QUAD (the four-camera launch, lk_flow_quad_merge_kernel): the ids of the new
 // entries, header word 6 and *next_id belong to the launch's last finisher, which knows the new entries of the lower cameras; they are left alone here
 template <bool QUAD>
-__device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c) {
+__device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c, const FlowCamera& v) {
   __shared__ SelectLds L;
   __shared__ float s_x[LKC_MAX], s_y[LKC_MAX];      // the tracked entries, then the accepted candidates
   __shared__ uint8_t s_blocked[FLOW_KMAX];
   __shared__ int s_acc;
-  int* hdr = reinterpret_cast<int*>(c.cur);
+  int* hdr = reinterpret_cast<int*>(v.cur);
   const int num = hdr[FLOW_HDR_NUM];
   const int tid = threadIdx.x, lane = tid & 63;
-  const int m = hdr[0], lack = hdr[FLOW_HDR_LACK], n_kp = flow_n_kp(c);
+  const int m = hdr[0], lack = hdr[FLOW_HDR_LACK], n_kp = list_n_kp(c, v);
   const int id0 = QUAD ? 0 : *c.next_id;
-  float* pts = c.cur + c.lay.off[D2FE_LKC_PTS];
-  const int K = fast_select_sorted(c.pool, min(c.count[0], c.pool_cap), num, L);
+  float* pts = v.cur + c.lay.off[D2FE_LKC_PTS];
+  const int K = fast_select_sorted(v.pool, min(v.count[0], c.pool_cap), num, L);
   // the selected candidates in order (over the keys, which the ranking no longer needs) and the tracked entries
   float* s_cx = reinterpret_cast<float*>(L.key);
   float* s_cy = s_cx + FLOW_KMAX;
   for (int k = tid; k < K; k += 1024) {
-    const int4 p = c.pool[L.ord[k]];
+    const int4 p = v.pool[L.ord[k]];
     s_cx[k] = (float)p.x; s_cy[k] = (float)p.y;
   }
   for (int k = tid; k < m; k += 1024) { s_x[k] = pts[2 * k]; s_y[k] = pts[2 * k + 1]; }
@@ -281,7 +249,7 @@ __device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c) {
   for (int k = tid; k < K; k += 1024) {
     const float px = s_cx[k], py = s_cy[k];
     bool hit = false;
-    for (int j = 0; j < n_kp && !hit; ++j) hit = nearer(px, py, c.kps[2 * j], c.kps[2 * j + 1], thr, lo, hi);
+    for (int j = 0; j < n_kp && !hit; ++j) hit = nearer(px, py, v.kps[2 * j], v.kps[2 * j + 1], thr, lo, hi);
     for (int j = 0; j < m && !hit; ++j) hit = nearer(px, py, s_x[j], s_y[j], thr, lo, hi);
     s_blocked[k] = hit ? 1 : 0;
   }
@@ -304,8 +272,8 @@ __device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c) {
   }
   __syncthreads();       // also: every thread has read *next_id
   const int acc = s_acc;
-  int* id = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_ID]);
-  int* src = reinterpret_cast<int*>(c.cur + c.lay.off[D2FE_LKC_SRC]);
+  int* id = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_ID]);
+  int* src = reinterpret_cast<int*>(v.cur + c.lay.off[D2FE_LKC_SRC]);
   for (int e = tid; e < acc; e += 1024) {
     pts[2 * (m + e)] = s_x[m + e]; pts[2 * (m + e) + 1] = s_y[m + e];
     if (!QUAD) id[m + e] = id0 + e;
@@ -319,7 +287,7 @@ __device__ __forceinline__ void flow_merge_body(const LkFlowArgs& c) {
 
 __global__ __launch_bounds__(1024) void lk_flow_merge_kernel(LkFlowArgs c) {
   if (reinterpret_cast<const int*>(c.cur)[FLOW_HDR_NUM] <= 0) return;
-  flow_merge_body<false>(c);
+  flow_merge_body<false>(c, flow_camera(c, 0, 0, 0, 0));
 }
 
 // ---- the quadcam form ---------------------------------------------------------------------------------------------------------------------------------------
@@ -334,19 +302,11 @@ struct LkFlowQuadArgs {
 };
 constexpr int FLOW_HDR_QUAD = 10;   // header word of CAMERA 0's current list: the quad-level arrival counter of launch 5 (a "rest 0" word of include/d2fe.h; left zero)
 
-__device__ __forceinline__ LkFlowArgs flow_camera(const LkFlowQuadArgs& q, int cam) {
-  LkFlowArgs c = q.c;
-  c.prev += (size_t)cam * q.list_stride; c.cur += (size_t)cam * q.list_stride;
-  c.prev_pyr += (size_t)cam * q.pyr_stride; c.cur_pyr += (size_t)cam * q.pyr_stride;
-  if (c.kp_cap > 0) { c.kps += (size_t)cam * c.kp_cap * 2; c.n_kp += cam; }      // rows of the dense [4][kp_cap] extract outputs
-  c.pool = reinterpret_cast<const int4*>(reinterpret_cast<const char*>(c.pool) + (size_t)cam * q.scratch_stride);
-  c.count = reinterpret_cast<const int*>(reinterpret_cast<const char*>(c.count) + (size_t)cam * q.scratch_stride);
-  return c;
-}
-
 // launch 1, grid (cap_tracks / 4, 4): camera blockIdx.y's workgroups take that camera's ticket (header word 5 of ITS list); word 6 of every header is next_id BEFORE the
 // quad frame, which is what four single steps leave when no camera detects
-__global__ __launch_bounds__(256) void lk_flow_quad_step_kernel(LkFlowQuadArgs q) { flow_step_body(flow_camera(q, blockIdx.y), blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void lk_flow_quad_step_kernel(LkFlowQuadArgs q) {
+  flow_step_body(q.c, list_camera(q.c, blockIdx.y, q.list_stride, q.pyr_stride), blockIdx.x, gridDim.x);
+}
 
 // launches 2-4 over four cameras: fast_clear_kernel, fast_region_kernel and fast_nonmax_kernel with the camera as a grid dimension; each camera reads its OWN `num`
 struct FastQuadArgs {
@@ -380,43 +340,18 @@ __global__ __launch_bounds__(256) void fast_quad_nonmax_kernel(FastQuadArgs a) {
                    fast_quad_at(a.count, cam, a.scratch_stride), blockIdx.x * 64 + (threadIdx.x & 63), blockIdx.y * 4 + (threadIdx.x >> 6));
 }
 
-// launch 5, four workgroups: workgroup c selects and merges for camera c (nothing when its `num` is 0), then the four take the quad-level ticket and the last one reads
-// the four counts of new entries and hands the ids out: camera c's k-th new entry gets next_id + (new entries of cameras < c) + k, header word 6 of camera c is
-// next_id after that camera, as four single steps in camera order leave them.  The workgroups can sit on different XCDs: agent-scope release / acquire around the ticket
+// launch 5, four workgroups: workgroup c selects and merges for camera c (nothing when its `num` is 0), then the four take the quad-level ticket and the last one hands
+// the ids out in camera order (quad_hand_out_ids, lk_list_device.h), as four single steps in camera order leave them
 __global__ __launch_bounds__(1024) void lk_flow_quad_merge_kernel(LkFlowQuadArgs q) {
   __shared__ int s_last;
-  const int tid = threadIdx.x, cam = blockIdx.x;
   float* cur0 = q.c.cur;
   int any = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) any |= reinterpret_cast<const int*>(cur0 + (size_t)k * q.list_stride)[FLOW_HDR_NUM] > 0 ? 1 : 0;
   if (!any) return;                 // the steady state: launch 1 left every header as four single steps do
-  const LkFlowArgs c = flow_camera(q, cam);
-  if (reinterpret_cast<const int*>(c.cur)[FLOW_HDR_NUM] > 0) flow_merge_body<true>(c);
-  // ---- the quad-level ticket: the list of this camera has left before its workgroup arrives
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  int* qt = reinterpret_cast<int*>(cur0) + FLOW_HDR_QUAD;
-  if (tid == 0) {
-    const int old = __hip_atomic_fetch_add(qt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == 3;
-    if (last) __hip_atomic_store(qt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  int base = *c.next_id;
-  for (int k = 0; k < 4; ++k) {
-    int* h = reinterpret_cast<int*>(cur0 + (size_t)k * q.list_stride);
-    const int len = __hip_atomic_load(h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), fresh = __hip_atomic_load(h + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int* id = h + c.lay.off[D2FE_LKC_ID];
-    for (int e = len - fresh + tid; e < len; e += 1024) id[e] = base + (e - (len - fresh));
-    base += fresh;
-    if (tid == 0) h[6] = base;
-  }
-  __syncthreads();       // every thread has read *next_id
-  if (tid == 0) *c.next_id = base;
+  const FlowCamera v = flow_camera(q.c, blockIdx.x, q.list_stride, q.pyr_stride, q.scratch_stride);
+  if (reinterpret_cast<const int*>(v.cur)[FLOW_HDR_NUM] > 0) flow_merge_body<true>(q.c, v);
+  quad_hand_out_ids(cur0, q.list_stride, FLOW_HDR_QUAD, q.c.lay.off[D2FE_LKC_ID], q.c.next_id, &s_last);
 }
 
 const char* flow_check_geometry(int width, int height, int cap_tracks, int cols, int rows, int threshold) {
@@ -473,7 +408,7 @@ const char* lk_flow_check_params(const d2fe_flow_params* fp, int width, int heig
   if (fp->struct_size != (int32_t)sizeof(d2fe_flow_params)) return "d2fe_flow_params.struct_size";
   if (const char* why = lk_carry_check_params(&fp->track)) return why;
   if (fp->superpoint != 0 && fp->superpoint != 1) return "superpoint must be 0 or 1";
-  return flow_check_geometry(width, height, fp->track.total_feature_num > 1 ? fp->track.total_feature_num : 1, fp->fast_cols, fp->fast_rows, fp->fast_threshold);
+  return flow_check_geometry(width, height, flow_cap_tracks(fp->track), fp->fast_cols, fp->fast_rows, fp->fast_threshold);
 }
 
 }  // namespace d2fe
@@ -522,29 +457,28 @@ int d2fe_detect_fast_device(d2fe_handle h, const uint8_t* d_pyr, int width, int 
   return D2FE_OK;
 }
 
+namespace {
+// what the two step entry points share: their refusals, the detector scratch of camera 0 and the kernel's arguments
+int flow_step_args(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev, void* d_cur, const float* d_kps_xy,
+                   const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp, int32_t* d_next_id, void* d_scratch, LkFlowArgs& c, FlowScratch& f, size_t* pyr_total) {
+  if (!fp || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (const char* why = lk_flow_check_params(fp, width, height)) return ctx_fail(D2FE_ERR_INVALID, why);
+  if ((uintptr_t)d_scratch & 15u) return ctx_fail(D2FE_ERR_INVALID, "the scratch must be 16-byte aligned");
+  const CarryLayout lay = list_layout(fp->track, 0);
+  f = flow_scratch(d_scratch, width, height, lay.cap, fp->fast_cols, fp->fast_rows);
+  c.pool = f.pool; c.count = f.count; c.pool_cap = f.pool_cap;
+  return list_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev, d_cur, lay, d_kps_xy, d_n_kp, kp_cap, fp->superpoint != 0, fp->track, d_next_id, c, pyr_total);
+}
+}  // namespace
+
 int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, int width, int height, const void* d_prev_list, void* d_cur_list,
                              const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp, int32_t* d_next_id, void* d_scratch, void* stream) {
-  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_list || !d_cur_list || !fp || !d_next_id || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  if (const char* why = lk_flow_check_params(fp, width, height)) return ctx_fail(D2FE_ERR_INVALID, why);
-  const d2fe_track_params& tp = fp->track;
-  const int cap_tracks = tp.total_feature_num > 1 ? tp.total_feature_num : 1;
-  if (d_prev_list == d_cur_list) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current list must be different blocks");
-  if ((uintptr_t)d_scratch & 15u) return ctx_fail(D2FE_ERR_INVALID, "the scratch must be 16-byte aligned");
-  if (kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "kp_cap must be 0..16384");
-  if (!fp->superpoint) kp_cap = 0;
-  if (kp_cap > 0 && (!d_kps_xy || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
+  LkFlowArgs c{};
+  FlowScratch f{};
+  if (const int rc = flow_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev_list, d_cur_list, d_kps_xy, d_n_kp, kp_cap, fp, d_next_id, d_scratch, c, f, nullptr)) return rc;
+  const int cap_tracks = c.lay.cap;
   HIP_TRY(hipSetDevice(ctx_device(h)));
   hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  const FlowScratch f = flow_scratch(d_scratch, width, height, cap_tracks, fp->fast_cols, fp->fast_rows);
-  LkFlowArgs c{};
-  lk_pyr_geometry(c.P, width, height, tp.levels, nullptr);
-  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp.win; c.iters = tp.iters;
-  c.prev = static_cast<const float*>(d_prev_list); c.cur = static_cast<float*>(d_cur_list);
-  c.lay = carry_layout(cap_tracks, 0);
-  c.kps = d_kps_xy; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
-  c.total = tp.total_feature_num; c.near_thr = (double)tp.near_lk_thread_rate; c.min_dist = tp.feature_min_dist;
-  c.next_id = d_next_id;
-  c.pool = f.pool; c.count = f.count; c.pool_cap = f.pool_cap;
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_flow_step_kernel, dim3((cap_tracks + 3) / 4), dim3(256), 0, s, c);
@@ -563,37 +497,18 @@ int d2fe_lk_flow_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uin
 int d2fe_lk_flow_quad_step_device(d2fe_handle h, const uint8_t* d_prev_pyr, const uint8_t* d_cur_pyr, size_t pyr_stride, int width, int height, const void* d_prev_lists,
                                   void* d_cur_lists, size_t list_stride, const float* d_kps_xy, const int32_t* d_n_kp, int kp_cap, const d2fe_flow_params* fp,
                                   int32_t* d_next_id, void* d_scratch, size_t scratch_stride, void* stream) {
-  if (!h || !d_prev_pyr || !d_cur_pyr || !d_prev_lists || !d_cur_lists || !fp || !d_next_id || !d_scratch) return ctx_fail(D2FE_ERR_INVALID, "null argument");
-  if (const char* why = lk_flow_check_params(fp, width, height)) return ctx_fail(D2FE_ERR_INVALID, why);
-  const d2fe_track_params& tp = fp->track;
-  const int cap_tracks = tp.total_feature_num > 1 ? tp.total_feature_num : 1;
-  if (kp_cap < 0 || kp_cap > 16384) return ctx_fail(D2FE_ERR_INVALID, "kp_cap must be 0..16384");
-  if (!fp->superpoint) kp_cap = 0;
-  if (kp_cap > 0 && (!d_kps_xy || !d_n_kp)) return ctx_fail(D2FE_ERR_INVALID, "null keypoint arrays with kp_cap > 0");
   LkFlowQuadArgs q{};
   LkFlowArgs& c = q.c;
+  FlowScratch f{};
   size_t total = 0;
-  lk_pyr_geometry(c.P, width, height, tp.levels, &total);
-  c.lay = carry_layout(cap_tracks, 0);
-  const FlowScratch f = flow_scratch(d_scratch, width, height, cap_tracks, fp->fast_cols, fp->fast_rows);
-  if (list_stride < (size_t)c.lay.words || list_stride > (1ul << 40)) return ctx_fail(D2FE_ERR_INVALID, "list_stride (words) must be at least one flow list block");
-  if (pyr_stride < total) return ctx_fail(D2FE_ERR_INVALID, "pyr_stride (bytes) must be at least one pyramid");
-  if (((uintptr_t)d_scratch & 15u) || (scratch_stride & 15u) || scratch_stride < f.bytes || scratch_stride > (1ul << 40))
+  if (const int rc = flow_step_args(h, d_prev_pyr, d_cur_pyr, width, height, d_prev_lists, d_cur_lists, d_kps_xy, d_n_kp, kp_cap, fp, d_next_id, d_scratch, c, f, &total)) return rc;
+  if (const int rc = list_quad_check(c, list_stride, pyr_stride, total)) return rc;
+  if ((scratch_stride & 15u) || scratch_stride < f.bytes || scratch_stride > (1ul << 40))
     return ctx_fail(D2FE_ERR_INVALID, "the scratch must be 16-byte aligned, scratch_stride (bytes) a multiple of 16 and at least d2fe_lk_flow_scratch_bytes");
-  {   // the four previous lists against the four current ones: no block may be both
-    const char* a = static_cast<const char*>(d_prev_lists); const char* b = static_cast<const char*>(d_cur_lists);
-    const size_t span = sizeof(float) * (3 * list_stride + (size_t)c.lay.words);
-    if (a < b + span && b < a + span) return ctx_fail(D2FE_ERR_INVALID, "the previous and the current lists must not overlap");
-  }
+  const int cap_tracks = c.lay.cap;
+  q.list_stride = (long)list_stride; q.pyr_stride = pyr_stride; q.scratch_stride = scratch_stride;
   HIP_TRY(hipSetDevice(ctx_device(h)));
   hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(h);
-  c.prev_pyr = d_prev_pyr; c.cur_pyr = d_cur_pyr; c.win = tp.win; c.iters = tp.iters;
-  c.prev = static_cast<const float*>(d_prev_lists); c.cur = static_cast<float*>(d_cur_lists);
-  c.kps = d_kps_xy; c.n_kp = d_n_kp; c.kp_cap = kp_cap;
-  c.total = tp.total_feature_num; c.near_thr = (double)tp.near_lk_thread_rate; c.min_dist = tp.feature_min_dist;
-  c.next_id = d_next_id;
-  c.pool = f.pool; c.count = f.count; c.pool_cap = f.pool_cap;
-  q.list_stride = (long)list_stride; q.pyr_stride = pyr_stride; q.scratch_stride = scratch_stride;
   {
     ProfScope ps(h, D2FE_PROF_LK, s);
     hipLaunchKernelGGL(lk_flow_quad_step_kernel, dim3((cap_tracks + 3) / 4, 4), dim3(256), 0, s, q);

@@ -459,7 +459,7 @@ int pipe_alloc_blocks(d2fe_pipe_s* p) {
     if (p->sp_lk) { p->o_trd = o; o += up64((NL * p->capT + 1) / 2); }
   }
   if (p->flow) {
-    p->capF = p->fp.track.total_feature_num > 1 ? p->fp.track.total_feature_num : 1;
+    p->capF = flow_cap_tracks(p->fp.track);
     p->flist_words = d2fe_lk_flow_list_bytes(p->capF) / sizeof(float);
     p->o_flist = o; o += NL * p->flist_words;
     if (!p->mono) {
@@ -532,6 +532,25 @@ int pipe_alloc_pairs(d2fe_pipe_s* p) {
     HIP_TRY(hipMalloc(&p->d_pairs, sizeof(MatchPairDesc) * tab.size()));
     HIP_TRY(hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice));
   }
+  return D2FE_OK;
+}
+
+// the three steps again for a pipe whose lanes exist (the list block changed size before the first submit); the blocks are zeroed on the null stream
+int pipe_realloc_blocks(d2fe_pipe_s* p) {
+  int rc = pipe_alloc_blocks(p);
+  for (auto& L : p->lanes) if (rc == D2FE_OK) rc = pipe_alloc_pinned(p, L);
+  if (rc == D2FE_OK) rc = pipe_alloc_pairs(p);
+  if (rc == D2FE_OK && hipDeviceSynchronize() != hipSuccess) rc = pipe_fail(D2FE_ERR_HIP, "hipDeviceSynchronize");
+  return rc;
+}
+
+// the state of a landmark-list chain (sp_lk at creation, the flow landmarks when they are switched on): the lanes' chain events, the carried pyramid and the id counter
+int pipe_alloc_chain(d2fe_pipe_s* p) {
+  for (auto& L : p->lanes) if (!L.ev_chain) HIP_TRY(hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming));
+  HIP_TRY(hipMalloc(&p->d_carry_pyr, p->pyr_total));
+  HIP_TRY(hipMemset(p->d_carry_pyr, 0, p->pyr_total));
+  HIP_TRY(hipMalloc(&p->d_next_id, 64));
+  HIP_TRY(hipMemset(p->d_next_id, 0, 64));
   return D2FE_OK;
 }
 
@@ -743,10 +762,8 @@ int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2
     if (nv_streams)      // CU-masked lanes whose second stream could not be created with the mask above
       for (auto& L : p->lanes) if (!L.nv) HIP_TRY(hipStreamCreateWithFlags(&L.nv, hipStreamNonBlocking));
     if (p->sp_lk) {
-      HIP_TRY(hipMalloc(&p->d_carry_pyr, p->pyr_total));
-      HIP_TRY(hipMemset(p->d_carry_pyr, 0, p->pyr_total));
-      HIP_TRY(hipMalloc(&p->d_next_id, 64));
-      HIP_TRY(hipMemset(p->d_next_id, 0, 64));
+      const int rcc = pipe_alloc_chain(p);
+      if (rcc) return rcc;
     }
     {
       const int rcr = pipe_alloc_pairs(p);
@@ -1060,18 +1077,9 @@ int d2fe_pipe_flow_enable(d2fe_pipe p, const d2fe_flow_params* fp) {
       HIP_TRY(hipMalloc(&p->d_lk_ws, p->lk_ws_lane * p->K));
       for (int k = 0; k < p->K; ++k) p->lanes[k].d_lk = p->d_lk_ws + (size_t)k * p->lk_ws_lane;
     }
-    for (auto& L : p->lanes) if (!L.ev_chain) HIP_TRY(hipEventCreateWithFlags(&L.ev_chain, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&p->d_carry_pyr, p->pyr_total));
-    HIP_TRY(hipMemset(p->d_carry_pyr, 0, p->pyr_total));
-    HIP_TRY(hipMalloc(&p->d_next_id, 64));
-    HIP_TRY(hipMemset(p->d_next_id, 0, 64));
-    const int capF = p->fp.track.total_feature_num > 1 ? p->fp.track.total_feature_num : 1;
-    HIP_TRY(hipMalloc(&p->d_flow_scratch, d2fe_lk_flow_scratch_bytes(p->W, p->H, capF, p->fp.fast_cols, p->fp.fast_rows)));
-    int rc2 = pipe_alloc_blocks(p);
-    for (auto& L : p->lanes) if (rc2 == D2FE_OK) rc2 = pipe_alloc_pinned(p, L);
-    if (rc2 == D2FE_OK) rc2 = pipe_alloc_pairs(p);
-    if (rc2 == D2FE_OK && hipDeviceSynchronize() != hipSuccess) rc2 = pipe_fail(D2FE_ERR_HIP, "hipDeviceSynchronize");      // the blocks are zeroed on the null stream
-    return rc2;
+    if (const int rc2 = pipe_alloc_chain(p)) return rc2;
+    HIP_TRY(hipMalloc(&p->d_flow_scratch, d2fe_lk_flow_scratch_bytes(p->W, p->H, flow_cap_tracks(p->fp.track), p->fp.fast_cols, p->fp.fast_rows)));
+    return pipe_realloc_blocks(p);
   }();
   if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
   return rc;
@@ -1091,14 +1099,8 @@ int d2fe_pipe_flow_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_flow_result
   const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
   const float* B = p->lanes[k].pin_out[set];
   const size_t r0 = p->C > 1 ? (size_t)ti.j : 0, T = (size_t)p->capF;
-  const float* list = B + p->o_flist + r0 * p->flist_words;
-  const int32_t* hdr = reinterpret_cast<const int32_t*>(list);
-  out->frames = p->F; out->cap_tracks = p->capF; out->list_words = (int32_t)p->flist_words;
-  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
-  out->lack = hdr + 7; out->num = hdr + 8; out->n_cand = hdr + 9;
-  out->pts_xy = list + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_PTS);
-  out->id = hdr + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_ID);
-  out->src = hdr + d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_SRC);
+  out->frames = p->F;
+  flow_list_view(out, B + p->o_flist + r0 * p->flist_words, p->capF, p->flist_words);
   if (!p->mono) {
     out->right_xy = B + p->o_frxy + r0 * T * 2;
     out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_frst) + r0 * T;
@@ -1120,10 +1122,7 @@ int d2fe_pipe_set_track_params(d2fe_pipe p, const d2fe_track_params* tp) {
   p->tp = *tp; p->tp.reserved = 0;
   if (p->tp.total_feature_num == old.total_feature_num) return D2FE_OK;       // same cap_tracks: same blocks
   // a failure below leaves the pipe without result blocks: final, like a failed submit
-  int rc = pipe_alloc_blocks(p);
-  for (auto& L : p->lanes) if (rc == D2FE_OK) rc = pipe_alloc_pinned(p, L);
-  if (rc == D2FE_OK) rc = pipe_alloc_pairs(p);
-  if (rc == D2FE_OK && hipDeviceSynchronize() != hipSuccess) rc = pipe_fail(D2FE_ERR_HIP, "hipDeviceSynchronize");      // the blocks are zeroed on the null stream
+  const int rc = pipe_realloc_blocks(p);
   if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
   return rc;
 }

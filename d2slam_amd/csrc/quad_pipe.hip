@@ -210,6 +210,103 @@ void quad_fill_pairs(const d2fe_quad_pipe_s* p, std::vector<MatchPairDesc>& tab)
     }
 }
 
+// What d2fe_quad_track_enable and d2fe_quad_flow_enable share (called with the pipe's mutex held, before the first submit): the mode's arrays in the result blocks,
+// everything the mode owns on the device and the host, and the pair tables that address the moved blocks.  The caller sets its mode flags when this returns D2FE_OK or
+// has set p->failed
+struct QuadListMode {
+  int cap;                 // slots of a list block (capT)
+  size_t list_words;       // words of a list block
+  size_t pyr_total;        // bytes of a view's pyramid
+  bool matches;            // sp_lk: the list matches (o_lm*, d_lpairs, d_lmatch_scratch) and the lanes' half-image pools of the lists (t_j*)
+  size_t fast_scratch;     // flow: bytes of one camera's detector scratch (0: none)
+};
+int quad_lists_enable(d2fe_quad_pipe_s* p, const QuadListMode& m) {
+  const int Q = p->Q, K = p->K;
+  const size_t T = (size_t)m.cap, D = (size_t)p->D, NI = (size_t)p->NI, NJ = 8 * (size_t)Q, lw = m.list_words, pyr_total = m.pyr_total;
+  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
+  size_t o = p->d2h_words;
+  const size_t o_list = o; o += NI * lw;
+  const size_t o_nbxy = o; o += up64(NI * T * 2);
+  const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
+  size_t o_lmn = 0, o_lmq = 0, o_lmt = 0, o_lmd = 0, t_jdesc = 0, t_jpts = 0, t_jmap = 0, t_jn = 0, t = 0;
+  if (m.matches) {
+    o_lmn = o; o += up64(NI);
+    o_lmq = o; o += up64(NI * T);
+    o_lmt = o; o += up64(NI * T);
+    o_lmd = o; o += up64(NI * T);
+    t_jdesc = t; t += up64(NJ * T * D);
+    t_jpts = t; t += up64(NJ * T * 2);
+    t_jmap = t; t += up64(NJ * T);
+    t_jn = t; t += up64(NJ);
+  }
+  const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap), tscr_words = t;
+  // everything new first; the pipe changes only when all of it is there
+  struct Fresh {
+    float* d_all = nullptr; float* d_trk = nullptr; uint8_t* d_pyr = nullptr; MatchPairDesc* d_lpairs = nullptr; int32_t* d_lms = nullptr; uint8_t* d_scr = nullptr;
+    std::vector<float*> pin; std::vector<hipEvent_t> ev; bool keep = false;
+    ~Fresh() {
+      if (keep) return;
+      for (void* q : {(void*)d_all, (void*)d_trk, (void*)d_pyr, (void*)d_lpairs, (void*)d_lms, (void*)d_scr}) if (q) (void)hipFree(q);
+      for (float* q : pin) if (q) (void)hipHostFree(q);
+      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+  } f;
+  const size_t all_words = 64 + (size_t)K * 2 * blk_words, trk_words = 4 * lw + 64 + (size_t)K * tscr_words;
+  const size_t pyr_bytes = (4 + (size_t)K * NI) * pyr_total, lms_lane = m.matches ? match_scratch_bytes(4 * Q, m.cap) : 0;
+  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
+  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // no keypoints, empty lists, every arrival counter zero
+  HIP_TRY(hipMalloc(&f.d_trk, sizeof(float) * trk_words));
+  HIP_TRY(hipMemset(f.d_trk, 0, sizeof(float) * trk_words));        // the four empty lists in front of the first quad frame, next_id = 0
+  HIP_TRY(hipMalloc(&f.d_pyr, pyr_bytes));
+  HIP_TRY(hipMemset(f.d_pyr, 0, pyr_bytes));
+  if (m.fast_scratch) HIP_TRY(hipMalloc(&f.d_scr, 4 * m.fast_scratch));      // its content between steps does not matter
+  f.pin.assign((size_t)2 * K, nullptr); f.ev.assign((size_t)K, nullptr);
+  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
+  for (int k = 0; k < K; ++k) HIP_TRY(hipEventCreateWithFlags(&f.ev[k], hipEventDisableTiming));
+  if (m.matches) {      // the neighbour pairs of the lists, on the lanes' pools
+    HIP_TRY(hipMalloc(&f.d_lpairs, sizeof(MatchPairDesc) * (size_t)K * 4 * Q));
+    HIP_TRY(hipMalloc(&f.d_lms, lms_lane * K));
+    HIP_TRY(hipMemset(f.d_lms, 0, lms_lane * K));
+    std::vector<MatchPairDesc> lt((size_t)K * 4 * Q);
+    for (int k = 0; k < K; ++k) {
+      float* X = f.d_trk + 4 * lw + 64 + (size_t)k * tscr_words;
+      for (int j = 0; j < 4 * Q; ++j) {
+        MatchPairDesc& d = lt[(size_t)k * 4 * Q + j];
+        const size_t ja = 2 * (size_t)j, jb = ja + 1;
+        d.a = X + t_jdesc + ja * T * D; d.b = X + t_jdesc + jb * T * D;
+        d.pts_a = X + t_jpts + ja * T * 2; d.pts_b = X + t_jpts + jb * T * 2;
+        d.na = reinterpret_cast<int32_t*>(X + t_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + t_jn) + jb;
+        d.radius = p->cfg.radius_neighbour;
+      }
+    }
+    HIP_TRY(hipMemcpy(f.d_lpairs, lt.data(), sizeof(MatchPairDesc) * lt.size(), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipDeviceSynchronize());        // the memsets ran on the null stream, which the lanes' streams do not wait for
+  // ---- commit: nothing has been submitted, so no stream holds an address of the old blocks
+  f.keep = true;
+  (void)hipFree(p->d_all);
+  p->d_all = f.d_all; p->d_trk = f.d_trk; p->d_trk_pyr = f.d_pyr; p->d_lpairs = f.d_lpairs; p->d_lmatch_scratch = f.d_lms; p->lmatch_scratch_lane = lms_lane;
+  p->d_flow_scratch = f.d_scr; p->flow_scratch_stride = m.fast_scratch;
+  for (int k = 0; k < K; ++k) {
+    auto& L = p->lanes[k];
+    for (int set = 0; set < 2; ++set) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = f.pin[(size_t)2 * k + set]; }
+    L.ev_chain = f.ev[k];
+  }
+  p->capT = m.cap; p->list_words = lw; p->pyr_total = pyr_total;
+  p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst; p->o_lmn = o_lmn; p->o_lmq = o_lmq; p->o_lmt = o_lmt; p->o_lmd = o_lmd;
+  p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
+  p->t_jdesc = t_jdesc; p->t_jpts = t_jpts; p->t_jmap = t_jmap; p->t_jn = t_jn; p->tscr_words = tscr_words;
+  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
+    std::vector<MatchPairDesc> tab;
+    quad_fill_pairs(p, tab);
+    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
+      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+    }
+  }
+  return D2FE_OK;
+}
+
 // one submit: H2D, undistort, NetVLAD beside SuperPoint, compaction, ONE matcher launch, remap, ONE D2H -- all on the lane's streams
 int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_stride, size_t quad_stride, int64_t* ticket) {
   const long long P = p->next_ticket;
@@ -594,92 +691,15 @@ int d2fe_quad_track_enable(d2fe_quad_pipe p, const d2fe_track_params* tp_in) {
   if (p->flow) return ctx_fail(D2FE_ERR_INVALID, "sp_lk excludes the flow landmarks: the reference runs one of the two branches (d2featuretracker.cpp:556-614)");
   if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_track_enable comes before the first submit");
   HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
-  const int Q = p->Q, K = p->K, capT = tp.total_feature_num + 1;
-  const size_t T = (size_t)capT, D = (size_t)p->D, NI = (size_t)p->NI, NJ = 8 * (size_t)Q;
-  const size_t lw = d2fe_lk_carry_list_bytes(capT, p->D) / sizeof(float);
-  const size_t pyr_total = d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, tp.levels) / 2;
-  if (!lw || !pyr_total) return ctx_fail(D2FE_ERR_INVALID, "bad list or pyramid geometry");
-  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
-  size_t o = p->d2h_words;
-  const size_t o_list = o; o += NI * lw;
-  const size_t o_nbxy = o; o += up64(NI * T * 2);
-  const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
-  const size_t o_lmn = o; o += up64(NI);
-  const size_t o_lmq = o; o += up64(NI * T);
-  const size_t o_lmt = o; o += up64(NI * T);
-  const size_t o_lmd = o; o += up64(NI * T);
-  const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap);
-  size_t t = 0;
-  const size_t t_jdesc = t; t += up64(NJ * T * D);
-  const size_t t_jpts = t; t += up64(NJ * T * 2);
-  const size_t t_jmap = t; t += up64(NJ * T);
-  const size_t t_jn = t; t += up64(NJ);
-  const size_t tscr_words = t;
-  // everything new first; the pipe changes only when all of it is there
-  struct Fresh {
-    float* d_all = nullptr; float* d_trk = nullptr; uint8_t* d_pyr = nullptr; MatchPairDesc* d_lpairs = nullptr; int32_t* d_lms = nullptr;
-    std::vector<float*> pin; std::vector<hipEvent_t> ev; bool keep = false;
-    ~Fresh() {
-      if (keep) return;
-      for (void* q : {(void*)d_all, (void*)d_trk, (void*)d_pyr, (void*)d_lpairs, (void*)d_lms}) if (q) (void)hipFree(q);
-      for (float* q : pin) if (q) (void)hipHostFree(q);
-      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-  } f;
-  const size_t all_words = 64 + (size_t)K * 2 * blk_words, trk_words = 4 * lw + 64 + (size_t)K * tscr_words;
-  const size_t pyr_bytes = (4 + (size_t)K * NI) * pyr_total, lms_lane = match_scratch_bytes(4 * Q, capT);
-  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
-  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // no keypoints, empty lists, every arrival counter zero
-  HIP_TRY(hipMalloc(&f.d_trk, sizeof(float) * trk_words));
-  HIP_TRY(hipMemset(f.d_trk, 0, sizeof(float) * trk_words));        // the four empty lists in front of the first quad frame, next_id = 0
-  HIP_TRY(hipMalloc(&f.d_pyr, pyr_bytes));
-  HIP_TRY(hipMemset(f.d_pyr, 0, pyr_bytes));
-  HIP_TRY(hipMalloc(&f.d_lpairs, sizeof(MatchPairDesc) * (size_t)K * 4 * Q));
-  HIP_TRY(hipMalloc(&f.d_lms, lms_lane * K));
-  HIP_TRY(hipMemset(f.d_lms, 0, lms_lane * K));
-  f.pin.assign((size_t)2 * K, nullptr); f.ev.assign((size_t)K, nullptr);
-  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
-  for (int k = 0; k < K; ++k) HIP_TRY(hipEventCreateWithFlags(&f.ev[k], hipEventDisableTiming));
-  {
-    std::vector<MatchPairDesc> lt((size_t)K * 4 * Q);
-    for (int k = 0; k < K; ++k) {
-      float* X = f.d_trk + 4 * lw + 64 + (size_t)k * tscr_words;
-      for (int j = 0; j < 4 * Q; ++j) {
-        MatchPairDesc& d = lt[(size_t)k * 4 * Q + j];
-        const size_t ja = 2 * (size_t)j, jb = ja + 1;
-        d.a = X + t_jdesc + ja * T * D; d.b = X + t_jdesc + jb * T * D;
-        d.pts_a = X + t_jpts + ja * T * 2; d.pts_b = X + t_jpts + jb * T * 2;
-        d.na = reinterpret_cast<int32_t*>(X + t_jn) + ja; d.nb = reinterpret_cast<int32_t*>(X + t_jn) + jb;
-        d.radius = p->cfg.radius_neighbour;
-      }
-    }
-    HIP_TRY(hipMemcpy(f.d_lpairs, lt.data(), sizeof(MatchPairDesc) * lt.size(), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipDeviceSynchronize());        // the memsets ran on the null stream, which the lanes' streams do not wait for
-  // ---- commit: nothing has been submitted, so no stream holds an address of the old blocks
-  f.keep = true;
-  (void)hipFree(p->d_all);
-  p->d_all = f.d_all; p->d_trk = f.d_trk; p->d_trk_pyr = f.d_pyr; p->d_lpairs = f.d_lpairs; p->d_lmatch_scratch = f.d_lms; p->lmatch_scratch_lane = lms_lane;
-  for (int k = 0; k < K; ++k) {
-    auto& L = p->lanes[k];
-    for (int set = 0; set < 2; ++set) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = f.pin[(size_t)2 * k + set]; }
-    L.ev_chain = f.ev[k];
-  }
-  p->tp = tp; p->capT = capT; p->list_words = lw; p->pyr_total = pyr_total;
-  p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst; p->o_lmn = o_lmn; p->o_lmq = o_lmq; p->o_lmt = o_lmt; p->o_lmd = o_lmd;
-  p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
-  p->t_jdesc = t_jdesc; p->t_jpts = t_jpts; p->t_jmap = t_jmap; p->t_jn = t_jn; p->tscr_words = tscr_words;
+  const int capT = tp.total_feature_num + 1;
+  QuadListMode m{capT, d2fe_lk_carry_list_bytes(capT, p->D) / sizeof(float), d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, tp.levels) / 2, true, 0};
+  if (!m.list_words || !m.pyr_total) return ctx_fail(D2FE_ERR_INVALID, "bad list or pyramid geometry");
+  const int rc = quad_lists_enable(p, m);
+  if (rc != D2FE_OK && !p->failed) return rc;      // nothing has changed
+  p->tp = tp;
   p->trk = true;
   p->trk_split = d2fe_dev_env("D2FE_QUAD_TRACK_SPLIT", 0) != 0;
-  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
-    std::vector<MatchPairDesc> tab;
-    quad_fill_pairs(p, tab);
-    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
-      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
-    }
-  }
-  return D2FE_OK;
+  return rc;
 }
 
 int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_track_result* out) {
@@ -718,65 +738,16 @@ int d2fe_quad_flow_enable(d2fe_quad_pipe p, const d2fe_flow_params* fp_in) {
   if (p->trk) return ctx_fail(D2FE_ERR_INVALID, "the flow landmarks exclude sp_lk: the reference runs one of the two branches (d2featuretracker.cpp:556-614)");
   if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_flow_enable comes before the first submit");
   HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
-  const int Q = p->Q, K = p->K, capF = fp.track.total_feature_num > 1 ? fp.track.total_feature_num : 1;
-  const size_t T = (size_t)capF, NI = (size_t)p->NI;
-  const size_t lw = d2fe_lk_flow_list_bytes(capF) / sizeof(float);
-  const size_t pyr_total = d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, fp.track.levels) / 2;
-  const size_t scr = d2fe_lk_flow_scratch_bytes(p->W, p->H, capF, fp.fast_cols, fp.fast_rows);
-  if (!lw || !pyr_total || !scr) return ctx_fail(D2FE_ERR_INVALID, "bad list, pyramid or detector geometry");
-  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
-  size_t o = p->d2h_words;
-  const size_t o_list = o; o += NI * lw;
-  const size_t o_nbxy = o; o += up64(NI * T * 2);
-  const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
-  const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap);
-  // everything new first; the pipe changes only when all of it is there
-  struct Fresh {
-    float* d_all = nullptr; float* d_trk = nullptr; uint8_t* d_pyr = nullptr; uint8_t* d_scr = nullptr;
-    std::vector<float*> pin; std::vector<hipEvent_t> ev; bool keep = false;
-    ~Fresh() {
-      if (keep) return;
-      for (void* q : {(void*)d_all, (void*)d_trk, (void*)d_pyr, (void*)d_scr}) if (q) (void)hipFree(q);
-      for (float* q : pin) if (q) (void)hipHostFree(q);
-      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-  } f;
-  const size_t all_words = 64 + (size_t)K * 2 * blk_words, trk_words = 4 * lw + 64;
-  const size_t pyr_bytes = (4 + (size_t)K * NI) * pyr_total;
-  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
-  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // no keypoints, empty lists, every arrival counter zero
-  HIP_TRY(hipMalloc(&f.d_trk, sizeof(float) * trk_words));
-  HIP_TRY(hipMemset(f.d_trk, 0, sizeof(float) * trk_words));        // the four empty lists in front of the first quad frame, next_id = 0
-  HIP_TRY(hipMalloc(&f.d_pyr, pyr_bytes));
-  HIP_TRY(hipMemset(f.d_pyr, 0, pyr_bytes));
-  HIP_TRY(hipMalloc(&f.d_scr, 4 * scr));                             // its content between steps does not matter
-  f.pin.assign((size_t)2 * K, nullptr); f.ev.assign((size_t)K, nullptr);
-  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
-  for (int k = 0; k < K; ++k) HIP_TRY(hipEventCreateWithFlags(&f.ev[k], hipEventDisableTiming));
-  HIP_TRY(hipDeviceSynchronize());        // the memsets ran on the null stream, which the lanes' streams do not wait for
-  // ---- commit: nothing has been submitted, so no stream holds an address of the old blocks
-  f.keep = true;
-  (void)hipFree(p->d_all);
-  p->d_all = f.d_all; p->d_trk = f.d_trk; p->d_trk_pyr = f.d_pyr; p->d_flow_scratch = f.d_scr; p->flow_scratch_stride = scr;
-  for (int k = 0; k < K; ++k) {
-    auto& L = p->lanes[k];
-    for (int set = 0; set < 2; ++set) { (void)hipHostFree(L.pin_out[set]); L.pin_out[set] = f.pin[(size_t)2 * k + set]; }
-    L.ev_chain = f.ev[k];
-  }
-  p->fp = fp; p->capT = capF; p->list_words = lw; p->pyr_total = pyr_total; p->tscr_words = 0;
-  p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst;
-  p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
+  const int capF = flow_cap_tracks(fp.track);
+  QuadListMode m{capF, d2fe_lk_flow_list_bytes(capF) / sizeof(float), d2fe_lk_stereo_workspace_bytes(1, p->W, p->H, fp.track.levels) / 2, false,
+                 d2fe_lk_flow_scratch_bytes(p->W, p->H, capF, fp.fast_cols, fp.fast_rows)};
+  if (!m.list_words || !m.pyr_total || !m.fast_scratch) return ctx_fail(D2FE_ERR_INVALID, "bad list, pyramid or detector geometry");
+  const int rc = quad_lists_enable(p, m);
+  if (rc != D2FE_OK && !p->failed) return rc;      // nothing has changed
+  p->fp = fp;
   p->flow = true;
   p->flow_split = d2fe_dev_env("D2FE_QUAD_FLOW_SPLIT", 0) != 0;
-  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
-    std::vector<MatchPairDesc> tab;
-    quad_fill_pairs(p, tab);
-    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
-      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
-    }
-  }
-  return D2FE_OK;
+  return rc;
 }
 
 int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_result* out) {
@@ -791,14 +762,8 @@ int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_r
   const auto& L = p->lanes[k];
   if (L.synced < ticket) return ctx_fail(D2FE_ERR_NOT_READY, "d2fe_quad_pipe_wait has not returned this ticket yet");
   const float* B = L.pin_out[set];
-  const float* list = B + p->o_list;
-  const int32_t* hdr = reinterpret_cast<const int32_t*>(list);
-  out->quads = p->Q; out->cap_tracks = p->capT; out->list_words = (int32_t)p->list_words;
-  out->n = hdr; out->n_tracked_in = hdr + 1; out->n_lost = hdr + 2; out->n_removed_near = hdr + 3; out->n_new = hdr + 4;
-  out->lack = hdr + 7; out->num = hdr + 8; out->n_cand = hdr + 9;
-  out->pts_xy = list + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_PTS);
-  out->id = hdr + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_ID);
-  out->src = hdr + d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_SRC);
+  out->quads = p->Q;
+  flow_list_view(out, B + p->o_list, p->capT, p->list_words);
   out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
   return D2FE_OK;
 }

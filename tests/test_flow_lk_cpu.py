@@ -251,12 +251,19 @@ def test_the_step_neither_synchronises_nor_allocates_and_shares_its_kernels():
     assert det.count("hipLaunchKernelGGL") == 1 and det.count("fast_device_launch(") == 1
     assert "D2FE_PROF_LK" in step and "D2FE_PROF_LK" in det and launch.count("D2FE_PROF_LK") == 3
     # one tracker, one detector, one b-c: the unit defines no second copy of what it shares
-    for name in ("void lk_calc(", "int lk_bidir(", "int fast_strength(", "void fast_region_kernel(", "void fast_nonmax_kernel(", "bool nearer(", "int list_reduce_prune("):
+    for name in ("void lk_calc(", "int lk_bidir(", "int fast_strength(", "void fast_region_kernel(", "void fast_nonmax_kernel(", "bool nearer(", "int list_reduce_prune(",
+                 "bool list_track_and_arrive(", "void quad_hand_out_ids("):
         assert name not in flow, name
         assert sum(open(os.path.join(csrc, f)).read().count(name) for f in os.listdir(csrc)) == 1, name
-    assert "lk_bidir(" in flow and "list_reduce_prune(" in flow and "nearer(" in flow and "fast_region_kernel," in flow and "fast_nonmax_kernel," in flow
+    # the step reaches the tracker through step a of both lists, list_track_and_arrive (lk_list_device.h), whose body holds the lk_bidir( call
+    lst = open(os.path.join(csrc, "lk_list_device.h")).read()
+    assert "list_track_and_arrive(" in _body(flow, "void flow_step_body(") and "lk_bidir(" in _body(lst, "bool list_track_and_arrive(")
+    assert "list_reduce_prune(" in flow and "nearer(" in flow and "fast_region_kernel," in flow and "fast_nonmax_kernel," in flow
+    for word in ("lk_calc(", "tex(", "lk_level("):
+        assert word not in flow and word not in lst, word
     carry = open(os.path.join(csrc, "lk_carry.hip")).read()
     assert "list_reduce_prune(" in carry and '#include "lk_list_device.h"' in carry and '#include "fast_device.h"' in open(os.path.join(csrc, "lk.hip")).read()
+    assert "list_track_and_arrive(" in carry and "quad_hand_out_ids(" in carry and "quad_hand_out_ids(" in flow
     # no selection is left to an option
     for word in ("getenv", "d2fe_dev_env"):
         assert word not in flow, word

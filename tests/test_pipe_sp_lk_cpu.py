@@ -92,8 +92,23 @@ def test_the_chain_neither_synchronises_nor_allocates():
             assert word not in text, word
     assert "D2FE_PROF_LK" in step and "D2FE_PROF_LK" in right
     # the new kernels call the tracker's device functions (lk_device.h, shared with lk.hip), not copies of them
-    kern = carry[carry.index("void lk_carry_step_kernel("):carry.index("void pyr_geometry(")]
-    assert kern.count("lk_bidir(") == 2 and "lk_calc(" not in kern and "tex(" not in kern and "lk_level(" not in kern
+    # -- the list kernels of both units reach the tracker only through lk_bidir / lk_bidir_half: step a of every list is list_track_and_arrive (lk_list_device.h), the one
+    # lk_bidir( of the landmark-list step code; lk_carry.hip keeps one for the left -> right launch and the lk_bidir_half( of the neighbour launch
+    lst = open(os.path.join(csrc, "lk_list_device.h")).read()
+    flow = open(os.path.join(csrc, "lk_flow.hip")).read()
+    for unit in (carry, flow, lst):
+        assert "lk_calc(" not in unit and "tex(" not in unit and "lk_level(" not in unit
+    assert _body(lst, "bool list_track_and_arrive(").count("lk_bidir(") == 1 and lst.count("lk_bidir(") == 1 and "lk_bidir_half(" not in lst
+    assert carry.count("lk_bidir(") == 1 and "lk_bidir(" in _body(carry, "void lk_carry_right_kernel(") and carry.count("lk_bidir_half(") == 1
+    assert "lk_bidir(" not in flow and "lk_bidir_half(" not in flow
+    # the ticket's protocol and the id hand-out exist once, and both units call them
+    for name in ("bool list_track_and_arrive(", "void quad_hand_out_ids("):
+        assert sum(open(os.path.join(csrc, f)).read().count(name) for f in os.listdir(csrc)) == 1 and lst.count(name) == 1, name
+        call = name.split(" ")[1]
+        assert carry.count(call) == 1 and flow.count(call) == 1, name
+    for unit in (carry, flow):
+        assert "__hip_atomic_fetch_add(" not in unit and "hdr + 5" not in unit
+    assert lst.count("__hip_atomic_fetch_add(hdr + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT)") == 1 and lst.count("__hip_atomic_fetch_add(") == 2
     assert '#include "lk_device.h"' in carry and '#include "lk_device.h"' in open(os.path.join(csrc, "lk.hip")).read()
     dev = open(os.path.join(csrc, "lk_device.h")).read()
     assert dev.count("int lk_bidir(") == 1 and _body(dev, "int lk_bidir(").count("lk_calc(") == 2        # forward and reverse, in one place for both kernels

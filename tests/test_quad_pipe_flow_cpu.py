@@ -119,7 +119,10 @@ def test_the_step_and_the_chain_neither_synchronise_nor_allocate():
     pipe = open(os.path.join(csrc, "quad_pipe.hip")).read()
     step = _body(flow, "int d2fe_lk_flow_quad_step_device(")
     fast = _body(flow, "void fast_quad_launch(")
-    nb = _body(carry, "int d2fe_lk_flow_neighbour_device(")
+    # the flow entry point of the neighbour tracks calls the ONE launch function of both list kinds and launches nothing beside
+    entry = _body(carry, "int d2fe_lk_flow_neighbour_device(")
+    assert entry.count("lk_neighbour_launch(") == 1 and "hipLaunchKernelGGL" not in entry
+    nb = _body(carry, "int lk_neighbour_launch(")
     chain = _body(pipe, "int quad_pass(d2fe_quad_pipe_s* p")
     assert step.count("hipLaunchKernelGGL") == 2 and step.count("fast_quad_launch(") == 1 and fast.count("hipLaunchKernelGGL") == 3
     assert step.count("ProfScope") == 2 and fast.count("ProfScope") == 3 and nb.count("hipLaunchKernelGGL") == 1 and "lk_carry_neighbour_kernel" in nb
@@ -130,7 +133,11 @@ def test_the_step_and_the_chain_neither_synchronise_nor_allocate():
         for word in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize", "hipMalloc", "hipHostMalloc", "hipFree", "hipMemset", "ctx_scratch"):
             assert word not in text, word
     enable = _body(pipe, "int d2fe_quad_flow_enable(")
-    assert "hipMalloc" in enable and "hipMemset" in enable
+    shared = _body(pipe, "int quad_lists_enable(")      # the one enable path of both modes
+    assert enable.count("quad_lists_enable(") == 1 and "hipMalloc" in shared and "hipMemset" in shared
+    assert 'p->flow_split = d2fe_dev_env("D2FE_QUAD_FLOW_SPLIT", 0) != 0;' in enable
+    # the quad-level ticket and the id hand-out: lk_list_device.h's, called once with the flow header's word
+    assert flow.count("quad_hand_out_ids(") == 1 and "quad_hand_out_ids(cur0, q.list_stride, FLOW_HDR_QUAD," in _body(flow, "void lk_flow_quad_merge_kernel(")
     # the quad-level ticket is a word the flow header documents as "rest 0": behind lack / num / n_cand (7-9)
     assert re.search(r"constexpr int FLOW_HDR_QUAD = (\d+);", flow).group(1) == "10"
     hdr = open(os.path.join(ROOT, "include", "d2fe.h")).read()

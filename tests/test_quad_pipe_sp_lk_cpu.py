@@ -110,7 +110,11 @@ def test_the_launches_and_the_chain_neither_synchronise_nor_allocate():
     carry = open(os.path.join(csrc, "lk_carry.hip")).read()
     pipe = open(os.path.join(csrc, "quad_pipe.hip")).read()
     step = _body(carry, "int d2fe_lk_carry_quad_step_device(")
-    nb = _body(carry, "int d2fe_lk_carry_neighbour_device(")
+    # the neighbour launch of both list kinds is ONE internal function, which each entry point calls once and launches nothing beside
+    nb = _body(carry, "int lk_neighbour_launch(")
+    for entry in ("int d2fe_lk_carry_neighbour_device(", "int d2fe_lk_flow_neighbour_device("):
+        assert _body(carry, entry).count("lk_neighbour_launch(") == 1 and "hipLaunchKernelGGL" not in _body(carry, entry), entry
+    assert carry.count("lk_neighbour_launch(") == 3
     chain = _body(pipe, "int quad_pass(d2fe_quad_pipe_s* p")
     assert "lk_carry_quad_step_kernel" in step and "lk_carry_neighbour_kernel" in nb
     assert step.count("hipLaunchKernelGGL") == 1 and nb.count("hipLaunchKernelGGL") == 1
@@ -127,10 +131,21 @@ def test_the_launches_and_the_chain_neither_synchronise_nor_allocate():
     # the kernels call the tracker's device functions of lk_device.h: the half-image form exists once, next to lk_bidir, with a forward and a reverse lk_calc
     dev = open(os.path.join(csrc, "lk_device.h")).read()
     assert dev.count("int lk_bidir_half(") == 1 and _body(dev, "int lk_bidir_half(").count("lk_calc(") == 2
-    kern = carry[carry.index("void lk_carry_quad_step_kernel("):carry.index("hipStream_t ctx_stream(d2fe_handle h);")]
-    assert kern.count("lk_bidir(") == 1 and kern.count("lk_bidir_half(") == 1 and "lk_calc(" not in kern and "tex(" not in kern
+    # the quad step kernel is the single kernel's body on the camera's view plus the id hand-out: step a (the one lk_bidir( of the list steps) is list_track_and_arrive
+    # in lk_list_device.h; the neighbour kernel holds the unit's one lk_bidir_half(
+    lst = open(os.path.join(csrc, "lk_list_device.h")).read()
+    quad = _body(carry, "void lk_carry_quad_step_kernel(")
+    assert "carry_step_body<true>(" in quad and quad.count("quad_hand_out_ids(") == 1 and "carry_step_body<false>(" in _body(carry, "void lk_carry_step_kernel(")
+    assert _body(carry, "bool carry_step_body(").count("list_track_and_arrive(") == 1 and _body(lst, "bool list_track_and_arrive(").count("lk_bidir(") == 1
+    kern = carry[carry.index("bool carry_step_body("):carry.index("hipStream_t ctx_stream(d2fe_handle h);")]
+    assert kern.count("lk_bidir(") == 1 and kern.count("lk_bidir_half(") == 1 and "lk_bidir_half(" in _body(carry, "void lk_carry_neighbour_kernel(")
+    for unit in (kern, lst):
+        assert "lk_calc(" not in unit and "tex(" not in unit and "lk_level(" not in unit
+    # allocation and zeroing: in the one enable path of both modes, which d2fe_quad_track_enable calls
     enable = _body(pipe, "int d2fe_quad_track_enable(")
-    assert "hipMalloc" in enable and "hipMemset" in enable
+    shared = _body(pipe, "int quad_lists_enable(")
+    assert enable.count("quad_lists_enable(") == 1 and "hipMalloc" in shared and "hipMemset" in shared and pipe.count("quad_lists_enable(") == 3
+    assert 'p->trk_split = d2fe_dev_env("D2FE_QUAD_TRACK_SPLIT", 0) != 0;' in enable
 
 
 def _fake_tracker(seed):
