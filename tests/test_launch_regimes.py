@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from d2slam_amd.synth import synth_descriptor_pair, synth_stereo
+from tests.helpers.match_ref import match_batch as _match_batch      # ONE d2fe_match_batch_device launch of a list of pairs (shared with tests/test_match_edges.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -410,32 +411,6 @@ def test_wino_layer_past_the_claim_threshold(api, orc, cin, cout, pool):
 
 def _unit(x):
     return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
-
-
-def _match_batch(api, fe, pairs, dim, cap, mode=0, ratio=0.8, radius=-1.0, pts=None):
-    """pairs: [(a, b)] -> [(q, t, dist)] through ONE d2fe_match_batch_device launch (pool form); pts: [(pa, pb)] for the radius gate"""
-    import torch
-    dev = torch.device("cuda", 0)
-    npairs = len(pairs)
-    pool = np.zeros((2 * npairs, cap, dim), np.float32); cnts = np.zeros(2 * npairs, np.int32)
-    ppool = np.zeros((2 * npairs, cap, 2), np.float32)
-    for p, (a, b) in enumerate(pairs):
-        pool[2 * p, :len(a)] = a; pool[2 * p + 1, :len(b)] = b; cnts[2 * p] = len(a); cnts[2 * p + 1] = len(b)
-        if pts is not None:
-            ppool[2 * p, :len(a)] = pts[p][0]; ppool[2 * p + 1, :len(b)] = pts[p][1]
-    d_pool = torch.from_numpy(pool).to(dev); d_cnt = torch.from_numpy(cnts).to(dev); d_pts = torch.from_numpy(ppool).to(dev)
-    a_off = torch.arange(0, 2 * npairs, 2, dtype=torch.int32, device=dev) * cap
-    b_off = a_off + cap
-    a_cnt = d_cnt[0::2].contiguous(); b_cnt = d_cnt[1::2].contiguous()
-    q = torch.zeros((npairs, cap), dtype=torch.int32, device=dev); t = torch.zeros_like(q)
-    d = torch.zeros((npairs, cap), dtype=torch.float32, device=dev); n = torch.zeros(npairs, dtype=torch.int32, device=dev)
-    fe.match_batch_device(d_pool.data_ptr(), d_pool.data_ptr(), a_off.data_ptr(), b_off.data_ptr(), a_cnt.data_ptr(), b_cnt.data_ptr(), npairs, dim, cap,
-                          q.data_ptr(), t.data_ptr(), d.data_ptr(), n.data_ptr(), mode=mode, ratio=ratio, radius=radius,
-                          d_pts_a=d_pts.data_ptr() if pts is not None else None, d_pts_b=d_pts.data_ptr() if pts is not None else None,
-                          stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    q, t, d, n = q.cpu().numpy(), t.cpu().numpy(), d.cpu().numpy(), n.cpu().numpy()
-    return [(q[p, :n[p]], t[p, :n[p]], d[p, :n[p]]) for p in range(npairs)]
 
 
 def _match_handle(api):
