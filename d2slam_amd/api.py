@@ -26,6 +26,7 @@ if os.environ.get("D2FE_LIB"):      # developer knob: same-box A/B of two builds
 
 POSTPROC_B, POSTPROC_A = 0, 1
 PREC_F32, PREC_F16X2, PREC_F32_WINO, PREC_F16 = 0, 1, 2, 3
+PREC_I8 = 5      # int8 operands, int32 accumulation (4 is unassigned); needs FrontEnd.set_int8_ranges after load_superpoint
 ERR_TRUNCATED = -4            # d2fe_status: output capacity too small, n_out holds what was written
 KEEP_ALL_CAP = 1024           # host-pointer staging capacity of a keep-all handle (max_keypoints = -1)
 PROF_STAGES = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPaDa",
@@ -242,7 +243,7 @@ _lib = None
 _dev_lib = None
 
 EXPORTS = [
-    "d2fe_last_error", "d2fe_version", "d2fe_default_config", "d2fe_create", "d2fe_destroy", "d2fe_load_superpoint", "d2fe_set_superpoint_pca",
+    "d2fe_last_error", "d2fe_version", "d2fe_default_config", "d2fe_create", "d2fe_destroy", "d2fe_load_superpoint", "d2fe_set_superpoint_pca", "d2fe_set_superpoint_int8_ranges",
     "d2fe_desc_dim", "d2fe_superpoint_extract", "d2fe_superpoint_extract_batch", "d2fe_superpoint_extract_device", "d2fe_extract_all",
     "d2fe_extract_all_batch", "d2fe_tail_stream", "d2fe_superpoint_wait_tail", "d2fe_load_netvlad", "d2fe_set_netvlad_pca", "d2fe_netvlad_dim",
     "d2fe_netvlad", "d2fe_netvlad_batch", "d2fe_netvlad_device", "d2fe_match_knn", "d2fe_match_crosscheck", "d2fe_match_batch_device",
@@ -281,7 +282,7 @@ DEBUG_EXPORTS = [
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
     "d2fe_debug_netvlad_plan", "d2fe_debug_netvlad_shapes", "d2fe_debug_netvlad_features", "d2fe_debug_netvlad_groups", "d2fe_debug_netvlad_slots", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
     "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a",
-    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a", "d2fe_debug_conv_layer", "d2fe_debug_conv1a"]
+    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a", "d2fe_debug_conv_layer", "d2fe_debug_conv_layer_q", "d2fe_debug_conv1a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -347,6 +348,7 @@ def _open_library(path, dev):
             lib.d2fe_debug_desc_head_sparse.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
             lib.d2fe_debug_sample_a.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, ci, vp, vp, ci, vp]
             lib.d2fe_debug_conv_layer.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            lib.d2fe_debug_conv_layer_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float]
             lib.d2fe_debug_conv1a.argtypes = [vp, ci, vp, ci, C.c_longlong, C.c_longlong, ci, ci, ci, vp, vp, vp, C.c_longlong]
         lib.d2fe_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
@@ -401,6 +403,7 @@ def _open_library(path, dev):
         lib.d2fe_netvlad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.d2fe_set_superpoint_pca.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         lib.d2fe_desc_dim.argtypes = [C.c_void_p]
+        lib.d2fe_set_superpoint_int8_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         lib.d2fe_profile_enable.argtypes = [C.c_void_p, C.c_int]
         lib.d2fe_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.d2fe_prepare_gray.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -681,6 +684,15 @@ class FrontEnd:
             return
         comp = np.ascontiguousarray(comp, np.float32); mean = np.ascontiguousarray(mean, np.float32)
         _check(self._lib.d2fe_set_superpoint_pca(self._h, _ptr(comp), _ptr(mean), comp.shape[0]))
+
+    def set_int8_ranges(self, ranges):
+        """PREC_I8 handles, after load_superpoint: the dynamic range of every layer's OUTPUT tensor -- a {layer name: range} dict or 12 numbers in SP_LAYERS
+        order (calibrate.measure_ranges gives the dict).  The entries of convPb and convDb are ignored (a dict may leave them out).  A later load_superpoint clears
+        the ranges; refused while pipes of the handle are alive."""
+        if isinstance(ranges, dict):
+            ranges = [ranges.get(name, 1.0) if name in ("convPb", "convDb") else ranges[name] for name in SP_LAYERS]
+        r = np.ascontiguousarray(ranges, np.float32)
+        _check(self._lib.d2fe_set_superpoint_int8_ranges(self._h, _ptr(r), int(r.size)))
 
     @property
     def desc_dim(self):
@@ -1150,8 +1162,8 @@ class DevFrontEnd(FrontEnd):
     # ---- one layer of the direct SuperPoint conv kernels on injected tensors (include/d2fe_debug.h; tests/test_conv_layer_edges.py) ----
     def debug_conv_layer(self, family, precision, shape, weight, bias, n, H, W, out, out_cstride, out_coff, out_img_stride, x=None, in_cstride=0, in_coff=0,
                          in_img_stride=0, pool=False, relu=True, conv64_tile=1, ncu=0, frames=None, img_stride=0, img_istride=0, w1a=None, b1a=None,
-                         status=False):
-        """d2fe_debug_conv_layer.  x: the WHOLE input buffer (any shape, fp32), out: the WHOLE pre-filled output buffer -- a copy comes back with what the
+                         status=False, in_range=None):
+        """d2fe_debug_conv_layer (in_range given: d2fe_debug_conv_layer_q, see debug_conv_layer_q).  x: the WHOLE input buffer (any shape, fp32), out: the WHOLE pre-filled output buffer -- a copy comes back with what the
         kernels wrote and the caller's values everywhere else.  weight [cout, cin, k, k], bias [cout]; shape 4 (CONV1B_FUSED) takes frames (u8, whole buffer) with
         w1a [64, 1, 3, 3] and b1a [64] instead of x.  Raises D2FEError (code -1 refused, -5 family 3: the launcher does not take the tensors); status=True returns (code, out) instead."""
         weight = np.ascontiguousarray(weight, np.float32); bias = np.ascontiguousarray(bias, np.float32)
@@ -1166,11 +1178,20 @@ class DevFrontEnd(FrontEnd):
         p = _DebugConv(int(family), int(precision), int(shape), int(conv64_tile), int(bool(pool)), int(bool(relu)), int(n), int(H), int(W), weight.shape[0],
                        int(in_cstride), int(in_coff), int(out_cstride), int(out_coff), int(img_stride), int(ncu), int(in_img_stride),
                        0 if x is None else x.size, int(out_img_stride), out.size, int(img_istride), 0 if frames is None else frames.size)
-        rc = int(self._lib.d2fe_debug_conv_layer(self._h, C.byref(p), _ptr(weight), _ptr(bias), _ptr(x), _ptr(out), _ptr(frames), _ptr(w1a), _ptr(b1a)))
+        if in_range is None:
+            rc = int(self._lib.d2fe_debug_conv_layer(self._h, C.byref(p), _ptr(weight), _ptr(bias), _ptr(x), _ptr(out), _ptr(frames), _ptr(w1a), _ptr(b1a)))
+        else:
+            rc = int(self._lib.d2fe_debug_conv_layer_q(self._h, C.byref(p), _ptr(weight), _ptr(bias), _ptr(x), _ptr(out), _ptr(frames), _ptr(w1a), _ptr(b1a),
+                                                       float(in_range)))
         if status:
             return rc, out
         _check(rc)
         return out
+
+    def debug_conv_layer_q(self, family, precision, shape, weight, bias, n, H, W, out, out_cstride, out_coff, out_img_stride, in_range, **kw):
+        """d2fe_debug_conv_layer_q: debug_conv_layer with the dynamic range of the layer's INPUT tensor -- the only entry that takes precision PREC_I8 (one-tile
+        kernels: family 0 or 1).  For shape 4 in_range is the range of conv1a's output."""
+        return self.debug_conv_layer(family, precision, shape, weight, bias, n, H, W, out, out_cstride, out_coff, out_img_stride, in_range=in_range, **kw)
 
     def debug_conv1a(self, kernel, frames, img_stride, img_istride, n, H, W, w1a, b1a, out):
         """d2fe_debug_conv1a: kernel 0 conv1a_mfma_kernel, 1 conv1a_kernel, -1 launch_conv1a's pick.  frames: the whole u8 buffer; out: the whole pre-filled

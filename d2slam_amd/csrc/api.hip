@@ -115,12 +115,12 @@ static int create_context(const d2fe_config* cfg_in, d2fe_handle* out, bool lane
   // variant A up to 1024.  A sorted top-K selection takes K <= 16384 (one workgroup's in-LDS bitonic sort); the reference's TensorRT
   // profile (1500 x 1500, superpoint_tensorrt.cpp:50-55) with max_keypoints in the thousands is inside that.
   if ((cfg->max_keypoints < 1 && cfg->max_keypoints != -1) || cfg->max_keypoints > 16384) return fail(D2FE_ERR_INVALID, "max_keypoints must be -1 (keep all) or in 1..16384");
-  if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO && cfg->precision != D2FE_PREC_F16) return fail(D2FE_ERR_INVALID, "bad precision");
+  if (cfg->precision != D2FE_PREC_F32 && cfg->precision != D2FE_PREC_F16X2 && cfg->precision != D2FE_PREC_F32_WINO && cfg->precision != D2FE_PREC_F16 && cfg->precision != D2FE_PREC_I8) return fail(D2FE_ERR_INVALID, "bad precision");
   if (cfg->postproc != D2FE_POSTPROC_B && cfg->postproc != D2FE_POSTPROC_A) return fail(D2FE_ERR_INVALID, "bad postproc");
   if (cfg->variant_b_pca != 0 && cfg->variant_b_pca != 1) return fail(D2FE_ERR_INVALID, "variant_b_pca must be 0 or 1");
   if (cfg->variant_b_pca && cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "variant_b_pca is an option of post-processing variant B (variant A applies the PCA without it)");
   if (cfg->exact_order) {
-    if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2 and D2FE_PREC_F16 are not supported)");
+    if (cfg->precision != D2FE_PREC_F32_WINO) return fail(D2FE_ERR_INVALID, "exact_order is an option of D2FE_PREC_F32_WINO (D2FE_PREC_F32 is exact already; D2FE_PREC_F16X2, D2FE_PREC_F16 and D2FE_PREC_I8 are not supported)");
     if (cfg->postproc != D2FE_POSTPROC_B) return fail(D2FE_ERR_INVALID, "exact_order needs post-processing variant B (NMS2 of variant A depends on the order in another way)");
     if (cfg->max_keypoints < 1) return fail(D2FE_ERR_INVALID, "exact_order needs max_keypoints >= 1 (keep-all handles are not supported)");
     if (!(cfg->exact_order_eps >= 0.f) || std::isinf(cfg->exact_order_eps)) return fail(D2FE_ERR_INVALID, "exact_order_eps must be finite and >= 0 (0 = the default)");

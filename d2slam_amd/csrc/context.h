@@ -36,6 +36,10 @@ struct Layer {
   void* wpack = nullptr;
   float* bias = nullptr;
   int cout = 0, cout_pad = 0, cin = 0, ks = 0;
+  // D2FE_PREC_I8: s_w[c] of the int8 pack (host, from the load); d_c = s_x * s_w[c] on the device and r of the input tensor, both from d2fe_set_superpoint_int8_ranges
+  std::vector<float> s_w;
+  float* dscale = nullptr;
+  float qr = 0.f;
 };
 
 // The one owner of a set of device buffers: hands out a pointer, remembers it and frees everything when it goes (SpNet, SpRun; a debug hook's buffers, whichever
@@ -71,6 +75,7 @@ struct DevPool {
 // while pipes are alive); owns its device memory
 struct SpNet {
   bool sp_loaded = false;
+  bool i8_ranges = false;      // D2FE_PREC_I8: d2fe_set_superpoint_int8_ranges has run since the last load
   float* w1a = nullptr;  // [9][64]
   float* b1a = nullptr;
   Layer L[L_COUNT];
@@ -292,6 +297,9 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
                    float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s, hipStream_t s_tail = nullptr, int bs = 0);
 int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_out, hipStream_t s);
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap);
+// why the handle's SuperPoint cannot run yet (weights not loaded; D2FE_PREC_I8: calibration ranges not set), nullptr when it can: D2FE_ERR_NOT_READY of every
+// extract call and pipe create
+const char* sp_not_ready(const d2fe_context* h);
 int desc_dim_of(const d2fe_context* h);      // floats per descriptor row: 256, or pca_dims where a PCA is set (d2fe_desc_dim)
 int nv_check(d2fe_context* h, int n, int W, int H, int stride);
 // a second context on the same device that SHARES the parent's networks (SpNet, NvNet: packed weights, PCA matrices) and owns its own

@@ -253,6 +253,7 @@ hipError_t launch_conv_tile(ConvShape shape, int precision, int conv64_tile, boo
                             hipStream_t s) {
   if (precision == 1) return launch_conv_f16x2(shape, conv64_tile, pool, relu, cout_pad, a, s);
   if (precision == 3) return launch_conv_f16(shape, conv64_tile, pool, relu, cout_pad, a, s);
+  if (precision == 5) return launch_conv_i8(shape, conv64_tile, pool, relu, cout_pad, a, s);
   if (precision != 0) return hipErrorInvalidValue;
   switch (shape) {
     case CONV_64_T8x32:
@@ -268,7 +269,7 @@ hipError_t launch_conv_tile(ConvShape shape, int precision, int conv64_tile, boo
 
 hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
                        hipStream_t s) {
-  if (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && shape != CONV1B_FUSED)) return launch_conv_pc(shape, precision, pool, relu, cout_pad, a, s);
+  if (precision != 5 && (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && shape != CONV1B_FUSED))) return launch_conv_pc(shape, precision, pool, relu, cout_pad, a, s);
   return launch_conv_tile(shape, precision, tune_conv64(), pool, relu, cout_pad, a, s);
 }
 

@@ -470,25 +470,33 @@ bool conv_compiled(int family, int shape, bool pool, bool relu) {
   }
   return false;
 }
-}  // namespace
+// D2FE_PREC_I8 has the one-tile kernels alone (conv_i8.hip: launch_i8 compiles the pool only with ReLU)
+bool conv_compiled_i8(int family, int shape, bool pool, bool relu) {
+  if (family != 1) return false;
+  if (shape == CONV1B_FUSED) return pool && relu;
+  return !pool || (relu && (shape == CONV_64_T8x32 || shape == CONV_128_T4x32));
+}
 
-int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out, const uint8_t* frames,
-                          const float* w1a, const float* b1a) {
+// quantised: d2fe_debug_conv_layer_q (precision 5 is accepted only there, with the input tensor's range)
+int conv_layer_hook(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out, const uint8_t* frames,
+                    const float* w1a, const float* b1a, bool quantised, float in_range) {
   if (!h || !p || !weight || !bias || !out) return fail(D2FE_ERR_INVALID, "null argument");
-  if (p->family < 0 || p->family > 3 || (p->precision != 0 && p->precision != 1 && p->precision != 3) || p->shape < 0 || p->shape > CONV1B_FUSED)
+  const bool i8 = quantised && p->precision == 5;
+  if (p->family < 0 || p->family > 3 || (p->precision != 0 && p->precision != 1 && p->precision != 3 && !i8) || p->shape < 0 || p->shape > CONV1B_FUSED)
     return fail(D2FE_ERR_INVALID, "family, precision or shape");
+  if (i8 && !(in_range >= 1e-30f && in_range <= 1e30f)) return fail(D2FE_ERR_INVALID, "in_range must be finite and in [1e-30, 1e30]");
   const bool pool = p->pool != 0, relu = p->relu != 0, fused = p->shape == CONV1B_FUSED;
   // family 0 = what conv() of superpoint_host.hip does in this process: convPb's own kernel first (fp32 modes, D2FE_CONV1X1), then launch_conv, which
   // takes the persistent or the one-tile kernels by D2FE_CONV_PC and the Cin-64 tile by D2FE_CONV64_TILE
   int family = p->family, conv64_tile = p->conv64_tile;
   if (family == 0) {
-    family = (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && !fused)) ? 2 : 1;
+    family = (!i8 && (tune_conv_pc() == 1 || (tune_conv_pc() == 2 && !fused))) ? 2 : 1;
     conv64_tile = tune_conv64();
   }
   const bool try_1x1 = p->family == 0 && p->precision == 0 && p->shape == CONV_256_1x1_T4x16 && p->cout == 65 && !pool && !relu && d2fe_dev_env("D2FE_CONV1X1", 1);
   if (p->family == 3) {
     if (p->precision != 0 || p->shape != CONV_256_1x1_T4x16 || pool || relu) return fail(D2FE_ERR_INVALID, "family 3 is the fp32 1x1 layer without pool and ReLU");
-  } else if (!conv_compiled(family, p->shape, pool, relu)) {
+  } else if (i8 ? !conv_compiled_i8(family, p->shape, pool, relu) : !conv_compiled(family, p->shape, pool, relu)) {
     return fail(D2FE_ERR_INVALID, "no kernel of this family is compiled for the shape with this pool / relu");
   }
   if (family == 1 && conv64_tile != 0 && conv64_tile != 1) return fail(D2FE_ERR_INVALID, "conv64_tile is 0 or 1");
@@ -526,12 +534,20 @@ int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* 
   // weights and bias as pack_layer of superpoint_host.hip prepares them
   std::vector<float> pf, bp(cout_pad, 0.f), t1a;
   std::vector<uint16_t> ph;
+  std::vector<int8_t> pq;
+  std::vector<float> dsc;      // D2FE_PREC_I8: d_c = s_x * s_w[c], as d2fe_set_superpoint_int8_ranges computes it
   memcpy(bp.data(), bias, sizeof(float) * cout);
-  if (p->precision == 0) { pf.resize(packed_weight_floats_f32(cout_pad, g.cin, g.ks)); pack_weights_f32(weight, cout, g.cin, g.ks, cout_pad, pf.data()); }
+  if (i8) {
+    pq.resize(packed_weight_bytes_i8(cout_pad, g.cin, g.ks)); dsc.resize(cout_pad);
+    pack_weights_i8(weight, cout, g.cin, g.ks, cout_pad, pq.data(), dsc.data());
+    const float s_x = in_range / 127.0f;
+    for (float& d : dsc) d = s_x * d;
+  }
+  else if (p->precision == 0) { pf.resize(packed_weight_floats_f32(cout_pad, g.cin, g.ks)); pack_weights_f32(weight, cout, g.cin, g.ks, cout_pad, pf.data()); }
   else if (p->precision == 1) { ph.resize(packed_weight_halfs_f16x2(cout_pad, g.cin, g.ks)); pack_weights_f16x2(weight, cout, g.cin, g.ks, cout_pad, ph.data()); }
   else { ph.resize(packed_weight_halfs_f16(cout_pad, g.cin, g.ks)); pack_weights_f16(weight, cout, g.cin, g.ks, cout_pad, ph.data()); }
   DevPool b;
-  float *d_in = nullptr, *d_out = nullptr, *d_b = nullptr, *d_w1a = nullptr, *d_b1a = nullptr, *d_zero = nullptr;
+  float *d_in = nullptr, *d_out = nullptr, *d_b = nullptr, *d_w1a = nullptr, *d_b1a = nullptr, *d_zero = nullptr, *d_dsc = nullptr;
   void* d_w = nullptr;
   uint8_t* d_img = nullptr;
   if (fused) {
@@ -545,7 +561,8 @@ int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* 
     HIP_TRY(b.get(&d_in, sizeof(float) * p->in_floats, in));
   }
   HIP_TRY(b.get(&d_out, sizeof(float) * p->out_floats, out));      // the caller's pre-filled buffer: what no kernel writes comes back as it went in
-  if (p->precision == 0) HIP_TRY(b.get(&d_w, sizeof(float) * pf.size(), pf.data()));
+  if (i8) { HIP_TRY(b.get(&d_w, pq.size(), pq.data())); HIP_TRY(b.get(&d_dsc, sizeof(float) * dsc.size(), dsc.data())); }
+  else if (p->precision == 0) HIP_TRY(b.get(&d_w, sizeof(float) * pf.size(), pf.data()));
   else HIP_TRY(b.get(&d_w, sizeof(uint16_t) * ph.size(), ph.data()));
   HIP_TRY(b.get(&d_b, sizeof(float) * bp.size(), bp.data()));
   HIP_TRY(b.get(&d_zero, sizeof(float) * 256, nullptr, 0));
@@ -556,6 +573,7 @@ int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* 
   a.in_img_stride = (long)p->in_img_stride; a.out_img_stride = (long)p->out_img_stride;
   a.img = d_img; a.img_stride = p->img_stride; a.img_istride = (long)p->img_istride; a.w1a = d_w1a; a.b1a = d_b1a;
   a.zeros = d_zero; a.ncu = ncu; a.tag = 0; a.ablate = 0;
+  if (i8) { a.qr = 127.0f / in_range; a.dscale = d_dsc; }
   const ConvShape shape = (ConvShape)p->shape;
   hipError_t e = hipErrorNotSupported;
   if (p->family == 3 || try_1x1) e = launch_conv1x1_256_65(a, h->stream);
@@ -571,6 +589,17 @@ int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* 
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, d_out, sizeof(float) * p->out_floats, hipMemcpyDeviceToHost));
   return D2FE_OK;
+}
+}  // namespace
+
+int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out, const uint8_t* frames,
+                          const float* w1a, const float* b1a) {
+  return conv_layer_hook(h, p, weight, bias, in, out, frames, w1a, b1a, false, 0.f);
+}
+
+int d2fe_debug_conv_layer_q(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out, const uint8_t* frames,
+                            const float* w1a, const float* b1a, float in_range) {
+  return conv_layer_hook(h, p, weight, bias, in, out, frames, w1a, b1a, true, in_range);
 }
 
 int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,

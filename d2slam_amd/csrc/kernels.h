@@ -55,6 +55,9 @@ struct ConvArgs {
   int ablate;               // development library only (D2FE_ABL): 1 skip patch loads, 2 skip B reloads, 4 skip stores; always 0 in the product library
   int* work_ctr = nullptr;  // Winograd kernels: zeroed device counter -> work items are claimed dynamically (null: static round-robin split)
   int ncu = 0;              // compute units of the handle's device (d2fe_create reads it once): the persistent kernels size their grids on it
+  // D2FE_PREC_I8 (conv_i8.hip): r = fl32(127 / T) of the layer's input tensor, and d_c = fl32(s_x * s_w[c]) per output channel, padded like the bias
+  float qr = 0.f;
+  const float* dscale = nullptr;
 };
 
 enum ConvShape {
@@ -65,7 +68,8 @@ enum ConvShape {
   CONV1B_FUSED,         // conv1a (1->64, from the u8 frame) fused into conv1b's patch staging, + ReLU + 2x2 pool
 };
 
-// precision (d2fe_precision): 0 = fp32 exact MFMA, 1 = fp16 hi/lo split MFMA, 3 = plain fp16 operands (the Winograd mode, 2, has launchers of its own below)
+// precision (d2fe_precision): 0 = fp32 exact MFMA, 1 = fp16 hi/lo split MFMA, 3 = plain fp16 operands, 5 = int8 operands (the Winograd mode, 2, has launchers
+// of its own below).  Precision 5 has one-tile kernels only: D2FE_CONV_PC has no effect on it
 hipError_t launch_conv(ConvShape shape, int precision, bool pool, bool relu, int cout_pad, const ConvArgs& a,
                        hipStream_t s);
 // the part of launch_conv behind D2FE_CONV_PC: the one-tile-per-workgroup kernels (conv.hip, conv_f16.hip).  conv64_tile: 1 = the 4x32 tile for CONV_64_T8x32
@@ -99,6 +103,10 @@ size_t packed_weight_halfs_f16x2(int cout_pad, int cin, int ks);
 void pack_weights_f16x2(const float* w, int cout, int cin, int ks, int cout_pad, uint16_t* dst);
 size_t packed_weight_halfs_f16(int cout_pad, int cin, int ks);      // D2FE_PREC_F16: the hi halves alone
 void pack_weights_f16(const float* w, int cout, int cin, int ks, int cout_pad, uint16_t* dst);
+// D2FE_PREC_I8: per-output-channel symmetric int8 weights in fragment order, and s_w [cout_pad] (1 for an all-zero or a padding channel)
+hipError_t launch_conv_i8(ConvShape shape, int conv64_tile, bool pool, bool relu, int cout_pad, const ConvArgs& a, hipStream_t s);
+size_t packed_weight_bytes_i8(int cout_pad, int cin, int ks);
+void pack_weights_i8(const float* w, int cout, int cin, int ks, int cout_pad, int8_t* dst, float* s_w);
 
 // ---- post-processing ------------------------------------------------------------------------------
 // softmax(65) -> drop dustbin -> 8x8 unfold; writes dense semi (optional) and appends variant-B candidates

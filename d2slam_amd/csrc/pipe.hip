@@ -636,7 +636,7 @@ int d2fe_pipe_create_camera(d2fe_handle h, const d2fe_pipe_config* cfg, const d2
   if (cfg->struct_size != (int32_t)sizeof(d2fe_pipe_config)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_config size mismatch");
   if (cam && cam->struct_size != (int32_t)sizeof(d2fe_pipe_camera)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_camera size mismatch");
   const int mono = cam ? cam->mono : 0, depth = cam ? cam->depth : 0;
-  if (!h->sp_net->sp_loaded) return pipe_fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
+  if (const char* why = sp_not_ready(h)) return pipe_fail(D2FE_ERR_NOT_READY, why);
   if (cfg->netvlad && !h->nv_net) return pipe_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
   if (cfg->lanes < 1 || cfg->lanes > 16 || cfg->frames < 1 || cfg->frames > 4096) return pipe_fail(D2FE_ERR_INVALID, "lanes must be 1..16, frames >= 1");
   const int C = cfg->coalesce > 0 ? cfg->coalesce : 1;

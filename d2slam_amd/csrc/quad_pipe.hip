@@ -499,7 +499,7 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
   if (!h || !cfg || !maps || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(d2fe_quad_pipe_config)) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_pipe_config size mismatch");
-  if (!h->sp_net->sp_loaded) return ctx_fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
+  if (const char* why = sp_not_ready(h)) return ctx_fail(D2FE_ERR_NOT_READY, why);
   if (cfg->netvlad && !h->nv_net) return ctx_fail(D2FE_ERR_NOT_READY, "netvlad weights not loaded");
   if (cfg->lanes < 1 || cfg->lanes > 16 || cfg->quads < 1) return ctx_fail(D2FE_ERR_INVALID, "lanes must be 1..16, quads >= 1");
   if (4L * cfg->quads > h->cfg.max_batch) return ctx_fail(D2FE_ERR_INVALID, "4 * quads views exceed the handle's max_batch");

@@ -38,6 +38,17 @@ int pack_layer(SpNet& net, int prec, int li, const d2fe_conv_params* l) {
   L.cout = cout; L.cout_pad = cout_pad; L.cin = cin; L.ks = ks;
   net.pool.give_back(L.wpack); L.wpack = nullptr;
   net.pool.give_back(L.bias); L.bias = nullptr;
+  net.pool.give_back(L.dscale); L.dscale = nullptr;
+  L.s_w.clear(); L.qr = 0.f;
+  if (prec == D2FE_PREC_I8 && !K.f32) {      // int8 fragments and s_w; d_c and r follow with the calibration ranges (d2fe_set_superpoint_int8_ranges)
+    std::vector<int8_t> pq(packed_weight_bytes_i8(cout_pad, cin, ks));
+    L.s_w.resize(cout_pad);
+    pack_weights_i8(w.data(), cout, cin, ks, cout_pad, pq.data(), L.s_w.data());
+    HIP_TRY(net.pool.get(&L.wpack, pq.size(), pq.data()));
+    HIP_TRY(net.pool.get(&L.bias, b.size() * sizeof(float), b.data()));
+    HIP_TRY(net.pool.get(&L.dscale, b.size() * sizeof(float), nullptr, 0));
+    return D2FE_OK;
+  }
   std::vector<float> pf;        // the fragments: fp32 words, or halves
   std::vector<uint16_t> ph;
   if (prec == D2FE_PREC_F32_WINO && ks == 3 && cin >= 64 && !K.f32) {
@@ -78,9 +89,10 @@ hipError_t conv(const Pass& p, ConvShape shape, const Layer& L, const float* in,
   a.img = p.img; a.img_stride = p.img_stride; a.img_istride = p.img_istride; a.w1a = net.w1a; a.b1a = net.b1a;
   a.H = hh; a.W = ww; a.n_img = p.n; a.in_img_stride = iis; a.out_img_stride = ois; a.zeros = run.zeros; a.ncu = p.h->ncu;
   a.tag = (&L == &net.L[L_1B]) ? 1 : 0;
+  a.qr = L.qr; a.dscale = L.dscale;
   a.work_ctr = (p.prec == D2FE_PREC_F32_WINO && run.wino_dynamic) ? run.work_ctrs + (int)(&L - &net.L[0]) : nullptr;
   { static const int ab = d2fe_dev_env("D2FE_ABLATE", 0); a.ablate = p.crops ? 0 : ab; }
-  if (p.prec != D2FE_PREC_F16X2 && p.prec != D2FE_PREC_F16 && shape == CONV_256_1x1_T4x16 && L.cout == 65 && !pool && !relu) {      // convPb: same bits either way
+  if (p.prec != D2FE_PREC_F16X2 && p.prec != D2FE_PREC_F16 && p.prec != D2FE_PREC_I8 && shape == CONV_256_1x1_T4x16 && L.cout == 65 && !pool && !relu) {      // convPb: same bits either way
     static const int on = d2fe_dev_env("D2FE_CONV1X1", 1);
     if (on || p.crops) { const hipError_t e = launch_conv1x1_256_65(a, p.s); if (e != hipErrorNotSupported) return e; }
   }
@@ -167,6 +179,8 @@ int SpRun::alloc(const d2fe_config& cfg) {
   // fp16-operand mode: the dense head would evaluate convDa | convDb with fp16 operands, the sparse head evaluates them as exact fp32 chains -- a frame's
   // descriptors must not depend on how many images travel with it, so every call takes the sparse head (1 image: 0.03 ms more per call, the figures above)
   if (cfg.precision == D2FE_PREC_F16) sp_min_batch = 1;
+  // int8-operand mode: the same reasoning (the dense head would quantise convDa | convDb)
+  if (cfg.precision == D2FE_PREC_I8) sp_min_batch = 1;
   sp_min_batch = d2fe_dev_env("D2FE_SPARSE_MIN_BATCH", sp_min_batch);
   if (sparse_desc) {
     sp_slots = 4 * (cfg.max_keypoints < 0 || cfg.max_keypoints > 1024 ? 1024 : cfg.max_keypoints);   // <= 4 corner cells per keypoint; larger calls take the dense head
@@ -311,9 +325,15 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
 // with d2fe_config.variant_b_pca: d2fe_set_superpoint_pca refuses every other handle)
 int desc_dim_of(const d2fe_context* h) { return h->sp_net->pca_dims ? h->sp_net->pca_dims : 256; }
 
+const char* sp_not_ready(const d2fe_context* h) {
+  if (!h->sp_net->sp_loaded) return "superpoint weights not loaded";
+  if (h->cfg.precision == D2FE_PREC_I8 && !h->sp_net->i8_ranges) return "D2FE_PREC_I8: the calibration ranges are not set (d2fe_set_superpoint_int8_ranges)";
+  return nullptr;
+}
+
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap) {
   if (!h) return fail(D2FE_ERR_INVALID, "null handle");
-  if (!h->sp_net->sp_loaded) return fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
+  if (const char* why = sp_not_ready(h)) return fail(D2FE_ERR_NOT_READY, why);
   if (n < 1 || n > h->cfg.max_batch) return fail(D2FE_ERR_INVALID, "batch size out of range");
   if (W < 16 || H < 16 || W > h->cfg.max_width || H > h->cfg.max_height || (long)W * H > (long)h->cfg.max_width * h->cfg.max_height)
     return fail(D2FE_ERR_INVALID, "image size must be at least 16x16 and within the configured maximum");
@@ -346,6 +366,7 @@ int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
   }
   SpNet& net = *h->sp_net;
   net.sp_loaded = false;
+  net.i8_ranges = false;
   // conv1a: [64][1][3][3] -> [9][64]
   {
     std::vector<float> t(9 * 64);
@@ -362,6 +383,38 @@ int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* w) {
     if (rc) return rc;
   }
   net.sp_loaded = true;
+  return D2FE_OK;
+}
+
+int d2fe_set_superpoint_int8_ranges(d2fe_handle h, const float* range, int n) {
+  if (h && h->life.pipes() > 0) return fail(D2FE_ERR_INVALID, "the handle has live pipes whose lanes read its packed weights: destroy them before setting the int8 ranges");
+  if (h) graphs_clear(h);
+  if (!h || !range) return fail(D2FE_ERR_INVALID, "null argument");
+  if (h->cfg.precision != D2FE_PREC_I8) return fail(D2FE_ERR_INVALID, "int8 ranges belong to a D2FE_PREC_I8 handle");
+  if (n != SP_NLAYERS) return fail(D2FE_ERR_INVALID, "n must be D2FE_SP_NUM_LAYERS");
+  SpNet& net = *h->sp_net;
+  if (!net.sp_loaded) return fail(D2FE_ERR_NOT_READY, "superpoint weights not loaded");
+  // the tensor a plan layer reads: the chain's predecessor; convPb reads convPa, convDa conv4b (as convPa does), convDb convDa
+  auto input_of = [](int layer) { return layer == SP_PB ? SP_PA : layer == SP_DA ? SP_4B : layer == SP_DB ? SP_DA : layer - 1; };
+  for (int i = 0; i < SP_NLAYERS; ++i) {
+    if (i == SP_PB || i == SP_DB) continue;      // no quantised layer reads them
+    if (!(range[i] >= 1e-30f && range[i] <= 1e30f)) return fail(D2FE_ERR_INVALID, std::string("int8 range of layer ") + SP_PLAN[i].name + " must be finite and in [1e-30, 1e30]");
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->tail_stream) HIP_TRY(hipStreamSynchronize(h->tail_stream));
+  net.i8_ranges = false;
+  for (int i = 0; i < L_COUNT; ++i) {
+    Layer& L = net.L[i];
+    if (SP_PACK[i].f32 || !L.dscale) continue;
+    const float T = range[input_of(SP_PACK[i].part[0])];
+    const float s_x = T / 127.0f;
+    L.qr = 127.0f / T;
+    std::vector<float> d(L.cout_pad);
+    for (int c = 0; c < L.cout_pad; ++c) d[c] = s_x * L.s_w[c];
+    HIP_TRY(hipMemcpy(L.dscale, d.data(), d.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  net.i8_ranges = true;
   return D2FE_OK;
 }
 

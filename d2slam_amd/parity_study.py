@@ -10,7 +10,10 @@ order_study(): the ORDER-aware comparison (list positions, not sets) of the plai
 the deviation of the Winograd score maps from the direct ones (what exact_order_eps has to bound) and what exact_order re-evaluates.
 
 f16_study(): the fp16-operand mode (PREC_F16) against the exact mode -- sets, matches and list positions (tools/f16_study.py, profiles/f16_study.json).  study() is
-unchanged by it: bench.py's in-run subset compares what it always compared."""
+unchanged by it: bench.py's in-run subset compares what it always compared.
+
+i8_study(): the int8-operand mode (PREC_I8, ranges from calibrate.measure_ranges on the first 64 images) against the exact mode, the same figures, with PREC_F16 beside it
+for scale (tools/i8_study.py, profiles/i8_study.json)."""
 import os
 
 import numpy as np
@@ -96,10 +99,12 @@ def study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
     return rec
 
 
-def _lists_and_matches(api, imgs, pairs, thr, N, prec, batch=32, device_id=0):
-    """(per-image raster-index lists in list order, per-pair sets of (index, index) matches) of one arithmetic mode"""
+def _lists_and_matches(api, imgs, pairs, thr, N, prec, batch=32, device_id=0, ranges=None):
+    """(per-image raster-index lists in list order, per-pair sets of (index, index) matches) of one arithmetic mode; ranges: PREC_I8's calibration ranges"""
     fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=N, input_width=W, input_height=H, max_batch=batch, precision=prec, keypoint_threshold=thr, device_id=device_id))
     fe.load_superpoint(weights_for(thr))
+    if ranges is not None:
+        fe.set_int8_ranges(ranges)
     idx, ds = [], []
     for i0 in range(0, len(imgs), batch):
         for k, s, d in fe.extract_batch(imgs[i0:i0 + batch], cap=N):
@@ -121,6 +126,27 @@ def f16_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
     NI = len(imgs)
     rec = {"threshold": thr, "max_keypoints": N, "images": NI, "images_per_call": batch}
     for name in ("f16", "f16x2", "wino"):
+        for part, lo, hi in (("all", 0, NI), ("synthetic", 0, n_syn), ("real_derived", n_syn, NI)):
+            plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
+            rec["%s_vs_f32_%s" % (name, part)] = compare(as_sets(got["f32"]), as_sets(got[name]), lo, hi, plo, phi)
+        order = compare_order(got["f32"][0], got[name][0])
+        order["images_differing"] = len(order["images_differing"])
+        rec["%s_vs_f32_positions" % name] = order
+    return rec
+
+
+def i8_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0, calib_images=64):
+    """one configuration: the int8-operand mode (PREC_I8) -- and, for scale, the fp16-operand mode -- against the exact mode: keypoint SETS and match sets (compare)
+    and list POSITIONS (compare_order).  The ranges are the MinMax ranges of the first `calib_images` images.  Figures to report, not bounds: an 8-bit network on
+    seeded random weights moves far more near-ties than fp16's 11 bits do."""
+    from d2slam_amd import calibrate
+    ranges = calibrate.measure_ranges(weights_for(thr), imgs[:calib_images])
+    modes = {"f32": (api.PREC_F32, None), "i8": (api.PREC_I8, ranges), "f16": (api.PREC_F16, None)}
+    got = {name: _lists_and_matches(api, imgs, pairs, thr, N, prec, batch, device_id, r) for name, (prec, r) in modes.items()}
+    as_sets = lambda g: ([set(a.tolist()) for a in g[0]], g[1])
+    NI = len(imgs)
+    rec = {"threshold": thr, "max_keypoints": N, "images": NI, "images_per_call": batch, "calibration_images": min(calib_images, NI), "ranges": ranges}
+    for name in ("i8", "f16"):
         for part, lo, hi in (("all", 0, NI), ("synthetic", 0, n_syn), ("real_derived", n_syn, NI)):
             plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
             rec["%s_vs_f32_%s" % (name, part)] = compare(as_sets(got["f32"]), as_sets(got[name]), lo, hi, plo, phi)

@@ -91,6 +91,36 @@ typedef enum {
                             Not available with exact_order. */
 } d2fe_precision;
 
+/* One more value of d2fe_config.precision (an int32_t), declared beside d2fe_precision in an enumeration of its own: the four enumerators above are pinned as
+ * the whole of d2fe_precision.  4 is unassigned and refused. */
+typedef enum {
+  D2FE_PREC_I8 = 5       /* int8 OPERANDS, int32 accumulation (v_mfma_i32_32x32x32_i8): the precision of the reference's real-time configuration
+                            (cnn_enable_tensorrt_int8, d435_multi_rt.yaml:119-122).  Activations between the layers stay fp32 NHWC in memory.  The
+                            quantised layers are the ones D2FE_PREC_F16 evaluates with fp16 operands (conv1b .. conv4b, convPa, and convPa | convDa in
+                            the dense head, the 1x1 heads convPb and -- dense head only -- convDb).  With T the dynamic range of the layer's INPUT tensor
+                            (d2fe_set_superpoint_int8_ranges) and c the output channel:
+                              r        = fl32(127 / T)                                   host, once
+                              s_x      = fl32(T / 127)                                   host, once
+                              amax_c   = max |w[c, :, :, :]|                             host, at load
+                              q_w      = clamp(rint((double)w * 127.0 / (double)amax_c), -127, 127)     round half to even, once at load;
+                                                                                         amax_c == 0: q_w = 0 and s_w[c] = 1
+                              s_w[c]   = fl32(amax_c / 127)
+                              d_c      = fl32(s_x * s_w[c])                              fp32 product, host
+                              q_x      = (int8) rintf(fminf(fmaxf(x * r, -127.f), 127.f))  fp32 product, round half to even; +inf -> 127; the zero
+                                                                                         padding is q = 0; never -128
+                              acc      = sum over (ky, kx, ci) of q_x * q_w              int32, EXACT and independent of the summation order;
+                                                                                         |acc| <= 1152 * 127^2 < 2^31
+                              y        = fl32(fl32((float)acc * d_c) + bias[c])          TWO roundings, not a fused multiply-add; (float)acc rounds to
+                                                                                         nearest even; then ReLU and the 2x2 max-pool as in every mode
+                            A layer therefore has exactly one correct answer, and tests/helpers/i8_oracle.py restates it in numpy bit for bit.  NaN
+                            activations are outside the contract.  What D2FE_PREC_F16 keeps in fp32 stays fp32: conv1a (fused into conv1b's staging,
+                            bit-equal to the exact mode, quantised with conv1b's r on its way into LDS), the sparse descriptor head, softmax, selection,
+                            sampling and the PCA tail.  As with D2FE_PREC_F16, handles of this mode take the sparse descriptor head for every call
+                            (exceptions: dense_descriptors handles, and capacities beyond 4 x min(max_keypoints, 1024) cells), so a frame's bits do not
+                            depend on entry point, batch or pipe.  Until the ranges are set every extract call and pipe create answers
+                            D2FE_ERR_NOT_READY.  Not available with exact_order. */
+} d2fe_precision_i8;
+
 /* Mirrors SuperPointConfig (d2frontend/include/d2frontend/CNN/superpoint_tensorrt.h:17-33) plus the
  * SuperPointONNX ctor arguments (superpoint_onnx.h:17-21) and the device/batch geometry. */
 typedef struct {
@@ -177,6 +207,14 @@ D2FE_API int d2fe_load_superpoint(d2fe_handle h, const d2fe_superpoint_weights* 
  * d2fe_desc_dim() returns the per-keypoint descriptor length of extract calls (256 or pca_dims).  Refused while pipes are alive. */
 D2FE_API int d2fe_set_superpoint_pca(d2fe_handle h, const float* comp, const float* mean, int pca_dims);
 D2FE_API int d2fe_desc_dim(d2fe_handle h);
+
+/* D2FE_PREC_I8: the calibration ranges (per-tensor thresholds, what a calibration table holds).  n = D2FE_SP_NUM_LAYERS; range[i] is the dynamic range of
+ * the OUTPUT tensor of layer i in the order of d2fe_superpoint_weights (conv1a .. convDb).  A quantised layer uses the range of the tensor it reads: convPa
+ * and convDa both read conv4b's; the entries of convPb and convDb are ignored.  Every used entry must be finite and lie in [1e-30, 1e30] (r and s_x are
+ * then finite normal fp32), else D2FE_ERR_INVALID naming the layer.  Valid only on a D2FE_PREC_I8 handle (else D2FE_ERR_INVALID), after
+ * d2fe_load_superpoint (else D2FE_ERR_NOT_READY); a later d2fe_load_superpoint clears the ranges.  A load: refused while pipes are alive.
+ * d2slam_amd/calibrate.py measures the ranges ("MinMax") offline. */
+D2FE_API int d2fe_set_superpoint_int8_ranges(d2fe_handle h, const float* range, int n);
 
 /* Extractor.  Replaces: bool SuperPoint::infer(const cv::Mat&, std::vector<cv::Point2f>&, std::vector<float>&
  * descriptors, std::vector<float>& scores) (superpoint_tensorrt.h:47-48, .cpp:161-183), called from

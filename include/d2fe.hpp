@@ -87,6 +87,8 @@ struct SuperPointConfig {
   bool fast_mode = false;                // D2FE_PREC_F16X2 instead of the bit-exact fp32 mode
   bool winograd = false;                 // D2FE_PREC_F32_WINO: fp32, 3x3 layers as Winograd F(2x2,3x3) (1.76x the direct mode's throughput)
   bool fp16_operands = false;            // D2FE_PREC_F16: fp16 operands, fp32 accumulation (the reference engine's kFP16 operand precision); wins over the two above
+  bool int8_operands = false;            // D2FE_PREC_I8: int8 operands, int32 accumulation (the reference's cnn_enable_tensorrt_int8); wins over the three above.  infer()
+                                         // answers false until setInt8Ranges has run
   bool exact_order = false;              // winograd only, max_keypoints >= 1: the keypoint list (count, indices, order) equals the exact mode's (d2fe_config::exact_order)
   float exact_order_eps = 0.f;           // 0: the library default
   int32_t exact_order_crops = 0;         // crop slots per call; 0: max_batch
@@ -109,7 +111,7 @@ class SuperPoint {
     c.max_width = cfg_.input_width; c.max_height = cfg_.input_height; c.max_batch = cfg_.max_batch;
     c.max_keypoints = cfg_.max_keypoints; c.remove_borders = cfg_.remove_borders; c.keypoint_threshold = cfg_.keypoint_threshold;
     c.postproc = D2FE_POSTPROC_B;
-    c.precision = cfg_.fp16_operands ? D2FE_PREC_F16 : cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
+    c.precision = cfg_.int8_operands ? (int32_t)D2FE_PREC_I8 : cfg_.fp16_operands ? D2FE_PREC_F16 : cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
     c.exact_order = cfg_.exact_order ? 1 : 0; c.exact_order_eps = cfg_.exact_order_eps; c.exact_order_crops = cfg_.exact_order_crops;
     c.variant_b_pca = cfg_.descriptor_pca ? 1 : 0;
     if (d2fe_create(&c, &h_) != D2FE_OK) { report("d2fe_create"); h_ = nullptr; return false; }
@@ -148,6 +150,12 @@ class SuperPoint {
   // row-major, mean [256], pca_dims 4..256 in multiples of 4 (0: off).  After build(), before any pipe is created; needs SuperPointConfig::descriptor_pca
   bool setDescriptorPCA(const float* comp, const float* mean, int pca_dims) {
     if (!h_ || d2fe_set_superpoint_pca(h_, comp, mean, pca_dims) != D2FE_OK) { report("d2fe_set_superpoint_pca"); return false; }
+    return true;
+  }
+  // D2FE_PREC_I8 (SuperPointConfig::int8_operands): the calibration table's per-tensor thresholds, range[i] = dynamic range of the OUTPUT of layer i in the
+  // order of d2fe_superpoint_weights (convPb's and convDb's entries are ignored).  After build(), before any pipe is created
+  bool setInt8Ranges(const float (&range)[D2FE_SP_NUM_LAYERS]) {
+    if (!h_ || d2fe_set_superpoint_int8_ranges(h_, range, D2FE_SP_NUM_LAYERS) != D2FE_OK) { report("d2fe_set_superpoint_int8_ranges"); return false; }
     return true;
   }
   int descriptorDim() const { return h_ ? d2fe_desc_dim(h_) : 256; }

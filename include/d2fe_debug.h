@@ -134,6 +134,12 @@ typedef struct d2fe_debug_conv {
 } d2fe_debug_conv;
 D2FE_API int d2fe_debug_conv_layer(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out,
                                    const uint8_t* frames, const float* w1a, const float* b1a);
+/* d2fe_debug_conv_layer with the dynamic range of the INPUT tensor added (finite, in [1e-30, 1e30]): the only entry point that accepts precision 5
+ * (D2FE_PREC_I8, csrc/conv_i8.hip), for tests/test_i8_layer_edges.py.  The hook packs the int8 weights, s_w and d_c = s_x * s_w[c] as d2fe_load_superpoint and
+ * d2fe_set_superpoint_int8_ranges do.  The mode has one-tile kernels only: family 0 and 1 launch them, family 2 and 3 are refused; the pool is compiled with
+ * ReLU alone.  For the shape-4 layer in_range is the range of conv1a's output.  Every other precision behaves as in d2fe_debug_conv_layer (in_range unused). */
+D2FE_API int d2fe_debug_conv_layer_q(d2fe_handle h, const d2fe_debug_conv* p, const float* weight, const float* bias, const float* in, float* out,
+                                     const uint8_t* frames, const float* w1a, const float* b1a, float in_range);
 /* The stand-alone conv1a (1 -> 64, 3x3, ReLU) on injected frames: kernel 0 conv1a_mfma_kernel, 1 conv1a_kernel, -1 launch_conv1a's own pick (D2FE_CONV1A_VALU).
  * frames as above; out is the caller's whole pre-filled buffer of out_floats >= n * H * W * 64 floats, uploaded first and downloaded whole. */
 D2FE_API int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,
