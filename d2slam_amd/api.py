@@ -144,6 +144,23 @@ class _PipeDepthResult(C.Structure):
                 ("track_depth_mm", C.c_void_p)]
 
 
+class _Camera(C.Structure):
+    """d2fe_camera: kind (CAM_PINHOLE / CAM_MEI) and its nine doubles (camera_pinhole / camera_mei)"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 9)]
+
+
+class _PipeBearings(C.Structure):
+    """d2fe_pipe_bearings: the bearings mode of a stereo / mono pipe (d2fe_pipe_bearings_enable)"""
+    _fields_ = [("struct_size", C.c_int32), ("lk_use_pred", C.c_int32), ("cam", _Camera * 2), ("T_right_left", C.c_double * 12), ("distance", C.c_double),
+                ("radius_lk", C.c_double)]
+
+
+class _PipeBearingsResult(C.Structure):
+    _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("cap_tracks", C.c_int32), ("reserved", C.c_int32), ("kp_bearing", C.c_void_p), ("kp_pred_xy", C.c_void_p),
+                ("lk_right_bearing", C.c_void_p), ("lk_pred_ok", C.c_void_p), ("list_bearing", C.c_void_p), ("list_pred_xy", C.c_void_p),
+                ("list_right_bearing", C.c_void_p), ("list_pred_ok", C.c_void_p)]
+
+
 class _PipeDeviceResult(C.Structure):
     _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("desc_dim", C.c_int32), ("netvlad_dim", C.c_int32),
                 ("d_kps_xy", C.c_void_p), ("d_scores", C.c_void_p), ("d_desc", C.c_void_p), ("d_n_kp", C.c_void_p), ("d_netvlad", C.c_void_p)]
@@ -261,6 +278,7 @@ EXPORTS = [
     "d2fe_pipe_set_track_params", "d2fe_pipe_camera_default", "d2fe_pipe_create_camera", "d2fe_pipe_submit_depth", "d2fe_pipe_depth_result_get", "d2fe_depth_at_device", "d2fe_lk_carry_quad_step_device", "d2fe_lk_carry_neighbour_device", "d2fe_quad_track_enable", "d2fe_quad_track_result_get",
     "d2fe_flow_default_params", "d2fe_lk_flow_list_bytes", "d2fe_lk_flow_list_offset", "d2fe_lk_flow_scratch_bytes", "d2fe_detect_fast_device", "d2fe_lk_flow_step_device",
     "d2fe_pipe_flow_enable", "d2fe_pipe_flow_result_get",
+    "d2fe_relative_extrinsic", "d2fe_bearings_device", "d2fe_pipe_bearings_default", "d2fe_pipe_bearings_enable", "d2fe_pipe_bearings_result_get",
     "d2fe_lk_flow_quad_step_device", "d2fe_lk_flow_neighbour_device", "d2fe_quad_flow_enable", "d2fe_quad_flow_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
@@ -486,6 +504,13 @@ def _open_library(path, dev):
         lib.d2fe_pipe_depth_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_depth_at_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p, C.c_void_p]
+        lib.d2fe_relative_extrinsic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_bearings_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_bearings_default.argtypes = [C.c_void_p]
+        lib.d2fe_pipe_bearings_default.restype = None
+        lib.d2fe_pipe_bearings_enable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.d2fe_pipe_bearings_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_device_view.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_device_release.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -1311,12 +1336,17 @@ class StereoPipe(_Owned):
     keeps its [2 F] rows, the right ones with n_kp = 0.  With sp_lk=True the list is carried on the one image and "track_right_pts" / "track_right_status" are None.
     depth=True (needs mono=True): PINHOLE_DEPTH -- submit(left, depth=...) with a uint16 depth frame per gray frame; wait() then also returns "kp_depth_mm"
     [F, cap] uint16 (the value under every keypoint, 0 beyond n_kp) and, with sp_lk, "track_depth_mm" [F, cap_tracks] (None otherwise).
+    bearings=dict(cam_left=..., cam_right=..., T_right_left=..., distance=100.0, lk_use_pred=True, radius_lk=...) (d2fe_pipe_bearings_enable; every pipe shape): unit
+    bearings, extrinsic predictions and the lk_lk_use_pred gate on the device; wait() then also returns "bearing_kp" [2 F, cap, 3] float64, "bearing_kp_pred" [F, cap, 2],
+    "bearing_lk_right" [F, cap, 3] / "bearing_lk_pred_ok" [F, cap] (lr_lk without lists) and "bearing_list" / "bearing_list_pred" / "bearing_list_right" /
+    "bearing_list_pred_ok" over the entries of the list the pipe carries; None for what the pipe's shape does not produce.  With match_lr and radius_lr > 0 the
+    L <-> R radius gate compares the predicted points.
     submit() enqueues and returns a ticket; wait() returns views into the lane's pinned result block (copy what must outlive 2 * lanes submits)."""
     _HANDLE, _DESTROY = "_p", "d2fe_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, lanes=4, frames=1, width=640, height=480, cap=None, netvlad=True, match_lr=True, match_prev=True,
                  ratio=0.8, radius_lr=-1.0, radius_prev=-1.0, pinned_input=False, cu_partition=False, netvlad_inline=None, coalesce=1, lane_cus=0, netvlad_group=1, coalesce_depth=0,
-                 lr_lk=False, sp_lk=False, track_params=None, mono=False, depth=False, flow_lk=False, flow_params=None):
+                 lr_lk=False, sp_lk=False, track_params=None, mono=False, depth=False, flow_lk=False, flow_params=None, bearings=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _PipeConfig()
@@ -1345,6 +1375,8 @@ class StereoPipe(_Owned):
             _check(self._lib.d2fe_pipe_create(fe.handle, C.byref(c), C.byref(self._p)))
         self._flow = False
         self._flow_res = _PipeFlowResult()
+        self._bearings = False
+        self._bear_res = _PipeBearingsResult()
         try:
             if track_params is not None:
                 self.set_track_params(track_params)
@@ -1352,6 +1384,8 @@ class StereoPipe(_Owned):
                 if flow_lk not in (True, "only"):
                     raise ValueError('flow_lk is False, True (beside SuperPoint) or "only" (superpoint = 0)')
                 self.flow_enable(flow_params, superpoint=0 if flow_lk == "only" else 1)
+            if bearings is not None:
+                self.bearings_enable(**bearings)
         except Exception:
             self.close()
             raise
@@ -1509,7 +1543,39 @@ class StereoPipe(_Owned):
             out["kp_depth_mm"] = np.frombuffer((C.c_uint16 * (F * cap)).from_address(d.kp_depth_mm), dtype=np.uint16).reshape(F, cap)
             T = d.cap_tracks
             out["track_depth_mm"] = np.frombuffer((C.c_uint16 * (F * T)).from_address(d.track_depth_mm), dtype=np.uint16).reshape(F, T) if d.track_depth_mm else None
+        if self._bearings:
+            b = self.bearings_result_raw(ticket)
+            T = b.cap_tracks
+
+            def raw(ptr, shape, ct, dt):
+                return np.frombuffer((ct * int(np.prod(shape))).from_address(ptr), dtype=dt).reshape(shape) if ptr else None
+            out["bearing_kp"] = raw(b.kp_bearing, (2 * F, cap, 3), C.c_double, np.float64)
+            out["bearing_kp_pred"] = view(b.kp_pred_xy, (F, cap, 2), np.float32)
+            out["bearing_lk_right"] = raw(b.lk_right_bearing, (F, cap, 3), C.c_double, np.float64)
+            out["bearing_lk_pred_ok"] = raw(b.lk_pred_ok, (F, cap), C.c_uint8, np.uint8)
+            out["bearing_list"] = raw(b.list_bearing, (F, T, 3), C.c_double, np.float64)
+            out["bearing_list_pred"] = view(b.list_pred_xy, (F, T, 2), np.float32)
+            out["bearing_list_right"] = raw(b.list_right_bearing, (F, T, 3), C.c_double, np.float64)
+            out["bearing_list_pred_ok"] = raw(b.list_pred_ok, (F, T), C.c_uint8, np.uint8)
         return out
+
+    def bearings_enable(self, cam_left, cam_right=None, T_right_left=None, distance=100.0, lk_use_pred=True, radius_lk=0.0):
+        """d2fe_pipe_bearings_enable: once, before the first submit.  cam_left / cam_right: camera_pinhole() / camera_mei(); T_right_left: 12 doubles, [3][4] row-major
+        (relative_extrinsic); radius_lk = search_local_max_dist_lr * width.  A mono pipe takes cam_left alone."""
+        b = _PipeBearings()
+        self._lib.d2fe_pipe_bearings_default(C.byref(b))
+        b.cam[0] = cam_left
+        b.cam[1] = cam_right if cam_right is not None else cam_left
+        if T_right_left is not None:
+            b.T_right_left = (C.c_double * 12)(*[float(v) for v in np.asarray(T_right_left, np.float64).reshape(-1)])
+        b.distance, b.lk_use_pred, b.radius_lk = float(distance), int(bool(lk_use_pred)), float(radius_lk)
+        _check(self._lib.d2fe_pipe_bearings_enable(self._p, C.byref(b)))
+        self._bearings = True
+
+    def bearings_result_raw(self, ticket):
+        """d2fe_pipe_bearings_result_get: the bearings of a ticket that wait() has returned (D2FE_ERR_UNSUPPORTED without the mode)"""
+        _check(self._lib.d2fe_pipe_bearings_result_get(self._p, C.c_int64(ticket), C.byref(self._bear_res)))
+        return self._bear_res
 
     def depth_result_raw(self, ticket):
         """d2fe_pipe_depth_result_get: the depth values of a ticket that wait() has returned (depth pipes)"""
@@ -1551,6 +1617,43 @@ def depth_at_device(fe, d_depth, width, height, depth_stride, depth_image_stride
     Asynchronous on `stream` (None: the handle's)."""
     _check(fe._lib.d2fe_depth_at_device(fe.handle, C.c_void_p(d_depth), int(width), int(height), int(depth_stride), int(depth_image_stride), C.c_void_p(d_pts_xy),
                                         int(pts_stride), C.c_void_p(d_n), int(n_lists), int(cap), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+
+CAM_PINHOLE, CAM_MEI = 0, 1
+
+
+def camera_pinhole(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
+    """d2fe_camera of camodocal's PinholeCamera (pinhole + radtan)"""
+    return _Camera(CAM_PINHOLE, 0, (C.c_double * 9)(float(fx), float(fy), float(cx), float(cy), float(k1), float(k2), float(p1), float(p2), 0.0))
+
+
+def camera_mei(cam):
+    """d2fe_camera of camodocal's CataCamera; cam: dict(xi,k1,k2,p1,p2,gamma1,gamma2,u0,v0) or the nine values in that order"""
+    return _Camera(CAM_MEI, 0, FrontEnd._mei(cam))
+
+
+def relative_extrinsic(q_a_wxyz, t_a, q_b_wxyz, t_b):
+    """d2fe_relative_extrinsic (host only): T_b_a [3, 4] = [R_b^T R_a | R_b^T (t_a - t_b)] from two poses (unit quaternion w x y z, translation) in a common frame"""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, np.float64).reshape(-1) for v in (q_a_wxyz, t_a, q_b_wxyz, t_b)]
+    if [len(v) for v in a] != [4, 3, 4, 3]:
+        raise ValueError("relative_extrinsic takes (q[4], t[3], q[4], t[3])")
+    T = np.zeros(12, np.float64)
+    _check(lib.d2fe_relative_extrinsic(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(T)))
+    return T.reshape(3, 4)
+
+
+def bearings_device(fe, cam, d_pts_xy, pts_stride, d_n, n_lists, cap, d_bearing, cam_other=None, T=None, distance=100.0, d_pred_xy=None, d_other_xy=None,
+                    d_other_status=None, radius=0.0, d_other_bearing=None, d_pred_ok=None, stream=None):
+    """d2fe_bearings_device on raw device addresses (ints): n_lists point lists [cap][2] float32 (pts_stride floats apart), counts d_n [n_lists] int32 -> unit bearings
+    d_bearing [n_lists][cap][3] float64.  T (12 host doubles) and d_pred_xy [n_lists][cap][2] float32: the extrinsic prediction.  The four gate arrays (d_other_xy
+    [n_lists][cap][2], d_other_status [n_lists][cap] uint8 -> d_other_bearing [n_lists][cap][3] float64, d_pred_ok [n_lists][cap] uint8) are given together, with cam_other.
+    Asynchronous on `stream` (None: the handle's)."""
+    Tc = None if T is None else (C.c_double * 12)(*[float(v) for v in np.asarray(T, np.float64).reshape(-1)])
+    _check(fe._lib.d2fe_bearings_device(fe.handle, C.byref(cam), None if cam_other is None else C.byref(cam_other), Tc, float(distance), C.c_void_p(d_pts_xy),
+                                        int(pts_stride), C.c_void_p(d_n), int(n_lists), int(cap), C.c_void_p(d_bearing), C.c_void_p(d_pred_xy or 0),
+                                        C.c_void_p(d_other_xy or 0), C.c_void_p(d_other_status or 0), float(radius), C.c_void_p(d_other_bearing or 0),
+                                        C.c_void_p(d_pred_ok or 0), C.c_void_p(stream or 0)))
 
 
 def _pinned_view(ptr, shape, dt):

@@ -349,6 +349,21 @@ struct DepthSeg { const float* pts; size_t pts_stride; const int32_t* n; size_t 
 int depth_gather_launch(d2fe_context* h, const uint16_t* d_depth, int W, int H, size_t depth_stride_px, size_t depth_image_stride_px, int n_lists, const DepthSeg* segs,
                         int n_segs, hipStream_t s);
 
+// bearings.hip: bearings_kernel over up to three segments of point lists in ONE launch (the pipe: the pass's left keypoint rows, its right keypoint rows, its landmark
+// lists).  List l of a segment reads its points at pts + l * pts_stride floats and its count at n[l * n_stride]; it lifts them with camera `cam` (0 / 1 of BearCams) and
+// writes bearing[(l * bearing_step) * cap * 3 ..).  pred != null: the extrinsic prediction, dense [list][cap][2].  pred_ok != null (needs pred): the gate against
+// other[l * other_stride ..) / status[l * status_stride ..), other_bearing (lifted with camera 1) and pred_ok dense.  Slots >= n are written as zero everywhere
+struct BearCam { int kind, distort; double p[9]; double iK11, iK13, iK22, iK23; };
+struct BearCams { BearCam cam[2]; double T[12]; double distance, radius; };
+struct BearSeg {
+  const float* pts; size_t pts_stride; const int32_t* n; size_t n_stride; int cap, cam;
+  double* bearing; size_t bearing_step; float* pred;
+  const float* other; size_t other_stride; const uint8_t* status; size_t status_stride; double* other_bearing; uint8_t* pred_ok;
+};
+const char* bearings_check_camera(const d2fe_camera* c);      // what d2fe_bearings_device refuses in a camera, as a message (nullptr: nothing)
+BearCam bearings_make_camera(const d2fe_camera& c);
+int bearings_launch(d2fe_context* h, const BearCams& cams, int n_lists, const BearSeg* segs, int n_segs, hipStream_t s);
+
 struct ProfScope {
   d2fe_context* h; int stage; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
   ProfScope(d2fe_context* h_, int stage_, hipStream_t s_, bool want = true) : h(h_), stage(stage_), s(s_) {      // want = false: a scope that records nothing

@@ -4,6 +4,7 @@
 //  (f)-3 int8 wire codec of descriptors         (d2common/include/d2common/d2frontend_types.h:228-237,260-268,313-351)
 // All three are HBM/latency-bound byte and float work: coalesced loads, wave reductions, no MFMA.
 #include "kernels.h"
+#include "camera_device.h"      // mei_space_to_plane
 
 namespace d2fe {
 
@@ -62,18 +63,6 @@ hipError_t launch_undistort(const uint8_t* src, int sh, int sw, int sstride, lon
 // One thread per map pixel, fp64 like the reference (camodocal works in double); the maps are born in HBM where
 // undistort_kernel reads them.  cam = xi k1 k2 p1 p2 gamma1 gamma2 u0 v0 (CataCamera, CataCamera.cc:495-515,617-633).
 struct MapArgs { double cam[9]; double q[4]; double f; double iK13, iK23; int width, height, mode; float* mapx; float* mapy; };
-
-__device__ __forceinline__ void mei_space_to_plane(const double* cam, double X, double Y, double Z, double& u, double& v) {
-  const double nrm = __builtin_sqrt(X * X + (Y * Y + Z * Z));
-  const double z = Z + cam[0] * nrm;
-  const double pu0 = X / z, pu1 = Y / z;
-  const double mx2 = pu0 * pu0, my2 = pu1 * pu1, mxy = pu0 * pu1, rho2 = mx2 + my2;
-  const double rad = cam[1] * rho2 + cam[2] * rho2 * rho2;
-  const double d0 = pu0 * rad + 2.0 * cam[3] * mxy + cam[4] * (rho2 + 2.0 * mx2);
-  const double d1 = pu1 * rad + 2.0 * cam[4] * mxy + cam[3] * (rho2 + 2.0 * my2);
-  u = cam[5] * (pu0 + d0) + cam[7];
-  v = cam[6] * (pu1 + d1) + cam[8];
-}
 
 __global__ __launch_bounds__(256) void gen_map_kernel(MapArgs a) {
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -80,6 +80,14 @@ struct d2fe_pipe_s {
   int capF = 0;
   size_t flist_words = 0, o_flist = 0, o_frxy = 0, o_frst = 0, o_fdep = 0;
   void* d_flow_scratch = nullptr;    // the detector's score map and candidate pool: one, the chain serialises the steps
+  // bearings (d2fe_pipe_bearings_enable): doubles [NI][cap][3] for the keypoint rows, the predicted left keypoints floats [F * C][cap][2] (stereo), on an lr_lk pipe without
+  // lists the right tracks' bearings doubles [F * C][cap][3] and their gate bytes [F * C][cap], with a list (capL = capT or capF) the same four arrays over its entries --
+  // all at the end of the region in front of d2h_words
+  bool bear = false;
+  BearCams bcams{};
+  int capL = 0;
+  size_t o_bkb = 0, o_bkp = 0, o_blb = 0, o_blo = 0, o_btb = 0, o_btp = 0, o_btr = 0, o_bto = 0;
+  bool bear_lk_gate() const { return lk && !sp_lk && !flow; }
   float* d_all = nullptr;            // [64 zero words | K lanes x 2 sets x block]
   MatchPairDesc* d_pairs = nullptr;  // [K][2][C variants: submits of the PREVIOUS pass][C * npp]
   int32_t* d_match_scratch = nullptr; size_t match_scratch_lane = 0;   // per lane: tickets + records
@@ -397,6 +405,52 @@ int pipe_flush(d2fe_pipe_s* p) {
     rc = depth_gather_launch(L.ctx, L.d_dep, W, H, (size_t)W, img, n_left, seg, p->sp_lk || p->flow ? 2 : 1, s);
     if (rc) return rc;
   }
+  if (p->bear) {
+    // the bearings of the pass's keypoint rows and list entries, the extrinsic predictions and their gates: ONE launch.  Rows are addressed as the depth launch
+    // addresses them (C > 1 on a left-only pipe: the compact staging rows feed the left segment)
+    const size_t cap = (size_t)p->cap, rstep = p->C > 1 ? 2 : 1;      // result rows between consecutive left images
+    BearSeg seg[3];
+    int ns = 0;
+    BearSeg& kl = seg[ns++];
+    kl = BearSeg{};
+    kl.pts = staged ? B + p->o_skps : B + p->o_kps; kl.pts_stride = staged ? cap * 2 : rstep * cap * 2;
+    kl.n = reinterpret_cast<const int32_t*>(staged ? B + p->o_scnt : B + p->o_cnt); kl.n_stride = staged ? 1 : rstep;
+    kl.cap = p->cap; kl.cam = 0;
+    kl.bearing = reinterpret_cast<double*>(B + p->o_bkb); kl.bearing_step = rstep;
+    if (!p->mono) kl.pred = B + p->o_bkp;
+    if (p->bear_lk_gate()) {
+      kl.other = B + p->o_lkp; kl.other_stride = cap * 2; kl.status = reinterpret_cast<const uint8_t*>(B + p->o_lks); kl.status_stride = cap;
+      kl.other_bearing = reinterpret_cast<double*>(B + p->o_blb); kl.pred_ok = reinterpret_cast<uint8_t*>(B + p->o_blo);
+    }
+    if (!left_only) {      // SuperPoint ran on the right images too: C == 1: rows [F, 2 F); C > 1: rows 2 j + 1
+      BearSeg& kr = seg[ns++];
+      kr = BearSeg{};
+      const size_t r0 = (size_t)p->right_row(0, 0);
+      kr.pts = B + p->o_kps + r0 * cap * 2; kr.pts_stride = rstep * cap * 2;
+      kr.n = reinterpret_cast<const int32_t*>(B + p->o_cnt) + r0; kr.n_stride = rstep;
+      kr.cap = p->cap; kr.cam = 1;
+      kr.bearing = reinterpret_cast<double*>(B + p->o_bkb) + r0 * cap * 3; kr.bearing_step = rstep;
+    }
+    if (p->capL) {
+      BearSeg& tl = seg[ns++];
+      tl = BearSeg{};
+      const size_t T = (size_t)p->capL;
+      const float* lists = B + (p->flow ? p->o_flist : p->o_list);
+      const size_t lw = p->flow ? p->flist_words : p->list_words;
+      tl.pts = lists + (p->flow ? d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_PTS) : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_PTS)); tl.pts_stride = lw;
+      tl.n = reinterpret_cast<const int32_t*>(lists + (p->flow ? 0 : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_HDR))); tl.n_stride = lw;
+      tl.cap = p->capL; tl.cam = 0;
+      tl.bearing = reinterpret_cast<double*>(B + p->o_btb); tl.bearing_step = 1;
+      if (!p->mono) {
+        tl.pred = B + p->o_btp;
+        tl.other = B + (p->flow ? p->o_frxy : p->o_rxy); tl.other_stride = T * 2;
+        tl.status = reinterpret_cast<const uint8_t*>(B + (p->flow ? p->o_frst : p->o_rst)); tl.status_stride = T;
+        tl.other_bearing = reinterpret_cast<double*>(B + p->o_btr); tl.pred_ok = reinterpret_cast<uint8_t*>(B + p->o_bto);
+      }
+    }
+    rc = bearings_launch(L.ctx, p->bcams, n_left, seg, ns, s);
+    if (rc) return rc;
+  }
   if (nv_side) {
     HIP_TRY(hipStreamWaitEvent(L.nv, L.ev_up, 0));
     rc = netvlad(L.nv);
@@ -468,6 +522,24 @@ int pipe_alloc_blocks(d2fe_pipe_s* p) {
     }
     if (p->depth) { p->o_fdep = o; o += up64((NL * p->capF + 1) / 2); }
   }
+  if (p->bear) {      // a double = two words; every array on a 64-word boundary, so the doubles are 8-byte aligned
+    p->capL = p->sp_lk ? p->capT : p->flow ? p->capF : 0;
+    const size_t T = (size_t)p->capL;
+    p->o_bkb = o; o += up64(NI * cap * 6);
+    if (!p->mono) { p->o_bkp = o; o += up64(NL * cap * 2); }
+    if (p->bear_lk_gate()) {
+      p->o_blb = o; o += up64(NL * cap * 6);
+      p->o_blo = o; o += up64((NL * cap + 3) / 4);
+    }
+    if (T) {
+      p->o_btb = o; o += up64(NL * T * 6);
+      if (!p->mono) {
+        p->o_btp = o; o += up64(NL * T * 2);
+        p->o_btr = o; o += up64(NL * T * 6);
+        p->o_bto = o; o += up64((NL * T + 3) / 4);
+      }
+    }
+  }
   p->d2h_words = o;
   p->o_idx = o; o += up64(NI * cap);
   if ((p->lk || p->mono) && C > 1) {
@@ -521,7 +593,12 @@ int pipe_alloc_pairs(d2fe_pipe_s* p) {
             d.radius = radius;
           };
           for (int j = 0; j < C; ++j) {
-            for (int f = 0; cfg->match_lr && f < (int)F; ++f) fill(row[pi++], B, p->left_row(j, f), B, p->right_row(j, f), cfg->radius_lr);
+            for (int f = 0; cfg->match_lr && f < (int)F; ++f) {
+              fill(row[pi], B, p->left_row(j, f), B, p->right_row(j, f), cfg->radius_lr);
+              // bearings: the radius gate of L <-> R compares the left keypoint PREDICTED into the right image (rows [F * C] of o_bkp: submit j, frame f)
+              if (p->bear && cfg->radius_lr > 0) row[pi].pts_a = B + p->o_bkp + (size_t)(C > 1 ? j : f) * cap * 2;
+              ++pi;
+            }
             for (int f = 0; cfg->match_prev && f < (int)F; ++f) {
               if (f > 0) fill(row[pi++], B, p->left_row(j, f), B, p->left_row(j, f - 1), cfg->radius_prev);
               else if (j > 0) fill(row[pi++], B, p->left_row(j, 0), B, p->left_row(j - 1, (int)F - 1), cfg->radius_prev);
@@ -1106,6 +1183,77 @@ int d2fe_pipe_flow_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_flow_result
     out->right_status = reinterpret_cast<const uint8_t*>(B + p->o_frst) + r0 * T;
   }
   if (p->depth) out->depth_mm = reinterpret_cast<const uint16_t*>(B + p->o_fdep) + r0 * T;
+  return D2FE_OK;
+}
+
+void d2fe_pipe_bearings_default(d2fe_pipe_bearings* b) {
+  memset(b, 0, sizeof(*b));
+  b->struct_size = (int32_t)sizeof(d2fe_pipe_bearings);
+  b->lk_use_pred = 1;
+  b->distance = 100.0;
+  b->T_right_left[0] = b->T_right_left[5] = b->T_right_left[10] = 1.0;
+}
+
+int d2fe_pipe_bearings_enable(d2fe_pipe p, const d2fe_pipe_bearings* b) {
+  if (!p || !b) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  if (b->struct_size != (int32_t)sizeof(d2fe_pipe_bearings)) return pipe_fail(D2FE_ERR_INVALID, "d2fe_pipe_bearings size mismatch");
+  if (const char* why = bearings_check_camera(&b->cam[0])) return pipe_fail(D2FE_ERR_INVALID, std::string("cam[0]: ") + why);
+  if (!p->mono) {
+    if (const char* why = bearings_check_camera(&b->cam[1])) return pipe_fail(D2FE_ERR_INVALID, std::string("cam[1]: ") + why);
+    if (!(b->distance - b->distance == 0.0)) return pipe_fail(D2FE_ERR_INVALID, "distance must be finite");
+    for (int i = 0; i < 12; ++i) if (!(b->T_right_left[i] - b->T_right_left[i] == 0.0)) return pipe_fail(D2FE_ERR_INVALID, "T_right_left must be finite");
+    if (b->radius_lk != b->radius_lk) return pipe_fail(D2FE_ERR_INVALID, "radius_lk must not be NaN");
+    if (b->lk_use_pred != 0 && b->lk_use_pred != 1) return pipe_fail(D2FE_ERR_INVALID, "lk_use_pred must be 0 or 1");
+  }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->next_ticket > 0) return pipe_fail(D2FE_ERR_INVALID, "the bearings are switched on before the first submit");
+  if (p->bear) return pipe_fail(D2FE_ERR_INVALID, "the bearings are already switched on");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  p->bear = true;
+  p->bcams = BearCams{};
+  p->bcams.cam[0] = bearings_make_camera(b->cam[0]);
+  p->bcams.cam[1] = bearings_make_camera(p->mono ? b->cam[0] : b->cam[1]);
+  if (!p->mono) {
+    for (int i = 0; i < 12; ++i) p->bcams.T[i] = b->T_right_left[i];
+    p->bcams.distance = b->distance;
+    p->bcams.radius = b->lk_use_pred ? b->radius_lk : 0.0;
+  }
+  // a failure below leaves the pipe without result blocks: final, like a failed submit
+  const int rc = pipe_realloc_blocks(p);
+  if (rc != D2FE_OK) { p->failed = rc; p->failed_msg = d2fe_last_error(); }
+  return rc;
+}
+
+int d2fe_pipe_bearings_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_bearings_result* out) {
+  if (!p || !out) return pipe_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (!p->bear) return pipe_fail(D2FE_ERR_UNSUPPORTED, "d2fe_pipe_bearings_enable was not called on this pipe: it computes no bearings");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return pipe_fail(p->failed, "the pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return pipe_fail(D2FE_ERR_INVALID, "unknown ticket");
+  const auto ti = p->tinfo[(size_t)(ticket % (long long)p->tinfo.size())];
+  if (ticket + (long long)p->tinfo.size() <= p->next_ticket || ti.pass < 0 || ti.pass + 2 * p->K < p->next_pass)
+    return pipe_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the bearings within 2 * lanes passes");
+  if (!ti.waited) return pipe_fail(D2FE_ERR_NOT_READY, "d2fe_pipe_wait has not returned this ticket yet");
+  const int k = (int)(ti.pass % p->K), set = (int)((ti.pass / p->K) & 1);
+  const float* B = p->lanes[k].pin_out[set];
+  const size_t cap = p->cap, T = (size_t)p->capL, r0 = p->C > 1 ? (size_t)ti.j : 0;
+  out->frames = p->F; out->cap = p->cap; out->cap_tracks = p->capL;
+  out->kp_bearing = reinterpret_cast<const double*>(B + p->o_bkb) + (size_t)p->left_row(ti.j, 0) * cap * 3;
+  if (!p->mono) out->kp_pred_xy = B + p->o_bkp + r0 * cap * 2;
+  if (p->bear_lk_gate()) {
+    out->lk_right_bearing = reinterpret_cast<const double*>(B + p->o_blb) + r0 * cap * 3;
+    out->lk_pred_ok = reinterpret_cast<const uint8_t*>(B + p->o_blo) + r0 * cap;
+  }
+  if (T) {
+    out->list_bearing = reinterpret_cast<const double*>(B + p->o_btb) + r0 * T * 3;
+    if (!p->mono) {
+      out->list_pred_xy = B + p->o_btp + r0 * T * 2;
+      out->list_right_bearing = reinterpret_cast<const double*>(B + p->o_btr) + r0 * T * 3;
+      out->list_pred_ok = reinterpret_cast<const uint8_t*>(B + p->o_bto) + r0 * T;
+    }
+  }
   return D2FE_OK;
 }
 

@@ -484,8 +484,9 @@ D2FE_API int d2fe_pipe_lk_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_lk_r
  * (pipe-wide, counted from 0 in order of discovery: the caller maps it to its lmanager id), src[i] = its index in the PREVIOUS frame's list (-1: discovered in
  * this frame, from SuperPoint keypoint kp[i] of d2fe_pipe_result's left row; kp = -1 for tracked entries), desc / scores = the SuperPoint row of its discovery
  * frame (d2featuretracker.cpp:509-521), right_xy[f][i] / right_status[f][i] = its left -> right track (trackLK(left, right), :697-752; semantics of
- * d2fe_pipe_lk_result).  Slots >= n hold zeros.  What stays with the caller: id -> lmanager ids, createLKLandmark / liftProjective (an entry it rejects keeps
- * its slot here), velocities and the lk_lk_use_pred gate. */
+ * d2fe_pipe_lk_result).  Slots >= n hold zeros.  What stays with the caller: id -> lmanager ids, the NaN skip of createLKLandmark (an entry it rejects keeps
+ * its slot here) and velocities; its liftProjective / bearings, the extrinsic prediction and the lk_lk_use_pred gate run on the device once
+ * d2fe_pipe_bearings_enable has switched them on, and are the caller's otherwise. */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
   int32_t frames, cap_tracks, desc_dim, list_words;
   const int32_t* n;                  /* per list: entries -- frame f's count is n[f * list_words], NOT n[f]; the same stride for every "per list" pointer below */
@@ -516,8 +517,8 @@ D2FE_API int d2fe_pipe_submit_depth(d2fe_pipe p, const uint8_t* gray, const uint
  * -0.5 -> 0), which is what cv::Mat::at<ushort>(cv::Point2f) does through Point_<float> -> Point_<int> -> saturate_cast<int> (upstream OpenCV behaviour, not part
  * of the reference tree; the reference's reads are loop_cam.cpp:382 and d2featuretracker.cpp:790-798).  If ix or iy falls outside the image, or a coordinate is NaN,
  * the value is 0: the reference would read out of bounds there, and 0 fails its dep > DEPTH_NEAR_THRES test.  Values are raw (millimetres for a RealSense): the
- * / 1000.0, DEPTH_NEAR_THRES / DEPTH_FAR_THRES, liftProjective, pt3d = pose_cam * (pt2d_norm * dep) and depth = pt3dcam.norm() stay with the caller
- * (INTEGRATION.md). */
+ * / 1000.0, DEPTH_NEAR_THRES / DEPTH_FAR_THRES, pt3d = pose_cam * (pt2d_norm * dep) and depth = pt3dcam.norm() stay with the caller; pt2d_norm (liftProjective,
+ * normalised) is d2fe_pipe_bearings_result::kp_bearing once d2fe_pipe_bearings_enable has switched the bearings on, the caller's otherwise. */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
   int32_t frames, cap, cap_tracks, reserved;
   const uint16_t* kp_depth_mm;       /* [frames][cap]: the value under keypoint i of frame f (d2fe_pipe_result::kps_xy row f); slots >= n_kp[f] hold 0 */
@@ -532,6 +533,78 @@ D2FE_API int d2fe_pipe_depth_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_d
 D2FE_API int d2fe_depth_at_device(d2fe_handle h, const uint16_t* d_depth, int width, int height, size_t depth_stride, size_t depth_image_stride,
                                   const float* d_pts_xy, size_t pts_stride /*floats between lists*/, const int32_t* d_n, int n_lists, int cap, uint16_t* d_out,
                                   void* stream);
+
+/* Bearings, extrinsic predictions and their gate ON THE DEVICE: the per-point pass the reference's tracker runs on everything the front end returns.
+ *   bearing     liftProjective of the point's camera, then P / sqrt(x*x + y*y + z*z) (LoopCam::extractorImgDescDeepnet, loop_cam.cpp:619-645;
+ *               D2FeatureTracker::createLKLandmark, d2featuretracker.cpp:777-802).  A NaN component stays NaN: the hasNaN() skip stays the caller's.
+ *   prediction  predictLandmarksWithExtrinsic (:1296-1313): X = T * (bearing * distance), then spaceToPlane OF THE CAMERA THE POINT WAS LIFTED WITH -- the reference
+ *               projects into the right image with cams.at(left camera_index) (:1309); that quirk is kept.  Stored as (float)u, (float)v.
+ *   gate        trackLK(left, right) with lk_lk_use_pred (:742-744): pred_ok[i] = status[i] && (radius <= 0 || cv::norm(pred[i] - other[i]) < radius), cv::norm on
+ *               Point2f (float differences, sqrt of the double sum of squares); a NaN prediction fails `<` and is dropped.  other_bearing = the lift of the other
+ *               point with the SECOND camera (createLKLandmark(right_frame, ...)).
+ * Camera models: pinhole + radtan (PinholeCamera.cc:337-418) and MEI (CataCamera.cc:425-515); the cylindrical model of the quadcam views is not served.
+ * Arithmetic contract: fp64, operation by operation in the order of the host restatements of include/d2fe.hpp (liftProjectivePinhole, liftProjectiveMEI, fillLandmarks,
+ * predictWithExtrinsic, spaceToPlanePinhole, spaceToPlaneMEI); no contraction.  The device's fp64 sqrt and divide are the only operations that may differ from the
+ * host's, by the last bit of their own result. */
+typedef enum { D2FE_CAM_PINHOLE = 0, D2FE_CAM_MEI = 1 } d2fe_camera_kind;
+typedef struct {
+  int32_t kind, reserved;   /* d2fe_camera_kind; 0 */
+  double p[9];              /* PINHOLE: fx fy cx cy k1 k2 p1 p2, p[8] = 0;  MEI: the nine doubles of d2fe_mei_camera in its order (xi k1 k2 p1 p2 gamma1 gamma2 u0 v0) */
+} d2fe_camera;
+/* T_b_a [3][4] row-major, the transform that takes a point of frame a into frame b, from the two poses (unit quaternion w x y z, translation) of a and b in a common
+ * frame: R(q) by the standard unit-quaternion formula after q /= sqrt(w*w + x*x + y*y + z*z), T_b_a = [R_b^T R_a | R_b^T (t_a - t_b)], every dot product summed left
+ * to right.  Host function, no device needed.  This is the library's OWN arithmetic: the reference takes the matrix from Swarm::Pose (swarm_msgs, not in its tree), so
+ * the last bits of its extrinsic are not restated here.  For the stereo prediction: a = left camera, b = right camera. */
+D2FE_API int d2fe_relative_extrinsic(const double* q_a_wxyz, const double* t_a, const double* q_b_wxyz, const double* t_b, double* T_b_a /*[12]*/);
+/* The single-call form (what the pipe launches): n_lists point lists, asynchronous on `stream` (a hipStream_t; NULL: the handle's stream), no host synchronisation.
+ * List l: points d_pts_xy + l * pts_stride floats as [cap][2], count d_n[l] (read on the device, clamped to 0..cap).  d_bearing [n_lists][cap][3] doubles.
+ * T (HOST, [12] row-major 3 x 4; NULL: no prediction) and d_pred_xy [n_lists][cap][2] floats (NULL: no prediction).  The gate's four pointers are given together or all
+ * NULL, and need d_pred_xy, T and cam_other: d_other_xy [n_lists][cap][2], d_other_status [n_lists][cap], d_other_bearing [n_lists][cap][3] doubles, d_pred_ok
+ * [n_lists][cap].  Every slot >= d_n[l] is written as zero in every output.  D2FE_ERR_INVALID: null arguments, cap outside 1..16384, n_lists outside 1..32767,
+ * pts_stride < 2 * cap with more than one list, an unknown kind, fx / fy / gamma1 / gamma2 zero or not finite, distance or T not finite, gate outputs without d_pred_xy. */
+D2FE_API int d2fe_bearings_device(d2fe_handle h, const d2fe_camera* cam, const d2fe_camera* cam_other /*NULL*/, const double* T /*NULL: no prediction*/, double distance,
+                                  const float* d_pts_xy, size_t pts_stride, const int32_t* d_n, int n_lists, int cap, double* d_bearing, float* d_pred_xy /*NULL*/,
+                                  const float* d_other_xy, const uint8_t* d_other_status, double radius, double* d_other_bearing,
+                                  uint8_t* d_pred_ok /* the last four NULL together */, void* stream);
+/* The same pass IN THE STEREO / MONO PIPE, switched on by a call before the first submit (d2fe_pipe_config and d2fe_pipe_camera are closed structs; the precedent is
+ * d2fe_pipe_flow_enable).  Works with every pipe shape and mode (lr_lk, sp_lk, the flow landmarks incl. superpoint = 0, mono, depth, coalesce), in any order with
+ * d2fe_pipe_flow_enable / d2fe_pipe_set_track_params.  Refused (D2FE_ERR_INVALID, the pipe stays as it
+ * was and usable): a wrong struct_size, after the first submit, a second time, what d2fe_bearings_device refuses in a camera, distance or T_right_left not finite,
+ * radius_lk NaN.  On a mono pipe cam[1], T_right_left and the gate are ignored.
+ * Per pass ONE more launch (bearings_kernel, D2FE_PROF_LK) behind the list chain and the left -> right launch, beside the depth launch, in front of the matcher:
+ *   left keypoint rows    bearing (cam[0]) and prediction; on an lr_lk pipe without lists also the gate against its left -> right tracks (d2fe_pipe_lk_result)
+ *   right keypoint rows   bearing (cam[1]); only pipes that run SuperPoint on both images
+ *   list entries          (sp_lk or the flow landmarks) bearing, prediction and the gate against right_xy / right_status
+ * With match_lr = 1 and radius_lr > 0 the L <-> R pairs of the matcher take the PREDICTED points as pts_a: the radius gate then is the reference's
+ * (track(), d2featuretracker.cpp:666-674: enable_prediction with prediction_using_extrinsic; the comparison feature_matcher.cpp:33 is `>`, under which a NaN
+ * prediction keeps the match).  The new arrays sit at the end of the region in front of d2h_words (inside the pass's one D2H); every existing offset, the device views and
+ * the exchanges' reads are unchanged, every other result is bit-identical, and a pipe that never enables the mode keeps its layout, allocations and launches.
+ * With the caller: the NaN skip, lmanager ids, velocities, lm.depth = (pt3d_norm * dep).norm(), motion prediction from lmanager positions
+ * (use_extrinsic = false), check_essential, the quad pipe and the cylindrical model. */
+typedef struct {
+  int32_t struct_size;      /* sizeof(d2fe_pipe_bearings), checked strictly */
+  int32_t lk_use_pred;      /* lk_lk_use_pred (d2featuretracker.h:62), default 1; 0: pred_ok = status */
+  d2fe_camera cam[2];       /* left, right */
+  double T_right_left[12];  /* takes a point of the left camera into the right one (d2fe_relative_extrinsic with a = left, b = right) */
+  double distance;          /* landmark_distance_assumption, default 100 */
+  double radius_lk;         /* search_local_max_dist_lr * width; <= 0: pred_ok = status */
+} d2fe_pipe_bearings;
+D2FE_API void d2fe_pipe_bearings_default(d2fe_pipe_bearings* b);      /* struct_size, lk_use_pred = 1, distance = 100, T = identity, everything else 0 */
+D2FE_API int d2fe_pipe_bearings_enable(d2fe_pipe p, const d2fe_pipe_bearings* b);
+/* The bearings of a ticket that d2fe_pipe_wait has returned (D2FE_ERR_NOT_READY before that, D2FE_ERR_UNSUPPORTED on a pipe without the mode).  Whatever the pipe's
+ * shape does not produce is NULL. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_pipe_result */
+  int32_t frames, cap, cap_tracks, reserved;      /* cap_tracks: of the list the pipe carries (sp_lk or flow), 0 without one */
+  const double* kp_bearing;          /* [2 frames][cap][3], the rows of d2fe_pipe_result::kps_xy; rows of images SuperPoint does not see hold zeros */
+  const float* kp_pred_xy;           /* [frames][cap][2]: the left keypoints predicted into the right image; NULL on a mono pipe */
+  const double* lk_right_bearing;    /* [frames][cap][3]: the lift of d2fe_pipe_lk_result::pts_xy with cam[1]; an lr_lk pipe without lists, NULL otherwise */
+  const uint8_t* lk_pred_ok;         /* [frames][cap]: the gate on d2fe_pipe_lk_result::status; NULL as lk_right_bearing */
+  const double* list_bearing;        /* [frames][cap_tracks][3], contiguous like right_xy; NULL without a list */
+  const float* list_pred_xy;         /* [frames][cap_tracks][2]; NULL without a list or on a mono pipe */
+  const double* list_right_bearing;  /* [frames][cap_tracks][3]: the lift of right_xy with cam[1]; NULL as list_pred_xy */
+  const uint8_t* list_pred_ok;       /* [frames][cap_tracks]: the gate on right_status; NULL as list_pred_xy */
+} d2fe_pipe_bearings_result;
+D2FE_API int d2fe_pipe_bearings_result_get(d2fe_pipe p, int64_t ticket, d2fe_pipe_bearings_result* out);
 
 /* Device-side consumers of a ticket's results: the cross-agent exchange (pack -> all-gather -> gate -> remote matching; the reference broadcasts
  * the frame it has just extracted, loop_net.cpp:24-87, d2featuretracker.cpp:237-310) runs on a stream of its OWN, behind the extraction of the ticket and beside the
@@ -1065,7 +1138,8 @@ D2FE_API int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* 
  * block (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the conventions of d2fe_pipe_track_result: n[(q * 4 + c) * list_words], ...); the list
  * of camera a that a neighbour pair tracks and matches is the list AFTER this frame's step.  d2fe_quad_pipe_result and its nb_* / prev_* stay keypoint-based,
  * governed by match_neighbour / match_prev (the reference's configuration of this mode has both off).  Results are bit-identical for every (lanes, quads).
- * With the caller, as for the stereo mode: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate. */
+ * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate -- the bearings mode of the stereo
+ * pipe (d2fe_pipe_bearings_enable) does not extend to the quad pipe: its views use the cylindrical model, which d2fe_bearings_device does not serve. */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
   int32_t quads, cap_tracks, desc_dim, list_words;
   const int32_t* n;                  /* per list: list (q, c)'s count is n[(q * 4 + c) * list_words]; the same stride for every "per list" pointer below */
@@ -1096,7 +1170,8 @@ D2FE_API int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_q
  * mode's matchKNN.  d2fe_quad_flow_result_get after d2fe_quad_pipe_wait (D2FE_ERR_NOT_READY before it, D2FE_ERR_UNSUPPORTED on a pipe without the mode): list (q, c)
  * is (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the convention of d2fe_quad_track_result); the list of camera a that a neighbour pair
  * tracks is the list AFTER this frame's step.  Results are bit-identical for every (lanes, quads).
- * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate. */
+ * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate (d2fe_pipe_bearings_enable is the
+ * stereo / mono pipe's; the cylindrical model of the quad views is not served). */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
   int32_t quads, cap_tracks, list_words, reserved;
   const int32_t *n, *n_tracked_in, *n_lost, *n_removed_near, *n_new, *lack, *num, *n_cand;      /* per list */

@@ -230,6 +230,15 @@ struct StereoFlowList {
   std::vector<uint16_t> depth_mm;
   int n_tracked_in = 0, n_lost = 0, n_removed_near = 0, n_new = 0, lack = 0, num = 0, n_cand = 0;
 };
+// StereoPipe::bearingsEnable (d2fe_pipe_bearings_enable): unit bearings as [n][3] doubles (x, y, z of entry i at 3 i), the extrinsic predictions of left points in the
+// right image and the lk_lk_use_pred gate, all computed on the device.  kp_*: the frame's keypoints (kps_left / kps_right); lk_*: the left -> right tracks of an lr_lk
+// pipe without lists (lk_right / lk_status); list_*: the entries of the list the pipe carries (tracks or flow).  A NaN bearing is returned as it is: the hasNaN() skip of
+// createLKLandmark stays with the caller.  Whatever the pipe's shape does not produce stays empty
+struct StereoBearings {
+  std::vector<double> kp_left, kp_right, lk_right, list, list_right;
+  std::vector<Point2f> kp_pred, list_pred;
+  std::vector<uint8_t> lk_pred_ok, list_pred_ok;
+};
 struct StereoFrameResult {
   std::vector<Point2f> kps_left, kps_right;
   std::vector<float> scores_left, scores_right;
@@ -246,6 +255,7 @@ struct StereoFrameResult {
   // a depth pipe (d2fe_pipe_camera::depth, PINHOLE_DEPTH): depth_mm[i] = depth.at<unsigned short>(kps_left[i]) of the frame's depth image (loop_cam.cpp:382), i.e. the pixel at
   // (cvRound(x), cvRound(y)), 0 outside the image; the / 1000.0, the DEPTH_NEAR_THRES / DEPTH_FAR_THRES test and liftProjective stay with the caller
   std::vector<uint16_t> depth_mm;
+  StereoBearings bearings;                           // StereoPipe::bearingsEnable
 };
 // borrowed view of a CV_16UC1 cv::Mat (a depth image); step in bytes
 struct DepthView {
@@ -286,6 +296,14 @@ class StereoPipe {
     if (!p_) return false;
     if (d2fe_pipe_flow_enable(p_, fp) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_flow_enable: %s\n", d2fe_last_error()); return false; }
     flow_ = true;
+    return true;
+  }
+  // bearings, extrinsic predictions and their gate on the device (d2fe_pipe_bearings_enable): once, before the first submit; b: d2fe_pipe_bearings_default + the two
+  // cameras, T_right_left (d2fe_relative_extrinsic), distance, radius_lk.  A refusal leaves the pipe as it was
+  bool bearingsEnable(const d2fe_pipe_bearings& b) {
+    if (!p_) return false;
+    if (d2fe_pipe_bearings_enable(p_, &b) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_bearings_enable: %s\n", d2fe_last_error()); return false; }
+    bearings_ = true;
     return true;
   }
   // returns the ticket (>= 0) or -1
@@ -371,6 +389,21 @@ class StereoPipe {
       out.depth_mm.assign(dr.kp_depth_mm, dr.kp_depth_mm + r.n_kp[0]);
       if (dr.track_depth_mm) out.tracks.depth_mm.assign(dr.track_depth_mm, dr.track_depth_mm + out.tracks.pts.size());
     }
+    out.bearings = StereoBearings();
+    if (bearings_) {
+      d2fe_pipe_bearings_result br;
+      if (d2fe_pipe_bearings_result_get(p_, ticket, &br) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_pipe_bearings_result_get: %s\n", d2fe_last_error()); return false; }
+      StereoBearings& b = out.bearings;
+      const size_t nl = (size_t)r.n_kp[0], nr = (size_t)r.n_kp[1], nt = sp_lk_ ? out.tracks.pts.size() : out.flow.pts.size();
+      auto pts = [](const float* xy, size_t n, std::vector<Point2f>& v) { for (size_t j = 0; xy && j < n; ++j) v.emplace_back(xy[2 * j], xy[2 * j + 1]); };
+      b.kp_left.assign(br.kp_bearing, br.kp_bearing + 3 * nl);
+      b.kp_right.assign(br.kp_bearing + (size_t)br.cap * 3, br.kp_bearing + (size_t)br.cap * 3 + 3 * nr);
+      pts(br.kp_pred_xy, nl, b.kp_pred);
+      if (br.lk_right_bearing) { b.lk_right.assign(br.lk_right_bearing, br.lk_right_bearing + 3 * nl); b.lk_pred_ok.assign(br.lk_pred_ok, br.lk_pred_ok + nl); }
+      if (br.list_bearing) b.list.assign(br.list_bearing, br.list_bearing + 3 * nt);
+      pts(br.list_pred_xy, nt, b.list_pred);
+      if (br.list_right_bearing) { b.list_right.assign(br.list_right_bearing, br.list_right_bearing + 3 * nt); b.list_pred_ok.assign(br.list_pred_ok, br.list_pred_ok + nt); }
+    }
     return true;
   }
   // d2fe_pipe_stream_placement: the hardware-pipe class measured for every lane's (own, second) stream; the return value = classes told apart (0: not measured)
@@ -387,7 +420,7 @@ class StereoPipe {
 
  private:
   d2fe_pipe p_ = nullptr;
-  bool lr_lk_ = false, sp_lk_ = false, depth_ = false, flow_ = false;
+  bool lr_lk_ = false, sp_lk_ = false, depth_ = false, flow_ = false, bearings_ = false;
 };
 
 // trackEnable(): the LK-carried landmark list of one view of a quad frame (what D2FeatureTracker::trackLK(frame) leaves in keyframe_lk_infos[frame_id][c] with
@@ -764,6 +797,38 @@ inline Vec3d liftProjectiveMEI(const d2fe_mei_camera& c, const Point2f& p) {
   if (xi == 1.0) return Vec3d{mx_u, my_u, (1.0 - mx_u * mx_u - my_u * my_u) / 2.0};
   const double rho2 = mx_u * mx_u + my_u * my_u;
   return Vec3d{mx_u, my_u, 1.0 - xi * (rho2 + 1.0) / (xi + std::sqrt(1.0 + (1.0 - xi * xi) * rho2))};
+}
+// PinholeCamera::spaceToPlane (PinholeCamera.cc:399-418)
+inline void spaceToPlanePinhole(double fx, double fy, double cx, double cy, const RadTan& d, const Vec3d& P, double& u, double& v) {
+  const double pu0 = P.x / P.z, pu1 = P.y / P.z;
+  double pd0 = pu0, pd1 = pu1;
+  if (d.k1 != 0 || d.k2 != 0 || d.p1 != 0 || d.p2 != 0) {
+    double dx, dy;
+    radtanDistortion(d, pu0, pu1, dx, dy);
+    pd0 = pu0 + dx; pd1 = pu1 + dy;
+  }
+  u = fx * pd0 + cx; v = fy * pd1 + cy;
+}
+// CataCamera::spaceToPlane (CataCamera.cc:495-515), in the operation order of the library's map generation (d2fe_gen_pinhole_map)
+inline void spaceToPlaneMEI(const d2fe_mei_camera& c, const Vec3d& P, double& u, double& v) {
+  const double nrm = std::sqrt(P.x * P.x + (P.y * P.y + P.z * P.z));
+  const double z = P.z + c.xi * nrm;
+  const double pu0 = P.x / z, pu1 = P.y / z;
+  double dx, dy;
+  radtanDistortion(RadTan{c.k1, c.k2, c.p1, c.p2}, pu0, pu1, dx, dy);
+  u = c.gamma1 * (pu0 + dx) + c.u0; v = c.gamma2 * (pu1 + dy) + c.v0;
+}
+// P / |P| as fillLandmarks below normalises (loop_cam.cpp:619-645)
+inline Vec3d unitBearing(Vec3d P) {
+  const double n = std::sqrt(P.x * P.x + P.y * P.y + P.z * P.z);
+  P.x /= n; P.y /= n; P.z /= n;
+  return P;
+}
+// predictLandmarksWithExtrinsic (d2featuretracker.cpp:1303-1310): the point of the unit bearing at `distance`, taken through T [3][4] row-major; the caller projects
+// it with the camera the bearing was lifted with (the reference's cams.at(left camera_index))
+inline Vec3d predictWithExtrinsic(const double* T, const Vec3d& bearing, double distance) {
+  const double Lx = bearing.x * distance, Ly = bearing.y * distance, Lz = bearing.z * distance;
+  return Vec3d{((T[0] * Lx + T[1] * Ly) + T[2] * Lz) + T[3], ((T[4] * Lx + T[5] * Ly) + T[6] * Lz) + T[7], ((T[8] * Lx + T[9] * Ly) + T[10] * Lz) + T[11]};
 }
 // CylindricalCamera::liftProjective (CylindricalCamera.cc:207-220)
 inline Vec3d liftProjectiveCylindrical(double fx, double fy, double cx, double cy, const Point2f& p) {
