@@ -145,7 +145,7 @@ class _PipeDepthResult(C.Structure):
 
 
 class _Camera(C.Structure):
-    """d2fe_camera: kind (CAM_PINHOLE / CAM_MEI) and its nine doubles (camera_pinhole / camera_mei)"""
+    """d2fe_camera: kind (CAM_PINHOLE / CAM_MEI / CAM_CYLINDRICAL) and its nine doubles (camera_pinhole / camera_mei / camera_cylindrical)"""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 9)]
 
 
@@ -159,6 +159,17 @@ class _PipeBearingsResult(C.Structure):
     _fields_ = [("frames", C.c_int32), ("cap", C.c_int32), ("cap_tracks", C.c_int32), ("reserved", C.c_int32), ("kp_bearing", C.c_void_p), ("kp_pred_xy", C.c_void_p),
                 ("lk_right_bearing", C.c_void_p), ("lk_pred_ok", C.c_void_p), ("list_bearing", C.c_void_p), ("list_pred_xy", C.c_void_p),
                 ("list_right_bearing", C.c_void_p), ("list_pred_ok", C.c_void_p)]
+
+
+class _QuadBearings(C.Structure):
+    """d2fe_quad_bearings: the bearings mode of a quad pipe (d2fe_quad_bearings_enable)"""
+    _fields_ = [("struct_size", C.c_int32), ("lk_use_pred", C.c_int32), ("cam", _Camera * 4), ("T_nb", C.c_double * 48), ("distance", C.c_double),
+                ("radius_lk", C.c_double)]
+
+
+class _QuadBearingsResult(C.Structure):
+    _fields_ = [("quads", C.c_int32), ("cap", C.c_int32), ("cap_tracks", C.c_int32), ("reserved", C.c_int32), ("kp_bearing", C.c_void_p), ("list_bearing", C.c_void_p),
+                ("nb_pred_xy", C.c_void_p), ("nb_bearing", C.c_void_p), ("nb_pred_ok", C.c_void_p)]
 
 
 class _PipeDeviceResult(C.Structure):
@@ -280,6 +291,7 @@ EXPORTS = [
     "d2fe_pipe_flow_enable", "d2fe_pipe_flow_result_get",
     "d2fe_relative_extrinsic", "d2fe_bearings_device", "d2fe_pipe_bearings_default", "d2fe_pipe_bearings_enable", "d2fe_pipe_bearings_result_get",
     "d2fe_lk_flow_quad_step_device", "d2fe_lk_flow_neighbour_device", "d2fe_quad_flow_enable", "d2fe_quad_flow_result_get",
+    "d2fe_cylinder_camera", "d2fe_quad_bearings_default", "d2fe_quad_bearings_enable", "d2fe_quad_bearings_result_get",
     "d2fe_detect_fast_by_region", "d2fe_good_features_to_track", "d2fe_pipe_default_config", "d2fe_pipe_create", "d2fe_pipe_destroy",
     "d2fe_pipe_lanes", "d2fe_pipe_stream_placement", "d2fe_pipe_classify_stream", "d2fe_pipe_submit", "d2fe_pipe_wait", "d2fe_pipe_profile_enable", "d2fe_pipe_profile_read",
     "d2fe_pipe_device_view", "d2fe_pipe_device_release", "d2fe_pipe_lane_stream", "d2fe_pipe_geometry", "d2fe_pipe_handle",
@@ -511,6 +523,11 @@ def _open_library(path, dev):
         lib.d2fe_pipe_bearings_default.restype = None
         lib.d2fe_pipe_bearings_enable.argtypes = [C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_bearings_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.d2fe_cylinder_camera.argtypes = [C.c_int, C.c_int, C.c_double, C.c_void_p]
+        lib.d2fe_quad_bearings_default.argtypes = [C.c_void_p]
+        lib.d2fe_quad_bearings_default.restype = None
+        lib.d2fe_quad_bearings_enable.argtypes = [C.c_void_p, C.c_void_p]
+        lib.d2fe_quad_bearings_result_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_device_view.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.d2fe_pipe_device_release.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         lib.d2fe_pipe_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -1619,7 +1636,7 @@ def depth_at_device(fe, d_depth, width, height, depth_stride, depth_image_stride
                                         int(pts_stride), C.c_void_p(d_n), int(n_lists), int(cap), C.c_void_p(d_out), C.c_void_p(stream or 0)))
 
 
-CAM_PINHOLE, CAM_MEI = 0, 1
+CAM_PINHOLE, CAM_MEI, CAM_CYLINDRICAL = 0, 1, 3
 
 
 def camera_pinhole(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
@@ -1630,6 +1647,18 @@ def camera_pinhole(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
 def camera_mei(cam):
     """d2fe_camera of camodocal's CataCamera; cam: dict(xi,k1,k2,p1,p2,gamma1,gamma2,u0,v0) or the nine values in that order"""
     return _Camera(CAM_MEI, 0, FrontEnd._mei(cam))
+
+
+def camera_cylindrical(fx, fy, cx, cy):
+    """d2fe_camera of camodocal's CylindricalCamera (the undistorted quadcam views)"""
+    return _Camera(CAM_CYLINDRICAL, 0, (C.c_double * 9)(float(fx), float(fy), float(cx), float(cy), 0.0, 0.0, 0.0, 0.0, 0.0))
+
+
+def cylinder_camera(width, height, fov_deg):
+    """d2fe_cylinder_camera (host only): the virtual camera gen_cylinder_map assumes for a width x height view of fov_deg degrees"""
+    c = _Camera()
+    _check(load_library().d2fe_cylinder_camera(int(width), int(height), float(fov_deg), C.byref(c)))
+    return c
 
 
 def relative_extrinsic(q_a_wxyz, t_a, q_b_wxyz, t_b):
@@ -1675,12 +1704,16 @@ class QuadPipe(_Owned):
     flow_lk=True (d2fe_quad_flow_enable; excludes sp_lk; flow_params: a dict of flow_params() keywords, a _FlowParams or None for the reference's defaults): the flow
     landmarks of the four cameras beside SuperPoint and their neighbour LK tracks; wait() then also returns per list (q, c) "flow_n", "flow_n_tracked_in",
     "flow_n_lost", "flow_n_removed_near", "flow_n_new", "flow_lack", "flow_num", "flow_n_cand" [quads, 4], "flow_pts" [quads, 4, cap_tracks, 2], "flow_id" /
-    "flow_src" [quads, 4, cap_tracks], and "flow_nb_lk_xy" [quads, 4, cap_tracks, 2] / "flow_nb_lk_status" [quads, 4, cap_tracks] per neighbour pair."""
+    "flow_src" [quads, 4, cap_tracks], and "flow_nb_lk_xy" [quads, 4, cap_tracks, 2] / "flow_nb_lk_status" [quads, 4, cap_tracks] per neighbour pair.
+    bearings=dict(cams=[4 cameras], T_nb=[4 x 12 doubles], distance=100.0, lk_use_pred=True, radius_lk=...) (d2fe_quad_bearings_enable; with or without a list mode):
+    unit bearings, neighbour predictions and the lk_lk_use_pred gate on the device; wait() then also returns "bear_kp" [quads, 4, cap, 3] float64 and, with lists,
+    "bear_list" [quads, 4, cap_tracks, 3] float64, "bear_nb_pred" [quads, 4, cap_tracks, 2], "bear_nb" [quads, 4, cap_tracks, 3] float64 and "bear_nb_pred_ok"
+    [quads, 4, cap_tracks] uint8 per neighbour pair (None without lists)."""
     _HANDLE, _DESTROY = "_p", "d2fe_quad_pipe_destroy"
 
     def __init__(self, fe: FrontEnd, maps, lanes=4, quads=1, raw_width=1280, raw_height=800, width=800, height=400, cap=None, netvlad=True,
                  match_neighbour=True, match_prev=True, ratio=0.8, radius_neighbour=None, radius_prev=-1.0, undistort_fov=200.0, pinned_input=False,
-                 sp_lk=False, track_params=None, flow_lk=False, flow_params=None):
+                 sp_lk=False, track_params=None, flow_lk=False, flow_params=None, bearings=None):
         self._lib = fe._lib
         self._fe = fe           # the pipe borrows the handle's weights
         c = _QuadPipeConfig()
@@ -1716,13 +1749,17 @@ class QuadPipe(_Owned):
         self._res = _QuadPipeResult()
         self._track_res = _QuadTrackResult()
         self._flow_res = _QuadFlowResult()
+        self._bear_res = _QuadBearingsResult()
         self._sp_lk = False
         self._flow = False
+        self._bearings = False
         try:
             if sp_lk:
                 self.track_enable(track_params)
             if flow_lk:
                 self.flow_enable(flow_params)
+            if bearings is not None:
+                self.bearings_enable(**bearings)
         except Exception:
             self.close()
             raise
@@ -1737,6 +1774,30 @@ class QuadPipe(_Owned):
         """d2fe_quad_flow_result_get: the flow lists of a ticket that wait() has returned (D2FE_ERR_UNSUPPORTED without the mode)"""
         _check(self._lib.d2fe_quad_flow_result_get(self._p, C.c_int64(ticket), C.byref(self._flow_res)))
         return self._flow_res
+
+    def bearings_enable(self, cams, T_nb=None, distance=100.0, lk_use_pred=True, radius_lk=0.0):
+        """d2fe_quad_bearings_enable: once, before the first submit, in any order with track_enable / flow_enable.  cams: four cameras (cylinder_camera() for the
+        undistorted views); T_nb: [4][12] doubles, pair n of (0,1) (1,2) (2,3) (0,3) as [3][4] row-major (relative_extrinsic); radius_lk = search_local_max_dist_lr *
+        width."""
+        b = _QuadBearings()
+        self._lib.d2fe_quad_bearings_default(C.byref(b))
+        if len(cams) != 4:
+            raise ValueError("QuadPipe.bearings_enable takes four cameras")
+        for c in range(4):
+            b.cam[c] = cams[c]
+        if T_nb is not None:
+            T = np.asarray(T_nb, np.float64).reshape(-1)
+            if T.size != 48:
+                raise ValueError("QuadPipe.bearings_enable: T_nb is [4][12] doubles")
+            b.T_nb = (C.c_double * 48)(*[float(v) for v in T])
+        b.distance, b.lk_use_pred, b.radius_lk = float(distance), int(bool(lk_use_pred)), float(radius_lk)
+        _check(self._lib.d2fe_quad_bearings_enable(self._p, C.byref(b)))
+        self._bearings = True
+
+    def bearings_result_raw(self, ticket):
+        """d2fe_quad_bearings_result_get: the bearings of a ticket that wait() has returned (D2FE_ERR_UNSUPPORTED without the mode)"""
+        _check(self._lib.d2fe_quad_bearings_result_get(self._p, C.c_int64(ticket), C.byref(self._bear_res)))
+        return self._bear_res
 
     def track_enable(self, tp=None):
         """d2fe_quad_track_enable: once, before the first submit (tp: dict of d2fe_track_params fields, a _TrackParams, or None for the defaults)"""
@@ -1828,6 +1889,17 @@ class QuadPipe(_Owned):
             out["flow_pts"] = flist(t.pts_xy, (T, 2), f); out["flow_id"] = flist(t.id, (T,), i); out["flow_src"] = flist(t.src, (T,), i)
             out["flow_nb_lk_xy"] = _pinned_view(t.nb_lk_xy, (Q, 4, T, 2), f)
             out["flow_nb_lk_status"] = np.frombuffer((C.c_uint8 * (Q * 4 * T)).from_address(t.nb_lk_status), dtype=np.uint8).reshape(Q, 4, T)
+        if self._bearings:
+            b = self.bearings_result_raw(ticket)
+            T = b.cap_tracks
+
+            def raw(ptr, shape, ct, dt):
+                return np.frombuffer((ct * int(np.prod(shape))).from_address(ptr), dtype=dt).reshape(shape) if ptr else None
+            out["bear_kp"] = raw(b.kp_bearing, (Q, 4, cap, 3), C.c_double, np.float64)
+            out["bear_list"] = raw(b.list_bearing, (Q, 4, T, 3), C.c_double, np.float64)
+            out["bear_nb_pred"] = _pinned_view(b.nb_pred_xy, (Q, 4, T, 2), f)
+            out["bear_nb"] = raw(b.nb_bearing, (Q, 4, T, 3), C.c_double, np.float64)
+            out["bear_nb_pred_ok"] = raw(b.nb_pred_ok, (Q, 4, T), C.c_uint8, np.uint8)
         return out
 
 

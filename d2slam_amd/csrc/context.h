@@ -349,14 +349,17 @@ struct DepthSeg { const float* pts; size_t pts_stride; const int32_t* n; size_t 
 int depth_gather_launch(d2fe_context* h, const uint16_t* d_depth, int W, int H, size_t depth_stride_px, size_t depth_image_stride_px, int n_lists, const DepthSeg* segs,
                         int n_segs, hipStream_t s);
 
-// bearings.hip: bearings_kernel over up to three segments of point lists in ONE launch (the pipe: the pass's left keypoint rows, its right keypoint rows, its landmark
-// lists).  List l of a segment reads its points at pts + l * pts_stride floats and its count at n[l * n_stride]; it lifts them with camera `cam` (0 / 1 of BearCams) and
-// writes bearing[(l * bearing_step) * cap * 3 ..).  pred != null: the extrinsic prediction, dense [list][cap][2].  pred_ok != null (needs pred): the gate against
-// other[l * other_stride ..) / status[l * status_stride ..), other_bearing (lifted with camera 1) and pred_ok dense.  Slots >= n are written as zero everywhere
+// bearings.hip: bearings_kernel over up to three segments of point lists in ONE launch (the stereo pipe: the pass's left keypoint rows, its right keypoint rows, its
+// landmark lists; the quad pipe: the keypoint rows, the four lists of every quad frame, its four neighbour pairs).  List l of a segment reads its points at
+// pts + s * pts_stride floats and its count at n[s * n_stride], s = l, or with by4 the list (l & ~3) + src[l & 3] (a neighbour pair reads the list of its camera a).
+// It lifts them with camera cam[j] of BearCams, j = 0, or l & 3 with by4, and writes bearing[(l * bearing_step) * cap * 3 ..) (bearing may be null when pred is
+// not).  pred != null: the prediction through extrinsic ext[j], dense [list][cap][2].  pred_ok != null (needs pred): the gate against other[l * other_stride ..) /
+// status[l * status_stride ..), other_bearing (lifted with camera ocam[j]) and pred_ok dense.  Slots >= n are written as zero everywhere
 struct BearCam { int kind, distort; double p[9]; double iK11, iK13, iK22, iK23; };
-struct BearCams { BearCam cam[2]; double T[12]; double distance, radius; };
+struct BearCams { BearCam cam[4]; double T[4][12]; double distance, radius; };
 struct BearSeg {
-  const float* pts; size_t pts_stride; const int32_t* n; size_t n_stride; int cap, cam;
+  const float* pts; size_t pts_stride; const int32_t* n; size_t n_stride; int cap, by4;
+  unsigned char cam[4], ocam[4], ext[4], src[4];
   double* bearing; size_t bearing_step; float* pred;
   const float* other; size_t other_stride; const uint8_t* status; size_t status_stride; double* other_bearing; uint8_t* pred_ok;
 };

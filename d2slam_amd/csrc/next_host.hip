@@ -127,6 +127,16 @@ int d2fe_gen_cylinder_map_device(d2fe_handle h, const d2fe_mei_camera* cam, int 
   if (!(fov_deg > 0)) return fail(D2FE_ERR_INVALID, "fov must be positive");
   return gen_map(h, cam, nullptr, 0, width, height, cyl_focal(width, fov_deg), d_mapx, d_mapy, true, stream);
 }
+// the virtual camera the two generators above assume (FisheyeUndist's CylindricalCamera, fisheye_undistort.h:492-495): the same focal length, the integer centre
+int d2fe_cylinder_camera(int width, int height, double fov_deg, d2fe_camera* out) {
+  if (!out) return fail(D2FE_ERR_INVALID, "null argument");
+  if (width < 1 || height < 1 || !(fov_deg > 0)) return fail(D2FE_ERR_INVALID, "width and height must be >= 1, fov positive");
+  *out = d2fe_camera{};
+  out->kind = D2FE_CAM_CYLINDRICAL;
+  out->p[0] = out->p[1] = cyl_focal(width, fov_deg);
+  out->p[2] = (double)((unsigned)width / 2); out->p[3] = (double)((unsigned)height / 2);
+  return D2FE_OK;
+}
 int d2fe_gen_pinhole_map(d2fe_handle h, const d2fe_mei_camera* cam, const double* q_wxyz, int width, int height, double f,
                          float* mapx, float* mapy) {
   return gen_map(h, cam, q_wxyz, 1, width, height, f, mapx, mapy, false, nullptr);

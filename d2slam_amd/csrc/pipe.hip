@@ -415,7 +415,7 @@ int pipe_flush(d2fe_pipe_s* p) {
     kl = BearSeg{};
     kl.pts = staged ? B + p->o_skps : B + p->o_kps; kl.pts_stride = staged ? cap * 2 : rstep * cap * 2;
     kl.n = reinterpret_cast<const int32_t*>(staged ? B + p->o_scnt : B + p->o_cnt); kl.n_stride = staged ? 1 : rstep;
-    kl.cap = p->cap; kl.cam = 0;
+    kl.cap = p->cap; kl.ocam[0] = 1;
     kl.bearing = reinterpret_cast<double*>(B + p->o_bkb); kl.bearing_step = rstep;
     if (!p->mono) kl.pred = B + p->o_bkp;
     if (p->bear_lk_gate()) {
@@ -428,7 +428,7 @@ int pipe_flush(d2fe_pipe_s* p) {
       const size_t r0 = (size_t)p->right_row(0, 0);
       kr.pts = B + p->o_kps + r0 * cap * 2; kr.pts_stride = rstep * cap * 2;
       kr.n = reinterpret_cast<const int32_t*>(B + p->o_cnt) + r0; kr.n_stride = rstep;
-      kr.cap = p->cap; kr.cam = 1;
+      kr.cap = p->cap; kr.cam[0] = 1;
       kr.bearing = reinterpret_cast<double*>(B + p->o_bkb) + r0 * cap * 3; kr.bearing_step = rstep;
     }
     if (p->capL) {
@@ -439,7 +439,7 @@ int pipe_flush(d2fe_pipe_s* p) {
       const size_t lw = p->flow ? p->flist_words : p->list_words;
       tl.pts = lists + (p->flow ? d2fe_lk_flow_list_offset(p->capF, D2FE_LKC_PTS) : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_PTS)); tl.pts_stride = lw;
       tl.n = reinterpret_cast<const int32_t*>(lists + (p->flow ? 0 : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_HDR))); tl.n_stride = lw;
-      tl.cap = p->capL; tl.cam = 0;
+      tl.cap = p->capL; tl.ocam[0] = 1;
       tl.bearing = reinterpret_cast<double*>(B + p->o_btb); tl.bearing_step = 1;
       if (!p->mono) {
         tl.pred = B + p->o_btp;
@@ -1215,7 +1215,7 @@ int d2fe_pipe_bearings_enable(d2fe_pipe p, const d2fe_pipe_bearings* b) {
   p->bcams.cam[0] = bearings_make_camera(b->cam[0]);
   p->bcams.cam[1] = bearings_make_camera(p->mono ? b->cam[0] : b->cam[1]);
   if (!p->mono) {
-    for (int i = 0; i < 12; ++i) p->bcams.T[i] = b->T_right_left[i];
+    for (int i = 0; i < 12; ++i) p->bcams.T[0][i] = b->T_right_left[i];
     p->bcams.distance = b->distance;
     p->bcams.radius = b->lk_use_pred ? b->radius_lk : 0.0;
   }

@@ -24,6 +24,11 @@
 // d2fe_lk_flow_quad_step_device (five launches for the four cameras) on the keypoints of that quad frame, with ONE pipe-owned detector scratch of four cameras that all
 // lanes share because the chain serialises the steps -- and ONE d2fe_lk_flow_neighbour_device over the pass's lists.  No matchKNN of the lists: flow entries carry no
 // descriptors.  The lists and the neighbour tracks sit where sp_lk puts its own (o_list, o_nbxy, o_nbst), in front of d2h_words.
+//
+// d2fe_quad_bearings_enable (with or without one of the two modes above, in any order): ONE bearings_kernel launch (bearings.hip) per pass behind the neighbour LK
+// launch and in front of the matcher -- the unit bearings of the 4 Q keypoint rows and, with lists, of the 4 Q lists, the prediction of every list entry through its
+// neighbour pair's extrinsic, the bearings of the neighbour tracks and the lk_lk_use_pred gate.  Its arrays are the last ones in front of d2h_words: the lists' arrays
+// keep the offsets they have without it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -156,6 +161,13 @@ struct d2fe_quad_pipe_s {
   uint8_t* d_flow_scratch = nullptr;   // [4 cameras][flow_scratch_stride]: score map, candidate pool and count of each camera
   size_t flow_scratch_stride = 0;
   int32_t* d_lmatch_scratch = nullptr; size_t lmatch_scratch_lane = 0;
+  // d2fe_quad_bearings_enable: doubles [4 Q][cap][3] of the keypoint rows and, with lists, doubles [4 Q][capT][3] of the list entries, per neighbour pair the
+  // predictions floats [4 Q][capT][2], the neighbour tracks' bearings doubles [4 Q][capT][3] and the gate bytes [4 Q][capT] -- behind the lists' arrays (lists_end),
+  // inside d2h_words.  base_words: d2h_words of the pipe as created, where the lists' arrays start
+  bool bear = false;
+  BearCams bcams{};
+  size_t base_words = 0, lists_end = 0;
+  size_t o_bkb = 0, o_blb = 0, o_bnp = 0, o_bnb = 0, o_bno = 0;
   struct Lane : LaneBase { uint8_t* d_raw = nullptr; };
   std::vector<Lane> lanes;
   std::vector<int> first_class, second_class;
@@ -210,6 +222,34 @@ void quad_fill_pairs(const d2fe_quad_pipe_s* p, std::vector<MatchPairDesc>& tab)
     }
 }
 
+// the bearings' arrays from word o on (T = 0: no lists); a double = two words, every array on a 64-word boundary, so the doubles are 8-byte aligned
+struct QuadBearLayout { size_t o_bkb, o_blb, o_bnp, o_bnb, o_bno, end; };
+QuadBearLayout quad_bear_layout(size_t o, size_t NI, size_t cap, size_t T) {
+  QuadBearLayout b{};
+  o = up64(o);
+  b.o_bkb = o; o += up64(NI * cap * 6);
+  if (T) {
+    b.o_blb = o; o += up64(NI * T * 6);
+    b.o_bnp = o; o += up64(NI * T * 2);
+    b.o_bnb = o; o += up64(NI * T * 6);
+    b.o_bno = o; o += up64((NI * T + 3) / 4);
+  }
+  b.end = o;
+  return b;
+}
+
+// the keypoints' pair table holds addresses inside the result blocks: filled again when they have moved.  A failure here is final, like a failed submit
+int quad_refill_pairs(d2fe_quad_pipe_s* p) {
+  if (!p->NP) return D2FE_OK;
+  std::vector<MatchPairDesc> tab;
+  quad_fill_pairs(p, tab);
+  if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
+    return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+  }
+  return D2FE_OK;
+}
+
 // What d2fe_quad_track_enable and d2fe_quad_flow_enable share (called with the pipe's mutex held, before the first submit): the mode's arrays in the result blocks,
 // everything the mode owns on the device and the host, and the pair tables that address the moved blocks.  The caller sets its mode flags when this returns D2FE_OK or
 // has set p->failed
@@ -223,8 +263,9 @@ struct QuadListMode {
 int quad_lists_enable(d2fe_quad_pipe_s* p, const QuadListMode& m) {
   const int Q = p->Q, K = p->K;
   const size_t T = (size_t)m.cap, D = (size_t)p->D, NI = (size_t)p->NI, NJ = 8 * (size_t)Q, lw = m.list_words, pyr_total = m.pyr_total;
-  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the extraction's index scratch (o_idx) moves behind them
-  size_t o = p->d2h_words;
+  // the mode's arrays go between the keypoint results and d2h_words: every earlier offset stays, the bearings' arrays (if they are on already) and the extraction's
+  // index scratch (o_idx) move behind them
+  size_t o = p->base_words;
   const size_t o_list = o; o += NI * lw;
   const size_t o_nbxy = o; o += up64(NI * T * 2);
   const size_t o_nbst = o; o += up64((NI * T + 3) / 4);
@@ -239,6 +280,9 @@ int quad_lists_enable(d2fe_quad_pipe_s* p, const QuadListMode& m) {
     t_jmap = t; t += up64(NJ * T);
     t_jn = t; t += up64(NJ);
   }
+  const size_t lists_end = o;
+  QuadBearLayout bl{};
+  if (p->bear) { bl = quad_bear_layout(o, NI, (size_t)p->cap, T); o = bl.end; }
   const size_t d2h_words = o, o_idx = o, blk_words = o + up64(NI * (size_t)p->cap), tscr_words = t;
   // everything new first; the pipe changes only when all of it is there
   struct Fresh {
@@ -294,17 +338,41 @@ int quad_lists_enable(d2fe_quad_pipe_s* p, const QuadListMode& m) {
   }
   p->capT = m.cap; p->list_words = lw; p->pyr_total = pyr_total;
   p->o_list = o_list; p->o_nbxy = o_nbxy; p->o_nbst = o_nbst; p->o_lmn = o_lmn; p->o_lmq = o_lmq; p->o_lmt = o_lmt; p->o_lmd = o_lmd;
+  p->lists_end = lists_end;
+  if (p->bear) { p->o_bkb = bl.o_bkb; p->o_blb = bl.o_blb; p->o_bnp = bl.o_bnp; p->o_bnb = bl.o_bnb; p->o_bno = bl.o_bno; }
   p->d2h_words = d2h_words; p->o_idx = o_idx; p->blk_words = blk_words;
   p->t_jdesc = t_jdesc; p->t_jpts = t_jpts; p->t_jmap = t_jmap; p->t_jn = t_jn; p->tscr_words = tscr_words;
-  if (p->NP) {      // the keypoints' pair table holds addresses inside the blocks that have just moved: a failure here is final, like a failed submit
-    std::vector<MatchPairDesc> tab;
-    quad_fill_pairs(p, tab);
-    if (hipMemcpy(p->d_pairs, tab.data(), sizeof(MatchPairDesc) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      p->failed = D2FE_ERR_HIP; p->failed_msg = "hipMemcpy of the pair table";
-      return ctx_fail(D2FE_ERR_HIP, p->failed_msg);
+  return quad_refill_pairs(p);
+}
+
+// d2fe_quad_bearings_enable with the pipe's mutex held, before the first submit: the bearings' arrays behind the lists' (or the keypoint results), new blocks and new
+// pinned copies of the larger d2h_words; the pipe changes only when all of it is there
+int quad_bear_blocks(d2fe_quad_pipe_s* p) {
+  const int K = p->K;
+  const size_t NI = (size_t)p->NI;
+  const QuadBearLayout bl = quad_bear_layout(p->lists_end, NI, (size_t)p->cap, p->trk || p->flow ? (size_t)p->capT : 0);
+  const size_t d2h_words = bl.end, blk_words = bl.end + up64(NI * (size_t)p->cap), all_words = 64 + (size_t)K * 2 * blk_words;
+  struct Fresh {
+    float* d_all = nullptr; std::vector<float*> pin; bool keep = false;
+    ~Fresh() {
+      if (keep) return;
+      if (d_all) (void)hipFree(d_all);
+      for (float* q : pin) if (q) (void)hipHostFree(q);
     }
-  }
-  return D2FE_OK;
+  } f;
+  HIP_TRY(hipMalloc(&f.d_all, sizeof(float) * all_words));
+  HIP_TRY(hipMemset(f.d_all, 0, sizeof(float) * all_words));        // as the blocks it replaces: no keypoints, empty lists, every arrival counter zero
+  f.pin.assign((size_t)2 * K, nullptr);
+  for (int i = 0; i < 2 * K; ++i) HIP_TRY(hipHostMalloc(&f.pin[i], sizeof(float) * d2h_words, hipHostMallocDefault));
+  HIP_TRY(hipDeviceSynchronize());        // the memset ran on the null stream, which the lanes' streams do not wait for
+  f.keep = true;
+  (void)hipFree(p->d_all);
+  p->d_all = f.d_all;
+  for (int k = 0; k < K; ++k)
+    for (int set = 0; set < 2; ++set) { (void)hipHostFree(p->lanes[k].pin_out[set]); p->lanes[k].pin_out[set] = f.pin[(size_t)2 * k + set]; }
+  p->o_bkb = bl.o_bkb; p->o_blb = bl.o_blb; p->o_bnp = bl.o_bnp; p->o_bnb = bl.o_bnb; p->o_bno = bl.o_bno;
+  p->d2h_words = d2h_words; p->o_idx = d2h_words; p->blk_words = blk_words;
+  return quad_refill_pairs(p);
 }
 
 // one submit: H2D, undistort, NetVLAD beside SuperPoint, compaction, ONE matcher launch, remap, ONE D2H -- all on the lane's streams
@@ -416,6 +484,35 @@ int quad_pass(d2fe_quad_pipe_s* p, const uint8_t* raw, int stride, size_t cam_st
                                                  reinterpret_cast<uint8_t*>(B + p->o_nbst), s)
                  : d2fe_lk_carry_neighbour_device(L.ctx, pyr, p->pyr_total, Q, W, H, p->cfg.undistort_fov, lists, p->list_words, p->D, &p->tp, B + p->o_nbxy,
                                                   reinterpret_cast<uint8_t*>(B + p->o_nbst), s);
+    if (rc) return rc;
+  }
+  if (p->bear) {
+    // the bearings of the pass's keypoint rows and list entries, the neighbour predictions and their gates: ONE launch over 4 Q lists per segment; row / list
+    // (q, c) takes camera c, pair (q, n) the list of its camera a, cameras a and b and extrinsic n
+    const size_t cap = (size_t)p->cap, T = (size_t)p->capT;
+    BearSeg seg[3];
+    int ns = 0;
+    BearSeg& kp = seg[ns++];
+    kp = BearSeg{};
+    kp.pts = B + p->o_kps; kp.pts_stride = cap * 2; kp.n = cnt; kp.n_stride = 1; kp.cap = p->cap; kp.by4 = 1;
+    for (int c = 0; c < 4; ++c) { kp.cam[c] = (unsigned char)c; kp.src[c] = (unsigned char)c; }
+    kp.bearing = reinterpret_cast<double*>(B + p->o_bkb); kp.bearing_step = 1;
+    if (p->trk || p->flow) {
+      const float* lists = B + p->o_list;
+      BearSeg& tl = seg[ns++];
+      tl = kp;
+      tl.pts = lists + (p->flow ? d2fe_lk_flow_list_offset(p->capT, D2FE_LKC_PTS) : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_PTS)); tl.pts_stride = p->list_words;
+      tl.n = reinterpret_cast<const int32_t*>(lists + (p->flow ? 0 : d2fe_lk_carry_list_offset(p->capT, p->D, D2FE_LKC_HDR))); tl.n_stride = p->list_words;
+      tl.cap = p->capT;
+      tl.bearing = reinterpret_cast<double*>(B + p->o_blb);
+      BearSeg& nb = seg[ns++];
+      nb = tl;
+      for (int n = 0; n < 4; ++n) { nb.cam[n] = nb.src[n] = (unsigned char)NB[n][0]; nb.ocam[n] = (unsigned char)NB[n][1]; nb.ext[n] = (unsigned char)n; }
+      nb.bearing = nullptr; nb.pred = B + p->o_bnp;
+      nb.other = B + p->o_nbxy; nb.other_stride = T * 2; nb.status = reinterpret_cast<const uint8_t*>(B + p->o_nbst); nb.status_stride = T;
+      nb.other_bearing = reinterpret_cast<double*>(B + p->o_bnb); nb.pred_ok = reinterpret_cast<uint8_t*>(B + p->o_bno);
+    }
+    rc = bearings_launch(L.ctx, p->bcams, NI, seg, ns, s);
     if (rc) return rc;
   }
   if (p->trk) {
@@ -535,7 +632,7 @@ int d2fe_quad_pipe_create(d2fe_handle h, const d2fe_quad_pipe_config* cfg, const
   p->o_mq = o; o += up64(NP * cap);
   p->o_mt = o; o += up64(NP * cap);
   p->o_md = o; o += up64(NP * cap);
-  p->d2h_words = o;
+  p->d2h_words = p->base_words = p->lists_end = o;
   p->o_idx = o; o += up64(NI * cap);
   p->blk_words = o;
   o = 0;
@@ -765,6 +862,65 @@ int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_r
   out->quads = p->Q;
   flow_list_view(out, B + p->o_list, p->capT, p->list_words);
   out->nb_lk_xy = B + p->o_nbxy; out->nb_lk_status = reinterpret_cast<const uint8_t*>(B + p->o_nbst);
+  return D2FE_OK;
+}
+
+void d2fe_quad_bearings_default(d2fe_quad_bearings* b) {
+  memset(b, 0, sizeof(*b));
+  b->struct_size = (int32_t)sizeof(d2fe_quad_bearings);
+  b->lk_use_pred = 1;
+  b->distance = 100.0;
+  for (int n = 0; n < 4; ++n) b->T_nb[n][0] = b->T_nb[n][5] = b->T_nb[n][10] = 1.0;
+}
+
+int d2fe_quad_bearings_enable(d2fe_quad_pipe p, const d2fe_quad_bearings* b) {
+  if (!p || !b) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  if (b->struct_size != (int32_t)sizeof(d2fe_quad_bearings)) return ctx_fail(D2FE_ERR_INVALID, "d2fe_quad_bearings size mismatch");
+  for (int c = 0; c < 4; ++c)
+    if (const char* why = bearings_check_camera(&b->cam[c])) return ctx_fail(D2FE_ERR_INVALID, "cam[" + std::to_string(c) + "]: " + why);
+  if (!(b->distance - b->distance == 0.0)) return ctx_fail(D2FE_ERR_INVALID, "distance must be finite");
+  for (int n = 0; n < 4; ++n)
+    for (int i = 0; i < 12; ++i) if (!(b->T_nb[n][i] - b->T_nb[n][i] == 0.0)) return ctx_fail(D2FE_ERR_INVALID, "T_nb must be finite");
+  if (b->radius_lk != b->radius_lk) return ctx_fail(D2FE_ERR_INVALID, "radius_lk must not be NaN");
+  if (b->lk_use_pred != 0 && b->lk_use_pred != 1) return ctx_fail(D2FE_ERR_INVALID, "lk_use_pred must be 0 or 1");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (p->next_ticket > 0) return ctx_fail(D2FE_ERR_INVALID, "the bearings are switched on before the first submit");
+  if (p->bear) return ctx_fail(D2FE_ERR_INVALID, "the bearings are already switched on");
+  HIP_TRY(hipSetDevice(p->parent->cfg.device_id));
+  const int rc = quad_bear_blocks(p);
+  if (rc != D2FE_OK && !p->failed) return rc;      // nothing has changed
+  p->bear = true;
+  p->bcams = BearCams{};
+  for (int c = 0; c < 4; ++c) p->bcams.cam[c] = bearings_make_camera(b->cam[c]);
+  for (int n = 0; n < 4; ++n)
+    for (int i = 0; i < 12; ++i) p->bcams.T[n][i] = b->T_nb[n][i];
+  p->bcams.distance = b->distance;
+  p->bcams.radius = b->lk_use_pred ? b->radius_lk : 0.0;
+  return rc;
+}
+
+int d2fe_quad_bearings_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_bearings_result* out) {
+  if (!p || !out) return ctx_fail(D2FE_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof(*out));
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (!p->bear) return ctx_fail(D2FE_ERR_UNSUPPORTED, "d2fe_quad_bearings_enable was not called on this pipe: it computes no bearings");
+  if (p->failed) return ctx_fail(p->failed, "the quad pipe failed in an earlier call (destroy it): " + p->failed_msg);
+  if (ticket < 0 || ticket >= p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "unknown ticket");
+  if (ticket + 2 * p->K < p->next_ticket) return ctx_fail(D2FE_ERR_INVALID, "the ticket's result block has been reused: read the bearings within 2 * lanes submits");
+  const int k = (int)(ticket % p->K), set = (int)((ticket / p->K) & 1);
+  const auto& L = p->lanes[k];
+  if (L.synced < ticket) return ctx_fail(D2FE_ERR_NOT_READY, "d2fe_quad_pipe_wait has not returned this ticket yet");
+  const float* B = L.pin_out[set];
+  const bool lists = p->trk || p->flow;
+  out->quads = p->Q; out->cap = p->cap; out->cap_tracks = lists ? p->capT : 0;
+  out->kp_bearing = reinterpret_cast<const double*>(B + p->o_bkb);
+  if (lists) {
+    out->list_bearing = reinterpret_cast<const double*>(B + p->o_blb);
+    out->nb_pred_xy = B + p->o_bnp;
+    out->nb_bearing = reinterpret_cast<const double*>(B + p->o_bnb);
+    out->nb_pred_ok = reinterpret_cast<const uint8_t*>(B + p->o_bno);
+  }
   return D2FE_OK;
 }
 

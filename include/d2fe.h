@@ -542,15 +542,29 @@ D2FE_API int d2fe_depth_at_device(d2fe_handle h, const uint16_t* d_depth, int wi
  *   gate        trackLK(left, right) with lk_lk_use_pred (:742-744): pred_ok[i] = status[i] && (radius <= 0 || cv::norm(pred[i] - other[i]) < radius), cv::norm on
  *               Point2f (float differences, sqrt of the double sum of squares); a NaN prediction fails `<` and is dropped.  other_bearing = the lift of the other
  *               point with the SECOND camera (createLKLandmark(right_frame, ...)).
- * Camera models: pinhole + radtan (PinholeCamera.cc:337-418) and MEI (CataCamera.cc:425-515); the cylindrical model of the quadcam views is not served.
- * Arithmetic contract: fp64, operation by operation in the order of the host restatements of include/d2fe.hpp (liftProjectivePinhole, liftProjectiveMEI, fillLandmarks,
- * predictWithExtrinsic, spaceToPlanePinhole, spaceToPlaneMEI); no contraction.  The device's fp64 sqrt and divide are the only operations that may differ from the
- * host's, by the last bit of their own result. */
-typedef enum { D2FE_CAM_PINHOLE = 0, D2FE_CAM_MEI = 1 } d2fe_camera_kind;
+ * Camera models: pinhole + radtan (PinholeCamera.cc:337-418), MEI (CataCamera.cc:425-515) and the cylindrical model of the quadcam views
+ * (CylindricalCamera.cc:207-238, the virtual camera of FisheyeUndist with enable_undistort_image).
+ * Arithmetic contract: fp64, operation by operation in the order of the host restatements of include/d2fe.hpp (liftProjectivePinhole, liftProjectiveMEI,
+ * liftProjectiveCylindrical, fillLandmarks, predictWithExtrinsic, spaceToPlanePinhole, spaceToPlaneMEI, spaceToPlaneCylindrical); no contraction.  For the first two
+ * models the device's fp64 sqrt and divide are the only operations that may differ from the host's, by the last bit of their own result.
+ * D2FE_CAM_CYLINDRICAL, one operation per line:
+ *   lift          phi = iK11 * x + iK13;  ybr = iK22 * y + iK23;  z = fabs(phi) > M_PI / 2 ? -1.0 : 1.0;  X = z * tan(phi);  rho = sqrt(X * X + z * z);  Y = ybr * rho;
+ *                 then (X, Y, z) / sqrt(X * X + Y * Y + z * z) as for the other models; iK11 = 1 / fx, iK13 = -cx / fx, iK22 = 1 / fy, iK23 = -cy / fy from the host
+ *   spaceToPlane  rho = sqrt(X * X + Z * Z);  phi = atan2(X, Z);  a = rho * phi;  uh = (fx * a + 0.0 * Y) + cx * rho;  vh = (0.0 * a + fy * Y) + cy * rho;
+ *                 w = (0.0 * a + 0.0 * Y) + 1.0 * rho;  u = uh / w;  v = vh / w -- K * (a, Y, rho) with the K of the constructor FisheyeUndist calls
+ *                 (CylindricalCamera.cc:138-150), zero terms kept: a non-finite Y reaches u as it does through the matrix product.  A point on the axis (rho = 0) gives u = NaN and v = +-inf (NaN for Y = 0).
+ *   tan and atan2 are the device math library's; like the device's sqrt and divide they may differ from the host's in the last bits of their own result, and the
+ *   bound the tests hold the bearings to allows for it. */
+typedef enum { D2FE_CAM_PINHOLE = 0, D2FE_CAM_MEI = 1, D2FE_CAM_CYLINDRICAL = 3 /* 2 is not a kind and is refused */ } d2fe_camera_kind;
 typedef struct {
   int32_t kind, reserved;   /* d2fe_camera_kind; 0 */
-  double p[9];              /* PINHOLE: fx fy cx cy k1 k2 p1 p2, p[8] = 0;  MEI: the nine doubles of d2fe_mei_camera in its order (xi k1 k2 p1 p2 gamma1 gamma2 u0 v0) */
+  double p[9];              /* PINHOLE: fx fy cx cy k1 k2 p1 p2, p[8] = 0;  MEI: the nine doubles of d2fe_mei_camera in its order (xi k1 k2 p1 p2 gamma1 gamma2 u0 v0);
+                               CYLINDRICAL: fx fy cx cy, p[4..8] = 0 */
 } d2fe_camera;
+/* The virtual camera d2fe_gen_cylinder_map assumes for a width x height view of fov_deg degrees (FisheyeUndist, fisheye_undistort.h:492-495): kind
+ * D2FE_CAM_CYLINDRICAL, fx = fy = the generator's own focal length (double)width / (fov_deg * (pi / 180)), cx = width / 2, cy = height / 2 (integer halves).  Host
+ * function, no device needed.  D2FE_ERR_INVALID: out NULL, width or height < 1, fov_deg not positive. */
+D2FE_API int d2fe_cylinder_camera(int width, int height, double fov_deg, d2fe_camera* out);
 /* T_b_a [3][4] row-major, the transform that takes a point of frame a into frame b, from the two poses (unit quaternion w x y z, translation) of a and b in a common
  * frame: R(q) by the standard unit-quaternion formula after q /= sqrt(w*w + x*x + y*y + z*z), T_b_a = [R_b^T R_a | R_b^T (t_a - t_b)], every dot product summed left
  * to right.  Host function, no device needed.  This is the library's OWN arithmetic: the reference takes the matrix from Swarm::Pose (swarm_msgs, not in its tree), so
@@ -561,7 +575,8 @@ D2FE_API int d2fe_relative_extrinsic(const double* q_a_wxyz, const double* t_a, 
  * T (HOST, [12] row-major 3 x 4; NULL: no prediction) and d_pred_xy [n_lists][cap][2] floats (NULL: no prediction).  The gate's four pointers are given together or all
  * NULL, and need d_pred_xy, T and cam_other: d_other_xy [n_lists][cap][2], d_other_status [n_lists][cap], d_other_bearing [n_lists][cap][3] doubles, d_pred_ok
  * [n_lists][cap].  Every slot >= d_n[l] is written as zero in every output.  D2FE_ERR_INVALID: null arguments, cap outside 1..16384, n_lists outside 1..32767,
- * pts_stride < 2 * cap with more than one list, an unknown kind, fx / fy / gamma1 / gamma2 zero or not finite, distance or T not finite, gate outputs without d_pred_xy. */
+ * pts_stride < 2 * cap with more than one list, an unknown kind (2 among them), fx / fy / gamma1 / gamma2 zero or not finite, a cylindrical camera with a non-zero
+ * p[4..8], distance or T not finite, gate outputs without d_pred_xy. */
 D2FE_API int d2fe_bearings_device(d2fe_handle h, const d2fe_camera* cam, const d2fe_camera* cam_other /*NULL*/, const double* T /*NULL: no prediction*/, double distance,
                                   const float* d_pts_xy, size_t pts_stride, const int32_t* d_n, int n_lists, int cap, double* d_bearing, float* d_pred_xy /*NULL*/,
                                   const float* d_other_xy, const uint8_t* d_other_status, double radius, double* d_other_bearing,
@@ -580,7 +595,7 @@ D2FE_API int d2fe_bearings_device(d2fe_handle h, const d2fe_camera* cam, const d
  * prediction keeps the match).  The new arrays sit at the end of the region in front of d2h_words (inside the pass's one D2H); every existing offset, the device views and
  * the exchanges' reads are unchanged, every other result is bit-identical, and a pipe that never enables the mode keeps its layout, allocations and launches.
  * With the caller: the NaN skip, lmanager ids, velocities, lm.depth = (pt3d_norm * dep).norm(), motion prediction from lmanager positions
- * (use_extrinsic = false), check_essential, the quad pipe and the cylindrical model. */
+ * (use_extrinsic = false), check_essential.  The quad pipe has the same pass as d2fe_quad_bearings_enable. */
 typedef struct {
   int32_t struct_size;      /* sizeof(d2fe_pipe_bearings), checked strictly */
   int32_t lk_use_pred;      /* lk_lk_use_pred (d2featuretracker.h:62), default 1; 0: pred_ok = status */
@@ -1138,8 +1153,8 @@ D2FE_API int d2fe_quad_pipe_geometry(d2fe_quad_pipe p, int32_t* quads, int32_t* 
  * block (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the conventions of d2fe_pipe_track_result: n[(q * 4 + c) * list_words], ...); the list
  * of camera a that a neighbour pair tracks and matches is the list AFTER this frame's step.  d2fe_quad_pipe_result and its nb_* / prev_* stay keypoint-based,
  * governed by match_neighbour / match_prev (the reference's configuration of this mode has both off).  Results are bit-identical for every (lanes, quads).
- * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate -- the bearings mode of the stereo
- * pipe (d2fe_pipe_bearings_enable) does not extend to the quad pipe: its views use the cylindrical model, which d2fe_bearings_device does not serve. */
+ * With the caller: id -> lmanager ids and velocities.  createLKLandmark / liftProjective, predictLandmarksWithExtrinsic and the lk_lk_use_pred gate
+ * of the neighbour tracks run on the device once d2fe_quad_bearings_enable has switched them on (below), and are the caller's otherwise. */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
   int32_t quads, cap_tracks, desc_dim, list_words;
   const int32_t* n;                  /* per list: list (q, c)'s count is n[(q * 4 + c) * list_words]; the same stride for every "per list" pointer below */
@@ -1170,8 +1185,8 @@ D2FE_API int d2fe_quad_track_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_q
  * mode's matchKNN.  d2fe_quad_flow_result_get after d2fe_quad_pipe_wait (D2FE_ERR_NOT_READY before it, D2FE_ERR_UNSUPPORTED on a pipe without the mode): list (q, c)
  * is (q * 4 + c) * list_words 32-bit words behind every per-list pointer (the convention of d2fe_quad_track_result); the list of camera a that a neighbour pair
  * tracks is the list AFTER this frame's step.  Results are bit-identical for every (lanes, quads).
- * With the caller: id -> lmanager ids, createLKLandmark / liftProjective, velocities, the lk_lk_use_pred gate (d2fe_pipe_bearings_enable is the
- * stereo / mono pipe's; the cylindrical model of the quad views is not served). */
+ * With the caller: id -> lmanager ids and velocities.  createLKLandmark / liftProjective, predictLandmarksWithExtrinsic and the lk_lk_use_pred gate
+ * of the neighbour tracks run on the device once d2fe_quad_bearings_enable has switched them on (below), and are the caller's otherwise. */
 typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
   int32_t quads, cap_tracks, list_words, reserved;
   const int32_t *n, *n_tracked_in, *n_lost, *n_removed_near, *n_new, *lack, *num, *n_cand;      /* per list */
@@ -1182,6 +1197,42 @@ typedef struct {            /* HOST pointers into the lane's pinned block, same 
 } d2fe_quad_flow_result;
 D2FE_API int d2fe_quad_flow_enable(d2fe_quad_pipe p, const d2fe_flow_params* fp);
 D2FE_API int d2fe_quad_flow_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_flow_result* out);
+/* Bearings, neighbour predictions and their gate IN THE QUAD PIPE: d2fe_pipe_bearings_enable's pass and contract (above) for the four cameras of the quad rig, whose
+ * views with enable_undistort_image are D2FE_CAM_CYLINDRICAL (d2fe_cylinder_camera); any kind d2fe_bearings_device serves is taken.  Accepted once, before the first
+ * submit, in any order with d2fe_quad_track_enable / d2fe_quad_flow_enable.  Refused (D2FE_ERR_INVALID, the pipe stays as it was and usable): a wrong struct_size,
+ * after the first submit, a second time, what d2fe_bearings_device refuses in a camera, distance or T_nb not finite, radius_lk NaN, lk_use_pred not 0 or 1.
+ * Per pass ONE more launch (bearings_kernel, D2FE_PROF_LK) behind the list chain and the neighbour LK launch, in front of the matcher:
+ *   keypoint rows      bearing of row (q, c) with cam[c]
+ *   list entries       (sp_lk or flow_lk) bearing of list (q, c) AFTER this frame's step with cam[c]
+ *   neighbour pairs    (sp_lk or flow_lk) pair n = (a, b) of (0,1) (1,2) (2,3) (0,3): entry i of list (q, a) predicted into camera b through T_nb[n] and projected with
+ *                      cam[a] -- the reference's cams.at(left camera_index) quirk, kept as in the stereo pipe --, the lift of nb_lk_xy with cam[b], and the gate
+ *                      nb_pred_ok[i] = nb_lk_status[i] && (radius_lk <= 0 || !lk_use_pred || cv::norm(pred - nb_lk_xy) < radius_lk) (trackLK(left, right, type),
+ *                      d2featuretracker.cpp:720-747).  List 0 is the left list of pairs 0 and 3 and is predicted twice: the arrays are per pair.
+ * No keypoint predictions: matchLocalFeatures computes them for neighbour pairs but its half-image branch never uses them (:1144-1173); nb_* / prev_* stay as they are.
+ * The new arrays sit at the end of the region in front of d2h_words (inside the pass's one D2H), behind the lists' arrays whichever enable came first; every other
+ * result is bit-identical, and a pipe that never enables the mode keeps its layout, allocations and launches.
+ * With the caller: the NaN skip, lmanager ids, velocities and colours, motion prediction from lmanager positions, check_essential. */
+typedef struct {
+  int32_t struct_size;      /* sizeof(d2fe_quad_bearings), checked strictly */
+  int32_t lk_use_pred;      /* lk_lk_use_pred, default 1; 0: nb_pred_ok = nb_lk_status */
+  d2fe_camera cam[4];       /* camera c of the rig */
+  double T_nb[4][12];       /* pair n = (a, b) in the pipe's order (0,1) (1,2) (2,3) (0,3): takes a point of camera a into camera b (d2fe_relative_extrinsic) */
+  double distance;          /* landmark_distance_assumption, default 100 */
+  double radius_lk;         /* search_local_max_dist_lr * width; <= 0: nb_pred_ok = nb_lk_status */
+} d2fe_quad_bearings;
+D2FE_API void d2fe_quad_bearings_default(d2fe_quad_bearings* b);      /* struct_size, lk_use_pred = 1, distance = 100, every T_nb = identity, everything else 0 */
+D2FE_API int d2fe_quad_bearings_enable(d2fe_quad_pipe p, const d2fe_quad_bearings* b);
+/* The bearings of a ticket that d2fe_quad_pipe_wait has returned (D2FE_ERR_NOT_READY before that, D2FE_ERR_UNSUPPORTED on a pipe without the mode).  Every array is
+ * contiguous; slots >= n hold zeros. */
+typedef struct {            /* HOST pointers into the lane's pinned block, same lifetime as d2fe_quad_pipe_result */
+  int32_t quads, cap, cap_tracks, reserved;      /* cap_tracks: of the lists the pipe carries (sp_lk or flow_lk), 0 without them */
+  const double* kp_bearing;          /* [quads][4][cap][3], the rows of d2fe_quad_pipe_result::kps_xy */
+  const double* list_bearing;        /* [quads][4][cap_tracks][3]: list (q, c); NULL without lists, as the three below */
+  const float* nb_pred_xy;           /* [quads][4][cap_tracks][2]: pair n, entry i of list a predicted into camera b */
+  const double* nb_bearing;          /* [quads][4][cap_tracks][3]: the lift of nb_lk_xy with cam[b] */
+  const uint8_t* nb_pred_ok;         /* [quads][4][cap_tracks]: the gate on nb_lk_status */
+} d2fe_quad_bearings_result;
+D2FE_API int d2fe_quad_bearings_result_get(d2fe_quad_pipe p, int64_t ticket, d2fe_quad_bearings_result* out);
 /* The pipe's undistort step on its own: ONE launch for 4 cameras x quads raw frames (image (q, c) at d_raw + q * quad_stride + c * camera_stride), maps
  * as above with device = 1 and every map pointer 16-byte aligned; view (q, c) is written to d_dst + (q * 4 + c) * dw * dh.  Same bytes as
  * d2fe_undistort_device camera by camera. */

@@ -451,6 +451,16 @@ struct QuadFlowNeighbourTracks {
   std::vector<Point2f> lk;
   std::vector<uint8_t> lk_status;
 };
+// bearingsEnable() (d2fe_quad_bearings_enable): unit bearings as [n][3] doubles (x, y, z of entry i at 3 i), computed on the device.  One per view (q, c): kp of the
+// view's keypoints, list of its list entries (trackEnable / flowEnable; empty without).  One per neighbour pair (q, n) = (a, b): pred[i] is entry i of list a
+// predicted into camera b through T_nb[n] (projected with camera a, as the reference does), nb the bearing of the neighbour track lk[i] with camera b, pred_ok the
+// lk_lk_use_pred gate on lk_status.  A NaN bearing is returned as it is: the hasNaN() skip of createLKLandmark stays with the caller
+struct QuadViewBearings { std::vector<double> kp, list; };
+struct QuadNeighbourBearings {
+  std::vector<Point2f> pred;
+  std::vector<double> nb;
+  std::vector<uint8_t> pred_ok;
+};
 
 // d2fe_quad_pipe_* (quadcam frames in flight, include/d2fe.h) with the lifetime of a C++ object; submit / wait go through get()
 class QuadPipe {
@@ -520,6 +530,34 @@ class QuadPipe {
       const int n = fr.n[(i / 4 * 4 + view_a[i % 4]) * lw];
       for (int j = 0; j < n; ++j) t.lk.emplace_back(fr.nb_lk_xy[(i * T + j) * 2], fr.nb_lk_xy[(i * T + j) * 2 + 1]);
       t.lk_status.assign(fr.nb_lk_status + i * T, fr.nb_lk_status + i * T + n);
+    }
+    return true;
+  }
+  // d2fe_quad_bearings_enable: once, before the first submit, in any order with trackEnable / flowEnable; b: d2fe_quad_bearings_default + the four cameras
+  // (d2fe_cylinder_camera for the undistorted views), the four neighbour extrinsics (d2fe_relative_extrinsic), distance and radius_lk
+  bool bearingsEnable(const d2fe_quad_bearings& b) {
+    if (!p_ || d2fe_quad_bearings_enable(p_, &b) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_bearings_enable: %s\n", d2fe_last_error()); return false; }
+    return true;
+  }
+  // the bearings of a ticket that d2fe_quad_pipe_wait has returned: views[q * 4 + c], pairs[q * 4 + n] (empty on a pipe without lists); n_kp / n_list: the counts of the
+  // views' keypoints and list entries (d2fe_quad_pipe_result::n_kp; the lists' n, nullptr without lists)
+  bool bearings(int64_t ticket, const int32_t* n_kp, const int32_t* n_list, size_t n_list_stride, std::vector<QuadViewBearings>& views,
+                std::vector<QuadNeighbourBearings>& pairs) const {
+    d2fe_quad_bearings_result br;
+    if (!p_ || d2fe_quad_bearings_result_get(p_, ticket, &br) != D2FE_OK) { std::fprintf(stderr, "[d2fe] d2fe_quad_bearings_result_get: %s\n", d2fe_last_error()); return false; }
+    static const int view_a[4] = {0, 1, 2, 0};
+    const size_t cap = (size_t)br.cap, T = (size_t)br.cap_tracks;
+    views.assign((size_t)4 * br.quads, QuadViewBearings()); pairs.assign(br.list_bearing && n_list ? (size_t)4 * br.quads : 0, QuadNeighbourBearings());
+    for (size_t i = 0; i < views.size(); ++i) {
+      views[i].kp.assign(br.kp_bearing + i * cap * 3, br.kp_bearing + (i * cap + (size_t)n_kp[i]) * 3);
+      if (br.list_bearing && n_list) views[i].list.assign(br.list_bearing + i * T * 3, br.list_bearing + (i * T + (size_t)n_list[i * n_list_stride]) * 3);
+    }
+    for (size_t i = 0; i < pairs.size(); ++i) {
+      QuadNeighbourBearings& t = pairs[i];
+      const size_t n = (size_t)n_list[(i / 4 * 4 + view_a[i % 4]) * n_list_stride];
+      for (size_t j = 0; j < n; ++j) t.pred.emplace_back(br.nb_pred_xy[(i * T + j) * 2], br.nb_pred_xy[(i * T + j) * 2 + 1]);
+      t.nb.assign(br.nb_bearing + i * T * 3, br.nb_bearing + (i * T + n) * 3);
+      t.pred_ok.assign(br.nb_pred_ok + i * T, br.nb_pred_ok + i * T + n);
     }
     return true;
   }
@@ -836,6 +874,19 @@ inline Vec3d liftProjectiveCylindrical(double fx, double fy, double cx, double c
   const double z = std::fabs(phi) > M_PI / 2 ? -1.0 : 1.0;
   const double x = z * std::tan(phi);
   return Vec3d{x, y_by_rho * std::sqrt(x * x + z * z), z};
+}
+// CylindricalCamera::spaceToPlane (CylindricalCamera.cc:228-238): K * (rho * phi, Y, rho) and the division by the third row, with the K of the constructor
+// FisheyeUndist calls (:138-150: fx 0 cx / 0 fy cy / 0 0 1).  The zero entries are multiplied out as Eigen's product does, so a non-finite Y reaches u as well; a point
+// on the axis (rho = 0) gives u = NaN and v = +-inf.  A restatement: unlike the lift, this function of the reference is not compiled anywhere in this repository's checks
+inline void spaceToPlaneCylindrical(double fx, double fy, double cx, double cy, const Vec3d& P, double& u, double& v) {
+  const double rho = std::sqrt(P.x * P.x + P.z * P.z);
+  const double phi = std::atan2(P.x, P.z);
+  const double a = rho * phi;
+  const double uh = (fx * a + 0.0 * P.y) + cx * rho;
+  const double vh = (0.0 * a + fy * P.y) + cy * rho;
+  const double w = (0.0 * a + 0.0 * P.y) + 1.0 * rho;
+  u = uh / w;
+  v = vh / w;
 }
 
 struct Landmark { Point2f pt2d; Vec3d pt3d_norm; int index = -1; };   // index = position of the keypoint (and of its descriptor)
