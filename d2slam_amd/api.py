@@ -272,6 +272,7 @@ _dev_lib = None
 
 EXPORTS = [
     "d2fe_last_error", "d2fe_version", "d2fe_default_config", "d2fe_create", "d2fe_destroy", "d2fe_load_superpoint", "d2fe_set_superpoint_pca", "d2fe_set_superpoint_int8_ranges",
+    "d2fe_calib_create", "d2fe_calib_collect", "d2fe_calib_freeze", "d2fe_calib_stats_get", "d2fe_calib_ranges", "d2fe_calib_destroy",
     "d2fe_desc_dim", "d2fe_superpoint_extract", "d2fe_superpoint_extract_batch", "d2fe_superpoint_extract_device", "d2fe_extract_all",
     "d2fe_extract_all_batch", "d2fe_tail_stream", "d2fe_superpoint_wait_tail", "d2fe_load_netvlad", "d2fe_set_netvlad_pca", "d2fe_netvlad_dim",
     "d2fe_netvlad", "d2fe_netvlad_batch", "d2fe_netvlad_device", "d2fe_match_knn", "d2fe_match_crosscheck", "d2fe_match_batch_device",
@@ -312,7 +313,8 @@ DEBUG_EXPORTS = [
     "d2fe_debug_pack_netvlad", "d2fe_debug_netvlad_tile", "d2fe_debug_conv3x3_wino", "d2fe_debug_match_stamps",
     "d2fe_debug_netvlad_plan", "d2fe_debug_netvlad_shapes", "d2fe_debug_netvlad_features", "d2fe_debug_netvlad_groups", "d2fe_debug_netvlad_slots", "d2fe_debug_regime_counts", "d2fe_debug_regime_reset",
     "d2fe_debug_softmax_cand", "d2fe_debug_select_b", "d2fe_debug_sample_b", "d2fe_debug_sample_b_pca", "d2fe_debug_nms2_a",
-    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a", "d2fe_debug_conv_layer", "d2fe_debug_conv_layer_q", "d2fe_debug_conv1a"]
+    "d2fe_debug_desc_head_sparse", "d2fe_debug_sample_a", "d2fe_debug_conv_layer", "d2fe_debug_conv_layer_q", "d2fe_debug_conv1a",
+    "d2fe_debug_calib_ranges_from_hist", "d2fe_debug_calib_stats", "d2fe_debug_calib_conv1a"]
 # enum d2fe_regime of include/d2fe_debug.h, in order: launches per size-dependent code path (the last two entries are the grid and the item count of the
 # most recent Winograd launch, not counts)
 REGIMES = ["wino_nt1_one", "wino_nt1_static", "wino_nt1_claimed", "wino_nt2_one", "wino_nt2_static", "wino_nt2_claimed_ring", "wino_nt2_claimed_fused1b",
@@ -380,7 +382,16 @@ def _open_library(path, dev):
             lib.d2fe_debug_conv_layer.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
             lib.d2fe_debug_conv_layer_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float]
             lib.d2fe_debug_conv1a.argtypes = [vp, ci, vp, ci, C.c_longlong, C.c_longlong, ci, ci, ci, vp, vp, vp, C.c_longlong]
+            lib.d2fe_debug_calib_ranges_from_hist.argtypes = [vp, ci, C.c_float, ci, C.c_double, vp, vp]
+            lib.d2fe_debug_calib_stats.argtypes = [vp, vp, C.c_longlong, ci, ci, ci, C.c_float, ci, ci, ci, vp, vp, vp, vp]
+            lib.d2fe_debug_calib_conv1a.argtypes = [vp, vp, ci, C.c_longlong, C.c_longlong, ci, ci, ci, vp, vp, C.c_float, ci, ci, vp, vp, vp, vp]
         lib.d2fe_destroy.restype = None
+        lib.d2fe_calib_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.d2fe_calib_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]
+        lib.d2fe_calib_freeze.argtypes = [C.c_void_p]
+        lib.d2fe_calib_stats_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.d2fe_calib_ranges.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        lib.d2fe_calib_destroy.argtypes = [C.c_void_p]; lib.d2fe_calib_destroy.restype = None
         lib.d2fe_half_move_cols.restype = C.c_float
         lib.d2fe_half_move_cols.argtypes = [C.c_int, C.c_double]
         lib.d2fe_default_config.restype = None
@@ -1246,6 +1257,46 @@ class DevFrontEnd(FrontEnd):
                                            _ptr(b1a), _ptr(out), out.size))
         return out
 
+    # ---- the calibration session's parts on injected data (include/d2fe_debug.h; tests/test_calib_cpu.py, tests/test_calib_edges.py) ----
+    @staticmethod
+    def calib_ranges_from_hist(hist, t, method, param=None):
+        """d2fe_debug_calib_ranges_from_hist: the host rule of d2fe_calib_ranges on one histogram (u64 [n_bins]) of a tensor with range t.  -> (range as
+        np.float32, index: ENTROPY the winning candidate, PERCENTILE b + 1, MINMAX and an empty histogram n_bins).  Needs no handle and no GPU."""
+        lib = load_library(dev=True)
+        hist = np.ascontiguousarray(hist, np.uint64)
+        r, k = C.c_float(), C.c_int()
+        _check(lib.d2fe_debug_calib_ranges_from_hist(_ptr(hist), int(hist.size), float(t), calib_method(method), float(0.0 if param is None else param),
+                                                     C.byref(r), C.byref(k)))
+        return np.float32(r.value), int(k.value)
+
+    @staticmethod
+    def _calib_out(n_bins, acc):
+        if acc is not None:
+            return [np.array(a, dt).reshape(-1) for a, dt in zip(acc, (np.uint32, np.uint64, np.uint64, np.uint64))]
+        return [np.zeros(1, np.uint32), np.zeros(int(n_bins), np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint64)]
+
+    def debug_calib_stats(self, tensor, ch_off, channels, t, n_bins, phase, wgs=0, acc=None):
+        """d2fe_debug_calib_stats: calib_stats_kernel on tensor [pixels, ch_stride] f32, channels ch_off .. ch_off + channels.  phase 0: the range phase, 1: the
+        histogram phase with T = t.  acc: the (t_max_bits, hist, n_zero, n_over) of an earlier call to accumulate into.  -> (t_max_bits, hist, n_zero, n_over)"""
+        self._need_dev("debug_calib_stats")
+        tensor = np.ascontiguousarray(tensor, np.float32)
+        assert tensor.ndim == 2
+        o = self._calib_out(n_bins, acc)
+        _check(self._lib.d2fe_debug_calib_stats(self._h, _ptr(tensor), tensor.shape[0], int(ch_off), int(channels), tensor.shape[1], float(t), int(n_bins), int(phase),
+                                                int(wgs), *[_ptr(a) for a in o]))
+        return int(o[0][0]), o[1], int(o[2][0]), int(o[3][0])
+
+    def debug_calib_conv1a(self, frames, img_stride, img_istride, n, H, W, w1a, b1a, t, n_bins, phase, acc=None):
+        """d2fe_debug_calib_conv1a: calib_conv1a_stats_kernel on injected frames and weights (as debug_conv1a takes them); outputs as debug_calib_stats"""
+        self._need_dev("debug_calib_conv1a")
+        frames = np.ascontiguousarray(frames, np.uint8)
+        w1a = np.ascontiguousarray(w1a, np.float32); b1a = np.ascontiguousarray(b1a, np.float32)
+        assert w1a.shape == (64, 1, 3, 3) and b1a.shape == (64,)
+        o = self._calib_out(n_bins, acc)
+        _check(self._lib.d2fe_debug_calib_conv1a(self._h, _ptr(frames), int(img_stride), int(img_istride), frames.size, int(n), int(H), int(W), _ptr(w1a), _ptr(b1a),
+                                                 float(t), int(n_bins), int(phase), *[_ptr(a) for a in o]))
+        return int(o[0][0]), o[1], int(o[2][0]), int(o[3][0])
+
     # ---- NetVLAD inspection (include/d2fe_debug.h; tests/test_netvlad_shapes*.py) ----
     @staticmethod
     def netvlad_shapes(family):
@@ -1333,6 +1384,65 @@ class _Owned:
             self.close()
         except Exception:
             pass
+
+
+CALIB_METHODS = {"minmax": 0, "entropy": 1, "percentile": 2}      # d2fe_calib_method of include/d2fe.h
+CALIB_PERCENTILE_DEFAULT = 99.99
+
+
+def calib_method(method):
+    return CALIB_METHODS[method] if isinstance(method, str) else int(method)
+
+
+class Int8Calibrator(_Owned):
+    """An int8 calibration session (include/d2fe.h, d2fe_calib_*) on a PREC_F32 handle with dense_descriptors and weights loaded; product library.  collect()
+    images (range phase), freeze(), collect() again (histogram phase), then ranges("entropy") -> the dict FrontEnd.set_int8_ranges takes.  n_bins 0: 2048."""
+    _HANDLE, _DESTROY = "_c", "d2fe_calib_destroy"
+
+    def __init__(self, fe: FrontEnd, n_bins=0):
+        self._lib = fe._lib
+        self._fe = fe           # the session borrows the handle
+        self._c = C.c_void_p()
+        _check(self._lib.d2fe_calib_create(fe.handle, int(n_bins), C.byref(self._c)))
+        self.n_bins = int(n_bins) or 2048
+        if not hasattr(fe, "_pipes"):      # closed with the handle's pipes, before the handle (FrontEnd.close)
+            import weakref
+            fe._pipes = weakref.WeakSet()
+        fe._pipes.add(self)
+
+    def collect(self, images):
+        """images: u8 [n, H, W] or [H, W]; n may exceed the handle's max_batch"""
+        images = np.ascontiguousarray(images, np.uint8)
+        if images.ndim == 2:
+            images = images[None]
+        n, H, W = images.shape
+        _check(self._lib.d2fe_calib_collect(self._c, _ptr(images), W, H, W, H * W, n))
+
+    def freeze(self):
+        _check(self._lib.d2fe_calib_freeze(self._c))
+
+    def stats(self, layer, hist=True):
+        """layer: a name of SP_LAYERS or its index.  -> {"t_max": np.float32, "hist": u64 [n_bins] (None before freeze() or with hist=False), "n_zero", "n_over",
+        "n_total"}"""
+        li = SP_LAYERS.index(layer) if isinstance(layer, str) else int(layer)
+        t = C.c_float()
+        h = np.zeros(self.n_bins, np.uint64) if hist else None
+        z, o, tot = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self._lib.d2fe_calib_stats_get(self._c, li, C.byref(t), _ptr(h), C.byref(z), C.byref(o), C.byref(tot))
+        if rc == -3 and hist:      # D2FE_ERR_NOT_READY: no histogram before the freeze
+            h = None
+            rc = self._lib.d2fe_calib_stats_get(self._c, li, C.byref(t), None, C.byref(z), C.byref(o), C.byref(tot))
+        _check(rc)
+        return {"t_max": np.float32(t.value), "hist": h, "n_zero": int(z.value), "n_over": int(o.value), "n_total": int(tot.value)}
+
+    def ranges(self, method="entropy", param=None):
+        """method: "minmax" | "entropy" | "percentile" (param: the percentile, default 99.99).  -> {layer name: range} in SP_LAYERS order, np.float32 values as floats"""
+        m = calib_method(method)
+        if param is None:
+            param = CALIB_PERCENTILE_DEFAULT if m == CALIB_METHODS["percentile"] else 0.0
+        r = np.zeros(len(SP_LAYERS), np.float32)
+        _check(self._lib.d2fe_calib_ranges(self._c, m, float(param), _ptr(r)))
+        return {name: float(r[i]) for i, name in enumerate(SP_LAYERS)}
 
 
 class StereoPipe(_Owned):

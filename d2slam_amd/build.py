@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libd2fe_hip.so")
-SOURCES = ["api.hip", "superpoint_host.hip", "conv.hip", "conv_f16.hip", "conv_i8.hip", "conv_pc.hip", "conv_wino.hip", "conv1x1.hip", "postproc.hip", "exact_order.hip", "match.hip", "netvlad.hip", "netvlad_fused.hip", "netvlad_pair.hip", "netvlad_host.hip", "next.hip", "swarm.hip", "lk.hip", "lk_carry.hip", "lk_flow.hip", "depth.hip", "bearings.hip", "pipe.hip", "exchange.hip", "quad_pipe.hip", "quad_exchange.hip", "loop.hip", "window.hip", "match_host.hip", "next_host.hip", "debug_hooks.hip"]
+SOURCES = ["api.hip", "superpoint_host.hip", "calib.hip", "conv.hip", "conv_f16.hip", "conv_i8.hip", "conv_pc.hip", "conv_wino.hip", "conv1x1.hip", "postproc.hip", "exact_order.hip", "match.hip", "netvlad.hip", "netvlad_fused.hip", "netvlad_pair.hip", "netvlad_host.hip", "next.hip", "swarm.hip", "lk.hip", "lk_carry.hip", "lk_flow.hip", "depth.hip", "bearings.hip", "pipe.hip", "exchange.hip", "quad_pipe.hip", "quad_exchange.hip", "loop.hip", "window.hip", "match_host.hip", "next_host.hip", "debug_hooks.hip"]
 HEADERS = ["kernels.h", "conv_common.h", "context.h", "handle_life.h", "stream_deal.h", "sp_plan.h", "lk_device.h", "lk_list_device.h", "camera_device.h", "fast_device.h", "consumer.h", "lane_ring.h", "exchange_wire.h", os.path.join("..", "..", "include", "d2fe.h"), os.path.join("..", "..", "include", "d2fe_debug.h")]
 # -ffp-contract=off: the post-processing arithmetic must follow the oracle operation by operation
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",

@@ -1,6 +1,6 @@
 """Offline calibration of D2FE_PREC_I8 (include/d2fe.h): the per-tensor dynamic ranges FrontEnd.set_int8_ranges takes.
 
-measure_ranges is the "MinMax" calibrator: the largest |value| of every layer's output tensor over a set of images, read from an exact-mode (PREC_F32) handle of
+collect_ranges runs a calibration session of the product library (MinMax, Entropy or Percentile; statistics on the device).  measure_ranges is the "MinMax" calibrator: the largest |value| of every layer's output tensor over a set of images, read from an exact-mode (PREC_F32) handle of
 the development library with the dense descriptor head through debug_read.  The reference calibrates offline as well (quadcam_tools/quantonnx.py:54-96 writes
 the table its engine loads); a caller who has such a table passes its thresholds to set_int8_ranges instead."""
 import numpy as np
@@ -38,3 +38,26 @@ def measure_ranges(weights, images, batch=8):
     finally:
         fe.close()
     return {name: max(float(np.float32(top[name])), RANGE_FLOOR) for name in api.SP_LAYERS}
+
+
+def collect_ranges(weights, images, method="entropy", param=None, n_bins=0, batch=8):
+    """The ranges by an int8 calibration session of the product library (api.Int8Calibrator; include/d2fe.h, d2fe_calib_*): the statistics are collected on the
+    device, two passes over `images` (the maxima, then the histograms; "minmax" needs the first alone), and turned into ranges by `method`: "minmax", "entropy" (the
+    reference's calibrator, quadcam_tools/quantonnx.py:66-67,84-85) or "percentile" (param: the percentile, default 99.99).  n_bins 0: 2048.
+    weights, images, batch and the result as for measure_ranges."""
+    images = np.ascontiguousarray(images, np.uint8)
+    if images.ndim == 2:
+        images = images[None]
+    n, H, W = images.shape
+    B = max(1, min(int(batch), n))
+    fe = api.FrontEnd(api.SuperPointConfig(max_keypoints=100, input_width=W, input_height=H, max_batch=B, precision=api.PREC_F32, dense_descriptors=True))
+    try:
+        fe.load_superpoint(weights)
+        cal = api.Int8Calibrator(fe, n_bins)
+        cal.collect(images)
+        if api.calib_method(method) != api.CALIB_METHODS["minmax"]:
+            cal.freeze()
+            cal.collect(images)
+        return cal.ranges(method, param)
+    finally:
+        fe.close()

@@ -295,6 +295,9 @@ namespace d2fe {
 // MobileNetVLADONNX::inference.  Both only enqueue work on the given stream(s)
 int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_kps, float* d_scores,
                    float* d_desc, int32_t* d_idx, int cap, int32_t* d_n, hipStream_t s, hipStream_t s_tail = nullptr, int bs = 0);
+// the network alone on a D2FE_PREC_F32 handle with the dense head (the calibration session, calib.hip): conv1b .. conv4b, convPa | convDa, convPb, convDb into the
+// handle's buffers -- the launches run_superpoint makes there -- and no tail.  Leaves the geometry for the debug reads as a call does
+int run_superpoint_trunk(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, hipStream_t s);
 int run_netvlad(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, float* d_out, hipStream_t s);
 int check_geometry(d2fe_context* h, int n, int W, int H, int stride, int cap);
 // why the handle's SuperPoint cannot run yet (weights not loaded; D2FE_PREC_I8: calibration ranges not set), nullptr when it can: D2FE_ERR_NOT_READY of every

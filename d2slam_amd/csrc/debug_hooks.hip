@@ -1,6 +1,6 @@
 // debug_hooks.hip -- the development library's hooks (include/d2fe_debug.h) that need nothing of the handle but its device and stream: the launch-regime
 // record, the host-side packings, one Winograd layer, one layer of the direct conv kernels and the stand-alone conv1a, the SuperPoint tail kernels, the sparse descriptor head and variant A's descriptor tail on injected
-// tensors, the count of captured launch sequences.  (The hooks that read a unit's own state back live with that state: d2fe_debug_read in
+// tensors, the calibration session's kernels and range rules (calib.hip), the count of captured launch sequences.  (The hooks that read a unit's own state back live with that state: d2fe_debug_read in
 // superpoint_host.hip, the NetVLAD ones in netvlad_host.hip, the matcher's stamps in match_host.hip.)  The whole unit compiles to nothing for the product library.
 #ifdef D2FE_DEVTOOLS
 #include <hip/hip_runtime.h>
@@ -628,6 +628,77 @@ int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost));
   return D2FE_OK;
+}
+
+// ---- the calibration session's parts (calib.hip) on injected data ----
+int d2fe_debug_calib_ranges_from_hist(const uint64_t* hist, int n_bins, float t, int method, double param, float* range, int* index) {
+  return calib_range_from_hist(reinterpret_cast<const unsigned long long*>(hist), n_bins, t, method, param, range, index);
+}
+
+namespace {
+// the in-out counters of a calibration hook on the device: uploaded from the caller's, downloaded behind the launch
+struct CalibHookOut {
+  DevPool pool;
+  CalibOut d{};
+  int n_bins = 0;
+  int up(int nb, const uint32_t* t_max_bits, const uint64_t* hist, const uint64_t* n_zero, const uint64_t* n_over) {
+    n_bins = nb;
+    HIP_TRY(pool.get(&d.t_max_bits, sizeof(uint32_t), t_max_bits));
+    HIP_TRY(pool.get(&d.hist, sizeof(uint64_t) * nb, hist));
+    HIP_TRY(pool.get(&d.n_zero, sizeof(uint64_t), n_zero));
+    HIP_TRY(pool.get(&d.n_over, sizeof(uint64_t), n_over));
+    return D2FE_OK;
+  }
+  int down(uint32_t* t_max_bits, uint64_t* hist, uint64_t* n_zero, uint64_t* n_over) {
+    HIP_TRY(hipMemcpy(t_max_bits, d.t_max_bits, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hist, d.hist, sizeof(uint64_t) * n_bins, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_zero, d.n_zero, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_over, d.n_over, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return D2FE_OK;
+  }
+};
+bool calib_hook_args_ok(float t, int n_bins, int phase) { return calib_bins_ok(n_bins) && (phase == 0 || phase == 1) && t >= 1e-30f && t <= 3e38f; }
+}  // namespace
+
+int d2fe_debug_calib_stats(d2fe_handle h, const float* tensor, long long pixels, int ch_off, int channels, int ch_stride, float t, int n_bins, int phase, int wgs,
+                           uint32_t* t_max_bits, uint64_t* hist, uint64_t* n_zero, uint64_t* n_over) {
+  if (!h || !tensor || !t_max_bits || !hist || !n_zero || !n_over) return fail(D2FE_ERR_INVALID, "null argument");
+  if (!calib_hook_args_ok(t, n_bins, phase) || pixels < 1 || channels < 1 || ch_off < 0 || ch_stride < 1 || ch_off + (long long)channels > ch_stride ||
+      pixels > (1ll << 28) / ch_stride || wgs < 0 || wgs > 4096)
+    return fail(D2FE_ERR_INVALID, "bad calibration hook arguments");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  CalibHookOut o;
+  float* d_x = nullptr;
+  HIP_TRY(o.pool.get(&d_x, sizeof(float) * (size_t)pixels * ch_stride, tensor));
+  { const int rc = o.up(n_bins, t_max_bits, hist, n_zero, n_over); if (rc) return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_calib_stats(d_x, pixels, ch_off, channels, ch_stride, phase == 1, t, (float)n_bins / t, n_bins, o.d, h->ncu, wgs, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return o.down(t_max_bits, hist, n_zero, n_over);
+}
+
+int d2fe_debug_calib_conv1a(d2fe_handle h, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W, const float* w1a,
+                            const float* b1a, float t, int n_bins, int phase, uint32_t* t_max_bits, uint64_t* hist, uint64_t* n_zero, uint64_t* n_over) {
+  if (!h || !frames || !w1a || !b1a || !t_max_bits || !hist || !n_zero || !n_over) return fail(D2FE_ERR_INVALID, "null argument");
+  if (!calib_hook_args_ok(t, n_bins, phase) || n < 1 || n > 64 || H < 1 || W < 1 || H > 4096 || W > 4096 || img_stride < W || img_stride > 65536 || img_istride < 0 ||
+      img_bytes < 1 || img_bytes > 4 * DEBUG_MAX_CONV_FLOATS || img_istride > 4 * DEBUG_MAX_CONV_FLOATS ||
+      (n - 1) * img_istride + (long long)(H - 1) * img_stride + W > img_bytes)
+    return fail(D2FE_ERR_INVALID, "bad calibration hook arguments, or the frames do not fit the frame buffer");
+  HIP_TRY(hipSetDevice(h->cfg.device_id));
+  std::vector<float> w9(9 * 64);
+  for (int co = 0; co < 64; ++co)
+    for (int k = 0; k < 9; ++k) w9[k * 64 + co] = w1a[co * 9 + k];
+  CalibHookOut o;
+  uint8_t* d_img = nullptr;
+  float *d_w = nullptr, *d_b = nullptr;
+  HIP_TRY(o.pool.get(&d_img, (size_t)img_bytes, frames));
+  HIP_TRY(o.pool.get(&d_w, sizeof(float) * w9.size(), w9.data()));
+  HIP_TRY(o.pool.get(&d_b, sizeof(float) * 64, b1a));
+  { const int rc = o.up(n_bins, t_max_bits, hist, n_zero, n_over); if (rc) return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(launch_calib_conv1a_stats(d_img, img_stride, (long)img_istride, H, W, n, d_w, d_b, phase == 1, t, (float)n_bins / t, n_bins, o.d, h->ncu, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return o.down(t_max_bits, hist, n_zero, n_over);
 }
 
 int d2fe_debug_graph_count(d2fe_handle h, int* rejected) {

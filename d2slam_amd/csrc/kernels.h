@@ -96,6 +96,21 @@ hipError_t launch_conv1a(const uint8_t* img, int stride, long img_stride_bytes, 
 hipError_t launch_conv1a_kernel(int valu, const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n,
                                 const float* w9x64, const float* bias, float* out, hipStream_t s);
 
+// int8 calibration statistics (calib.hip; the contract is at d2fe_calib_create in include/d2fe.h).  One tensor's counters on the device: the range phase writes
+// t_max_bits alone, the histogram phase the other three
+struct CalibOut { unsigned int* t_max_bits; unsigned long long* hist /*[n_bins]*/; unsigned long long* n_zero; unsigned long long* n_over; };
+// calib_stats_kernel over the values base[p * ch_stride + ch_off + c], p < pixels, c < channels.  hist_phase false: max |x| bits; true: the binning with T and
+// scale into n_bins bins.  wgs: workgroups, 0 = sized on ncu.  hipErrorInvalidValue: more values than one launch's 32-bit counters cover, a bad n_bins
+hipError_t launch_calib_stats(const float* base, long long pixels, int ch_off, int channels, int ch_stride, bool hist_phase, float T, float scale, int n_bins,
+                              const CalibOut& out, int ncu, int wgs, hipStream_t s);
+// calib_conv1a_stats_kernel: the same statistics over conv1a + ReLU of the u8 frames (arguments as launch_conv1a), the activation never written
+hipError_t launch_calib_conv1a_stats(const uint8_t* img, int stride, long img_stride_bytes, int H, int W, int n, const float* w9x64, const float* bias,
+                                     bool hist_phase, float T, float scale, int n_bins, const CalibOut& out, int ncu, hipStream_t s);
+constexpr int CALIB_BINS_STEP = 128, CALIB_BINS_MAX = 4096, CALIB_BINS_DEFAULT = 2048, CALIB_LEVELS = 128;
+inline bool calib_bins_ok(int n_bins) { return n_bins >= CALIB_BINS_STEP && n_bins <= CALIB_BINS_MAX && n_bins % CALIB_BINS_STEP == 0; }
+// the host rule of d2fe_calib_ranges on one histogram (plain C++, no device): D2FE_OK or D2FE_ERR_INVALID; *index (may be null) as d2fe_debug_calib_ranges_from_hist says
+int calib_range_from_hist(const unsigned long long* hist, int n_bins, float T, int method, double param, float* range, int* index);
+
 // host-side packing helpers (fragment order of the kernels above)
 size_t packed_weight_floats_f32(int cout_pad, int cin, int ks);
 void pack_weights_f32(const float* w /*[cout][cin][k][k]*/, int cout, int cin, int ks, int cout_pad, float* dst);

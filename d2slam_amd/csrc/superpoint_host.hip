@@ -321,6 +321,26 @@ int run_superpoint(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, 
   return D2FE_OK;
 }
 
+int run_superpoint_trunk(d2fe_context* h, const uint8_t* d_gray, int n, int W, int H, int stride, size_t image_stride, hipStream_t s) {
+  const SpNet& net = *h->sp_net;
+  const SpRun& run = h->sp_run;
+  float* act[SP_PA + 1];
+  for (int i = 0; i <= SP_PA; ++i) act[i] = run.act[i];
+  const int Hc = H >> SP_CELL_LEVEL, Wc = W >> SP_CELL_LEVEL;
+  const Pass p{h, D2FE_PREC_F32, false, d_gray, stride, (long)image_stride, n, s};
+  { const int rc = run_chain(p, &net.L[L_1B], SP_4B, H, W, act); if (rc) return rc; }
+  auto head = [&](const Layer& L, const float* in, int ics, int ico, float* out, int ocs, bool relu) {
+    return conv(p, conv_shape(L.cin, L.ks, SP_CELL_LEVEL), L, in, ics, ico, (long)Hc * Wc * ics, out, ocs, (long)Hc * Wc * ocs, Hc, Wc, false, relu);
+  };
+  HIP_TRY(head(net.L[L_PADA], act[SP_4B], 128, 0, act[SP_PA], 512, true));
+  HIP_TRY(head(net.L[L_PB], act[SP_PA], 512, 0, run.logits, 65, false));
+  HIP_TRY(head(net.L[L_DB], act[SP_PA], 512, 256, run.draw, 256, false));
+  h->last_set = 0;
+  h->last_w = W; h->last_h = H; h->last_n = n;
+  h->last_gray = d_gray; h->last_stride = stride; h->last_istride = image_stride;
+  return D2FE_OK;
+}
+
 // floats per descriptor row of every extract call, pipe and list of the handle: pca_dims can only be non-zero where the PCA is applied (variant A, or variant B
 // with d2fe_config.variant_b_pca: d2fe_set_superpoint_pca refuses every other handle)
 int desc_dim_of(const d2fe_context* h) { return h->sp_net->pca_dims ? h->sp_net->pca_dims : 256; }

@@ -135,18 +135,27 @@ def f16_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0):
     return rec
 
 
-def i8_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0, calib_images=64):
+def i8_study(api, imgs, pairs, n_syn, thr, N, batch=32, device_id=0, calib_images=64, calibrators=None):
     """one configuration: the int8-operand mode (PREC_I8) -- and, for scale, the fp16-operand mode -- against the exact mode: keypoint SETS and match sets (compare)
     and list POSITIONS (compare_order).  The ranges are the MinMax ranges of the first `calib_images` images.  Figures to report, not bounds: an 8-bit network on
-    seeded random weights moves far more near-ties than fp16's 11 bits do."""
+    seeded random weights moves far more near-ties than fp16's 11 bits do.
+    calibrators: names among "minmax", "entropy", "percentile" or "percentile:<p>" -- the int8 mode once more per name with the ranges of a calibration session over
+    the same images (calibrate.collect_ranges); the record gains "i8_<name>_vs_f32_*" and "ranges_<name>"."""
     from d2slam_amd import calibrate
     ranges = calibrate.measure_ranges(weights_for(thr), imgs[:calib_images])
     modes = {"f32": (api.PREC_F32, None), "i8": (api.PREC_I8, ranges), "f16": (api.PREC_F16, None)}
+    session = {}
+    for cal in calibrators or ():
+        method, _, p = cal.partition(":")
+        session[cal] = calibrate.collect_ranges(weights_for(thr), imgs[:calib_images], method=method, param=float(p) if p else None, batch=min(batch, 8))
+        modes["i8_" + cal] = (api.PREC_I8, session[cal])
     got = {name: _lists_and_matches(api, imgs, pairs, thr, N, prec, batch, device_id, r) for name, (prec, r) in modes.items()}
     as_sets = lambda g: ([set(a.tolist()) for a in g[0]], g[1])
     NI = len(imgs)
     rec = {"threshold": thr, "max_keypoints": N, "images": NI, "images_per_call": batch, "calibration_images": min(calib_images, NI), "ranges": ranges}
-    for name in ("i8", "f16"):
+    for cal, r in session.items():
+        rec["ranges_" + cal] = r
+    for name in [m for m in modes if m != "f32"]:
         for part, lo, hi in (("all", 0, NI), ("synthetic", 0, n_syn), ("real_derived", n_syn, NI)):
             plo, phi = (0, len(pairs)) if part == "all" else ((0, n_syn // 2) if part == "synthetic" else (n_syn // 2, len(pairs)))
             rec["%s_vs_f32_%s" % (name, part)] = compare(as_sets(got["f32"]), as_sets(got[name]), lo, hi, plo, phi)

@@ -213,8 +213,55 @@ D2FE_API int d2fe_desc_dim(d2fe_handle h);
  * and convDa both read conv4b's; the entries of convPb and convDb are ignored.  Every used entry must be finite and lie in [1e-30, 1e30] (r and s_x are
  * then finite normal fp32), else D2FE_ERR_INVALID naming the layer.  Valid only on a D2FE_PREC_I8 handle (else D2FE_ERR_INVALID), after
  * d2fe_load_superpoint (else D2FE_ERR_NOT_READY); a later d2fe_load_superpoint clears the ranges.  A load: refused while pipes are alive.
- * d2slam_amd/calibrate.py measures the ranges ("MinMax") offline. */
+ * d2slam_amd/calibrate.py measures the ranges ("MinMax") offline; the calibration session below collects them on the device. */
 D2FE_API int d2fe_set_superpoint_int8_ranges(d2fe_handle h, const float* range, int n);
+
+/* Int8 calibration session: the statistics of the twelve tensors above, collected on the device, and the ranges by one of three rules on the host.
+ *
+ * d2fe_calib_create: h must be a D2FE_PREC_F32 handle with dense_descriptors = 1 (else D2FE_ERR_INVALID) and SuperPoint weights loaded (else
+ *   D2FE_ERR_NOT_READY): the statistics are those of the exact network, and convDa / convDb exist densely.  n_bins: 128 .. 4096 in multiples of 128; 0 = 2048,
+ *   the bin count of the published TensorRT calibrator.  The session counts as a user of the handle as a pipe does: d2fe_load_superpoint and the other loads are
+ *   refused while it lives, d2fe_destroy is deferred to d2fe_calib_destroy.  Refused (D2FE_ERR_INVALID) while the handle has live pipes or another session.
+ * d2fe_calib_collect: runs the exact network on n host images of one size (u8, `stride` bytes per row, `image_stride` bytes per image) within the handle's
+ *   max_width x max_height; n may exceed max_batch (the call is sliced).  Behind the network the statistics kernels run on the handle's stream over: the outputs of
+ *   conv1a .. conv4b as the next layer reads them (behind ReLU and, where the layer has one, the pool); convPa and convDa (ReLU outputs, the two channel halves of one
+ *   buffer); convPb (the 65 logits) and convDb (the raw 256-channel map before normalisation) by absolute value.  No keypoints, no device-to-host copy, one host
+ *   synchronisation, at the end.  Not re-entrant per handle, like the extract calls; do not interleave it with extract calls of other threads.
+ * Range phase (before d2fe_calib_freeze): per tensor the running t_max = max |x| (kept as the fp32 bits of |x| under an integer max) and n_total.  NaN activations
+ *   are outside the contract, as for D2FE_PREC_I8.
+ * d2fe_calib_freeze: reads the maxima back and fixes per tensor T = max(t_max, 1e-30f) and scale = (float)n_bins / T (one fp32 divide); zeroes the histograms;
+ *   n_total restarts.  D2FE_ERR_NOT_READY with no image collected, D2FE_ERR_INVALID a second time.
+ * Histogram phase (d2fe_calib_collect after the freeze): for every value a = |x|, exactly
+ *     a == 0 (either sign)  -> n_zero += 1                 (a zero quantises to 0 under any range: it is no part of the distribution)
+ *     a >  T                -> n_over += 1, hist[n_bins - 1] += 1
+ *     else                  -> hist[min(n_bins - 1, (int)(a * scale))] += 1      (one fp32 multiply, round to nearest even, then truncation)
+ *   All counters are 64-bit integers: the statistics of a set of images do not depend on how it is split into calls or batches.  Images first seen in this
+ *   phase are legal; values above T are what n_over counts.
+ * d2fe_calib_stats_get: layer in 0 .. D2FE_SP_NUM_LAYERS - 1; every output may be NULL.  t_max: the running maximum (range phase) or the frozen one; hist (n_bins
+ *   counters; D2FE_ERR_NOT_READY before the freeze), n_zero and n_over (0 before the freeze), n_total of the current phase.
+ * d2fe_calib_ranges: range[D2FE_SP_NUM_LAYERS], every entry clamped to [1e-30, 1e30] (acceptable to d2fe_set_superpoint_int8_ranges).  Host code in double
+ *   precision, plain sequential loops.  With N = the sum of hist (zeros excluded):
+ *   D2FE_CALIB_MINMAX      T (param ignored); answerable in the range phase too.
+ *   D2FE_CALIB_PERCENTILE  param in (0, 100] (else D2FE_ERR_INVALID): target = (uint64)ceil((double)N * (param / 100.0)); b = the first bin whose cumulative count
+ *                          reaches target; range = (float)((double)(b + 1) * (double)T / n_bins).  N = 0: T.
+ *   D2FE_CALIB_ENTROPY     (param ignored) the published KL-divergence calibration (NVIDIA, "8-bit inference with TensorRT"; ORT's Entropy method and MXNet follow
+ *                          it), one-sided (the quantised inputs are ReLU outputs), 128 levels.  For every candidate i in 128 .. n_bins: P = hist[0 .. i) with the sum
+ *                          of hist[i ..) added to P[i - 1]; level j covers the bins floor(j * i / 128) .. floor((j + 1) * i / 128) - 1; Q[b] = (the sum of the RAW hist
+ *                          over b's level) / (the number of bins of the level with P[b] != 0) where P[b] != 0, else 0; p = P / sum(P), q = Q / sum(Q) (sums over b
+ *                          ascending); KL(i) = the sum over b ascending with P[b] > 0 of p_b * ln(p_b / q_b).  A candidate with some p_b > 0, q_b = 0 is skipped (the
+ *                          last level's raw counts all zero while outliers were folded in); no smoothing.  The smallest KL wins, among exact ties the smallest i;
+ *                          range = (float)((double)i * (double)T / n_bins).  N = 0: T.  i = n_bins is always a valid candidate.
+ *   The histogram phase is required for the last two (D2FE_ERR_NOT_READY before the freeze).
+ * Limit: the entropy rule is this header's own statement of the published algorithm, not pinned to onnxruntime's bits (ORT's default of 128 histogram bins is
+ * n_bins = 128); calibration table files of ORT or TensorRT are neither read nor written. */
+typedef struct d2fe_calib_s* d2fe_calib;
+typedef enum { D2FE_CALIB_MINMAX = 0, D2FE_CALIB_ENTROPY = 1, D2FE_CALIB_PERCENTILE = 2 } d2fe_calib_method;
+D2FE_API int d2fe_calib_create(d2fe_handle h, int n_bins, d2fe_calib* out);
+D2FE_API int d2fe_calib_collect(d2fe_calib c, const uint8_t* gray, int width, int height, int stride, long long image_stride, int n);
+D2FE_API int d2fe_calib_freeze(d2fe_calib c);
+D2FE_API int d2fe_calib_stats_get(d2fe_calib c, int layer, float* t_max, uint64_t* hist, uint64_t* n_zero, uint64_t* n_over, uint64_t* n_total);
+D2FE_API int d2fe_calib_ranges(d2fe_calib c, int method, double param, float* range);
+D2FE_API void d2fe_calib_destroy(d2fe_calib c);
 
 /* Extractor.  Replaces: bool SuperPoint::infer(const cv::Mat&, std::vector<cv::Point2f>&, std::vector<float>&
  * descriptors, std::vector<float>& scores) (superpoint_tensorrt.h:47-48, .cpp:161-183), called from

@@ -92,6 +92,7 @@ struct SuperPointConfig {
   bool exact_order = false;              // winograd only, max_keypoints >= 1: the keypoint list (count, indices, order) equals the exact mode's (d2fe_config::exact_order)
   float exact_order_eps = 0.f;           // 0: the library default
   int32_t exact_order_crops = 0;         // crop slots per call; 0: max_batch
+  bool dense_descriptors = false;        // d2fe_config::dense_descriptors: convDa / convDb on every cell (same descriptors); what an Int8Calibrator needs of its handle
   bool descriptor_pca = false;           // d2fe_config::variant_b_pca: setDescriptorPCA is accepted and infer() returns pca_dims floats per keypoint (params->enable_pca_superpoint)
 };
 
@@ -114,6 +115,7 @@ class SuperPoint {
     c.precision = cfg_.int8_operands ? (int32_t)D2FE_PREC_I8 : cfg_.fp16_operands ? D2FE_PREC_F16 : cfg_.fast_mode ? D2FE_PREC_F16X2 : (cfg_.winograd ? D2FE_PREC_F32_WINO : D2FE_PREC_F32);
     c.exact_order = cfg_.exact_order ? 1 : 0; c.exact_order_eps = cfg_.exact_order_eps; c.exact_order_crops = cfg_.exact_order_crops;
     c.variant_b_pca = cfg_.descriptor_pca ? 1 : 0;
+    c.dense_descriptors = cfg_.dense_descriptors ? 1 : 0;
     if (d2fe_create(&c, &h_) != D2FE_OK) { report("d2fe_create"); h_ = nullptr; return false; }
     if (d2fe_load_superpoint(h_, &w) != D2FE_OK) { report("d2fe_load_superpoint"); return false; }
     return true;
@@ -176,6 +178,46 @@ class SuperPoint {
   SuperPointConfig cfg_;
   d2fe_handle h_ = nullptr;
   std::vector<float> kp_, sc_, de_;
+};
+
+// An int8 calibration session (d2fe_calib_* of d2fe.h) on the handle of a SuperPoint built in the exact precision (none of fast_mode, winograd, fp16_operands,
+// int8_operands) with dense_descriptors: collect() the calibration frames, freeze(), collect() them again, then ranges() gives what setInt8Ranges of the
+// int8_operands SuperPoint takes.  The reference calibrates with the entropy rule (quadcam_tools/quantonnx.py:66-67,84-85).  Destroy it before the SuperPoint
+class Int8Calibrator {
+ public:
+  explicit Int8Calibrator(const SuperPoint& sp, int n_bins = 0) : n_bins_(n_bins ? n_bins : 2048) {
+    if (d2fe_calib_create(sp.handle(), n_bins, &c_) != D2FE_OK) { report("d2fe_calib_create"); c_ = nullptr; }
+  }
+  ~Int8Calibrator() { if (c_) d2fe_calib_destroy(c_); }
+  Int8Calibrator(const Int8Calibrator&) = delete;
+  Int8Calibrator& operator=(const Int8Calibrator&) = delete;
+  bool ok() const { return c_ != nullptr; }
+  // n images of one size, `image_stride` bytes apart (n = 1: ignored); before freeze() the range phase, behind it the histogram phase
+  bool collect(const ImageView& first, int n = 1, long long image_stride = 0) {
+    const long long is = image_stride ? image_stride : (long long)first.step * first.rows;
+    if (!c_ || first.channels != 1 || d2fe_calib_collect(c_, first.data, first.cols, first.rows, (int)first.step, is, n) != D2FE_OK) { report("d2fe_calib_collect"); return false; }
+    return true;
+  }
+  bool freeze() {
+    if (!c_ || d2fe_calib_freeze(c_) != D2FE_OK) { report("d2fe_calib_freeze"); return false; }
+    return true;
+  }
+  // method: D2FE_CALIB_MINMAX (also before freeze()), D2FE_CALIB_ENTROPY, D2FE_CALIB_PERCENTILE with param in (0, 100]
+  bool ranges(d2fe_calib_method method, float (&range)[D2FE_SP_NUM_LAYERS], double param = 99.99) {
+    if (!c_ || d2fe_calib_ranges(c_, (int)method, param, range) != D2FE_OK) { report("d2fe_calib_ranges"); return false; }
+    return true;
+  }
+  // the statistics of one layer's output tensor (d2fe_calib_stats_get); hist (may be null): the session's n_bins counters, behind freeze() only
+  bool stats(int layer, float& t_max, uint64_t& n_zero, uint64_t& n_over, uint64_t& n_total, std::vector<uint64_t>* hist = nullptr) {
+    if (hist) hist->assign((size_t)n_bins_, 0);
+    if (!c_ || d2fe_calib_stats_get(c_, layer, &t_max, hist ? hist->data() : nullptr, &n_zero, &n_over, &n_total) != D2FE_OK) { report("d2fe_calib_stats_get"); return false; }
+    return true;
+  }
+
+ private:
+  static void report(const char* what) { std::fprintf(stderr, "[d2fe] %s: %s\n", what, d2fe_last_error()); }
+  d2fe_calib c_ = nullptr;
+  int n_bins_;
 };
 
 // MobileNetVLADONNX (mobilenetvlad_onnx.h:18-74) on an existing handle: colour conversion / resize / PCA as in inference()

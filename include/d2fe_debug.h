@@ -145,6 +145,23 @@ D2FE_API int d2fe_debug_conv_layer_q(d2fe_handle h, const d2fe_debug_conv* p, co
 D2FE_API int d2fe_debug_conv1a(d2fe_handle h, int kernel, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,
                                const float* w1a, const float* b1a, float* out, long long out_floats);
 
+/* The int8 calibration session's parts (csrc/calib.hip; the contract is at d2fe_calib_create in d2fe.h) on injected data, for tests/test_calib_cpu.py and
+ * tests/test_calib_edges.py.
+ *   calib_ranges_from_hist: the host rule of d2fe_calib_ranges on one histogram; needs no GPU.  hist [n_bins]; t = the tensor's T; method and param as there.
+ *                 -> *range, and *index (may be NULL): ENTROPY the winning candidate i, PERCENTILE b + 1, MINMAX and N = 0 n_bins.
+ *   calib_stats:  calib_stats_kernel on a host tensor of pixels * ch_stride floats: channel c of pixel p at p * ch_stride + ch_off + c, c < channels.  phase 0:
+ *                 the range phase, *t_max_bits = max(*t_max_bits, bits of max |x|).  phase 1: the histogram phase with T = t and scale = (float)n_bins / t.  Every output is
+ *                 in-out: uploaded first, downloaded behind the launch, so that a second call accumulates into the first one's counts.  wgs: the launch's
+ *                 workgroups, 0 = the launcher's own choice.  Refused: null pointers, t outside [1e-30, 3e38], a bad n_bins, ch_off + channels > ch_stride, more than
+ *                 2^28 floats.
+ *   calib_conv1a: calib_conv1a_stats_kernel on injected frames and weights (frames, w1a, b1a as for d2fe_debug_conv1a); outputs as for calib_stats. */
+D2FE_API int d2fe_debug_calib_ranges_from_hist(const uint64_t* hist, int n_bins, float t, int method, double param, float* range, int* index);
+D2FE_API int d2fe_debug_calib_stats(d2fe_handle h, const float* tensor, long long pixels, int ch_off, int channels, int ch_stride, float t, int n_bins, int phase,
+                                    int wgs, uint32_t* t_max_bits, uint64_t* hist, uint64_t* n_zero, uint64_t* n_over);
+D2FE_API int d2fe_debug_calib_conv1a(d2fe_handle h, const uint8_t* frames, int img_stride, long long img_istride, long long img_bytes, int n, int H, int W,
+                                     const float* w1a, const float* b1a, float t, int n_bins, int phase, uint32_t* t_max_bits, uint64_t* hist, uint64_t* n_zero,
+                                     uint64_t* n_over);
+
 /* Host-pointer calls replay cached hipGraphs of their launch sequences from the third call with the same geometry on (D2FE_GRAPH=0 in the
  * environment turns that off).  Returns how many graphs the handle holds; *rejected (may be NULL) = geometries whose capture failed and which
  * therefore keep launching kernel by kernel (diagnostic). */
